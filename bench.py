@@ -16,11 +16,17 @@ own streams, no collective on the data path).
 `python bench.py --gpus N` starts the N ranks itself (one process per GPU under torch.distributed.run, RCCL);
 under an external launcher (WORLD_SIZE set) it is one of the ranks.
 
-Also reported in the same JSON line (1 GPU): the roofline of the only kernel that moves compulsory HBM bytes
-(kstrongest_rows, hipEvent timings from inside the timed region), the same for dense-row scenes
+Also reported in the same JSON line: the roofline of the only kernel that moves compulsory HBM bytes
+(kstrongest_rows, hipEvent timings from inside the timed region).  A plain run stops there: set up, warm up, time
+the steps, print the line.  With --full the line also holds (1 GPU) the same roofline for dense-row scenes
 (roofline_dense + the full-path rate on them), the per-kernel breakdown, one stream alone (single_stream: the
 literal configs[1] latency case), host-resident input (host_input: pinned images, H2D inside the timed region),
-the loop-closure candidate workload (loopclosure), and the CPU oracle timed on the host beside it.
+the loop-closure candidate workload (loopclosure), and the CPU oracle timed on the host beside it; at every N the
+sharded loop-closure / verification section.
+
+--dump-outputs DIR writes what the timed path returned for its last step (the per-frame records of the streams, one
+.npy per field; a fixed sample of the streams where all would pass 60 MB) so that two builds can be compared output
+for output: the input is the same on every run.
 """
 import argparse
 import json
@@ -125,9 +131,9 @@ class Dist:
             torch.cuda.set_device(self.local_rank)              # rank i <-> GPU i
         self.dev = torch.device("cpu") if self.dry else torch.device("cuda", self.local_rank)
         self.dist = None
-        # the sharded workloads bring the process group up at ONE rank too, so that the driver's N = 1 run executes the
-        # same collective (a 1-rank RCCL all_gather) as N = 8
-        if self.world > 1 or not self.dry:
+        # the sharded workloads (--full, --workload loopclosure / verify) bring the process group up at ONE rank too, so that
+        # the N = 1 run executes the same collective (a 1-rank RCCL all_gather) as N = 8; a plain odometry run needs none
+        if self.world > 1 or not (self.dry or (args.workload == "odometry" and not args.full)):
             import torch.distributed as dist
             os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
             if self.world == 1:
@@ -178,14 +184,20 @@ class Dist:
 # input: rings of sweeps along closed circles, rendered on the GPU
 # ---------------------------------------------------------------------------------------------------------
 def make_rings(n_seq, ring, seed0, dev, dense=False):
-    """uint8 [n_seq][ring][ROWS][COLS] on the GPU + the Scene objects."""
+    """uint8 [n_seq][ring][ROWS][COLS] on the GPU + the Scene objects.  The same bytes on every run: the renderer's
+    index_add_ of the returns runs in torch's deterministic mode (atomics would round a pixel differently now and then)."""
     import torch
     from tbv_slam_public_amd import synth
     rings = torch.empty((n_seq, ring, ROWS, COLS), dtype=torch.uint8, device=dev)
     kw = dict(synth.DENSE_KW) if dense else {}
-    for s in range(n_seq):
-        sc = synth.Scene(seed0 + s, circle_frames=ring, cols=COLS, **kw)
-        rings[s] = synth.render_frames_torch(sc, list(range(ring)), dev)
+    was_deterministic = torch.are_deterministic_algorithms_enabled()
+    torch.use_deterministic_algorithms(True)
+    try:
+        for s in range(n_seq):
+            sc = synth.Scene(seed0 + s, circle_frames=ring, cols=COLS, **kw)
+            rings[s] = synth.render_frames_torch(sc, list(range(ring)), dev)
+    finally:
+        torch.use_deterministic_algorithms(was_deterministic)
     torch.cuda.synchronize()
     return rings
 
@@ -205,9 +217,10 @@ class StreamSet:
         return (self.seq * self.F + (self.start + t) % self.F) * IMG
 
 
-def run_odometry(od, rings, ss, n_frames, t0=0, record=None):
+def run_odometry(od, rings, ss, n_frames, t0=0, record=None, infos=None):
     """Advances every stream by n_frames frames (frame t0 .. t0 + n_frames - 1 of its ring walk); the filter of frame
-    t + 1 is prefetched behind frame t.  record: (array [n_frames, n, 3], n) receives the poses of streams 0 .. n-1."""
+    t + 1 is prefetched behind frame t.  record: (array [n_frames, n, 3], n) receives the poses of streams 0 .. n-1;
+    infos (a list) receives every frame's FRAMEINFO records."""
     stats = {"points": 0.0, "cells": 0.0, "bad": 0, "frames": 0}
     for t in range(t0, t0 + n_frames):
         info = od.process_offsets(rings, ss.offsets(t), ss.offsets(t + 1))
@@ -217,7 +230,31 @@ def run_odometry(od, rings, ss, n_frames, t0=0, record=None):
         stats["frames"] += 1
         if record is not None:
             record[0][t - t0] = info["pose"][:record[1]]
+        if infos is not None:
+            infos.append(info)
     return stats
+
+
+DUMP_BYTES = 60 * 10 ** 6            # --dump-outputs stays under 64 MB (the .npy headers included)
+
+
+def dump_outputs(dirname, infos):
+    """--dump-outputs: the FRAMEINFO records the timed path returned for the frames of its last step, one float64 array
+    per field ([frame][stream]; pose [frame][stream][3]).  Where all streams would exceed DUMP_BYTES, a fixed sample of
+    them (seed 0, in stream order) is written, and its stream numbers as stream_index.npy."""
+    rec = np.stack(infos)
+    per_stream = 8 * rec.shape[0] * sum(int(np.prod(rec.dtype[f].shape)) for f in rec.dtype.names)
+    os.makedirs(dirname, exist_ok=True)
+    index_path = os.path.join(dirname, "stream_index.npy")
+    if rec.shape[1] * per_stream > DUMP_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(rec.shape[1], max(1, DUMP_BYTES // (per_stream + 8)), replace=False))
+        rec = rec[:, keep]
+        np.save(index_path, keep.astype(np.float64))
+    elif os.path.exists(index_path):
+        os.remove(index_path)
+    for f in rec.dtype.names:
+        np.save(os.path.join(dirname, f + ".npy"), np.ascontiguousarray(rec[f], dtype=np.float64))
+    return {"dir": dirname, "frames": rec.shape[0], "streams": rec.shape[1], "fields": list(rec.dtype.names)}
 
 
 def roofline_of(prof, n_scans_per_launch, mean_points):
@@ -674,7 +711,18 @@ def main(argv=None):
                     help="A/B runs: a context option of include/cfear_hip.h (enum cfear_option without the CFEAR_OPT_ prefix, e.g. "
                          "FUSED_DECODE=0, MATCHER_LDS_KB=52) applied to every context this run creates")
     ap.add_argument("--dry-run", action="store_true", help="launcher test without GPUs: ranks rendezvous over gloo and exit")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the per-kernel breakdown pass, the sharded loop-closure / "
+                         "verification section, the extra passes (dense scenes, single stream, host input, other configs, loop "
+                         "closure) and the CPU baseline with its pose comparison; --no-extras / --no-cpu-baseline / --no-sharded "
+                         "/ --no-profile leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="odometry: write what the timed path returned for its last step to DIR/<field>.npy (float64)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "odometry":
+        ap.error("--dump-outputs: the odometry workload only")
     COLS, IMG = int(args.cols), ROWS * int(args.cols)
     maybe_self_launch(args, argv)
     D = Dist(args)
@@ -735,18 +783,20 @@ def main(argv=None):
             sys.stderr.write("bench.py: --bins-major/--keep-nodes walk %d gathered frames forth and back (the motion reverses "
                              "at both ends)\n" % G)
 
-        def advance(n, t_first, record=None):
+        def advance(n, t_first, record=None, infos=None):
             st = {"points": 0.0, "cells": 0.0, "bad": 0, "frames": 0}
             for t in range(t_first, t_first + n):
                 info = od.process(cache[pingpong(t, G)], cache[pingpong(t + 1, G)])
                 st["points"] += float(info["n_points"].mean()); st["cells"] += float(info["n_cells"].mean())
                 st["bad"] += int((info["reg_status"] != 0).sum()); st["frames"] += 1
+                if infos is not None:
+                    infos.append(info)
             return st
     else:
         od = new_fuser(B, estimate_cov_by_sampling=int(args.cov_sampling))
 
-        def advance(n, t_first, record=None):
-            return run_odometry(od, rings, ss, n, t_first, record)
+        def advance(n, t_first, record=None, infos=None):
+            return run_odometry(od, rings, ss, n, t_first, record, infos)
 
     poses = np.zeros(((W + K) * FPS, n_cmp, 3))
     for w in range(W):
@@ -758,19 +808,22 @@ def main(argv=None):
     ctx.profile_read(reset=True)
     t1 = time.perf_counter()
     tot = {"points": 0.0, "cells": 0.0, "bad": 0, "frames": 0}
+    last_step = [] if args.dump_outputs else None
     for s in range(K):
         # The filter of the next frame is enqueued behind each frame's kernels (it needs no state of that frame): the
         # sweep of the first timed frame ran during warm-up and the sweep of the frame after the last one runs inside
         # the timed region, so exactly K * frames_per_step filter sweeps (and as many of every other kernel) are timed.
-        st = advance(FPS, (W + s) * FPS, (poses[(W + s) * FPS:], n_cmp))
+        st = advance(FPS, (W + s) * FPS, (poses[(W + s) * FPS:], n_cmp), last_step if s == K - 1 else None)
         for k_ in tot:
             tot[k_] += st[k_]
     D.barrier()
     elapsed_local = time.perf_counter() - t1
     prof = ctx.profile_read(reset=True)
     ctx.profile_enable(False)
+    if last_step is not None and D.rank == 0:
+        note("outputs of the last step: %s" % dump_outputs(args.dump_outputs, last_step))
     prof_all, n_all = {}, 0
-    if not args.no_profile:                          # untimed: the same frames again with every kernel bracketed
+    if args.full and not args.no_profile:            # untimed: the same frames again with every kernel bracketed
         ctx.profile_enable(1)
         st_all = advance(FPS, (W + K) * FPS)
         D.barrier()
@@ -781,7 +834,7 @@ def main(argv=None):
     bad_total = sum(D.gather(tot["bad"]))
     # ---- the workloads that SHARD, on every rank, whatever N (the odometry above is replicas only) -------------------
     sharded, lc_world = {}, None
-    if not (args.no_sharded or args.no_extras) and D.dist is not None:
+    if args.full and not (args.no_sharded or args.no_extras) and D.dist is not None:
         note("sharded: loop closure + verification over %d rank(s)" % D.world)
         try:
             lc_world = _on_side_stream(D, lambda: LoopClosureWorld(D))
@@ -841,15 +894,16 @@ def main(argv=None):
         "per_rank_value": per_rank,
         "roofline": roof,
         "roofline_whole_path": whole_path_of(nf, tot["cells"] / max(tot["frames"], 1), 4, value / D.world),
-        "kernel_breakdown": breakdown,
-        "kernel_breakdown_note": "hipEvents around every kernel in an extra pass of %d frames AFTER the timed region; inside it only "
-                                 "the polar sweep is bracketed (roofline.avg_launch_ms)" % n_all,
         "mean_cells_per_scan": tot["cells"] / max(tot["frames"], 1),
         "failed_registrations": int(bad_total),
         "input_generation_s": t_gen,
     }
+    if args.full:
+        out["kernel_breakdown"] = breakdown
+        out["kernel_breakdown_note"] = ("hipEvents around every kernel in an extra pass of %d frames AFTER the timed region; inside "
+                                        "it only the polar sweep is bracketed (roofline.avg_launch_ms)" % n_all)
     out.update(sharded)
-    if D.world > 1:
+    if D.world > 1 or not args.full:
         return emit(D, out)
 
     # =====================================================================================================

@@ -6,23 +6,137 @@ nanoflann.hpp + KDTreeVectorOfVectorsAdaptor.h behind oracle/ref_nanoflann_shim.
 (ii) FLANN-lineage single kd-tree with L2_Simple on float 2-D points -- what PCL's KdTreeFLANN<PointXY> runs for
      MapPointNormal's radius search (pointnormal.cpp:291) and GetClosestIdx (:238-254) -- against the oracle's restatement
      (SURVEY App. B.2 / B.3): strict `<` radius rule, float accumulation x then y, sorted result order, 1-NN incl. ties.
+
+Where oracle/_ref is not built (it needs the reference's sources), the reference trees' answers recorded from it stand in:
+tests/golden/ref_nanoflann.npz holds every call's result in call order, per test, with a checksum of the inputs the test
+hands the trees.  Where the library is there, its answers are checked against that recording as well.  Re-record (only
+with the library built, after a deliberate change of what a test asks the trees):
+    CFEAR_RECORD_REF_NANOFLANN=1 python -m pytest tests/test_ref_nanoflann.py
 """
 import ctypes as C
 import os
 import subprocess
+import zlib
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SO = os.path.join(ROOT, "oracle", "_ref", "libref_nanoflann.so")
+GOLDEN = os.path.join(ROOT, "tests", "golden", "ref_nanoflann.npz")
+RECORD = os.environ.get("CFEAR_RECORD_REF_NANOFLANN") == "1"
+
+# the calls a test makes on the reference trees; the float 2-D trees' distances are not stored but recomputed from the
+# returned indices on replay (L2_Simple in float, x then y: bit for bit what the library returns, checked when recording)
+_KEY_BUILD, _KEY_KNN, _XY_BUILD, _XY_RADIUS, _XY_KNN = range(5)
+_D2_RECOMPUTED = (_XY_RADIUS, _XY_KNN)
+_TAPE = None            # the running test's _Tape (set by the _reference_tape fixture)
+_RECORDED = {}          # record mode: arrays for GOLDEN
+
+
+def _bytes(*parts):
+    return b"".join(np.ascontiguousarray(p).tobytes() + np.asarray(np.shape(p), np.int64).tobytes() for p in parts)
+
+
+class _Tape:
+    """One test's calls on the reference trees, in order: recorded from the library, replayed without it, or compared
+    with the library's answers."""
+
+    def __init__(self, name):
+        self.name, self.mode, self.crc, self.calls = name, None, 0, []
+
+    def _load(self):
+        if not os.path.exists(GOLDEN):
+            raise FileNotFoundError("%s is missing and oracle/_ref is not built" % GOLDEN)
+        g, p = np.load(GOLDEN), self.name + "."
+        if p + "kind" not in g.files:
+            raise KeyError("%s holds no recording of %s" % (GOLDEN, self.name))
+        self.kind, self.ret, self.len = g[p + "kind"], g[p + "ret"], g[p + "len"]
+        self.idx, self.d2, self.expect_crc = g[p + "idx"].astype(np.int64), g[p + "d2"], int(g[p + "crc"])
+        self.i = self.io = self.do = 0
+
+    def step(self, kind, data, got, d2_of):
+        if self.mode is None:
+            self.mode = "record" if RECORD else ("replay" if got is None else "check")
+            if self.mode == "record" and got is None:
+                raise RuntimeError("CFEAR_RECORD_REF_NANOFLANN=1 needs oracle/_ref/libref_nanoflann.so (make -C oracle _ref)")
+            if self.mode != "record":
+                self._load()
+        self.crc = zlib.crc32(data, self.crc)
+        if self.mode == "record":
+            ret, idx, d2 = got
+            if kind in _D2_RECOMPUTED:
+                assert np.array_equal(d2_of(idx), d2), "%s: the tree's distances are not L2_Simple in float" % self.name
+            self.calls.append((kind, ret, idx, None if kind in _D2_RECOMPUTED else d2))
+            return got
+        i = self.i
+        assert i < len(self.kind) and self.kind[i] == kind, \
+            "%s: call %d on the reference trees is not the recorded one (re-record %s)" % (self.name, i, GOLDEN)
+        n = int(self.len[i])
+        idx = self.idx[self.io:self.io + n]
+        self.io += n
+        if kind in _D2_RECOMPUTED:
+            d2 = d2_of(idx)
+        else:
+            d2 = self.d2[self.do:self.do + n]
+            self.do += n
+        self.i += 1
+        exp = (int(self.ret[i]), idx, d2)
+        if got is None:
+            return exp
+        assert got[0] == exp[0] and np.array_equal(got[1], exp[1]) and np.array_equal(got[2], exp[2]), \
+            "%s: call %d: the library's answer differs from %s" % (self.name, i, GOLDEN)
+        return got
+
+    def finish(self):
+        if self.mode == "record":
+            p = self.name + "."
+            idx = np.concatenate([c[2] for c in self.calls]) if self.calls else np.zeros(0, np.int64)
+            _RECORDED[p + "kind"] = np.array([c[0] for c in self.calls], np.int8)
+            _RECORDED[p + "ret"] = np.array([c[1] for c in self.calls], np.int32)
+            _RECORDED[p + "len"] = np.array([len(c[2]) for c in self.calls], np.int32)
+            _RECORDED[p + "idx"] = idx.astype(np.uint16 if idx.size == 0 or idx.max() < 1 << 16 else np.uint32)
+            _RECORDED[p + "d2"] = np.concatenate([np.zeros(0, np.float32)] + [c[3] for c in self.calls if c[3] is not None])
+            _RECORDED[p + "crc"] = np.uint32(self.crc)
+        elif self.mode is not None:
+            assert self.i == len(self.kind), "%s: %d of %d recorded calls made" % (self.name, self.i, len(self.kind))
+            assert self.crc == self.expect_crc, "%s: the inputs differ from the recorded ones (re-record %s)" % (self.name, GOLDEN)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _write_recording():
+    yield
+    if RECORD and _RECORDED:
+        arrays = dict(np.load(GOLDEN)) if os.path.exists(GOLDEN) else {}
+        arrays.update(_RECORDED)
+        np.savez_compressed(GOLDEN, **arrays)
+
+
+@pytest.fixture(autouse=True)
+def _reference_tape(request):
+    global _TAPE
+    _TAPE = _Tape(request.node.name)
+    yield
+    tape, _TAPE = _TAPE, None
+    tape.finish()
+
+
+class _RefLib:
+    """The reference's nanoflann behind oracle/ref_nanoflann_shim.cpp (lib), or None: the recorded answers."""
+
+    def __init__(self, lib):
+        self.lib = lib
+
+    def call(self, kind, data, live, d2_of=None):
+        got = live() if self.lib is not None else None
+        return got if _TAPE is None else _TAPE.step(kind, data, got, d2_of)
 
 
 def _ref():
     if not os.path.exists(SO) and os.path.isdir("/root/reference/place_recognition_radar"):
         subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "_ref"])
     if not os.path.exists(SO):
-        pytest.skip("oracle/_ref/libref_nanoflann.so not built and /root/reference absent")
+        return _RefLib(None)
     L = C.CDLL(SO)
     L.ref_keytree_build.restype = C.c_void_p
     L.ref_keytree_build.argtypes = [C.c_void_p, C.c_int64, C.c_int32]
@@ -36,51 +150,79 @@ def _ref():
     L.ref_tree2f_radius.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
     L.ref_tree2f_knn.restype = C.c_int64
     L.ref_tree2f_knn.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    return L
+    return _RefLib(L)
+
+
+_BUILT = (0, np.zeros(0, np.int64), np.zeros(0, np.float32))
 
 
 class RefKeyTree:
     def __init__(self, L, keys):
-        self.L = L
+        self.L, self.h = L, None
         k = np.ascontiguousarray(keys, np.float32)
-        self.h = L.ref_keytree_build(k.ctypes.data, k.shape[0], k.shape[1])
-        assert self.h
+
+        def build():
+            self.h = L.lib.ref_keytree_build(k.ctypes.data, k.shape[0], k.shape[1])
+            assert self.h
+            return _BUILT
+        L.call(_KEY_BUILD, _bytes(k), build)
 
     def knn(self, q, k):
         q = np.ascontiguousarray(q, np.float32)
-        idx = np.zeros(k, np.uint64)
-        d2 = np.zeros(k, np.float32)
-        n = self.L.ref_keytree_knn(self.h, q.ctypes.data, k, idx.ctypes.data, d2.ctypes.data)
-        return int(n), idx.astype(np.int64), d2
+
+        def live():
+            idx = np.zeros(k, np.uint64)
+            d2 = np.zeros(k, np.float32)
+            n = self.L.lib.ref_keytree_knn(self.h, q.ctypes.data, k, idx.ctypes.data, d2.ctypes.data)
+            return int(n), idx.astype(np.int64), d2
+        return self.L.call(_KEY_KNN, _bytes(q, np.int64(k)), live)
 
     def __del__(self):
-        self.L.ref_keytree_free(self.h)
+        if self.h:
+            self.L.lib.ref_keytree_free(self.h)
 
 
 class RefTree2f:
     def __init__(self, L, xy, leaf=15):          # pcl::KdTreeFLANN builds KDTreeSingleIndexParams(15)
-        self.L = L
+        self.L, self.h = L, None
         p = np.ascontiguousarray(xy, np.float32)
-        self.n = p.shape[0]
-        self.h = L.ref_tree2f_build(p.ctypes.data, p.shape[0], leaf)
-        assert self.h
+        self.n, self.pts = p.shape[0], p
+
+        def build():
+            self.h = L.lib.ref_tree2f_build(p.ctypes.data, p.shape[0], leaf)
+            assert self.h
+            return _BUILT
+        L.call(_XY_BUILD, _bytes(p, np.int64(leaf)), build)
+
+    def _d2(self, q):
+        return lambda idx: _l2_simple(q, self.pts[idx])
 
     def radius(self, q, r2, sorted_=True):
         q = np.ascontiguousarray(q, np.float32)
-        idx = np.zeros(self.n, np.uint64)
-        d2 = np.zeros(self.n, np.float32)
-        n = self.L.ref_tree2f_radius(self.h, q.ctypes.data, np.float32(r2), int(sorted_), self.n, idx.ctypes.data, d2.ctypes.data)
-        return idx[:n].astype(np.int64), d2[:n]
+
+        def live():
+            idx = np.zeros(self.n, np.uint64)
+            d2 = np.zeros(self.n, np.float32)
+            n = self.L.lib.ref_tree2f_radius(self.h, q.ctypes.data, np.float32(r2), int(sorted_), self.n, idx.ctypes.data,
+                                             d2.ctypes.data)
+            return int(n), idx[:n].astype(np.int64), d2[:n]
+        _, idx, d2 = self.L.call(_XY_RADIUS, _bytes(q, np.float32(r2), np.int64(sorted_)), live, self._d2(q))
+        return idx, d2
 
     def knn(self, q, k=1):
         q = np.ascontiguousarray(q, np.float32)
-        idx = np.zeros(k, np.uint64)
-        d2 = np.zeros(k, np.float32)
-        n = self.L.ref_tree2f_knn(self.h, q.ctypes.data, k, idx.ctypes.data, d2.ctypes.data)
-        return idx[:n].astype(np.int64), d2[:n]
+
+        def live():
+            idx = np.zeros(k, np.uint64)
+            d2 = np.zeros(k, np.float32)
+            n = self.L.lib.ref_tree2f_knn(self.h, q.ctypes.data, k, idx.ctypes.data, d2.ctypes.data)
+            return int(n), idx[:n].astype(np.int64), d2[:n]
+        _, idx, d2 = self.L.call(_XY_KNN, _bytes(q, np.int64(k)), live, self._d2(q))
+        return idx, d2
 
     def __del__(self):
-        self.L.ref_tree2f_free(self.h)
+        if self.h:
+            self.L.lib.ref_tree2f_free(self.h)
 
 
 # ---------------------------------------------------------------------------------------------------------------

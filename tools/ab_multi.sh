@@ -6,7 +6,7 @@
 L=tbv_slam_public_amd
 cp $L/libcfear_hip.so /tmp/cur.so
 run() {
-  python bench.py --no-cpu-baseline --no-extras ${BENCH_ARGS:---steps 8} 2>&1 | tail -1 | python -c "
+  python bench.py --full --no-cpu-baseline --no-extras ${BENCH_ARGS:---steps 8} 2>&1 | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('%-14s' % '$1', 'value', round(d['value']), 'ms/batch', round(d['ms_per_frame_batch'],4), {k: round(v['ms_per_frame_batch'],4) for k,v in d['kernel_breakdown'].items() if v['ms_per_frame_batch'] > 0.02})"

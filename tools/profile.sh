@@ -24,17 +24,17 @@ keep = [rows[0]] + [r for r in rows[1:] if any(k in r[0] for k in ours)] if rows
 csv.writer(open(sys.argv[2], "w")).writerows(keep)
 PY
 }
-# 1. kernel trace + stats of the default bench command (headline launches + the extra passes)
-( cd /tmp && rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/bench" -o bench -- python "$ROOT/bench.py" --no-cpu-baseline --no-extras > "$SUM/bench_stdout.json" 2> "$OUT/bench.err" )
+# 1. kernel trace + stats of the bench command with --full (headline launches + the extra passes)
+( cd "$OUT" && rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/bench" -o bench -- python "$ROOT/bench.py" --full --no-cpu-baseline --no-extras > "$SUM/bench_stdout.json" 2> "$OUT/bench.err" )
 keep_ours "$OUT/bench" "$SUM/bench_kernel_stats.csv"; rm -rf "$OUT/bench"
-( cd /tmp && rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/dense" -o d -- python "$ROOT/bench.py" --no-cpu-baseline --no-extras --dense --streams 1024 --sequences 64 --steps 4 --frames-per-step 8 > "$SUM/bench_dense_stdout.json" 2> "$OUT/dense.err" )
+( cd "$OUT" && rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/dense" -o d -- python "$ROOT/bench.py" --full --no-cpu-baseline --no-extras --dense --streams 1024 --sequences 64 --steps 4 --frames-per-step 8 > "$SUM/bench_dense_stdout.json" 2> "$OUT/dense.err" )
 keep_ours "$OUT/dense" "$SUM/bench_dense_kernel_stats.csv"; rm -rf "$OUT/dense"
 # 1b. the neighbouring workloads
 ( cd /tmp && rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/verify" -o v -- python "$ROOT/bench.py" --workload verify --steps 5 --warmup 2 > "$SUM/verify_stdout.json" 2> "$OUT/verify.err" )
 keep_ours "$OUT/verify" "$SUM/verify_kernel_stats.csv"; rm -rf "$OUT/verify"
 ( cd /tmp && rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/lc" -o v -- python "$ROOT/bench.py" --workload loopclosure --steps 20 --warmup 3 > "$SUM/loopclosure_stdout.json" 2> "$OUT/lc.err" )
 keep_ours "$OUT/lc" "$SUM/loopclosure_kernel_stats.csv"; rm -rf "$OUT/lc"
-( cd /tmp && rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/binsmajor" -o b -- python "$ROOT/bench.py" --no-cpu-baseline --no-extras --bins-major --steps 3 --frames-per-step 8 > "$SUM/bins_major_stdout.json" 2> "$OUT/binsmajor.err" )
+( cd "$OUT" && rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/binsmajor" -o b -- python "$ROOT/bench.py" --full --no-cpu-baseline --no-extras --bins-major --steps 3 --frames-per-step 8 > "$SUM/bins_major_stdout.json" 2> "$OUT/binsmajor.err" )
 keep_ours "$OUT/binsmajor" "$SUM/bins_major_kernel_stats.csv"; rm -rf "$OUT/binsmajor"
 # 1c. [bins][azimuths] sweeps: the fused decode (kstrong_image), its fall-backs and the two-kernel route on 2048 images
 for MODE in fused two-pass tile lists; do

@@ -7,7 +7,7 @@ S=gpurun_out/profiles_$TAG
 python -m pytest tests -m gpu -q 2>&1 | tail -4 > gpurun_out/gpu_tests_$TAG.txt
 bash tools/profile.sh $TAG > gpurun_out/profile_sh_$TAG.log 2>&1
 mv gpurun_out/gpu_tests_$TAG.txt $S/gpu_tests.txt
-python bench.py > $S/bench_default_stdout.json 2> $S/bench_default_stderr.txt
+python bench.py --full > $S/bench_default_stdout.json 2> $S/bench_default_stderr.txt
 STREAMS=4096 bash tools/prof_quick.sh > /dev/null 2>&1; cp gpurun_out/pc/pmc_summary.txt $S/pmc_pipe_per_kernel.txt; rm -rf gpurun_out/pc
 bash tools/reg_quick.sh > $S/matcher_phase_split.txt 2>&1
 STREAMS=1 bash tools/reg_quick.sh > $S/matcher_phase_split_single_stream.txt 2>&1

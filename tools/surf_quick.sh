@@ -1,7 +1,7 @@
 #!/bin/bash
 # quick look at the surface kernels: bench kernel breakdown with the release build, then the phase split of
 # surface_sort_kernel with the -DCFEAR_SURF_TIMING build (the timing build is NOT kept: the release .so is restored)
-python bench.py --no-cpu-baseline --no-extras ${BENCH_ARGS:-} 2>&1 | tail -1 | python -c "
+python bench.py --full --no-cpu-baseline --no-extras ${BENCH_ARGS:-} 2>&1 | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('value', round(d['value']), 'ms/batch', round(d['ms_per_frame_batch'],4), {k: round(v['ms_per_frame_batch'],4) for k,v in d['kernel_breakdown'].items()}, 'frac', round(d['roofline']['frac'],3))"
