@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -23,6 +24,26 @@ struct ProfRow {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
 
+// Workspace slots (cfear_ctx::ws).  Stages that are live at the same time use different slots; a slot with several users is
+// never live in two of them at once (each user is done with it before it returns).
+enum WsSlot : int {
+  kWsImages = 0,          // staged polar images: filter host entry points; the rotated images of cfear_filter_row_keys
+  kWsFilter = 1,          // filter host entry points: staged outputs and scratch
+  kWsTrig = 2,            // cos / sin tables of the k-strongest cloud (cfear_ctx::trig_rows)
+  kWsFilterRows = 3,      // k-strongest per-row counts; CA-CFAR detection bits and counts
+  kWsSurface = 4,         // surface / scan host entry points: staged clouds, cells, queries, job records
+  kWsSurfaceScratch = 5,  // cfear_scan_create's surface scratch
+  kWsRegJobs = 6,         // matcher job records and results
+  kWsRegScratch = 7,      // matcher scratch; also verify's registrations
+  kWsClouds = 8,          // staged peak clouds: coral, verify, scan-context descriptors; scan-context distance buffers
+  kWsCoral = 9,           // coral job records, results and per-point terms; scan-context descriptor buffers
+  kWsCoralScratch = 10,   // coral scratch; also shard's allgather staging (never live at the same time)
+  kWsSurfaceList = 11,    // the surface pipeline's fallback work list
+  kWsKstrongCand = 12,    // fused k-strongest candidate lists
+  kWsCandResults = 13,    // cfear_register_candidates: results for a host caller
+  kWsVerify = 14,         // the verification chain's records and results
+};
+
 struct cfear_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -31,7 +52,7 @@ struct cfear_ctx {
   int profile = 0;            // 0 off, 1 every kernel family, 2 the polar filter's row kernels only (the HBM-bound launch)
   std::vector<ProfRow> prof;
   std::vector<hipEvent_t> event_pool;
-  // grow-only device workspaces (indexed by purpose so stages of one pipeline do not alias)
+  // grow-only device workspaces (indexed by WsSlot so stages of one pipeline do not alias)
   struct Ws { void* p = nullptr; size_t bytes = 0; };
   Ws ws[16];
   // pinned host staging for small read-backs
@@ -43,7 +64,7 @@ struct cfear_ctx {
   struct Slab { void* p; int cap; };
   std::vector<Slab> free_slabs;
   int64_t live_scans = 0;
-  int trig_rows = 0;       // rows the cos/sin tables in ws[2] were built for
+  int trig_rows = 0;       // rows the cos/sin tables in ws[kWsTrig] were built for
   int n_cu = 256;          // compute units of the device (cfear_ctx_create)
   int64_t opt[CFEAR_OPT_COUNT] = {1, 0, 0, 0};   // cfear_ctx_set_option (test / measurement hooks; include/cfear_hip.h)
   bool surf_list_dirty = true;   // the surface pipeline's hand-over counter may be non-zero (see cfear_surface_launch)
@@ -51,6 +72,12 @@ struct cfear_ctx {
 };
 
 int cfear_set_error(cfear_ctx* ctx, int status, const char* fmt, ...);
+
+#define CFEAR_CHECK(expr)                                                                       \
+  do {                                                                                          \
+    const int _rc = (expr);                                                                     \
+    if (_rc != CFEAR_OK) return _rc;                                                            \
+  } while (0)
 
 #define CFEAR_HIP_CHECK(ctx, expr)                                                              \
   do {                                                                                          \
@@ -63,12 +90,83 @@ int cfear_set_error(cfear_ctx* ctx, int status, const char* fmt, ...);
 // true if p is device (or managed) memory visible to kernels without a copy
 bool cfear_is_device_ptr(const void* p);
 // grow-only workspace `slot` of at least `bytes`; returns nullptr on allocation failure
-void* cfear_workspace(cfear_ctx* ctx, int slot, size_t bytes);
+void* cfear_workspace(cfear_ctx* ctx, WsSlot slot, size_t bytes);
 // Pinned staging of at least `bytes`.  A caller that leaves an asynchronous copy from it in flight (results kept on the
 // device: no synchronisation before it returns) calls cfear_pinned_mark() behind the copy; cfear_pinned() then waits for
 // that copy before it hands the buffer out again.
+// Everything else that crosses from or into the caller's memory goes through HostStage: no copy from or into caller memory
+// outlives the C-ABI call that enqueued it, on the error paths as well.
 void* cfear_pinned(cfear_ctx* ctx, size_t bytes);
 void cfear_pinned_mark(cfear_ctx* ctx);
+
+// One C-ABI call's boundary with the caller's memory.  The call first plans what it needs -- in() / out() / piece() bind a
+// pointer to the device address it resolves to, images() and cloud_in() stage polar images and peak clouds in their own
+// slots -- then carve() allocates every piece with one cfear_workspace call (256-byte aligned) and enqueues the uploads.
+// Device memory of the caller is used in place.  finish() enqueues the copy-backs and synchronises, but only if the call
+// touched host memory: an all-device call stays asynchronous.  The destructor, and finish() when it fails, drain the stream
+// if a copy was enqueued, so host memory (the caller's, record(), or locals declared before the stage) outlives every copy.
+class HostStage {
+ public:
+  HostStage(cfear_ctx* ctx, WsSlot slot) : ctx_(ctx), slot_(slot) {}
+  ~HostStage() { drain(); }
+  HostStage(const HostStage&) = delete;
+  HostStage& operator=(const HostStage&) = delete;
+
+  // true if p is host memory; in() / out() / images() ask this of the caller's pointers, mixed() compares the answers
+  bool is_host(const void* p);
+  bool mixed() const { return host_ && device_; }
+  bool any_host() const { return host_; }
+  // in: p itself, or a piece that carve() uploads p's bytes to (and that finish() copies back when `back`); p may be null
+  // when bytes is 0.  Returns true if p is staged.
+  template <class T> bool in(T*& dev, T* p, size_t bytes, bool back = false) {
+    if (!p || !bytes || !is_host(p)) { dev = p; return false; }
+    plan(&dev, bind<T*>, bytes, p, back ? (void*)p : nullptr);
+    return true;
+  }
+  // out: p itself, or a piece that finish() copies back to p.  A null p gets a piece that is not copied back.
+  template <class T> bool out(T*& dev, T* p, size_t bytes) {
+    if (p && !is_host(p)) { dev = p; return false; }
+    plan(&dev, bind<T*>, bytes, nullptr, p);
+    return p != nullptr;
+  }
+  template <class T> void piece(T*& dev, size_t bytes) { plan(&dev, bind<T*>, bytes, nullptr, nullptr); }
+  // a batch of polar images (batch_stride between images when batch > 1): host images are staged densely in kWsImages
+  cfear_polar_desc images(const uint8_t*& dev, const uint8_t* p, const cfear_polar_desc& desc);
+  // peak clouds ([n] float4): one query per distinct pointer, host clouds staged once each in kWsClouds, at the longest n
+  // any use names.  After carve(), cloud(p) is the device address of p (p itself if it was not staged).
+  void cloud_in(const float* p, int n);
+  const float4* cloud(const float* p) const;
+
+  int carve();
+  // a host record the call builds and uploads after carve(); owned by the stage, so it outlives the upload
+  void* record(size_t bytes) { record_.assign(bytes, 0); return record_.data(); }
+  int upload(void* dev, const void* host, size_t bytes);
+  // a copy-back finish() enqueues (pitched when rows > 1)
+  void back(void* host, const void* dev, size_t width, size_t rows = 1, size_t host_pitch = 0, size_t dev_pitch = 0) {
+    backs_.push_back({host, dev, width, rows, host_pitch, dev_pitch});
+  }
+  int finish();
+
+ private:
+  template <class P> static void bind(void* where, char* addr) { *(P*)where = (P)addr; }
+  void plan(void* where, void (*set)(void*, char*), size_t bytes, const void* up, void* down);
+  void drain();
+
+  struct Piece { void* where; void (*set)(void*, char*); size_t off, bytes; const void* up; void* down; };
+  struct Back { void* host; const void* dev; size_t width, rows, host_pitch, dev_pitch; };
+  struct Images { const uint8_t** where = nullptr; const uint8_t* p = nullptr; size_t img_bytes = 0; int64_t stride = 0; int batch = 0; };
+  struct Cloud { bool host; int n; size_t off; };
+  cfear_ctx* ctx_;
+  WsSlot slot_;
+  size_t bytes_ = 0, cloud_bytes_ = 0;
+  std::vector<Piece> pieces_;
+  std::vector<Back> backs_;
+  Images images_;
+  std::map<const float*, Cloud> clouds_;
+  char* cloud_base_ = nullptr;
+  std::vector<char> record_;
+  bool host_ = false, device_ = false, sync_ = false, pending_ = false;
+};
 // hipFuncAttributeMaxDynamicSharedMemorySize, once per (context, kernel, size): the attribute is per device and contexts are
 // per device, so a launch path asks every time and pays a linear look-up over a dozen entries instead of a runtime call
 int cfear_allow_lds(cfear_ctx* ctx, const void* kernel, size_t bytes);
@@ -214,14 +312,15 @@ struct RegCostMode {
 // What the caller knows about the batch's registrations (the kernel decides per registration from the device-side sizes):
 // cfear_coral_quality_batch in two halves (coral.hip): launch, then read back -- host work of the caller in between
 struct CoralPending {
-  std::vector<char> host_jobs;        // the uploaded job records (pageable: must outlive the copy)
+  explicit CoralPending(cfear_ctx* ctx) : stage(ctx, kWsCoral) {}
+  HostStage stage;                    // the staged clouds and job records; drained unless cfear_coral_collect completes
   void* d_res = nullptr;
   void* d_pp = nullptr;
   int n_jobs = 0, cap = 0;
 };
 int cfear_coral_enqueue(cfear_ctx* ctx, const cfear_coral_job* jobs, int32_t n_jobs, const cfear_coral_params* par, bool want_per_point,
                         CoralPending& pend);
-int cfear_coral_collect(cfear_ctx* ctx, const cfear_coral_job* jobs, const CoralPending& pend, cfear_coral_result* results, double* per_point);
+int cfear_coral_collect(cfear_ctx* ctx, const cfear_coral_job* jobs, CoralPending& pend, cfear_coral_result* results, double* per_point);
 
 // One registration of the matcher (matcher.hip).  The scan views come LAST so that a batch whose jobs use at most m scans can be
 // stored with the shorter stride reg_job_stride(m): a two-scan loop-closure candidate is 0.5 KB instead of 1.9 KB to build and

@@ -22,7 +22,6 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
-#include <map>
 #include <vector>
 
 #include "common.hpp"
@@ -607,7 +606,7 @@ int cfear_coral_launch_device(cfear_ctx* ctx, const CoralJob* d_jobs, int n_jobs
   cm.scratch_stride = coral_scratch_bytes(cm.cap);
   cm.per_point = nullptr;
   const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_jobs, ((size_t)1 << 30) / cm.scratch_stride));
-  char* scr = (char*)cfear_workspace(ctx, 10, cm.scratch_stride * (size_t)chunk);
+  char* scr = (char*)cfear_workspace(ctx, kWsCoralScratch, cm.scratch_stride * (size_t)chunk);
   if (!scr) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
   cm.scratch = scr;
   { const int rc_lds = cfear_allow_lds(ctx, (const void*)coral_kernel, 160 * 1024); if (rc_lds != CFEAR_OK) return rc_lds; }
@@ -630,33 +629,16 @@ extern "C" void cfear_coral_params_default(cfear_coral_params* p) {
 
 // The batch in two halves, so that a caller with host work of its own (verify.hip) can do it while the kernel runs:
 // cfear_coral_enqueue stages the clouds, uploads the jobs and launches; cfear_coral_collect reads the results back and
-// synchronises.  `pend` carries what must outlive the launch.
-static int coral_enqueue_impl(cfear_ctx* ctx, const cfear_coral_job* jobs, int32_t n_jobs, const cfear_coral_params* par, bool want_per_point,
-                              CoralPending& pend);
-
-// The enqueue half may leave asynchronous copies FROM pageable host memory in flight (pend.host_jobs, the caller's peak
-// clouds): when it fails behind the first of them the stream is drained before the error returns, so that whoever destroys
-// `pend` or the clouds next does not pull them from under a copy (collect() is the only other place that waits).
+// synchronises.  `pend` carries what must outlive the launch; its stage drains the stream if collect() does not complete.
 int cfear_coral_enqueue(cfear_ctx* ctx, const cfear_coral_job* jobs, int32_t n_jobs, const cfear_coral_params* par, bool want_per_point,
                         CoralPending& pend) {
-  const int rc = coral_enqueue_impl(ctx, jobs, n_jobs, par, want_per_point, pend);
-  if (rc != CFEAR_OK) (void)hipStreamSynchronize(ctx->stream);
-  return rc;
-}
-
-static int coral_enqueue_impl(cfear_ctx* ctx, const cfear_coral_job* jobs, int32_t n_jobs, const cfear_coral_params* par, bool want_per_point,
-                              CoralPending& pend) {
   pend.n_jobs = 0;
   if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
   if (!jobs || !par || n_jobs < 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
   if (!(par->radius > 0.0)) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "radius must be > 0");
   if (n_jobs == 0) return CFEAR_OK;
-  const bool per_point = want_per_point;
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  // stage host clouds once each (perturbation sets and candidate lists share clouds)
-  std::map<const float*, size_t> staged;                 // host pointer -> offset (floats) in the staging buffer
-  std::map<const float*, bool> on_device;                // one hipPointerGetAttributes per distinct cloud, not per job
-  size_t stage_floats = 0;
+  HostStage& st = pend.stage;                            // host clouds staged once each (perturbation sets and candidate lists share clouds)
   int cap = 1;
   for (int j = 0; j < n_jobs; j++) {
     const cfear_coral_job& jb = jobs[j];
@@ -665,43 +647,8 @@ static int coral_enqueue_impl(cfear_ctx* ctx, const cfear_coral_job* jobs, int32
     if ((long long)jb.n_ref + jb.n_src > kCoralMaxPoints)
       return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "job %d: %d + %d points exceed %d", j, jb.n_ref, jb.n_src, kCoralMaxPoints);
     cap = std::max(cap, jb.n_ref + jb.n_src);
-    const float* ptrs[2] = {jb.ref_xyzi, jb.src_xyzi};
-    const int ns[2] = {jb.n_ref, jb.n_src};
-    for (int c = 0; c < 2; c++) {
-      if (ns[c] == 0 || !ptrs[c]) continue;
-      auto it = on_device.find(ptrs[c]);
-      if (it != on_device.end()) continue;
-      const bool dev = cfear_is_device_ptr(ptrs[c]);
-      on_device[ptrs[c]] = dev;
-      if (!dev) {
-        staged[ptrs[c]] = stage_floats;
-        stage_floats += ((size_t)ns[c] * 4 + 3) & ~(size_t)3;
-      }
-    }
-  }
-  float* d_stage = nullptr;
-  if (stage_floats) {
-    d_stage = (float*)cfear_workspace(ctx, 8, stage_floats * 4);
-    if (!d_stage) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-    std::map<const float*, int> len;
-    for (int j = 0; j < n_jobs; j++) {
-      len[jobs[j].ref_xyzi] = std::max(len[jobs[j].ref_xyzi], jobs[j].n_ref);
-      len[jobs[j].src_xyzi] = std::max(len[jobs[j].src_xyzi], jobs[j].n_src);
-    }
-    for (auto& kv : staged)
-      if (len[kv.first] > 0)
-        CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(d_stage + kv.second, kv.first, (size_t)len[kv.first] * 16, hipMemcpyHostToDevice, ctx->stream));
-  }
-  pend.host_jobs.resize((size_t)n_jobs * sizeof(CoralJob));
-  CoralJob* hj = (CoralJob*)pend.host_jobs.data();
-  for (int j = 0; j < n_jobs; j++) {
-    const cfear_coral_job& jb = jobs[j];
-    CoralJob& o = hj[j];
-    o.ref = (const float4*)(staged.count(jb.ref_xyzi) ? d_stage + staged[jb.ref_xyzi] : jb.ref_xyzi);
-    o.src = (const float4*)(staged.count(jb.src_xyzi) ? d_stage + staged[jb.src_xyzi] : jb.src_xyzi);
-    o.n_ref_ptr = o.n_src_ptr = nullptr;
-    o.n_ref = jb.n_ref; o.n_src = jb.n_src;
-    for (int k = 0; k < 3; k++) { o.ref_pose[k] = jb.ref_pose[k]; o.src_pose[k] = jb.src_pose[k]; o.offset[k] = jb.offset[k]; }
+    st.cloud_in(jb.ref_xyzi, jb.n_ref);
+    st.cloud_in(jb.src_xyzi, jb.n_src);
   }
   CoralCommon cm;
   cm.radius = par->radius;
@@ -713,16 +660,28 @@ static int coral_enqueue_impl(cfear_ctx* ctx, const cfear_coral_job* jobs, int32
   cm.scratch_stride = coral_scratch_bytes(cap);
   // scratch bounded to 1 GiB per launch
   const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_jobs, ((size_t)1 << 30) / cm.scratch_stride));
-  const size_t jb_bytes = (size_t)n_jobs * sizeof(CoralJob), rb = (size_t)n_jobs * sizeof(cfear_coral_result);
-  const size_t pp_bytes = per_point ? (size_t)n_jobs * cap * 3 * sizeof(double) : 0;
-  char* ws = (char*)cfear_workspace(ctx, 9, (jb_bytes + 255) / 256 * 256 + (rb + 255) / 256 * 256 + pp_bytes + 512);
-  char* scr = (char*)cfear_workspace(ctx, 10, cm.scratch_stride * (size_t)chunk);
-  if (!ws || !scr) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-  CoralJob* d_jobs = (CoralJob*)ws;
-  cfear_coral_result* d_res = (cfear_coral_result*)(ws + (jb_bytes + 255) / 256 * 256);
-  double* d_pp = per_point ? (double*)((char*)d_res + (rb + 255) / 256 * 256) : nullptr;
+  const size_t jb_bytes = (size_t)n_jobs * sizeof(CoralJob);
+  CoralJob* d_jobs;
+  cfear_coral_result* d_res;
+  double* d_pp = nullptr;
+  st.piece(d_jobs, jb_bytes);
+  st.piece(d_res, (size_t)n_jobs * sizeof(cfear_coral_result));
+  if (want_per_point) st.piece(d_pp, (size_t)n_jobs * cap * 3 * sizeof(double));
+  char* scr = (char*)cfear_workspace(ctx, kWsCoralScratch, cm.scratch_stride * (size_t)chunk);
+  if (!scr) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
+  CFEAR_CHECK(st.carve());
+  CoralJob* hj = (CoralJob*)st.record(jb_bytes);
+  for (int j = 0; j < n_jobs; j++) {
+    const cfear_coral_job& jb = jobs[j];
+    CoralJob& o = hj[j];
+    o.ref = st.cloud(jb.ref_xyzi);
+    o.src = st.cloud(jb.src_xyzi);
+    o.n_ref_ptr = o.n_src_ptr = nullptr;
+    o.n_ref = jb.n_ref; o.n_src = jb.n_src;
+    for (int k = 0; k < 3; k++) { o.ref_pose[k] = jb.ref_pose[k]; o.src_pose[k] = jb.src_pose[k]; o.offset[k] = jb.offset[k]; }
+  }
   cm.scratch = scr;
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(d_jobs, hj, jb_bytes, hipMemcpyHostToDevice, ctx->stream));
+  CFEAR_CHECK(st.upload(d_jobs, hj, jb_bytes));
   { const int rc_lds = cfear_allow_lds(ctx, (const void*)coral_kernel, 160 * 1024); if (rc_lds != CFEAR_OK) return rc_lds; }
   {
     ProfScope ps(ctx, "coral_quality");
@@ -738,20 +697,16 @@ static int coral_enqueue_impl(cfear_ctx* ctx, const cfear_coral_job* jobs, int32
   return CFEAR_OK;
 }
 
-int cfear_coral_collect(cfear_ctx* ctx, const cfear_coral_job* jobs, const CoralPending& pend, cfear_coral_result* results, double* per_point) {
+int cfear_coral_collect(cfear_ctx* ctx, const cfear_coral_job* jobs, CoralPending& pend, cfear_coral_result* results, double* per_point) {
   const int n_jobs = pend.n_jobs, cap = pend.cap;
   if (n_jobs == 0) return CFEAR_OK;
-  const size_t rb = (size_t)n_jobs * sizeof(cfear_coral_result);
-  const size_t pp_bytes = per_point ? (size_t)n_jobs * cap * 3 * sizeof(double) : 0;
-  const cfear_coral_result* d_res = (const cfear_coral_result*)pend.d_res;
-  const double* d_pp = (const double*)pend.d_pp;
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(results, d_res, rb, hipMemcpyDeviceToHost, ctx->stream));
+  pend.stage.back(results, pend.d_res, (size_t)n_jobs * sizeof(cfear_coral_result));
   std::vector<double> hpp;
   if (per_point) {
     hpp.resize((size_t)n_jobs * cap * 3);
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(hpp.data(), d_pp, pp_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    pend.stage.back(hpp.data(), pend.d_pp, hpp.size() * sizeof(double));
   }
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  CFEAR_CHECK(pend.stage.finish());                    // (drains on failure: hpp outlives every copy into it)
   if (per_point) {                                       // compact [job][n_src + n_ref][3]
     size_t o = 0;
     for (int j = 0; j < n_jobs; j++) {
@@ -770,7 +725,7 @@ extern "C" int cfear_coral_quality_batch(cfear_ctx* ctx, const cfear_coral_job* 
                                          const cfear_coral_params* par, cfear_coral_result* results, double* per_point) {
   if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
   if (!results) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
-  CoralPending pend;
+  CoralPending pend(ctx);
   const int rc = cfear_coral_enqueue(ctx, jobs, n_jobs, par, per_point != nullptr, pend);
   if (rc != CFEAR_OK) return rc;
   return cfear_coral_collect(ctx, jobs, pend, results, per_point);

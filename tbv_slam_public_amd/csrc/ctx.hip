@@ -1,4 +1,5 @@
 // ctx.hip -- context, error reporting, profiling, workspaces and scan slabs of libcfear_hip.so.
+#include <algorithm>
 #include <cstdarg>
 
 #include "common.hpp"
@@ -24,7 +25,7 @@ bool cfear_is_device_ptr(const void* p) {
   return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
 }
 
-void* cfear_workspace(cfear_ctx* ctx, int slot, size_t bytes) {
+void* cfear_workspace(cfear_ctx* ctx, WsSlot slot, size_t bytes) {
   cfear_ctx::Ws& w = ctx->ws[slot];
   if (w.bytes >= bytes && w.p) return w.p;
   if (w.p) {
@@ -41,6 +42,94 @@ void* cfear_workspace(cfear_ctx* ctx, int slot, size_t bytes) {
   }
   w.bytes = want;
   return w.p;
+}
+
+bool HostStage::is_host(const void* p) {
+  const bool host = !cfear_is_device_ptr(p);
+  (host ? host_ : device_) = true;
+  return host;
+}
+
+void HostStage::plan(void* where, void (*set)(void*, char*), size_t bytes, const void* up, void* down) {
+  pieces_.push_back({where, set, bytes_, bytes, up, down});
+  bytes_ += (bytes + 255) / 256 * 256;
+}
+
+cfear_polar_desc HostStage::images(const uint8_t*& dev, const uint8_t* p, const cfear_polar_desc& desc) {
+  dev = p;
+  if (!is_host(p)) return desc;
+  images_.where = &dev;
+  images_.p = p;
+  images_.img_bytes = (size_t)desc.rows * desc.stride;
+  images_.stride = desc.batch > 1 ? desc.batch_stride : (int64_t)images_.img_bytes;
+  images_.batch = desc.batch;
+  cfear_polar_desc dense = desc;
+  dense.batch_stride = (int64_t)images_.img_bytes;
+  return dense;
+}
+
+void HostStage::cloud_in(const float* p, int n) {
+  if (!p || n <= 0) return;
+  auto it = clouds_.find(p);
+  if (it == clouds_.end()) clouds_.emplace(p, Cloud{is_host(p), n, 0});
+  else it->second.n = std::max(it->second.n, n);
+}
+
+const float4* HostStage::cloud(const float* p) const {
+  auto it = clouds_.find(p);
+  return it != clouds_.end() && it->second.host ? (const float4*)(cloud_base_ + it->second.off) : (const float4*)p;
+}
+
+int HostStage::carve() {
+  for (auto& kv : clouds_)
+    if (kv.second.host) { kv.second.off = cloud_bytes_; cloud_bytes_ += (size_t)kv.second.n * 16; }
+  char* base = bytes_ ? (char*)cfear_workspace(ctx_, slot_, bytes_) : nullptr;
+  char* img = images_.where ? (char*)cfear_workspace(ctx_, kWsImages, images_.img_bytes * images_.batch) : nullptr;
+  cloud_base_ = cloud_bytes_ ? (char*)cfear_workspace(ctx_, kWsClouds, cloud_bytes_) : nullptr;
+  if ((bytes_ && !base) || (images_.where && !img) || (cloud_bytes_ && !cloud_base_))
+    return cfear_set_error(ctx_, CFEAR_ERR_HIP, "workspace allocation failed");
+  int rc = CFEAR_OK;
+  for (const Piece& pc : pieces_) {
+    pc.set(pc.where, base + pc.off);
+    if (pc.up && rc == CFEAR_OK) rc = upload(base + pc.off, pc.up, pc.bytes);
+    if (pc.down) back(pc.down, base + pc.off, pc.bytes);
+  }
+  if (images_.where) {
+    *images_.where = (const uint8_t*)img;
+    for (int b = 0; b < images_.batch && rc == CFEAR_OK; b++)
+      rc = upload(img + (size_t)b * images_.img_bytes, images_.p + (size_t)b * images_.stride, images_.img_bytes);
+  }
+  for (const auto& kv : clouds_)
+    if (kv.second.host && rc == CFEAR_OK) rc = upload(cloud_base_ + kv.second.off, kv.first, (size_t)kv.second.n * 16);
+  return rc;
+}
+
+int HostStage::upload(void* dev, const void* host, size_t bytes) {
+  sync_ = pending_ = true;
+  CFEAR_HIP_CHECK(ctx_, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, ctx_->stream));
+  return CFEAR_OK;
+}
+
+int HostStage::finish() {
+  hipError_t e = hipSuccess;
+  for (const Back& b : backs_) {
+    if (e != hipSuccess) break;
+    pending_ = true;
+    e = b.rows > 1 ? hipMemcpy2DAsync(b.host, b.host_pitch, b.dev, b.dev_pitch, b.width, b.rows, hipMemcpyDeviceToHost, ctx_->stream)
+                   : hipMemcpyAsync(b.host, b.dev, b.width, hipMemcpyDeviceToHost, ctx_->stream);
+  }
+  if (e == hipSuccess && (host_ || sync_ || !backs_.empty())) e = hipStreamSynchronize(ctx_->stream);
+  if (e != hipSuccess) {
+    drain();
+    return cfear_set_error(ctx_, CFEAR_ERR_HIP, "staging copy failed: %s", hipGetErrorString(e));
+  }
+  pending_ = false;
+  return CFEAR_OK;
+}
+
+void HostStage::drain() {
+  if (pending_) (void)hipStreamSynchronize(ctx_->stream);
+  pending_ = false;
 }
 
 void cfear_pinned_mark(cfear_ctx* ctx) {

@@ -1899,7 +1899,7 @@ int cfear_trig_tables(cfear_ctx* ctx, int rows, double** d_cos, double** d_sin) 
     h[bearing] = std::cos(theta);
     h[rows + bearing] = std::sin(theta);
   }
-  double* d = (double*)cfear_workspace(ctx, 2, h.size() * sizeof(double));
+  double* d = (double*)cfear_workspace(ctx, kWsTrig, h.size() * sizeof(double));
   if (!d) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
   CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));   // h goes out of scope
@@ -1964,7 +1964,7 @@ int cfear_kstrong_device(cfear_ctx* ctx, const uint8_t* d_polar, const cfear_pol
   if (fused && fused->row_valid) {
     a.row_valid = fused->row_valid;
   } else if (want_cloud) {
-    a.row_valid = (int32_t*)cfear_workspace(ctx, 3, (size_t)desc->batch * desc->rows * 8);
+    a.row_valid = (int32_t*)cfear_workspace(ctx, kWsFilterRows, (size_t)desc->batch * desc->rows * 8);
     if (!a.row_valid) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
   }
   const bool vec = (((uintptr_t)d_polar) % 4 == 0) && (a.stride % 4 == 0) && (a.batch_stride % 4 == 0);
@@ -2061,7 +2061,7 @@ int cfear_kstrong_cols_device(cfear_ctx* ctx, const uint8_t* d_src, const cfear_
   const int n_cu = ctx->n_cu;
   if (fused->cand_stats) CFEAR_HIP_CHECK(ctx, hipMemsetAsync(fused->cand_stats, 0, 64 * 4, ctx->stream));
   if (!all_tiles) {
-    char* ws = (char*)cfear_workspace(ctx, 12, o_cand + n_rows * kCandCap * 4);
+    char* ws = (char*)cfear_workspace(ctx, kWsKstrongCand, o_cand + n_rows * kCandCap * 4);
     if (!ws) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
     int32_t* cand_cnt = (int32_t*)ws;
     uint32_t* tile_flag = (uint32_t*)(ws + o_flag);
@@ -2154,7 +2154,7 @@ extern "C" int cfear_filter_kstrongest_rowkeys(cfear_ctx* ctx, const uint8_t* po
   cfear_polar_desc rd{};                                      // the rotated images: rows = azimuths
   rd.rows = desc->cols; rd.cols = desc->rows; rd.stride = (desc->rows + 15) & ~15; rd.batch = desc->batch;
   rd.batch_stride = (int64_t)rd.rows * rd.stride;
-  uint8_t* rot = (uint8_t*)cfear_workspace(ctx, 0, (size_t)rd.batch_stride * rd.batch);
+  uint8_t* rot = (uint8_t*)cfear_workspace(ctx, kWsImages, (size_t)rd.batch_stride * rd.batch);
   if (!rot) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
   const int rc = cfear_rotate_ccw_device(ctx, polar, desc, rot, rd.stride, rd.batch_stride);
   if (rc != CFEAR_OK) return rc;
@@ -2165,8 +2165,7 @@ extern "C" int cfear_filter_kstrongest(cfear_ctx* ctx, const uint8_t* polar, con
                                        const cfear_kstrong_params* par, const cfear_kstrong_out* out) {
   if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
   if (!polar || !par || !out) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
-  int rc = check_desc(ctx, desc);
-  if (rc != CFEAR_OK) return rc;
+  CFEAR_CHECK(check_desc(ctx, desc));
   if (par->k_strongest < 1 || par->k_strongest > kMaxK)
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "k_strongest must be in [1,%d]", kMaxK);
   if (!(par->range_res > 0.f))
@@ -2174,69 +2173,22 @@ extern "C" int cfear_filter_kstrongest(cfear_ctx* ctx, const uint8_t* polar, con
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const int rows = desc->rows, k = par->k_strongest, batch = desc->batch;
   const size_t nsel = (size_t)batch * rows * k;
-  const bool dev = cfear_is_device_ptr(polar);
-  const bool want_cloud = out->xyzi || out->n_points;
   const bool want_pk = par->want_peaks && (out->is_peak || out->xyzi_peaks || out->n_peaks);
-  // device buffers: caller's (device mode) or workspace
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-  const bool need_ws_sel = !dev || !out->sel_range || !out->sel_intensity || !out->sel_count || (want_pk && !out->is_peak);
-  size_t o_sr = 0, o_si = 0, o_sc = 0, o_pk = 0, o_xyz = 0, o_np = 0, o_xyzp = 0, o_npp = 0;
-  if (need_ws_sel || !dev) {
-    o_sr = carve(nsel * 4); o_si = carve(nsel); o_sc = carve((size_t)batch * rows * 4); o_pk = carve(nsel);
-  }
-  if (!dev) {
-    o_xyz = carve(nsel * 16); o_np = carve((size_t)batch * 4);
-    o_xyzp = carve(nsel * 16); o_npp = carve((size_t)batch * 4);
-  }
-  char* ws = off ? (char*)cfear_workspace(ctx, 1, off) : nullptr;
-  if (off && !ws) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed (%zu bytes)", off);
-  cfear_kstrong_out d;
-  d.sel_range = (dev && out->sel_range) ? out->sel_range : (int32_t*)(ws + o_sr);
-  d.sel_intensity = (dev && out->sel_intensity) ? out->sel_intensity : (uint8_t*)(ws + o_si);
-  d.sel_count = (dev && out->sel_count) ? out->sel_count : (int32_t*)(ws + o_sc);
-  d.is_peak = want_pk ? ((dev && out->is_peak) ? out->is_peak : (uint8_t*)(ws + o_pk)) : nullptr;
-  if (dev) {
-    d.xyzi = out->xyzi; d.n_points = out->n_points;
-    d.xyzi_peaks = want_pk ? out->xyzi_peaks : nullptr; d.n_peaks = want_pk ? out->n_peaks : nullptr;
-  } else {
-    d.xyzi = want_cloud ? (float*)(ws + o_xyz) : nullptr;
-    d.n_points = want_cloud ? (int32_t*)(ws + o_np) : nullptr;
-    const bool pc = want_pk && (out->xyzi_peaks || out->n_peaks);
-    d.xyzi_peaks = pc ? (float*)(ws + o_xyzp) : nullptr;
-    d.n_peaks = pc ? (int32_t*)(ws + o_npp) : nullptr;
-  }
-  const uint8_t* d_polar = polar;
-  cfear_polar_desc dd = *desc;
-  if (!dev) {
-    // stage the images densely: [batch][rows][stride]
-    const size_t img_bytes = (size_t)rows * desc->stride;
-    uint8_t* st = (uint8_t*)cfear_workspace(ctx, 0, img_bytes * batch);
-    if (!st) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-    const int64_t bs = batch > 1 ? desc->batch_stride : (int64_t)img_bytes;
-    for (int b = 0; b < batch; b++)
-      CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(st + (size_t)b * img_bytes, polar + (size_t)b * bs, img_bytes,
-                                          hipMemcpyHostToDevice, ctx->stream));
-    d_polar = st;
-    dd.batch_stride = (int64_t)img_bytes;
-  }
-  rc = cfear_kstrong_device(ctx, d_polar, &dd, par, &d);
-  if (rc != CFEAR_OK) return rc;
-  if (!dev) {
-    auto back = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
-      return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
-    };
-    CFEAR_HIP_CHECK(ctx, back(out->sel_range, d.sel_range, nsel * 4));
-    CFEAR_HIP_CHECK(ctx, back(out->sel_intensity, d.sel_intensity, nsel));
-    CFEAR_HIP_CHECK(ctx, back(out->sel_count, d.sel_count, (size_t)batch * rows * 4));
-    if (want_pk) CFEAR_HIP_CHECK(ctx, back(out->is_peak, d.is_peak, nsel));
-    if (d.xyzi) CFEAR_HIP_CHECK(ctx, back(out->xyzi, d.xyzi, nsel * 16));
-    if (d.n_points) CFEAR_HIP_CHECK(ctx, back(out->n_points, d.n_points, (size_t)batch * 4));
-    if (d.xyzi_peaks) CFEAR_HIP_CHECK(ctx, back(out->xyzi_peaks, d.xyzi_peaks, nsel * 16));
-    if (d.n_peaks) CFEAR_HIP_CHECK(ctx, back(out->n_peaks, d.n_peaks, (size_t)batch * 4));
-    CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return CFEAR_OK;
+  HostStage st(ctx, kWsFilter);
+  const uint8_t* d_polar;
+  const cfear_polar_desc dd = st.images(d_polar, polar, *desc);
+  cfear_kstrong_out d{};                                      // the selection (and peak flags) always; the rest if asked for
+  st.out(d.sel_range, out->sel_range, nsel * 4);
+  st.out(d.sel_intensity, out->sel_intensity, nsel);
+  st.out(d.sel_count, out->sel_count, (size_t)batch * rows * 4);
+  if (want_pk) st.out(d.is_peak, out->is_peak, nsel);
+  if (out->xyzi) st.out(d.xyzi, out->xyzi, nsel * 16);
+  if (out->n_points) st.out(d.n_points, out->n_points, (size_t)batch * 4);
+  if (want_pk && out->xyzi_peaks) st.out(d.xyzi_peaks, out->xyzi_peaks, nsel * 16);
+  if (want_pk && out->n_peaks) st.out(d.n_peaks, out->n_peaks, (size_t)batch * 4);
+  CFEAR_CHECK(st.carve());
+  CFEAR_CHECK(cfear_kstrong_device(ctx, d_polar, &dd, par, &d));
+  return st.finish();
 }
 
 
@@ -2245,76 +2197,63 @@ extern "C" int cfear_filter_kstrongest_legacy(cfear_ctx* ctx, const uint8_t* pol
                                               int32_t cap_points) {
   if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
   if (!polar || !xyzi || !n_points || cap_points <= 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
-  int rc = check_desc(ctx, desc);
-  if (rc != CFEAR_OK) return rc;
+  CFEAR_CHECK(check_desc(ctx, desc));
   if (k_strongest < 1 || k_strongest > kMaxK) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "k_strongest must be in [1,%d]", kMaxK);
   if (!(range_res > 0.0)) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "range_res must be > 0");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const int rows = desc->rows, cols = desc->cols, batch = desc->batch, k = k_strongest;
-  const bool dev = cfear_is_device_ptr(polar);
-  if (dev != cfear_is_device_ptr(xyzi) || dev != cfear_is_device_ptr(n_points))
+  HostStage st(ctx, kWsFilter);
+  const uint8_t* d_polar;
+  const cfear_polar_desc dd = st.images(d_polar, polar, *desc);
+  float* d_xyzi;
+  int32_t* d_np;
+  st.out(d_xyzi, xyzi, (size_t)batch * cap_points * 16);
+  st.out(d_np, n_points, (size_t)batch * 4);
+  if (st.mixed())
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "polar, xyzi and n_points must all be host or all be device memory");
-  const size_t img_bytes = (size_t)rows * desc->stride;
-  const uint8_t* d_polar = polar;
-  long long bs = batch > 1 ? desc->batch_stride : (long long)img_bytes;
-  if (!dev) {
-    uint8_t* st = (uint8_t*)cfear_workspace(ctx, 0, img_bytes * batch);
-    if (!st) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-    for (int b = 0; b < batch; b++)
-      CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(st + (size_t)b * img_bytes, polar + (size_t)b * bs, img_bytes, hipMemcpyHostToDevice, ctx->stream));
-    d_polar = st;
-    bs = (long long)img_bytes;
-  }
-  // workspace: reversed masked images | first-bin records | sel arrays | float trig tables | (host mode) cloud
+  // scratch: reversed masked images | first-bin records | sel arrays | float trig tables
   const int rev_stride = (cols + 15) / 16 * 16;
   const size_t nsel = (size_t)batch * rows * k;
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-  const size_t o_rev = carve((size_t)batch * rows * rev_stride), o_first = carve((size_t)batch * rows * 8);
-  const size_t o_sr = carve(nsel * 4), o_si = carve(nsel), o_sc = carve((size_t)batch * rows * 4), o_trig = carve((size_t)rows * 8);
-  const size_t o_xyz = carve(dev ? 0 : (size_t)batch * cap_points * 16), o_np = carve((size_t)batch * 4);
-  char* ws = (char*)cfear_workspace(ctx, 1, off);
-  if (!ws) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed (%zu bytes)", off);
-  {
-    std::vector<float> h(2 * (size_t)rows);                // host cosf / sinf of the FLOAT theta: bit-exact with glibc
-    for (int bearing = 0; bearing < rows; bearing++) {
-      const float theta = ((float)(bearing + 1) / rows) * 2 * M_PI;            // radar_filters.cpp:52
-      h[bearing] = std::cos(theta);
-      h[rows + bearing] = std::sin(theta);
-    }
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(ws + o_trig, h.data(), h.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  uint8_t* d_rev;
+  int32_t* d_first;
+  float* d_trig;
+  cfear_kstrong_out o{};
+  st.piece(d_rev, (size_t)batch * rows * rev_stride);
+  st.piece(d_first, (size_t)batch * rows * 8);
+  st.piece(o.sel_range, nsel * 4);
+  st.piece(o.sel_intensity, nsel);
+  st.piece(o.sel_count, (size_t)batch * rows * 4);
+  st.piece(d_trig, (size_t)rows * 8);
+  CFEAR_CHECK(st.carve());
+  float* h = (float*)st.record((size_t)rows * 8);          // host cosf / sinf of the FLOAT theta: bit-exact with glibc
+  for (int bearing = 0; bearing < rows; bearing++) {
+    const float theta = ((float)(bearing + 1) / rows) * 2 * M_PI;            // radar_filters.cpp:52
+    h[bearing] = std::cos(theta);
+    h[rows + bearing] = std::sin(theta);
   }
+  CFEAR_CHECK(st.upload(d_trig, h, (size_t)rows * 8));
   int u_z = (int)std::ceil(z_min);                         // uchar v < z_min  <=>  v < ceil(z_min)
   u_z = std::max(0, std::min(256, u_z));
   {
     ProfScope ps(ctx, "kstrong_legacy_prepare");
-    hipLaunchKernelGGL(legacy_prepare_kernel, dim3((rows + 3) / 4, batch), dim3(256), 0, ctx->stream, d_polar, rows, cols, desc->stride, bs,
-                       u_z, (uint8_t*)(ws + o_rev), rev_stride, (int32_t*)(ws + o_first));
+    hipLaunchKernelGGL(legacy_prepare_kernel, dim3((rows + 3) / 4, batch), dim3(256), 0, ctx->stream, d_polar, rows, cols, desc->stride,
+                       (long long)dd.batch_stride, u_z, d_rev, rev_stride, d_first);
   }
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
   cfear_polar_desc rd{rows, cols, rev_stride, batch, (int64_t)rows * rev_stride};
   cfear_kstrong_params kp{k, 1.0f, 1.0f, 0.0f, 0};
-  cfear_kstrong_out o{};
-  o.sel_range = (int32_t*)(ws + o_sr); o.sel_intensity = (uint8_t*)(ws + o_si); o.sel_count = (int32_t*)(ws + o_sc);
-  rc = cfear_kstrong_device(ctx, (const uint8_t*)(ws + o_rev), &rd, &kp, &o);
-  if (rc != CFEAR_OK) return rc;
-  float* d_xyzi = dev ? xyzi : (float*)(ws + o_xyz);
-  int32_t* d_np = dev ? n_points : (int32_t*)(ws + o_np);
+  CFEAR_CHECK(cfear_kstrong_device(ctx, d_rev, &rd, &kp, &o));
   {
     ProfScope ps(ctx, "kstrong_legacy_cloud");
     hipLaunchKernelGGL(legacy_cloud_kernel, dim3(batch), dim3(256), (size_t)(rows + 1) * 4, ctx->stream, o.sel_range, o.sel_intensity,
-                       o.sel_count, (const int32_t*)(ws + o_first), (const float*)(ws + o_trig), (const float*)(ws + o_trig) + rows, rows, cols, k,
-                       range_res, min_distance * min_distance, d_xyzi, d_np, cap_points);
+                       o.sel_count, d_first, d_trig, d_trig + rows, rows, cols, k, range_res, min_distance * min_distance, d_xyzi, d_np,
+                       cap_points);
   }
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
-  if (!dev) {
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(n_points, d_np, (size_t)batch * 4, hipMemcpyDeviceToHost, ctx->stream));
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(xyzi, d_xyzi, (size_t)batch * cap_points * 16, hipMemcpyDeviceToHost, ctx->stream));
-    CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  CFEAR_CHECK(st.finish());
+  if (st.any_host())
     for (int b = 0; b < batch; b++)
       if (n_points[b] > cap_points) return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "image %d: %d points > cap_points %d", b, n_points[b], cap_points);
-  }
   return CFEAR_OK;
 }
 
@@ -2416,7 +2355,7 @@ int cfear_cacfar_device(cfear_ctx* ctx, const uint8_t* d_polar, const cfear_pola
     a.row_keys = fused->row_keys; a.row_cnt = fused->row_cnt; a.kcap = fused->kcap;
   } else {
     size_t bits_bytes = (size_t)batch * rows * words * 8, cnt_bytes = (size_t)batch * rows * 4;
-    char* ws = (char*)cfear_workspace(ctx, 3, bits_bytes + cnt_bytes + 256);
+    char* ws = (char*)cfear_workspace(ctx, kWsFilterRows, bits_bytes + cnt_bytes + 256);
     if (!ws) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
     a.det_bits = (unsigned long long*)ws;
     a.det_count = (int32_t*)(ws + (bits_bytes + 255) / 256 * 256);
@@ -2506,37 +2445,27 @@ extern "C" int cfear_filter_cacfar(cfear_ctx* ctx, const uint8_t* polar, const c
   if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
   if (!polar || !par || !xyzi || !n_points || cap_points <= 0)
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
-  int rc = check_desc(ctx, desc);
-  if (rc != CFEAR_OK) return rc;
+  CFEAR_CHECK(check_desc(ctx, desc));
   if (par->window_size < 1 || par->nb_guard_cells < 0 || !(par->range_res > 0.f))
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "bad CFAR parameters");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const int rows = desc->rows, cols = desc->cols, batch = desc->batch;
-  const bool dev = cfear_is_device_ptr(polar);
-  if (dev) return cfear_cacfar_device(ctx, polar, desc, par, xyzi, n_points, cap_points, det_mask);
-  const size_t img_bytes = (size_t)rows * desc->stride;
-  const size_t xyz_bytes = (size_t)batch * cap_points * 16, mask_bytes = det_mask ? (size_t)batch * rows * cols : 0;
-  char* st = (char*)cfear_workspace(ctx, 0, img_bytes * batch);
-  char* ws = (char*)cfear_workspace(ctx, 1, xyz_bytes + mask_bytes + 1024);
-  if (!st || !ws) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-  const int64_t bs = batch > 1 ? desc->batch_stride : (int64_t)img_bytes;
-  for (int b = 0; b < batch; b++)
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(st + (size_t)b * img_bytes, polar + (size_t)b * bs, img_bytes,
-                                        hipMemcpyHostToDevice, ctx->stream));
-  cfear_polar_desc dd = *desc;
-  dd.batch_stride = (int64_t)img_bytes;
-  float* d_xyzi = (float*)ws;
-  int32_t* d_np = (int32_t*)(ws + (xyz_bytes + 255) / 256 * 256);
-  uint8_t* d_mask = det_mask ? (uint8_t*)(ws + (xyz_bytes + 255) / 256 * 256 + 256) : nullptr;
-  rc = cfear_cacfar_device(ctx, (const uint8_t*)st, &dd, par, d_xyzi, d_np, cap_points, d_mask);
-  if (rc != CFEAR_OK) return rc;
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(n_points, d_np, (size_t)batch * 4, hipMemcpyDeviceToHost, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(xyzi, d_xyzi, xyz_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  if (det_mask) CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(det_mask, d_mask, mask_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  for (int b = 0; b < batch; b++)
-    if (n_points[b] > cap_points)
-      return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "image %d: %d detections > cap_points %d", b, n_points[b], cap_points);
+  HostStage st(ctx, kWsFilter);
+  const uint8_t* d_polar;
+  const cfear_polar_desc dd = st.images(d_polar, polar, *desc);
+  float* d_xyzi;
+  int32_t* d_np;
+  uint8_t* d_mask = nullptr;
+  st.out(d_xyzi, xyzi, (size_t)batch * cap_points * 16);
+  st.out(d_np, n_points, (size_t)batch * 4);
+  if (det_mask) st.out(d_mask, det_mask, (size_t)batch * rows * cols);
+  CFEAR_CHECK(st.carve());
+  CFEAR_CHECK(cfear_cacfar_device(ctx, d_polar, &dd, par, d_xyzi, d_np, cap_points, d_mask));
+  CFEAR_CHECK(st.finish());
+  if (st.any_host())
+    for (int b = 0; b < batch; b++)
+      if (n_points[b] > cap_points)
+        return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "image %d: %d detections > cap_points %d", b, n_points[b], cap_points);
   return CFEAR_OK;
 }
 
@@ -2750,28 +2679,21 @@ extern "C" int cfear_polar_rotate_ccw(cfear_ctx* ctx, const uint8_t* src, const 
       (d.batch > 1 && (d.batch_stride < (int64_t)d.rows * d.stride || dst_batch_stride < (int64_t)d.cols * dst_stride)))
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "bad polar descriptor");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const bool dev = cfear_is_device_ptr(src);
-  if (dev != cfear_is_device_ptr(dst))
+  HostStage st(ctx, kWsFilter);
+  const uint8_t* d_src;
+  const cfear_polar_desc dd = st.images(d_src, src, d);
+  st.is_host(dst);
+  if (st.mixed())
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "src and dst must both be host or both be device memory");
-  if (dev) return cfear_rotate_ccw_device(ctx, src, src_desc, dst, dst_stride, dst_batch_stride);
-  // host images: stage densely, rotate, copy back row by row into the caller's pitch
-  const size_t in_bytes = (size_t)d.rows * d.stride;
+  if (!st.any_host()) return cfear_rotate_ccw_device(ctx, src, src_desc, dst, dst_stride, dst_batch_stride);
+  // host images: rotated densely, copied back row by row into the caller's pitch
   const int ostride = (d.rows + 15) / 16 * 16;
   const size_t out_bytes = (size_t)d.cols * ostride;
-  uint8_t* st = (uint8_t*)cfear_workspace(ctx, 0, in_bytes * d.batch);
-  uint8_t* ot = (uint8_t*)cfear_workspace(ctx, 1, out_bytes * d.batch);
-  if (!st || !ot) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-  const int64_t bs = d.batch > 1 ? d.batch_stride : (int64_t)in_bytes;
-  for (int b = 0; b < d.batch; b++)
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(st + (size_t)b * in_bytes, src + (size_t)b * bs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  cfear_polar_desc dd = d;
-  dd.batch_stride = (int64_t)in_bytes;
-  const int rc = cfear_rotate_ccw_device(ctx, st, &dd, ot, ostride, (int64_t)out_bytes);
-  if (rc != CFEAR_OK) return rc;
+  uint8_t* ot;
+  st.piece(ot, out_bytes * d.batch);
+  CFEAR_CHECK(st.carve());
+  CFEAR_CHECK(cfear_rotate_ccw_device(ctx, d_src, &dd, ot, ostride, (int64_t)out_bytes));
   const int64_t obs = d.batch > 1 ? dst_batch_stride : 0;
-  for (int b = 0; b < d.batch; b++)
-    CFEAR_HIP_CHECK(ctx, hipMemcpy2DAsync(dst + (size_t)b * obs, dst_stride, ot + (size_t)b * out_bytes, ostride, d.rows, d.cols,
-                                          hipMemcpyDeviceToHost, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  return CFEAR_OK;
+  for (int b = 0; b < d.batch; b++) st.back(dst + (size_t)b * obs, ot + (size_t)b * out_bytes, d.rows, d.cols, dst_stride, ostride);
+  return st.finish();
 }

@@ -1574,8 +1574,8 @@ int cfear_register_batch_device(cfear_ctx* ctx, const cfear_reg_job* jobs, int32
     if (rc != CFEAR_OK) return rc;
   }
   const size_t sb = reg_scratch_bytes(sz.pairs_cap) * (size_t)n_jobs;
-  char* ws = (char*)cfear_workspace(ctx, 6, jb + rb + 512);
-  char* scr = (char*)cfear_workspace(ctx, 7, sb);
+  char* ws = (char*)cfear_workspace(ctx, kWsRegJobs, jb + rb + 512);
+  char* scr = (char*)cfear_workspace(ctx, kWsRegScratch, sb);
   if (!ws || !scr) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
   char* d_jobs = ws;
   cfear_reg_result* d_res = d_out ? d_out : (cfear_reg_result*)(ws + (jb + 255) / 256 * 256);
@@ -1705,7 +1705,7 @@ int cfear_candidates_expand(cfear_ctx* ctx, hipStream_t stream, const cfear_scan
 // match: the matcher over the job records expand left at d_jobs, on the context's stream; records to d_res (device)
 int cfear_candidates_match(cfear_ctx* ctx, const char* d_jobs, int32_t n, const cfear_reg_params* par, const CandGeometry* geom,
                            cfear_reg_result* d_res) {
-  char* scr = (char*)cfear_workspace(ctx, 7, reg_scratch_bytes(geom->pairs_cap) * (size_t)n);
+  char* scr = (char*)cfear_workspace(ctx, kWsRegScratch, reg_scratch_bytes(geom->pairs_cap) * (size_t)n);
   if (!scr) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
   return cfear_register_launch(ctx, d_jobs, n, par, geom->pairs_cap, scr, d_res, nullptr, reg_job_stride(2), geom->hint);
 }
@@ -1713,7 +1713,7 @@ int cfear_candidates_match(cfear_ctx* ctx, const char* d_jobs, int32_t n, const 
 int cfear_candidates_enqueue(cfear_ctx* ctx, const cfear_scan_table* table, const cfear_candidate* cands, int32_t n,
                              const cfear_reg_params* par, cfear_candidate* h_stage, cfear_reg_result* d_res, int32_t* d_trailer,
                              int trailer_status) {
-  char* ws = (char*)cfear_workspace(ctx, 6, (size_t)n * reg_job_stride(2) + 512);
+  char* ws = (char*)cfear_workspace(ctx, kWsRegJobs, (size_t)n * reg_job_stride(2) + 512);
   if (!ws) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
   CandGeometry geom;
   const int rc = cfear_candidates_expand(ctx, ctx->stream, table, cands, n, par, h_stage, ws, d_trailer, trailer_status, &geom);
@@ -1734,7 +1734,7 @@ extern "C" int cfear_register_candidates(cfear_ctx* ctx, const cfear_scan_table*
   const bool dev_out = cfear_is_device_ptr(results);
   cfear_reg_result* d_res = results;
   if (!dev_out) {
-    d_res = (cfear_reg_result*)cfear_workspace(ctx, 13, rb);
+    d_res = (cfear_reg_result*)cfear_workspace(ctx, kWsCandResults, rb);
     if (!d_res) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
   }
   rc = cfear_candidates_enqueue(ctx, table, cands, n, par, hc, d_res, nullptr, 0);
@@ -1803,8 +1803,8 @@ int run_cost_batch(cfear_ctx* ctx, const cfear_reg_job* jobs, int n_jobs, const 
   const size_t per = reg_scratch_bytes(sz.pairs_cap) * (size_t)mode.blocks_per_job;
   const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_jobs, ((size_t)1 << 30) / per));
   const size_t rb = out.size() * sizeof(cfear_reg_result);
-  char* ws = (char*)cfear_workspace(ctx, 6, (jb + 255) / 256 * 256 + rb + 512);
-  char* scr = (char*)cfear_workspace(ctx, 7, per * (size_t)chunk);
+  char* ws = (char*)cfear_workspace(ctx, kWsRegJobs, (jb + 255) / 256 * 256 + rb + 512);
+  char* scr = (char*)cfear_workspace(ctx, kWsRegScratch, per * (size_t)chunk);
   if (!ws || !scr) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
   char* d_jobs = ws;
   cfear_reg_result* d_res = (cfear_reg_result*)(ws + (jb + 255) / 256 * 256);

@@ -244,56 +244,41 @@ extern "C" int cfear_sc_descriptors(cfear_ctx* ctx, const cfear_sc_cloud* clouds
                                     double* ringkey, double* sectorkey) {
   if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
   if (!clouds || !desc || n_clouds < 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
-  int rc = check_sc_params(ctx, par);
-  if (rc != CFEAR_OK) return rc;
+  CFEAR_CHECK(check_sc_params(ctx, par));
   if (n_aug < 1 || n_aug > kScMaxAug || (n_aug > 1 && !shifts_y))
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "n_aug must be in [1, %d]", kScMaxAug);
   if (n_clouds == 0) return CFEAR_OK;
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const int R = par->num_ring, S = par->num_sector, cells = R * S;
-  // stage host clouds
-  size_t stage = 0;
+  HostStage st(ctx, kWsCoral);
   for (int i = 0; i < n_clouds; i++) {
     if (clouds[i].n < 0 || (clouds[i].n > 0 && !clouds[i].xyzi)) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "cloud %d: null", i);
-    if (!cfear_is_device_ptr(clouds[i].xyzi)) stage += ((size_t)clouds[i].n * 16 + 255) / 256 * 256;
+    st.cloud_in(clouds[i].xyzi, clouds[i].n);
   }
   const size_t nd = (size_t)n_clouds * n_aug;
-  const bool desc_dev = cfear_is_device_ptr(desc);          // descriptor database kept in HBM: written in place
-  const size_t out_bytes = nd * ((desc_dev ? 0 : cells) + R + S) * sizeof(double);
-  const size_t head = ((size_t)n_clouds * sizeof(ScCloud) + 255) / 256 * 256;
-  char* ws = (char*)cfear_workspace(ctx, 8, head + stage + 256);
-  char* wo = (char*)cfear_workspace(ctx, 9, out_bytes + 256);
-  if (!ws || !wo) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-  std::vector<ScCloud> h(n_clouds);
-  size_t off = head;
+  ScDescArgs a;
+  st.piece(a.clouds, (size_t)n_clouds * sizeof(ScCloud));
+  st.out(a.desc, desc, nd * cells * sizeof(double));         // a descriptor database kept in HBM is written in place
+  st.piece(a.ringkey, nd * (R + S) * sizeof(double));
+  CFEAR_CHECK(st.carve());
+  ScCloud* h = (ScCloud*)st.record((size_t)n_clouds * sizeof(ScCloud));
   for (int i = 0; i < n_clouds; i++) {
     h[i].n = clouds[i].n; h[i].pad = 0;
-    if (cfear_is_device_ptr(clouds[i].xyzi) || clouds[i].n == 0) h[i].xyzi = (const float4*)clouds[i].xyzi;
-    else {
-      CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(ws + off, clouds[i].xyzi, (size_t)clouds[i].n * 16, hipMemcpyHostToDevice, ctx->stream));
-      h[i].xyzi = (const float4*)(ws + off);
-      off += ((size_t)clouds[i].n * 16 + 255) / 256 * 256;
-    }
+    h[i].xyzi = st.cloud(clouds[i].xyzi);
   }
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(ws, h.data(), h.size() * sizeof(ScCloud), hipMemcpyHostToDevice, ctx->stream));
-  ScDescArgs a;
-  a.clouds = (const ScCloud*)ws;
+  CFEAR_CHECK(st.upload((void*)a.clouds, h, (size_t)n_clouds * sizeof(ScCloud)));
   a.num_ring = R; a.num_sector = S; a.desc_function = par->desc_function; a.n_aug = n_aug;
   a.max_radius = par->max_radius; a.desc_divider = par->desc_divider; a.no_point = par->no_point;
   for (int k = 0; k < kScMaxAug; k++) a.shift_y[k] = (k < n_aug && shifts_y) ? shifts_y[k] : 0.0;
-  a.desc = desc_dev ? desc : (double*)wo;
-  a.ringkey = desc_dev ? (double*)wo : a.desc + nd * cells;
   a.sectorkey = a.ringkey + nd * R;
   {
     ProfScope ps(ctx, "sc_descriptor");
     hipLaunchKernelGGL(sc_descriptor_kernel, dim3(n_clouds, n_aug), dim3(256), (size_t)cells * 12, ctx->stream, a);
   }
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
-  if (!desc_dev) CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(desc, a.desc, nd * cells * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (ringkey) CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(ringkey, a.ringkey, nd * R * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (sectorkey) CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(sectorkey, a.sectorkey, nd * S * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  return CFEAR_OK;
+  if (ringkey) st.back(ringkey, a.ringkey, nd * R * sizeof(double));
+  if (sectorkey) st.back(sectorkey, a.sectorkey, nd * S * sizeof(double));
+  return st.finish();
 }
 
 extern "C" int cfear_sc_distance_batch(cfear_ctx* ctx, const double* desc_q, int32_t n_q, const double* desc_c,
@@ -302,8 +287,7 @@ extern "C" int cfear_sc_distance_batch(cfear_ctx* ctx, const double* desc_q, int
   if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
   if (!desc_q || !desc_c || !pairs || !dist || !shift || n_pairs < 0 || n_q < 0 || n_c < 0)
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
-  int rc = check_sc_params(ctx, par);
-  if (rc != CFEAR_OK) return rc;
+  CFEAR_CHECK(check_sc_params(ctx, par));
   if (n_pairs == 0) return CFEAR_OK;
   for (int i = 0; i < n_pairs; i++)
     if (pairs[2 * i] < 0 || pairs[2 * i] >= n_q || pairs[2 * i + 1] < 0 || pairs[2 * i + 1] >= n_c)
@@ -311,18 +295,14 @@ extern "C" int cfear_sc_distance_batch(cfear_ctx* ctx, const double* desc_q, int
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const int R = par->num_ring, S = par->num_sector, cells = R * S;
   const size_t qb = (size_t)n_q * cells * 8, cb = (size_t)n_c * cells * 8, pb = (size_t)n_pairs * 8;
-  const bool qdev = cfear_is_device_ptr(desc_q), cdev = cfear_is_device_ptr(desc_c);
-  auto r256 = [](size_t b) { return (b + 255) / 256 * 256; };
-  char* ws = (char*)cfear_workspace(ctx, 8, (qdev ? 0 : r256(qb)) + (cdev ? 0 : r256(cb)) + r256(pb) + r256((size_t)n_pairs * 12) + 256);
-  if (!ws) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-  size_t off = 0;
+  HostStage st(ctx, kWsClouds);
   ScDistArgs a;
-  if (qdev) a.desc_q = desc_q; else { CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(ws + off, desc_q, qb, hipMemcpyHostToDevice, ctx->stream)); a.desc_q = (const double*)(ws + off); off += r256(qb); }
-  if (cdev) a.desc_c = desc_c; else { CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(ws + off, desc_c, cb, hipMemcpyHostToDevice, ctx->stream)); a.desc_c = (const double*)(ws + off); off += r256(cb); }
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(ws + off, pairs, pb, hipMemcpyHostToDevice, ctx->stream));
-  a.pairs = (const int32_t*)(ws + off); off += r256(pb);
-  a.dist = (double*)(ws + off);
-  a.shift = (int32_t*)(ws + off + (size_t)n_pairs * 8);
+  st.in(a.desc_q, desc_q, qb);
+  st.in(a.desc_c, desc_c, cb);
+  st.in(a.pairs, pairs, pb);
+  st.out(a.dist, dist, (size_t)n_pairs * 8);
+  st.out(a.shift, shift, (size_t)n_pairs * 4);
+  CFEAR_CHECK(st.carve());
   a.num_ring = R; a.num_sector = S; a.search_ratio = par->search_ratio;
   const size_t base = (((size_t)2 * cells + 5 * S) * 8 + (size_t)(2 + 2 * S + 2) * 4 + 16 + 15) & ~(size_t)15;
   const int m_max = 2 * (int)std::round(0.5 * par->search_ratio * S) + 1;
@@ -337,10 +317,7 @@ extern "C" int cfear_sc_distance_batch(cfear_ctx* ctx, const double* desc_q, int
     hipLaunchKernelGGL(sc_distance_kernel, dim3(n_pairs), dim3(kScDistThreads), lds, ctx->stream, a);
   }
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(dist, a.dist, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(shift, a.shift, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  return CFEAR_OK;
+  return st.finish();
 }
 
 // ---- RSCManager: descriptor database + retrieval policy (host) around the two kernels ----------------------

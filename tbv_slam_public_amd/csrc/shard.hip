@@ -161,15 +161,14 @@ extern "C" int cfear_rccl_allgather_device(void* user, const void* d_send, void*
 extern "C" int cfear_rccl_allgather(void* user, const void* send, void* recv, size_t bytes) {
   cfear_rccl_comm* c = (cfear_rccl_comm*)user;
   if (!c || !c->ctx || !c->nccl_comm || c->world < 1) return CFEAR_ERR_INVALID_ARGUMENT;
-  cfear_ctx* ctx = c->ctx;
-  char* ws = (char*)cfear_workspace(ctx, 10, bytes * ((size_t)c->world + 1));
-  if (!ws) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(ws, send, bytes, hipMemcpyHostToDevice, ctx->stream));
-  const int rc = cfear_rccl_allgather_device(user, ws, ws + bytes, bytes);
-  if (rc != 0) return rc;
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(recv, ws + bytes, bytes * (size_t)c->world, hipMemcpyDeviceToHost, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  return 0;
+  HostStage st(c->ctx, kWsCoralScratch);
+  const void* d_send;
+  void* d_recv;
+  st.in(d_send, send, bytes);
+  st.out(d_recv, recv, bytes * (size_t)c->world);
+  int rc = st.carve();
+  if (rc == CFEAR_OK) rc = cfear_rccl_allgather_device(user, d_send, d_recv, bytes);
+  return rc != CFEAR_OK ? rc : st.finish();
 }
 
 // ---- sharded callers ---------------------------------------------------------------------------------------------------
@@ -187,7 +186,7 @@ extern "C" int cfear_register_batch_sharded(cfear_ctx* ctx, const cfear_reg_job*
     // the device, ncclAllGather moves them over xGMI, ONE device-to-host copy returns all n records (the generic route
     // would read the block back, upload it again and synchronise twice for 36 KiB).
     const size_t rbytes = (size_t)per * sizeof(cfear_reg_result), bytes = rbytes + sizeof(ShardTrailer);
-    char* ws = (char*)cfear_workspace(ctx, 10, bytes * ((size_t)world + 1) + 256);
+    char* ws = (char*)cfear_workspace(ctx, kWsCoralScratch, bytes * ((size_t)world + 1) + 256);
     if (!ws) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
     std::vector<char> host(bytes * (size_t)world);
     char* d_send = ws;

@@ -24,6 +24,7 @@
 // Working set per scan is a few hundred KB and stays in LDS / L2; nothing here is HBM-bound.
 #include <cfloat>
 #include <cmath>
+#include <memory>
 #include <type_traits>
 
 #include "common.hpp"
@@ -1636,10 +1637,10 @@ int cfear_surface_launch(cfear_ctx* ctx, const void* d_jobs, int n_jobs, const c
   // (the counter is zeroed by surface_finish_kernel for the next launch; it is zeroed HERE when the workspace was (re)allocated
   // -- hipFree + hipMalloc may hand back the same address -- or when the previous launch sequence did not reach its finish
   // kernel: ctx->surf_list_dirty stays set from before the first launch until after the last one was enqueued without error)
-  const size_t ws_bytes_before = ctx->ws[11].bytes;
-  cm.fallback = (int32_t*)cfear_workspace(ctx, 11, ((size_t)n_jobs + 16) * 4);
+  const size_t ws_bytes_before = ctx->ws[kWsSurfaceList].bytes;
+  cm.fallback = (int32_t*)cfear_workspace(ctx, kWsSurfaceList, ((size_t)n_jobs + 16) * 4);
   if (!cm.fallback) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-  if (ctx->ws[11].bytes != ws_bytes_before || ctx->surf_list_dirty)
+  if (ctx->ws[kWsSurfaceList].bytes != ws_bytes_before || ctx->surf_list_dirty)
     CFEAR_HIP_CHECK(ctx, hipMemsetAsync(cm.fallback, 0, 4, ctx->stream));
   ctx->surf_list_dirty = true;
   // per launch: the attribute is per device, and contexts on other threads / devices share this code
@@ -1737,23 +1738,16 @@ extern "C" int cfear_compensate(cfear_ctx* ctx, float* xyzi, int32_t n, const do
   if (!xyzi || !mot || n < 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
   if (n == 0) return CFEAR_OK;
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const bool dev = cfear_is_device_ptr(xyzi);
-  float* d = xyzi;
-  if (!dev) {
-    d = (float*)cfear_workspace(ctx, 4, (size_t)n * 16);
-    if (!d) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(d, xyzi, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-  }
+  HostStage st(ctx, kWsSurface);
+  float* d;
+  st.in(d, xyzi, (size_t)n * 16, true);
+  CFEAR_CHECK(st.carve());
   {
     ProfScope ps(ctx, "compensate");
     hipLaunchKernelGGL(compensate_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (float4*)d, n, mot[0], mot[1], mot[2], ccw);
   }
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
-  if (!dev) {
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(xyzi, d, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
-    CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return CFEAR_OK;
+  return st.finish();
 }
 
 extern "C" int cfear_scan_create(cfear_ctx* ctx, float* xyzi, int32_t n, const cfear_feature_params* par, cfear_scan** out) {
@@ -1763,39 +1757,30 @@ extern "C" int cfear_scan_create(cfear_ctx* ctx, float* xyzi, int32_t n, const c
   if (n <= 0) return cfear_set_error(ctx, CFEAR_ERR_EMPTY_CLOUD, "error, cloud empty");   // pointnormal.cpp:72-75
   if (n > kScanCreateMaxPoints) return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "n = %d > %d points", n, kScanCreateMaxPoints);
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const bool dev = cfear_is_device_ptr(xyzi);
-  float* d = xyzi;
-  if (!dev) {
-    d = (float*)cfear_workspace(ctx, 4, (size_t)n * 16);
-    if (!d) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(d, xyzi, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-  }
   cfear_scan* s = nullptr;
-  int rc = cfear_scan_alloc(ctx, n, &s);          // at most one cell per point
-  if (rc != CFEAR_OK) return rc;
-  char* ws = (char*)cfear_workspace(ctx, 5, cfear_surface_scratch_bytes(n) + 1024);
-  if (!ws) { cfear_scan_destroy(s); return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed"); }
-  char* d_job = ws;                                // job record + status in front of the scratch
-  int32_t* d_status = (int32_t*)(ws + 512);
-  char* d_scratch = ws + 1024;
-  unsigned char hjob[sizeof(SurfJob)];
+  CFEAR_CHECK(cfear_scan_alloc(ctx, n, &s));          // at most one cell per point
+  std::unique_ptr<cfear_scan, int (*)(cfear_scan*)> owned(s, cfear_scan_destroy);   // on every error, after the drain
+  int32_t hst[2] = {0, 0};                         // status, cells
+  HostStage st(ctx, kWsSurface);
+  float* d;
+  void* d_job;
+  int32_t* d_status;
+  st.in(d, xyzi, (size_t)n * 16, par->compensate != 0);     // compensated in place: back to a host caller
+  st.piece(d_job, sizeof(SurfJob));
+  st.piece(d_status, 4);
+  char* d_scratch = (char*)cfear_workspace(ctx, kWsSurfaceScratch, cfear_surface_scratch_bytes(n));
+  if (!d_scratch) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
+  CFEAR_CHECK(st.carve());
+  void* hjob = st.record(sizeof(SurfJob));
   cfear_surface_fill_job(hjob, d, nullptr, n, par->compensate, par->mot, s->view);
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(d_job, hjob, sizeof(SurfJob), hipMemcpyHostToDevice, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));     // hjob is on the stack
-  rc = cfear_surface_launch(ctx, d_job, 1, par, d_scratch, d_status, nullptr, n, n);
-  if (rc != CFEAR_OK) { cfear_scan_destroy(s); return rc; }
-  int32_t hst[2] = {0, 0};
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(&hst[0], d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(&hst[1], s->view.n_cells, 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (!dev && par->compensate)
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(xyzi, d, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  if (hst[0] != CFEAR_OK) {
-    cfear_scan_destroy(s);
-    return cfear_set_error(ctx, hst[0], "surface point extraction failed: %s", cfear_status_string(hst[0]));
-  }
+  CFEAR_CHECK(st.upload(d_job, hjob, sizeof(SurfJob)));
+  CFEAR_CHECK(cfear_surface_launch(ctx, d_job, 1, par, d_scratch, d_status, nullptr, n, n));
+  st.back(&hst[0], d_status, 4);
+  st.back(&hst[1], s->view.n_cells, 4);
+  CFEAR_CHECK(st.finish());
+  if (hst[0] != CFEAR_OK) return cfear_set_error(ctx, hst[0], "surface point extraction failed: %s", cfear_status_string(hst[0]));
   s->n_cells_host = hst[1];
-  *out = s;
+  *out = owned.release();
   return CFEAR_OK;
 }
 
@@ -1803,22 +1788,22 @@ extern "C" int cfear_scan_from_cells(cfear_ctx* ctx, const cfear_cell* cells, in
   if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
   if (!out || n_cells < 0 || (!cells && n_cells > 0)) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
   *out = nullptr;
+  if (n_cells > kMaxPoints) return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "more than %d cells", kMaxPoints);
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   cfear_scan* s = nullptr;
-  int rc = cfear_scan_alloc(ctx, n_cells > 0 ? n_cells : 1, &s);
-  if (rc != CFEAR_OK) return rc;
-  cfear_cell* d = (cfear_cell*)cfear_workspace(ctx, 4, (size_t)(n_cells > 0 ? n_cells : 1) * sizeof(cfear_cell));
-  if (!d) { cfear_scan_destroy(s); return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed"); }
-  if (n_cells > 0)
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(d, cells, (size_t)n_cells * sizeof(cfear_cell), hipMemcpyHostToDevice, ctx->stream));
+  CFEAR_CHECK(cfear_scan_alloc(ctx, n_cells > 0 ? n_cells : 1, &s));
+  std::unique_ptr<cfear_scan, int (*)(cfear_scan*)> owned(s, cfear_scan_destroy);   // on every error, after the drain
+  HostStage st(ctx, kWsSurface);
+  const cfear_cell* d;
+  st.in(d, cells, (size_t)n_cells * sizeof(cfear_cell));
+  CFEAR_CHECK(st.carve());
   hipLaunchKernelGGL(cells_to_slab_kernel, dim3((n_cells + 255) / 256 + 1), dim3(256), 0, ctx->stream, d, n_cells, s->view);
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
-  if (n_cells > kMaxPoints) { cfear_scan_destroy(s); return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "more than %d cells", kMaxPoints); }
   hipLaunchKernelGGL(scan_grid_kernel, dim3(1), dim3(kSurfThreads), 0, ctx->stream, s->view);
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));     // caller's host array may go away
+  CFEAR_CHECK(st.finish());
   s->n_cells_host = n_cells;
-  *out = s;
+  *out = owned.release();
   return CFEAR_OK;
 }
 
@@ -1830,12 +1815,13 @@ extern "C" int cfear_scan_get_cells(const cfear_scan* scan, cfear_cell* out_host
   if (n > cap) return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "%d cells > cap %d", n, cap);
   if (n == 0) return 0;
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  cfear_cell* d = (cfear_cell*)cfear_workspace(ctx, 4, (size_t)n * sizeof(cfear_cell));
-  if (!d) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
+  HostStage st(ctx, kWsSurface);
+  cfear_cell* d;
+  st.out(d, out_host, (size_t)n * sizeof(cfear_cell));
+  CFEAR_CHECK(st.carve());
   hipLaunchKernelGGL(slab_to_cells_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, scan->view, n, d);
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(out_host, d, (size_t)n * sizeof(cfear_cell), hipMemcpyDeviceToHost, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  CFEAR_CHECK(st.finish());
   return n;
 }
 
@@ -1877,25 +1863,17 @@ extern "C" int cfear_scan_closest_idx(const cfear_scan* scan, const double* quer
   const int n = cfear_scan_size(scan);
   if (n < 0) return n;
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const bool dev = cfear_is_device_ptr(queries_xy);
-  if (dev != cfear_is_device_ptr(idx))
+  HostStage st(ctx, kWsSurface);
+  const double2* dq;
+  int32_t* di;
+  st.in(dq, (const double2*)queries_xy, (size_t)n_queries * 16);
+  st.out(di, idx, (size_t)n_queries * 4);
+  if (st.mixed())
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "queries and idx must both be host or both be device memory");
-  const double2* dq = (const double2*)queries_xy;
-  int32_t* di = idx;
-  if (!dev) {
-    char* ws = (char*)cfear_workspace(ctx, 4, (size_t)n_queries * 20 + 256);
-    if (!ws) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(ws, queries_xy, (size_t)n_queries * 16, hipMemcpyHostToDevice, ctx->stream));
-    dq = (const double2*)ws;
-    di = (int32_t*)(ws + (((size_t)n_queries * 16 + 255) & ~(size_t)255));
-  }
+  CFEAR_CHECK(st.carve());
   hipLaunchKernelGGL(closest_idx_kernel, dim3((n_queries + 255) / 256), dim3(256), 0, ctx->stream, scan->view, n, dq, n_queries,
                      d * d, di);
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
-  if (!dev) {
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(idx, di, (size_t)n_queries * 4, hipMemcpyDeviceToHost, ctx->stream));
-    CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return CFEAR_OK;
+  return st.finish();
 }
 

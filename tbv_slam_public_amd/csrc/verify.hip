@@ -17,7 +17,6 @@
 #include <chrono>
 #include <algorithm>
 #include <cmath>
-#include <map>
 #include <numeric>
 #include <vector>
 
@@ -278,9 +277,8 @@ int verify_device_chain(cfear_ctx* ctx, const cfear_verify_job* jobs, int32_t n_
 #endif
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   // ---- host: one record per candidate; peak clouds that live on the host are staged once each -----------------------
-  std::map<const float*, const float4*> where;           // cloud -> its device address (one hipPointerGetAttributes per distinct cloud)
-  std::vector<std::pair<const float*, int>> to_stage;
-  size_t stage_floats = 0;
+  int32_t first_bad = 0x7fffffff;
+  HostStage st(ctx, kWsVerify);
   int max_cells = 0, cap = 1;
   for (size_t j = 0; j < n; j++) {
     const cfear_verify_job& jb = jobs[j];
@@ -290,55 +288,27 @@ int verify_device_chain(cfear_ctx* ctx, const cfear_verify_job* jobs, int32_t n_
     if ((long long)jb.n_from + jb.n_to > cfear_coral_max_points())
       return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "job %zu: %d + %d points exceed %d", j, jb.n_from, jb.n_to, cfear_coral_max_points());
     cap = std::max(cap, jb.n_from + jb.n_to);
-    const float* ptrs[2] = {jb.from_peaks, jb.to_peaks};
-    const int ns[2] = {jb.n_from, jb.n_to};
-    for (int c = 0; c < 2; c++) {
-      if (ns[c] == 0 || !ptrs[c]) continue;
-      auto it = where.find(ptrs[c]);
-      if (it == where.end()) {
-        if (cfear_is_device_ptr(ptrs[c])) where[ptrs[c]] = (const float4*)ptrs[c];
-        else { where[ptrs[c]] = (const float4*)(uintptr_t)(stage_floats * 4); to_stage.emplace_back(ptrs[c], ns[c]); stage_floats += ((size_t)ns[c] * 4 + 3) & ~(size_t)3; }
-      } else if (!to_stage.empty()) {
-        for (auto& ts : to_stage) if (ts.first == ptrs[c]) { if (ns[c] > ts.second) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "job %zu: a host cloud is used with two lengths", j); break; }
-      }
-    }
+    st.cloud_in(jb.from_peaks, jb.n_from);
+    st.cloud_in(jb.to_peaks, jb.n_to);
     const int ct = cfear_scan_size(jb.to_scan), cf = cfear_scan_size(jb.from_scan);
     if (ct < 0) return ct;
     if (cf < 0) return cf;
     max_cells = std::max(max_cells, std::max(ct, cf));
   }
-  float* d_stage = nullptr;
-  if (stage_floats) {
-    d_stage = (float*)cfear_workspace(ctx, 8, stage_floats * 4);
-    if (!d_stage) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-    for (auto& ts : to_stage) {
-      const size_t off = (size_t)(uintptr_t)where[ts.first] / 4;
-      CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(d_stage + off, ts.first, (size_t)ts.second * 16, hipMemcpyHostToDevice, ctx->stream));
-      where[ts.first] = (const float4*)(d_stage + off);
-    }
-  }
-  mark(0);
-  VerifyDev* hc = (VerifyDev*)cfear_pinned(ctx, n * sizeof(VerifyDev));
-  if (!hc) return cfear_set_error(ctx, CFEAR_ERR_HIP, "pinned staging allocation failed");
-  for (size_t j = 0; j < n; j++) {
-    const cfear_verify_job& jb = jobs[j];
-    VerifyDev& v = hc[j];
-    v.to = jb.to_scan->view; v.from = jb.from_scan->view;
-    v.from_peaks = jb.n_from > 0 ? where[jb.from_peaks] : nullptr;
-    v.to_peaks = jb.n_to > 0 ? where[jb.to_peaks] : nullptr;
-    v.n_from = jb.n_from; v.n_to = jb.n_to;
-    for (int k = 0; k < 3; k++) { v.from_pose[k] = jb.from_pose[k]; v.t_be_guess[k] = jb.t_be_guess[k]; }
-    v.sc_sim = jb.sc_sim; v.odom_bounds = jb.odom_bounds;
-  }
-  mark(1);
   // ---- device buffers: one workspace, carved ---------------------------------------------------------------------------
-  const size_t stride = reg_job_stride(2);
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t o_cand = 0, o_reg_jobs = o_cand + up(n * sizeof(VerifyDev)), o_cost_jobs = o_reg_jobs + up(n * stride),
-               o_coral_jobs = o_cost_jobs + up(n * stride), o_reg = o_coral_jobs + up(n * sizeof(CoralJob)),
-               o_q = o_reg + up(n * sizeof(cfear_reg_result)), o_coral = o_q + up(n * sizeof(cfear_reg_result)),
-               o_out = o_coral + up(n * sizeof(cfear_coral_result)), o_flag = o_out + up(n * sizeof(cfear_verify_result)), total = o_flag + 256;
-  char* ws = (char*)cfear_workspace(ctx, 14, total);
+  VerifyChain c;
+  c.stride = reg_job_stride(2);
+  st.piece(c.cand, n * sizeof(VerifyDev));
+  st.piece(c.reg_jobs, n * c.stride);
+  st.piece(c.cost_jobs, n * c.stride);
+  st.piece(c.coral_jobs, n * sizeof(CoralJob));
+  st.piece(c.reg, n * sizeof(cfear_reg_result));
+  st.piece(c.q, n * sizeof(cfear_reg_result));
+  st.piece(c.coral, n * sizeof(cfear_coral_result));
+  // results on the DEVICE (a sharded caller gathers them there): the finish kernel writes them in place, nothing but the error
+  // flag comes back, and ApplyConstratins is the caller's (cfear_verify_apply_constraints over the gathered list)
+  const bool host_out = st.out(c.out, results, n * sizeof(cfear_verify_result));
+  st.piece(c.first_bad, 4);
   // RegisterLoopCandidate: P2L, Huber 0.1, uniform weights, SetParameters(4, 10) (loopclosure.cpp:56-57); CFEARQuality:
   // n_scan_normal_reg(P2L, Huber, 0.3), fresh -- itr_ = 0 (AlignmentQuality.cpp:330-354)
   cfear_reg_params rp, qp;
@@ -351,45 +321,49 @@ int verify_device_chain(cfear_ctx* ctx, const cfear_verify_job* jobs, int32_t n_
   cfear_reg_pair_geometry(&rp, max_cells, max_cells, &pairs_cap, &hint);
   cfear_reg_pair_geometry(&qp, max_cells, max_cells, &pairs_cap_q, &hint_q);
   hint_q.small_pairs = false;
-  char* scr = (char*)cfear_workspace(ctx, 7, cfear_register_scratch_bytes(std::max(pairs_cap, pairs_cap_q)) * n);
-  if (!ws || !scr) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-  VerifyChain c;
-  c.cand = (const VerifyDev*)(ws + o_cand); c.reg_jobs = ws + o_reg_jobs; c.cost_jobs = ws + o_cost_jobs; c.stride = stride;
-  c.coral_jobs = (CoralJob*)(ws + o_coral_jobs); c.reg = (const cfear_reg_result*)(ws + o_reg); c.q = (const cfear_reg_result*)(ws + o_q);
-  // results on the DEVICE (a sharded caller gathers them there): the finish kernel writes them in place, nothing but the error
-  // flag comes back, and ApplyConstratins is the caller's (cfear_verify_apply_constraints over the gathered list)
-  const bool dev_out = cfear_is_device_ptr(results);
-  c.coral = (const cfear_coral_result*)(ws + o_coral); c.out = dev_out ? results : (cfear_verify_result*)(ws + o_out); c.first_bad = (int32_t*)(ws + o_flag);
+  char* scr = (char*)cfear_workspace(ctx, kWsRegScratch, cfear_register_scratch_bytes(std::max(pairs_cap, pairs_cap_q)) * n);
+  if (!scr) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
+  CFEAR_CHECK(st.carve());
+  mark(0);
+  VerifyDev* hc = (VerifyDev*)cfear_pinned(ctx, n * sizeof(VerifyDev));
+  if (!hc) return cfear_set_error(ctx, CFEAR_ERR_HIP, "pinned staging allocation failed");
+  for (size_t j = 0; j < n; j++) {
+    const cfear_verify_job& jb = jobs[j];
+    VerifyDev& v = hc[j];
+    v.to = jb.to_scan->view; v.from = jb.from_scan->view;
+    v.from_peaks = jb.n_from > 0 ? st.cloud(jb.from_peaks) : nullptr;
+    v.to_peaks = jb.n_to > 0 ? st.cloud(jb.to_peaks) : nullptr;
+    v.n_from = jb.n_from; v.n_to = jb.n_to;
+    for (int k = 0; k < 3; k++) { v.from_pose[k] = jb.from_pose[k]; v.t_be_guess[k] = jb.t_be_guess[k]; }
+    v.sc_sim = jb.sc_sim; v.odom_bounds = jb.odom_bounds;
+  }
+  mark(1);
   c.n = n_jobs; c.par = *par;
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
   // ---- the chain ---------------------------------------------------------------------------------------------------------
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(ws + o_cand, hc, n * sizeof(VerifyDev), hipMemcpyHostToDevice, ctx->stream));
+  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync((void*)c.cand, hc, n * sizeof(VerifyDev), hipMemcpyHostToDevice, ctx->stream));
   cfear_pinned_mark(ctx);
-  int rc = CFEAR_OK;
   { ProfScope ps(ctx, "verify_glue"); hipLaunchKernelGGL(verify_expand_kernel, grid, block, 0, ctx->stream, c); }
-  rc = cfear_register_launch(ctx, c.reg_jobs, n_jobs, &rp, pairs_cap, scr, (cfear_reg_result*)(ws + o_reg), nullptr, stride, hint);
+  int rc = cfear_register_launch(ctx, c.reg_jobs, n_jobs, &rp, pairs_cap, scr, (cfear_reg_result*)c.reg, nullptr, c.stride, hint);
   if (rc == CFEAR_OK) {
     { ProfScope ps(ctx, "verify_glue"); hipLaunchKernelGGL(verify_prepare_kernel, grid, block, 0, ctx->stream, c); }
     RegCostMode mode;                                        // GetCost at the jobs' own poses
-    mode.blocks_per_job = std::max(1, std::min(1, (1024 + n_jobs - 1) / n_jobs));
-    rc = cfear_register_launch(ctx, c.cost_jobs, n_jobs, &qp, pairs_cap_q, scr, (cfear_reg_result*)(ws + o_q), &mode, stride, hint_q);
+    rc = cfear_register_launch(ctx, c.cost_jobs, n_jobs, &qp, pairs_cap_q, scr, (cfear_reg_result*)c.q, &mode, c.stride, hint_q);
   }
-  if (rc == CFEAR_OK) rc = cfear_coral_launch_device(ctx, c.coral_jobs, n_jobs, cap, &par->coral, (cfear_coral_result*)(ws + o_coral));
-  if (rc != CFEAR_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+  if (rc == CFEAR_OK) rc = cfear_coral_launch_device(ctx, c.coral_jobs, n_jobs, cap, &par->coral, (cfear_coral_result*)c.coral);
+  if (rc != CFEAR_OK) return rc;
   { ProfScope ps(ctx, "verify_glue"); hipLaunchKernelGGL(verify_finish_kernel, grid, block, 0, ctx->stream, c); }
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
   mark(2);
-  int32_t first_bad = 0x7fffffff;
-  if (!dev_out) CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(results, ws + o_out, n * sizeof(cfear_verify_result), hipMemcpyDeviceToHost, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(&first_bad, ws + o_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  st.back(&first_bad, c.first_bad, 4);
+  CFEAR_CHECK(st.finish());
   if (first_bad != 0x7fffffff) {
     cfear_coral_result bad;
-    CFEAR_HIP_CHECK(ctx, hipMemcpy(&bad, ws + o_coral + (size_t)first_bad * sizeof(cfear_coral_result), sizeof(bad), hipMemcpyDeviceToHost));
+    CFEAR_HIP_CHECK(ctx, hipMemcpy(&bad, c.coral + first_bad, sizeof(bad), hipMemcpyDeviceToHost));
     return cfear_set_error(ctx, bad.status, "job %d: %s", first_bad, cfear_status_string(bad.status));
   }
   mark(3);
-  if (!dev_out) apply_constraints(jobs, n, par, results);
+  if (host_out) apply_constraints(jobs, n, par, results);
   mark(4);
 #ifdef CFEAR_VERIFY_TIMING
   fprintf(stderr, "verify us: scan clouds + sizes %.0f | fill records %.0f | enqueue the chain %.0f | kernels + read-back %.0f | ApplyConstratins %.0f\n",
@@ -482,7 +456,7 @@ static int verify_host_chain(cfear_ctx* ctx, const cfear_verify_job* jobs, int32
   }
   std::vector<cfear_coral_result> coral(n);
   mark(2);
-  CoralPending pend;
+  CoralPending pend(ctx);
   rc = cfear_coral_enqueue(ctx, cjobs.data(), n_jobs, &par->coral, false, pend);
   if (rc != CFEAR_OK) return rc;
   mark(3);

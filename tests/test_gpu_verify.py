@@ -211,3 +211,23 @@ def test_verify_records_left_on_the_device_equal_the_host_records(nodes):
         assert host["accepted"].sum() >= 2
     with pytest.raises(L.CfearError):
         api.verify_loop_candidates(jobs, api.verify_params(use_covariance_sampling=1), device_ptr=buf.data_ptr())
+
+
+def test_verify_host_cloud_shared_at_two_lengths(nodes):
+    """One host peak cloud named by two candidates with different n, the shorter (a prefix of it) first: it is staged once, at
+    the longer length, and the records equal those of the same batch in which each candidate has a copy of its own."""
+    from tbv_slam_public_amd import api
+    cands = _candidates(nodes)[:2]                                                     # both from node 4
+    pk = np.ascontiguousarray(nodes[4]["peaks"], dtype=np.float32)
+    m = len(pk) // 2
+    assert m > 0
+
+    def run(first):
+        jobs = [dict(from_scan=nodes[c["f"]]["scan"], to_scan=nodes[c["t"]]["scan"], from_peaks=fp, to_peaks=nodes[c["t"]]["peaks"],
+                     from_pose=nodes[c["f"]]["T"], t_be_guess=c["t_be_guess"], sc_sim=c["sc_sim"], odom_bounds=c["odom_bounds"],
+                     group=c["group"]) for c, fp in zip(cands, (first, pk))]
+        return api.verify_loop_candidates(jobs, api.verify_params())
+    shared = run(pk[:m])
+    separate = run(pk[:m].copy())
+    assert shared.tobytes() == separate.tobytes()
+    assert shared["reg_ok"].all()
