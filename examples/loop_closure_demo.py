@@ -9,7 +9,7 @@
 The sensor drives a closed circle, so the last nodes revisit the first ones: the demo prints the loop constraints the
 verifier accepts and how far their registered transforms are from the ground truth.  `run(backend)` is shared with
 tests/test_gpu_tbv_loop.py, which runs it a second time with the CPU oracle behind the same host logic.
-    python examples/loop_closure_demo.py [--frames 68]"""
+    python examples/loop_closure_demo.py [--frames 68] [--raw-scan-context]"""
 import argparse
 import os
 import sys
@@ -87,8 +87,10 @@ class HipBackend:
                      reg_ok=bool(r["reg_ok"][i]), alignment_quality=float(r["alignment_quality"][i])) for i in range(len(cands))]
 
 
-def run(backend, n_frames=68, scene=None, log=None):
-    """-> dict(poses, gt, candidates [dict], results [dict]) ; candidates[i] / results[i] belong together."""
+def run(backend, n_frames=68, scene=None, log=None, raw_scan_context=False):
+    """-> dict(poses, gt, candidates [dict], results [dict]) ; candidates[i] / results[i] belong together.
+    raw_scan_context: TBV's --raw_radar_scan true (loopclosure.cpp:573-577): each node's descriptor is made from its raw
+    polar sweep instead of the local map of peaks."""
     sc = scene or circle_scene()
     imgs = np.stack([sc.render(f, n_frames) for f in range(n_frames)])
     gt = np.stack([sc.pose_at(f, n_frames) for f in range(n_frames)])
@@ -98,12 +100,15 @@ def run(backend, n_frames=68, scene=None, log=None):
     rsc = backend.scan_context()
     cands = []
     for i in range(n_frames - 1):                                                # the closure thread trails the odometry by one node
+        if raw_scan_context:
+            rsc.makeAndSaveScancontextAndKeysRadarRaw(imgs[i], poses[i])
         merged = []
         for j in (i - 1, i, i + 1):                                              # ScansToLocalMap, N_aggregate = 1 (loopclosure.cpp:552-570)
             if 0 <= j < n_frames:
                 merged.append(transform_cloud(nodes[j]["peaks"], poses[j]))
         local = transform_cloud(np.concatenate(merged), xyt_inverse(poses[i]))
-        rsc.makeAndSaveScancontextAndKeysRadarCloud(local, poses[i])
+        if not raw_scan_context:
+            rsc.makeAndSaveScancontextAndKeysRadarCloud(local, poses[i])
         for c in rsc.detectLoopClosureID():
             to = c["nn_idx"]
             rel = [xyt_compose(xyt_inverse(poses[k]), poses[k + 1]) for k in range(to, i)]
@@ -126,8 +131,9 @@ def run(backend, n_frames=68, scene=None, log=None):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=68)
+    ap.add_argument("--raw-scan-context", action="store_true", help="Scan Context of the raw sweeps (TBV --raw_radar_scan)")
     a = ap.parse_args()
-    out = run(HipBackend(), a.frames, log=print)
+    out = run(HipBackend(), a.frames, log=print, raw_scan_context=a.raw_scan_context)
     acc = sum(r["accepted"] for r in out["results"])
     drift = np.abs(out["poses"][-1] - out["gt"][-1])
     print("%d candidates verified, %d loop constraints accepted; odometry drift after the lap: %.2f m" %

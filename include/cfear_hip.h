@@ -473,6 +473,31 @@ int cfear_sc_distance_batch(cfear_ctx* ctx, const double* desc_q, int32_t n_q, c
                             const int32_t* pairs, int32_t n_pairs, const cfear_sc_params* par, double* dist,
                             int32_t* shift);
 
+/* Raw-sweep Scan Context: RSCManager::MakeRadarContext (RadarScancontext.cpp:41-57), the descriptor TBV builds with
+ * --raw_radar_scan true (loopclosure.cpp:573-577): cv::threshold(THRESH_TOZERO) of the 8-bit sweep, then cv::resize to
+ * num_ring x num_sector with INTER_AREA, restated from OpenCV 4.2 (resize.cpp: computeResizeAreaTab + resizeArea_<uchar,
+ * float> in float without FMA, or resizeAreaFast_<uchar, int> when both scales are integers; cvRound half to even).
+ * Rings run along the image's rows, sectors along its columns, of the image the reader returns (PNGReaderInterface::Get
+ * transposes when rows < cols): transpose = 1 reads an azimuth-major sweep [azimuths][bins] (the filters' layout)
+ * transposed, transpose = 0 reads stored rows as rings.  The image is read only (the reference thresholds it in place).
+ * Refused with CFEAR_ERR_INVALID_ARGUMENT: normalize = 1 (cv::normalize runs in OpenCV's AVX2 FMA dispatch and cannot be
+ * restated exactly), interpolations other than CFEAR_SC_INTER_AREA, scales below 1, an integer 2 x 2 scale (OpenCV's SIMD
+ * and scalar code round it differently), a non-finite threshold.  TBV reaches none of them.                           */
+#define CFEAR_SC_INTER_AREA 3           /* cv::INTER_AREA */
+typedef struct cfear_sc_raw_params {
+  double radar_threshold;               /* 0: cvFloor(t); bins <= t become 0                                */
+  int32_t transpose;                    /* 1: the stored sweep is [azimuths][bins] (rings over its columns) */
+  int32_t normalize;                    /* must be 0                                                        */
+  int32_t interpolation;                /* must be CFEAR_SC_INTER_AREA                                      */
+  int32_t pad;
+} cfear_sc_raw_params;                  /* 24 bytes */
+void cfear_sc_raw_params_default(cfear_sc_raw_params* p);
+/* desc->batch sweeps (host or device, any stride and batch_stride) -> desc_out [batch][num_ring * num_sector] (host or
+ * device; (double) of the 8-bit cell), ringkey [batch][num_ring] and sectorkey [batch][num_sector] optional host arrays.
+ * Only num_ring / num_sector of par are read.                                                                        */
+int cfear_sc_raw_descriptors(cfear_ctx* ctx, const uint8_t* imgs, const cfear_polar_desc* desc, const cfear_sc_params* par,
+                             const cfear_sc_raw_params* raw, double* desc_out, double* ringkey, double* sectorkey);
+
 /* RSCManager as a library object (place_recognition_radar RadarScancontext.cpp:156-345): the descriptor database
  * lives in HBM; makeAndSaveScancontextAndKeysRadarCloud = add, detectLoopClosureID = detect.  Host policy (recent-node
  * exclusion, odometry likelihood, ring-key search, candidate ranking) runs in the library's C++.                    */
@@ -499,6 +524,11 @@ typedef struct cfear_sc_candidate {     /* RSCManager::candidate */
 int cfear_sc_manager_create(cfear_ctx* ctx, const cfear_sc_manager_params* par, cfear_sc_manager** out);
 /* cloud: the node's local map [n][4] in the node frame (host or device); Todom: the node's pose (x, y, theta). */
 int cfear_sc_manager_add(cfear_sc_manager* m, const float* xyzi, int32_t n_points, const double Todom[3]);
+/* makeAndSaveScancontextAndKeysRadarRaw (RadarScancontext.cpp:148-154): the node's descriptor from its raw sweep (one
+ * image, host or device, see cfear_sc_raw_descriptors); the node has no lateral augmentations whatever augment_sc says.
+ * Raw and cloud nodes may share one database.                                                                       */
+int cfear_sc_manager_add_raw(cfear_sc_manager* m, const uint8_t* img, const cfear_polar_desc* desc,
+                             const cfear_sc_raw_params* raw, const double Todom[3]);
 /* candidates for the node added last, closest first; *n_out <= n_candidates.                                   */
 int cfear_sc_manager_detect(cfear_sc_manager* m, cfear_sc_candidate* out, int32_t cap, int32_t* n_out);
 int cfear_sc_manager_size(const cfear_sc_manager* m);

@@ -777,6 +777,23 @@ class RSCManager {
     const double T[3] = {Todom.x, Todom.y, Todom.theta};
     ctx_.check(cfear_sc_manager_add(m_, cloud.empty() ? nullptr : &cloud[0].x, (int32_t)cloud.size(), T));
   }
+  // makeAndSaveScancontextAndKeysRadarRaw (:148-154): the node's raw 8-bit sweep, rows x cols with `stride` bytes per row (host
+  // or device).  raw == nullptr: TBV's settings, transposed when rows < cols as PNGReaderInterface::Get does (utils.cpp:4-19)
+  void makeAndSaveScancontextAndKeysRadarRaw(const uint8_t* image, int rows, int cols, int stride, const CFEAR_Radarodometry::Pose2d& Todom,
+                                             const cfear_sc_raw_params* raw = nullptr) {
+    cfear_sc_raw_params def;
+    if (!raw) { cfear_sc_raw_params_default(&def); def.transpose = rows < cols ? 1 : 0; raw = &def; }
+    const cfear_polar_desc d{rows, cols, stride, 1, (int64_t)rows * stride};
+    const double T[3] = {Todom.x, Todom.y, Todom.theta};
+    ctx_.check(cfear_sc_manager_add_raw(m_, image, &d, raw, T));
+  }
+#ifdef CFEAR_HIP_HAVE_CV_BRIDGE
+  // the reference's signature (RadarScancontext.h; loopclosure.cpp:573-577 passes the reader's CV_8U image); unlike the
+  // reference, the image is not thresholded in place
+  void makeAndSaveScancontextAndKeysRadarRaw(cv::Mat& scan_mat, const CFEAR_Radarodometry::Pose2d& Todom) {
+    makeAndSaveScancontextAndKeysRadarRaw(scan_mat.data, scan_mat.rows, scan_mat.cols, (int)scan_mat.step, Todom);
+  }
+#endif
   std::vector<cfear_sc_candidate> detectLoopClosureID() {                                             // :286-345
     std::vector<cfear_sc_candidate> out((size_t)std::max(n_candidates_, 1));
     int32_t n = 0;

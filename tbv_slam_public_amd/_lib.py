@@ -130,6 +130,14 @@ class ScCloud(C.Structure):
     _fields_ = [("xyzi", C.c_void_p), ("n", C.c_int32), ("pad", C.c_int32)]
 
 
+SC_INTER_AREA = 3                   # CFEAR_SC_INTER_AREA (cv::INTER_AREA)
+
+
+class ScRawParams(C.Structure):
+    _fields_ = [("radar_threshold", C.c_double), ("transpose", C.c_int32), ("normalize", C.c_int32),
+                ("interpolation", C.c_int32), ("pad", C.c_int32)]
+
+
 class ScManagerParams(C.Structure):
     _fields_ = [("sc", ScParams), ("num_candidates_from_tree", C.c_int32), ("n_candidates", C.c_int32),
                 ("odom_sigma_error", C.c_double), ("odometry_coupled_closure", C.c_int32), ("augment_sc", C.c_int32),
@@ -203,7 +211,8 @@ EXPORTS = [
     "cfear_coral_quality_batch", "cfear_sc_params_default", "cfear_sc_descriptors", "cfear_sc_distance_batch",
     "cfear_polar_rotate_ccw", "cfear_scan_closest_idx",
     "cfear_sc_manager_params_default", "cfear_sc_manager_create", "cfear_sc_manager_add", "cfear_sc_manager_detect",
-    "cfear_sc_manager_size", "cfear_sc_manager_destroy", "cfear_verify_params_default", "cfear_verify_loop_candidates", "cfear_verify_by_odometry", "cfear_verify_apply_constraints",
+    "cfear_sc_manager_size", "cfear_sc_manager_destroy", "cfear_sc_raw_params_default", "cfear_sc_raw_descriptors",
+    "cfear_sc_manager_add_raw", "cfear_verify_params_default", "cfear_verify_loop_candidates", "cfear_verify_by_odometry", "cfear_verify_apply_constraints",
     "cfear_cost_prepare", "cfear_cost_num_blocks", "cfear_cost_num_residuals", "cfear_cost_get_blocks",
     "cfear_cost_evaluate", "cfear_cost_normal_eq", "cfear_cost_destroy",
     "cfear_odometry_params_default", "cfear_odometry_params_preset", "cfear_odometry_create", "cfear_odometry_process",
@@ -341,6 +350,10 @@ def lib():
     L.cfear_sc_manager_create.argtypes = [vp, C.POINTER(ScManagerParams), C.POINTER(vp)]
     L.cfear_sc_manager_add.argtypes = [vp, vp, C.c_int32, C.POINTER(C.c_double)]
     L.cfear_sc_manager_detect.argtypes = [vp, vp, C.c_int32, C.POINTER(C.c_int32)]
+    L.cfear_sc_raw_params_default.argtypes = [C.POINTER(ScRawParams)]
+    L.cfear_sc_raw_params_default.restype = None
+    L.cfear_sc_raw_descriptors.argtypes = [vp, vp, C.POINTER(PolarDesc), C.POINTER(ScParams), C.POINTER(ScRawParams), vp, vp, vp]
+    L.cfear_sc_manager_add_raw.argtypes = [vp, vp, C.POINTER(PolarDesc), C.POINTER(ScRawParams), C.POINTER(C.c_double)]
     L.cfear_sc_manager_size.argtypes = [vp]
     L.cfear_sc_manager_destroy.argtypes = [vp]
     L.cfear_scan_closest_idx.argtypes = [vp, vp, C.c_int32, C.c_double, vp]

@@ -1115,6 +1115,72 @@ def sc_distance_batch(desc_q, desc_c, pairs, par=None, ctx=None):
     return dist, shift
 
 
+def sc_raw_params(**kw):
+    """cfear_sc_raw_params with TBV's values (radar_threshold 0, no normalisation, INTER_AREA, an azimuth-major
+    sweep read transposed); keyword overrides use the C field names (interpolation also takes "area")."""
+    p = L.ScRawParams()
+    L.lib().cfear_sc_raw_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k == "interpolation" and isinstance(v, str):
+            v = {"nearest_neighbor": 0, "bilinear": 1, "bicubic": 2, "area": L.SC_INTER_AREA}[v]
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _image_desc(img):
+    """PolarDesc of a uint8 [B, H, W] / [H, W] NumPy array or torch tensor whose rows are contiguous (any row and
+    batch stride) -> (desc, pointer, keep-alive)."""
+    if _is_torch(img):
+        assert img.dtype.is_floating_point is False and img.element_size() == 1, "uint8 images"
+        st = list(img.stride())
+        if st[-1] != 1:
+            img = img.contiguous()
+            st = list(img.stride())
+        ptr = img.data_ptr()
+    else:
+        if img.dtype != np.uint8:
+            raise TypeError("uint8 images")
+        if img.strides[-1] != 1:
+            img = np.ascontiguousarray(img)
+        st = list(img.strides)
+        ptr = img.ctypes.data
+    shape = tuple(img.shape)
+    d = L.PolarDesc()
+    d.rows, d.cols = shape[-2], shape[-1]
+    d.stride = st[-2]
+    d.batch = shape[0] if len(shape) == 3 else 1
+    d.batch_stride = st[0] if len(shape) == 3 else d.rows * d.stride
+    return d, ptr, img
+
+
+def sc_raw_descriptors(imgs, par=None, raw=None, ctx=None, device_out=False):
+    """MakeRadarContext (RadarScancontext.cpp:41-57) of raw polar sweeps: uint8 [B, H, W] or [H, W], NumPy (host) or torch
+    CUDA (device), rows contiguous.  -> (desc [B, R, S] float64, ringkey [B, R], sectorkey [B, S]; [R, S], [R], [S] for
+    one 2-D sweep).  raw defaults to TBV's settings with transpose = (H < W), the reader's rule (PNGReaderInterface::Get).
+    With device_out the descriptors stay in HBM (torch CUDA tensor); the keys always come back to the host."""
+    ctx = ctx or default_context()
+    par = par or sc_params()
+    if raw is None:
+        raw = sc_raw_params(transpose=int(imgs.shape[-2] < imgs.shape[-1]))
+    d, ptr, keep = _image_desc(imgs)
+    B, R, S = d.batch, par.num_ring, par.num_sector
+    if device_out:
+        import torch
+        desc = torch.zeros((B, R, S), dtype=torch.float64, device="cuda:%d" % ctx.device)
+    else:
+        desc = np.zeros((B, R, S), np.float64)
+    rk = np.zeros((B, R), np.float64)
+    sk = np.zeros((B, S), np.float64)
+    ctx.check(ctx._lib.cfear_sc_raw_descriptors(ctx.h, ptr, C.byref(d), C.byref(par), C.byref(raw), _ptr(desc)[0],
+                                                rk.ctypes.data, sk.ctypes.data))
+    del keep
+    if len(imgs.shape) == 2:
+        return desc[0], rk[0], sk[0]
+    return desc, rk, sk
+
+
 class RSCManager:
     """RSCManager (place_recognition_radar RadarScancontext.{h,cpp}) for cloud descriptors: the descriptor
     database, the recent-node exclusion, the odometry similarity and the candidate ranking are host policy
@@ -1124,9 +1190,10 @@ class RSCManager:
     AUGMENTS_Y = (-2.0, 2.0, -4.0, 4.0)               # RadarScancontext.cpp:164
 
     def __init__(self, par=None, num_candidates_from_tree=10, n_candidates=3, odom_sigma_error=0.05,
-                 odometry_coupled_closure=True, augment_sc=True, ctx=None):
+                 odometry_coupled_closure=True, augment_sc=True, ctx=None, raw_par=None):
         self.ctx = ctx
         self.par = par or sc_params()
+        self.raw_par = raw_par                        # cfear_sc_raw_params of the raw path; None: the reader's rule per image
         self.NUM_CANDIDATES_FROM_TREE = int(num_candidates_from_tree)
         self.N_candidates = int(n_candidates)
         self.odom_sigma_error = float(odom_sigma_error)
@@ -1145,6 +1212,18 @@ class RSCManager:
 
     def _distances(self, desc_q, desc_c, pairs):
         return sc_distance_batch(desc_q, desc_c, pairs, self.par, self.ctx)
+
+    def _raw_descriptor(self, img):
+        return sc_raw_descriptors(img, self.par, self.raw_par, self.ctx, device_out=True)
+
+    def makeAndSaveScancontextAndKeysRadarRaw(self, img, Todom):
+        """RadarScancontext.cpp:148-154 (+ :133-146, :181-222): the descriptor of the node's raw sweep [H, W]; the node
+        has no lateral augmentations, whatever augment_sc says."""
+        desc, rk, _ = self._raw_descriptor(img)
+        self.polarcontexts_.append(desc)
+        self.polarcontext_invkeys_mat_.append(rk.astype(np.float32))
+        self.current_and_augments_ = [(desc, rk.astype(np.float32), (0.0, 0.0, 0.0))]
+        self._exclude_and_update_likelihood(np.asarray(Todom, np.float64))
 
     def makeAndSaveScancontextAndKeysRadarCloud(self, cloud, Todom):
         """RadarScancontext.cpp:156-180 (+ :133-146, :181-225)."""
@@ -1279,8 +1358,9 @@ class RSCManagerNative:
     Same two calls as RSCManager; what a C++ host uses (include/cfear_hip.hpp)."""
 
     def __init__(self, par=None, num_candidates_from_tree=10, n_candidates=3, odom_sigma_error=0.05,
-                 odometry_coupled_closure=True, augment_sc=True, ctx=None):
+                 odometry_coupled_closure=True, augment_sc=True, ctx=None, raw_par=None):
         self.ctx = ctx or default_context()
+        self.raw_par = raw_par
         p = L.ScManagerParams()
         self.ctx._lib.cfear_sc_manager_params_default(C.byref(p))
         if par is not None:
@@ -1296,6 +1376,14 @@ class RSCManagerNative:
         ptr, n, _keep = _cloud_ptr(cloud)
         T = (C.c_double * 3)(*[float(v) for v in Todom])
         self.ctx.check(self.ctx._lib.cfear_sc_manager_add(self._h, ptr, n, T))
+
+    def makeAndSaveScancontextAndKeysRadarRaw(self, img, Todom):
+        if len(img.shape) != 2:
+            raise ValueError("one sweep [H, W]")
+        raw = self.raw_par if self.raw_par is not None else sc_raw_params(transpose=int(img.shape[0] < img.shape[1]))
+        d, ptr, _keep = _image_desc(img)
+        T = (C.c_double * 3)(*[float(v) for v in Todom])
+        self.ctx.check(self.ctx._lib.cfear_sc_manager_add_raw(self._h, ptr, C.byref(d), C.byref(raw), T))
 
     def detectLoopClosureID(self):
         out = np.zeros(max(int(self.par.n_candidates), 1), L.SC_CANDIDATE_DTYPE)

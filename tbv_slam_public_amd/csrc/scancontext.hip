@@ -17,6 +17,8 @@
 //   40 x 120); one thread per column / per shift, every inner sum sequential in the reference's order, so
 //   distances and argmin shifts are bit-identical with the CPU restatement.
 #include <algorithm>
+#include <cfloat>
+#include <climits>
 #include <cmath>
 #include <vector>
 
@@ -29,6 +31,7 @@ constexpr int kScDistThreads = 1024;     // one distance workgroup per CU (two d
 constexpr int kScMaxAug = 8;
 
 struct ScCloud { const float4* xyzi; int32_t n; int32_t pad; };
+typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 
 struct ScDescArgs {
   const ScCloud* clouds;
@@ -49,6 +52,21 @@ __device__ __forceinline__ float sc_xy2theta(float x, float y) {
   if ((x < 0) & (y < 0)) return (float)(180 + ((180 / M_PI) * atan_f(y / x)));
   if ((x >= 0) & (y < 0)) return (float)(360 - ((180 / M_PI) * atan_f((-y) / x)));
   return 0;
+}
+
+// makeRingkeyFromScancontext / makeSectorkeyFromScancontext (Scancontext.cpp:239-268) of one descriptor d [R][S], by the
+// whole workgroup
+__device__ __forceinline__ void sc_keys(const double* d, int R, int S, double* rk, double* sk) {
+  for (int r = threadIdx.x; r < R; r += blockDim.x) {  // row means, sequential like Eigen's row.mean() restatement
+    double s = 0;
+    for (int c = 0; c < S; c++) s += d[r * S + c];
+    rk[r] = s / S;
+  }
+  for (int c = threadIdx.x; c < S; c += blockDim.x) {
+    double s = 0;
+    for (int r = 0; r < R; r++) s += d[r * S + c];
+    sk[c] = s / R;
+  }
 }
 
 __global__ __launch_bounds__(256) void sc_descriptor_kernel(const ScDescArgs a) {
@@ -99,18 +117,8 @@ __global__ __launch_bounds__(256) void sc_descriptor_kernel(const ScDescArgs a) 
     out[i] = d;
   }
   __syncthreads();
-  double* rk = a.ringkey + ((size_t)blockIdx.x * a.n_aug + blockIdx.y) * R;
-  double* sk = a.sectorkey + ((size_t)blockIdx.x * a.n_aug + blockIdx.y) * S;
-  for (int r = threadIdx.x; r < R; r += blockDim.x) {  // row means, sequential like Eigen's row.mean() restatement
-    double s = 0;
-    for (int c = 0; c < S; c++) s += acc[r * S + c];
-    rk[r] = s / S;
-  }
-  for (int c = threadIdx.x; c < S; c += blockDim.x) {
-    double s = 0;
-    for (int r = 0; r < R; r++) s += acc[r * S + c];
-    sk[c] = s / R;
-  }
+  sc_keys(acc, R, S, a.ringkey + ((size_t)blockIdx.x * a.n_aug + blockIdx.y) * R,
+          a.sectorkey + ((size_t)blockIdx.x * a.n_aug + blockIdx.y) * S);
 }
 
 struct ScDistArgs {
@@ -217,6 +225,179 @@ __global__ __launch_bounds__(1024) void sc_distance_kernel(const ScDistArgs a) {
   if (threadIdx.x == 0) { a.dist[blockIdx.x] = best; a.shift[blockIdx.x] = best_shift; }
 }
 
+// ---- raw-sweep Scan Context: RSCManager::MakeRadarContext (RadarScancontext.cpp:41-57) ------------------------------
+// cv::threshold(THRESH_TOZERO) of the 8-bit sweep + cv::resize(INTER_AREA) to num_ring x num_sector, as OpenCV 4.2 computes
+// them (DESIGN.md section "raw-sweep Scan Context"; restated from OpenCV's imgproc sources, NOT pinned against OpenCV here):
+//  * threshold (thresh.cpp, 8U): t = cvFloor(radar_threshold); v is kept where v > t, else 0 (t < 0 keeps all, t >= 255
+//    clears all).  The reference thresholds the caller's image in place; this reads it only.
+//  * the logical image L [H][W] is the reader's (PNGReaderInterface::Get transposes when rows < cols): rings run along H,
+//    sectors along W.  transpose = 1: the stored sweep is azimuth-major, L[y][x] = stored[x][y]; transpose = 0: L = stored.
+//  * scale = 1 / ((double)dsize / ssize) per axis.  Both integer (|scale - cvRound(scale)| < DBL_EPSILON): resizeAreaFast_
+//    <uchar, int>, integer box sum, cvRound((float)sum * (1.f / area)); 2 x 2 is refused (OpenCV's SIMD body rounds it
+//    (s + 2) >> 2, its scalar tail half to even).  Otherwise, both >= 1: computeResizeAreaTab + resizeArea_<uchar, float>:
+//    per source row sy (y-table order) buf[dx] = sum of (float)L[sy][sx] * alpha over the x-table entries of dx in order,
+//    then sum[dx] = beta * buf[dx] (first row of the output row) or sum[dx] += beta * buf[dx]; every product and sum a
+//    separate float operation (no FMA); result saturate_cast<uchar> = cvRound, half to even.  Scales below 1 are refused.
+//  * desc = (double)u8; desc_divider / no_point do not apply; keys as sc_keys.  normalize = true and interpolations other
+//    than INTER_AREA are refused: TBV cannot reach them, and cv::normalize's convertTo runs in OpenCV's AVX2 FMA dispatch,
+//    which a restatement cannot follow exactly.
+// sc_raw_descriptor_kernel: one workgroup per (sweep, block of NS sectors).  Stage 1 forms buf[dx][y] for the block's sectors
+// and every y into LDS: the source rows x the block touches are walked in ascending x, each row adding into the (at most two)
+// sectors it belongs to, so every sector sees its x-table entries in table order, and a row two sectors share is read once.
+// transpose = 1: a lane owns 16 consecutive y (one 16-byte load per row, up to kScRawRows rows in flight); transpose = 0: a
+// lane owns one y and reads the row's bytes.  Stage 2: one lane per (sector, ring) sums the ring's y-table entries from LDS in
+// ascending order.
+constexpr int kScRawRows = 8;            // source rows loaded together per lane (transpose = 1)
+constexpr int kScRawMaxH = 16384;        // ring-axis source length: NS = 1 needs H * 4 bytes of LDS
+constexpr int kScRawLdsBudget = 32 * 1024;
+
+struct ScRawArgs {
+  const uint8_t* img;
+  int rows, cols, stride, thr;           // stored layout; thr = cvFloor(radar_threshold) clamped to [-1, 255]
+  long long batch_stride;
+  int H, W, R, S, nblk, Hp, fast;        // logical image H x W -> R x S; nblk sector blocks per sweep; LDS pitch (floats)
+  float inv_area;                        // fast path: 1.f / (iscale_x * iscale_y)
+  const int4* rowtab;                    // [W] per source x: (dx, alpha bits, dx', alpha' bits), dx' = -1 if none
+  const int2* xspan;                     // [S] first / last source x of sector dx
+  const int* yoff;                       // [R + 1] y-table entries of ring dy: [yoff[dy], yoff[dy + 1])
+  const int2* yent;                      // (sy, beta bits)
+  double* desc;                          // [batch][R * S]
+};
+
+__device__ __forceinline__ float sc_raw_val(uint32_t byte, int thr) { return (int)byte > thr ? (float)byte : 0.0f; }
+
+// one source row's contribution: acc[k] += v * alpha for each sector dx0 + k of the block the row belongs to (table entry
+// t, see ScRawArgs::rowtab); no FMA: the order and rounding of resizeArea_
+template <int NS, int N>
+__device__ __forceinline__ void sc_raw_row(float (&acc)[NS][N], const float (&v)[N], const int4 t, int dx0) {
+#pragma unroll
+  for (int k = 0; k < NS; k++) {
+    const int dx = dx0 + k;
+    if (t.x == dx || t.z == dx) {
+      const float alpha = __int_as_float(t.x == dx ? t.y : t.w);
+#pragma unroll
+      for (int j = 0; j < N; j++) acc[k][j] = __fadd_rn(acc[k][j], __fmul_rn(v[j], alpha));
+    }
+  }
+}
+
+// 16 bytes of a row from `pos` into w, zeros past n.  The piece is read whole (one 16-byte load) where the row starts on a
+// 4-byte boundary and the piece ends inside the image (room = bytes from the row start to the image's end); the bytes past n
+// are then cleared in registers.  Otherwise only bytes < n are read, one by one.
+__device__ __forceinline__ void sc_raw_piece(const uint8_t* rowp, int pos, int n, long long room, uint32_t (&w)[4]) {
+  if ((((uintptr_t)rowp) & 3) == 0 && (long long)pos + 16 <= room) {
+    const u32x4_a4 v = __builtin_nontemporal_load((const u32x4_a4*)(rowp + pos));
+    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    if (pos + 16 > n) {
+#pragma unroll
+      for (int d = 0; d < 4; d++) {
+        const int rem = n - (pos + 4 * d);
+        w[d] &= rem >= 4 ? 0xffffffffu : (rem <= 0 ? 0u : ((1u << (8 * rem)) - 1u));
+      }
+    }
+  } else {
+#pragma unroll
+    for (int d = 0; d < 4; d++) {
+      uint32_t word = 0;
+#pragma unroll
+      for (int by = 0; by < 4; by++) {
+        const int p = pos + 4 * d + by;
+        if (p < n) word |= (uint32_t)rowp[p] << (8 * by);
+      }
+      w[d] = word;
+    }
+  }
+}
+
+template <int NS, int TRANSPOSE>
+__global__ __launch_bounds__(256) void sc_raw_descriptor_kernel(const ScRawArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  float* buf = (float*)smem;                                   // [NS][Hp]
+  const int blk = blockIdx.x % a.nblk, b = blockIdx.x / a.nblk;
+  const int dx0 = blk * NS, ns = min(NS, a.S - dx0);
+  const int xr0 = a.xspan[dx0].x, xr1 = a.xspan[dx0 + ns - 1].y;
+  const uint8_t* img = a.img + (long long)b * a.batch_stride;
+  const long long img_end = (long long)(a.rows - 1) * a.stride + a.cols;
+  if (TRANSPOSE) {
+    // stored rows are x (azimuths), contiguous along y
+    const int npieces = (a.H + 15) / 16;
+    for (int p = threadIdx.x; p < npieces; p += blockDim.x) {
+      float acc[NS][16];
+#pragma unroll
+      for (int k = 0; k < NS; k++)
+#pragma unroll
+        for (int j = 0; j < 16; j++) acc[k][j] = 0.0f;
+      for (int x0 = xr0; x0 <= xr1; x0 += kScRawRows) {
+        uint32_t w[kScRawRows][4];
+#pragma unroll
+        for (int r = 0; r < kScRawRows; r++) {
+          const int x = x0 + r;
+          if (x <= xr1) {
+            const long long off = (long long)x * a.stride;
+            sc_raw_piece(img + off, p * 16, a.H, img_end - off, w[r]);
+          }
+        }
+#pragma unroll
+        for (int r = 0; r < kScRawRows; r++) {
+          const int x = x0 + r;
+          if (x <= xr1) {
+            float v[16];
+#pragma unroll
+            for (int j = 0; j < 16; j++) v[j] = sc_raw_val((w[r][j >> 2] >> (8 * (j & 3))) & 0xffu, a.thr);
+            sc_raw_row<NS, 16>(acc, v, a.rowtab[x], dx0);
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < NS; k++)
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+          *(float4*)(buf + k * a.Hp + p * 16 + 4 * q) = make_float4(acc[k][4 * q], acc[k][4 * q + 1], acc[k][4 * q + 2], acc[k][4 * q + 3]);
+    }
+  } else {
+    // stored rows are y, contiguous along x
+    for (int y = threadIdx.x; y < a.H; y += blockDim.x) {
+      float acc[NS][1];
+#pragma unroll
+      for (int k = 0; k < NS; k++) acc[k][0] = 0.0f;
+      const uint8_t* rowp = img + (long long)y * a.stride;
+      for (int x = xr0; x <= xr1; x++) {
+        const float v[1] = {sc_raw_val(rowp[x], a.thr)};
+        sc_raw_row<NS, 1>(acc, v, a.rowtab[x], dx0);
+      }
+#pragma unroll
+      for (int k = 0; k < NS; k++) buf[k * a.Hp + y] = acc[k][0];
+    }
+  }
+  __syncthreads();
+  double* out = a.desc + (size_t)b * a.R * a.S;
+  for (int t = threadIdx.x; t < ns * a.R; t += blockDim.x) {
+    const int k = t / a.R, dy = t - k * a.R;
+    const float* bk = buf + k * a.Hp;
+    const int e0 = a.yoff[dy], e1 = a.yoff[dy + 1];
+    float v;
+    if (a.fast) {                                              // resizeAreaFast_: integer box sum (buf holds integers)
+      int s = 0;
+      for (int e = e0; e < e1; e++) s += (int)bk[a.yent[e].x];
+      v = __fmul_rn((float)s, a.inv_area);
+    } else {
+      const int2 f = a.yent[e0];
+      v = __fmul_rn(__int_as_float(f.y), bk[f.x]);
+      for (int e = e0 + 1; e < e1; e++) {
+        const int2 g = a.yent[e];
+        v = __fadd_rn(v, __fmul_rn(__int_as_float(g.y), bk[g.x]));
+      }
+    }
+    const int u = min(max(__float2int_rn(v), 0), 255);        // saturate_cast<uchar>(float): cvRound, half to even
+    out[(size_t)dy * a.S + dx0 + k] = (double)u;
+  }
+}
+
+__global__ __launch_bounds__(256) void sc_raw_keys_kernel(const double* desc, int R, int S, double* ringkey, double* sectorkey) {
+  const size_t b = blockIdx.x;
+  sc_keys(desc + b * R * S, R, S, ringkey + b * R, sectorkey + b * S);
+}
+
 int check_sc_params(cfear_ctx* ctx, const cfear_sc_params* p) {
   if (!p) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null parameters");
   if (p->num_ring < 1 || p->num_sector < 1 || (long long)p->num_ring * p->num_sector > kScMaxCells)
@@ -320,6 +501,149 @@ extern "C" int cfear_sc_distance_batch(cfear_ctx* ctx, const double* desc_q, int
   return st.finish();
 }
 
+extern "C" void cfear_sc_raw_params_default(cfear_sc_raw_params* p) {
+  if (!p) return;
+  p->radar_threshold = 0.0;                        // RadarScancontext.h:36
+  p->transpose = 1;                                // an azimuth-major sweep, read as PNGReaderInterface::Get returns it
+  p->normalize = 0;                                // :45
+  p->interpolation = CFEAR_SC_INTER_AREA;          // "area" (:46)
+  p->pad = 0;
+}
+
+namespace {
+// computeResizeAreaTab (OpenCV imgproc/src/resize.cpp) for one axis: entries (output index, source index, weight) in order
+void sc_area_tab(int ssize, int dsize, std::vector<int>& di, std::vector<int>& si, std::vector<float>& alpha) {
+  const double scale = 1. / ((double)dsize / ssize);
+  for (int d = 0; d < dsize; d++) {
+    const double fs1 = d * scale, fs2 = fs1 + scale, cell = std::min(scale, ssize - fs1);
+    int s1 = (int)std::ceil(fs1), s2 = (int)std::floor(fs2);
+    s2 = std::min(s2, ssize - 1);
+    s1 = std::min(s1, s2);
+    if (s1 - fs1 > 1e-3) { di.push_back(d); si.push_back(s1 - 1); alpha.push_back((float)((s1 - fs1) / cell)); }
+    for (int s = s1; s < s2; s++) { di.push_back(d); si.push_back(s); alpha.push_back((float)(1.0 / cell)); }
+    if (fs2 - s2 > 1e-3) { di.push_back(d); si.push_back(s2); alpha.push_back((float)(std::min(std::min(fs2 - s2, 1.), cell) / cell)); }
+  }
+}
+
+int float_bits(float f) { int i; memcpy(&i, &f, 4); return i; }
+
+template <int NS>
+void sc_raw_launch(const ScRawArgs& a, int transpose, int batch, size_t lds, hipStream_t s) {
+  if (transpose) hipLaunchKernelGGL((sc_raw_descriptor_kernel<NS, 1>), dim3(a.nblk * batch), dim3(256), lds, s, a);
+  else hipLaunchKernelGGL((sc_raw_descriptor_kernel<NS, 0>), dim3(a.nblk * batch), dim3(256), lds, s, a);
+}
+}  // namespace
+
+extern "C" int cfear_sc_raw_descriptors(cfear_ctx* ctx, const uint8_t* imgs, const cfear_polar_desc* desc,
+                                        const cfear_sc_params* par, const cfear_sc_raw_params* raw, double* out,
+                                        double* ringkey, double* sectorkey) {
+  if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
+  if (!imgs || !desc || !par || !raw || !out) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
+  if (raw->normalize)
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "raw scan context: normalize = true is not supported");
+  if (raw->interpolation != CFEAR_SC_INTER_AREA)
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "raw scan context: only INTER_AREA interpolation is supported");
+  if (raw->transpose != 0 && raw->transpose != 1)
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "raw scan context: transpose must be 0 or 1");
+  if (!(raw->radar_threshold >= -2147483648.0 && raw->radar_threshold < 2147483648.0))
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "raw scan context: radar_threshold must be finite and fit an int");
+  const int R = par->num_ring, S = par->num_sector;
+  if (R < 1 || S < 1 || (long long)R * S > kScMaxCells)
+    return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "num_ring x num_sector must be in [1, %d]", kScMaxCells);
+  const cfear_polar_desc& d = *desc;
+  if (d.rows <= 0 || d.cols <= 0 || d.stride < d.cols || d.batch < 0 || (d.batch > 1 && d.batch_stride < (int64_t)d.rows * d.stride))
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "bad polar descriptor");
+  const int H = raw->transpose ? d.cols : d.rows, W = raw->transpose ? d.rows : d.cols;
+  if (H > kScRawMaxH) return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "raw scan context: %d source rings > %d", H, kScRawMaxH);
+  const double scale_x = 1. / ((double)S / W), scale_y = 1. / ((double)R / H);
+  if (scale_x < 1 || scale_y < 1)
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "raw scan context: a %d x %d image cannot be area-downscaled to %d x %d",
+                           H, W, R, S);
+  const int isx = (int)std::nearbyint(scale_x), isy = (int)std::nearbyint(scale_y);
+  const bool fast = std::abs(scale_x - isx) < DBL_EPSILON && std::abs(scale_y - isy) < DBL_EPSILON;
+  if (fast && isx == 2 && isy == 2)
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "raw scan context: INTER_AREA at exactly 2 x 2 is not supported");
+  if (d.batch == 0) return CFEAR_OK;
+  // tables: per source x its (at most two) sectors, per sector its source span, per ring its y entries
+  std::vector<int> xd, xs, yd, ys;
+  std::vector<float> xa, ya;
+  if (fast) {
+    for (int x = 0; x < W; x++) { xd.push_back(x / isx); xs.push_back(x); xa.push_back(1.0f); }
+    for (int y = 0; y < H; y++) { yd.push_back(y / isy); ys.push_back(y); ya.push_back(1.0f); }
+  } else {
+    sc_area_tab(W, S, xd, xs, xa);
+    sc_area_tab(H, R, yd, ys, ya);
+  }
+  const size_t ny = ys.size();
+  const size_t o_span = (size_t)W * 16, o_yoff = o_span + (size_t)S * 8, o_yent = (o_yoff + (size_t)(R + 1) * 4 + 7) & ~(size_t)7;
+  const size_t tab_bytes = o_yent + ny * 8;
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  HostStage st(ctx, kWsCoral);
+  const uint8_t* d_img;
+  const cfear_polar_desc dd = st.images(d_img, imgs, d);
+  ScRawArgs a;
+  char* d_tab;
+  st.piece(d_tab, tab_bytes);
+  st.out(a.desc, out, (size_t)d.batch * R * S * sizeof(double));
+  double* d_keys = nullptr;
+  if (ringkey || sectorkey) st.piece(d_keys, (size_t)d.batch * (R + S) * sizeof(double));
+  char* h = (char*)st.record(tab_bytes);
+  int4* rowtab = (int4*)h;
+  int2* span = (int2*)(h + o_span);
+  int* yoff = (int*)(h + o_yoff);
+  int2* yent = (int2*)(h + o_yent);
+  for (int x = 0; x < W; x++) rowtab[x] = make_int4(-1, 0, -1, 0);
+  for (int s = 0; s < S; s++) span[s] = make_int2(INT32_MAX, -1);
+  for (size_t e = 0; e < xs.size(); e++) {
+    int4& t = rowtab[xs[e]];
+    if (t.x < 0) { t.x = xd[e]; t.y = float_bits(xa[e]); }
+    else if (t.z < 0) { t.z = xd[e]; t.w = float_bits(xa[e]); }
+    else return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "raw scan context: source column %d in more than two sectors", xs[e]);
+    span[xd[e]].x = std::min(span[xd[e]].x, xs[e]);
+    span[xd[e]].y = std::max(span[xd[e]].y, xs[e]);
+  }
+  for (int s = 0; s < S; s++)
+    if (span[s].y < 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "raw scan context: sector %d is empty", s);
+  for (int r = 0; r <= R; r++) yoff[r] = 0;
+  for (size_t e = 0; e < ny; e++) { yoff[yd[e] + 1]++; yent[e] = make_int2(ys[e], float_bits(ya[e])); }
+  for (int r = 0; r < R; r++) {
+    if (yoff[r + 1] == 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "raw scan context: ring %d is empty", r);
+    yoff[r + 1] += yoff[r];
+  }
+  CFEAR_CHECK(st.carve());
+  CFEAR_CHECK(st.upload(d_tab, h, tab_bytes));
+  a.img = d_img;
+  a.rows = dd.rows; a.cols = dd.cols; a.stride = dd.stride;
+  a.batch_stride = dd.batch > 1 ? dd.batch_stride : 0;
+  a.thr = (int)std::max(-1.0, std::min(255.0, std::floor(raw->radar_threshold)));
+  a.H = H; a.W = W; a.R = R; a.S = S; a.fast = fast ? 1 : 0;
+  a.inv_area = 1.f / (float)(fast ? isx * isy : 1);
+  a.rowtab = (const int4*)d_tab; a.xspan = (const int2*)(d_tab + o_span);
+  a.yoff = (const int*)(d_tab + o_yoff); a.yent = (const int2*)(d_tab + o_yent);
+  a.Hp = (H + 15) / 16 * 16;
+  const int ns = (size_t)4 * a.Hp * 4 <= (size_t)kScRawLdsBudget && S >= 4 ? 4 : ((size_t)2 * a.Hp * 4 <= (size_t)kScRawLdsBudget && S >= 2 ? 2 : 1);
+  a.nblk = (S + ns - 1) / ns;
+  const size_t lds = (size_t)ns * a.Hp * 4;
+  if ((long long)a.nblk * d.batch > INT32_MAX) return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "raw scan context: batch too large");
+  {
+    ProfScope ps(ctx, "sc_raw_descriptor");
+    if (ns == 4) sc_raw_launch<4>(a, raw->transpose, d.batch, lds, ctx->stream);
+    else if (ns == 2) sc_raw_launch<2>(a, raw->transpose, d.batch, lds, ctx->stream);
+    else sc_raw_launch<1>(a, raw->transpose, d.batch, lds, ctx->stream);
+  }
+  CFEAR_HIP_CHECK(ctx, hipGetLastError());
+  if (d_keys) {
+    {
+      ProfScope ps(ctx, "sc_raw_keys");
+      hipLaunchKernelGGL(sc_raw_keys_kernel, dim3(d.batch), dim3(256), 0, ctx->stream, a.desc, R, S, d_keys, d_keys + (size_t)d.batch * R);
+    }
+    CFEAR_HIP_CHECK(ctx, hipGetLastError());
+    if (ringkey) st.back(ringkey, d_keys, (size_t)d.batch * R * sizeof(double));
+    if (sectorkey) st.back(sectorkey, d_keys + (size_t)d.batch * R, (size_t)d.batch * S * sizeof(double));
+  }
+  return st.finish();
+}
+
 // ---- RSCManager: descriptor database + retrieval policy (host) around the two kernels ----------------------
 // Restates RSCManager::makeAndSaveScancontextAndKeysRadarCloud (RadarScancontext.cpp:156-180), the recent-node
 // exclusion and odometry likelihood (:181-222), OdometryNNSearch / the ring-key KNN (:225-284) and
@@ -333,6 +657,7 @@ struct cfear_sc_manager {
   int cap = 0, n = 0;
   double* d_cur = nullptr;       // [n_aug][cells] current node and its augmentations
   int n_aug = 1;
+  int cur_aug = 1;               // entries of current_and_augments_: n_aug after add, 1 after add_raw (RadarScancontext.cpp:133-146)
   std::vector<std::vector<float>> ringkeys;          // polarcontext_invkeys_mat_
   std::vector<std::vector<float>> cur_keys;          // ring keys of current_and_augments_
   std::vector<double> shifts;                        // lateral shift of every augmentation (Taug = (0, shift, 0))
@@ -392,15 +717,12 @@ extern "C" int cfear_sc_manager_destroy(cfear_sc_manager* m) {
 
 extern "C" int cfear_sc_manager_size(const cfear_sc_manager* m) { return m ? m->n : CFEAR_ERR_INVALID_ARGUMENT; }
 
-extern "C" int cfear_sc_manager_add(cfear_sc_manager* m, const float* xyzi, int32_t n_points, const double Todom[3]) {
-  if (!m || !Todom || n_points < 0 || (n_points > 0 && !xyzi)) return CFEAR_ERR_INVALID_ARGUMENT;
+namespace {
+// makeAndSaveScancontextAndKeys (RadarScancontext.cpp:133-146) + ExcludeAndUpdateLikelihood (:181-222) for the descriptors
+// just written to d_cur: d_cur[0] joins the database, the n_cur entries of d_cur (ring keys rk) become current_and_augments_
+int sc_manager_commit(cfear_sc_manager* m, const std::vector<double>& rk, int n_cur, const double Todom[3]) {
   cfear_ctx* ctx = m->ctx;
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const int R = m->par.sc.num_ring;
-  cfear_sc_cloud cloud{xyzi, n_points, 0};
-  std::vector<double> rk((size_t)m->n_aug * R);
-  int rc = cfear_sc_descriptors(ctx, &cloud, 1, &m->par.sc, m->shifts.data(), m->n_aug, m->d_cur, rk.data(), nullptr);
-  if (rc != CFEAR_OK) return rc;
   if (m->n == m->cap) {                                      // grow the database (device to device)
     const int ncap = std::max(256, m->cap * 2);
     double* nd = nullptr;
@@ -416,8 +738,9 @@ extern "C" int cfear_sc_manager_add(cfear_sc_manager* m, const float* xyzi, int3
   CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(m->d_db + (size_t)m->n * m->cells, m->d_cur, (size_t)m->cells * sizeof(double),
                                       hipMemcpyDeviceToDevice, ctx->stream));
   m->n++;
-  m->cur_keys.assign(m->n_aug, std::vector<float>(R));
-  for (int k = 0; k < m->n_aug; k++)
+  m->cur_aug = n_cur;
+  m->cur_keys.assign(n_cur, std::vector<float>(R));
+  for (int k = 0; k < n_cur; k++)
     for (int r = 0; r < R; r++) m->cur_keys[k][r] = (float)rk[(size_t)k * R + r];      // eig2stdvec: double -> float
   m->ringkeys.push_back(m->cur_keys[0]);
   // ExcludeAndUpdateLikelihood (:181-222)
@@ -451,6 +774,32 @@ extern "C" int cfear_sc_manager_add(cfear_sc_manager* m, const float* xyzi, int3
   }
   return CFEAR_OK;
 }
+}  // namespace
+
+extern "C" int cfear_sc_manager_add(cfear_sc_manager* m, const float* xyzi, int32_t n_points, const double Todom[3]) {
+  if (!m || !Todom || n_points < 0 || (n_points > 0 && !xyzi)) return CFEAR_ERR_INVALID_ARGUMENT;
+  cfear_ctx* ctx = m->ctx;
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const int R = m->par.sc.num_ring;
+  cfear_sc_cloud cloud{xyzi, n_points, 0};
+  std::vector<double> rk((size_t)m->n_aug * R);
+  int rc = cfear_sc_descriptors(ctx, &cloud, 1, &m->par.sc, m->shifts.data(), m->n_aug, m->d_cur, rk.data(), nullptr);
+  if (rc != CFEAR_OK) return rc;
+  return sc_manager_commit(m, rk, m->n_aug, Todom);
+}
+
+// makeAndSaveScancontextAndKeysRadarRaw (RadarScancontext.cpp:148-154): the node's raw sweep, no lateral augmentations
+extern "C" int cfear_sc_manager_add_raw(cfear_sc_manager* m, const uint8_t* img, const cfear_polar_desc* desc,
+                                        const cfear_sc_raw_params* raw, const double Todom[3]) {
+  if (!m || !Todom || !img || !desc || !raw) return CFEAR_ERR_INVALID_ARGUMENT;
+  cfear_ctx* ctx = m->ctx;
+  if (desc->batch != 1) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "add_raw takes one sweep (batch = 1)");
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  std::vector<double> rk((size_t)m->par.sc.num_ring);
+  const int rc = cfear_sc_raw_descriptors(ctx, img, desc, &m->par.sc, raw, m->d_cur, rk.data(), nullptr);
+  if (rc != CFEAR_OK) return rc;
+  return sc_manager_commit(m, rk, 1, Todom);
+}
 
 extern "C" int cfear_sc_manager_detect(cfear_sc_manager* m, cfear_sc_candidate* out, int32_t cap, int32_t* n_out) {
   if (!m || !n_out || cap < 0 || (cap > 0 && !out)) return CFEAR_ERR_INVALID_ARGUMENT;
@@ -460,7 +809,7 @@ extern "C" int cfear_sc_manager_detect(cfear_sc_manager* m, cfear_sc_candidate* 
   const int R = m->par.sc.num_ring;
   const int cur = m->n - 1;
   std::vector<int32_t> pairs;                                                 // (augmentation, candidate) in visiting order
-  for (int k = 0; k < m->n_aug; k++) {
+  for (int k = 0; k < m->cur_aug; k++) {
     const std::vector<float>& key = m->cur_keys[k];
     std::vector<std::pair<float, int>> cands;
     if (m->par.odometry_coupled_closure) {                                    // OdometryNNSearch (:259-284)
@@ -510,7 +859,7 @@ extern "C" int cfear_sc_manager_detect(cfear_sc_manager* m, cfear_sc_candidate* 
   if (np == 0) return CFEAR_OK;
   std::vector<double> dist(np);
   std::vector<int32_t> shift(np);
-  const int rc = cfear_sc_distance_batch(ctx, m->d_cur, m->n_aug, m->d_db, m->n, pairs.data(), np, &m->par.sc, dist.data(),
+  const int rc = cfear_sc_distance_batch(ctx, m->d_cur, m->cur_aug, m->d_db, m->n, pairs.data(), np, &m->par.sc, dist.data(),
                                          shift.data());
   if (rc != CFEAR_OK) return rc;
   const double unit = 360.0 / (double)m->par.sc.num_sector;
