@@ -9,7 +9,7 @@
 The sensor drives a closed circle, so the last nodes revisit the first ones: the demo prints the loop constraints the
 verifier accepts and how far their registered transforms are from the ground truth.  `run(backend)` is shared with
 tests/test_gpu_tbv_loop.py, which runs it a second time with the CPU oracle behind the same host logic.
-    python examples/loop_closure_demo.py [--frames 68] [--raw-scan-context]"""
+    python examples/loop_closure_demo.py [--frames 68] [--raw-scan-context | --batched-scan-context]"""
 import argparse
 import os
 import sys
@@ -87,10 +87,12 @@ class HipBackend:
                      reg_ok=bool(r["reg_ok"][i]), alignment_quality=float(r["alignment_quality"][i])) for i in range(len(cands))]
 
 
-def run(backend, n_frames=68, scene=None, log=None, raw_scan_context=False):
+def run(backend, n_frames=68, scene=None, log=None, raw_scan_context=False, batched_scan_context=False):
     """-> dict(poses, gt, candidates [dict], results [dict]) ; candidates[i] / results[i] belong together.
     raw_scan_context: TBV's --raw_radar_scan true (loopclosure.cpp:573-577): each node's descriptor is made from its raw
-    polar sweep instead of the local map of peaks."""
+    polar sweep instead of the local map of peaks.
+    batched_scan_context: the offline form (tbv_slam_offline): every node's candidates come from one whole-graph call
+    (api.sc_detect_sequence, local maps merged on the GPU) before the loop; the candidates are the same."""
     sc = scene or circle_scene()
     imgs = np.stack([sc.render(f, n_frames) for f in range(n_frames)])
     gt = np.stack([sc.pose_at(f, n_frames) for f in range(n_frames)])
@@ -98,18 +100,25 @@ def run(backend, n_frames=68, scene=None, log=None, raw_scan_context=False):
     # graph nodes: every frame is a keyframe here (2.5 m between sweeps > 1.5 m)
     poses, nodes = backend.sequence(imgs)
     rsc = backend.scan_context()
+    batched = None
+    if batched_scan_context:
+        batched = backend.api.sc_detect_sequence([nd["peaks"] for nd in nodes], poses, n_aggregate=1, n_detect=n_frames - 1)
     cands = []
     for i in range(n_frames - 1):                                                # the closure thread trails the odometry by one node
-        if raw_scan_context:
+        if batched is not None:
+            found = batched[i]
+        elif raw_scan_context:
             rsc.makeAndSaveScancontextAndKeysRadarRaw(imgs[i], poses[i])
-        merged = []
-        for j in (i - 1, i, i + 1):                                              # ScansToLocalMap, N_aggregate = 1 (loopclosure.cpp:552-570)
-            if 0 <= j < n_frames:
-                merged.append(transform_cloud(nodes[j]["peaks"], poses[j]))
-        local = transform_cloud(np.concatenate(merged), xyt_inverse(poses[i]))
-        if not raw_scan_context:
-            rsc.makeAndSaveScancontextAndKeysRadarCloud(local, poses[i])
-        for c in rsc.detectLoopClosureID():
+        if batched is None:
+            merged = []
+            for j in (i - 1, i, i + 1):                                          # ScansToLocalMap, N_aggregate = 1 (loopclosure.cpp:552-570)
+                if 0 <= j < n_frames:
+                    merged.append(transform_cloud(nodes[j]["peaks"], poses[j]))
+            local = transform_cloud(np.concatenate(merged), xyt_inverse(poses[i]))
+            if not raw_scan_context:
+                rsc.makeAndSaveScancontextAndKeysRadarCloud(local, poses[i])
+            found = rsc.detectLoopClosureID()
+        for c in found:
             to = c["nn_idx"]
             rel = [xyt_compose(xyt_inverse(poses[k]), poses[k + 1]) for k in range(to, i)]
             # Tsrcguess = Taug^-1 * Rz(sc yaw) (loopclosure.cpp:693-697)
@@ -132,8 +141,12 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=68)
     ap.add_argument("--raw-scan-context", action="store_true", help="Scan Context of the raw sweeps (TBV --raw_radar_scan)")
+    ap.add_argument("--batched-scan-context", action="store_true",
+                    help="propose every node's candidates with one whole-graph call before verifying (offline mode)")
     a = ap.parse_args()
-    out = run(HipBackend(), a.frames, log=print, raw_scan_context=a.raw_scan_context)
+    if a.raw_scan_context and a.batched_scan_context:
+        ap.error("--batched-scan-context covers the local-map (cloud) mode only")
+    out = run(HipBackend(), a.frames, log=print, raw_scan_context=a.raw_scan_context, batched_scan_context=a.batched_scan_context)
     acc = sum(r["accepted"] for r in out["results"])
     drift = np.abs(out["poses"][-1] - out["gt"][-1])
     print("%d candidates verified, %d loop constraints accepted; odometry drift after the lap: %.2f m" %

@@ -84,9 +84,11 @@ int cfear_ctx_get_stream(const cfear_ctx* ctx, void** hip_stream);
  *                            the correspondence arrays (which only unusually large registrations reach otherwise).
  *   CFEAR_OPT_MATCHER_WAVES  0 (default): wavefronts per registration chosen by the batch; 2, 4, 8, 16 force a form.
  *   CFEAR_OPT_HOST_TIMELINE  1: the batched odometry prints where the host spends a frame (every 256 calls).
+ *   CFEAR_OPT_SC_QUERY_CHUNK 0 (default): cfear_sc_detect_sequence sizes its query chunks by a device budget; n >= 1:
+ *                            at most n query nodes per chunk, so that small graphs cross chunk boundaries.
  * Returns CFEAR_ERR_INVALID_ARGUMENT for an unknown option or a value outside its range.                          */
 enum cfear_option { CFEAR_OPT_FUSED_DECODE = 0, CFEAR_OPT_MATCHER_LDS_KB = 1, CFEAR_OPT_MATCHER_WAVES = 2,
-                    CFEAR_OPT_HOST_TIMELINE = 3, CFEAR_OPT_COUNT = 4 };
+                    CFEAR_OPT_HOST_TIMELINE = 3, CFEAR_OPT_SC_QUERY_CHUNK = 4, CFEAR_OPT_COUNT = 5 };
 int cfear_ctx_set_option(cfear_ctx* ctx, int32_t option, int64_t value);
 int cfear_ctx_get_option(const cfear_ctx* ctx, int32_t option, int64_t* value);
 /* Per-kernel-family device time measured with hipEvents on the context's stream.
@@ -533,6 +535,33 @@ int cfear_sc_manager_add_raw(cfear_sc_manager* m, const uint8_t* img, const cfea
 int cfear_sc_manager_detect(cfear_sc_manager* m, cfear_sc_candidate* out, int32_t cap, int32_t* n_out);
 int cfear_sc_manager_size(const cfear_sc_manager* m);
 int cfear_sc_manager_destroy(cfear_sc_manager* m);
+
+/* Whole-graph Scan Context in cloud mode (ScanContextClosure: CreateContext, loopclosure.cpp:571-591, then
+ * detectLoopClosureID) for a graph known before the first detection (tbv_slam_offline).  A node carries its cloud in its
+ * own frame (peaks or not, as use_peaks chooses) and rows 0 and 1 of its 4 x 4 node -> world matrix and of the inverse,
+ * as the caller computed them (GetPose().matrix(), GetPose().inverse().matrix()).  The local map of node i
+ * (ScansToLocalMap, loopclosure.cpp:553-569) merges the nodes whose id lies in [id_i - n_aggregate, id_i + n_aggregate]:
+ * every point goes to the world frame and back into node i's frame with pcl::transformPointCloud's arithmetic (double
+ * products summed left to right, ((m0 x + m1 y) + m2 z) + m3, rounded to float); z and the intensity are carried.        */
+typedef struct cfear_sc_node {
+  cfear_sc_cloud cloud;                 /* [n][4] in the node frame, host or device                              */
+  double T[8];                          /* node -> world, rows 0 and 1 of the 4 x 4 matrix                       */
+  double Tinv[8];                       /* world -> node                                                         */
+  int32_t id, pad;                      /* idx_ of the node; strictly increasing                                 */
+} cfear_sc_node;                        /* 152 bytes */
+/* MakeRadarCloudContext of the local maps of nodes centers[0 .. n_centers) (indices into nodes), with the lateral shifts
+ * of cfear_sc_descriptors: bit-identical to cfear_sc_descriptors of the host-merged clouds.  desc [n_centers][n_aug]
+ * [num_ring * num_sector], ringkey [..][num_ring] and sectorkey [..][num_sector] (optional): host or device.            */
+int cfear_sc_local_map_descriptors(cfear_ctx* ctx, const cfear_sc_node* nodes, int32_t n_nodes, const int32_t* centers,
+                                   int32_t n_centers, int32_t n_aggregate, const cfear_sc_params* par, const double* shifts_y,
+                                   int32_t n_aug, double* desc, double* ringkey, double* sectorkey);
+/* The candidates a streaming cfear_sc_manager returns when nodes 0 .. n_detect - 1 are added in order, each with its local
+ * map and Todom = (T[3], T[7]), and each is detected right after it is added (n_detect <= n_nodes; nodes past n_detect only
+ * join local maps).  out [n_detect][par->n_candidates] and n_out [n_detect] are host arrays.  The odometry similarity is
+ * evaluated on the device: its hypot / exp may differ from the host's libm in the last place.
+ * Refused with CFEAR_ERR_CAPACITY: num_candidates_from_tree > 64.                                                      */
+int cfear_sc_detect_sequence(cfear_ctx* ctx, const cfear_sc_manager_params* par, const cfear_sc_node* nodes, int32_t n_nodes,
+                             int32_t n_aggregate, int32_t n_detect, cfear_sc_candidate* out, int32_t* n_out);
 
 /* ---- caller: loop-candidate verification --------------------------------------------------------------
  * What the loop-closure thread does per candidate (tbv_slam/src/tbv_slam/loopclosure.cpp:658-725), for a batch:

@@ -9,6 +9,7 @@
 #pragma once
 #include <cstdint>
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <ctime>
 #include <iostream>
@@ -806,6 +807,49 @@ class RSCManager {
   cfear_sc_manager* m_ = nullptr;
   int n_candidates_ = 3;
 };
+
+// Whole-graph Scan Context (cfear_sc_detect_sequence): ScanContextClosure's candidates for nodes 0 .. n_detect - 1 in one
+// call, as RSCManager returns them node by node (tbv_slam_offline knows the graph before the first detection).  Each node
+// gives its cloud in its own frame (peaks or not, as use_peaks chooses), rows 0 and 1 of its node -> world matrix and of the
+// inverse (ScNodeRows(GetPose().matrix()), ScNodeRows(GetPose().inverse().matrix())), and its id.
+typedef std::array<double, 8> ScNodeRows8;
+template <class Matrix4>
+inline ScNodeRows8 ScNodeRows(const Matrix4& m) {
+  return ScNodeRows8{{m(0, 0), m(0, 1), m(0, 2), m(0, 3), m(1, 0), m(1, 1), m(1, 2), m(1, 3)}};
+}
+inline std::vector<cfear_sc_node> ScNodes(const std::vector<const CFEAR_Radarodometry::PointCloud*>& clouds,
+                                          const std::vector<ScNodeRows8>& T, const std::vector<ScNodeRows8>& Tinv,
+                                          const std::vector<int>& ids) {
+  if (T.size() != clouds.size() || Tinv.size() != clouds.size() || ids.size() != clouds.size())
+    throw CFEAR_Radarodometry::CfearError(CFEAR_ERR_INVALID_ARGUMENT, "one matrix pair and one id per cloud");
+  std::vector<cfear_sc_node> nodes(clouds.size());
+  for (size_t i = 0; i < clouds.size(); i++) {
+    cfear_sc_node& n = nodes[i];
+    n = cfear_sc_node{};
+    n.cloud.xyzi = clouds[i]->empty() ? nullptr : &(*clouds[i])[0].x;
+    n.cloud.n = (int32_t)clouds[i]->size();
+    for (int j = 0; j < 8; j++) { n.T[j] = T[i][j]; n.Tinv[j] = Tinv[i][j]; }
+    n.id = ids[i];
+  }
+  return nodes;
+}
+// -> candidates of every detected node, closest first
+inline std::vector<std::vector<cfear_sc_candidate>> DetectLoopClosureSequence(
+    CFEAR_Radarodometry::Context& ctx, const std::vector<const CFEAR_Radarodometry::PointCloud*>& clouds,
+    const std::vector<ScNodeRows8>& T, const std::vector<ScNodeRows8>& Tinv, const std::vector<int>& ids, int n_aggregate,
+    int n_detect, const cfear_sc_manager_params* par = nullptr) {
+  cfear_sc_manager_params def;
+  if (!par) { cfear_sc_manager_params_default(&def); par = &def; }
+  const std::vector<cfear_sc_node> nodes = ScNodes(clouds, T, Tinv, ids);
+  const int nc = std::max(par->n_candidates, 1);
+  std::vector<cfear_sc_candidate> out((size_t)std::max(n_detect, 1) * nc);
+  std::vector<int32_t> n_out((size_t)std::max(n_detect, 1));
+  ctx.check(cfear_sc_detect_sequence(ctx.get(), par, nodes.data(), (int32_t)nodes.size(), n_aggregate, n_detect, out.data(),
+                                     n_out.data()));
+  std::vector<std::vector<cfear_sc_candidate>> res((size_t)std::max(n_detect, 0));
+  for (size_t i = 0; i < res.size(); i++) res[i].assign(out.begin() + i * nc, out.begin() + i * nc + n_out[i]);
+  return res;
+}
 
 // Loop-candidate verification of tbv_slam::loopclosure (tbv_slam/src/tbv_slam/loopclosure.cpp:320-384, 261-274,
 // 776-808) for a batch of candidates.

@@ -144,6 +144,10 @@ class ScManagerParams(C.Structure):
                 ("distance_exclude_recent", C.c_double), ("pad", C.c_int64)]
 
 
+class ScNode(C.Structure):         # cfear_sc_node
+    _fields_ = [("cloud", ScCloud), ("T", C.c_double * 8), ("Tinv", C.c_double * 8), ("id", C.c_int32), ("pad", C.c_int32)]
+
+
 SC_CANDIDATE_DTYPE = np.dtype([("min_dist", "<f8"), ("min_dist_sc", "<f8"), ("min_dist_odom", "<f8"),
                                ("yaw_diff_rad", "<f4"), ("nn_idx", "<i4"), ("argmin_shift", "<i4"), ("pad", "<i4"),
                                ("Taug", "<f8", (3,))])
@@ -212,7 +216,8 @@ EXPORTS = [
     "cfear_polar_rotate_ccw", "cfear_scan_closest_idx",
     "cfear_sc_manager_params_default", "cfear_sc_manager_create", "cfear_sc_manager_add", "cfear_sc_manager_detect",
     "cfear_sc_manager_size", "cfear_sc_manager_destroy", "cfear_sc_raw_params_default", "cfear_sc_raw_descriptors",
-    "cfear_sc_manager_add_raw", "cfear_verify_params_default", "cfear_verify_loop_candidates", "cfear_verify_by_odometry", "cfear_verify_apply_constraints",
+    "cfear_sc_manager_add_raw", "cfear_sc_local_map_descriptors", "cfear_sc_detect_sequence",
+    "cfear_verify_params_default", "cfear_verify_loop_candidates", "cfear_verify_by_odometry", "cfear_verify_apply_constraints",
     "cfear_cost_prepare", "cfear_cost_num_blocks", "cfear_cost_num_residuals", "cfear_cost_get_blocks",
     "cfear_cost_evaluate", "cfear_cost_normal_eq", "cfear_cost_destroy",
     "cfear_odometry_params_default", "cfear_odometry_params_preset", "cfear_odometry_create", "cfear_odometry_process",
@@ -238,7 +243,7 @@ class RcclComm(C.Structure):        # cfear_rccl_comm
 
 
 # enum cfear_option (include/cfear_hip.h): test / measurement hooks of a context
-OPT_FUSED_DECODE, OPT_MATCHER_LDS_KB, OPT_MATCHER_WAVES, OPT_HOST_TIMELINE, OPT_COUNT = 0, 1, 2, 3, 4
+OPT_FUSED_DECODE, OPT_MATCHER_LDS_KB, OPT_MATCHER_WAVES, OPT_HOST_TIMELINE, OPT_SC_QUERY_CHUNK, OPT_COUNT = 0, 1, 2, 3, 4, 5
 
 
 class PgoParams(C.Structure):
@@ -354,6 +359,10 @@ def lib():
     L.cfear_sc_raw_params_default.restype = None
     L.cfear_sc_raw_descriptors.argtypes = [vp, vp, C.POINTER(PolarDesc), C.POINTER(ScParams), C.POINTER(ScRawParams), vp, vp, vp]
     L.cfear_sc_manager_add_raw.argtypes = [vp, vp, C.POINTER(PolarDesc), C.POINTER(ScRawParams), C.POINTER(C.c_double)]
+    L.cfear_sc_local_map_descriptors.argtypes = [vp, C.POINTER(ScNode), C.c_int32, vp, C.c_int32, C.c_int32, C.POINTER(ScParams),
+                                                 C.POINTER(C.c_double), C.c_int32, vp, vp, vp]
+    L.cfear_sc_detect_sequence.argtypes = [vp, C.POINTER(ScManagerParams), C.POINTER(ScNode), C.c_int32, C.c_int32, C.c_int32,
+                                           vp, vp]
     L.cfear_sc_manager_size.argtypes = [vp]
     L.cfear_sc_manager_destroy.argtypes = [vp]
     L.cfear_scan_closest_idx.argtypes = [vp, vp, C.c_int32, C.c_double, vp]

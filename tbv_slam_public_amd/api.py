@@ -1353,6 +1353,120 @@ class RSCManager:
         return similar
 
 
+def sc_manager_params(par=None, num_candidates_from_tree=10, n_candidates=3, odom_sigma_error=0.05,
+                      odometry_coupled_closure=True, augment_sc=True):
+    """cfear_sc_manager_params: TBV's defaults with RSCManager's keyword overrides (par: cfear_sc_params)."""
+    p = L.ScManagerParams()
+    L.lib().cfear_sc_manager_params_default(C.byref(p))
+    if par is not None:
+        p.sc = par
+    p.num_candidates_from_tree, p.n_candidates = int(num_candidates_from_tree), int(n_candidates)
+    p.odom_sigma_error = float(odom_sigma_error)
+    p.odometry_coupled_closure, p.augment_sc = int(odometry_coupled_closure), int(augment_sc)
+    return p
+
+
+def _sc_candidates(rows):
+    """cfear_sc_candidate records -> RSCManager's candidate dicts, closest first."""
+    return [dict(min_dist=float(c["min_dist"]), min_dist_sc=float(c["min_dist_sc"]), min_dist_odom=float(c["min_dist_odom"]),
+                 yaw_diff_rad=float(c["yaw_diff_rad"]), nn_idx=int(c["nn_idx"]), argmin_shift=int(c["argmin_shift"]),
+                 Taug=tuple(float(v) for v in c["Taug"])) for c in rows]
+
+
+def sc_node_affines(poses_xyt):
+    """Rows 0 and 1 of every node's node -> world matrix and of its inverse, built from (x, y, theta) the way
+    examples/loop_closure_demo.py does (transform_cloud of the pose, and of xyt_inverse of the pose): scalar cos / sin
+    calls, the inverse's angle negated.  -> (T [n, 8], Tinv [n, 8]) float64, the rows of cfear_sc_node."""
+    P = np.asarray(poses_xyt, np.float64).reshape(-1, 3)
+    T = np.zeros((P.shape[0], 8))
+    Ti = np.zeros((P.shape[0], 8))
+    for i, a in enumerate(P):
+        c, s = np.cos(a[2]), np.sin(a[2])
+        T[i] = (c, -s, 0.0, a[0], s, c, 0.0, a[1])
+        inv = np.array([-(c * a[0] + s * a[1]), s * a[0] - c * a[1], -a[2]])       # xyt_inverse
+        ci, si = np.cos(inv[2]), np.sin(inv[2])
+        Ti[i] = (ci, -si, 0.0, inv[0], si, ci, 0.0, inv[1])
+    return T, Ti
+
+
+def _sc_nodes(clouds, poses_xyt, affines, ids):
+    """cfear_sc_node array of clouds (float32 [n, 4] NumPy or torch CUDA) with their matrices -> (array, keep-alive)."""
+    T, Ti = affines if affines is not None else sc_node_affines(poses_xyt)
+    n = len(clouds)
+    if len(T) != n or len(Ti) != n or (ids is not None and len(ids) != n):
+        raise ValueError("one pose (or matrix pair) and one id per cloud")
+    arr = (L.ScNode * max(n, 1))()
+    keep = []
+    for i, c in enumerate(clouds):
+        ptr, m, k = _cloud_ptr(c)
+        keep.append(k)
+        arr[i].cloud.xyzi, arr[i].cloud.n = ptr, m
+        arr[i].T[:] = [float(v) for v in T[i]]
+        arr[i].Tinv[:] = [float(v) for v in Ti[i]]
+        arr[i].id = int(ids[i]) if ids is not None else i
+    return arr, keep
+
+
+def sc_local_map_descriptors(clouds, poses_xyt=None, n_aggregate=1, centers=None, par=None, shifts_y=(0.0,), ids=None,
+                             affines=None, ctx=None, device_out=False):
+    """ScansToLocalMap + MakeRadarCloudContext (loopclosure.cpp:553-591) of the local maps of `centers` (node indices;
+    default every node): each node's cloud is in its own frame, merged with the nodes whose id lies within n_aggregate of
+    the centre's, on the GPU.  Poses (x, y, theta) or affines = (T, Tinv) [n, 8]; ids default to 0 .. n - 1.
+    -> (desc [nc, A, R, S], ringkey [nc, A, R], sectorkey [nc, A, S]), as sc_descriptors of the merged clouds."""
+    ctx = ctx or default_context()
+    par = par or sc_params()
+    arr, keep = _sc_nodes(clouds, poses_xyt, affines, ids)
+    ctr = np.ascontiguousarray(np.arange(len(clouds)) if centers is None else centers, dtype=np.int32)
+    nc, A, R, S = ctr.shape[0], len(shifts_y), par.num_ring, par.num_sector
+    if device_out:
+        import torch
+        desc = torch.zeros((nc, A, R, S), dtype=torch.float64, device="cuda:%d" % ctx.device)
+    else:
+        desc = np.zeros((nc, A, R, S), np.float64)
+    rk = np.zeros((nc, A, R), np.float64)
+    sk = np.zeros((nc, A, S), np.float64)
+    sh = (C.c_double * A)(*[float(v) for v in shifts_y])
+    ctx.check(ctx._lib.cfear_sc_local_map_descriptors(ctx.h, arr, len(clouds), ctr.ctypes.data, nc, int(n_aggregate), C.byref(par),
+                                                      sh, A, _ptr(desc)[0], rk.ctypes.data, sk.ctypes.data))
+    del keep
+    return desc, rk, sk
+
+
+def _sc_upload_clouds(clouds, ctx):
+    """Host clouds of a whole graph in one host-to-device copy (one torch CUDA tensor, viewed per node): the C-ABI would
+    stage every host cloud with a copy of its own.  -> (clouds, keep-alive)."""
+    if not clouds or not all(isinstance(c, np.ndarray) for c in clouds):
+        return clouds, None
+    import torch
+    flat = np.concatenate([np.ascontiguousarray(c, np.float32).reshape(-1, 4) for c in clouds])
+    dev = torch.from_numpy(flat).to("cuda:%d" % ctx.device)
+    torch.cuda.current_stream(dev.device).synchronize()             # the library enqueues on its own stream
+    off = np.concatenate([[0], np.cumsum([c.shape[0] for c in clouds])])
+    return [dev[off[i]:off[i + 1]] for i in range(len(clouds))], dev
+
+
+def sc_detect_sequence(clouds, poses_xyt=None, n_aggregate=1, n_detect=None, ids=None, affines=None, par=None, ctx=None,
+                       upload_clouds=True, **manager_kw):
+    """Scan Context candidate proposal for a whole graph in one call (cfear_sc_detect_sequence): what RSCManagerNative
+    returns when nodes 0 .. n_detect - 1 (default: every node) are added in order with their local maps (n_aggregate) and
+    poses, each detected right after it is added.  Clouds: float32 [n, 4] NumPy (uploaded together unless upload_clouds is
+    False) or torch CUDA.  manager_kw: RSCManagerNative's keywords (num_candidates_from_tree, n_candidates,
+    odom_sigma_error, odometry_coupled_closure, augment_sc).  -> one list of candidate dicts per node."""
+    ctx = ctx or default_context()
+    p = sc_manager_params(par, **manager_kw)
+    if upload_clouds:
+        clouds, _dev = _sc_upload_clouds(clouds, ctx)
+    arr, keep = _sc_nodes(clouds, poses_xyt, affines, ids)
+    n = len(clouds)
+    nd = n if n_detect is None else int(n_detect)
+    out = np.zeros((max(nd, 1), max(int(p.n_candidates), 1)), L.SC_CANDIDATE_DTYPE)
+    n_out = np.zeros(max(nd, 1), np.int32)
+    ctx.check(ctx._lib.cfear_sc_detect_sequence(ctx.h, C.byref(p), arr, n, int(n_aggregate), nd, out.ctypes.data,
+                                                n_out.ctypes.data))
+    del keep
+    return [_sc_candidates(out[i, :n_out[i]]) for i in range(nd)]
+
+
 class RSCManagerNative:
     """The same manager as a library object (cfear_sc_manager_*): database in HBM, policy in the library's C++.
     Same two calls as RSCManager; what a C++ host uses (include/cfear_hip.hpp)."""
@@ -1361,13 +1475,7 @@ class RSCManagerNative:
                  odometry_coupled_closure=True, augment_sc=True, ctx=None, raw_par=None):
         self.ctx = ctx or default_context()
         self.raw_par = raw_par
-        p = L.ScManagerParams()
-        self.ctx._lib.cfear_sc_manager_params_default(C.byref(p))
-        if par is not None:
-            p.sc = par
-        p.num_candidates_from_tree, p.n_candidates = int(num_candidates_from_tree), int(n_candidates)
-        p.odom_sigma_error = float(odom_sigma_error)
-        p.odometry_coupled_closure, p.augment_sc = int(odometry_coupled_closure), int(augment_sc)
+        p = sc_manager_params(par, num_candidates_from_tree, n_candidates, odom_sigma_error, odometry_coupled_closure, augment_sc)
         self.par = p
         self._h = C.c_void_p()
         self.ctx.check(self.ctx._lib.cfear_sc_manager_create(self.ctx.h, C.byref(p), C.byref(self._h)))
@@ -1389,9 +1497,7 @@ class RSCManagerNative:
         out = np.zeros(max(int(self.par.n_candidates), 1), L.SC_CANDIDATE_DTYPE)
         n = C.c_int32()
         self.ctx.check(self.ctx._lib.cfear_sc_manager_detect(self._h, out.ctypes.data, out.shape[0], C.byref(n)))
-        return [dict(min_dist=float(c["min_dist"]), min_dist_sc=float(c["min_dist_sc"]), min_dist_odom=float(c["min_dist_odom"]),
-                     yaw_diff_rad=float(c["yaw_diff_rad"]), nn_idx=int(c["nn_idx"]), argmin_shift=int(c["argmin_shift"]),
-                     Taug=tuple(float(v) for v in c["Taug"])) for c in out[:n.value]]
+        return _sc_candidates(out[:n.value])
 
     def size(self):
         return self.ctx._lib.cfear_sc_manager_size(self._h)

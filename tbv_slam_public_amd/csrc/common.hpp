@@ -42,6 +42,7 @@ enum WsSlot : int {
   kWsKstrongCand = 12,    // fused k-strongest candidate lists
   kWsCandResults = 13,    // cfear_register_candidates: results for a host caller
   kWsVerify = 14,         // the verification chain's records and results
+  kWsScSequence = 15,     // whole-graph Scan Context: node tables, descriptor database, query chunks
 };
 
 struct cfear_ctx {

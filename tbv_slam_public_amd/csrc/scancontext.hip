@@ -55,13 +55,14 @@ __device__ __forceinline__ float sc_xy2theta(float x, float y) {
 }
 
 // makeRingkeyFromScancontext / makeSectorkeyFromScancontext (Scancontext.cpp:239-268) of one descriptor d [R][S], by the
-// whole workgroup
+// whole workgroup; sk may be null
 __device__ __forceinline__ void sc_keys(const double* d, int R, int S, double* rk, double* sk) {
   for (int r = threadIdx.x; r < R; r += blockDim.x) {  // row means, sequential like Eigen's row.mean() restatement
     double s = 0;
     for (int c = 0; c < S; c++) s += d[r * S + c];
     rk[r] = s / S;
   }
+  if (!sk) return;
   for (int c = threadIdx.x; c < S; c += blockDim.x) {
     double s = 0;
     for (int r = 0; r < R; r++) s += d[r * S + c];
@@ -69,56 +70,263 @@ __device__ __forceinline__ void sc_keys(const double* d, int R, int S, double* r
   }
 }
 
+// The LDS accumulator of one descriptor, shared by sc_descriptor_kernel and sc_local_map_kernel: acc [cells] fp64 sums,
+// hit [cells] hit counts (sum) or the order-preserving int image of the float maximum (max).
+struct ScBin {
+  int num_ring, num_sector, desc_function;
+  double max_radius, desc_divider, no_point;
+};
+
+__device__ __forceinline__ void sc_acc_clear(double* acc, int* hit, const ScBin& b) {
+  const int cells = b.num_ring * b.num_sector;
+  for (int i = threadIdx.x; i < cells; i += blockDim.x) { acc[i] = 0.0; hit[i] = b.desc_function == 0 ? 0 : (int)0x80000000; }
+}
+
+// one point: the lateral augmentation, then the ceil-indexed polar binning (MakeRadarCloudContext)
+__device__ __forceinline__ void sc_acc_point(double* acc, int* hit, const float4 p, double shift_y, const ScBin& b) {
+  const int R = b.num_ring, S = b.num_sector;
+  float px = p.x, py = p.y;
+  if (shift_y != 0.0) {                              // pcl::transformPointCloud with an identity rotation (:163-170)
+    px = (float)(((1.0 * (double)p.x + 0.0 * (double)p.y) + 0.0 * (double)p.z) + 0.0);
+    py = (float)(((0.0 * (double)p.x + 1.0 * (double)p.y) + 0.0 * (double)p.z) + shift_y);
+  }
+  const float azim_range = sqrtf(__fadd_rn(__fmul_rn(px, px), __fmul_rn(py, py)));
+  const float azim_angle = sc_xy2theta(px, py);
+  if ((double)azim_range > b.max_radius) return;
+  const double rr = ceil(((double)azim_range / b.max_radius) * R), ss = ceil(((double)azim_angle / 360.0) * S);
+  const int ring_idx = max(min(R, rr == rr ? (int)rr : 1), 1);
+  const int sctor_idx = max(min(S, ss == ss ? (int)ss : 1), 1);
+  const int cell = (ring_idx - 1) * S + (sctor_idx - 1);
+  if (b.desc_function == 0) {
+    atomicAdd(&acc[cell], (double)p.w);
+    atomicAdd(&hit[cell], 1);
+  } else {                                           // max: order-preserving int image of the float intensity
+    int u = __float_as_int(p.w);
+    u = u >= 0 ? u : (u ^ 0x7fffffff);
+    atomicMax(&hit[cell], u);
+  }
+}
+
+// the finished descriptor, into acc (for the keys) and out
+__device__ __forceinline__ void sc_acc_finish(double* acc, const int* hit, const ScBin& b, double* out) {
+  const int cells = b.num_ring * b.num_sector;
+  const int NO_POINT = -1000;
+  for (int i = threadIdx.x; i < cells; i += blockDim.x) {
+    double d;
+    if (b.desc_function == 0) d = hit[i] > 0 ? acc[i] : (double)NO_POINT;
+    else {
+      const int u = hit[i];
+      d = u == (int)0x80000000 ? (double)NO_POINT : (double)__int_as_float(u >= 0 ? u : (u ^ 0x7fffffff));
+    }
+    d = d / b.desc_divider;                          // "Divison before no_point check" (:113)
+    if (d == NO_POINT) d = b.no_point;
+    acc[i] = d;
+    out[i] = d;
+  }
+}
+
 __global__ __launch_bounds__(256) void sc_descriptor_kernel(const ScDescArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const ScBin b{a.num_ring, a.num_sector, a.desc_function, a.max_radius, a.desc_divider, a.no_point};
   const int R = a.num_ring, S = a.num_sector, cells = R * S;
   double* acc = (double*)smem;                       // [cells] sum
   int* hit = (int*)(acc + cells);                    // [cells] count (sum) / float-ordered max (max)
   const ScCloud cl = a.clouds[blockIdx.x];
   const double shift_y = a.shift_y[blockIdx.y];
-  for (int i = threadIdx.x; i < cells; i += blockDim.x) { acc[i] = 0.0; hit[i] = a.desc_function == 0 ? 0 : (int)0x80000000; }
+  sc_acc_clear(acc, hit, b);
   __syncthreads();
-  for (int k = threadIdx.x; k < cl.n; k += blockDim.x) {
-    const float4 p = cl.xyzi[k];
-    float px = p.x, py = p.y;
-    if (shift_y != 0.0) {                            // pcl::transformPointCloud with an identity rotation (:163-170)
-      px = (float)(((1.0 * (double)p.x + 0.0 * (double)p.y) + 0.0 * (double)p.z) + 0.0);
-      py = (float)(((0.0 * (double)p.x + 1.0 * (double)p.y) + 0.0 * (double)p.z) + shift_y);
-    }
-    const float azim_range = sqrtf(__fadd_rn(__fmul_rn(px, px), __fmul_rn(py, py)));
-    const float azim_angle = sc_xy2theta(px, py);
-    if ((double)azim_range > a.max_radius) continue;
-    const double rr = ceil(((double)azim_range / a.max_radius) * R), ss = ceil(((double)azim_angle / 360.0) * S);
-    const int ring_idx = max(min(R, rr == rr ? (int)rr : 1), 1);
-    const int sctor_idx = max(min(S, ss == ss ? (int)ss : 1), 1);
-    const int cell = (ring_idx - 1) * S + (sctor_idx - 1);
-    if (a.desc_function == 0) {
-      atomicAdd(&acc[cell], (double)p.w);
-      atomicAdd(&hit[cell], 1);
-    } else {                                         // max: order-preserving int image of the float intensity
-      int u = __float_as_int(p.w);
-      u = u >= 0 ? u : (u ^ 0x7fffffff);
-      atomicMax(&hit[cell], u);
-    }
-  }
+  for (int k = threadIdx.x; k < cl.n; k += blockDim.x) sc_acc_point(acc, hit, cl.xyzi[k], shift_y, b);
   __syncthreads();
-  const int NO_POINT = -1000;
-  double* out = a.desc + ((size_t)blockIdx.x * a.n_aug + blockIdx.y) * cells;
-  for (int i = threadIdx.x; i < cells; i += blockDim.x) {
-    double d;
-    if (a.desc_function == 0) d = hit[i] > 0 ? acc[i] : (double)NO_POINT;
-    else {
-      const int u = hit[i];
-      d = u == (int)0x80000000 ? (double)NO_POINT : (double)__int_as_float(u >= 0 ? u : (u ^ 0x7fffffff));
-    }
-    d = d / a.desc_divider;                          // "Divison before no_point check" (:113)
-    if (d == NO_POINT) d = a.no_point;
-    acc[i] = d;
-    out[i] = d;
-  }
+  sc_acc_finish(acc, hit, b, a.desc + ((size_t)blockIdx.x * a.n_aug + blockIdx.y) * cells);
   __syncthreads();
   sc_keys(acc, R, S, a.ringkey + ((size_t)blockIdx.x * a.n_aug + blockIdx.y) * R,
           a.sectorkey + ((size_t)blockIdx.x * a.n_aug + blockIdx.y) * S);
+}
+
+// ---- whole-graph Scan Context ------------------------------------------------------------------
+// sc_local_map_kernel: one workgroup per (centre node, augmentation).  ScansToLocalMap (loopclosure.cpp:553-569) + the
+// descriptor: every point of every member node goes to the world frame and back into the centre's frame with
+// pcl::transformPointCloud's arithmetic (double products, summed left to right, rounded to float; z and the intensity are
+// carried), then into the same LDS accumulator as sc_descriptor_kernel.
+struct ScMapNode {
+  const float4* xyzi;
+  int32_t n, pad;
+  double T[8], Tinv[8];              // rows 0 and 1 of node -> world and world -> node
+};
+
+struct ScMapArgs {
+  const ScMapNode* nodes;
+  const int32_t* center;             // [n_centers] node index
+  const int2* members;               // [n_centers] first / last member node index
+  ScBin bin;
+  int n_aug;
+  double shift_y[kScMaxAug];
+  double* desc;                      // [n_centers][n_aug][R * S]
+  double* db;                        // optional: augmentation 0 also to db [n_centers][R * S]
+  double* ringkey;                   // [n_centers][n_aug][R]
+  double* sectorkey;                 // optional [n_centers][n_aug][S]
+};
+
+__device__ __forceinline__ float sc_affine_row(const double* m, float x, float y, float z) {
+  return (float)(((m[0] * (double)x + m[1] * (double)y) + m[2] * (double)z) + m[3]);
+}
+
+__global__ __launch_bounds__(256) void sc_local_map_kernel(const ScMapArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const int R = a.bin.num_ring, S = a.bin.num_sector, cells = R * S;
+  double* acc = (double*)smem;
+  int* hit = (int*)(acc + cells);
+  const int c = blockIdx.x, k = blockIdx.y;
+  const double* Ti = a.nodes[a.center[c]].Tinv;
+  const double shift_y = a.shift_y[k];
+  const int2 mem = a.members[c];
+  sc_acc_clear(acc, hit, a.bin);
+  __syncthreads();
+  for (int j = mem.x; j <= mem.y; j++) {
+    const ScMapNode& m = a.nodes[j];
+    for (int i = threadIdx.x; i < m.n; i += blockDim.x) {
+      const float4 p = m.xyzi[i];
+      const float wx = sc_affine_row(m.T, p.x, p.y, p.z), wy = sc_affine_row(m.T + 4, p.x, p.y, p.z);
+      const float4 q = make_float4(sc_affine_row(Ti, wx, wy, p.z), sc_affine_row(Ti + 4, wx, wy, p.z), p.z, p.w);
+      sc_acc_point(acc, hit, q, shift_y, a.bin);
+    }
+  }
+  __syncthreads();
+  const size_t o = (size_t)c * a.n_aug + k;
+  sc_acc_finish(acc, hit, a.bin, a.desc + o * cells);
+  if (k == 0 && a.db)
+    for (int i = threadIdx.x; i < cells; i += blockDim.x) a.db[(size_t)c * cells + i] = acc[i];
+  __syncthreads();
+  sc_keys(acc, R, S, a.ringkey + o * R, a.sectorkey ? a.sectorkey + o * S : nullptr);
+}
+
+// Odometry terms of ExcludeAndUpdateLikelihood (RadarScancontext.cpp:201-222) for the query nodes q0 .. q0 + nq - 1.
+// sc_travel_kernel: one thread per query node i sums the segment lengths seg[m] = |p_{m+1} - p_m| from m = i - 1 downwards,
+// in the reference's order; trav [s][nq] is the sum down to node i - 1 - s.
+__global__ __launch_bounds__(256) void sc_travel_kernel(const double* seg, int q0, int nq, double* trav) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nq) return;
+  const int i = q0 + t;
+  double s = 0.0;
+  for (int m = i - 1; m >= 0; m--) {
+    s += seg[m];
+    trav[(size_t)(i - 1 - m) * nq + t] = s;
+  }
+}
+
+// sc_odom_sim_kernel: odom_similarity[idx] = 1 - exp(-rel^2 / (2 sigma^2)), rel = max(|p_i - p_idx| - 5, 0) / trav, for every
+// query node i and idx < i: sim [nq][ld]
+__global__ __launch_bounds__(256) void sc_odom_sim_kernel(const double2* pos, const double* trav, int q0, int nq, int ld,
+                                                          double sigma, double* sim) {
+  const size_t n_items = (size_t)nq * (q0 + nq);
+  for (size_t it = (size_t)blockIdx.x * blockDim.x + threadIdx.x; it < n_items; it += (size_t)gridDim.x * blockDim.x) {
+    const int t = (int)(it % nq), s = (int)(it / nq);
+    const int i = q0 + t, idx = i - 1 - s;
+    if (idx < 0) continue;
+    const double2 pi = pos[i], pj = pos[idx];
+    const double est = hypot(pi.x - pj.x, pi.y - pj.y);
+    const double e5 = est - 5.0;
+    const double error = e5 < 0.0 ? 0.0 : e5;        // std::max(est - 5.0, 0.0)
+    const double rel = error / trav[(size_t)s * nq + t];
+    const double prob = exp(-rel * rel / (2 * sigma * sigma));
+    sim[(size_t)t * ld + idx] = 1.0 - prob;
+  }
+}
+
+// sc_keysearch_kernel: one workgroup per (query node, augmentation).  The ring-key search of detectLoopClosureID
+// (RadarScancontext.cpp:225-284) over the eligible prefix [0, n_search): OdometryNNSearch's L2norm (float accumulator, double
+// error terms, a 41st element 10 x odometry similarity) or VanillaKDNNSearch's L2_Adaptor (groups of four), and the
+// k_sel smallest by (distance, index) -- the order std::stable_sort leaves.  Every thread keeps its own sorted k_sel best in
+// LDS (it visits ascending indices, so equal distances stay in index order), then k_sel rounds of a workgroup minimum over the
+// list heads pick the result.  Vanilla mode pads a short result with node 0 (the zero-initialised index vector).
+constexpr int kScSearchThreads = 256;
+constexpr int kScMaxTreeK = 64;
+
+struct ScSearchArgs {
+  const double* ringkey;             // [n_db][n_aug][R]: the database is augmentation 0
+  const double* sim;                 // odometry mode: [nq][ld]
+  const int32_t* n_search;           // [nq][n_aug] eligible prefix (odometry: max(i - 1 - exclude, 0); vanilla: the tree's size)
+  const int32_t* pair_off;           // [nq][n_aug] first pair (of the whole call); -1: no search
+  int pair_base;                     // first pair of the chunk
+  int q0, ld, R, n_aug, k_sel, odometry;
+  int32_t* pairs;                    // [.][2] (query (node - q0) * n_aug + k, database node)
+  double* pair_sim;                  // odometry similarity of the pair's database node
+};
+
+__device__ __forceinline__ bool sc_key_less(float da, int ia, float db, int ib) { return da < db || (da == db && ia < ib); }
+
+__global__ __launch_bounds__(kScSearchThreads) void sc_keysearch_kernel(const ScSearchArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const int t = blockIdx.x, k = blockIdx.y, R = a.R, K = a.k_sel;
+  if (a.pair_off[t * a.n_aug + k] < 0) return;
+  const int off = a.pair_off[t * a.n_aug + k] - a.pair_base;
+  const int L = a.n_search[t * a.n_aug + k];
+  float* ld = (float*)smem;                          // [K][threads] distances of every thread's list
+  int* li = (int*)(ld + (size_t)K * kScSearchThreads);   // [K][threads] indices
+  float* qk = (float*)(li + (size_t)K * kScSearchThreads);   // [R + 1] query key
+  float* rd = qk + R + 1;                            // [waves] per-wave minimum
+  int* ri = (int*)(rd + kScSearchThreads / 64);
+  const int i = a.q0 + t;
+  for (int r = threadIdx.x; r < R; r += blockDim.x) qk[r] = (float)a.ringkey[((size_t)i * a.n_aug + k) * R + r];   // eig2stdvec
+  __syncthreads();
+  const double* srow = a.odometry ? a.sim + (size_t)t * a.ld : nullptr;
+  int cnt = 0;
+  for (int idx = threadIdx.x; idx < L; idx += blockDim.x) {
+    const double* kk = a.ringkey + (size_t)idx * a.n_aug * R;
+    float d = 0.f;
+    if (a.odometry) {                                // L2norm (:250-257)
+      for (int r = 0; r < R; r++) {
+        const double err = (double)(qk[r] - (float)kk[r]);
+        d = (float)((double)d + err * err);
+      }
+      const double err = (double)(0.0f - (float)(10 * srow[idx]));
+      d = (float)((double)d + err * err);
+    } else {                                         // L2_Adaptor::evalMetric
+      int r = 0;
+      for (; r + 3 < R; r += 4) {
+        const float e0 = qk[r] - (float)kk[r], e1 = qk[r + 1] - (float)kk[r + 1], e2 = qk[r + 2] - (float)kk[r + 2],
+                    e3 = qk[r + 3] - (float)kk[r + 3];
+        d += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
+      }
+      for (; r < R; r++) { const float e = qk[r] - (float)kk[r]; d += e * e; }
+    }
+    if (cnt == K && !(d < ld[(K - 1) * kScSearchThreads + threadIdx.x])) continue;
+    int pos = cnt < K ? cnt : K - 1;                 // insert after every entry <= d (they have smaller indices)
+    while (pos > 0 && d < ld[(pos - 1) * kScSearchThreads + threadIdx.x]) {
+      ld[pos * kScSearchThreads + threadIdx.x] = ld[(pos - 1) * kScSearchThreads + threadIdx.x];
+      li[pos * kScSearchThreads + threadIdx.x] = li[(pos - 1) * kScSearchThreads + threadIdx.x];
+      pos--;
+    }
+    ld[pos * kScSearchThreads + threadIdx.x] = d;
+    li[pos * kScSearchThreads + threadIdx.x] = idx;
+    cnt = min(cnt + 1, K);
+  }
+  const int n_out = a.odometry ? min(L, K) : K;
+  int head = 0;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int c = 0; c < n_out; c++) {
+    float bd = 0.f;
+    int bi = INT_MAX;
+    if (head < cnt) { bd = ld[head * kScSearchThreads + threadIdx.x]; bi = li[head * kScSearchThreads + threadIdx.x]; }
+    for (int o = 32; o > 0; o >>= 1) {
+      const float od = __shfl_xor(bd, o);
+      const int oi = __shfl_xor(bi, o);
+      if (oi != INT_MAX && (bi == INT_MAX || sc_key_less(od, oi, bd, bi))) { bd = od; bi = oi; }
+    }
+    if (lane == 0) { rd[wave] = bd; ri[wave] = bi; }
+    __syncthreads();
+    bd = rd[0]; bi = ri[0];
+    for (int w = 1; w < kScSearchThreads / 64; w++)
+      if (ri[w] != INT_MAX && (bi == INT_MAX || sc_key_less(rd[w], ri[w], bd, bi))) { bd = rd[w]; bi = ri[w]; }
+    __syncthreads();
+    if (head < cnt && li[head * kScSearchThreads + threadIdx.x] == bi) head++;
+    if (threadIdx.x == 0) {
+      const int db_idx = bi == INT_MAX ? 0 : bi;      // vanilla: a tree with fewer points leaves node 0 in place
+      a.pairs[2 * (off + c)] = t * a.n_aug + k;
+      a.pairs[2 * (off + c) + 1] = db_idx;
+      a.pair_sim[off + c] = a.odometry ? srow[db_idx] : 0.0;
+    }
+  }
 }
 
 struct ScDistArgs {
@@ -407,6 +615,33 @@ int check_sc_params(cfear_ctx* ctx, const cfear_sc_params* p) {
   return CFEAR_OK;
 }
 
+// sc_distance_kernel over n_pairs device pairs: a carries the device buffers, the rest is filled in here
+int sc_distance_launch(cfear_ctx* ctx, ScDistArgs a, int n_pairs, const cfear_sc_params* par) {
+  if (n_pairs == 0) return CFEAR_OK;
+  const int R = par->num_ring, S = par->num_sector, cells = R * S;
+  a.num_ring = R; a.num_sector = S; a.search_ratio = par->search_ratio;
+  const size_t base = (((size_t)2 * cells + 5 * S) * 8 + (size_t)(2 + 2 * S + 2) * 4 + 16 + 15) & ~(size_t)15;
+  const int m_max = 2 * (int)std::round(0.5 * par->search_ratio * S) + 1;
+  const size_t room = base < (size_t)156 * 1024 ? ((size_t)156 * 1024 - base) / ((size_t)S * 8) : 0;
+  // tmp[] holds one distance per shift of a chunk (<= S); one thread sums each shift (<= block size)
+  a.chunk = (int)std::max<size_t>(1, std::min<size_t>({room, (size_t)m_max, (size_t)256, (size_t)S}));
+  a.sim_off = (uint32_t)base;
+  const size_t lds = base + (size_t)a.chunk * S * 8;
+  CFEAR_CHECK(cfear_allow_lds(ctx, (const void*)sc_distance_kernel, 160 * 1024));
+  {
+    ProfScope ps(ctx, "sc_distance");
+    hipLaunchKernelGGL(sc_distance_kernel, dim3(n_pairs), dim3(kScDistThreads), lds, ctx->stream, a);
+  }
+  CFEAR_HIP_CHECK(ctx, hipGetLastError());
+  return CFEAR_OK;
+}
+
+// the query's lateral shifts: the node itself, then RadarScancontext.cpp:164's augmentations
+std::vector<double> sc_aug_shifts(bool augment) {
+  if (!augment) return {0.0};
+  return {0.0, -2.0, 2.0, -4.0, 4.0};
+}
+
 }  // namespace
 
 extern "C" void cfear_sc_params_default(cfear_sc_params* p) {
@@ -484,20 +719,7 @@ extern "C" int cfear_sc_distance_batch(cfear_ctx* ctx, const double* desc_q, int
   st.out(a.dist, dist, (size_t)n_pairs * 8);
   st.out(a.shift, shift, (size_t)n_pairs * 4);
   CFEAR_CHECK(st.carve());
-  a.num_ring = R; a.num_sector = S; a.search_ratio = par->search_ratio;
-  const size_t base = (((size_t)2 * cells + 5 * S) * 8 + (size_t)(2 + 2 * S + 2) * 4 + 16 + 15) & ~(size_t)15;
-  const int m_max = 2 * (int)std::round(0.5 * par->search_ratio * S) + 1;
-  const size_t room = base < (size_t)156 * 1024 ? ((size_t)156 * 1024 - base) / ((size_t)S * 8) : 0;
-  // tmp[] holds one distance per shift of a chunk (<= S); one thread sums each shift (<= block size)
-  a.chunk = (int)std::max<size_t>(1, std::min<size_t>({room, (size_t)m_max, (size_t)256, (size_t)S}));
-  a.sim_off = (uint32_t)base;
-  const size_t lds = base + (size_t)a.chunk * S * 8;
-  { const int rc_lds = cfear_allow_lds(ctx, (const void*)sc_distance_kernel, 160 * 1024); if (rc_lds != CFEAR_OK) return rc_lds; }
-  {
-    ProfScope ps(ctx, "sc_distance");
-    hipLaunchKernelGGL(sc_distance_kernel, dim3(n_pairs), dim3(kScDistThreads), lds, ctx->stream, a);
-  }
-  CFEAR_HIP_CHECK(ctx, hipGetLastError());
+  CFEAR_CHECK(sc_distance_launch(ctx, a, n_pairs, par));
   return st.finish();
 }
 
@@ -693,8 +915,7 @@ extern "C" int cfear_sc_manager_create(cfear_ctx* ctx, const cfear_sc_manager_pa
   cfear_sc_manager* m = new cfear_sc_manager();
   m->ctx = ctx; m->par = *par;
   m->cells = par->sc.num_ring * par->sc.num_sector;
-  m->shifts = {0.0};
-  if (par->augment_sc) { m->shifts.push_back(-2.0); m->shifts.push_back(2.0); m->shifts.push_back(-4.0); m->shifts.push_back(4.0); }   // :164
+  m->shifts = sc_aug_shifts(par->augment_sc != 0);
   m->n_aug = (int)m->shifts.size();
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (hipMalloc((void**)&m->d_cur, (size_t)m->n_aug * m->cells * sizeof(double)) != hipSuccess) {
@@ -718,6 +939,46 @@ extern "C" int cfear_sc_manager_destroy(cfear_sc_manager* m) {
 extern "C" int cfear_sc_manager_size(const cfear_sc_manager* m) { return m ? m->n : CFEAR_ERR_INVALID_ARGUMENT; }
 
 namespace {
+// Host policy shared by the streaming manager and cfear_sc_detect_sequence.
+// ExcludeAndUpdateLikelihood's recent-node count (RadarScancontext.cpp:181-200) for node `cur`; seg(i) = |p_i - p_{i+1}|
+template <class Seg>
+int sc_num_exclude_recent(int cur, double distance_exclude_recent, Seg seg) {
+  if (cur + 1 <= 2) return 2;
+  double distance = 0.0;
+  int n_ex = 0;
+  for (int i = cur; i >= 0 && distance < distance_exclude_recent; i--) {
+    distance = distance + (i == cur ? std::hypot(0.0, 0.0) : seg(i));
+    n_ex++;
+  }
+  return n_ex;
+}
+
+// VanillaKDNNSearch's tree bookkeeping for one call (:227-238): rebuilt on every 50th call from the n - exclude oldest keys
+inline void sc_tree_step(int& counter, int& tree_n, int n, int num_exclude_recent) {
+  if (counter % 50 == 0) tree_n = std::max(n - num_exclude_recent, 0);
+  counter++;
+}
+
+// detectLoopClosureID's ranking (:300-322) of one (augmentation, candidate) pair: std::sort of the growing list, then the
+// worst is erased.  The list is sorted already, so the stable sort puts the new entry after every entry of equal min_dist.
+void sc_rank_push(std::vector<cfear_sc_candidate>& similar, const cfear_sc_manager_params& par, double dist, int shift,
+                  double odom_sim, int idx, double shift_y) {
+  const double unit = 360.0 / (double)par.sc.num_sector;
+  cfear_sc_candidate c{};
+  c.min_dist_sc = dist;
+  c.min_dist_odom = par.odometry_coupled_closure ? odom_sim : 0.0;
+  c.min_dist = par.odometry_coupled_closure ? dist + c.min_dist_odom : dist;
+  const float ang = (float)(shift * unit);
+  c.yaw_diff_rad = (float)(ang * M_PI / 180.0);
+  c.nn_idx = idx;
+  c.argmin_shift = shift;
+  c.Taug[0] = 0.0; c.Taug[1] = shift_y; c.Taug[2] = 0.0;
+  similar.push_back(c);
+  std::stable_sort(similar.begin(), similar.end(),
+                   [](const cfear_sc_candidate& a, const cfear_sc_candidate& b) { return a.min_dist < b.min_dist; });
+  if ((int)similar.size() > par.n_candidates) similar.pop_back();
+}
+
 // makeAndSaveScancontextAndKeys (RadarScancontext.cpp:133-146) + ExcludeAndUpdateLikelihood (:181-222) for the descriptors
 // just written to d_cur: d_cur[0] joins the database, the n_cur entries of d_cur (ring keys rk) become current_and_augments_
 int sc_manager_commit(cfear_sc_manager* m, const std::vector<double>& rk, int n_cur, const double Todom[3]) {
@@ -748,18 +1009,8 @@ int sc_manager_commit(cfear_sc_manager* m, const std::vector<double>& rk, int n_
   const int np = (int)m->poses.size() / 3;
   auto px = [&](int i) { return m->poses[3 * (size_t)i]; };
   auto py = [&](int i) { return m->poses[3 * (size_t)i + 1]; };
-  if (np <= 2) {
-    m->num_exclude_recent = 2;
-  } else {
-    double distance = 0.0;
-    int n_ex = 0, prev = np - 1;
-    for (int i = np - 1; i >= 0 && distance < m->par.distance_exclude_recent; i--) {
-      distance = distance + std::hypot(px(i) - px(prev), py(i) - py(prev));
-      prev = i;
-      n_ex++;
-    }
-    m->num_exclude_recent = n_ex;
-  }
+  m->num_exclude_recent = sc_num_exclude_recent(np - 1, m->par.distance_exclude_recent,
+                                                [&](int i) { return std::hypot(px(i) - px(i + 1), py(i) - py(i + 1)); });
   const int cur = np - 1;
   m->odom_similarity.assign(cur, 0.0);
   double tpx = Todom[0], tpy = Todom[1], trav = 0.0;
@@ -829,8 +1080,7 @@ extern "C" int cfear_sc_manager_detect(cfear_sc_manager* m, cfear_sc_candidate* 
       // node 0 for the missing places.  A linear scan with the tree's metric arithmetic (L2_Adaptor::evalMetric: four
       // squared differences are added among themselves, then to the running sum) finds the same neighbours; equal
       // distances come back in index order here, in tree-visiting order there (tests/test_ref_nanoflann.py).
-      if (m->tree_making_period_counter % 50 == 0) m->tree_n = std::max(m->n - m->num_exclude_recent, 0);
-      m->tree_making_period_counter++;
+      sc_tree_step(m->tree_making_period_counter, m->tree_n, m->n, m->num_exclude_recent);
       for (int idx = 0; idx < m->tree_n; idx++) {
         const float* kk = m->ringkeys[idx].data();
         float d = 0.f;
@@ -862,26 +1112,277 @@ extern "C" int cfear_sc_manager_detect(cfear_sc_manager* m, cfear_sc_candidate* 
   const int rc = cfear_sc_distance_batch(ctx, m->d_cur, m->cur_aug, m->d_db, m->n, pairs.data(), np, &m->par.sc, dist.data(),
                                          shift.data());
   if (rc != CFEAR_OK) return rc;
-  const double unit = 360.0 / (double)m->par.sc.num_sector;
   std::vector<cfear_sc_candidate> similar;
   for (int i = 0; i < np; i++) {                                              // :300-322
     const int k = pairs[2 * i], idx = pairs[2 * i + 1];
-    cfear_sc_candidate c{};
-    c.min_dist_sc = dist[i];
-    c.min_dist_odom = m->par.odometry_coupled_closure ? m->odom_similarity[idx] : 0.0;
-    c.min_dist = m->par.odometry_coupled_closure ? dist[i] + c.min_dist_odom : dist[i];
-    const float ang = (float)(shift[i] * unit);
-    c.yaw_diff_rad = (float)(ang * M_PI / 180.0);
-    c.nn_idx = idx;
-    c.argmin_shift = shift[i];
-    c.Taug[0] = 0.0; c.Taug[1] = m->shifts[k]; c.Taug[2] = 0.0;
-    similar.push_back(c);
-    std::stable_sort(similar.begin(), similar.end(),
-                     [](const cfear_sc_candidate& a, const cfear_sc_candidate& b) { return a.min_dist < b.min_dist; });
-    if ((int)similar.size() > m->par.n_candidates) similar.pop_back();
+    sc_rank_push(similar, m->par, dist[i], shift[i], m->par.odometry_coupled_closure ? m->odom_similarity[idx] : 0.0, idx,
+                 m->shifts[k]);
   }
   *n_out = (int32_t)similar.size();
   if ((int)similar.size() > cap) return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "%d candidates > cap %d", (int)similar.size(), cap);
   for (size_t i = 0; i < similar.size(); i++) out[i] = similar[i];
+  return CFEAR_OK;
+}
+
+// ---- whole-graph Scan Context: cfear_sc_local_map_descriptors / cfear_sc_detect_sequence ---------
+namespace {
+constexpr size_t kScSeqBudget = (size_t)512 << 20;   // device bytes of one query chunk of cfear_sc_detect_sequence
+static_assert(sizeof(cfear_sc_node) == 152, "cfear_sc_node is 152 bytes (include/cfear_hip.h)");
+
+int check_sc_nodes(cfear_ctx* ctx, const cfear_sc_node* nodes, int32_t n_nodes, int32_t n_aggregate) {
+  if (n_nodes < 0 || (n_nodes > 0 && !nodes)) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null nodes");
+  if (n_aggregate < 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "n_aggregate must be >= 0");
+  for (int i = 0; i < n_nodes; i++) {
+    const cfear_sc_cloud& c = nodes[i].cloud;
+    if (c.n < 0 || (c.n > 0 && !c.xyzi)) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "node %d: null cloud", i);
+    if (i > 0 && nodes[i].id <= nodes[i - 1].id)
+      return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "node %d: ids must increase strictly", i);
+  }
+  return CFEAR_OK;
+}
+
+// NodeExists over [id - n_aggregate, id + n_aggregate] (loopclosure.cpp:553-569): the ids increase, so the members of a
+// centre are one range of nodes
+int2 sc_members(const cfear_sc_node* nodes, int32_t n_nodes, int32_t center, int32_t n_aggregate) {
+  const int64_t lo_id = (int64_t)nodes[center].id - n_aggregate, hi_id = (int64_t)nodes[center].id + n_aggregate;
+  int lo = center, hi = center;
+  {
+    int a = 0, b = center;                           // first node with id >= lo_id
+    while (a < b) { const int m = (a + b) / 2; if ((int64_t)nodes[m].id < lo_id) a = m + 1; else b = m; }
+    lo = a;
+  }
+  {
+    int a = center, b = n_nodes;                     // first node with id > hi_id
+    while (a < b) { const int m = (a + b) / 2; if ((int64_t)nodes[m].id <= hi_id) a = m + 1; else b = m; }
+    hi = a - 1;
+  }
+  return make_int2(lo, hi);
+}
+
+// the node table the local-map kernel reads (after carve(): st.cloud resolves staged clouds)
+void sc_fill_nodes(const HostStage& st, const cfear_sc_node* nodes, int32_t n_nodes, ScMapNode* h) {
+  for (int i = 0; i < n_nodes; i++) {
+    h[i].xyzi = st.cloud(nodes[i].cloud.xyzi);
+    h[i].n = nodes[i].cloud.n;
+    h[i].pad = 0;
+    for (int j = 0; j < 8; j++) { h[i].T[j] = nodes[i].T[j]; h[i].Tinv[j] = nodes[i].Tinv[j]; }
+  }
+}
+
+int sc_local_map_launch(cfear_ctx* ctx, const ScMapArgs& a, int n_centers) {
+  const size_t cells = (size_t)a.bin.num_ring * a.bin.num_sector;
+  {
+    ProfScope ps(ctx, "sc_local_map");
+    hipLaunchKernelGGL(sc_local_map_kernel, dim3(n_centers, a.n_aug), dim3(256), cells * 12, ctx->stream, a);
+  }
+  CFEAR_HIP_CHECK(ctx, hipGetLastError());
+  return CFEAR_OK;
+}
+
+ScBin sc_bin(const cfear_sc_params* p) {
+  return ScBin{p->num_ring, p->num_sector, p->desc_function, p->max_radius, p->desc_divider, p->no_point};
+}
+}  // namespace
+
+extern "C" int cfear_sc_local_map_descriptors(cfear_ctx* ctx, const cfear_sc_node* nodes, int32_t n_nodes,
+                                              const int32_t* centers, int32_t n_centers, int32_t n_aggregate,
+                                              const cfear_sc_params* par, const double* shifts_y, int32_t n_aug, double* desc,
+                                              double* ringkey, double* sectorkey) {
+  if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
+  if (n_centers < 0 || (n_centers > 0 && (!centers || !desc)))
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
+  CFEAR_CHECK(check_sc_params(ctx, par));
+  if (n_aug < 1 || n_aug > kScMaxAug || (n_aug > 1 && !shifts_y))
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "n_aug must be in [1, %d]", kScMaxAug);
+  CFEAR_CHECK(check_sc_nodes(ctx, nodes, n_nodes, n_aggregate));
+  for (int c = 0; c < n_centers; c++)
+    if (centers[c] < 0 || centers[c] >= n_nodes)
+      return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "centre %d: node %d out of range", c, (int)centers[c]);
+  if (n_centers == 0) return CFEAR_OK;
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const int R = par->num_ring, S = par->num_sector, cells = R * S;
+  const size_t nd = (size_t)n_centers * n_aug;
+  const size_t o_center = (size_t)n_nodes * sizeof(ScMapNode), o_mem = o_center + (((size_t)n_centers * 4 + 7) & ~(size_t)7);
+  const size_t tab_bytes = o_mem + (size_t)n_centers * sizeof(int2);
+  HostStage st(ctx, kWsScSequence);
+  for (int i = 0; i < n_nodes; i++) st.cloud_in(nodes[i].cloud.xyzi, nodes[i].cloud.n);
+  ScMapArgs a{};
+  char* d_tab;
+  st.piece(d_tab, tab_bytes);
+  st.out(a.desc, desc, nd * cells * sizeof(double));
+  st.out(a.ringkey, ringkey, nd * R * sizeof(double));
+  if (sectorkey) st.out(a.sectorkey, sectorkey, nd * S * sizeof(double));
+  CFEAR_CHECK(st.carve());
+  char* h = (char*)st.record(tab_bytes);
+  sc_fill_nodes(st, nodes, n_nodes, (ScMapNode*)h);
+  memcpy(h + o_center, centers, (size_t)n_centers * 4);
+  int2* mem = (int2*)(h + o_mem);
+  for (int c = 0; c < n_centers; c++) mem[c] = sc_members(nodes, n_nodes, centers[c], n_aggregate);
+  CFEAR_CHECK(st.upload(d_tab, h, tab_bytes));
+  a.nodes = (const ScMapNode*)d_tab;
+  a.center = (const int32_t*)(d_tab + o_center);
+  a.members = (const int2*)(d_tab + o_mem);
+  a.bin = sc_bin(par);
+  a.n_aug = n_aug;
+  for (int k = 0; k < kScMaxAug; k++) a.shift_y[k] = (k < n_aug && shifts_y) ? shifts_y[k] : 0.0;
+  CFEAR_CHECK(sc_local_map_launch(ctx, a, n_centers));
+  return st.finish();
+}
+
+extern "C" int cfear_sc_detect_sequence(cfear_ctx* ctx, const cfear_sc_manager_params* par, const cfear_sc_node* nodes,
+                                        int32_t n_nodes, int32_t n_aggregate, int32_t n_detect, cfear_sc_candidate* out,
+                                        int32_t* n_out) {
+  if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
+  if (!par) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null parameters");
+  CFEAR_CHECK(check_sc_params(ctx, &par->sc));
+  if (par->num_candidates_from_tree < 1 || par->n_candidates < 1 || !(par->odom_sigma_error > 0))
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "bad scan-context manager parameters");
+  if (par->num_candidates_from_tree > kScMaxTreeK)
+    return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "num_candidates_from_tree %d > %d", par->num_candidates_from_tree, kScMaxTreeK);
+  CFEAR_CHECK(check_sc_nodes(ctx, nodes, n_nodes, n_aggregate));
+  if (n_detect < 0 || n_detect > n_nodes)
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "n_detect %d must be in [0, n_nodes = %d]", (int)n_detect, (int)n_nodes);
+  if (n_detect > 0 && (!out || !n_out)) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null output");
+  if (n_detect > 0 && (cfear_is_device_ptr(out) || cfear_is_device_ptr(n_out)))
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "out / n_out must be host memory");
+  if (n_detect == 0) return CFEAR_OK;
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const int R = par->sc.num_ring, S = par->sc.num_sector, cells = R * S, K = par->num_candidates_from_tree;
+  const int N = n_detect;
+  const bool odo = par->odometry_coupled_closure != 0;
+  const std::vector<double> shifts = sc_aug_shifts(par->augment_sc != 0);
+  const int A = (int)shifts.size();
+  // host policy, O(N): segment lengths, recent-node exclusion, the vanilla tree schedule, every (node, augmentation)'s
+  // eligible prefix and its place in the pair list
+  std::vector<double> seg(N > 1 ? N - 1 : 1);
+  auto px = [&](int i) { return nodes[i].T[3]; };
+  auto py = [&](int i) { return nodes[i].T[7]; };
+  for (int i = 0; i + 1 < N; i++) seg[i] = std::hypot(px(i) - px(i + 1), py(i) - py(i + 1));   // = |p_{i+1} - p_i|: hypot is even
+  std::vector<int32_t> n_search((size_t)N * A, 0), pair_off((size_t)N * A, -1);
+  std::vector<int> node_pairs(N + 1, 0);             // first pair of each node
+  {
+    int counter = 0, tree_n = 0;
+    int total = 0;
+    for (int i = 0; i < N; i++) {
+      node_pairs[i] = total;
+      const int nex = sc_num_exclude_recent(i, par->distance_exclude_recent, [&](int j) { return seg[j]; });
+      if (i + 1 < nex + 1) continue;                 // detectLoopClosureID's gate (:288-291)
+      for (int k = 0; k < A; k++) {
+        int L, cnt;
+        if (odo) { L = std::max(i - 1 - nex, 0); cnt = std::min(L, K); }
+        else { sc_tree_step(counter, tree_n, i + 1, nex); L = tree_n; cnt = K; }
+        n_search[(size_t)i * A + k] = L;
+        if (cnt > 0) { pair_off[(size_t)i * A + k] = total; total += cnt; }
+      }
+    }
+    node_pairs[N] = total;
+  }
+  const int n_pairs = node_pairs[N];
+  // query chunks: the descriptors of the chunk's nodes and augmentations, the odometry terms and the pair list
+  const size_t per_node = (size_t)A * cells * 8 + (odo ? (size_t)2 * N * 8 : 0) + (size_t)A * K * (8 + 8 + 4 + 8);
+  int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)N, kScSeqBudget / per_node));
+  if (ctx->opt[CFEAR_OPT_SC_QUERY_CHUNK] > 0) chunk = (int)std::min<int64_t>(chunk, ctx->opt[CFEAR_OPT_SC_QUERY_CHUNK]);
+  int max_chunk_pairs = 1;
+  for (int q0 = 0; q0 < N; q0 += chunk) max_chunk_pairs = std::max(max_chunk_pairs, node_pairs[std::min(N, q0 + chunk)] - node_pairs[q0]);
+  std::vector<int32_t> h_pairs((size_t)std::max(n_pairs, 1) * 2), h_shift(std::max(n_pairs, 1));
+  std::vector<double> h_dist(std::max(n_pairs, 1)), h_psim(std::max(n_pairs, 1));
+  // device: tables (uploaded once), database + ring keys of every node, one chunk's working set
+  const size_t o_center = (size_t)n_nodes * sizeof(ScMapNode);
+  const size_t o_mem = o_center + (((size_t)N * 4 + 15) & ~(size_t)15);
+  const size_t o_pos = o_mem + (size_t)N * 8;
+  const size_t o_seg = o_pos + (size_t)N * 16;
+  const size_t o_ns = o_seg + (size_t)seg.size() * 8;
+  const size_t o_po = o_ns + (size_t)N * A * 4;
+  const size_t tab_bytes = o_po + (size_t)N * A * 4;
+  HostStage st(ctx, kWsScSequence);
+  for (int i = 0; i < n_nodes; i++) st.cloud_in(nodes[i].cloud.xyzi, nodes[i].cloud.n);
+  char* d_tab;
+  double *d_db, *d_rk, *d_q, *d_trav = nullptr, *d_sim = nullptr, *d_dist, *d_psim;
+  int32_t *d_pairs, *d_shift;
+  st.piece(d_tab, tab_bytes);
+  st.piece(d_db, (size_t)N * cells * 8);
+  st.piece(d_rk, (size_t)N * A * R * 8);
+  st.piece(d_q, (size_t)chunk * A * cells * 8);
+  if (odo) { st.piece(d_trav, (size_t)N * chunk * 8); st.piece(d_sim, (size_t)chunk * N * 8); }
+  st.piece(d_pairs, (size_t)max_chunk_pairs * 8);
+  st.piece(d_dist, (size_t)max_chunk_pairs * 8);
+  st.piece(d_shift, (size_t)max_chunk_pairs * 4);
+  st.piece(d_psim, (size_t)max_chunk_pairs * 8);
+  CFEAR_CHECK(st.carve());
+  char* h = (char*)st.record(tab_bytes);
+  sc_fill_nodes(st, nodes, n_nodes, (ScMapNode*)h);
+  int32_t* hc = (int32_t*)(h + o_center);
+  int2* hm = (int2*)(h + o_mem);
+  double2* hp = (double2*)(h + o_pos);
+  for (int i = 0; i < N; i++) { hc[i] = i; hm[i] = sc_members(nodes, n_nodes, i, n_aggregate); hp[i] = make_double2(px(i), py(i)); }
+  memcpy(h + o_seg, seg.data(), seg.size() * 8);
+  memcpy(h + o_ns, n_search.data(), (size_t)N * A * 4);
+  memcpy(h + o_po, pair_off.data(), (size_t)N * A * 4);
+  CFEAR_CHECK(st.upload(d_tab, h, tab_bytes));
+  ScMapArgs ma{};
+  ma.nodes = (const ScMapNode*)d_tab;
+  ma.bin = sc_bin(&par->sc);
+  ma.n_aug = A;
+  for (int k = 0; k < kScMaxAug; k++) ma.shift_y[k] = k < A ? shifts[k] : 0.0;
+  const size_t search_lds = (size_t)K * kScSearchThreads * 8 + (size_t)(R + 1) * 4 + (kScSearchThreads / 64) * 8;
+  CFEAR_CHECK(cfear_allow_lds(ctx, (const void*)sc_keysearch_kernel, search_lds));
+  for (int q0 = 0; q0 < N; q0 += chunk) {
+    const int nq = std::min(chunk, N - q0);
+    const int p0 = node_pairs[q0], np = node_pairs[q0 + nq] - p0;
+    ma.center = (const int32_t*)(d_tab + o_center) + q0;
+    ma.members = (const int2*)(d_tab + o_mem) + q0;
+    ma.desc = d_q;
+    ma.db = d_db + (size_t)q0 * cells;
+    ma.ringkey = d_rk + (size_t)q0 * A * R;
+    ma.sectorkey = nullptr;
+    CFEAR_CHECK(sc_local_map_launch(ctx, ma, nq));
+    if (np == 0) continue;
+    if (odo) {
+      {
+        ProfScope ps(ctx, "sc_odom_terms");
+        hipLaunchKernelGGL(sc_travel_kernel, dim3((nq + 255) / 256), dim3(256), 0, ctx->stream, (const double*)(d_tab + o_seg), q0,
+                           nq, d_trav);
+        const size_t items = (size_t)nq * (q0 + nq);
+        const int blocks = (int)std::max<size_t>(1, std::min<size_t>((items + 255) / 256, (size_t)ctx->n_cu * 16));
+        hipLaunchKernelGGL(sc_odom_sim_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const double2*)(d_tab + o_pos), d_trav, q0,
+                           nq, N, par->odom_sigma_error, d_sim);
+      }
+      CFEAR_HIP_CHECK(ctx, hipGetLastError());
+    }
+    ScSearchArgs sa{};
+    sa.ringkey = d_rk;
+    sa.sim = d_sim;
+    sa.n_search = (const int32_t*)(d_tab + o_ns) + (size_t)q0 * A;
+    sa.pair_off = (const int32_t*)(d_tab + o_po) + (size_t)q0 * A;
+    sa.pair_base = p0;
+    sa.q0 = q0; sa.ld = N; sa.R = R; sa.n_aug = A; sa.k_sel = K; sa.odometry = odo ? 1 : 0;
+    sa.pairs = d_pairs;
+    sa.pair_sim = d_psim;
+    {
+      ProfScope ps(ctx, "sc_keysearch");
+      hipLaunchKernelGGL(sc_keysearch_kernel, dim3(nq, A), dim3(kScSearchThreads), search_lds, ctx->stream, sa);
+    }
+    CFEAR_HIP_CHECK(ctx, hipGetLastError());
+    ScDistArgs da{};
+    da.desc_q = d_q; da.desc_c = d_db; da.pairs = d_pairs; da.dist = d_dist; da.shift = d_shift;
+    CFEAR_CHECK(sc_distance_launch(ctx, da, np, &par->sc));
+    // the chunk's buffers are reused by the next chunk: its copies are ordered before that on the stream
+    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(h_pairs.data() + (size_t)2 * p0, d_pairs, (size_t)np * 8, hipMemcpyDeviceToHost, ctx->stream));
+    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(h_dist.data() + p0, d_dist, (size_t)np * 8, hipMemcpyDeviceToHost, ctx->stream));
+    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(h_shift.data() + p0, d_shift, (size_t)np * 4, hipMemcpyDeviceToHost, ctx->stream));
+    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(h_psim.data() + p0, d_psim, (size_t)np * 8, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  CFEAR_CHECK(st.finish());
+  // the ranking of every node's pairs, in the streaming loop's visiting order (augmentation, then search rank)
+  std::vector<cfear_sc_candidate> similar;
+  for (int i = 0; i < N; i++) {
+    similar.clear();
+    for (int p = node_pairs[i]; p < node_pairs[i + 1]; p++) {
+      const int k = h_pairs[2 * (size_t)p] % A;                                // query = (node - q0) * A + k
+      sc_rank_push(similar, *par, h_dist[p], h_shift[p], h_psim[p], h_pairs[2 * (size_t)p + 1], shifts[k]);
+    }
+    n_out[i] = (int32_t)similar.size();
+    for (size_t j = 0; j < similar.size(); j++) out[(size_t)i * par->n_candidates + j] = similar[j];
+  }
   return CFEAR_OK;
 }

@@ -244,3 +244,29 @@ def render_frames_torch(sc, frames, device, generator=None):
         start = int(rs.integers(200, cols - 100))
         img[int(r), start:start + int(rs.integers(20, 60))] = 255.0
     return torch.clamp(torch.round(img), 0, 255).to(torch.uint8).view(F, rows, cols)
+
+
+def sc_graph(n_nodes, seed=0, points=600, step=2.5, radius=120.0):
+    """A pose graph for whole-graph Scan Context: the sensor drives laps of a wobbling circle (step metres between nodes,
+    so a 4096-node graph revisits every place several times), each node seeing up to `points` landmarks of a fixed world
+    within 80 m, in its own frame, with integer intensities (as radar peaks have).
+    -> (clouds [float32 [m, 4]] per node, poses [n, 3] (x, y, theta) float64)."""
+    rng = np.random.default_rng(seed)
+    world = rng.uniform(-radius - 100.0, radius + 100.0, (40000, 2))
+    inten = np.floor(rng.uniform(1.0, 120.0, 40000))
+    arc = step / radius
+    poses, clouds = np.zeros((n_nodes, 3)), []
+    for i in range(n_nodes):
+        a = i * arc
+        r = radius + 6.0 * np.sin(0.37 * a) + rng.normal(0.0, 0.3)
+        poses[i] = (r * np.cos(a), r * np.sin(a), a + np.pi / 2 + rng.normal(0.0, 0.02))
+        d = world - poses[i, :2]
+        near = np.flatnonzero(np.hypot(d[:, 0], d[:, 1]) < 80.0)
+        near = near[rng.permutation(near.size)[:points]]
+        c, s = np.cos(poses[i, 2]), np.sin(poses[i, 2])
+        local = np.stack([c * d[near, 0] + s * d[near, 1], -s * d[near, 0] + c * d[near, 1]], 1)
+        local += rng.normal(0.0, 0.05, local.shape)
+        cl = np.zeros((near.size, 4), np.float32)
+        cl[:, :2], cl[:, 3] = local, inten[near]
+        clouds.append(cl)
+    return clouds, poses

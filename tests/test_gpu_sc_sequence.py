@@ -1,0 +1,183 @@
+"""GPU: whole-graph Scan Context (cfear_sc_local_map_descriptors / cfear_sc_detect_sequence) against the streaming path it
+replaces: local maps merged on the GPU vs merged in NumPy (examples/loop_closure_demo.py transform_cloud) and described by
+cfear_sc_descriptors, bit for bit; the batch's candidates vs RSCManagerNative fed node by node."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "examples"))
+
+from tests.test_oracle_coral import _peaks   # noqa: E402
+
+
+def _merge(clouds, poses, ids, i, n_agg):
+    """ScansToLocalMap in NumPy, as the demo does it."""
+    import loop_closure_demo as demo
+    mem = [j for j in range(len(clouds)) if abs(int(ids[j]) - int(ids[i])) <= n_agg]
+    merged = [demo.transform_cloud(clouds[j], poses[j]) for j in mem]
+    return demo.transform_cloud(np.concatenate(merged), demo.xyt_inverse(poses[i]))
+
+
+def _graph(n=9, seed=30):
+    clouds, _ = _peaks(seed, list(range(n)), k=12)
+    rng = np.random.default_rng(seed)
+    poses = np.cumsum(np.stack([rng.uniform(1.5, 3.0, n), rng.uniform(-0.5, 0.5, n), rng.uniform(-0.1, 0.1, n)], 1), 0)
+    return clouds, poses
+
+
+@pytest.mark.parametrize("fn,div", [("sum", 1000.0), ("max", 1.0)])
+@pytest.mark.parametrize("n_agg", [0, 1, 3])
+def test_local_map_descriptors_bit_identical_to_host_merge(fn, div, n_agg):
+    import torch
+    from tbv_slam_public_amd import api
+    clouds, poses = _graph()
+    clouds[4] = np.zeros((0, 4), np.float32)                       # an empty member cloud
+    ids = np.array([0, 1, 2, 3, 4, 6, 7, 8, 9])                    # an id gap between the 5th and 6th node
+    par = api.sc_params(desc_function=fn, desc_divider=div)
+    shifts = (0.0, -2.0, 2.0, -4.0, 4.0)
+    for dev in (False, True):
+        cl = [torch.from_numpy(c).cuda() for c in clouds] if dev else clouds
+        centers = None if not dev else [8, 0, 5, 4]                # both ends, the gap, the empty node; in any order
+        desc, rk, sk = api.sc_local_map_descriptors(cl, poses, n_agg, centers, par, shifts, ids=ids)
+        ctr = range(len(clouds)) if centers is None else centers
+        merged = [_merge(clouds, poses, ids, i, n_agg) for i in ctr]
+        ed, erk, esk = api.sc_descriptors(merged, par, shifts)
+        np.testing.assert_array_equal(desc, ed)
+        np.testing.assert_array_equal(rk, erk)
+        np.testing.assert_array_equal(sk, esk)
+    # descriptors kept in HBM: the same bits
+    dd = api.sc_local_map_descriptors(clouds, poses, n_agg, None, par, shifts, ids=ids, device_out=True)[0]
+    assert dd.is_cuda
+    np.testing.assert_array_equal(dd.cpu().numpy(), api.sc_local_map_descriptors(clouds, poses, n_agg, None, par, shifts, ids=ids)[0])
+
+
+def _lap_maps():
+    import loop_closure_demo as demo
+    from oracle import pyoracle as O
+    sc = demo.circle_scene()
+    n = 68
+    gt = np.stack([sc.pose_at(f, n) for f in range(n)])
+    poses = np.array([demo.xyt_compose(demo.xyt_inverse(gt[0]), g) for g in gt])
+    peaks = []
+    for f in range(n):
+        img = sc.render(f, n)
+        sr, si, cnt = O.kstrongest(img, 40, 60)
+        peaks.append(O.kstrongest_cloud(sr, si, cnt, 0.0438, 2.5, mask=O.peaks(img, 40, sr, cnt)))
+    return peaks, poses
+
+
+def _streaming(clouds, poses, n_agg, n_detect, **kw):
+    from tbv_slam_public_amd import api
+    ids = np.arange(len(clouds))
+    nat = api.RSCManagerNative(**kw)
+    out = []
+    for i in range(n_detect):
+        nat.makeAndSaveScancontextAndKeysRadarCloud(_merge(clouds, poses, ids, i, n_agg), poses[i])
+        out.append(nat.detectLoopClosureID())
+    nat.close()
+    return out
+
+
+def _assert_same(batch, stream):
+    assert len(batch) == len(stream)
+    found = 0
+    for i, (a, b) in enumerate(zip(batch, stream)):
+        assert [c["nn_idx"] for c in a] == [c["nn_idx"] for c in b], i
+        for ca, cb in zip(a, b):
+            for f in ("argmin_shift", "Taug", "yaw_diff_rad", "min_dist_sc"):
+                assert ca[f] == cb[f], (i, f, ca[f], cb[f])
+            for f in ("min_dist", "min_dist_odom"):
+                assert abs(ca[f] - cb[f]) <= 1e-12, (i, f, ca[f], cb[f])
+        found += len(a)
+    return found
+
+
+@pytest.mark.parametrize("kw", [dict(), dict(odometry_coupled_closure=False), dict(augment_sc=False, n_candidates=5)])
+def test_detect_sequence_equals_streaming_manager_over_the_lap(kw):
+    from tbv_slam_public_amd import api
+    peaks, poses = _lap_maps()
+    n = len(peaks)
+    got = api.sc_detect_sequence(peaks, poses, n_aggregate=1, n_detect=n - 1, **kw)
+    assert _assert_same(got, _streaming(peaks, poses, 1, n - 1, **kw)) > 100
+
+
+@pytest.mark.parametrize("kw,upload", [(dict(odometry_coupled_closure=False), True), (dict(), False)])
+def test_detect_sequence_long_graph_with_revisits_and_small_chunks(kw, upload):
+    from tbv_slam_public_amd import api, synth
+    from tbv_slam_public_amd import _lib as L
+    clouds, poses = synth.sc_graph(320, seed=3, points=250)
+    ctx = api.default_context()
+    ctx.set_option(L.OPT_SC_QUERY_CHUNK, 37)
+    try:
+        got = api.sc_detect_sequence(clouds, poses, n_aggregate=1, n_detect=319, ctx=ctx, upload_clouds=upload, **kw)
+    finally:
+        ctx.set_option(L.OPT_SC_QUERY_CHUNK, 0)
+    exp = _streaming(clouds, poses, 1, 319, **kw)
+    assert _assert_same(got, exp) > 300
+    # the graph revisits its places: late nodes find nodes one lap earlier
+    assert any(c["nn_idx"] < i - 100 for i, g in enumerate(got) for c in g)
+    if not kw.get("odometry_coupled_closure", True):
+        assert len({c["nn_idx"] for g in got for c in g}) > 20    # several 50-call tree rebuilds, not node 0 alone
+    # one chunk, and the other cloud route, give the same candidates
+    assert api.sc_detect_sequence(clouds, poses, n_aggregate=1, n_detect=319, ctx=ctx, upload_clouds=not upload, **kw) == got
+
+
+def test_demo_batched_scan_context_equals_the_default_run():
+    import loop_closure_demo as demo
+    a = demo.run(demo.HipBackend())
+    b = demo.run(demo.HipBackend(), batched_scan_context=True)
+    assert len(a["candidates"]) > 50
+    assert [(c["from"], c["to"], c["sc_yaw"]) for c in a["candidates"]] == [(c["from"], c["to"], c["sc_yaw"]) for c in b["candidates"]]
+    for ca, cb in zip(a["candidates"], b["candidates"]):
+        assert abs(ca["sc_sim"] - cb["sc_sim"]) <= 1e-12
+        np.testing.assert_array_equal(ca["t_be_guess"], cb["t_be_guess"])
+    for ra, rb in zip(a["results"], b["results"]):
+        assert ra["accepted"] == rb["accepted"] and ra["reg_ok"] == rb["reg_ok"]
+        np.testing.assert_allclose(ra["t_be"], rb["t_be"], rtol=0, atol=1e-12)
+        assert abs(ra["probability"] - rb["probability"]) <= 1e-9
+
+
+def test_bad_arguments_are_refused_and_the_context_stays_usable():
+    from tbv_slam_public_amd import api
+    from tbv_slam_public_amd import _lib as L
+    clouds, poses = _graph(6, seed=31)
+    ctx = api.default_context()
+    lib = ctx._lib
+    p = api.sc_manager_params()
+    sp = api.sc_params()
+    good = api.sc_detect_sequence(clouds, poses, n_detect=6)
+    arr, keep = api._sc_nodes(clouds, poses, None, None)
+    out = np.zeros((6, 3), L.SC_CANDIDATE_DTYPE)
+    n_out = np.zeros(6, np.int32)
+    desc = np.zeros((6, 1, 40, 120))
+    rk = np.zeros((6, 1, 40))
+    ctr = np.arange(6, dtype=np.int32)
+    sh = (C.c_double * 1)(0.0)
+
+    def detect(nodes=arr, n_nodes=6, n_agg=1, n_detect=6, o=out.ctypes.data, no=n_out.ctypes.data):
+        return lib.cfear_sc_detect_sequence(ctx.h, C.byref(p), nodes, n_nodes, n_agg, n_detect, o, no)
+
+    def local(nodes=arr, n_nodes=6, centers=ctr.ctypes.data, n_centers=6, n_agg=1):
+        return lib.cfear_sc_local_map_descriptors(ctx.h, nodes, n_nodes, centers, n_centers, n_agg, C.byref(sp), sh, 1,
+                                                  desc.ctypes.data, rk.ctypes.data, None)
+
+    bad = [detect(n_detect=7), detect(n_agg=-1), detect(nodes=None), detect(o=None), detect(no=None), detect(n_nodes=-1),
+           local(n_agg=-1), local(centers=None), local(nodes=None), local(n_centers=-1)]
+    ctr[3] = 6
+    bad.append(local())
+    ctr[3] = 3
+    arr[3].id = 2                                                  # ids must increase strictly
+    bad += [detect(), local()]
+    arr[3].id = 3
+    arr[2].cloud.xyzi = None                                       # a null cloud with points
+    bad += [detect(), local()]
+    assert bad == [L.ERR_INVALID_ARGUMENT] * len(bad), bad
+    del keep
+    assert api.sc_detect_sequence(clouds, poses, n_detect=6) == good
+    assert detect(nodes=api._sc_nodes(clouds, poses, None, None)[0], n_detect=0) == 0
