@@ -456,12 +456,22 @@ typedef struct cfear_sc_params {
   double desc_divider;                  /* 1000 in TBV's launch defaults                               */
   double no_point;                      /* value of empty bins (reached only when desc_divider == 1)   */
 } cfear_sc_params;
+/* Limits, checked by every call that takes these parameters -- descriptors, distances, managers, whole-graph calls:
+ * num_ring x num_sector in [1, 5120] (CFEAR_ERR_CAPACITY); search_ratio finite (CFEAR_ERR_INVALID_ARGUMENT); and the
+ * distance kernel's LDS, 160 KiB, must hold (2 R S + 6 S) * 8 + (2 + m) * 4 bytes, m = 2 round(0.5 search_ratio S) + 1
+ * (CFEAR_ERR_CAPACITY).  With one ring and search_ratio 0.1 that allows S <= 2543; 2 x 2560 and 1 x 5120 are refused. */
 void cfear_sc_params_default(cfear_sc_params* p);
 typedef struct cfear_sc_cloud {
   const float* xyzi;                    /* [n][4] x,y,z,intensity in the node's frame; host or device   */
   int32_t n, pad;
 } cfear_sc_cloud;
-/* MakeRadarCloudContext for n_clouds clouds x n_aug lateral shifts (shifts_y[0] is normally 0; TBV augments
+/* Intensity domain: bins are summed with fp64 atomics ("sum") or take an order-preserving maximum ("max").  For
+ * non-negative integer intensities whose bin sums stay below 2^53 -- every cloud TBV makes: raw u8 values or
+ * value - zmin -- this is exactly the reference's rule (a bin still at NO_POINT = -1000 is replaced, otherwise added to /
+ * maxed).  Outside that domain a bin holds the plain sum (its last bits may depend on the order of arrival when the
+ * intensities are fractional) or the plain maximum of its intensities; the reference's replace rule is not followed
+ * when a running value passes through -1000.  A result equal to NO_POINT after the division still becomes no_point.
+ * MakeRadarCloudContext for n_clouds clouds x n_aug lateral shifts (shifts_y[0] is normally 0; TBV augments
  * with {-2, 2, -4, 4}).  desc [n_clouds][n_aug][num_ring * num_sector] row-major (ring, sector); ringkey
  * [..][num_ring] and sectorkey [..][num_sector] optional.  desc may be HOST or DEVICE memory (a descriptor
  * database kept in HBM feeds cfear_sc_distance_batch without crossing PCIe); the keys are host arrays -- the
@@ -470,7 +480,10 @@ int cfear_sc_descriptors(cfear_ctx* ctx, const cfear_sc_cloud* clouds, int32_t n
                          const cfear_sc_params* par, const double* shifts_y, int32_t n_aug, double* desc,
                          double* ringkey, double* sectorkey);
 /* distanceBtnScanContext for pairs[i] = (query index into desc_q, candidate index into desc_c); descriptors
- * host or device; dist / shift host [n_pairs] (shift = argmin column shift of the candidate).          */
+ * host or device; dist / shift host [n_pairs] (shift = argmin column shift of the candidate).  The search space keeps
+ * the reference's duplicates; shift is in [0, S) while round(0.5 search_ratio S) <= S.  Past that (search_ratio > 2)
+ * the reference's (argmin - ii + S) % S turns negative; such a shift k is applied as k + S and reported as k, in
+ * (-S, 0), like the reference's index arithmetic (whose circshift is undefined there).                 */
 int cfear_sc_distance_batch(cfear_ctx* ctx, const double* desc_q, int32_t n_q, const double* desc_c, int32_t n_c,
                             const int32_t* pairs, int32_t n_pairs, const cfear_sc_params* par, double* dist,
                             int32_t* shift);

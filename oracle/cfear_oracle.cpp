@@ -1387,6 +1387,26 @@ extern "C" void orc_sc_descriptor(const float* xyzi, int n, int num_ring, int nu
     if (desc[i] == NO_POINT) desc[i] = no_point;                          // only reachable when desc_divider == 1
 }
 
+// The (ring, sector) bin orc_sc_descriptor gives each point, 0-based; -1 for a dropped point (range > max_radius).
+// Tests use it to find points whose sector depends on how atan rounds.
+extern "C" void orc_sc_bins(const float* xyzi, int n, int num_ring, int num_sector, double max_radius, double shift_y,
+                            int32_t* ring, int32_t* sector) {
+  for (int k = 0; k < n; k++) {
+    float px = xyzi[4 * k], py = xyzi[4 * k + 1];
+    if (shift_y != 0.0) {
+      px = (float)(((1.0 * (double)px + 0.0 * (double)py) + 0.0 * (double)xyzi[4 * k + 2]) + 0.0);
+      py = (float)(((0.0 * (double)xyzi[4 * k] + 1.0 * (double)py) + 0.0 * (double)xyzi[4 * k + 2]) + shift_y);
+    }
+    const float azim_range = std::sqrt(px * px + py * py);
+    const float azim_angle = sc_xy2theta(px, py);
+    ring[k] = sector[k] = -1;
+    if (azim_range > max_radius) continue;
+    double rr = std::ceil((azim_range / max_radius) * num_ring), ss = std::ceil((azim_angle / 360.0) * num_sector);
+    ring[k] = std::max(std::min(num_ring, rr == rr ? (int)rr : 1), 1) - 1;
+    sector[k] = std::max(std::min(num_sector, ss == ss ? (int)ss : 1), 1) - 1;
+  }
+}
+
 // makeRingkeyFromScancontext / makeSectorkeyFromScancontext (Scancontext.cpp:239-268): row / column means
 extern "C" void orc_sc_keys(const double* desc, int num_ring, int num_sector, double* ringkey, double* sectorkey) {
   for (int r = 0; r < num_ring; r++) {

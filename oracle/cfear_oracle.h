@@ -140,6 +140,8 @@ int orc_coral_quality(const float* ref_xyzi, int n_ref, const float* src_xyzi, i
  * row-major [ring][sector].  desc_function 0 = sum, 1 = max; shift_y = the y offset of an augmentation. */
 void orc_sc_descriptor(const float* xyzi, int n, int num_ring, int num_sector, double max_radius,
                        int desc_function, double desc_divider, double no_point, double shift_y, double* desc);
+void orc_sc_bins(const float* xyzi, int n, int num_ring, int num_sector, double max_radius, double shift_y,
+                 int32_t* ring, int32_t* sector);
 void orc_sc_keys(const double* desc, int num_ring, int num_sector, double* ringkey, double* sectorkey);
 double orc_sc_distance(const double* sc1, const double* sc2, int num_ring, int num_sector,
                        double search_ratio, int32_t* argmin_shift);

@@ -100,6 +100,8 @@ def lib():
         L.orc_sc_descriptor.argtypes = [f32p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double,
                                         C.c_double, f64p]
         L.orc_sc_descriptor.restype = None
+        L.orc_sc_bins.argtypes = [f32p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, i32p, i32p]
+        L.orc_sc_bins.restype = None
         L.orc_sc_keys.argtypes = [f64p, C.c_int, C.c_int, f64p, f64p]
         L.orc_sc_keys.restype = None
         L.orc_sc_distance.argtypes = [f64p, f64p, C.c_int, C.c_int, C.c_double, i32p]
@@ -264,6 +266,15 @@ def sc_descriptor(xyzi, num_ring=40, num_sector=120, max_radius=80.0, desc_funct
                             0 if desc_function == "sum" else 1, float(desc_divider), float(no_point), float(shift_y),
                             _p(desc, C.c_double))
     return desc
+
+
+def sc_bins(xyzi, num_ring=40, num_sector=120, max_radius=80.0, shift_y=0.0):
+    """The 0-based (ring [n], sector [n]) bin sc_descriptor gives each point; -1 where the point is dropped."""
+    c = np.ascontiguousarray(xyzi, dtype=np.float32)
+    ring, sector = np.zeros(c.shape[0], np.int32), np.zeros(c.shape[0], np.int32)
+    lib().orc_sc_bins(_p(c, C.c_float), c.shape[0], num_ring, num_sector, float(max_radius), float(shift_y),
+                      _p(ring, C.c_int32), _p(sector, C.c_int32))
+    return ring, sector
 
 
 def sc_keys(desc):

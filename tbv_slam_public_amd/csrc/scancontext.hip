@@ -351,7 +351,7 @@ __global__ __launch_bounds__(1024) void sc_distance_kernel(const ScDistArgs a) {
   double* v1 = n2 + S;                 // [S] sector keys
   double* v2 = v1 + S;
   double* tmp = v2 + S;                // [S] per-shift / per-column results
-  int* ctl = (int*)(tmp + S);          // [2 + 2 * S] argmin, count, search space
+  int* ctl = (int*)(tmp + S);          // [2 + m] argmin, count, search space (sc_distance_layout)
   const int qi = a.pairs[2 * blockIdx.x], ci = a.pairs[2 * blockIdx.x + 1];
   const double* gq = a.desc_q + (size_t)qi * cells;
   const double* gc = a.desc_c + (size_t)ci * cells;
@@ -606,28 +606,49 @@ __global__ __launch_bounds__(256) void sc_raw_keys_kernel(const double* desc, in
   sc_keys(desc + b * R * S, R, S, ringkey + b * R, sectorkey + b * S);
 }
 
+// LDS of sc_distance_kernel: both descriptors, five [S] vectors, ctl = (argmin, count, search space), then the [chunk][S]
+// similarity matrix.  The search space holds m = 2 round(0.5 search_ratio S) + 1 shifts (duplicates included, as the
+// reference keeps them); a negative radius leaves the vkey argmin alone.
+constexpr size_t kScDistLds = (size_t)160 * 1024;
+constexpr double kScMaxSpace = 1 << 20;  // search-space entries checked before the int conversion (the LDS refuses far fewer)
+
+struct ScDistLayout { size_t base; int m_max; };
+
+// the layout for (R, S, ratio); ratio must be finite
+ScDistLayout sc_distance_layout(int R, int S, double ratio) {
+  const double rad = std::round(0.5 * ratio * S);
+  const int m_max = rad < 0 ? 1 : (rad > kScMaxSpace ? (int)kScMaxSpace : 2 * (int)rad + 1);
+  const size_t base = (((size_t)2 * R * S + 5 * (size_t)S) * 8 + (size_t)(2 + m_max) * 4 + 15) & ~(size_t)15;
+  return {base, m_max};
+}
+
 int check_sc_params(cfear_ctx* ctx, const cfear_sc_params* p) {
   if (!p) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null parameters");
   if (p->num_ring < 1 || p->num_sector < 1 || (long long)p->num_ring * p->num_sector > kScMaxCells)
     return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "num_ring x num_sector must be in [1, %d]", kScMaxCells);
-  if (!(p->max_radius > 0) || p->desc_divider == 0.0 || p->desc_function < 0 || p->desc_function > 1)
+  if (!(p->max_radius > 0) || p->desc_divider == 0.0 || p->desc_function < 0 || p->desc_function > 1 || !std::isfinite(p->search_ratio))
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "bad scan-context parameters");
+  // the distance kernel keeps both descriptors, the search space and one shift's similarities in LDS
+  const ScDistLayout l = sc_distance_layout(p->num_ring, p->num_sector, p->search_ratio);
+  if (l.base + (size_t)p->num_sector * 8 > kScDistLds)
+    return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "scan-context distance of %d x %d with search_ratio %g needs more than %d KiB of LDS",
+                           p->num_ring, p->num_sector, p->search_ratio, (int)(kScDistLds / 1024));
   return CFEAR_OK;
 }
 
-// sc_distance_kernel over n_pairs device pairs: a carries the device buffers, the rest is filled in here
+// sc_distance_kernel over n_pairs device pairs: a carries the device buffers, the rest is filled in here; par passed
+// check_sc_params
 int sc_distance_launch(cfear_ctx* ctx, ScDistArgs a, int n_pairs, const cfear_sc_params* par) {
   if (n_pairs == 0) return CFEAR_OK;
-  const int R = par->num_ring, S = par->num_sector, cells = R * S;
+  const int R = par->num_ring, S = par->num_sector;
   a.num_ring = R; a.num_sector = S; a.search_ratio = par->search_ratio;
-  const size_t base = (((size_t)2 * cells + 5 * S) * 8 + (size_t)(2 + 2 * S + 2) * 4 + 16 + 15) & ~(size_t)15;
-  const int m_max = 2 * (int)std::round(0.5 * par->search_ratio * S) + 1;
-  const size_t room = base < (size_t)156 * 1024 ? ((size_t)156 * 1024 - base) / ((size_t)S * 8) : 0;
+  const ScDistLayout l = sc_distance_layout(R, S, par->search_ratio);
+  const size_t room = (kScDistLds - l.base) / ((size_t)S * 8);
   // tmp[] holds one distance per shift of a chunk (<= S); one thread sums each shift (<= block size)
-  a.chunk = (int)std::max<size_t>(1, std::min<size_t>({room, (size_t)m_max, (size_t)256, (size_t)S}));
-  a.sim_off = (uint32_t)base;
-  const size_t lds = base + (size_t)a.chunk * S * 8;
-  CFEAR_CHECK(cfear_allow_lds(ctx, (const void*)sc_distance_kernel, 160 * 1024));
+  a.chunk = (int)std::max<size_t>(1, std::min<size_t>({room, (size_t)l.m_max, (size_t)256, (size_t)S}));
+  a.sim_off = (uint32_t)l.base;
+  const size_t lds = l.base + (size_t)a.chunk * S * 8;
+  CFEAR_CHECK(cfear_allow_lds(ctx, (const void*)sc_distance_kernel, kScDistLds));
   {
     ProfScope ps(ctx, "sc_distance");
     hipLaunchKernelGGL(sc_distance_kernel, dim3(n_pairs), dim3(kScDistThreads), lds, ctx->stream, a);

@@ -178,6 +178,19 @@ def test_bad_arguments_are_refused_and_the_context_stays_usable():
     arr[2].cloud.xyzi = None                                       # a null cloud with points
     bad += [detect(), local()]
     assert bad == [L.ERR_INVALID_ARGUMENT] * len(bad), bad
+    # K above the key search's 64, shapes past the 5120-cell accumulators or the distance kernel's LDS, bad ratios
+    full = []
+    p.num_candidates_from_tree = 65
+    full.append(detect())
+    p.num_candidates_from_tree = 64
+    for kw, status in [(dict(num_ring=41, num_sector=125), L.ERR_CAPACITY), (dict(num_ring=2, num_sector=2560), L.ERR_CAPACITY),
+                       (dict(num_ring=1, num_sector=5120), L.ERR_CAPACITY), (dict(num_ring=0), L.ERR_CAPACITY),
+                       (dict(search_ratio=float("nan")), L.ERR_INVALID_ARGUMENT), (dict(search_ratio=float("inf")), L.ERR_INVALID_ARGUMENT)]:
+        p.sc = sp = api.sc_params(**kw)
+        full += [detect(), local()]
+        assert full[-2:] == [status, status], (kw, full[-2:])
+    p.sc = sp = api.sc_params()
+    assert full[0] == L.ERR_CAPACITY
     del keep
     assert api.sc_detect_sequence(clouds, poses, n_detect=6) == good
     assert detect(nodes=api._sc_nodes(clouds, poses, None, None)[0], n_detect=0) == 0
