@@ -429,10 +429,27 @@ typedef struct cfear_coral_result {
   int32_t valid;                        /* valid_                                                      */
   int32_t count_valid;                  /* points with both covariances and finite entropies           */
   int32_t status;                       /* CFEAR_OK / CFEAR_ERR_EMPTY_CLOUD / CFEAR_ERR_CAPACITY       */
-  int32_t pad;
+  int32_t pad;                          /* diagnostic: CFEAR_CORAL_PATH_* of a served job, 0 otherwise */
 } cfear_coral_result;                   /* 40 bytes */
+/* Diagnostic, like cfear_reg_result.reserved: which code path served the job.  The kernel chooses it from the shape
+ * of the merged cloud (points, occupied grid cells, grid size); results do not depend on it and callers should not.  */
+#define CFEAR_CORAL_PATH_SCRATCH 1      /* sorted points in the per-job global scratch, not in LDS     */
+#define CFEAR_CORAL_PATH_BSEARCH 2      /* cell lookup by binary searches, not by the occupancy bitmap */
+#define CFEAR_CORAL_PATH_SORT_MASK 12   /* 0: two-level row sort                                       */
+#define CFEAR_CORAL_PATH_SORT_RADIX 4
+#define CFEAR_CORAL_PATH_SORT_BITONIC 8
 
-/* per_point (optional, host): [n_src + n_ref][3] = joint_res_, sep_res_, sep_valid in the reference's
+/* Limits.  The kernel sorts the merged cloud into a uniform grid of radius * 1.0001 cells over its bounding box, rows
+ * along y.  radius must be > 0 (not NaN), else CFEAR_ERR_INVALID_ARGUMENT.  CFEAR_ERR_CAPACITY:
+ *   - n_ref + n_src > 16384 in any job: the call returns at entry, nothing is launched, no record is written;
+ *   - per job, as results[j].status: more than 4096 grid rows (y extent / radius), more than 2^31 - 1 grid cells, or a
+ *     NaN coordinate.  The limits are not symmetric: two clusters 4200 radii apart along y are refused, along x they
+ *     are served; radius 0.05 over a 300 m scan is refused.
+ * An empty cloud is the job's status CFEAR_ERR_EMPTY_CLOUD and does not fail the call.  Any other failed job makes the
+ * batch call return that job's status (the first such job's); every record is written all the same -- failed jobs as
+ * zeros with their status, all others valid.  The per_point rows of a failed job are unspecified.
+ *
+ * per_point (optional, host): [n_src + n_ref][3] = joint_res_, sep_res_, sep_valid in the reference's
  * index order (source points first); invalid points hold the reference's initial 100.0.             */
 int cfear_coral_quality(cfear_ctx* ctx, const cfear_coral_job* job, const cfear_coral_params* par,
                         cfear_coral_result* result, double* per_point);

@@ -746,6 +746,7 @@ class CorAlRadarQuality:
         self.quality_ = [float(r["joint"]), float(r["sep"]), float(r["overlap"])]
         self.valid_ = bool(r["valid"])
         self.count_valid = int(r["count_valid"])
+        self.path = int(r["pad"])                     # CFEAR_CORAL_PATH_* (diagnostic)
         self.per_point = pp[0] if want_per_point else None
 
     def GetQualityMeasure(self):

@@ -193,12 +193,16 @@ __global__ __launch_bounds__(kCoralThreads) void coral_kernel(const CoralJob* __
   unsigned long long* keys = (unsigned long long*)smem;
   int npad = grid_sort_rows_block(smem, n, dbx, dby, (uint32_t*)(smem + kCoralRowbegOff), red_i, red_c, 512,
                                   [&](int i, int& ix, int& iy) { cell_xy(point(i), ix, iy); });
-  if (npad == 0)                                       // crowded grid row or a large cloud: generic block sort
+  int path = 0;                                        // cfear_coral_result.pad: CFEAR_CORAL_PATH_* (diagnostic)
+  if (npad == 0) {                                     // crowded grid row or a large cloud: generic block sort
+    int ib, vb;
+    path = grid_sort_is_radix(n, (long long)dbx * dby, ib, vb) ? CFEAR_CORAL_PATH_SORT_RADIX : CFEAR_CORAL_PATH_SORT_BITONIC;
     npad = grid_sort_block(smem, n, (long long)dbx * dby, red_i, [&](int i) {
       int ix, iy;
       cell_xy(point(i), ix, iy);
       return (uint32_t)(ix + iy * dbx);
     });
+  }
   CORAL_T(2);
   // ---- 3. sorted points -> scratch; cell table (key, start) -> LDS ---------------------------------
   const int per = npad / kCoralThreads;                 // 1..16 consecutive sorted elements per thread
@@ -269,6 +273,7 @@ __global__ __launch_bounds__(kCoralThreads) void coral_kernel(const CoralJob* __
   const bool bitmap = occ_off + (size_t)nw32_ll * 6 + 16 <= kCoralRowbegOff;
   uint32_t* occ = (uint32_t*)(smem + occ_off);
   const int nw32 = bitmap ? (int)nw32_ll : 0;
+  path |= (spt_in_lds ? 0 : CFEAR_CORAL_PATH_SCRATCH) | (bitmap ? 0 : CFEAR_CORAL_PATH_BSEARCH);
   unsigned short* wpref = (unsigned short*)(occ + nw32);
   if (!bitmap) {                                        // first cell of every grid row, for the binary searches
     for (int y = tid; y <= dby; y += kCoralThreads)
@@ -573,7 +578,7 @@ __global__ __launch_bounds__(kCoralThreads) void coral_kernel(const CoralJob* __
       cfear_coral_result& r = cm.results[blockIdx.x];
       r.joint = joint; r.sep = sep; r.overlap = overlap;                        // quality_ = {joint_, sep_, overlap_}
       r.valid = overlap < 0.1 ? 0 : 1;                                          // :197-204
-      r.count_valid = count_valid; r.status = CFEAR_OK; r.pad = 0;
+      r.count_valid = count_valid; r.status = CFEAR_OK; r.pad = path;
     }
   }
 #ifdef CFEAR_CORAL_TIMING

@@ -87,17 +87,25 @@ __device__ int grid_sort_rows_block(uint8_t* smem, int n, int dbx, int dby, uint
 //   n <= 8192 and cell bits + index bits <= 32: packed 32-bit keys, stable LSD radix sort on the cell digits
 //   (4 bits per pass, thread-contiguous chunks keep the input order, per-thread u16 digit counters);
 //   otherwise: bitonic sort of the 64-bit keys.
+// Which path grid_sort_block takes for n points in n_cells cells.  ib: index bits, 2^ib >= npad; vb: cell-index bits.
+__device__ __forceinline__ bool grid_sort_is_radix(int n, long long n_cells, int& ib, int& vb) {
+  int npad = (n + kGridSortThreads - 1) / kGridSortThreads * kGridSortThreads;
+  if (npad < kGridSortThreads) npad = kGridSortThreads;
+  ib = 10;
+  while ((1 << ib) < npad) ib++;
+  vb = 1;
+  while (((long long)1 << vb) < n_cells) vb++;
+  return (npad <= kGridSortRadixMaxPoints) && (vb + ib <= 32);
+}
+
 template <typename CellFn>
 __device__ int grid_sort_block(uint8_t* smem, int n, long long n_cells, int* red_i, CellFn cell_of) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   unsigned long long* keys = (unsigned long long*)smem;
   int npad = (n + kGridSortThreads - 1) / kGridSortThreads * kGridSortThreads;   // radix path: any multiple of 1024
   if (npad < kGridSortThreads) npad = kGridSortThreads;
-  int ib = 10;                                             // index bits: 2^ib >= npad
-  while ((1 << ib) < npad) ib++;
-  int vb = 1;                                              // cell-index bits
-  while (((long long)1 << vb) < n_cells) vb++;
-  const bool radix = (npad <= kGridSortRadixMaxPoints) && (vb + ib <= 32);
+  int ib, vb;
+  const bool radix = grid_sort_is_radix(n, n_cells, ib, vb);
   if (!radix) {                                            // the bitonic network needs a power of two
     npad = 1024;
     while (npad < n) npad <<= 1;
@@ -153,8 +161,10 @@ __device__ int grid_sort_block(uint8_t* smem, int n, long long n_cells, int* red
 #pragma unroll
     for (int q = 0; q < kGridSortRadixMaxPoints / kGridSortThreads; q++)
       if (q < per) {
+        // padding is what the stable sort left behind the n points, not the key value: with 2^ib points in 2^vb cells
+        // and vb + ib = 32 the last point of the last cell has the all-ones key too
         const uint32_t key = mine32[q];
-        keys[tid * per + q] = key == 0xFFFFFFFFu ? ~0ull
+        keys[tid * per + q] = tid * per + q >= n ? ~0ull
                                                  : (((unsigned long long)(key >> ib)) << 32) | (key & ((1u << ib) - 1u));
       }
     __syncthreads();

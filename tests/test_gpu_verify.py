@@ -231,3 +231,45 @@ def test_verify_host_cloud_shared_at_two_lengths(nodes):
     separate = run(pk[:m].copy())
     assert shared.tobytes() == separate.tobytes()
     assert shared["reg_ok"].all()
+
+
+def _padded_nodes(nodes):
+    """Nodes 4, 0 with a dense world-fixed cluster in their peak clouds (merged cloud past the LDS: scratch path) and
+    nodes 3, 1 with a small world-fixed cluster 3 km away (grid past the bitmap: binary-search path), each expressed in the
+    node's own frame.  Registration works on the cells and is untouched."""
+    from oracle import pyoracle as O
+    from tests import coral_geometry as G
+    from tests.test_oracle_coral import _tf
+
+    def in_frame(world, T):
+        out = world.copy()
+        out[:, :2] = _tf(world, O.xyt_inverse(T))
+        return out
+    dense = G.cluster_pair(60, 2600, 2600, (150, 200, 150, 200))
+    far = G.cluster_pair(61, 120, 120, (3000, 3008, 400, 408))
+    out = [dict(n) for n in nodes]
+    for i, extra in ((4, dense[0]), (0, dense[1]), (3, far[0]), (1, far[1])):
+        out[i]["peaks"] = np.ascontiguousarray(np.concatenate([nodes[i]["peaks"], in_frame(extra, nodes[i]["T"])]), dtype=np.float32)
+    return out
+
+
+def test_verify_candidates_on_the_scratch_and_binary_search_paths(nodes):
+    """The chain's CorAl launch (cfear_coral_launch_device, capacity taken from the batch) with one candidate whose merged
+    peak cloud lies in the global scratch and one whose grid needs the binary-search lookup.  The verification record does
+    not carry the path bits, so the same clouds at the registered poses go through coral_quality_batch, which reports them."""
+    from oracle import pyoracle as O
+    from tbv_slam_public_amd import api
+    from tests import coral_geometry as G
+    pn = _padded_nodes(nodes)
+    cands = [_candidates(nodes)[i] for i in (0, 3)]                     # 4 -> 0: scratch; 3 -> 1 (below): binary search
+    cands[1] = dict(cands[1], t=1, t_be_guess=O.xyt_compose(O.xyt_inverse(pn[3]["T"]), pn[1]["T"]) + np.array([0.2, 0.1, 0.01]))
+    got, exp = _run_both(pn, cands)
+    _compare(got, exp, cands)
+    assert got["reg_ok"].all()
+    jobs = [(pn[c["f"]]["peaks"], pn[c["f"]]["T"], pn[c["t"]]["peaks"], O.xyt_compose(pn[c["f"]]["T"], g["t_be"]), (0, 0, 0))
+            for c, g in zip(cands, got)]
+    out, _ = api.coral_quality_batch(jobs)
+    assert out["pad"][0] & G.PATH_SCRATCH and out["pad"][1] & G.PATH_BSEARCH
+    for r, g, e in zip(out, got, exp):
+        np.testing.assert_allclose([r["joint"], r["sep"], r["overlap"]], g["coral"], rtol=1e-6, atol=1e-9)
+        assert e["coral"][2] > 0.1

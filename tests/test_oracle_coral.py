@@ -109,3 +109,112 @@ def test_coral_degenerate_inputs():
     assert not ok and q[2] == 0.0 and not pp[:, 2].any()
     ok, q, pp = O.coral_quality(a, a.copy(), np.zeros(3), np.zeros(3))    # identical clouds overlap fully
     assert ok and q[2] == 1.0
+
+
+# ---- the oracle against exact rational covariances (tests/coral_geometry.py::exact_coral) --------------------------------
+def _oracle_vs_exact(ref, src, radius, src_pose=(0.0, 0.0, 0.0), weight=False):
+    from oracle import pyoracle as O
+    from tests import coral_geometry as G
+    ok, q, pp = O.coral_quality(ref, src, np.zeros(3), np.asarray(src_pose, float), (0, 0, 0), radius, weight)
+    e = G.exact_coral(ref, src, np.zeros(3), np.asarray(src_pose, float), (0, 0, 0), radius, weight)
+    keep = ~e["marginal"]
+    np.testing.assert_array_equal(pp[keep, 2].astype(bool), e["valid"][keep])         # integer outcomes stay exact
+    v = e["valid"] & keep & pp[:, 2].astype(bool)
+    worst = max(np.abs(pp[v, 0] - e["joint"][v]).max(), np.abs(pp[v, 1] - e["sep"][v]).max()) if v.any() else 0.0
+    return worst, e, (ok, q, pp)
+
+
+@pytest.mark.parametrize("radius", [0.3, 1.0, 3.0, 8.0])
+def test_oracle_against_exact_thin_neighbourhoods(radius):
+    """Where the GPU's per-point tolerance comes from: the largest |oracle - exact| over thin, near-collinear
+    neighbourhoods is the value tabulated in tests/coral_geometry.py (ORACLE_VS_EXACT), not more and not much less."""
+    from tests import coral_geometry as G
+    worst, n_pts, n_marginal = 0.0, 0, 0
+    for ref, src in G.thin_inputs(radius):
+        w, e, _ = _oracle_vs_exact(ref, src, radius, (0.01, -0.02, 0.0))
+        worst, n_pts, n_marginal = max(worst, w), n_pts + len(e["valid"]), n_marginal + int(e["marginal"].sum())
+        assert e["valid"].sum() >= 100
+    print("radius %g: max |oracle - exact| = %.3e over %d points, %d rounding-dependent" % (radius, worst, n_pts, n_marginal))
+    assert n_marginal <= 1e-3 * n_pts
+    assert G.ORACLE_VS_EXACT[radius] / 1.05 <= worst <= G.ORACLE_VS_EXACT[radius]
+    assert G.per_point_atol(radius) == max(1e-6, 4 * G.ORACLE_VS_EXACT[radius])
+
+
+def test_per_point_tolerance_table():
+    from tests import coral_geometry as G
+    assert [G.per_point_atol(r) for r in (0.25, 0.6, 1.0)] == [1e-6] * 3
+    assert G.per_point_atol(2.5) == 4 * G.ORACLE_VS_EXACT[3.0] and G.per_point_atol(5.0) == G.per_point_atol(8.0) == 4 * G.ORACLE_VS_EXACT[8.0]
+    with pytest.raises(ValueError):
+        G.per_point_atol(8.5)
+
+
+def test_oracle_against_exact_crafted_edges():
+    """The hand-placed neighbourhoods of tests/test_gpu_coral_geometry.py: none is rounding-dependent, the oracle's
+    validity is the exact one and its entropies are exact to 1e-12; plus what each case was placed for."""
+    from tests import coral_geometry as G
+    cases = G.edge_cases()
+    res = {}
+    for name, (ref, src) in cases.items():
+        worst, e, (ok, q, pp) = _oracle_vs_exact(ref, src, 1.0)
+        assert not e["marginal"].any(), name
+        assert worst <= 1e-12, (name, worst)
+        np.testing.assert_allclose(q, e["quality"], rtol=1e-12, atol=1e-15, err_msg=name)
+        assert ok == e["ok"]
+        res[name] = e
+    # source points first: the triple is valid, the pair (own set of 2) is not; the lone reference point is not although
+    # its joint set has 4 points; the reference triple is
+    np.testing.assert_array_equal(res["own_2_and_3"]["valid"], [1, 1, 1, 0, 0, 0, 1, 1, 1])
+    for k in ("px", "py", "mx", "my"):
+        assert res["at_radius_" + k]["count_valid"] == 0                 # d2 == r^2 is no neighbour
+        np.testing.assert_array_equal(res["inside_radius_" + k]["valid"], [1, 0, 0, 1, 0, 0])
+    for k in ("lattice_borders", "one_cell", "one_grid_row", "one_grid_column", "duplicates"):
+        assert res[k]["valid"].all()
+    np.testing.assert_allclose(res["duplicates"]["joint"], 0.5 * np.log(1e-8), rtol=1e-15)
+    np.testing.assert_allclose(res["duplicates"]["sep"], 0.5 * np.log(1e-8), rtol=1e-15)
+    np.testing.assert_array_equal(res["single_source_point"]["valid"], [0] + [1] * 25)
+    g = {k: G.grid_of(*cases[k], np.zeros(3), np.zeros(3)) for k in cases}
+    assert (g["one_cell"]["dbx"], g["one_cell"]["dby"]) == (1, 1)
+    assert g["one_grid_row"]["dby"] == 1 and g["one_grid_row"]["dbx"] > 1
+    assert g["one_grid_column"]["dbx"] == 1 and g["one_grid_column"]["dby"] > 1
+    assert g["at_radius_mx"]["dbx"] == 3 and g["at_radius_my"]["dby"] == 3      # the neighbour sits in the next cell
+
+
+def test_exact_coral_agrees_with_numpy_on_a_scene():
+    """exact_coral against the file's NumPy restatement on a cut of a synthetic scene (the two share only the points)."""
+    from tests import coral_geometry as G
+    clouds, gt = _peaks(8, [0, 2])
+    keep = lambda c: c[(np.abs(c[:, 0] - 30) < 12) & (np.abs(c[:, 1]) < 12)]
+    ref, src = keep(clouds[0]), keep(_tf_cloud(clouds[1], _rel(gt[0], gt[2])))
+    assert 100 <= len(ref) + len(src) <= 1500
+    e = G.exact_coral(ref, src, np.zeros(3), np.zeros(3))
+    _, q, ej, es, ev = _numpy_coral(ref, src, np.zeros(3), np.zeros(3), np.zeros(3), 1.0)
+    keep_pts = ~e["marginal"]
+    np.testing.assert_array_equal(ev[keep_pts], e["valid"][keep_pts])
+    v = ev & e["valid"]
+    assert v.sum() >= 30
+    np.testing.assert_allclose(ej[v], e["joint"][v], rtol=1e-9, atol=1e-6)
+    np.testing.assert_allclose(es[v], e["sep"][v], rtol=1e-9, atol=1e-6)
+
+
+def _tf_cloud(cloud, pose):
+    out = cloud.copy()
+    out[:, :2] = _tf(cloud, pose)
+    return out
+
+
+def test_path_matrix_inputs_are_predicted_on_their_paths():
+    """Rehearsal of tests/test_gpu_coral_geometry.py's path matrix without a GPU: predict_path puts every job on the path
+    it is meant for, and together they cover the four storage x lookup combinations and the three sorts.  (The GPU test
+    asserts the bits the kernel reports, not this prediction.)"""
+    from tests import coral_geometry as G
+    jobs = G.matrix_jobs()
+    z = np.zeros(3)
+    for name, (ref, src, want) in jobs.items():
+        assert G.predict(ref, src, z, z) == want, name
+    bits = {w for _, _, w in jobs.values()}
+    assert {b & 3 for b in bits} == {0, 1, 2, 3} and {b >> 2 for b in bits} == {0, 1, 2}
+    assert len(jobs["scratch_bitmap_bitonic_16384"][0]) + len(jobs["scratch_bitmap_bitonic_16384"][1]) == G.MAX_POINTS
+    assert len(jobs["scratch_edge"][1]) == len(jobs["lds_edge"][1]) + 1
+    # the refusals predict_path restates
+    assert G.predict_path(16385, 10, 10, 10) is None and G.predict_path(100, 10, 10, 4097) is None
+    assert G.predict_path(100, 10, 4097, 10) is not None and G.predict_path(100, 10, 65536, 32768) is None
