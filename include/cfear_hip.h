@@ -914,6 +914,73 @@ int cfear_pgo_solve(cfear_pose3d* poses, const uint64_t* ids, int32_t n, const c
  * sub-space and zero elsewhere.  CFEAR_ERR_INVALID_ARGUMENT if the last frame added no keyframe or the first one.   */
 int cfear_odometry_get_constraint(cfear_odometry* od, int32_t stream, cfear_graph_constraint* out);
 
+/* ---- after the path: trajectory evaluation (the KITTI odometry metric) ---------------------------------------------
+ * What every run script of the reference ends in: radar_kitti_benchmark/python/eval_odom.py --align 6dof, i.e.
+ * KittiEvalOdom.eval of radar_kitti_benchmark/python/kitti_odometry.py (:636-784), for a batch of (estimate, ground
+ * truth) pairs in one call.  Per pair: both trajectories are normalised by the inverse of their own first pose (:708-714),
+ * the estimate is aligned (`6dof`: umeyama_alignment without scale, :32-79), the ground-truth distances are summed
+ * serially (:123-141), and for every start frame 0, step_size, 2 step_size, ... and every length the segment ending at
+ * the first frame whose distance EXCEEDS dist[first] + length gives one row (:197-249).  Inverses are general 3 x 4
+ * inverses (np.linalg.inv), not transposes: the rotation blocks of a 6-decimal pose file are not orthonormal.
+ * All figures are radians and fractions; write_result (:608-630) prints ave_t_err * 100 [%], ave_r_err / pi * 180 * 100
+ * [deg / 100 m], the two rotation RPE figures and bias_theta * 180 / pi [deg], and the rest as they are.
+ * A trajectory's results do not depend on the other trajectories of the batch.               */
+#define CFEAR_EVAL_NUM_LENGTHS 8
+#define CFEAR_EVAL_ALIGN_NONE 0
+#define CFEAR_EVAL_ALIGN_6DOF 1
+#define CFEAR_EVAL_ALIGN_SCALE 2        /* the devkit's scale, 7dof and scale_7dof: named so that they can be refused */
+#define CFEAR_EVAL_ALIGN_7DOF 3
+#define CFEAR_EVAL_ALIGN_SCALE_7DOF 4
+typedef struct cfear_eval_params {
+  int32_t step_size;                    /* 10 (eval_odom.py); >= 1                                                   */
+  int32_t alignment;                    /* CFEAR_EVAL_ALIGN_NONE or _6DOF; anything else: CFEAR_ERR_INVALID_ARGUMENT */
+  double lengths[CFEAR_EVAL_NUM_LENGTHS];   /* 100 ... 800 m (:90); positive and strictly ascending                  */
+} cfear_eval_params;                    /* 72 bytes */
+void cfear_eval_params_default(cfear_eval_params* p);
+typedef struct cfear_eval_summary {
+  double ave_t_err, ave_r_err;          /* means of t_err / len and r_err / len over all rows; 0 without rows (:264-287) */
+  double ate;                           /* compute_ATE (:477-505): RMS position difference after the alignment       */
+  double rpe_trans, rpe_trans_dev;      /* compute_RPE (:508-583) over consecutive frames: mean and population       */
+  double rpe_rot, rpe_rot_dev;          /*   standard deviation of the translation and of the rotation error         */
+  double bias_x, bias_y;                /* means of the relative error's x and y                                     */
+  double bias_theta;                    /* mean of rot2eul(...)[0] as the devkit writes it (:14-18, :550-551): the angle
+                                           about x, 0 for planar trajectories                                        */
+  double rmse_trans;                    /* sqrt of the mean squared relative translation error                       */
+  double seg_t_err[CFEAR_EVAL_NUM_LENGTHS], seg_r_err[CFEAR_EVAL_NUM_LENGTHS];   /* compute_segment_error (:442-475); 0 where seg_count is 0 */
+  double align[12];                     /* the [r | t] the estimate was left-multiplied by (identity for `none`)     */
+  int64_t n_rows;
+  int32_t seg_count[CFEAR_EVAL_NUM_LENGTHS];
+  int32_t n_poses;
+  int32_t status;                       /* CFEAR_OK; CFEAR_ERR_SOLVER: a figure is not finite (a singular pose), or the
+                                           6dof alignment is undetermined (all positions on one line; identity rotation used) */
+} cfear_eval_summary;                   /* 360 bytes */
+typedef struct cfear_eval_row {         /* one line of errors/NN.txt (:248), plus the pair and last_frame            */
+  int32_t trajectory, first_frame, last_frame, pad;
+  double length, r_err, t_err, speed;   /* r_err and t_err are already divided by the length; speed = len / (0.1 frames) */
+} cfear_eval_row;                       /* 48 bytes */
+/* est, gt: [..][12] doubles, the rows of the 3 x 4 pose as a KITTI line holds them; both host or both device, 16-byte
+ * aligned.  Pair t is poses offsets[t] .. offsets[t] + lengths[t] - 1 of both arrays (offsets NULL: the pairs follow each
+ * other); offsets and lengths are host arrays.  summaries [n_traj] and rows [row_cap] (optional; ordered by pair, start
+ * frame, length) are host or device; *n_rows (optional, host) receives the number of rows of the batch.  With more rows
+ * than row_cap the table holds the first row_cap and the call returns CFEAR_ERR_CAPACITY after completing the summaries.
+ * Refused with CFEAR_ERR_INVALID_ARGUMENT, because the devkit does not define them: a pair with fewer than 2 poses,
+ * step_size < 1, an alignment other than none / 6dof.  The call synchronises once (the 3 x 3 SVDs are host code).      */
+int cfear_eval_trajectories(cfear_ctx* ctx, const double* est, const double* gt, const int64_t* offsets, const int32_t* lengths,
+                            int32_t n_traj, const cfear_eval_params* par, cfear_eval_summary* summaries, cfear_eval_row* rows,
+                            int64_t row_cap, int64_t* n_rows);
+/* The refusals of cfear_eval_trajectories as host code, for callers that hold the two trajectories of a pair separately:
+ * also refuses a pair whose estimate and ground truth differ in length (the devkit normalises only the estimate's keys). */
+int cfear_eval_check(const cfear_eval_params* par, const int32_t* est_lengths, const int32_t* gt_lengths, int32_t n_traj);
+/* Host helpers, no context.  cfear_kitti_read: load_poses_from_txt (:93-121), lines of 12 numbers or of 13 with the frame
+ * index first (which must count 0, 1, 2, ...: CFEAR_ERR_FORMAT otherwise, as for any other line).  *n_out = poses in the
+ * file; poses [cap][12] may be NULL with cap 0 to ask for the count; CFEAR_ERR_CAPACITY if the file holds more than cap.
+ * cfear_kitti_write: EvalTrajectory::Write (cfear_radarodometry/src/cfear_radarodometry/eval_trajectory.cpp:169-183),
+ * std::fixed with 6 decimals.  cfear_kitti_from_xyt: planar (x, y, theta) to [cos -sin 0 x; sin cos 0 y; 0 0 1 0];
+ * stride = doubles between poses (3 for packed triples, 7 for the pose of consecutive cfear_frame_info records).      */
+int cfear_kitti_read(const char* path, double* poses, int64_t cap, int64_t* n_out);
+int cfear_kitti_write(const char* path, const double* poses, int64_t n);
+int cfear_kitti_from_xyt(const double* xyt, int64_t n, int64_t stride, double* poses);
+
 #ifdef __cplusplus
 }
 #endif

@@ -895,3 +895,35 @@ inline std::vector<cfear_verify_result> VerifyLoopCandidates(CFEAR_Radarodometry
   return res;
 }
 }  // namespace tbv_slam
+
+// Trajectory evaluation (cfear_eval_trajectories): the KITTI odometry metric of radar_kitti_benchmark/python/eval_odom.py
+// for a batch of (estimate, ground truth) pairs.  A trajectory is [n][12] doubles, the rows of the 3 x 4 pose (what
+// cfear_kitti_read returns and cfear_kitti_from_xyt builds from planar poses).  -> one summary per pair, and every segment
+// row of the batch in `rows` when it is given.  Figures are radians and fractions (include/cfear_hip.h).
+inline std::vector<cfear_eval_summary> EvalTrajectories(CFEAR_Radarodometry::Context& ctx, const std::vector<std::vector<double>>& est,
+                                                        const std::vector<std::vector<double>>& gt,
+                                                        const cfear_eval_params* par = nullptr,
+                                                        std::vector<cfear_eval_row>* rows = nullptr) {
+  cfear_eval_params def;
+  if (!par) { cfear_eval_params_default(&def); par = &def; }
+  if (est.size() != gt.size()) throw CFEAR_Radarodometry::CfearError(CFEAR_ERR_INVALID_ARGUMENT, "one ground truth per estimate");
+  std::vector<int32_t> le(est.size()), lg(gt.size());
+  std::vector<double> e, g;
+  int64_t cap = 0;
+  for (size_t i = 0; i < est.size(); i++) {
+    le[i] = (int32_t)(est[i].size() / 12);
+    lg[i] = (int32_t)(gt[i].size() / 12);
+    e.insert(e.end(), est[i].begin(), est[i].begin() + (size_t)le[i] * 12);
+    g.insert(g.end(), gt[i].begin(), gt[i].begin() + (size_t)lg[i] * 12);
+    cap += ((int64_t)le[i] + std::max(par->step_size, 1) - 1) / std::max(par->step_size, 1) * CFEAR_EVAL_NUM_LENGTHS;
+  }
+  const int rc = cfear_eval_check(par, le.data(), lg.data(), (int32_t)le.size());
+  if (rc != CFEAR_OK) throw CFEAR_Radarodometry::CfearError(rc, "evaluation refused: step_size, alignment, or a pair's lengths");
+  std::vector<cfear_eval_summary> out(est.size());
+  int64_t n_rows = 0;
+  if (rows) rows->resize((size_t)cap);
+  ctx.check(cfear_eval_trajectories(ctx.get(), e.data(), g.data(), nullptr, le.data(), (int32_t)le.size(), par, out.data(),
+                                    rows ? rows->data() : nullptr, rows ? cap : 0, &n_rows));
+  if (rows) rows->resize((size_t)n_rows);
+  return out;
+}

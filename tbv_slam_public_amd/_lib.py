@@ -233,6 +233,8 @@ EXPORTS = [
     "cfear_ctx_get_stream", "cfear_ctx_set_option", "cfear_ctx_get_option",
     "cfear_rccl_unique_id", "cfear_rccl_comm_init", "cfear_rccl_comm_destroy",
     "cfear_candidate_pipe_create", "cfear_candidate_pipe_submit", "cfear_candidate_pipe_collect", "cfear_candidate_pipe_destroy", "cfear_candidate_pipe_stats",
+    "cfear_eval_params_default", "cfear_eval_trajectories", "cfear_eval_check", "cfear_kitti_read", "cfear_kitti_write",
+    "cfear_kitti_from_xyt",
 ]
 
 PIPE_GRAPH, PIPE_TIMING = 1, 2      # enum { CFEAR_PIPE_GRAPH, CFEAR_PIPE_TIMING }
@@ -279,6 +281,25 @@ class GraphNode(C.Structure):
                 ("cells", C.c_void_p), ("n_cells", C.c_int32), ("radius", C.c_float), ("weight_intensity", C.c_int32),
                 ("pad", C.c_int32), ("constraints", C.POINTER(GraphConstraint)), ("n_constraints", C.c_int32), ("pad2", C.c_int32)]
 
+
+EVAL_NUM_LENGTHS = 8
+EVAL_ALIGN = {"none": 0, None: 0, "6dof": 1, "scale": 2, "7dof": 3, "scale_7dof": 4}      # CFEAR_EVAL_ALIGN_*
+
+
+class EvalParams(C.Structure):      # cfear_eval_params
+    _fields_ = [("step_size", C.c_int32), ("alignment", C.c_int32), ("lengths", C.c_double * EVAL_NUM_LENGTHS)]
+
+
+EVAL_SUMMARY_DTYPE = np.dtype([("ave_t_err", "<f8"), ("ave_r_err", "<f8"), ("ate", "<f8"), ("rpe_trans", "<f8"),
+                               ("rpe_trans_dev", "<f8"), ("rpe_rot", "<f8"), ("rpe_rot_dev", "<f8"), ("bias_x", "<f8"),
+                               ("bias_y", "<f8"), ("bias_theta", "<f8"), ("rmse_trans", "<f8"),
+                               ("seg_t_err", "<f8", (EVAL_NUM_LENGTHS,)), ("seg_r_err", "<f8", (EVAL_NUM_LENGTHS,)),
+                               ("align", "<f8", (12,)), ("n_rows", "<i8"), ("seg_count", "<i4", (EVAL_NUM_LENGTHS,)),
+                               ("n_poses", "<i4"), ("status", "<i4")])
+assert EVAL_SUMMARY_DTYPE.itemsize == 360
+EVAL_ROW_DTYPE = np.dtype([("trajectory", "<i4"), ("first_frame", "<i4"), ("last_frame", "<i4"), ("pad", "<i4"),
+                           ("length", "<f8"), ("r_err", "<f8"), ("t_err", "<f8"), ("speed", "<f8")])
+assert EVAL_ROW_DTYPE.itemsize == 48
 
 _LIB = None
 
@@ -428,5 +449,13 @@ def lib():
     L.cfear_candidate_pipe_collect.argtypes = [vp, C.c_int64, vp]
     L.cfear_candidate_pipe_destroy.argtypes = [vp]
     L.cfear_candidate_pipe_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    L.cfear_eval_params_default.argtypes = [C.POINTER(EvalParams)]
+    L.cfear_eval_params_default.restype = None
+    L.cfear_eval_trajectories.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.POINTER(EvalParams), vp, vp, C.c_int64,
+                                          C.POINTER(C.c_int64)]
+    L.cfear_eval_check.argtypes = [C.POINTER(EvalParams), vp, vp, C.c_int32]
+    L.cfear_kitti_read.argtypes = [C.c_char_p, vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.cfear_kitti_write.argtypes = [C.c_char_p, vp, C.c_int64]
+    L.cfear_kitti_from_xyt.argtypes = [vp, C.c_int64, C.c_int64, vp]
     _LIB = L
     return L

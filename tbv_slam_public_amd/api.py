@@ -1873,3 +1873,157 @@ def pose_graph_optimize(poses, ids, constraints, **par):
     out = np.array([list(a.p) + list(a.q) for a in arr])
     return out, dict(initial_cost=s.initial_cost, final_cost=s.final_cost, iterations=s.iterations, usable=bool(s.usable),
                      num_residual_blocks=s.num_residual_blocks, linear_iterations=s.linear_iterations)
+
+
+# ------------------------------------------------------------------------------------------------
+# trajectory evaluation: the KITTI odometry metric (radar_kitti_benchmark/python/kitti_odometry.py)
+# ------------------------------------------------------------------------------------------------
+def eval_params(step_size=10, alignment="6dof", lengths=None):
+    """cfear_eval_params: eval_odom.py's defaults.  alignment: None / "none" or "6dof"; the devkit's "scale", "7dof" and
+    "scale_7dof" are passed on and refused by the library."""
+    p = L.EvalParams()
+    L.lib().cfear_eval_params_default(C.byref(p))
+    if alignment not in L.EVAL_ALIGN:
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "unknown alignment %r" % (alignment,))
+    p.step_size, p.alignment = int(step_size), L.EVAL_ALIGN[alignment]
+    if lengths is not None:
+        if len(lengths) != L.EVAL_NUM_LENGTHS:
+            raise L.CfearError(L.ERR_INVALID_ARGUMENT, "%d lengths are evaluated" % L.EVAL_NUM_LENGTHS)
+        for k, v in enumerate(lengths):
+            p.lengths[k] = float(v)
+    return p
+
+
+def kitti_read(path):
+    """load_poses_from_txt (kitti_odometry.py:93-121) -> float64 [n, 12]; lines of 12 numbers, or of 13 with the index first."""
+    lib = L.lib()
+    n = C.c_int64()
+    rc = lib.cfear_kitti_read(os.fsencode(path), None, 0, C.byref(n))
+    if rc != L.OK:
+        raise L.CfearError(rc, "cfear_kitti_read(%s)" % path)
+    out = np.zeros((n.value, 12), np.float64)
+    rc = lib.cfear_kitti_read(os.fsencode(path), out.ctypes.data, n.value, C.byref(n))
+    if rc != L.OK:
+        raise L.CfearError(rc, "cfear_kitti_read(%s)" % path)
+    return out
+
+
+def kitti_write(path, poses):
+    """EvalTrajectory::Write (eval_trajectory.cpp:169-183): one pose per line, 12 numbers with 6 decimals."""
+    poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+    rc = L.lib().cfear_kitti_write(os.fsencode(path), poses.ctypes.data, poses.shape[0])
+    if rc != L.OK:
+        raise L.CfearError(rc, "cfear_kitti_write(%s)" % path)
+
+
+def kitti_from_xyt(xyt):
+    """Planar poses [..., 3] (x, y, theta), e.g. OdometryKeyframeFuser's info["pose"] of one stream over time -> [..., 12]."""
+    xyt = np.ascontiguousarray(xyt, np.float64)
+    assert xyt.shape[-1] == 3
+    out = np.zeros(xyt.shape[:-1] + (12,), np.float64)
+    rc = L.lib().cfear_kitti_from_xyt(xyt.ctypes.data, xyt.size // 3, 3, out.ctypes.data)
+    if rc != L.OK:
+        raise L.CfearError(rc, "cfear_kitti_from_xyt")
+    return out
+
+
+def eval_trajectories(est, gt, lengths=None, step_size=10, alignment="6dof", want_rows=True, par=None, ctx=None):
+    """The KITTI odometry metric of a batch of (estimate, ground truth) pairs in one call (cfear_eval_trajectories).
+
+    est, gt: lists of [n_i, 12] arrays (one per pair), or one [N, 12] array / torch CUDA tensor each holding the pairs one
+    after the other with `lengths` [n_traj] (a single pair when lengths is None).  Returns (summaries, rows): structured
+    arrays of L.EVAL_SUMMARY_DTYPE [n_traj] and L.EVAL_ROW_DTYPE [n_rows] (None unless want_rows); figures in radians and
+    fractions (write_result's conversions: include/cfear_hip.h).  A pair whose two trajectories differ in length, one with
+    fewer than 2 poses, step_size < 1 and the scale / 7dof alignments raise CfearError(ERR_INVALID_ARGUMENT)."""
+    p = par if par is not None else eval_params(step_size, alignment)
+    lib = L.lib()
+    if isinstance(est, (list, tuple)):
+        if not isinstance(gt, (list, tuple)) or len(gt) != len(est):
+            raise L.CfearError(L.ERR_INVALID_ARGUMENT, "est and gt must hold the same number of trajectories")
+        est = [np.asarray(e, np.float64).reshape(-1, 12) for e in est]
+        gt = [np.asarray(g, np.float64).reshape(-1, 12) for g in gt]
+        le = np.array([e.shape[0] for e in est], np.int32)
+        lg = np.array([g.shape[0] for g in gt], np.int32)
+        rc = lib.cfear_eval_check(C.byref(p), le.ctypes.data, lg.ctypes.data, len(est))
+        if rc != L.OK:
+            raise L.CfearError(rc, "evaluation refused: step_size >= 1, alignment none / 6dof, every pair of one length >= 2")
+        est = np.ascontiguousarray(np.concatenate(est, 0)) if est else np.zeros((0, 12))
+        gt = np.ascontiguousarray(np.concatenate(gt, 0)) if gt else np.zeros((0, 12))
+        lengths = le
+    else:
+        if _is_torch(est) != _is_torch(gt):
+            raise L.CfearError(L.ERR_INVALID_ARGUMENT, "est and gt must both be torch CUDA tensors or both be host arrays")
+        if _is_torch(est):
+            import torch
+            for name, x in (("est", est), ("gt", gt)):
+                # the kernels read 96 bytes per pose: anything but contiguous float64 [N, 12] on the device would be read past its end
+                if x.dtype != torch.float64 or x.dim() != 2 or x.shape[1] != 12 or not x.is_cuda or not x.is_contiguous():
+                    raise L.CfearError(L.ERR_INVALID_ARGUMENT, "%s: a contiguous float64 [N, 12] CUDA tensor is needed, got %s %s on %s"
+                                       % (name, x.dtype, tuple(x.shape), x.device))
+        else:
+            est, gt = (np.ascontiguousarray(np.asarray(a, np.float64).reshape(-1, 12)) for a in (est, gt))
+        n_e, n_g = est.shape[0], gt.shape[0]
+        lengths = np.array([n_e], np.int32) if lengths is None else np.ascontiguousarray(lengths, np.int32)
+        lg = lengths if n_g == n_e else np.array([n_g], np.int32)
+        rc = lib.cfear_eval_check(C.byref(p), lengths.ctypes.data, lg.ctypes.data, len(lengths))
+        if rc != L.OK or n_e != n_g or int(lengths.sum()) != n_e or len(lg) != len(lengths):
+            raise L.CfearError(L.ERR_INVALID_ARGUMENT, "evaluation refused: step_size >= 1, alignment none / 6dof, est and gt "
+                               "of one shape, lengths >= 2 that add up to it")
+    ctx = ctx or default_context()
+    n_traj = len(lengths)
+    summaries = np.zeros(n_traj, L.EVAL_SUMMARY_DTYPE)
+    rows, cap = None, 0
+    if want_rows:
+        # every start frame has at most one row per length
+        cap = int(sum((int(n) + p.step_size - 1) // p.step_size for n in lengths)) * L.EVAL_NUM_LENGTHS
+        rows = np.zeros(max(cap, 1), L.EVAL_ROW_DTYPE)
+    n_rows = C.c_int64()
+    ctx.check(ctx._lib.cfear_eval_trajectories(ctx.h, _ptr(est)[0], _ptr(gt)[0], None, lengths.ctypes.data, n_traj, C.byref(p),
+                                               summaries.ctypes.data, rows.ctypes.data if want_rows else None, cap,
+                                               C.byref(n_rows)))
+    return summaries, (rows[:n_rows.value] if want_rows else None)
+
+
+def eval_result_lines(seq, s):
+    """write_result (kitti_odometry.py:608-630): the 12 lines of result.txt for one summary record."""
+    return ["Sequence-nr, {} \n".format(seq),
+            "Trans.err.(%), {:.5f} \n".format(s["ave_t_err"] * 100),
+            "Rot.err.(deg/100m), {:.5f} \n".format(s["ave_r_err"] / np.pi * 180 * 100),
+            "ATE(m), {:.5f} \n".format(s["ate"]),
+            "RPE(m), {:.5f} \n".format(s["rpe_trans"]),
+            "RPE-dev(m), {:.5f} \n".format(s["rpe_trans_dev"]),
+            "RPE(deg), {:.5f} \n".format(s["rpe_rot"] * 180 / np.pi),
+            "RPE-dev(deg), {:.5f} \n".format(s["rpe_rot_dev"] * 180 / np.pi),
+            "bias-x(m), {:.6f} \n".format(s["bias_x"]),
+            "bias-y(m), {:.6f} \n".format(s["bias_y"]),
+            "bias-theta(deg), {:.6f} \n".format(s["bias_theta"] * 180 / np.pi),
+            "RMSE (m), {:.5f} \n".format(s["rmse_trans"])]
+
+
+class KittiEvalOdom:
+    """KittiEvalOdom of radar_kitti_benchmark/python/kitti_odometry.py (:82-91, :636-784) without the plots: eval() scores
+    every NN.txt of result_dir (NN = 00 .. 34, as the devkit's seq_list) against gt_dir/NN.txt in ONE evaluator call and
+    writes result_dir/result.txt and result_dir/errors/NN.txt in the devkit's format, so the directory can be diffed
+    against one the devkit wrote."""
+
+    def __init__(self, step_size=10, ctx=None):
+        self.step_size = step_size
+        self.lengths = [100, 200, 300, 400, 500, 600, 700, 800]
+        self.ctx = ctx
+
+    def eval(self, gt_dir, result_dir, alignment=None, seqs=None):
+        if seqs is None:
+            seqs = [i for i in range(35) if os.path.exists(os.path.join(result_dir, "%02d.txt" % i))]
+        self.eval_seqs = list(seqs)
+        est = [kitti_read(os.path.join(result_dir, "%02d.txt" % i)) for i in self.eval_seqs]
+        gt = [kitti_read(os.path.join(gt_dir, "%02d.txt" % i)) for i in self.eval_seqs]
+        summaries, rows = eval_trajectories(est, gt, par=eval_params(self.step_size, alignment, self.lengths), ctx=self.ctx)
+        os.makedirs(os.path.join(result_dir, "errors"), exist_ok=True)
+        with open(os.path.join(result_dir, "result.txt"), "w") as f:
+            for k, i in enumerate(self.eval_seqs):
+                r = rows[rows["trajectory"] == k]
+                with open(os.path.join(result_dir, "errors", "%02d.txt" % i), "w") as fe:       # save_sequence_errors, :251-262
+                    fe.writelines("%d %r %r %d %r\n" % (a, float(b), float(c), int(d), float(e)) for a, b, c, d, e in
+                                  zip(r["first_frame"], r["r_err"], r["t_err"], r["length"], r["speed"]))
+                f.writelines(eval_result_lines(i, summaries[k]))
+        return summaries, rows

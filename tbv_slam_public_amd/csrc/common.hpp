@@ -43,6 +43,7 @@ enum WsSlot : int {
   kWsCandResults = 13,    // cfear_register_candidates: results for a host caller
   kWsVerify = 14,         // the verification chain's records and results
   kWsScSequence = 15,     // whole-graph Scan Context: node tables, descriptor database, query chunks
+  kWsEval = 16,           // trajectory evaluation: staged and normalised poses, distances, tables, staged outputs
 };
 
 struct cfear_ctx {
@@ -55,7 +56,7 @@ struct cfear_ctx {
   std::vector<hipEvent_t> event_pool;
   // grow-only device workspaces (indexed by WsSlot so stages of one pipeline do not alias)
   struct Ws { void* p = nullptr; size_t bytes = 0; };
-  Ws ws[16];
+  Ws ws[17];
   // pinned host staging for small read-backs
   void* pinned = nullptr;
   size_t pinned_bytes = 0;
