@@ -1,0 +1,104 @@
+#!/usr/bin/env python
+"""Sweeps in, corrected and scored trajectories out: N synthetic laps, every stage one batched device call.
+
+  radar sweeps  -> CFEAR-3 odometry of all laps at once (OdometryKeyframeFuser, one stream per lap); every keyframe
+                   leaves a graph node and the odometry constraint of cfear_odometry_get_constraint
+  per lap       -> loop candidates of the whole graph in one call (api.sc_detect_sequence)
+  all laps      -> every candidate registered, scored and classified in one call (api.verify_loop_candidates)
+  all laps      -> every pose graph solved in ONE call (api.pose_graph_optimize_batch, one wavefront per graph)
+  all laps      -> raw and corrected trajectories scored by ONE api.eval_trajectories call (KITTI odometry metric)
+
+The laps are the closed circle of examples/loop_closure_demo.py with different landmark seeds.  --loop-scaling weighs the
+loops: the reference's 500000 leaves the graph leaning on odometry, 1 trusts the verified loops as much as a step.
+    python examples/slam_batch_demo.py [--laps 3] [--frames 68] [--loop-scaling 1]"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import loop_closure_demo as demo          # noqa: E402
+
+
+def run(n_laps=3, n_frames=68, loop_scaling=1.0, log=None):
+    """-> dict(raw, corrected, gt [lap][node, 3], keyframes [lap] frame indices, loops [lap] accepted constraints, pgo [lap] summaries, before, after)."""
+    from tbv_slam_public_amd import api
+    backend = demo.HipBackend()
+    scenes = [demo.circle_scene(seed=21 + lap) for lap in range(n_laps)]
+    gt = []
+    for sc in scenes:
+        g = np.stack([sc.pose_at(f, n_frames) for f in range(n_frames)])
+        gt.append(np.array([demo.xyt_compose(demo.xyt_inverse(g[0]), x) for x in g]))
+    # ---- odometry of all laps, one stream each; nodes and odometry constraints as the keyframes arrive ------------------
+    od = api.OdometryKeyframeFuser(n_laps, scenes[0].rows, scenes[0].cols, api.odometry_preset("CFEAR-3", "oxford", keep_nodes=1))
+    raw = np.zeros((n_laps, n_frames, 3))
+    kf = [[] for _ in range(n_laps)]                                             # the frames that became keyframes = graph nodes
+    nodes = [[] for _ in range(n_laps)]
+    cons = [[] for _ in range(n_laps)]
+    for f in range(n_frames):
+        imgs = np.stack([sc.render(f, n_frames) for sc in scenes])
+        info = od.process(imgs)
+        raw[:, f] = info["pose"]
+        for lap in range(n_laps):
+            if not info["keyframe_added"][lap]:
+                continue
+            nd = od.node(lap)
+            nodes[lap].append(dict(scan=nd["scan"], peaks=nd["peaks"]))
+            kf[lap].append(f)
+            c = od.constraint(lap)                                               # None for a stream's first keyframe
+            if c is not None:
+                cons[lap].append(c)
+    od.close()
+    poses = [raw[lap, kf[lap]] for lap in range(n_laps)]                         # node poses; ids = keyframe ordinals 0, 1, 2, ...
+    gt = [gt[lap][kf[lap]] for lap in range(n_laps)]
+    # ---- loop candidates per graph, then ONE verification call for all laps ---------------------------------------------
+    cands, owner = [], []
+    for lap in range(n_laps):
+        found = api.sc_detect_sequence([nd["peaks"] for nd in nodes[lap]], poses[lap], n_aggregate=1, n_detect=len(kf[lap]) - 1)
+        for i, group in enumerate(found):
+            for c in group:
+                to = c["nn_idx"]
+                rel = [demo.xyt_compose(demo.xyt_inverse(poses[lap][k]), poses[lap][k + 1]) for k in range(to, i)]
+                guess = demo.xyt_compose(demo.xyt_inverse(np.asarray(c["Taug"], np.float64)), np.array([0.0, 0.0, c["yaw_diff_rad"]]))
+                cands.append({"from": i, "to": to, "from_pose": poses[lap][i], "t_be_guess": guess, "sc_sim": c["min_dist"],
+                              "odom_bounds": backend.odom_bounds(np.array(rel).reshape(-1, 3))})
+                owner.append(lap)
+    jobs = [dict(from_scan=nodes[lap][c["from"]]["scan"], to_scan=nodes[lap][c["to"]]["scan"], from_peaks=nodes[lap][c["from"]]["peaks"],
+                 to_peaks=nodes[lap][c["to"]]["peaks"], from_pose=c["from_pose"], t_be_guess=c["t_be_guess"], sc_sim=c["sc_sim"],
+                 odom_bounds=c["odom_bounds"], group=lap * n_frames + c["from"]) for lap, c in zip(owner, cands)]
+    res = api.verify_loop_candidates(jobs) if jobs else None
+    loops = [[] for _ in range(n_laps)]
+    for k, (lap, c) in enumerate(zip(owner, cands)):
+        if res is not None and res["accepted"][k]:
+            # the odometry constraints number the keyframes 0, 1, 2, ... per stream: so do the loops
+            loops[lap].append(dict(id_begin=c["from"], id_end=c["to"], t_be=res["t_be"][k].copy(), information=np.eye(6), type=1))
+    # ---- every graph in one solve, every trajectory in one evaluation ---------------------------------------------------
+    graphs = [(poses[lap], np.arange(len(kf[lap])), cons[lap] + loops[lap]) for lap in range(n_laps)]
+    solved = api.pose_graph_optimize_batch(graphs, loop_scaling=loop_scaling)
+    corrected = []
+    for out, _ in solved:
+        xyt = np.zeros((len(out), 3))
+        for i, p in enumerate(out):
+            xyt[i] = [p[0], p[1], 2.0 * np.arctan2(p[5], p[6])]
+        corrected.append(xyt)
+    est = [api.kitti_from_xyt(poses[lap]) for lap in range(n_laps)] + [api.kitti_from_xyt(c) for c in corrected]
+    summaries, _ = api.eval_trajectories(est, [api.kitti_from_xyt(g) for g in gt] * 2, alignment="none", want_rows=False)
+    if log:
+        log("lap  nodes  odometry constraints  loops  LM iterations  end-point gap raw -> corrected (m)   ATE raw -> corrected (m)")
+        for lap in range(n_laps):
+            gap = [np.hypot(*(t[-1, :2] - gt[lap][-1, :2])) for t in (poses[lap], corrected[lap])]
+            log("%3d %6d %21d %6d %14d %18.3f -> %.3f %22.3f -> %.3f" % (lap, len(kf[lap]), len(cons[lap]), len(loops[lap]), solved[lap][1]["iterations"],
+                                                                   gap[0], gap[1], summaries[lap]["ate"], summaries[n_laps + lap]["ate"]))
+    return dict(raw=poses, keyframes=kf, corrected=corrected, gt=gt, loops=loops, pgo=[s for _, s in solved], before=summaries[:n_laps],
+                after=summaries[n_laps:])
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--laps", type=int, default=3)
+    ap.add_argument("--frames", type=int, default=68)
+    ap.add_argument("--loop-scaling", type=float, default=1.0)
+    a = ap.parse_args()
+    run(a.laps, a.frames, a.loop_scaling, log=print)

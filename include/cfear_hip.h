@@ -86,9 +86,13 @@ int cfear_ctx_get_stream(const cfear_ctx* ctx, void** hip_stream);
  *   CFEAR_OPT_HOST_TIMELINE  1: the batched odometry prints where the host spends a frame (every 256 calls).
  *   CFEAR_OPT_SC_QUERY_CHUNK 0 (default): cfear_sc_detect_sequence sizes its query chunks by a device budget; n >= 1:
  *                            at most n query nodes per chunk, so that small graphs cross chunk boundaries.
+ *   CFEAR_OPT_PGO_GRAPH_CHUNK n >= 1: cfear_pgo_solve_batch takes at most n graphs per chunk (on top of its device budget),
+ *                            so that small batches cross chunk boundaries; INT32_MAX lifts the cap again.  A context that
+ *                            never set it reads 0 and sizes its chunks by the budget alone; 0 itself is not a cap and,
+ *                            unlike the options above, is refused.
  * Returns CFEAR_ERR_INVALID_ARGUMENT for an unknown option or a value outside its range.                          */
 enum cfear_option { CFEAR_OPT_FUSED_DECODE = 0, CFEAR_OPT_MATCHER_LDS_KB = 1, CFEAR_OPT_MATCHER_WAVES = 2,
-                    CFEAR_OPT_HOST_TIMELINE = 3, CFEAR_OPT_SC_QUERY_CHUNK = 4, CFEAR_OPT_COUNT = 5 };
+                    CFEAR_OPT_HOST_TIMELINE = 3, CFEAR_OPT_SC_QUERY_CHUNK = 4, CFEAR_OPT_PGO_GRAPH_CHUNK = 5, CFEAR_OPT_COUNT = 6 };
 int cfear_ctx_set_option(cfear_ctx* ctx, int32_t option, int64_t value);
 int cfear_ctx_get_option(const cfear_ctx* ctx, int32_t option, int64_t* value);
 /* Per-kernel-family device time measured with hipEvents on the context's stream.
@@ -887,8 +891,8 @@ int cfear_graph_destroy(cfear_graph* g);
  * types -- the loop_v* values are never read, :79-88) or the constraint's own information, times 1 / loop_scaling for
  * loop constraints; no loss on odometry, CauchyLoss(0.1) on loop_appearance; mini_loop / candidate constraints are not
  * optimised; the first node (smallest id) is constant; quaternions move on ceres::EigenQuaternionParameterization;
- * ceres::Solve with the default trust-region LM and max_num_iterations 200.  Host code (csrc/pgo.hip says why), no
- * context.  poses [n] in/out, ids [n] strictly ascending (the reference's node map order).                        */
+ * ceres::Solve with the default trust-region LM and max_num_iterations 200.  cfear_pgo_solve is host code and takes one
+ * graph and no context; cfear_pgo_solve_batch below solves many on the device (csrc/pgo.hip says what runs where).  poses [n] in/out, ids [n] strictly ascending (the reference's node map order).                        */
 typedef struct cfear_pgo_params {        /* tbv_slam::OptimizationParamsConfig as CeresLeastSquares::Parameters sets it */
   double loop_vxx, loop_vyy, loop_vtt, odom_vxx, odom_vyy, odom_vtt, loop_scaling;
   int32_t replace_cov_by_identity;
@@ -905,6 +909,23 @@ typedef struct cfear_pgo_summary {
 } cfear_pgo_summary;
 int cfear_pgo_solve(cfear_pose3d* poses, const uint64_t* ids, int32_t n, const cfear_graph_constraint* constraints,
                     int32_t m, const cfear_pgo_params* par, cfear_pgo_summary* summary);
+/* n_graphs independent graphs in one call, one wavefront each (csrc/pgo_batch.hip): graph g owns poses / ids
+ * [node_offsets[g], node_offsets[g + 1]) and constraints [constraint_offsets[g], constraint_offsets[g + 1]); both offset
+ * arrays hold n_graphs + 1 entries, start at 0 and end at n_nodes / n_constraints (the lengths of the arrays, so that a
+ * mis-sized table is refused).  One parameter set for the batch, summaries [n_graphs].  Per graph the semantics are those
+ * of cfear_pgo_solve, decision for decision: the same residual blocks in the same order, loss, constant first node,
+ * parameterisation, column scaling, trust-region bookkeeping and tolerances; sums that the host runs serially are split
+ * over the lanes in an order fixed by the graph alone, so iterations, usable and num_residual_blocks equal the host's and
+ * poses and costs agree with it to summation-order noise (EXPERIMENTS.md, "Batched pose-graph optimisation").  A graph's poses and summary are
+ * bit-identical whatever else the batch holds, wherever the graph sits in it and however the batch is chunked
+ * (CFEAR_OPT_PGO_GRAPH_CHUNK).  All arrays are host memory; the call returns when poses and summaries are written.
+ * A graph that cfear_pgo_solve would refuse (ids not ascending, a constraint on an unknown node, nothing to optimise,
+ * information that is not positive definite) fails the whole call with CFEAR_ERR_INVALID_ARGUMENT before anything is
+ * launched or written; a graph whose state exceeds one chunk's device budget (millions of nodes) fails it with
+ * CFEAR_ERR_CAPACITY.  *failed_graph (optional) is the first such graph, or -1; cfear_last_error names it too.       */
+int cfear_pgo_solve_batch(cfear_ctx* ctx, cfear_pose3d* poses, const uint64_t* ids, const int64_t* node_offsets, int64_t n_nodes,
+                          const cfear_graph_constraint* constraints, const int64_t* constraint_offsets, int64_t n_constraints,
+                          int32_t n_graphs, const cfear_pgo_params* par, cfear_pgo_summary* summaries, int32_t* failed_graph);
 
 /* OdometryKeyframeFuser::AddToGraph (odometrykeyframefuser.cpp:428-445) for `stream`: the odometry constraint from the
  * keyframe added by the LAST processed frame to the keyframe before it -- id_begin / id_end are the stream's keyframe

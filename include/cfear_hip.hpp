@@ -927,3 +927,35 @@ inline std::vector<cfear_eval_summary> EvalTrajectories(CFEAR_Radarodometry::Con
   if (rows) rows->resize((size_t)n_rows);
   return out;
 }
+
+// Pose-graph optimisation of a batch (cfear_pgo_solve_batch): every graph's poses are replaced by its solution in ONE
+// device call, one summary per graph.  par == nullptr: CeresLeastSquares::Parameters' defaults.  A graph the host solver
+// would refuse fails the whole call before anything is solved: CfearError, with the graph's index in *failed_graph.
+struct PoseGraph {
+  std::vector<cfear_pose3d> poses;                   // in / out
+  std::vector<uint64_t> ids;                         // strictly ascending, one per pose
+  std::vector<cfear_graph_constraint> constraints;   // odometry (0) and loop_appearance (1) are optimised
+};
+inline std::vector<cfear_pgo_summary> SolvePoseGraphs(CFEAR_Radarodometry::Context& ctx, std::vector<PoseGraph>& graphs,
+                                                      const cfear_pgo_params* par = nullptr, int32_t* failed_graph = nullptr) {
+  cfear_pgo_params def;
+  if (!par) { cfear_pgo_params_default(&def); par = &def; }
+  std::vector<int64_t> node_off(1, 0), con_off(1, 0);
+  std::vector<cfear_pose3d> poses;
+  std::vector<uint64_t> ids;
+  std::vector<cfear_graph_constraint> cons;
+  for (const PoseGraph& g : graphs) {
+    if (g.ids.size() != g.poses.size()) throw CFEAR_Radarodometry::CfearError(CFEAR_ERR_INVALID_ARGUMENT, "one id per pose");
+    poses.insert(poses.end(), g.poses.begin(), g.poses.end());
+    ids.insert(ids.end(), g.ids.begin(), g.ids.end());
+    cons.insert(cons.end(), g.constraints.begin(), g.constraints.end());
+    node_off.push_back((int64_t)poses.size());
+    con_off.push_back((int64_t)cons.size());
+  }
+  std::vector<cfear_pgo_summary> out(graphs.size());
+  ctx.check(cfear_pgo_solve_batch(ctx.get(), poses.data(), ids.data(), node_off.data(), (int64_t)poses.size(), cons.data(), con_off.data(),
+                                  (int64_t)cons.size(), (int32_t)graphs.size(), par, out.data(), failed_graph));
+  for (size_t g = 0; g < graphs.size(); g++)
+    std::copy(poses.begin() + node_off[g], poses.begin() + node_off[g + 1], graphs[g].poses.begin());
+  return out;
+}

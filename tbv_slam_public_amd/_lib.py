@@ -228,7 +228,7 @@ EXPORTS = [
     "cfear_graph_save", "cfear_graph_load", "cfear_graph_size", "cfear_graph_node_at", "cfear_graph_destroy",
     "cfear_pose3d_from_xyt", "cfear_pose3d_to_xyt", "cfear_odometry_get_constraint",
     "cfear_shard_range", "cfear_gather_records", "cfear_register_batch_sharded", "cfear_verify_loop_candidates_sharded",
-    "cfear_rccl_allgather", "cfear_rccl_allgather_device", "cfear_pgo_params_default", "cfear_pgo_solve",
+    "cfear_rccl_allgather", "cfear_rccl_allgather_device", "cfear_pgo_params_default", "cfear_pgo_solve", "cfear_pgo_solve_batch",
     "cfear_scan_table_create", "cfear_scan_table_size", "cfear_scan_table_destroy", "cfear_register_candidates",
     "cfear_ctx_get_stream", "cfear_ctx_set_option", "cfear_ctx_get_option",
     "cfear_rccl_unique_id", "cfear_rccl_comm_init", "cfear_rccl_comm_destroy",
@@ -246,6 +246,9 @@ class RcclComm(C.Structure):        # cfear_rccl_comm
 
 # enum cfear_option (include/cfear_hip.h): test / measurement hooks of a context
 OPT_FUSED_DECODE, OPT_MATCHER_LDS_KB, OPT_MATCHER_WAVES, OPT_HOST_TIMELINE, OPT_SC_QUERY_CHUNK, OPT_COUNT = 0, 1, 2, 3, 4, 5
+# OPT_COUNT counts the options above, which all take 0 as "the library's choice"; it is NOT the header's CFEAR_OPT_COUNT (6).
+# CFEAR_OPT_PGO_GRAPH_CHUNK follows them with a different value range: n >= 1 graphs per chunk of cfear_pgo_solve_batch, 0 refused.
+OPT_PGO_GRAPH_CHUNK = 5
 
 
 class PgoParams(C.Structure):
@@ -272,6 +275,15 @@ class GraphConstraint(C.Structure):
     _fields_ = [("id_begin", C.c_uint64), ("id_end", C.c_uint64), ("t_be", Pose3d), ("information", C.c_double * 36),
                 ("type", C.c_int32), ("n_quality", C.c_int32), ("quality_keys", C.POINTER(C.c_char_p)),
                 ("quality_values", C.POINTER(C.c_double)), ("info", C.c_char_p)]
+
+
+# cfear_graph_constraint / cfear_pgo_summary as numpy records, for callers that marshal whole batches at once
+GRAPH_CONSTRAINT_DTYPE = np.dtype([("id_begin", "<u8"), ("id_end", "<u8"), ("t_be", "<f8", (7,)), ("information", "<f8", (36,)),
+                                   ("type", "<i4"), ("n_quality", "<i4"), ("quality_keys", "<u8"), ("quality_values", "<u8"),
+                                   ("info", "<u8")])
+PGO_SUMMARY_DTYPE = np.dtype([("initial_cost", "<f8"), ("final_cost", "<f8"), ("iterations", "<i4"), ("usable", "<i4"),
+                              ("num_residual_blocks", "<i4"), ("linear_iterations", "<i4")])
+assert GRAPH_CONSTRAINT_DTYPE.itemsize == C.sizeof(GraphConstraint) and PGO_SUMMARY_DTYPE.itemsize == C.sizeof(PgoSummary)
 
 
 class GraphNode(C.Structure):
@@ -424,6 +436,8 @@ def lib():
     L.cfear_pgo_params_default.argtypes = [C.POINTER(PgoParams)]
     L.cfear_pgo_params_default.restype = None
     L.cfear_pgo_solve.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.POINTER(PgoParams), C.POINTER(PgoSummary)]
+    L.cfear_pgo_solve_batch.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int32, C.POINTER(PgoParams), vp,
+                                        C.POINTER(C.c_int32)]
     L.cfear_shard_range.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.cfear_gather_records.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
     L.cfear_graph_save.argtypes = [C.c_char_p, C.POINTER(GraphNode), C.c_int32]

@@ -1845,7 +1845,8 @@ def LoadSimpleGraph(path):
 def pose_graph_optimize(poses, ids, constraints, **par):
     """CeresLeastSquares::Solve (tbv_slam/src/tbv_slam/ceresoptimizer.cpp:13-62) over the nodes `poses` ([n, 7] = p, q(x, y, z, w),
     or [n, 3] planar (x, y, theta)) with node ids `ids` (ascending) and `constraints` (SaveSimpleGraph's constraint dicts:
-    id_begin, id_end, t_be, information, type).  Keyword overrides: the cfear_pgo_params fields.  Host code, no GPU.
+    id_begin, id_end, t_be, information, type).  Keyword overrides: the cfear_pgo_params fields.  Host code, no GPU
+    (pose_graph_optimize_batch solves many graphs in one device call).
     Returns (poses [n, 7], summary dict)."""
     lib = L.lib()
     poses = np.asarray(poses, np.float64)
@@ -1873,6 +1874,94 @@ def pose_graph_optimize(poses, ids, constraints, **par):
     out = np.array([list(a.p) + list(a.q) for a in arr])
     return out, dict(initial_cost=s.initial_cost, final_cost=s.final_cost, iterations=s.iterations, usable=bool(s.usable),
                      num_residual_blocks=s.num_residual_blocks, linear_iterations=s.linear_iterations)
+
+
+def _pgo_graph_arrays(poses, ids, constraints, where):
+    """One graph as the arrays cfear_pgo_solve_batch reads: poses [n, 7], ids [n] uint64, constraints [m] records."""
+    poses = np.asarray(poses, np.float64)
+    if poses.ndim != 2 or poses.shape[1] not in (3, 7):
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "%s: poses must be [n, 7] (p, q) or [n, 3] (x, y, theta), got %s" % (where, poses.shape))
+    if poses.shape[1] == 3:
+        poses = np.array([np.concatenate(pose3d_from_xyt(p)) for p in poses]).reshape(-1, 7)
+    ids = np.asarray(ids)
+    if ids.ndim != 1 or ids.shape[0] != poses.shape[0]:
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "%s: %d ids for %d poses" % (where, ids.size, poses.shape[0]))
+    if ids.size and ids.min() < 0:
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "%s: negative node id" % where)
+    rec = np.zeros(len(constraints), L.GRAPH_CONSTRAINT_DTYPE)
+    for j, c in enumerate(constraints):
+        try:
+            rec[j]["id_begin"], rec[j]["id_end"] = int(c["id_begin"]), int(c["id_end"])
+            t = c.get("t_be")
+            t = np.array([0, 0, 0, 0, 0, 0, 1.0]) if t is None else np.asarray(t, np.float64).reshape(-1)
+            rec[j]["t_be"] = np.concatenate(pose3d_from_xyt(t)) if t.size == 3 else t
+            rec[j]["information"] = np.asarray(c.get("information", np.eye(6)), np.float64).reshape(36)
+            rec[j]["type"] = int(c.get("type", 0))
+        except (KeyError, ValueError, TypeError, OverflowError) as e:
+            raise L.CfearError(L.ERR_INVALID_ARGUMENT, "%s: constraint %d: %s" % (where, j, e))
+    return np.ascontiguousarray(poses), ids.astype(np.uint64), rec
+
+
+def pose_graph_optimize_batch(graphs, ctx=None, **par):
+    """cfear_pgo_solve_batch: every graph of `graphs` -- (poses, ids, constraints) triples as pose_graph_optimize takes them,
+    the planar [n, 3] shorthand included -- solved in ONE device call, one wavefront per graph.  Keyword overrides: the
+    cfear_pgo_params fields, one set for the batch.  Returns a list of (poses [n, 7], summary dict), in the order given.
+    A graph that pose_graph_optimize would refuse fails the whole call: CfearError with .graph = its index; nothing is solved."""
+    lib = L.lib()
+    p = L.PgoParams()
+    lib.cfear_pgo_params_default(C.byref(p))
+    for k, v in par.items():
+        if not hasattr(p, k):
+            raise L.CfearError(L.ERR_INVALID_ARGUMENT, "unknown cfear_pgo_params field %r" % k)
+        setattr(p, k, type(getattr(p, k))(v))
+    arrs = []
+    for g, tri in enumerate(graphs):
+        if len(tri) != 3:
+            raise L.CfearError(L.ERR_INVALID_ARGUMENT, "graph %d: a (poses, ids, constraints) triple is needed" % g)
+        arrs.append(_pgo_graph_arrays(tri[0], tri[1], tri[2], "graph %d" % g))
+    if not arrs:
+        return []
+    node_off = np.concatenate([[0], np.cumsum([a[0].shape[0] for a in arrs])]).astype(np.int64)
+    con_off = np.concatenate([[0], np.cumsum([a[2].shape[0] for a in arrs])]).astype(np.int64)
+    poses = np.ascontiguousarray(np.concatenate([a[0] for a in arrs], 0))
+    ids = np.ascontiguousarray(np.concatenate([a[1] for a in arrs]))
+    cons = np.ascontiguousarray(np.concatenate([a[2] for a in arrs]))
+    summ = np.zeros(len(arrs), L.PGO_SUMMARY_DTYPE)
+    ctx = ctx or default_context()
+    bad = C.c_int32(-1)
+    rc = ctx._lib.cfear_pgo_solve_batch(ctx.h, poses.ctypes.data, ids.ctypes.data, node_off.ctypes.data, int(node_off[-1]),
+                                        cons.ctypes.data, con_off.ctypes.data, int(con_off[-1]), len(arrs), C.byref(p),
+                                        summ.ctypes.data, C.byref(bad))
+    if rc != L.OK:
+        err = L.CfearError(rc, ctx._lib.cfear_last_error(ctx.h).decode())
+        err.graph = int(bad.value)
+        raise err
+    return [(poses[node_off[g]:node_off[g + 1]].copy(),
+             dict(initial_cost=float(s["initial_cost"]), final_cost=float(s["final_cost"]), iterations=int(s["iterations"]),
+                  usable=bool(s["usable"]), num_residual_blocks=int(s["num_residual_blocks"]),
+                  linear_iterations=int(s["linear_iterations"])))
+            for g, s in enumerate(summ)]
+
+
+def pose_graph_prefixes(poses, ids, constraints):
+    """The graphs the reference's optimisation thread solves while ONE sequence is mapped: one per accepted loop
+    (type 1 constraint, in the order given), holding the nodes up to the loop's later node and every constraint, of any
+    type, between them.  Returns a list of (poses, ids, constraints) triples for pose_graph_optimize_batch; ids must ascend."""
+    poses, ids = np.asarray(poses, np.float64), np.asarray(ids)
+    if ids.ndim != 1 or ids.shape[0] != poses.shape[0] or np.any(ids[1:] <= ids[:-1]):
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "ids must ascend and number the poses")
+    known = set(int(i) for i in ids)
+    out = []
+    for c in constraints:
+        if int(c.get("type", 0)) != 1:
+            continue
+        last = max(int(c["id_begin"]), int(c["id_end"]))
+        if int(c["id_begin"]) not in known or int(c["id_end"]) not in known:
+            raise L.CfearError(L.ERR_INVALID_ARGUMENT, "loop %d -> %d joins an unknown node" % (c["id_begin"], c["id_end"]))
+        n = int(np.searchsorted(ids, last, side="right"))
+        out.append((poses[:n].copy(), ids[:n].copy(),
+                    [k for k in constraints if max(int(k["id_begin"]), int(k["id_end"])) <= last]))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

@@ -370,6 +370,7 @@ int cfear_ctx_set_option(cfear_ctx* ctx, int32_t option, int64_t value) {
     case CFEAR_OPT_MATCHER_LDS_KB: ok = value == 0 || (value >= 8 && value <= 160); break;
     case CFEAR_OPT_MATCHER_WAVES: ok = value == 0 || value == 2 || value == 4 || value == 8 || value == 16; break;
     case CFEAR_OPT_SC_QUERY_CHUNK: ok = value >= 0 && value <= INT32_MAX; break;
+    case CFEAR_OPT_PGO_GRAPH_CHUNK: ok = value >= 1 && value <= INT32_MAX; break;   // a cap of 0 graphs is no cap: refused
     default: return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "unknown option %d", (int)option);
   }
   if (!ok) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "option %d: value %lld out of range", (int)option, (long long)value);

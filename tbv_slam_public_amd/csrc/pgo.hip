@@ -1,4 +1,4 @@
-// pgo.hip -- pose-graph optimisation (host code; SURVEY.md 8f-4, second half: the step AFTER the path).
+// pgo.hip -- pose-graph optimisation, one graph on the host (second half: the step AFTER the path).
 //
 // Replaces (tbv_slam/):
 //   CeresLeastSquares::{Solve, BuildOptimizationProblem, AddConstraintType, SolveOptimizationProblem}
@@ -7,12 +7,14 @@
 //   ceres::EigenQuaternionParameterization, ceres::CauchyLoss, ceres::Solve (TRUST_REGION / LEVENBERG_MARQUARDT,
 //   SPARSE_NORMAL_CHOLESKY, max_num_iterations 200)    third-party, Ceres 2.1.0
 //
-// Why this runs on the host: the problem is one sparse nonlinear least squares over a CHAIN of poses (6 (n - 1) unknowns,
-// n ~ 5 000 keyframes, block-tridiagonal normal equations plus a few hundred weak loop blocks), solved once per loop
-// closure.  Its kernels are block-tridiagonal recurrences -- 2 n dependent 6 x 6 steps per solve, a serial chain that a
-// CPU core finishes in well under a millisecond and a GPU wavefront in tens -- and the whole optimisation is ~10^8
-// flops, a thousandth of one registration batch.  The reference keeps it on the host as well ("sparse PGO, runs
-// once").  The trust-region bookkeeping is the one restated for the matcher (matcher.hip lm_round).
+// What runs where: the problem is one sparse nonlinear least squares over a CHAIN of poses (6 (n - 1) unknowns, n ~ 5 000
+// keyframes, block-tridiagonal normal equations plus a few hundred weak loop blocks).  ONE solve is a serial recurrence -- 2 n
+// dependent 6 x 6 steps per preconditioner application -- with no data parallelism to give a GPU, so cfear_pgo_solve below
+// stays host code on one thread, needs no context, and is the yardstick of the device solver's tests.  A BATCH of solves is
+// parallel across graphs (one per odometry stream, per job of a parameter sweep, per accepted loop of a sequence):
+// cfear_pgo_solve_batch (pgo_batch.hip) runs this file's LM loop for many graphs at once, one wavefront per graph, and takes
+// its residual blocks and their arithmetic from the same pgo_terms.hpp, so both refuse the same inputs and take the same
+// decisions.  The trust-region bookkeeping is the one restated for the matcher (matcher.hip lm_round).
 //
 // Linear algebra: Ceres factorises J^T J + D^2 with CHOLMOD.  Here the same system is solved by conjugate gradients
 // preconditioned with the exact block-tridiagonal Cholesky factor of its odometry chain part; the loop constraints enter
@@ -26,56 +28,17 @@
 #include <vector>
 
 #include "../../include/cfear_hip.h"
+#include "pgo_terms.hpp"
 
 namespace {
 
-// ---- forward-mode automatic differentiation over the 14 parameters (p_a 3, q_a 4, p_b 3, q_b 4), like ceres::Jet ------
-constexpr int NJ = 14;
-struct Jet {
-  double a;
-  double v[NJ];
-  Jet() : a(0) { for (int i = 0; i < NJ; i++) v[i] = 0; }
-  Jet(double x) : a(x) { for (int i = 0; i < NJ; i++) v[i] = 0; }
-  Jet(double x, int k) : a(x) { for (int i = 0; i < NJ; i++) v[i] = 0; v[k] = 1; }
-};
-inline Jet operator+(const Jet& x, const Jet& y) { Jet r; r.a = x.a + y.a; for (int i = 0; i < NJ; i++) r.v[i] = x.v[i] + y.v[i]; return r; }
-inline Jet operator-(const Jet& x, const Jet& y) { Jet r; r.a = x.a - y.a; for (int i = 0; i < NJ; i++) r.v[i] = x.v[i] - y.v[i]; return r; }
-inline Jet operator-(const Jet& x) { Jet r; r.a = -x.a; for (int i = 0; i < NJ; i++) r.v[i] = -x.v[i]; return r; }
-inline Jet operator*(const Jet& x, const Jet& y) { Jet r; r.a = x.a * y.a; for (int i = 0; i < NJ; i++) r.v[i] = x.a * y.v[i] + x.v[i] * y.a; return r; }
-
-template <typename T> struct Quat { T x, y, z, w; };
-template <typename T> Quat<T> qmul(const Quat<T>& a, const Quat<T>& b) {       // Eigen::Quaternion operator*
-  return Quat<T>{a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y, a.w * b.y + a.y * b.w + a.z * b.x - a.x * b.z,
-                 a.w * b.z + a.z * b.w + a.x * b.y - a.y * b.x, a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z};
-}
-template <typename T> Quat<T> qconj(const Quat<T>& a) { return Quat<T>{-a.x, -a.y, -a.z, a.w}; }
-// Eigen::Quaternion * Vector3: v + 2 w (u x v) + 2 u x (u x v), evaluated as Eigen's _transformVector does
-template <typename T> void qrot(const Quat<T>& q, const T v[3], T out[3]) {
-  const T ux = q.y * v[2] - q.z * v[1], uy = q.z * v[0] - q.x * v[2], uz = q.x * v[1] - q.y * v[0];
-  const T two(2.0);
-  const T tx = two * ux, ty = two * uy, tz = two * uz;
-  out[0] = v[0] + q.w * tx + (q.y * tz - q.z * ty);
-  out[1] = v[1] + q.w * ty + (q.z * tx - q.x * tz);
-  out[2] = v[2] + q.w * tz + (q.x * ty - q.y * tx);
-}
-
-// PoseGraph3dErrorTerm::operator() (ceresoptimizer.h:62-97): residual = L * [p_ab_est - p_ab_meas; 2 vec(q_meas * q_ab_est^-1)]
-template <typename T>
-void error_term(const T pa[3], const Quat<T>& qa, const T pb[3], const Quat<T>& qb, const cfear_pose3d& meas, const double L[36], T r[6]) {
-  const Quat<T> qa_inv = qconj(qa);
-  const Quat<T> q_ab = qmul(qa_inv, qb);
-  const T d[3] = {pb[0] - pa[0], pb[1] - pa[1], pb[2] - pa[2]};
-  T p_ab[3];
-  qrot(qa_inv, d, p_ab);
-  const Quat<T> qm{T(meas.q[0]), T(meas.q[1]), T(meas.q[2]), T(meas.q[3])};
-  const Quat<T> dq = qmul(qm, qconj(q_ab));
-  T e[6] = {p_ab[0] - T(meas.p[0]), p_ab[1] - T(meas.p[1]), p_ab[2] - T(meas.p[2]), T(2.0) * dq.x, T(2.0) * dq.y, T(2.0) * dq.z};
-  for (int i = 0; i < 6; i++) {                                  // residuals.applyOnTheLeft(sqrt_information)
-    T s(0.0);
-    for (int k = 0; k < 6; k++) s = s + T(L[i * 6 + k]) * e[k];
-    r[i] = s;
-  }
-}
+using pgo::Quat;
+using pgo::error_term;
+using pgo::llt6;
+using pgo::plus;
+#define CFEAR_PGO_TRY(expr) do { const int _rc = (expr); if (_rc != CFEAR_OK) return _rc; } while (0)
+constexpr int NJ = 14;                        // p_a 3, q_a 4, p_b 3, q_b 4
+using Jet = pgo::JetT<NJ>;
 
 struct Con {
   int a, b;                 // node indices (0 = the fixed first node)
@@ -85,18 +48,6 @@ struct Con {
   double r[6];              // robustified residuals at the current point
   double J[6][12];          // robustified, column-scaled Jacobian wrt the tangent (3 + 3 per node): a then b
 };
-
-bool llt6(const double A[36], double L[36]) {
-  memset(L, 0, 36 * sizeof(double));
-  for (int i = 0; i < 6; i++)
-    for (int j = 0; j <= i; j++) {
-      double s = A[i * 6 + j];
-      for (int k = 0; k < j; k++) s -= L[i * 6 + k] * L[j * 6 + k];
-      if (i == j) { if (!(s > 0.0)) return false; L[i * 6 + i] = std::sqrt(s); }
-      else L[i * 6 + j] = s / L[j * 6 + j];
-    }
-  return true;
-}
 
 struct Problem {
   int n = 0;                                   // nodes; unknown blocks are nodes 1 .. n-1
@@ -132,15 +83,8 @@ struct Problem {
       loss(c.cauchy, s, rho0, rho1);
       cost += 0.5 * rho0;
       const double sr = std::sqrt(rho1);                         // Corrector, alpha = 0 (rho'' <= 0 for Cauchy)
-      // EigenQuaternionParameterization::ComputeJacobian (4 x 3, Eigen coefficient order x, y, z, w)
-      auto local = [](const double q[4], double G[12]) {
-        G[0] = q[3];  G[1] = q[2];  G[2] = -q[1];
-        G[3] = -q[2]; G[4] = q[3];  G[5] = q[0];
-        G[6] = q[1];  G[7] = -q[0]; G[8] = q[3];
-        G[9] = -q[0]; G[10] = -q[1]; G[11] = -q[2];
-      };
       double Ga[12], Gb[12];
-      local(A.q, Ga); local(B.q, Gb);
+      pgo::local_jacobian(A.q, Ga); pgo::local_jacobian(B.q, Gb);
       for (int i = 0; i < 6; i++) {
         c.r[i] = r[i].a * sr;
         for (int k = 0; k < 3; k++) { c.J[i][k] = r[i].v[k] * sr; c.J[i][6 + k] = r[i].v[7 + k] * sr; }
@@ -153,12 +97,7 @@ struct Problem {
     }
     return cost;
   }
-  void loss(bool cauchy, double s, double& rho0, double& rho1) const {
-    if (!cauchy) { rho0 = s; rho1 = 1.0; return; }
-    const double b = cauchy_a * cauchy_a, cc = 1.0 / b, sum = 1.0 + s * cc, inv = 1.0 / sum;   // ceres::CauchyLoss
-    rho0 = b * std::log(sum);
-    rho1 = std::max(std::numeric_limits<double>::min(), inv);
-  }
+  void loss(bool cauchy, double s, double& rho0, double& rho1) const { pgo::loss(cauchy, cauchy_a, s, rho0, rho1); }
   // column norms / scaling and column scaling of J (node 0's columns are constant: zeroed)
   void column_sq_norms(std::vector<double>& out) const {
     out.assign((size_t)6 * n, 0.0);
@@ -265,20 +204,6 @@ struct ChainPrecond {
 
 double dot(const std::vector<double>& a, const std::vector<double>& b) { double s = 0; for (size_t i = 0; i < a.size(); i++) s += a[i] * b[i]; return s; }
 
-// x_plus_delta: p += dp; q = exp(dq) * q (ceres::EigenQuaternionParameterization::Plus)
-void plus(const cfear_pose3d& x, const double d[6], cfear_pose3d& out) {
-  for (int k = 0; k < 3; k++) out.p[k] = x.p[k] + d[k];
-  const double nd = std::sqrt(d[3] * d[3] + d[4] * d[4] + d[5] * d[5]);
-  if (nd > 0.0) {
-    const double s = std::sin(nd) / nd;
-    const Quat<double> dq{s * d[3], s * d[4], s * d[5], std::cos(nd)}, q{x.q[0], x.q[1], x.q[2], x.q[3]};
-    const Quat<double> r = qmul(dq, q);
-    out.q[0] = r.x; out.q[1] = r.y; out.q[2] = r.z; out.q[3] = r.w;
-  } else {
-    for (int k = 0; k < 4; k++) out.q[k] = x.q[k];
-  }
-}
-
 }  // namespace
 
 extern "C" void cfear_pgo_params_default(cfear_pgo_params* p) {          // CeresLeastSquares::Parameters (ceresoptimizer.cpp:18-27)
@@ -294,33 +219,21 @@ extern "C" int cfear_pgo_solve(cfear_pose3d* poses, const uint64_t* ids, int32_t
                                int32_t m, const cfear_pgo_params* par, cfear_pgo_summary* summary) {
   if (!poses || !ids || n < 1 || (m > 0 && !constraints) || m < 1 || !par || !summary) return CFEAR_ERR_INVALID_ARGUMENT;   // CHECK(size != 0)
   memset(summary, 0, sizeof(*summary));
-  for (int i = 1; i < n; i++) if (!(ids[i - 1] < ids[i])) return CFEAR_ERR_INVALID_ARGUMENT;   // the node map is ordered by id
-  auto find = [&](uint64_t id) { const uint64_t* p = std::lower_bound(ids, ids + n, id); return (p != ids + n && *p == id) ? (int)(p - ids) : -1; };
+  std::vector<pgo::Term> terms;
+  std::vector<pgo::Factor> factors;
+  CFEAR_PGO_TRY(pgo::collect_terms(ids, n, constraints, m, par, terms, factors));
   Problem P;
   P.n = n;
   P.x.assign(poses, poses + n);
   P.cauchy_a = par->loop_loss_limit;
-  for (int pass = 0; pass < 2; pass++)                                   // AddConstraintType(odometry), then (loop_appearance)
-    for (int j = 0; j < m; j++) {
-      const cfear_graph_constraint& c = constraints[j];
-      if (c.type != pass) continue;                                      // mini_loop / candidate constraints are not optimised
-      Con k;
-      k.a = find(c.id_begin); k.b = find(c.id_end);
-      if (k.a < 0 || k.b < 0) return CFEAR_ERR_INVALID_ARGUMENT;         // "Nodes doesn't exist" (:74-75)
-      k.meas = c.t_be;
-      k.cauchy = pass == 1;
-      const double loop_scale_factor = pass == 1 ? 1.0 / par->loop_scaling : 1.0;     // :85
-      double I[36] = {0};
-      if (par->replace_cov_by_identity) {                                // :86-88: the odom_* variances scale BOTH types
-        const double d[6] = {1.0 / par->odom_vxx, 1.0 / par->odom_vyy, 1, 1, 1, 1.0 / par->odom_vtt};
-        for (int t = 0; t < 6; t++) I[t * 7] = d[t] * loop_scale_factor;
-      } else {
-        for (int t = 0; t < 36; t++) I[t] = c.information[t] * loop_scale_factor;
-      }
-      if (!llt6(I, k.L)) return CFEAR_ERR_INVALID_ARGUMENT;              // Eigen's llt() of a non-SPD matrix is garbage; refuse
-      P.cons.push_back(k);
-    }
-  if (P.cons.empty()) return CFEAR_ERR_INVALID_ARGUMENT;
+  for (const pgo::Term& t : terms) {
+    Con k;
+    k.a = t.a; k.b = t.b;
+    k.meas = constraints[t.j].t_be;
+    k.cauchy = t.cauchy;
+    memcpy(k.L, factors[t.l].L, sizeof(k.L));
+    P.cons.push_back(k);
+  }
   // ---- ceres::Solve: trust-region Levenberg-Marquardt (Ceres 2.1 defaults) ------------------------
   const double function_tolerance = 1e-6, gradient_tolerance = 1e-10, parameter_tolerance = 1e-8;
   const double min_relative_decrease = 1e-3, min_lm_diagonal = 1e-6, max_lm_diagonal = 1e32, max_radius = 1e16, min_radius = 1e-32;

@@ -270,3 +270,85 @@ def sc_graph(n_nodes, seed=0, points=600, step=2.5, radius=120.0):
         cl[:, :2], cl[:, 3] = local, inten[near]
         clouds.append(cl)
     return clouds, poses
+
+
+# ------------------------------------------------------------------------------------------------
+# pose graphs for the batched pose-graph solver (tests, tools/pgo_batch_probe.py, examples/slam_batch_demo.py): closed laps in
+# the manner of tests/test_pgo.py::_loop_graph -- nodes = integrated drifting odometry, odometry constraints = the drifting
+# relative motions, loop constraints = the true relative poses across the lap -- built with numpy
+# ------------------------------------------------------------------------------------------------
+def _pgo_pose7(xyt):
+    xyt = np.atleast_2d(np.asarray(xyt, np.float64))
+    out = np.zeros((xyt.shape[0], 7))
+    out[:, :2] = xyt[:, :2]
+    out[:, 5], out[:, 6] = np.sin(xyt[:, 2] / 2), np.cos(xyt[:, 2] / 2)
+    return out
+
+
+def _pgo_rel(a, b):
+    c, s = np.cos(a[..., 2]), np.sin(a[..., 2])
+    d = b[..., :2] - a[..., :2]
+    return np.stack([c * d[..., 0] + s * d[..., 1], -s * d[..., 0] + c * d[..., 1], b[..., 2] - a[..., 2]], -1)
+
+
+def _pgo_spd(rng):
+    a = rng.normal(0, 0.3, (6, 6))
+    return a @ a.T + np.diag([100.0, 100.0, 1.0, 1.0, 1.0, 1000.0])
+
+
+def pgo_lap_graph(n, rng, n_loops=4, drift=(0.02, 0.01, 0.004), direction="back", outlier=False, extras=True, id_step=10):
+    """-> (poses [n, 7], ids [n], constraints, true [n, 3]).  direction: "back" stores odometry from the new node to the one
+    before (a = b + 1, what AddToGraph does), "forward" the other way (a = b - 1), "mixed" draws per constraint.  outlier: the
+    loops measure a pose metres away from the truth (the Cauchy loss's flat region).  extras: mini_loop and candidate
+    constraints that the solver must ignore.  Every constraint carries its own positive definite information."""
+    th = 2 * np.pi / max(n, 2)
+    i = np.arange(n)
+    true = np.stack([20 * np.sin(i * th), 20 * (1 - np.cos(i * th)), i * th], 1)
+    scale = min(1.0, 24.0 / n)                     # the lap's total drift stays that of a 24-node lap
+    step = _pgo_rel(true[:-1], true[1:]) + np.asarray(drift) * scale + rng.normal(0, 0.003 * scale, (n - 1, 3))
+    est = np.zeros((n, 3))
+    est[0] = true[0]
+    for k in range(1, n):
+        c, s = np.cos(est[k - 1, 2]), np.sin(est[k - 1, 2])
+        est[k] = [est[k - 1, 0] + c * step[k - 1, 0] - s * step[k - 1, 1], est[k - 1, 1] + s * step[k - 1, 0] + c * step[k - 1, 1],
+                  est[k - 1, 2] + step[k - 1, 2]]
+    ids = i * id_step
+    cons = []
+    back = _pgo_pose7(_pgo_rel(est[1:], est[:-1])) if n > 1 else None
+    fwd = _pgo_pose7(_pgo_rel(est[:-1], est[1:])) if n > 1 else None
+    for k in range(1, n):
+        b = direction == "back" or (direction == "mixed" and rng.random() < 0.5)
+        cons.append(dict(id_begin=int(ids[k] if b else ids[k - 1]), id_end=int(ids[k - 1] if b else ids[k]),
+                         t_be=(back if b else fwd)[k - 1], information=_pgo_spd(rng), type=0))
+    for k in range(min(n_loops, n // 2)):
+        a, b = n - 1 - k, k
+        meas = _pgo_rel(true[a], true[b]) + rng.normal(0, 0.002, 3) + (np.array([6.0, -4.0, 0.3]) if outlier else 0.0)
+        cons.append(dict(id_begin=int(ids[a]), id_end=int(ids[b]), t_be=_pgo_pose7(meas)[0], information=_pgo_spd(rng), type=1))
+    if extras and n > 1:
+        cons.insert(len(cons) // 2, dict(id_begin=int(ids[1]), id_end=int(ids[0]), t_be=_pgo_pose7([9, 9, 1])[0], information=np.eye(6), type=3))
+        cons.append(dict(id_begin=int(ids[0]), id_end=int(ids[n - 1]), t_be=_pgo_pose7([-3, 2, 0.5])[0], information=np.eye(6), type=2))
+    return _pgo_pose7(est), ids, cons, true
+
+
+def pgo_ragged_batch(seed, n_graphs=256, n_max=4096, loops_max=64):
+    """The seeded batch of the device-against-host test: 2 .. n_max nodes (log-uniform, both ends present), 0 .. loops_max
+    loops, the three storage directions, and the edge cases -- no loop at all, a single loop that is an outlier."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for g in range(n_graphs):
+        n = int(np.exp(rng.uniform(np.log(2), np.log(n_max + 1))))
+        n = min(max(n, 2), n_max)
+        loops = int(rng.integers(0, loops_max + 1))
+        kind = dict(direction=("back", "forward", "mixed")[g % 3], outlier=False)
+        if g == 0:
+            n, loops = 2, 1
+        elif g == 1:
+            n, loops = n_max, loops_max
+        elif g == 2:
+            loops = 0                                # odometry only: already at its optimum
+        elif g == 3:
+            n, loops, kind["outlier"] = max(n, 40), 1, True
+        elif g % 16 == 5:
+            kind["outlier"] = True                   # every loop an outlier
+        out.append(pgo_lap_graph(n, rng, n_loops=loops, **kind)[:3])
+    return out
