@@ -61,7 +61,7 @@ struct cfear_ctx {
   // pinned host staging for small read-backs
   void* pinned = nullptr;
   size_t pinned_bytes = 0;
-  hipEvent_t pinned_ev = nullptr;   // recorded behind the last asynchronous copy OUT of `pinned` (cfear_pinned_mark)
+  hipEvent_t pinned_ev = nullptr;   // recorded behind the last asynchronous reader of `pinned` (HostStage::pinned)
   bool pinned_busy = false;
   // free list of scan slabs (capacity -> device pointers) so streaming does not hipMalloc
   struct Slab { void* p; int cap; };
@@ -94,20 +94,14 @@ int cfear_set_error(cfear_ctx* ctx, int status, const char* fmt, ...);
 bool cfear_is_device_ptr(const void* p);
 // grow-only workspace `slot` of at least `bytes`; returns nullptr on allocation failure
 void* cfear_workspace(cfear_ctx* ctx, WsSlot slot, size_t bytes);
-// Pinned staging of at least `bytes`.  A caller that leaves an asynchronous copy from it in flight (results kept on the
-// device: no synchronisation before it returns) calls cfear_pinned_mark() behind the copy; cfear_pinned() then waits for
-// that copy before it hands the buffer out again.
-// Everything else that crosses from or into the caller's memory goes through HostStage: no copy from or into caller memory
-// outlives the C-ABI call that enqueued it, on the error paths as well.
-void* cfear_pinned(cfear_ctx* ctx, size_t bytes);
-void cfear_pinned_mark(cfear_ctx* ctx);
-
-// One C-ABI call's boundary with the caller's memory.  The call first plans what it needs -- in() / out() / piece() bind a
-// pointer to the device address it resolves to, images() and cloud_in() stage polar images and peak clouds in their own
-// slots -- then carve() allocates every piece with one cfear_workspace call (256-byte aligned) and enqueues the uploads.
-// Device memory of the caller is used in place.  finish() enqueues the copy-backs and synchronises, but only if the call
-// touched host memory: an all-device call stays asynchronous.  The destructor, and finish() when it fails, drain the stream
-// if a copy was enqueued, so host memory (the caller's, record(), or locals declared before the stage) outlives every copy.
+// One C-ABI call's boundary with host memory: everything that crosses from or into the caller's memory, and every host
+// record or read-back of the callee, goes through a HostStage, so no copy from or into host memory outlives the call that
+// enqueued it, on the error paths as well.  The call first plans what it needs -- in() / out() / piece() bind a pointer to
+// the device address it resolves to, images() and cloud_in() stage polar images and peak clouds in their own slots -- then
+// carve() allocates every piece with one cfear_workspace call (256-byte aligned) and enqueues the uploads.  Device memory
+// of the caller is used in place.  finish() enqueues the copy-backs and synchronises, but only if the call touched host
+// memory: an all-device call stays asynchronous (its pinned() record is marked busy on the stream instead of waited for).
+// The destructor, and wait() / finish() when they fail, drain the stream if a copy was enqueued.
 class HostStage {
  public:
   HostStage(cfear_ctx* ctx, WsSlot slot) : ctx_(ctx), slot_(slot) {}
@@ -143,7 +137,16 @@ class HostStage {
   int carve();
   // a host record the call builds and uploads after carve(); owned by the stage, so it outlives the upload
   void* record(size_t bytes) { record_.assign(bytes, 0); return record_.data(); }
+  // The same in the context's pinned staging (one per call), for records of megabytes -- a pageable source is staged
+  // synchronously at a fraction of the PCIe rate -- and for records a kernel reads in place.  It does not make the call
+  // synchronous: the staging is marked busy behind its upload (by finish(), behind the kernels, when it is read in place)
+  // and handed out again once the stream is past the mark.  nullptr, with the error set, when the allocation fails.
+  void* pinned(size_t bytes);
   int upload(void* dev, const void* host, size_t bytes);
+  // a read-back into host memory the callee owns, enqueued at once; wait() -- or finish() -- waits for those enqueued so
+  // far and reports the first that failed
+  void fetch(void* host, const void* dev, size_t bytes);
+  int wait();
   // a copy-back finish() enqueues (pitched when rows > 1)
   void back(void* host, const void* dev, size_t width, size_t rows = 1, size_t host_pitch = 0, size_t dev_pitch = 0) {
     backs_.push_back({host, dev, width, rows, host_pitch, dev_pitch});
@@ -168,6 +171,8 @@ class HostStage {
   std::map<const float*, Cloud> clouds_;
   char* cloud_base_ = nullptr;
   std::vector<char> record_;
+  void* pinned_ = nullptr;            // pinned() handed out and not yet marked busy
+  hipError_t err_ = hipSuccess;       // the first copy-back or fetch() that failed
   bool host_ = false, device_ = false, sync_ = false, pending_ = false;
 };
 // hipFuncAttributeMaxDynamicSharedMemorySize, once per (context, kernel, size): the attribute is per device and contexts are
@@ -297,8 +302,6 @@ int cfear_trig_tables(cfear_ctx* ctx, int rows, double** d_cos, double** d_sin);
 int cfear_surface_launch(cfear_ctx* ctx, const void* d_jobs, int n_jobs, const cfear_feature_params* par,
                          char* d_scratch, int32_t* d_status, int32_t* d_ncells_out, int max_cell_cap, int cap_points,
                          const cfear_surface_polar* polar = nullptr);
-int cfear_register_batch_device(cfear_ctx* ctx, const cfear_reg_job* jobs, int32_t n_jobs, const cfear_reg_params* par,
-                                cfear_reg_result* d_out, cfear_reg_result** d_used);
 size_t cfear_reg_job_bytes();
 int cfear_reg_max_scans();
 void cfear_reg_fill_job(void* dst, const ScanView* views, int n_scans, const double* poses_xyt);

@@ -44,6 +44,35 @@ void* cfear_workspace(cfear_ctx* ctx, WsSlot slot, size_t bytes) {
   return w.p;
 }
 
+// The context's pinned staging of at least `bytes`.  A call that leaves an asynchronous reader of it in flight (no
+// synchronisation before it returns) calls cfear_pinned_mark() behind that reader; cfear_pinned() then waits for it before it
+// hands the buffer out again.
+static void cfear_pinned_mark(cfear_ctx* ctx) {
+  if (!ctx->pinned_ev && hipEventCreateWithFlags(&ctx->pinned_ev, hipEventDisableTiming) != hipSuccess) {
+    (void)hipGetLastError();
+    ctx->pinned_ev = nullptr;
+    (void)hipStreamSynchronize(ctx->stream);               // no event: the copy is simply waited for here
+    return;
+  }
+  ctx->pinned_busy = hipEventRecord(ctx->pinned_ev, ctx->stream) == hipSuccess;
+  if (!ctx->pinned_busy) (void)hipStreamSynchronize(ctx->stream);
+}
+
+static void* cfear_pinned(cfear_ctx* ctx, size_t bytes) {
+  if (ctx->pinned_busy) { (void)hipEventSynchronize(ctx->pinned_ev); ctx->pinned_busy = false; }
+  if (ctx->pinned_bytes >= bytes && ctx->pinned) return ctx->pinned;
+  if (ctx->pinned) { (void)hipStreamSynchronize(ctx->stream); (void)hipHostFree(ctx->pinned); ctx->pinned = nullptr; }
+  size_t want = bytes + 4096;
+  if (hipHostMalloc(&ctx->pinned, want, hipHostMallocDefault) != hipSuccess) {
+    (void)hipGetLastError();
+    ctx->pinned = nullptr;
+    ctx->pinned_bytes = 0;
+    return nullptr;
+  }
+  ctx->pinned_bytes = want;
+  return ctx->pinned;
+}
+
 bool HostStage::is_host(const void* p) {
   const bool host = !cfear_is_device_ptr(p);
   (host ? host_ : device_) = true;
@@ -104,21 +133,29 @@ int HostStage::carve() {
   return rc;
 }
 
+void* HostStage::pinned(size_t bytes) {
+  pinned_ = cfear_pinned(ctx_, bytes);
+  if (!pinned_) cfear_set_error(ctx_, CFEAR_ERR_HIP, "pinned staging allocation failed");
+  return pinned_;
+}
+
 int HostStage::upload(void* dev, const void* host, size_t bytes) {
-  sync_ = pending_ = true;
+  const bool from_pinned = pinned_ && host == pinned_;
+  if (!from_pinned) sync_ = pending_ = true;
   CFEAR_HIP_CHECK(ctx_, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, ctx_->stream));
+  if (from_pinned) { cfear_pinned_mark(ctx_); pinned_ = nullptr; }
   return CFEAR_OK;
 }
 
-int HostStage::finish() {
-  hipError_t e = hipSuccess;
-  for (const Back& b : backs_) {
-    if (e != hipSuccess) break;
-    pending_ = true;
-    e = b.rows > 1 ? hipMemcpy2DAsync(b.host, b.host_pitch, b.dev, b.dev_pitch, b.width, b.rows, hipMemcpyDeviceToHost, ctx_->stream)
-                   : hipMemcpyAsync(b.host, b.dev, b.width, hipMemcpyDeviceToHost, ctx_->stream);
-  }
-  if (e == hipSuccess && (host_ || sync_ || !backs_.empty())) e = hipStreamSynchronize(ctx_->stream);
+void HostStage::fetch(void* host, const void* dev, size_t bytes) {
+  if (err_ != hipSuccess) return;
+  sync_ = pending_ = true;
+  err_ = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx_->stream);
+}
+
+int HostStage::wait() {
+  const hipError_t e = err_ != hipSuccess ? err_ : hipStreamSynchronize(ctx_->stream);
+  err_ = hipSuccess;
   if (e != hipSuccess) {
     drain();
     return cfear_set_error(ctx_, CFEAR_ERR_HIP, "staging copy failed: %s", hipGetErrorString(e));
@@ -127,35 +164,26 @@ int HostStage::finish() {
   return CFEAR_OK;
 }
 
+int HostStage::finish() {
+  for (const Back& b : backs_) {
+    if (err_ != hipSuccess) break;
+    pending_ = true;
+    err_ = b.rows > 1 ? hipMemcpy2DAsync(b.host, b.host_pitch, b.dev, b.dev_pitch, b.width, b.rows, hipMemcpyDeviceToHost, ctx_->stream)
+                      : hipMemcpyAsync(b.host, b.dev, b.width, hipMemcpyDeviceToHost, ctx_->stream);
+  }
+  if (host_ || sync_ || !backs_.empty()) {
+    CFEAR_CHECK(wait());
+    pinned_ = nullptr;                                       // whatever read it is done
+  }
+  drain();                                                   // an asynchronous call: marks the pinned record a kernel reads in place
+  return CFEAR_OK;
+}
+
 void HostStage::drain() {
   if (pending_) (void)hipStreamSynchronize(ctx_->stream);
+  else if (pinned_) cfear_pinned_mark(ctx_);                 // a kernel may be reading the record in place
   pending_ = false;
-}
-
-void cfear_pinned_mark(cfear_ctx* ctx) {
-  if (!ctx->pinned_ev && hipEventCreateWithFlags(&ctx->pinned_ev, hipEventDisableTiming) != hipSuccess) {
-    (void)hipGetLastError();
-    ctx->pinned_ev = nullptr;
-    (void)hipStreamSynchronize(ctx->stream);               // no event: the copy is simply waited for here
-    return;
-  }
-  ctx->pinned_busy = hipEventRecord(ctx->pinned_ev, ctx->stream) == hipSuccess;
-  if (!ctx->pinned_busy) (void)hipStreamSynchronize(ctx->stream);
-}
-
-void* cfear_pinned(cfear_ctx* ctx, size_t bytes) {
-  if (ctx->pinned_busy) { (void)hipEventSynchronize(ctx->pinned_ev); ctx->pinned_busy = false; }
-  if (ctx->pinned_bytes >= bytes && ctx->pinned) return ctx->pinned;
-  if (ctx->pinned) { (void)hipStreamSynchronize(ctx->stream); (void)hipHostFree(ctx->pinned); ctx->pinned = nullptr; }
-  size_t want = bytes + 4096;
-  if (hipHostMalloc(&ctx->pinned, want, hipHostMallocDefault) != hipSuccess) {
-    (void)hipGetLastError();
-    ctx->pinned = nullptr;
-    ctx->pinned_bytes = 0;
-    return nullptr;
-  }
-  ctx->pinned_bytes = want;
-  return ctx->pinned;
+  pinned_ = nullptr;
 }
 
 int cfear_allow_lds(cfear_ctx* ctx, const void* kernel, size_t bytes) {

@@ -516,10 +516,10 @@ extern "C" int cfear_eval_trajectories(cfear_ctx* ctx, const double* est, const 
                        ctx->stream, a);
   }
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
-  // host half: the row table's prefix and the alignment of every pair (h_sums / h_counts outlive the stage)
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(h_counts.data(), a.counts, h_counts.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (align) CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(h_sums.data(), a.sums, h_sums.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  // host half: the row table's prefix and the alignment of every pair
+  st.fetch(h_counts.data(), a.counts, h_counts.size() * 4);
+  if (align) st.fetch(h_sums.data(), a.sums, h_sums.size() * 8);
+  CFEAR_CHECK(st.wait());
   EvalPost* post = (EvalPost*)(h + tab1);
   int64_t row_total = 0;
   for (int t = 0; t < n_traj; t++) {

@@ -1893,16 +1893,19 @@ int cfear_trig_tables(cfear_ctx* ctx, int rows, double** d_cos, double** d_sin) 
     *d_sin = (double*)ctx->ws[2].p + rows;
     return CFEAR_OK;
   }
-  std::vector<double> h(2 * (size_t)rows);
+  HostStage st(ctx, kWsTrig);
+  const size_t bytes = 2 * (size_t)rows * sizeof(double);
+  double* h = (double*)st.record(bytes);
   for (int bearing = 0; bearing < rows; bearing++) {
     const double theta = (double(bearing + 1) / rows) * 2. * M_PI;           // radar_filters.cpp:317
     h[bearing] = std::cos(theta);
     h[rows + bearing] = std::sin(theta);
   }
-  double* d = (double*)cfear_workspace(ctx, kWsTrig, h.size() * sizeof(double));
-  if (!d) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));   // h goes out of scope
+  double* d;
+  st.piece(d, bytes);
+  CFEAR_CHECK(st.carve());
+  CFEAR_CHECK(st.upload(d, h, bytes));
+  CFEAR_CHECK(st.finish());
   ctx->trig_rows = rows;
   *d_cos = d;
   *d_sin = d + rows;

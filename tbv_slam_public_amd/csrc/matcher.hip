@@ -1514,8 +1514,9 @@ namespace {
 
 // what the host learns about a batch while it marshals it: the scratch size and which forms its registrations want
 struct JobSizes {
-  int pairs_cap = 1, cost = CFEAR_P2L;
-  bool huber = true, small_pairs = true, any_large = false, any_huge = false;
+  int pairs_cap = 1, cost;
+  bool huber, small_pairs = true, any_large = false, any_huge = false;
+  explicit JobSizes(const cfear_reg_params* par) : cost(par->cost), huber(par->loss == CFEAR_LOSS_HUBER) {}
   void add(int n_scans, int sum_pad, int max_pad, int n_src) {
     const int last = n_scans - 1, fields = reg_dense_fields(cost);
     pairs_cap = std::max(pairs_cap, last * std::max(n_src, 1));
@@ -1547,58 +1548,53 @@ int gather_job(cfear_ctx* ctx, const cfear_scan* const* scans, int n_scans, cons
 
 }  // namespace
 
-// The batch with its results left ON THE DEVICE (enqueued on the context's stream, not synchronised): d_out when given,
-// otherwise the context's workspace; *d_used receives the pointer.  cfear_register_batch reads them back; the sharded
-// entry hands them straight to the collective (shard.hip).
-int cfear_register_batch_device(cfear_ctx* ctx, const cfear_reg_job* jobs, int32_t n_jobs, const cfear_reg_params* par,
-                                cfear_reg_result* d_out, cfear_reg_result** d_used) {
-  if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
-  if (!jobs || n_jobs < 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
-  int rc = check_params(ctx, par);
-  if (rc != CFEAR_OK) return rc;
-  if (d_used) *d_used = d_out;
-  if (n_jobs == 0) return CFEAR_OK;
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  // job records are built in pinned memory: up to 1.9 KB each, so a 4096-candidate batch is an upload of megabytes that a
-  // pageable source would stage synchronously at a fraction of the PCIe rate
+namespace {
+
+// A batch of jobs as device records, built in the stage's pinned record with the stride of the batch's longest job, and
+// where its n_results results go: used in place when they are device memory, copied back by finish() when the host's.
+struct JobBatch {
+  explicit JobBatch(const cfear_reg_params* par) : sz(par) {}
+  JobSizes sz;
+  size_t stride = 0;
+  char* d_jobs = nullptr;
+  cfear_reg_result* d_res = nullptr;
+};
+int stage_jobs(cfear_ctx* ctx, HostStage& st, const cfear_reg_job* jobs, int n_jobs, const int32_t* itrs /*nullable: per-job itr_*/,
+               cfear_reg_result* results, size_t n_results, JobBatch& b) {
   int max_scans = 2;
   for (int j = 0; j < n_jobs; j++) max_scans = std::max(max_scans, std::min(jobs[j].n_scans, kMaxScans));
-  const size_t stride = reg_job_stride(max_scans);
-  const size_t jb = (size_t)n_jobs * stride, rb = (size_t)n_jobs * sizeof(cfear_reg_result);
-  unsigned char* hjobs = (unsigned char*)cfear_pinned(ctx, jb);
-  if (!hjobs) return cfear_set_error(ctx, CFEAR_ERR_HIP, "pinned staging allocation failed");
-  JobSizes sz;
-  sz.cost = par->cost; sz.huber = par->loss == CFEAR_LOSS_HUBER;
+  b.stride = reg_job_stride(max_scans);
+  const size_t jb = (size_t)n_jobs * b.stride;
+  unsigned char* hjobs = (unsigned char*)st.pinned(jb);
+  if (!hjobs) return CFEAR_ERR_HIP;
   for (int j = 0; j < n_jobs; j++) {
-    rc = gather_job(ctx, jobs[j].scans, jobs[j].n_scans, jobs[j].poses_xyt, hjobs + (size_t)j * stride, sz);
-    if (rc != CFEAR_OK) return rc;
+    unsigned char* dst = hjobs + (size_t)j * b.stride;
+    CFEAR_CHECK(gather_job(ctx, jobs[j].scans, jobs[j].n_scans, jobs[j].poses_xyt, dst, b.sz));
+    if (itrs) cfear_reg_job_set_itr(dst, itrs[j]);
   }
-  const size_t sb = reg_scratch_bytes(sz.pairs_cap) * (size_t)n_jobs;
-  char* ws = (char*)cfear_workspace(ctx, kWsRegJobs, jb + rb + 512);
-  char* scr = (char*)cfear_workspace(ctx, kWsRegScratch, sb);
-  if (!ws || !scr) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-  char* d_jobs = ws;
-  cfear_reg_result* d_res = d_out ? d_out : (cfear_reg_result*)(ws + (jb + 255) / 256 * 256);
-  if (d_used) *d_used = d_res;
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(d_jobs, hjobs, jb, hipMemcpyHostToDevice, ctx->stream));
-  if (d_out) cfear_pinned_mark(ctx);                        // results stay on the device: nothing below waits for this copy
-  rc = cfear_register_launch(ctx, d_jobs, n_jobs, par, sz.pairs_cap, scr, d_res, nullptr, stride, sz.hint(n_jobs));
-  if (rc != CFEAR_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-  return CFEAR_OK;
+  st.piece(b.d_jobs, jb);
+  st.out(b.d_res, results, n_results * sizeof(cfear_reg_result));
+  CFEAR_CHECK(st.carve());
+  return st.upload(b.d_jobs, hjobs, jb);
 }
 
+}  // namespace
+
+// results on the device stay there, stream-ordered and not synchronised (the sharded entry hands them to the collective)
 extern "C" int cfear_register_batch(cfear_ctx* ctx, const cfear_reg_job* jobs, int32_t n_jobs,
                                     const cfear_reg_params* par, cfear_reg_result* results) {
   if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
   if (!jobs || !results || n_jobs < 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
-  // results on the device: the records stay there, the launch is stream-ordered and not synchronised
-  if (cfear_is_device_ptr(results)) return cfear_register_batch_device(ctx, jobs, n_jobs, par, results, nullptr);
-  cfear_reg_result* d_res = nullptr;
-  const int rc = cfear_register_batch_device(ctx, jobs, n_jobs, par, nullptr, &d_res);
-  if (rc != CFEAR_OK || n_jobs == 0) return rc;
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(results, d_res, (size_t)n_jobs * sizeof(cfear_reg_result), hipMemcpyDeviceToHost, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  return CFEAR_OK;
+  CFEAR_CHECK(check_params(ctx, par));
+  if (n_jobs == 0) return CFEAR_OK;
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  HostStage st(ctx, kWsRegJobs);
+  JobBatch b(par);
+  CFEAR_CHECK(stage_jobs(ctx, st, jobs, n_jobs, nullptr, results, (size_t)n_jobs, b));
+  char* scr = (char*)cfear_workspace(ctx, kWsRegScratch, reg_scratch_bytes(b.sz.pairs_cap) * (size_t)n_jobs);
+  if (!scr) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
+  CFEAR_CHECK(cfear_register_launch(ctx, b.d_jobs, n_jobs, par, b.sz.pairs_cap, scr, b.d_res, nullptr, b.stride, b.sz.hint(n_jobs)));
+  return st.finish();
 }
 
 // ---- candidate pairs among a table of scans (loop closure) ---------------------------------------------------------
@@ -1634,7 +1630,9 @@ extern "C" int cfear_scan_table_create(cfear_ctx* ctx, const cfear_scan* const* 
   if (!scans || !out || n_scans < 1) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument / empty table");
   *out = nullptr;
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  std::vector<ScanView> views((size_t)n_scans);
+  HostStage st(ctx, kWsRegJobs);
+  const size_t vb = (size_t)n_scans * sizeof(ScanView);
+  ScanView* views = (ScanView*)st.record(vb);
   std::unique_ptr<cfear_scan_table> t(new cfear_scan_table());
   t->ctx = ctx;
   t->n_cells.resize((size_t)n_scans);
@@ -1643,12 +1641,11 @@ extern "C" int cfear_scan_table_create(cfear_ctx* ctx, const cfear_scan* const* 
     if (scans[i]->ctx != ctx) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "scan belongs to another context");
     const int nc = cfear_scan_size(scans[i]);
     if (nc < 0) return nc;
-    views[(size_t)i] = scans[i]->view;
+    views[i] = scans[i]->view;
     t->n_cells[(size_t)i] = nc;
   }
-  CFEAR_HIP_CHECK(ctx, hipMalloc((void**)&t->d_views, views.size() * sizeof(ScanView)));
-  if (hipMemcpyAsync(t->d_views, views.data(), views.size() * sizeof(ScanView), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-      hipStreamSynchronize(ctx->stream) != hipSuccess) {
+  CFEAR_HIP_CHECK(ctx, hipMalloc((void**)&t->d_views, vb));
+  if (st.upload(t->d_views, views, vb) != CFEAR_OK || st.finish() != CFEAR_OK) {
     (void)hipFree(t->d_views);
     return cfear_set_error(ctx, CFEAR_ERR_HIP, "scan table upload failed");
   }
@@ -1681,8 +1678,7 @@ int cfear_candidates_expand(cfear_ctx* ctx, hipStream_t stream, const cfear_scan
                             CandGeometry* geom) {
   if (table->ctx != ctx) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "table belongs to another context");
   const int nt = (int)table->n_cells.size();
-  JobSizes sz;
-  sz.cost = par->cost; sz.huber = par->loss == CFEAR_LOSS_HUBER;
+  JobSizes sz(par);
   int max_tar = 0, max_src = 0;
   for (int i = 0; i < n; i++) {
     const cfear_candidate& c = cands[i];
@@ -1728,29 +1724,21 @@ extern "C" int cfear_register_candidates(cfear_ctx* ctx, const cfear_scan_table*
   int rc = check_params(ctx, par);
   if (rc != CFEAR_OK || n == 0) return rc;
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const size_t cb = (size_t)n * sizeof(cfear_candidate), rb = (size_t)n * sizeof(cfear_reg_result);
-  cfear_candidate* hc = (cfear_candidate*)cfear_pinned(ctx, cb);
-  if (!hc) return cfear_set_error(ctx, CFEAR_ERR_HIP, "pinned staging allocation failed");
-  const bool dev_out = cfear_is_device_ptr(results);
-  cfear_reg_result* d_res = results;
-  if (!dev_out) {
-    d_res = (cfear_reg_result*)cfear_workspace(ctx, kWsCandResults, rb);
-    if (!d_res) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-  }
-  rc = cfear_candidates_enqueue(ctx, table, cands, n, par, hc, d_res, nullptr, 0);
-  if (dev_out) cfear_pinned_mark(ctx);                      // (no synchronisation below: the staging buffer stays in use)
-  if (rc != CFEAR_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-  if (dev_out) return CFEAR_OK;
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(results, d_res, rb, hipMemcpyDeviceToHost, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  return CFEAR_OK;
+  // the candidates are copied into the pinned record and read from there by the expanding kernel (cfear_candidates_expand)
+  HostStage st(ctx, kWsCandResults);
+  cfear_candidate* hc = (cfear_candidate*)st.pinned((size_t)n * sizeof(cfear_candidate));
+  if (!hc) return CFEAR_ERR_HIP;
+  cfear_reg_result* d_res;
+  st.out(d_res, results, (size_t)n * sizeof(cfear_reg_result));
+  CFEAR_CHECK(st.carve());
+  CFEAR_CHECK(cfear_candidates_enqueue(ctx, table, cands, n, par, hc, d_res, nullptr, 0));
+  return st.finish();
 }
 
 int cfear_check_reg_params(cfear_ctx* ctx, const cfear_reg_params* par) { return check_params(ctx, par); }
 
 void cfear_reg_pair_geometry(const cfear_reg_params* par, int max_tar_cells, int max_src_cells, int* pairs_cap, RegLaunchHint* hint) {
-  JobSizes sz;
-  sz.cost = par->cost; sz.huber = par->loss == CFEAR_LOSS_HUBER;
+  JobSizes sz(par);
   sz.add(2, scan_grid_pad(max_tar_cells), scan_grid_pad(max_tar_cells), max_src_cells);
   *pairs_cap = sz.pairs_cap;
   *hint = sz.hint(1);
@@ -1774,50 +1762,29 @@ extern "C" int cfear_register(cfear_ctx* ctx, const cfear_scan* const* scans, in
 // ---- GetCost for batches and covariance by cost sampling ---------------------------------------------
 namespace {
 
-// Runs the cost-only mode over `jobs`; out receives max(mode.n_samples, 1) records per job.
+// Runs the cost-only mode over `jobs`; results (host or device) receives max(mode.n_samples, 1) records per job.
 // itrs (nullable) = per-job leftover itr_; otherwise par->itr applies to every job.
 int run_cost_batch(cfear_ctx* ctx, const cfear_reg_job* jobs, int n_jobs, const cfear_reg_params* par,
-                   const int32_t* itrs, RegCostMode mode, std::vector<cfear_reg_result>& out) {
-  int rc = check_params(ctx, par);
-  if (rc != CFEAR_OK) return rc;
-  const int m = mode.n_samples > 0 ? mode.n_samples : 1;
-  out.assign((size_t)n_jobs * m, cfear_reg_result{});
+                   const int32_t* itrs, RegCostMode mode, cfear_reg_result* results) {
+  CFEAR_CHECK(check_params(ctx, par));
   if (n_jobs == 0) return CFEAR_OK;
+  const int m = mode.n_samples > 0 ? mode.n_samples : 1;
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  int max_scans = 2;
-  for (int j = 0; j < n_jobs; j++) max_scans = std::max(max_scans, std::min(jobs[j].n_scans, kMaxScans));
-  const size_t stride = reg_job_stride(max_scans);
-  const size_t jb = (size_t)n_jobs * stride;
-  unsigned char* hjobs = (unsigned char*)cfear_pinned(ctx, jb);          // pinned: see cfear_register_batch
-  if (!hjobs) return cfear_set_error(ctx, CFEAR_ERR_HIP, "pinned staging allocation failed");
-  JobSizes sz;
-  sz.cost = par->cost; sz.huber = par->loss == CFEAR_LOSS_HUBER;
-  for (int j = 0; j < n_jobs; j++) {
-    unsigned char* dst = hjobs + (size_t)j * stride;
-    rc = gather_job(ctx, jobs[j].scans, jobs[j].n_scans, jobs[j].poses_xyt, dst, sz);
-    if (rc != CFEAR_OK) return rc;
-    if (itrs) cfear_reg_job_set_itr(dst, itrs[j]);
-  }
+  HostStage st(ctx, kWsRegJobs);
+  JobBatch b(par);
+  CFEAR_CHECK(stage_jobs(ctx, st, jobs, n_jobs, itrs, results, (size_t)n_jobs * m, b));
   // a few workgroups per job when the batch alone cannot fill the GPU; scratch bounded to 1 GiB per launch
   mode.blocks_per_job = std::max(1, std::min(m, (1024 + n_jobs - 1) / n_jobs));
-  const size_t per = reg_scratch_bytes(sz.pairs_cap) * (size_t)mode.blocks_per_job;
+  const size_t per = reg_scratch_bytes(b.sz.pairs_cap) * (size_t)mode.blocks_per_job;
   const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_jobs, ((size_t)1 << 30) / per));
-  const size_t rb = out.size() * sizeof(cfear_reg_result);
-  char* ws = (char*)cfear_workspace(ctx, kWsRegJobs, (jb + 255) / 256 * 256 + rb + 512);
   char* scr = (char*)cfear_workspace(ctx, kWsRegScratch, per * (size_t)chunk);
-  if (!ws || !scr) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-  char* d_jobs = ws;
-  cfear_reg_result* d_res = (cfear_reg_result*)(ws + (jb + 255) / 256 * 256);
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(d_jobs, hjobs, jb, hipMemcpyHostToDevice, ctx->stream));
+  if (!scr) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
   for (int j0 = 0; j0 < n_jobs; j0 += chunk) {
     const int nj = std::min(chunk, n_jobs - j0);
-    rc = cfear_register_launch(ctx, d_jobs + (size_t)j0 * stride, nj, par, sz.pairs_cap, scr, d_res + (size_t)j0 * m, &mode, stride,
-                               sz.hint(nj));
-    if (rc != CFEAR_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    CFEAR_CHECK(cfear_register_launch(ctx, b.d_jobs + (size_t)j0 * b.stride, nj, par, b.sz.pairs_cap, scr, b.d_res + (size_t)j0 * m, &mode,
+                                      b.stride, b.sz.hint(nj)));
   }
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(out.data(), d_res, rb, hipMemcpyDeviceToHost, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  return CFEAR_OK;
+  return st.finish();
 }
 
 }  // namespace
@@ -1826,11 +1793,7 @@ extern "C" int cfear_get_cost_batch(cfear_ctx* ctx, const cfear_reg_job* jobs, i
                                     const cfear_reg_params* par, cfear_reg_result* results) {
   if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
   if (!jobs || !results || n_jobs < 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
-  std::vector<cfear_reg_result> out;
-  const int rc = run_cost_batch(ctx, jobs, n_jobs, par, nullptr, RegCostMode{}, out);
-  if (rc != CFEAR_OK) return rc;
-  std::copy(out.begin(), out.end(), results);
-  return CFEAR_OK;
+  return run_cost_batch(ctx, jobs, n_jobs, par, nullptr, RegCostMode{}, results);
 }
 
 extern "C" void cfear_cov_sampling_params_default(cfear_cov_sampling_params* p) {
@@ -1858,10 +1821,9 @@ extern "C" int cfear_covariance_by_sampling_batch(cfear_ctx* ctx, const cfear_re
   mode.yaw_half = sp->yaw_range * 0.5;
   std::vector<int32_t> itrs(n_jobs);
   for (int j = 0; j < n_jobs; j++) itrs[j] = regs[j].outer_iters;      // GetCost's radius follows the leftover itr_
-  std::vector<cfear_reg_result> out;
-  const int rc = run_cost_batch(ctx, jobs, n_jobs, par, itrs.data(), mode, out);
-  if (rc != CFEAR_OK) return rc;
   const int m = mode.n_samples;
+  std::vector<cfear_reg_result> out((size_t)n_jobs * m);
+  CFEAR_CHECK(run_cost_batch(ctx, jobs, n_jobs, par, itrs.data(), mode, out.data()));
   CovFit fit;
   fit.prepare(n, mode.xy_half, mode.yaw_half);
   std::vector<double> costs(m);
@@ -1921,13 +1883,12 @@ extern "C" int cfear_cost_prepare(cfear_ctx* ctx, const cfear_scan* const* scans
   if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
   if (!scans || !poses_xyt || !out) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
   *out = nullptr;
-  int rc = check_params(ctx, par);
-  if (rc != CFEAR_OK) return rc;
+  CFEAR_CHECK(check_params(ctx, par));
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  unsigned char hjob[sizeof(RegJob)];
-  JobSizes sz;
-  rc = gather_job(ctx, scans, n_scans, poses_xyt, hjob, sz);
-  if (rc != CFEAR_OK) return rc;
+  HostStage st(ctx, kWsRegJobs);                      // (no piece: the object owns its device memory)
+  unsigned char* hjob = (unsigned char*)st.record(sizeof(RegJob));
+  JobSizes sz(par);
+  CFEAR_CHECK(gather_job(ctx, scans, n_scans, poses_xyt, hjob, sz));
   cfear_cost* c = new cfear_cost();
   c->ctx = ctx; c->par = *par; c->pairs_cap = sz.pairs_cap; c->n_scans = n_scans;
   c->n_src = cfear_scan_size(scans[n_scans - 1]);
@@ -1936,7 +1897,7 @@ extern "C" int cfear_cost_prepare(cfear_ctx* ctx, const cfear_scan* const* scans
   if (hipMalloc(&c->d_job, sizeof(RegJob) + 256) != hipSuccess) return fail(CFEAR_ERR_HIP, "hipMalloc failed");
   if (hipMalloc((void**)&c->d_scratch, slots_bytes(c->pairs_cap)) != hipSuccess) return fail(CFEAR_ERR_HIP, "hipMalloc failed");
   if (hipMalloc((void**)&c->d_out, ((size_t)c->pairs_cap * 10 + 16) * sizeof(double)) != hipSuccess) return fail(CFEAR_ERR_HIP, "hipMalloc failed");
-  if (hipMemcpyAsync(c->d_job, hjob, sizeof(RegJob), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail(CFEAR_ERR_HIP, "memcpy failed");
+  if (st.upload(c->d_job, hjob, sizeof(RegJob)) != CFEAR_OK) return fail(CFEAR_ERR_HIP, "memcpy failed");
   MatchCommon cm{};
   cm.par = *par; cm.angle_outlier = std::cos(M_PI / 6.0);
   cm.scratch = c->d_scratch; cm.scratch_stride = 0;
@@ -1951,15 +1912,12 @@ extern "C" int cfear_cost_prepare(cfear_ctx* ctx, const cfear_scan* const* scans
   c->h_w.assign(std::max(c->n_slots, 1), -1.0);
   c->h_tidx.assign(std::max(c->n_slots, 1), -1);
   int32_t nb = 0;
-  bool ok = hipMemcpyAsync(&nb, d_nb, 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+  st.fetch(&nb, d_nb, 4);
   if (c->n_slots > 0) {
-    ok = ok && hipMemcpyAsync(c->h_w.data(), (double*)c->d_scratch + 5 * (size_t)c->pairs_cap, (size_t)c->n_slots * 8,
-                              hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-    ok = ok && hipMemcpyAsync(c->h_tidx.data(), (double*)c->d_scratch + 6 * (size_t)c->pairs_cap, (size_t)c->n_slots * 4,
-                              hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    st.fetch(c->h_w.data(), (double*)c->d_scratch + 5 * (size_t)c->pairs_cap, (size_t)c->n_slots * 8);
+    st.fetch(c->h_tidx.data(), (double*)c->d_scratch + 6 * (size_t)c->pairs_cap, (size_t)c->n_slots * 4);
   }
-  ok = ok && hipStreamSynchronize(ctx->stream) == hipSuccess;
-  if (!ok) return fail(CFEAR_ERR_HIP, "read-back failed");
+  if (st.wait() != CFEAR_OK) return fail(CFEAR_ERR_HIP, "read-back failed");
   if (nb < 0) return fail(CFEAR_ERR_CAPACITY, "association capacity exceeded");
   c->n_blocks = nb;
   *out = c;
@@ -1988,6 +1946,21 @@ int run_eval(cfear_cost* c, const double x[3], bool want_raw) {
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
   return CFEAR_OK;
 }
+
+// per-slot residuals r [n_slots][2] (and Jacobians j [n_slots][6], nullable) -> the blocks' rows, the first `cap` of them
+void compact_blocks(const cfear_cost* c, const double* r, const double* j, double* residuals, int cap, double* jacobian) {
+  const int rpb = c->par.cost == CFEAR_P2L ? 1 : 2;
+  int b = 0;
+  for (int slot = 0; slot < c->n_slots; slot++) {
+    if (c->h_w[slot] < 0.0) continue;
+    for (int i = 0; i < rpb; i++) {
+      if (b * rpb + i >= cap) continue;
+      if (residuals) residuals[b * rpb + i] = r[slot * 2 + i];
+      if (jacobian) for (int k = 0; k < 3; k++) jacobian[(b * rpb + i) * 3 + k] = j[slot * 6 + i * 3 + k];
+    }
+    b++;
+  }
+}
 }  // namespace
 
 extern "C" int cfear_cost_get_blocks(const cfear_cost* c, int32_t* pairs, double* weights) {
@@ -2010,21 +1983,13 @@ extern "C" int cfear_cost_evaluate(cfear_cost* c, const double x[3], double* res
   if (rc != CFEAR_OK) return rc;
   const size_t sc = (size_t)c->pairs_cap;
   std::vector<double> r(2 * (size_t)std::max(c->n_slots, 1)), j(6 * (size_t)std::max(c->n_slots, 1));
+  HostStage st(ctx, kWsRegJobs);
   if (c->n_slots > 0) {
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(r.data(), c->d_out, (size_t)c->n_slots * 16, hipMemcpyDeviceToHost, ctx->stream));
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(j.data(), c->d_out + 2 * sc, (size_t)c->n_slots * 48, hipMemcpyDeviceToHost, ctx->stream));
+    st.fetch(r.data(), c->d_out, (size_t)c->n_slots * 16);
+    st.fetch(j.data(), c->d_out + 2 * sc, (size_t)c->n_slots * 48);
   }
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  const int rpb = c->par.cost == CFEAR_P2L ? 1 : 2;
-  int b = 0;
-  for (int slot = 0; slot < c->n_slots; slot++) {
-    if (c->h_w[slot] < 0.0) continue;
-    for (int i = 0; i < rpb; i++) {
-      if (residuals) residuals[b * rpb + i] = r[slot * 2 + i];
-      if (jacobian) for (int k = 0; k < 3; k++) jacobian[(b * rpb + i) * 3 + k] = j[slot * 6 + i * 3 + k];
-    }
-    b++;
-  }
+  CFEAR_CHECK(st.wait());
+  compact_blocks(c, r.data(), j.data(), residuals, INT32_MAX, jacobian);
   return CFEAR_OK;
 }
 
@@ -2035,8 +2000,9 @@ extern "C" int cfear_cost_normal_eq(cfear_cost* c, const double x[3], double H[9
   int rc = run_eval(c, x, false);
   if (rc != CFEAR_OK) return rc;
   double neq[10];
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(neq, c->d_out + 10 * (size_t)c->pairs_cap, sizeof(neq), hipMemcpyDeviceToHost, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  HostStage st(ctx, kWsRegJobs);
+  st.fetch(neq, c->d_out + 10 * (size_t)c->pairs_cap, sizeof(neq));
+  CFEAR_CHECK(st.wait());
   if (cost) *cost = neq[0];
   if (g) { g[0] = neq[1]; g[1] = neq[2]; g[2] = neq[3]; }
   if (H) {
@@ -2075,18 +2041,11 @@ extern "C" int cfear_get_cost(cfear_ctx* ctx, const cfear_scan* const* scans, in
   const size_t sc = (size_t)c->pairs_cap;
   std::vector<double> r(2 * (size_t)c->n_slots);
   double neq[10];
-  hipError_t e1 = hipMemcpyAsync(r.data(), c->d_out + 8 * sc, (size_t)c->n_slots * 16, hipMemcpyDeviceToHost, ctx->stream);
-  hipError_t e2 = hipMemcpyAsync(neq, c->d_out + 10 * sc, sizeof(neq), hipMemcpyDeviceToHost, ctx->stream);
-  hipError_t e3 = hipStreamSynchronize(ctx->stream);
-  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) { cfear_cost_destroy(c); return cfear_set_error(ctx, CFEAR_ERR_HIP, "read-back failed"); }
-  const int rpb = par->cost == CFEAR_P2L ? 1 : 2;
-  int b = 0;
-  for (int slot = 0; slot < c->n_slots; slot++) {
-    if (c->h_w[slot] < 0.0) continue;
-    for (int i = 0; i < rpb; i++)
-      if (residuals && b * rpb + i < cap) residuals[b * rpb + i] = r[slot * 2 + i];
-    b++;
-  }
+  HostStage st(ctx, kWsRegJobs);
+  st.fetch(r.data(), c->d_out + 8 * sc, (size_t)c->n_slots * 16);
+  st.fetch(neq, c->d_out + 10 * sc, sizeof(neq));
+  if (st.wait() != CFEAR_OK) { cfear_cost_destroy(c); return cfear_set_error(ctx, CFEAR_ERR_HIP, "read-back failed"); }
+  compact_blocks(c, r.data(), nullptr, residuals, cap, nullptr);
   *cost = neq[0];
   *n_residuals = nres;
   *score = neq[0] / (double)std::max(nres, 1);                                            // :209

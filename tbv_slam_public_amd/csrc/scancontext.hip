@@ -1388,10 +1388,10 @@ extern "C" int cfear_sc_detect_sequence(cfear_ctx* ctx, const cfear_sc_manager_p
     da.desc_q = d_q; da.desc_c = d_db; da.pairs = d_pairs; da.dist = d_dist; da.shift = d_shift;
     CFEAR_CHECK(sc_distance_launch(ctx, da, np, &par->sc));
     // the chunk's buffers are reused by the next chunk: its copies are ordered before that on the stream
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(h_pairs.data() + (size_t)2 * p0, d_pairs, (size_t)np * 8, hipMemcpyDeviceToHost, ctx->stream));
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(h_dist.data() + p0, d_dist, (size_t)np * 8, hipMemcpyDeviceToHost, ctx->stream));
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(h_shift.data() + p0, d_shift, (size_t)np * 4, hipMemcpyDeviceToHost, ctx->stream));
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(h_psim.data() + p0, d_psim, (size_t)np * 8, hipMemcpyDeviceToHost, ctx->stream));
+    st.fetch(h_pairs.data() + (size_t)2 * p0, d_pairs, (size_t)np * 8);
+    st.fetch(h_dist.data() + p0, d_dist, (size_t)np * 8);
+    st.fetch(h_shift.data() + p0, d_shift, (size_t)np * 4);
+    st.fetch(h_psim.data() + p0, d_psim, (size_t)np * 8);
   }
   CFEAR_CHECK(st.finish());
   // the ranking of every node's pairs, in the streaming loop's visiting order (augmentation, then search rank)

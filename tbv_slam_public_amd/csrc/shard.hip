@@ -194,7 +194,7 @@ extern "C" int cfear_register_batch_sharded(cfear_ctx* ctx, const cfear_reg_job*
     int local_rc = CFEAR_OK;
     if (hipMemsetAsync(d_send, 0, bytes, ctx->stream) != hipSuccess) local_rc = CFEAR_ERR_HIP;
     if (local_rc == CFEAR_OK && hi > lo)
-      local_rc = cfear_register_batch_device(ctx, jobs + lo, hi - lo, par, (cfear_reg_result*)d_send, nullptr);
+      local_rc = cfear_register_batch(ctx, jobs + lo, hi - lo, par, (cfear_reg_result*)d_send);   // device results: not synchronised
     // the trailer travels with the block (a failed block is zeros + the status); written by the device so that no host
     // buffer has to outlive this call
     if (local_rc != CFEAR_OK) (void)hipMemsetAsync(d_send, 0, rbytes, ctx->stream);

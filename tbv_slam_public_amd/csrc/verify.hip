@@ -325,8 +325,8 @@ int verify_device_chain(cfear_ctx* ctx, const cfear_verify_job* jobs, int32_t n_
   if (!scr) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
   CFEAR_CHECK(st.carve());
   mark(0);
-  VerifyDev* hc = (VerifyDev*)cfear_pinned(ctx, n * sizeof(VerifyDev));
-  if (!hc) return cfear_set_error(ctx, CFEAR_ERR_HIP, "pinned staging allocation failed");
+  VerifyDev* hc = (VerifyDev*)st.pinned(n * sizeof(VerifyDev));
+  if (!hc) return CFEAR_ERR_HIP;
   for (size_t j = 0; j < n; j++) {
     const cfear_verify_job& jb = jobs[j];
     VerifyDev& v = hc[j];
@@ -341,8 +341,7 @@ int verify_device_chain(cfear_ctx* ctx, const cfear_verify_job* jobs, int32_t n_
   c.n = n_jobs; c.par = *par;
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
   // ---- the chain ---------------------------------------------------------------------------------------------------------
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync((void*)c.cand, hc, n * sizeof(VerifyDev), hipMemcpyHostToDevice, ctx->stream));
-  cfear_pinned_mark(ctx);
+  CFEAR_CHECK(st.upload((void*)c.cand, hc, n * sizeof(VerifyDev)));
   { ProfScope ps(ctx, "verify_glue"); hipLaunchKernelGGL(verify_expand_kernel, grid, block, 0, ctx->stream, c); }
   int rc = cfear_register_launch(ctx, c.reg_jobs, n_jobs, &rp, pairs_cap, scr, (cfear_reg_result*)c.reg, nullptr, c.stride, hint);
   if (rc == CFEAR_OK) {
@@ -359,7 +358,8 @@ int verify_device_chain(cfear_ctx* ctx, const cfear_verify_job* jobs, int32_t n_
   CFEAR_CHECK(st.finish());
   if (first_bad != 0x7fffffff) {
     cfear_coral_result bad;
-    CFEAR_HIP_CHECK(ctx, hipMemcpy(&bad, c.coral + first_bad, sizeof(bad), hipMemcpyDeviceToHost));
+    st.fetch(&bad, c.coral + first_bad, sizeof(bad));
+    CFEAR_CHECK(st.wait());
     return cfear_set_error(ctx, bad.status, "job %d: %s", first_bad, cfear_status_string(bad.status));
   }
   mark(3);
