@@ -192,75 +192,118 @@ def test_validity_verdict_does_not_flip_between_the_two_eigensolvers():
 # =====================================================================================================
 # 2. Ceres 2.1.0 trust-region LM on dense matrices
 # =====================================================================================================
+LOSSES = ("None", "Huber", "Cauchy", "SoftLOne", "Combined", "Tukey")
+
+
 def _loss(kind, a, s):
-    """ceres::LossFunction::Evaluate -> (rho, rho', rho'') (ceres/loss_function.cc)."""
-    if kind == "Huber":
-        b = a * a
-        if s > b:
-            r = np.sqrt(s)
-            rho1 = max(np.finfo(float).tiny, a / r)
-            return 2.0 * a * r - b, rho1, -rho1 / (2.0 * s)
-        return s, 1.0, 0.0
-    if kind == "Cauchy":
-        b = a * a
-        c = 1.0 / b
-        sm = 1.0 + s * c
-        inv = 1.0 / sm
-        return b * np.log(sm), max(np.finfo(float).tiny, inv), -c * (inv * inv)
+    """ceres::LossFunction::Evaluate -> (rho, rho', rho'') (Ceres 2.1 ceres/loss_function.cc), written from the losses'
+    definitions.  s: a scalar or an array of squared norms, float64 or longdouble; the result has s's shape and type."""
+    s = np.asarray(s)
+    s = s if s.dtype == np.longdouble else s.astype(np.float64)
+    a = s.dtype.type(a)
+    tiny = s.dtype.type(np.finfo(np.float64).tiny)              # std::numeric_limits<double>::min()
+    one, zero = np.ones_like(s), np.zeros_like(s)
     if kind == "None":
-        return s, 1.0, 0.0
+        return s, one, zero
+    if kind == "Huber":                                         # rho = s inside a^2, 2 a sqrt(s) - a^2 outside
+        b = a * a
+        out = s > b
+        r = np.sqrt(np.where(out, s, one))
+        rho1 = np.maximum(tiny, a / r)
+        return np.where(out, 2 * a * r - b, s), np.where(out, rho1, one), np.where(out, -rho1 / (2 * np.where(out, s, one)), zero)
+    if kind == "Cauchy":                                        # rho = a^2 log(1 + s / a^2)
+        b = a * a
+        c = 1 / b
+        sm = 1 + s * c
+        inv = 1 / sm
+        return b * np.log(sm), np.maximum(tiny, inv), -c * (inv * inv)
+    if kind == "SoftLOne":                                      # rho = 2 a^2 (sqrt(1 + s / a^2) - 1)
+        b = a * a
+        sm = 1 + s / b
+        t = np.sqrt(sm)
+        return 2 * b * (t - 1), np.maximum(tiny, 1 / t), -1 / (2 * b * t * sm)
+    if kind == "Tukey":                                         # rho = a^2 / 3 (1 - (1 - s / a^2)^3) inside a^2, a^2 / 3 outside
+        b = a * a
+        inl = s <= b
+        v = 1 - s / b
+        return np.where(inl, b / 3 * (1 - v * v * v), b / 3 + zero), np.where(inl, v * v, zero), np.where(inl, -2 * v / b, zero)
+    if kind == "Combined":                                      # ComposedLoss(f = Huber(1), g = Cauchy(1)), registration.cpp:88-92
+        g0, g1, g2 = _loss("Cauchy", 1.0, s)                    # loss_limit is ignored
+        f0, f1, f2 = _loss("Huber", 1.0, g0)
+        return f0, f1 * g1, f2 * g1 * g1 + f1 * g2
     raise ValueError(kind)
 
 
 class DenseProblem:
     """The residual blocks n_scan_normal_reg::AddScanPairCost hands to ceres::Problem (n_scan_normal.cpp:264-318), from the
-    association list, with the reference's functors (n_scan_normal.h:180-361) and ScaledLoss(GetLoss(), w)."""
+    association list, with the reference's functors (n_scan_normal.h:180-361) and ScaledLoss(GetLoss(), w).  Held as arrays
+    over the blocks, in `dtype`: float64 as Ceres computes, or np.longdouble as the reference the kernels are judged by."""
 
-    def __init__(self, scans, poses, pairs, weights, cost, loss, loss_limit, regularization=0.01, cov_scale=1.0):
-        self.cost, self.loss, self.a = cost, loss, loss_limit
-        self.blocks = []
-        for (ts, ti, si), w in zip(pairs, weights):
-            x, y, th = poses[ts]
-            Rt = np.array([[np.cos(th), -np.sin(th)], [np.sin(th), np.cos(th)]])
-            tar = scans[ts][ti]
-            src = scans[-1][si]
-            blk = {"w": w, "src": src["mean"].copy(), "tar_w": Rt @ tar["mean"] + np.array([x, y])}
-            if cost == "P2L":
-                blk["n_w"] = Rt @ tar["normal"]
-            elif cost == "P2D":
-                cov = tar["cov"].reshape(2, 2)
-                tar_cov = (regularization * np.eye(2) + Rt @ cov @ Rt.T) * cov_scale
-                blk["L"] = np.linalg.cholesky(np.linalg.inv(tar_cov))     # .inverse().llt().matrixL()
-            self.blocks.append(blk)
+    def __init__(self, scans, poses, pairs, weights, cost, loss, loss_limit, regularization=0.01, cov_scale=1.0, dtype=np.float64):
+        self.cost, self.loss, self.a, self.dtype = cost, loss, loss_limit, dtype
+        pairs = np.asarray(pairs).reshape(-1, 3)
+        n = pairs.shape[0]
+        P = np.asarray(poses, dtype)[pairs[:, 0]]                                    # each block's keyframe pose
+        c, s = np.cos(P[:, 2]), np.sin(P[:, 2])
+        Rt = np.stack([np.stack([c, -s], 1), np.stack([s, c], 1)], 1)                # [n, 2, 2]
+        tar = np.zeros(n, O.CELL_DTYPE)
+        for t in np.unique(pairs[:, 0]):
+            tar[pairs[:, 0] == t] = np.asarray(scans[t])[pairs[pairs[:, 0] == t, 1]]
+        self.w = np.asarray(weights, dtype)
+        self.src = scans[-1]["mean"][pairs[:, 2]].astype(dtype)
+        self.tar_w = np.einsum("nij,nj->ni", Rt, tar["mean"].astype(dtype)) + P[:, :2]
+        if cost == "P2L":
+            self.n_w = np.einsum("nij,nj->ni", Rt, tar["normal"].astype(dtype))
+        elif cost == "P2D":
+            cov = tar["cov"].astype(dtype).reshape(n, 2, 2)
+            tc = (dtype(regularization) * np.eye(2, dtype=dtype) + np.einsum("nij,njk,nlk->nil", Rt, cov, Rt)) * dtype(cov_scale)
+            det = tc[:, 0, 0] * tc[:, 1, 1] - tc[:, 0, 1] * tc[:, 1, 0]
+            tr = tc[:, 0, 0] + tc[:, 1, 1]
+            self.kappa = (tr + np.sqrt(tr * tr - 4 * det)) ** 2 / (4 * det)            # condition number of each tar_cov
+            i00, i10, i11 = tc[:, 1, 1] / det, -tc[:, 1, 0] / det, tc[:, 0, 0] / det   # tar_cov.inverse() ...
+            l00 = np.sqrt(i00)                                                       # ... .llt().matrixL()
+            l10 = i10 / l00
+            self.L = np.zeros((n, 2, 2), dtype)
+            self.L[:, 0, 0], self.L[:, 1, 0], self.L[:, 1, 1] = l00, l10, np.sqrt(i11 - l10 * l10)
         self.rpb = 1 if cost == "P2L" else 2
+
+    def raw(self, x):
+        """The functors' own residuals [n, rpb] and Jacobians [n, rpb, 3] at x, before any loss."""
+        x = np.asarray(x, self.dtype)
+        c, s = np.cos(x[2]), np.sin(x[2])
+        R = np.array([[c, -s], [s, c]], self.dtype)
+        dR = np.array([[-s, -c], [c, -s]], self.dtype)
+        p = self.src @ R.T + x[:2]
+        dp = self.src @ dR.T
+        n = p.shape[0]
+        A = np.zeros((n, 2, 3), self.dtype)                       # d p / d (x, y, theta)
+        A[:, 0, 0] = A[:, 1, 1] = 1
+        A[:, :, 2] = dp
+        if self.cost == "P2L":
+            r = np.einsum("ni,ni->n", p - self.tar_w, self.n_w)[:, None]
+            J = np.einsum("ni,nik->nk", self.n_w, A)[:, None, :]
+        elif self.cost == "P2P":
+            r, J = self.tar_w - p, -A
+        else:
+            r = np.einsum("nij,nj->ni", self.L, p - self.tar_w)
+            J = np.einsum("nij,njk->nik", self.L, A)
+        return r, J
 
     def evaluate(self, x, want_jac):
         """ResidualBlock::Evaluate for every block: cost = 1/2 sum rho(s); residuals and Jacobian rows scaled by the
         Corrector (alpha = 0 because rho'' <= 0 here, ceres/corrector.cc)."""
-        c, s = np.cos(x[2]), np.sin(x[2])
-        R = np.array([[c, -s], [s, c]])
-        dR = np.array([[-s, -c], [c, -s]])
-        r_all, J_all, cost = [], [], 0.0
-        for b in self.blocks:
-            p = R @ b["src"] + x[:2]
-            dp = dR @ b["src"]
-            if self.cost == "P2L":
-                r = np.array([(p - b["tar_w"]) @ b["n_w"]])
-                J = np.array([[b["n_w"][0], b["n_w"][1], dp @ b["n_w"]]])
-            elif self.cost == "P2P":
-                r = b["tar_w"] - p
-                J = -np.array([[1.0, 0.0, dp[0]], [0.0, 1.0, dp[1]]])
-            else:
-                r = b["L"] @ (p - b["tar_w"])
-                J = b["L"] @ np.array([[1.0, 0.0, dp[0]], [0.0, 1.0, dp[1]]])
-            sq = float(r @ r)
-            rho = np.array(_loss(self.loss, self.a, sq)) * b["w"]           # ScaledLoss
-            cost += 0.5 * rho[0]
-            sr = np.sqrt(rho[1])
-            r_all.append(r * sr)
-            if want_jac:
-                J_all.append(J * sr)
-        return cost, np.concatenate(r_all), (np.vstack(J_all) if want_jac else None)
+        r, J = self.raw(x)
+        self.sq = (r * r).sum(1)
+        rho0, rho1, rho2 = _loss(self.loss, self.a, self.sq)
+        assert (rho2 <= 0).all()
+        cost = 0.5 * (rho0 * self.w).sum()                        # ScaledLoss
+        sr = np.sqrt(rho1 * self.w)
+        return cost, (r * sr[:, None]).reshape(-1), ((J * sr[:, None, None]).reshape(-1, 3) if want_jac else None)
+
+    def normal_eq(self, x):
+        """(H = J^T J, g = J^T r, cost) of the robustified problem at x."""
+        cost, r, J = self.evaluate(x, True)
+        return J.T @ J, J.T @ r, cost
 
 
 def ceres_trust_region_lm(problem, x0, max_num_iterations):
@@ -351,21 +394,38 @@ def ceres_trust_region_lm(problem, x0, max_num_iterations):
     return x, np.array(iters), final_cost, usable
 
 
-@pytest.mark.parametrize("cost,loss,limit,wopt", [("P2L", "Huber", 0.1, 0), ("P2P", "Huber", 0.1, 4), ("P2L", "Huber", 0.3, 0),
-                                                  ("P2P", "Cauchy", 0.1, 4), ("P2D", "Huber", 0.1, 0), ("P2L", "None", 0.1, 1)])
+_SCANS = {}
+
+
+def _scene_scans(seed, n):
+    """(cells of the first n frames of synth.scene_v1(seed), ground truth), built once per module."""
+    if (seed, n) not in _SCANS:
+        from tbv_slam_public_amd import synth
+        imgs, gt, _ = synth.scene_v1(seed, n)
+        scans = []
+        for f in range(n):
+            sr, si, sc = O.kstrongest(imgs[f], 40, 60)
+            scans.append(O.surface_points(O.kstrongest_cloud(sr, si, sc, 0.0438, 2.5), 3.0, 1.0, (0, 0), True))
+        _SCANS[(seed, n)] = (scans, gt)
+    return _SCANS[(seed, n)]
+
+
+# every loss x every cost x limits {0.1, 0.3, 1.0} (P2D: 2.0 as well) x weights {0, 4}, and the one case of the earlier,
+# shorter list that lies outside that grid
+_LM_CASES = [(c, l, a, w) for c in ("P2P", "P2L", "P2D") for l in LOSSES for a in ((0.1, 0.3, 1.0, 2.0) if c == "P2D" else (0.1, 0.3, 1.0))
+             for w in (0, 4)] + [("P2L", "None", 0.1, 1)]
+
+
+@pytest.mark.parametrize("cost,loss,limit,wopt", _LM_CASES)
 def test_ceres_lm_restatement_tracks_the_oracle_iterate_by_iterate(cost, loss, limit, wopt):
-    from tbv_slam_public_amd import synth
-    imgs, gt, _ = synth.scene_v1(77, 3)
-    scans = []
-    for f in range(3):
-        sr, si, sc = O.kstrongest(imgs[f], 40, 60)
-        scans.append(O.surface_points(O.kstrongest_cloud(sr, si, sc, 0.0438, 2.5), 3.0, 1.0, (0, 0), True))
+    scans, gt = _scene_scans(77, 3)
     rng = np.random.default_rng(5)
     n_cmp = 0
-    for trial in range(6):
+    for trial in range(9):                                         # the last three start a tenth as far from the truth: there
+        near = 0.1 if trial >= 6 else 1.0                          # the narrow limits have inliers and the solver has work to do
         use = scans[:2] if trial % 2 == 0 else scans               # 1 or 2 fixed keyframes
         poses = np.array([gt[i] - gt[0] for i in range(len(use))])
-        poses[-1] += np.concatenate([rng.normal(0, 0.4, 2), rng.normal(0, np.deg2rad(1.5), 1)])
+        poses[-1] += near * np.concatenate([rng.normal(0, 0.4, 2), rng.normal(0, np.deg2rad(1.5), 1)])
         par = O.reg_params(cost=cost, loss=loss, loss_limit=limit, weight_opt=wopt, regularization=0.01)
         for itr, max_iter in ((1, 20), (2, 10)):                   # radius 2 r on the first outer iteration, r afterwards
             pairs, w = O.associate(use, poses, par, itr)
@@ -382,6 +442,72 @@ def test_ceres_lm_restatement_tracks_the_oracle_iterate_by_iterate(cost, loss, l
             assert abs(fc_o - fc_n) <= 1e-9 * max(fc_o, 1e-12)
             n_cmp += tr_o.shape[0]
     assert n_cmp > 20
+
+
+@pytest.mark.parametrize("cost", ["P2P", "P2L", "P2D"])
+@pytest.mark.parametrize("loss", LOSSES)
+@pytest.mark.parametrize("wopt", [0, 1, 2, 3, 4])
+def test_oracle_normal_equations_and_cost_match_the_longdouble_restatement(cost, loss, wopt):
+    """Point-wise, every (cost, loss, weight) triple at two limits: the oracle's H, g, cost (orc_normal_eq) and its GetCost
+    (cost, robustified residuals, score) against DenseProblem evaluated in np.longdouble with the independently written
+    losses.  Bounds of test_association_pairs_and_normal_equations / test_get_cost_matches_oracle: H rtol 1e-10, g 1e-9, cost
+    1e-11, residuals 1e-9.  Limits 0.3 and 1.0 put blocks on both sides of Huber's and Tukey's branch for P2P and P2L; P2D is
+    evaluated nearer the truth for the same reason (asserted below: no branch of any loss goes unvisited)."""
+    scans, gt = _scene_scans(1, 3)
+    both_sides = 0
+    for limit in (0.3, 1.0):
+        for use, off in ((scans[:2], 1.0), (scans, 0.25 if cost == "P2D" else 0.5)):
+            poses = np.array([gt[i] - gt[0] for i in range(len(use))])
+            poses[-1] += off * np.array([0.4, -0.3, 0.01])
+            x = poses[-1] + (10.0 if cost == "P2L" else 1.0) * np.array([0.05, -0.02, 0.003])   # (P2L: |r| must pass 1 m)
+            for itr in (1, 2):
+                par = O.reg_params(cost=cost, loss=loss, loss_limit=limit, weight_opt=wopt, regularization=0.01, first_itr=itr)
+                pairs, w = O.associate(use, poses, par, itr)
+                assert len(pairs) > 30
+                prob = DenseProblem(use, poses, pairs, w, cost, loss, limit, dtype=np.longdouble)
+                H, g, c = prob.normal_eq(x)
+                Ho, go, co, nres = O.normal_eq(use, poses, par, itr, x)
+                assert nres == len(pairs) * prob.rpb
+                np.testing.assert_allclose(Ho, H.astype(np.float64), rtol=1e-10, atol=1e-10)
+                np.testing.assert_allclose(go, g.astype(np.float64), rtol=1e-9, atol=1e-9)
+                np.testing.assert_allclose(co, float(c), rtol=1e-11)
+                if loss in ("Huber", "Tukey", "Combined"):
+                    out = (np.log1p(prob.sq) > 1.0) if loss == "Combined" else (prob.sq > np.longdouble(limit) ** 2)
+                    both_sides += 0.05 <= out.mean() <= 0.95
+                c2, r2, _ = prob.evaluate(poses[-1], False)            # GetCost evaluates at the pose it associates at
+                ok, cg, rg, sg = O.get_cost(use, poses, par)
+                assert ok and rg.shape == r2.shape
+                np.testing.assert_allclose(cg, float(c2), rtol=1e-11)
+                np.testing.assert_allclose(rg, r2.astype(np.float64), rtol=1e-9, atol=1e-12)
+                np.testing.assert_allclose(sg, float(c2) / r2.shape[0], rtol=1e-11)
+    if loss in ("Huber", "Tukey", "Combined"):
+        assert both_sides >= 4, both_sides                            # at least half of the 8 evaluations straddle the branch
+
+
+def test_loss_restatement_is_consistent_with_its_own_derivatives():
+    """rho' and rho'' of the six restated losses are the derivatives of rho (central differences in longdouble), rho(0) = 0,
+    rho'(0) = 1 and rho'' <= 0: a swapped a / a^2 or a missing factor in _loss cannot hide behind an equal slip elsewhere."""
+    s = np.concatenate([np.linspace(0.0, 4.5, 181), 10.0 ** np.linspace(-8, 2, 41)]).astype(np.longdouble)
+    for kind in LOSSES:
+        for a in (0.1, 0.3, 1.0, 2.0):
+            lim = np.longdouble(a) ** 2 if kind in ("Huber", "Tukey") else np.longdouble(np.e - 1) if kind == "Combined" else None
+            h = np.longdouble(1e-7) * np.maximum(s, np.longdouble(1e-3))
+            keep = s - h > 0
+            if lim is not None:
+                keep &= np.abs(s - lim) > 2 * h                         # the kink itself has no second derivative
+            r0, r1, r2 = _loss(kind, a, s)
+            d1 = (_loss(kind, a, s + h)[0] - _loss(kind, a, s - h)[0]) / (2 * h)
+            d2 = (_loss(kind, a, s + h)[1] - _loss(kind, a, s - h)[1]) / (2 * h)
+            np.testing.assert_allclose(r1[keep].astype(float), d1[keep].astype(float), rtol=1e-7, atol=1e-9)
+            np.testing.assert_allclose(r2[keep].astype(float), d2[keep].astype(float), rtol=1e-6, atol=1e-8)
+            z = _loss(kind, a, np.longdouble(0.0))
+            assert float(z[0]) == 0.0 and float(z[1]) == 1.0 and (r2 <= 0).all()
+            assert (np.diff(r0.astype(float)[:181]) >= 0).all()         # rho is non-decreasing
+    # hand values: Huber(0.5) at s = 1: 2 * 0.5 * 1 - 0.25; Tukey(2) at s = 2: 4/3 * (1 - 1/8); SoftLOne(1) at s = 3: 2
+    assert abs(float(_loss("Huber", 0.5, 1.0)[0]) - 0.75) < 1e-15
+    assert abs(float(_loss("Tukey", 2.0, 2.0)[0]) - 7.0 / 6.0) < 1e-15 and abs(float(_loss("Tukey", 2.0, 2.0)[1]) - 0.25) < 1e-15
+    assert abs(float(_loss("SoftLOne", 1.0, 3.0)[0]) - 2.0) < 1e-15 and abs(float(_loss("SoftLOne", 1.0, 3.0)[1]) - 0.5) < 1e-15
+    assert abs(float(_loss("Combined", 7.0, np.e ** 4 - 1)[0]) - 3.0) < 1e-14      # g = 4 > 1: 2 sqrt(4) - 1
 
 
 def test_lm_fixed_point_is_a_minimum_of_the_robust_cost():
