@@ -211,6 +211,33 @@ int cfear_filter_cacfar(cfear_ctx* ctx, const uint8_t* polar, const cfear_polar_
                         const cfear_cacfar_params* par, float* xyzi, int32_t* n_points,
                         int32_t cap_points, uint8_t* det_mask);
 
+/* Cen and Newman's 2018 landmark detector: replaces cen2018features (coral_alignment_quality/src/alignment_checker/
+ * Utils.cpp:348-434) and the cloud loop of Cen2018Radar (ScanType.cpp:68-88).  Per azimuth row: f = v / 255, q = f - mean(f)
+ * (serial float sum), p = q filtered with 3 * sigma_gauss Gaussian taps (BORDER_REFLECT101), sigma = sqrt(mean of 2 q^2 over
+ * the bins with q < 0) (0.034 when there is none), y = q (1 - N(q - p)) + p (N(q - p) - N(p)) with N(x) = exp(-x^2 / 2 sigma^2);
+ * every maximal run of bins with y > zq * sigma gives ONE target, element len / 2 of the run.  Points sit at the bin EDGE
+ * (range_res * bin), azimuth (row + 1) / rows * 2 pi, intensity = the raw byte; ordered (row, bin).
+ * min_range_bins: the reference hands sensor_min_distance (2.5, metres) to an `int min_range` that its loop uses as a BIN
+ * index, so its near cut is bin 2 whatever the resolution; the parameter is therefore in bins and defaults to 2, not to
+ * min_distance / range_res.
+ * xyzi float [batch][cap_points][4], n_points int32 [batch]; optional: targets int32 [batch][cap_points][2] (azimuth, bin),
+ * det_mask uint8 [batch][rows][cols] (y > thres; 0 below min_range_bins), row_stats float [batch][rows][2] (mean, sigma).
+ * The image and every output are all host or all device memory.  An image with more than cap_points targets yields
+ * CFEAR_ERR_CAPACITY (n_points then holds the counts, the buffers the first cap_points).  CFEAR_ERR_INVALID_ARGUMENT:
+ * sigma_gauss even, below 1 or above 341, 3 * sigma_gauss > cols, min_range_bins < 0, zq not finite, range_res not finite.
+ * The call waits for the counts on every route (it is synchronous).                                                      */
+typedef struct cfear_cen2018_params {
+  float zq;                             /* threshold in noise sigmas: 3.0 (ScanType.cpp:72) */
+  int32_t sigma_gauss;                  /* 17; the filter has 3 * sigma_gauss taps */
+  int32_t min_range_bins;               /* 2 (see above) */
+  int32_t pad;
+  double range_res;                     /* 0.04328 (ScanType.h:62) */
+} cfear_cen2018_params;
+void cfear_cen2018_params_default(cfear_cen2018_params* par);
+int cfear_filter_cen2018(cfear_ctx* ctx, const uint8_t* polar, const cfear_polar_desc* desc, const cfear_cen2018_params* par,
+                         float* xyzi, int32_t* n_points, int32_t cap_points, int32_t* targets, uint8_t* det_mask,
+                         float* row_stats);
+
 /* ---- C: motion compensation ----------------------------------------------------------------
  * Replaces Compensate(cloud, mot, ccw)  utils.cpp:96-107 (+ GetRelTimeStamp utils.h:28-32).
  * xyzi float [n][4] modified in place; mot = (x, y, theta) of the previous motion.           */

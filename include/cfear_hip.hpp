@@ -759,6 +759,48 @@ class CorAlRadarQuality {
  private:
   cfear_coral_result res_{};
 };
+
+// Cen2018Radar (ScanType.h:148, ScanType.cpp:68-88): the Cen and Newman 2018 landmark cloud of one polar sweep.  Parameters
+// carries the members of PoseScan::Parameters (ScanType.h:55-76) the constructor reads.  sensor_min_distance reaches
+// cen2018features as `int min_range`, a BIN index (Utils.cpp:348, :402): int(2.5) = bin 2 whatever range_res is -- the mirror
+// truncates it the same way.
+class Cen2018Radar {
+ public:
+  struct Parameters {
+    double sensor_min_distance = 2.5, range_res = 0.04328;
+    bool compensate = true, ccw = false;
+  };
+  Cen2018Radar(CFEAR_Radarodometry::Context& ctx, const Parameters& pars, const uint8_t* image, int rows, int cols, int stride,
+               const CFEAR_Radarodometry::Pose2d& T = CFEAR_Radarodometry::Pose2d{0, 0, 0},
+               const CFEAR_Radarodometry::Pose2d& Tmotion = CFEAR_Radarodometry::Pose2d{0, 0, 0})
+      : T_(T), Tmotion_(Tmotion) {
+    cfear_polar_desc d{rows, cols, stride, 1, 0};
+    cfear_cen2018_params p;
+    cfear_cen2018_params_default(&p);                      // zq 3.0, sigma_gauss 17 (ScanType.cpp:72)
+    p.min_range_bins = (int32_t)pars.sensor_min_distance;
+    p.range_res = pars.range_res;
+    const int32_t cap = rows * ((cols + 1) / 2);           // a row of n bins holds at most ceil(n / 2) runs
+    cloud_.resize((size_t)cap);
+    std::vector<int32_t> tg((size_t)cap * 2);
+    int32_t n = 0;
+    ctx.check(cfear_filter_cen2018(ctx.get(), image, &d, &p, &cloud_[0].x, &n, cap, tg.data(), nullptr, nullptr));
+    cloud_.resize((size_t)n);
+    targets_.assign(tg.begin(), tg.begin() + 2 * (size_t)n);
+    if (pars.compensate) CFEAR_Radarodometry::Compensate(ctx, cloud_, Tmotion_, pars.ccw);      // ScanType.cpp:86-87
+  }
+#ifdef CFEAR_HIP_HAVE_CV_BRIDGE
+  // the reference's constructor shape (ScanType.cpp:68)
+  Cen2018Radar(const Parameters& pars, cv_bridge::CvImagePtr& polar, const Eigen::Affine3d& T, const Eigen::Affine3d& Tmotion)
+      : Cen2018Radar(CFEAR_Radarodometry::Context::Default(), pars, polar->image.data, polar->image.rows, polar->image.cols,
+                     (int)polar->image.step, CFEAR_Radarodometry::Affine3dToPose2d(T), CFEAR_Radarodometry::Affine3dToPose2d(Tmotion)) {}
+#endif
+  const CFEAR_Radarodometry::PointCloud& GetCloud() const { return cloud_; }
+  const std::vector<int32_t>& GetTargets() const { return targets_; }       // (azimuth, bin) pairs: targets_ rows 0 and 1
+  CFEAR_Radarodometry::Pose2d T_, Tmotion_;
+ private:
+  CFEAR_Radarodometry::PointCloud cloud_;
+  std::vector<int32_t> targets_;
+};
 }  // namespace CorAlignment
 
 // RSCManager (place_recognition_radar/RadarScancontext.h): descriptor database + candidate retrieval.

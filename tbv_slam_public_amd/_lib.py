@@ -50,6 +50,11 @@ class CacfarParams(C.Structure):
                 ("max_distance", C.c_double)]
 
 
+class Cen2018Params(C.Structure):
+    _fields_ = [("zq", C.c_float), ("sigma_gauss", C.c_int32), ("min_range_bins", C.c_int32), ("pad", C.c_int32),
+                ("range_res", C.c_double)]
+
+
 class Cell(C.Structure):
     _fields_ = [("mean", C.c_double * 2), ("normal", C.c_double * 2), ("cov", C.c_double * 4),
                 ("scale", C.c_double), ("avg_intensity", C.c_double), ("lambda_min", C.c_double),
@@ -234,7 +239,7 @@ EXPORTS = [
     "cfear_rccl_unique_id", "cfear_rccl_comm_init", "cfear_rccl_comm_destroy",
     "cfear_candidate_pipe_create", "cfear_candidate_pipe_submit", "cfear_candidate_pipe_collect", "cfear_candidate_pipe_destroy", "cfear_candidate_pipe_stats",
     "cfear_eval_params_default", "cfear_eval_trajectories", "cfear_eval_check", "cfear_kitti_read", "cfear_kitti_write",
-    "cfear_kitti_from_xyt",
+    "cfear_kitti_from_xyt", "cfear_cen2018_params_default", "cfear_filter_cen2018",
 ]
 
 PIPE_GRAPH, PIPE_TIMING = 1, 2      # enum { CFEAR_PIPE_GRAPH, CFEAR_PIPE_TIMING }
@@ -354,6 +359,9 @@ def lib():
                                           C.POINTER(KStrongOut)]
     L.cfear_filter_cacfar.argtypes = [vp, vp, C.POINTER(PolarDesc), C.POINTER(CacfarParams), vp, vp,
                                       C.c_int32, vp]
+    L.cfear_cen2018_params_default.argtypes = [C.POINTER(Cen2018Params)]
+    L.cfear_cen2018_params_default.restype = None
+    L.cfear_filter_cen2018.argtypes = [vp, vp, C.POINTER(PolarDesc), C.POINTER(Cen2018Params), vp, vp, C.c_int32, vp, vp, vp]
     L.cfear_compensate.argtypes = [vp, vp, C.c_int32, C.POINTER(C.c_double), C.c_int32]
     L.cfear_scan_create.argtypes = [vp, vp, C.c_int32, C.POINTER(FeatureParams), C.POINTER(vp)]
     L.cfear_scan_from_cells.argtypes = [vp, vp, C.c_int32, C.POINTER(vp)]
