@@ -1029,6 +1029,54 @@ int cfear_kitti_read(const char* path, double* poses, int64_t cap, int64_t* n_ou
 int cfear_kitti_write(const char* path, const double* poses, int64_t n);
 int cfear_kitti_from_xyt(const double* xyt, int64_t n, int64_t stride, double* poses);
 
+/* ---- after the path: training the classifiers (alignment_checker's LogisticRegression::fit) --------------------------
+ * What the reference asks of sklearn.linear_model.LogisticRegression(class_weight="balanced", max_iter=1000) through
+ * pybind11 (coral_alignment_quality/src/alignment_checker/alignmentinterface.cpp:192-222), for a batch of models in one
+ * launch, one workgroup each (csrc/logreg.hip).  Per model, over (w in R^d, b):
+ *     F = 1/2 w.w + C sum_i s_i [log(1 + exp(z_i)) - y_i z_i],  z_i = w.x_i + b,  y_i in {0, 1},
+ *     s_i = n / (2 n_class(i)) with class_weight_balanced, else 1; the intercept is not penalised.
+ * With both classes present F is strictly convex; the kernel minimises it in fp64 by a damped Newton iteration (LDL^T
+ * of the Jacobi-scaled Hessian, Armijo backtracking) and stops when the Newton decrement is at most 1e-16 max(1, |F|)
+ * or no trial step decreases F.  It is a second-order solve, so it lands on the minimiser where sklearn's L-BFGS may
+ * stop short on unscaled features (EXPERIMENTS.md, "Fitting the classifiers").  Every sum has a fixed order: a
+ * model's record is bit-identical at any batch position and whether its buffers were host or device memory.            */
+#define CFEAR_LOGREG_MAX_FEATURES 8
+typedef struct cfear_logreg_params {
+  double C;                             /* 1.0: inverse regularisation strength, > 0                                 */
+  int32_t class_weight_balanced;        /* 1                                                                         */
+  int32_t fit_intercept;                /* 1                                                                         */
+  int32_t max_iterations;               /* 100 Newton steps (the reference's 1000 bounds L-BFGS steps)               */
+  int32_t pad;
+} cfear_logreg_params;                  /* 24 bytes */
+void cfear_logreg_params_default(cfear_logreg_params* p);
+typedef struct cfear_logreg_job {
+  const double* X;                      /* [n_rows][row_stride], host or device                                      */
+  const double* y;                      /* [n_rows], host or device                                                  */
+  const int32_t* columns;               /* host: n_features indices into a row, or NULL = 0 .. n_features - 1        */
+  const uint8_t* row_mask;              /* [n_rows], host or device: 0 = the row is left out; or NULL                */
+  int64_t n_rows;
+  int32_t row_stride, n_features;       /* doubles between rows; 1 .. CFEAR_LOGREG_MAX_FEATURES                      */
+} cfear_logreg_job;                     /* 48 bytes */
+typedef struct cfear_logreg_result {
+  double intercept, coef[CFEAR_LOGREG_MAX_FEATURES];   /* coef[n_features ..] = 0                                    */
+  double objective, grad_inf;           /* F and the largest absolute entry of its gradient at the result            */
+  double balanced_accuracy;             /* sklearn's balanced_accuracy_score of predict() on the used rows (:69-80)  */
+  int64_t n_used, n_pos;                /* rows the mask leaves; of those, rows with y = 1                           */
+  int64_t confusion[4];                 /* tn, fp, fn, tp at z > 0: confusion_matrix row-major (:83-94)              */
+  int32_t iterations;                   /* Newton steps taken                                                        */
+  int32_t status;                       /* CFEAR_OK; CFEAR_ERR_INVALID_ARGUMENT; CFEAR_ERR_SOLVER                    */
+} cfear_logreg_result;                  /* 152 bytes */
+/* Jobs that name the same X, y or row_mask pointer share one upload (at the longest extent any of them names), so the
+ * CorAl, CFEAR and combined models of one table, or the folds of a cross-validation, cost one copy.  results [n_jobs] is
+ * host memory; the call returns when it is written.  A job's own trouble is its status and leaves the call and the other
+ * jobs alone: CFEAR_ERR_INVALID_ARGUMENT for no used rows, one class only (sklearn raises), a label that is not 0 or 1,
+ * a used value that is not finite (the reference's DataValid exits the process); CFEAR_ERR_SOLVER when max_iterations
+ * steps did not converge or an iterate is not finite -- the record then holds the last iterate.  The whole call is
+ * refused with CFEAR_ERR_INVALID_ARGUMENT, before anything is launched, for n_jobs < 0, null pointers, n_features outside
+ * 1 .. 8, a negative column index, or a row_stride smaller than n_features or than max(columns) + 1; n_jobs = 0 is OK.  */
+int cfear_logreg_fit_batch(cfear_ctx* ctx, const cfear_logreg_job* jobs, int32_t n_jobs, const cfear_logreg_params* par,
+                           cfear_logreg_result* results);
+
 #ifdef __cplusplus
 }
 #endif

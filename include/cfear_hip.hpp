@@ -11,7 +11,9 @@
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <cstdio>
 #include <ctime>
+#include <fstream>
 #include <iostream>
 #include <map>
 #include <memory>
@@ -800,6 +802,239 @@ class Cen2018Radar {
  private:
   CFEAR_Radarodometry::PointCloud cloud_;
   std::vector<int32_t> targets_;
+};
+
+// PythonClassifierInterface + LogisticRegression (alignmentinterface.h:32-119, alignmentinterface.cpp:14-279) without the
+// embedded interpreter: fit() minimises the objective of sklearn's LogisticRegression(class_weight="balanced") on the GPU
+// (cfear_logreg_fit_batch).  Eigen::MatrixXd X_ becomes row-major doubles with cols_ values a row.  Where the reference
+// exits the process on invalid training data (:194-196) fit() throws CfearError.
+class LogisticRegression {
+ public:
+  LogisticRegression() : ctx_(nullptr) {}                                     // the calling thread's default context
+  explicit LogisticRegression(CFEAR_Radarodometry::Context& ctx) : ctx_(&ctx) {}
+  void AddDataPoint(const std::vector<double>& X_i, const std::vector<double>& y_i) {         // :50-66: y_i.size() rows
+    if (y_i.empty() || X_i.size() % y_i.size() != 0 || (!y_.empty() && X_i.size() / y_i.size() != cols_))
+      throw CFEAR_Radarodometry::CfearError(CFEAR_ERR_INVALID_ARGUMENT, "AddDataPoint: rows of a different width");
+    cols_ = X_i.size() / y_i.size();
+    X_.insert(X_.end(), X_i.begin(), X_i.end());
+    y_.insert(y_.end(), y_i.begin(), y_i.end());
+  }
+  void AddDataPoint(const std::vector<double>& x, double y) { AddDataPoint(x, std::vector<double>{y}); }
+  bool DataValid() const {                                                     // :172-185
+    if (y_.empty() || X_.size() != y_.size() * cols_) return false;
+    for (double v : X_) if (!std::isfinite(v)) return false;
+    for (double v : y_) if (!std::isfinite(v)) return false;
+    return true;
+  }
+  void fit() {                                                                 // :192-222
+    if (!DataValid()) throw CFEAR_Radarodometry::CfearError(CFEAR_ERR_INVALID_ARGUMENT, "training data invalid");
+    CFEAR_Radarodometry::Context& ctx = ctx_ ? *ctx_ : CFEAR_Radarodometry::Context::Default();
+    cfear_logreg_params par;
+    cfear_logreg_params_default(&par);
+    cfear_logreg_job job{};
+    job.X = X_.data(); job.y = y_.data(); job.n_rows = (int64_t)y_.size();
+    job.row_stride = job.n_features = (int32_t)cols_;
+    ctx.check(cfear_logreg_fit_batch(ctx.get(), &job, 1, &par, &record_));
+    if (record_.status != CFEAR_OK)
+      throw CFEAR_Radarodometry::CfearError(record_.status, record_.status == CFEAR_ERR_SOLVER ? "logistic regression did not converge"
+                                                                                               : "training data invalid: one class only, or a label that is not 0 or 1");
+    coef_.assign(record_.coef, record_.coef + cols_);
+    intercept_ = record_.intercept;
+    is_fit_ = true;
+  }
+  bool IsFit() const { return is_fit_; }
+  std::vector<double> predict_linear(const std::vector<double>& X) const {     // :271-279
+    const size_t d = coef_.size(), n = d ? X.size() / d : 0;
+    std::vector<double> score(n);
+    for (size_t i = 0; i < n; i++) {
+      double s = 0;
+      for (size_t k = 0; k < d; k++) s += coef_[k] * X[i * d + k];
+      score[i] = s + intercept_;
+    }
+    return score;
+  }
+  std::vector<double> predict_proba(const std::vector<double>& X) const {      // :21-33: P(y = 1); zeros when not fitted
+    if (!is_fit_) return std::vector<double>(cols_ ? X.size() / cols_ : 0, 0.0);
+    std::vector<double> p = predict_linear(X);
+    for (double& v : p) v = 1.0 / (1.0 + std::exp(-v));
+    return p;
+  }
+  std::vector<double> predict_proba() const { return predict_proba(X_); }
+  std::vector<double> predict(const std::vector<double>& X) const {            // :36-47: the class, 1 where z > 0
+    if (!is_fit_) return std::vector<double>(cols_ ? X.size() / cols_ : 0, 0.0);
+    std::vector<double> p = predict_linear(X);
+    for (double& v : p) v = v > 0.0 ? 1.0 : 0.0;
+    return p;
+  }
+  std::vector<double> predict() const { return predict(X_); }
+  // sklearn's confusion_matrix, row-major {tn, fp, fn, tp} (:83-94), and balanced_accuracy_score (:69-80; -1 as the reference)
+  static std::array<int64_t, 4> ConfusionMatrix(const std::vector<double>& y_true, const std::vector<double>& y_pred) {
+    std::array<int64_t, 4> c{{0, 0, 0, 0}};
+    if (y_true.size() != y_pred.size()) return c;
+    for (size_t i = 0; i < y_true.size(); i++) c[(y_true[i] != 0.0 ? 2 : 0) + (y_pred[i] != 0.0 ? 1 : 0)]++;
+    return c;
+  }
+  std::array<int64_t, 4> ConfusionMatrix() const { return ConfusionMatrix(y_, predict()); }
+  static double Accuracy(const std::vector<double>& y_true, const std::vector<double>& y_pred) {
+    if (y_true.size() != y_pred.size() || y_true.empty()) return -1;
+    const std::array<int64_t, 4> c = ConfusionMatrix(y_true, y_pred);
+    double sum = 0;
+    int classes = 0;
+    if (c[0] + c[1] > 0) { sum += (double)c[0] / (double)(c[0] + c[1]); classes++; }
+    if (c[2] + c[3] > 0) { sum += (double)c[3] / (double)(c[2] + c[3]); classes++; }
+    return sum / classes;
+  }
+  double Accuracy() const { return Accuracy(y_, predict()); }
+  void LoadData(const std::string& path) {                                     // :96-130: "y,x0,x1,..." per line
+    std::ifstream file(path);
+    std::string line;
+    std::vector<double> X, y;
+    while (std::getline(file, line)) {
+      if (line.empty()) continue;
+      std::stringstream ls(line);
+      std::string value;
+      std::getline(ls, value, ',');
+      y.push_back(std::stod(value));
+      while (std::getline(ls, value, ',')) X.push_back(std::stod(value));
+    }
+    if (!y.empty()) { cols_ = X.size() / y.size(); X_.swap(X); y_.swap(y); }
+  }
+  void SaveData(const std::string& path) const {                               // :149-170, the stream's default precision
+    std::ofstream f(path, std::ofstream::out);
+    if (!f.is_open()) return;
+    for (size_t i = 0; i < y_.size(); i++) {
+      f << y_[i];
+      for (size_t k = 0; k < cols_; k++) f << "," << X_[i * cols_ + k];
+      f << std::endl;
+    }
+  }
+  void LoadCoefficients(const std::string& path) {                             // :224-253: "intercept,c0,c1,..."
+    std::ifstream file(path);
+    std::string line;
+    std::vector<double> coefs;
+    while (std::getline(file, line)) {
+      if (line.empty()) continue;
+      std::stringstream ls(line);
+      std::string value;
+      std::getline(ls, value, ',');
+      intercept_ = std::stod(value);
+      while (std::getline(ls, value, ',')) coefs.push_back(std::stod(value));
+    }
+    coef_ = coefs;
+    if (!cols_) cols_ = coef_.size();
+    is_fit_ = true;
+  }
+  void SaveCoefficients(const std::string& path) const {                       // :255-269
+    std::ofstream f(path);
+    if (!f.is_open()) return;
+    f << intercept_ << ",";
+    for (size_t i = 0; i < coef_.size(); i++) f << coef_[i] << (i + 1 != coef_.size() ? "," : "");
+    f << "\n";
+  }
+  const std::vector<double>& coef() const { return coef_; }
+  double intercept() const { return intercept_; }
+  const cfear_logreg_result& record() const { return record_; }               // objective, grad_inf, iterations of the last fit()
+  std::vector<double> X_, y_;                                                  // training rows [y_.size()][cols_] and labels
+  size_t cols_ = 0;
+ private:
+  CFEAR_Radarodometry::Context* ctx_;
+  std::vector<double> coef_;
+  double intercept_ = 0.0;
+  bool is_fit_ = false;
+  cfear_logreg_result record_{};
+};
+
+// ScanLearningInterface (alignmentinterface.h:127-218, alignmentinterface.cpp:288-510) over the mirrors above: the 13
+// perturbations of AddTrainingData, CorAl and CFEAR quality per pair, the classifiers fitted on the GPU.  A thin mirror:
+// one quality call per perturbation (the Python mirror's AddTrainingDataBatch batches a whole sequence).
+class ScanLearningInterface {
+ public:
+  struct s_scan {                                                              // :130-146 (cld is never read)
+    CFEAR_Radarodometry::Pose2d T{0, 0, 0};
+    const CFEAR_Radarodometry::PointCloud* cldPeaks = nullptr;
+    const CFEAR_Radarodometry::MapPointNormal* CFEAR = nullptr;
+  };
+  explicit ScanLearningInterface(CFEAR_Radarodometry::Context& ctx, bool combined = true)
+      : ctx_(ctx), cfear_class(ctx), coral_class(ctx), combined_class(ctx), combined_(combined) {
+    const double e = range_error_, th[3] = {0.5 * M_PI / 180.0, 2 * M_PI / 180.0, 15 * M_PI / 180.0}, m[3] = {1, 2, 4};
+    vek_perturbation_.push_back({0, 0, 0});                                    // CreatePerturbations (:479-495)
+    for (int k = 0; k < 3; k++) {
+      vek_perturbation_.push_back({m[k] * e, 0, th[k]}); vek_perturbation_.push_back({0, m[k] * e, th[k]});
+      vek_perturbation_.push_back({-m[k] * e, 0, th[k]}); vek_perturbation_.push_back({0, -m[k] * e, th[k]});
+    }
+  }
+  void AddTrainingData(const s_scan& current) {                                // :296-347
+    if (frame_++ == 0) { prev_ = current; return; }
+    if (std::hypot(current.T.x - prev_.T.x, current.T.y - prev_.T.y) < min_dist_btw_scans_) return;
+    for (const CFEAR_Radarodometry::Pose2d& verr : vek_perturbation_) {
+      const std::vector<double> xc = CorAlQuality(current, prev_, verr), xf = CFEARQuality(current, prev_, verr);
+      const double y = std::fabs(verr.x) + std::fabs(verr.y) + std::fabs(verr.theta) < 0.0001 ? 1.0 : 0.0;
+      if (combined_) {
+        std::vector<double> x(xc);
+        x.insert(x.end(), xf.begin(), xf.end());
+        combined_class.AddDataPoint(x, y);
+      } else {
+        coral_class.AddDataPoint(xc, y);
+        cfear_class.AddDataPoint(xf, y);
+      }
+    }
+    prev_ = current;
+  }
+  void PredAlignment(const s_scan& current, const s_scan& prev, std::map<std::string, double>& quality) {      // :349-367
+    const CFEAR_Radarodometry::Pose2d id{0, 0, 0};
+    const std::vector<double> xc = CorAlQuality(current, prev, id), xf = CFEARQuality(current, prev, id);
+    if (combined_) {
+      std::vector<double> x(xc);
+      x.insert(x.end(), xf.begin(), xf.end());
+      quality["alignment_quality"] = combined_class.predict_linear(x)[0];
+    } else {
+      quality["coral"] = coral_class.predict_proba(xc)[0];
+      quality["CFEAR"] = cfear_class.predict_proba(xf)[0];
+    }
+  }
+  void FitModels(const std::string& = "LogisticRegression") {                  // :423-434
+    if (combined_) combined_class.fit();
+    else { coral_class.fit(); cfear_class.fit(); }
+  }
+  void LoadData(const std::string& dir) {                                      // :376-383
+    if (combined_) combined_class.LoadData(dir + "/combined.txt");
+    else { coral_class.LoadData(dir + "/CorAl.txt"); cfear_class.LoadData(dir + "/CFEAR.txt"); }
+  }
+  void SaveData(const std::string& dir) {                                      // :386-393
+    if (combined_) combined_class.SaveData(dir + "/combined.txt");
+    else { coral_class.SaveData(dir + "/CorAl.txt"); cfear_class.SaveData(dir + "/CFEAR.txt"); }
+  }
+  void LoadCoefficients(const std::string& dir) {                              // :396-403: dir is concatenated without "/"
+    if (combined_) combined_class.LoadCoefficients(dir + "trained_alignment_classifier.txt");
+    else { coral_class.LoadCoefficients(dir + "trained_alignment_classifier_CorAl.txt"); cfear_class.LoadCoefficients(dir + "trained_alignment_classifier_CFEAR.txt"); }
+  }
+  void SaveCoefficients(const std::string& dir) {                              // :405-412
+    if (combined_) combined_class.SaveCoefficients(dir + "/trained_alignment_classifier.txt");
+    else { coral_class.SaveCoefficients(dir + "/trained_alignment_classifier_CorAl.txt"); cfear_class.SaveCoefficients(dir + "/trained_alignment_classifier_CFEAR.txt"); }
+  }
+  LogisticRegression& Combined() { return combined_class; }
+  LogisticRegression& CorAl() { return coral_class; }
+  LogisticRegression& CFEAR() { return cfear_class; }
+ private:
+  std::vector<double> CorAlQuality(const s_scan& cur, const s_scan& prev, const CFEAR_Radarodometry::Pose2d& off) {      // :437-456
+    return CorAlRadarQuality(ctx_, *cur.cldPeaks, cur.T, *prev.cldPeaks, prev.T, off).GetQualityMeasure();
+  }
+  std::vector<double> CFEARQuality(const s_scan& cur, const s_scan& prev, const CFEAR_Radarodometry::Pose2d& off) {      // :459-478, AlignmentQuality.cpp:330-354
+    CFEAR_Radarodometry::n_scan_normal_reg reg(ctx_, CFEAR_P2L, CFEAR_LOSS_HUBER, 0.3);
+    const double c = std::cos(prev.T.theta), s = std::sin(prev.T.theta);
+    const std::vector<CFEAR_Radarodometry::Pose2d> T = {cur.T, {c * off.x - s * off.y + prev.T.x, s * off.x + c * off.y + prev.T.y, prev.T.theta + off.theta}};
+    double score = 0;
+    std::vector<double> residuals;
+    if (!reg.GetCost({cur.CFEAR, prev.CFEAR}, T, score, residuals)) return {0, 0, 0};
+    return {score, (double)residuals.size(), (double)(prev.CFEAR->GetSize() + cur.CFEAR->GetSize()) / 2.0};
+  }
+  CFEAR_Radarodometry::Context& ctx_;
+  LogisticRegression cfear_class, coral_class, combined_class;
+  const double range_error_ = 0.5, min_dist_btw_scans_ = 0.5;                  // :196-197
+  s_scan prev_;
+  unsigned frame_ = 0;
+  bool combined_;
+  std::vector<CFEAR_Radarodometry::Pose2d> vek_perturbation_;
 };
 }  // namespace CorAlignment
 

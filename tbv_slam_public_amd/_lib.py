@@ -240,6 +240,7 @@ EXPORTS = [
     "cfear_candidate_pipe_create", "cfear_candidate_pipe_submit", "cfear_candidate_pipe_collect", "cfear_candidate_pipe_destroy", "cfear_candidate_pipe_stats",
     "cfear_eval_params_default", "cfear_eval_trajectories", "cfear_eval_check", "cfear_kitti_read", "cfear_kitti_write",
     "cfear_kitti_from_xyt", "cfear_cen2018_params_default", "cfear_filter_cen2018",
+    "cfear_logreg_params_default", "cfear_logreg_fit_batch",
 ]
 
 PIPE_GRAPH, PIPE_TIMING = 1, 2      # enum { CFEAR_PIPE_GRAPH, CFEAR_PIPE_TIMING }
@@ -317,6 +318,24 @@ assert EVAL_SUMMARY_DTYPE.itemsize == 360
 EVAL_ROW_DTYPE = np.dtype([("trajectory", "<i4"), ("first_frame", "<i4"), ("last_frame", "<i4"), ("pad", "<i4"),
                            ("length", "<f8"), ("r_err", "<f8"), ("t_err", "<f8"), ("speed", "<f8")])
 assert EVAL_ROW_DTYPE.itemsize == 48
+
+LOGREG_MAX_FEATURES = 8
+
+
+class LogregParams(C.Structure):    # cfear_logreg_params
+    _fields_ = [("C", C.c_double), ("class_weight_balanced", C.c_int32), ("fit_intercept", C.c_int32),
+                ("max_iterations", C.c_int32), ("pad", C.c_int32)]
+
+
+class LogregJob(C.Structure):       # cfear_logreg_job
+    _fields_ = [("X", C.c_void_p), ("y", C.c_void_p), ("columns", C.POINTER(C.c_int32)), ("row_mask", C.c_void_p),
+                ("n_rows", C.c_int64), ("row_stride", C.c_int32), ("n_features", C.c_int32)]
+
+
+LOGREG_RESULT_DTYPE = np.dtype([("intercept", "<f8"), ("coef", "<f8", (LOGREG_MAX_FEATURES,)), ("objective", "<f8"),
+                                ("grad_inf", "<f8"), ("balanced_accuracy", "<f8"), ("n_used", "<i8"), ("n_pos", "<i8"),
+                                ("confusion", "<i8", (4,)), ("iterations", "<i4"), ("status", "<i4")])
+assert C.sizeof(LogregParams) == 24 and C.sizeof(LogregJob) == 48 and LOGREG_RESULT_DTYPE.itemsize == 152
 
 _LIB = None
 
@@ -479,5 +498,8 @@ def lib():
     L.cfear_kitti_read.argtypes = [C.c_char_p, vp, C.c_int64, C.POINTER(C.c_int64)]
     L.cfear_kitti_write.argtypes = [C.c_char_p, vp, C.c_int64]
     L.cfear_kitti_from_xyt.argtypes = [vp, C.c_int64, C.c_int64, vp]
+    L.cfear_logreg_params_default.argtypes = [C.POINTER(LogregParams)]
+    L.cfear_logreg_params_default.restype = None
+    L.cfear_logreg_fit_batch.argtypes = [vp, C.POINTER(LogregJob), C.c_int32, C.POINTER(LogregParams), vp]
     _LIB = L
     return L

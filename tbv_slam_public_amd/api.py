@@ -933,10 +933,75 @@ def prepare_verify_batch(cands):
     return (arr, n, keep + [cands])
 
 
+def logreg_params(ctx=None, **kw):
+    """cfear_logreg_params with the reference's settings (C = 1, balanced class weights, intercept, 100 Newton steps)."""
+    p = L.LogregParams()
+    L.lib().cfear_logreg_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in ("C", "class_weight_balanced", "fit_intercept", "max_iterations"):
+            raise KeyError(k)
+        setattr(p, k, float(v) if k == "C" else int(v))
+    return p
+
+
+def logreg_fit_batch(jobs, ctx=None, **params):
+    """cfear_logreg_fit_batch: every model of `jobs` fitted in one launch -> LOGREG_RESULT_DTYPE array (coef[n_features:] = 0).
+    A job is a dict, or a tuple in this order, of
+      X         float64 [n_rows, row_stride], NumPy (host) or torch CUDA tensor, rows contiguous
+      y         float64 [n_rows], 0 or 1
+      columns   optional: the indices into a row that are the model's features (default: all of them, at most 8)
+      row_mask  optional: uint8 / bool [n_rows], 0 = the row is left out
+    Jobs that pass the same array object share its upload.  params: C, class_weight_balanced, fit_intercept,
+    max_iterations.  A job's own failure is its record's status; arguments the library refuses raise CfearError."""
+    ctx = ctx or default_context()
+    par = logreg_params(ctx, **params)
+    n = len(jobs)
+    arr = (L.LogregJob * max(n, 1))()
+    seen, keep = {}, []
+
+    def buf(x, dtype):
+        if x is None:
+            return None, None
+        if id(x) not in seen:
+            if _is_torch(x):
+                import torch
+                want = {np.float64: torch.float64, np.uint8: torch.uint8}[dtype]
+                v = x.view(torch.uint8) if dtype is np.uint8 and x.dtype == torch.bool else x
+                assert v.dtype == want and v.is_contiguous(), "torch buffers must be contiguous %s" % want
+            else:
+                v = np.ascontiguousarray(x, dtype=dtype)
+            seen[id(x)] = v
+            keep.append((x, v))
+        v = seen[id(x)]
+        return _ptr(v)[0], v
+
+    for i, job in enumerate(jobs):
+        if not isinstance(job, dict):
+            job = dict(zip(("X", "y", "columns", "row_mask"), job))
+        pX, X = buf(job["X"], np.float64)
+        py, y = buf(job["y"], np.float64)
+        pm, m = buf(job.get("row_mask"), np.uint8)
+        assert X.ndim == 2 and y.ndim == 1 and y.shape[0] == X.shape[0] and (m is None or tuple(m.shape) == (X.shape[0],))
+        cols = job.get("columns")
+        j = arr[i]
+        j.X, j.y, j.row_mask = pX, py, pm
+        j.n_rows, j.row_stride = int(X.shape[0]), int(X.shape[1])
+        if cols is None:
+            j.columns, j.n_features = None, int(X.shape[1])
+        else:
+            c = (C.c_int32 * len(cols))(*[int(k) for k in cols])
+            keep.append(c)
+            j.columns, j.n_features = c, len(cols)
+    out = np.zeros(n, L.LOGREG_RESULT_DTYPE)
+    ctx.check(ctx._lib.cfear_logreg_fit_batch(ctx.h, arr, n, C.byref(par), out.ctypes.data))
+    return out
+
+
 class LogisticRegression:
     """PythonClassifierInterface + LogisticRegression (alignmentinterface.cpp:14-279): training rows, the two text
     formats, predict_linear.  fit() is sklearn's LogisticRegression(class_weight="balanced", max_iter=1000), the
-    call the reference makes through pybind11 (:192-222)."""
+    call the reference makes through pybind11 (:192-222); fit_device() minimises the same objective on the GPU
+    (cfear_logreg_fit_batch) and needs no sklearn."""
 
     def __init__(self):
         self.X_ = np.zeros((0, 0))
@@ -966,6 +1031,25 @@ class LogisticRegression:
         self.coef_ = np.asarray(clf.coef_[0], np.float64).copy()
         self.intercept_ = float(clf.intercept_[0])
         self.is_fit_ = True
+
+    def _take_record(self, r):
+        """Adopts one cfear_logreg_result; what the reference exits on raises ValueError, as fit() does."""
+        self.fit_record_ = r
+        if r["status"] == L.ERR_INVALID_ARGUMENT:
+            raise ValueError("training data invalid")
+        if r["status"] != L.OK:
+            raise L.CfearError(int(r["status"]), "logistic regression did not converge in %d Newton steps" % r["iterations"])
+        self.coef_ = np.array(r["coef"][:self.X_.shape[1]], np.float64)
+        self.intercept_ = float(r["intercept"])
+        self.is_fit_ = True
+
+    def fit_device(self, ctx=None, **params):
+        """fit() on the GPU: the minimiser of sklearn's objective by Newton's method in fp64 -> the cfear_logreg_result
+        record (objective, grad_inf, iterations, confusion, balanced_accuracy: what the reference prints, :211)."""
+        if not self.DataValid():
+            raise ValueError("training data invalid")
+        self._take_record(logreg_fit_batch([(self.X_, self.y_)], ctx, **params)[0])
+        return self.fit_record_
 
     def LoadData(self, path):                                           # :103-134: "y,x0,x1,..." per line
         rows = [ln.strip().split(",") for ln in open(path) if ln.strip()]
@@ -1046,6 +1130,36 @@ class ScanLearningInterface:
                 self.cfear_class.AddDataPoint(xf, y)
         self.prev_ = current
 
+    def AddTrainingDataBatch(self, scans):
+        """AddTrainingData for a whole sequence: the same first-frame, min_dist_btw_scans_ and prev_ bookkeeping as calling
+        it scan by scan, but every kept pair x the 13 perturbations goes through ONE coral_quality_batch launch and ONE
+        cfear_quality_batch launch instead of one of each per pair."""
+        pairs = []
+        for current in scans:
+            first = self.frame_ == 0
+            self.frame_ += 1
+            if first:
+                self.prev_ = current
+                continue
+            d = np.hypot(current["T"][0] - self.prev_["T"][0], current["T"][1] - self.prev_["T"][1])
+            if d < self.min_dist_btw_scans_:
+                continue
+            pairs.append((current, self.prev_))
+            self.prev_ = current
+        if not pairs:
+            return
+        cj = [(c["cldPeaks"], c["T"], p["cldPeaks"], p["T"], o) for c, p in pairs for o in self.vek_perturbation_]
+        qj = [(c["CFEAR"], c["T"], p["CFEAR"], p["T"], o) for c, p in pairs for o in self.vek_perturbation_]
+        co, _ = coral_quality_batch(cj, 1.0, False, False, self.ctx)
+        Xc = np.stack([co["joint"], co["sep"], co["overlap"]], 1).astype(np.float64)
+        Xf = cfear_quality_batch(qj, "P2L", self.ctx)
+        y = np.array([float(sum(abs(v) for v in verr) < 0.0001) for verr in self.vek_perturbation_] * len(pairs), np.float64)
+        if self.combined_:
+            self.combined_class.AddDataPoint(np.concatenate([Xc, Xf], 1), y)
+        else:
+            self.coral_class.AddDataPoint(Xc, y)
+            self.cfear_class.AddDataPoint(Xf, y)
+
     def PredAlignment(self, current, prev, quality=None):                # :349-367
         """-> (quality dict, X_CorAl, X_CFEAR); `valid` of the reference is valid1 && valid2 of two locals that
         are never written, i.e. always false, and unused by its callers."""
@@ -1085,6 +1199,18 @@ class ScanLearningInterface:
     def FitModels(self, model="LogisticRegression"):                     # :423-434
         for clf, _ in self._files("", "", "", ""):
             clf.fit()
+
+    def FitModelsDevice(self, **params):
+        """FitModels on the GPU: the models this interface owns (combined, or CorAl and CFEAR) in one
+        cfear_logreg_fit_batch call -> their records."""
+        models = [clf for clf, _ in self._files("", "", "", "")]
+        for clf in models:
+            if not clf.DataValid():
+                raise ValueError("training data invalid")
+        out = logreg_fit_batch([(clf.X_, clf.y_) for clf in models], self.ctx, **params)
+        for clf, r in zip(models, out):
+            clf._take_record(r)
+        return out
 
     def verify_params(self, **kw):
         """cfear_verify_params carrying this interface's combined classifier."""

@@ -45,6 +45,7 @@ enum WsSlot : int {
   kWsScSequence = 15,     // whole-graph Scan Context: node tables, descriptor database, query chunks
   kWsEval = 16,           // trajectory evaluation: staged and normalised poses, distances, tables, staged outputs
   kWsPgo = 17,            // batched pose-graph optimisation: one chunk's poses, tables and solver state
+  kWsLogreg = 18,         // classifier fits: staged rows, labels and masks, job records, results
 };
 
 struct cfear_ctx {
@@ -57,7 +58,7 @@ struct cfear_ctx {
   std::vector<hipEvent_t> event_pool;
   // grow-only device workspaces (indexed by WsSlot so stages of one pipeline do not alias)
   struct Ws { void* p = nullptr; size_t bytes = 0; };
-  Ws ws[18];
+  Ws ws[19];
   // pinned host staging for small read-backs
   void* pinned = nullptr;
   size_t pinned_bytes = 0;

@@ -12,8 +12,8 @@
 //   VerificationModel (:220-238) over {odom-bounds, sc-sim, alignment_quality}
 //   ApplyConstratins (:261-274): accept by probability, all candidates or the best of each query.
 // Three device launches for the whole batch; the classifiers are a dozen multiply-adds per candidate on the host,
-// as in the reference.  Training the classifiers (sklearn through pybind11 in the reference,
-// alignmentinterface.cpp:192-222) is not part of the library: coefficients come in through cfear_verify_params.
+// as in the reference.  Coefficients come in through cfear_verify_params; fitting them (sklearn through pybind11 in the
+// reference, alignmentinterface.cpp:192-222) is cfear_logreg_fit_batch, csrc/logreg.hip.
 #include <chrono>
 #include <algorithm>
 #include <cmath>
