@@ -489,6 +489,63 @@ int cfear_coral_quality(cfear_ctx* ctx, const cfear_coral_job* job, const cfear_
 int cfear_coral_quality_batch(cfear_ctx* ctx, const cfear_coral_job* jobs, int32_t n_jobs,
                               const cfear_coral_params* par, cfear_coral_result* results, double* per_point);
 
+/* ---- caller: point-to-point alignment quality and keypoint repeatability -----------------------------
+ * Replaces p2pQuality and keypointRepetability (coral_alignment_quality/src/alignment_checker/AlignmentQuality.cpp:
+ * 235-328), the measures AlignmentQualityFactory::CreateQualityType (AlignmentQuality.h:260-312) builds for
+ * Cen2018Radar, kstrongStructuredRadar and BFARScan scans with method "P2P" / "keypoint_repetability" and that
+ * scanEvaluator (ScanEvaluator.cpp:57-114, the body of evaluate_scans) scores a sequence with.  The source cloud is
+ * moved by Tchange = Tref.inverse() * Tsrc * Toffset (:260-264) with pcl::transformPointCloud's rounding, every moved
+ * point asks pcl::KdTreeFLANN<PointXYZI>::radiusSearch over the reference cloud (3-D, d = dx dx + dy dy + dz dz in float,
+ * kept when d < float(radius * radius), strictly) for its nearest neighbour, and
+ *   p2pQuality            residuals_ = the nearest d of every source point that has one, in source order, pushed BEHIND
+ *                         the {0, 0, 0} the base constructor leaves there (AlignmentQuality.h:92): quality_[0] = mean =
+ *                         sum / (matched + 3), quality_ = {mean, 0, 0};
+ *   keypointRepetability  quality_ = {matched / n_src, matched, n_src} -- read off the same record.
+ * The caller composes Tchange (include/cfear_hip.hpp and api.py do, with the same fp64 formula), so a record is a pure
+ * function of (ref, src, T, radius).  Eigen's Affine3d::inverse() is a general inverse: the reference's last bits of T
+ * are not pinned.                                                                                 */
+typedef struct cfear_p2p_job {
+  const float* ref_xyzi;                /* [n_ref][4] x,y,z,intensity, host or device                   */
+  const float* src_xyzi;                /* [n_src][4], host or device                                   */
+  int32_t n_ref, n_src;
+  double T[6];                          /* Tchange, row-major 2x3: x' = T0 x + T1 y + T2, y' = T3 x + T4 y + T5 */
+} cfear_p2p_job;
+
+typedef struct cfear_p2p_result {
+  double mean;                          /* p2pQuality quality_[0] = sum / (matched + 3)                 */
+  double sum;                           /* sum of the matched points' nearest squared distances         */
+  int32_t matched;                      /* source points with a neighbour: keypointRepetability quality_[1] */
+  int32_t n_src;                        /* keypointRepetability quality_[2]                             */
+  int32_t status;                       /* CFEAR_OK / CFEAR_ERR_EMPTY_CLOUD / CFEAR_ERR_CAPACITY        */
+  int32_t pad;
+} cfear_p2p_result;                     /* 32 bytes */
+
+/* Limits.  One workgroup sorts a reference cloud into a uniform grid of radius * 1.0001 cells over its bounding box and
+ * serves every job of the batch that names it (same pointer, same n_ref): the perturbations of a scan pair cost one sort.
+ * radius must be > 0 and finite and every T finite, else CFEAR_ERR_INVALID_ARGUMENT.  CFEAR_ERR_CAPACITY:
+ *   - n_ref > CFEAR_P2P_MAX_REF_POINTS or n_src > CFEAR_P2P_MAX_SRC_POINTS in any job: the call returns at entry,
+ *     nothing is launched, no record is written;
+ *   - per job, as results[j].status: a NaN coordinate (x, y or z) in either cloud -- for the source cloud, after the
+ *     transform as well (0 * inf) -- or a reference cloud whose grid has
+ *     more than 4096 rows (y extent / radius), more than 2^31 - 1 cells, or a cell index beyond 2^22 (|x| or |y| /
+ *     radius).  The source cloud may lie anywhere: points outside the grid have no neighbour.
+ * An empty source or reference cloud is the job's status CFEAR_ERR_EMPTY_CLOUD and does not fail the call.  Any other
+ * failed job makes the call return that job's status (the first such job's); every record is written all the same --
+ * failed jobs as zeros with their status, all others valid.  The per_point row of a failed job is unspecified.
+ *
+ * matched, n_src and per_point are exact.  sum is added per thread in source order (stride 1024) and then over a fixed
+ * tree, so it is within 2 n_src 2^-53, relatively, of the reference's serial sum; a job's record and per_point row do not
+ * depend on the batch around it.
+ *
+ * results [n_jobs] and per_point (optional; the jobs' [n_src] floats back to back: the nearest d, or -1.0f where the point
+ * has none) may each be host or device memory.  With device clouds and device outputs the call is only enqueued; the
+ * statuses are then the caller's to read, and the call returns CFEAR_OK.                                             */
+#define CFEAR_P2P_MAX_REF_POINTS 16384
+#define CFEAR_P2P_MAX_SRC_POINTS 1048576
+int cfear_p2p_quality(cfear_ctx* ctx, const cfear_p2p_job* job, double radius, cfear_p2p_result* result, float* per_point);
+int cfear_p2p_quality_batch(cfear_ctx* ctx, const cfear_p2p_job* jobs, int32_t n_jobs, double radius,
+                            cfear_p2p_result* results, float* per_point);
+
 /* ---- before the path: radar Scan Context (loop-candidate generation) ------------------------------
  * Replaces the arithmetic of RSCManager / SCManager (place_recognition_radar/src/place_recognition_radar/
  * RadarScancontext.cpp:59-131, 156-180; Scancontext.cpp:60-268): the ring x sector descriptor of a

@@ -804,6 +804,223 @@ class Cen2018Radar {
   std::vector<int32_t> targets_;
 };
 
+// p2pQuality, keypointRepetability (AlignmentQuality.h:119-150, AlignmentQuality.cpp:235-328) and scanEvaluator
+// (ScanEvaluator.h:21-137, ScanEvaluator.cpp:4-114) over cfear_p2p_quality.  A PoseScan here is the cloud, the pose and the
+// id the measures read (ScanType.h: GetCloudNoCopy, GetAffine, pose_id); Eigen::Affine3d becomes Pose2d.
+struct PoseScan {
+  CFEAR_Radarodometry::PointCloud cloud;
+  CFEAR_Radarodometry::Pose2d T{0, 0, 0};
+  int pose_id = 0;
+  const CFEAR_Radarodometry::Pose2d& GetAffine() const { return T; }
+};
+typedef std::shared_ptr<PoseScan> PoseScan_S;
+
+class AlignmentQuality {
+ public:
+  class parameters {                                                           // AlignmentQuality.h:53-86
+   public:
+    parameters() {}
+    std::string method = "P2L";
+    double radius = 3;
+    bool weight_res_intensity = false;
+    bool output_overlap = true;
+    bool visualize = false;
+  };
+  AlignmentQuality(const parameters& par, const CFEAR_Radarodometry::Pose2d& Toffset) : par_(par), Toffset_(Toffset) {
+    quality_ = {0, 0, 0};
+    residuals_ = {0, 0, 0};                                                    // AlignmentQuality.h:92: p2pQuality pushes BEHIND these
+  }
+  virtual ~AlignmentQuality() {}
+  virtual std::vector<double> GetResiduals() { return residuals_; }
+  virtual std::vector<double> GetQualityMeasure() { return quality_; }
+  // Tchange = Tref.inverse() * Tsrc * Toffset (AlignmentQuality.cpp:260-264) as cfear_p2p_job::T: the inverse is
+  // (R^T, -R^T t), every product a plain fp64 multiply and add, left to right -- api.p2p_tchange is the same formula
+  static std::array<double, 6> Tchange(const CFEAR_Radarodometry::Pose2d& ref, const CFEAR_Radarodometry::Pose2d& src,
+                                       const CFEAR_Radarodometry::Pose2d& off) {
+    typedef std::array<double, 6> A;                                           // l0 l1 l2 l3 t0 t1
+    const auto aff = [](const CFEAR_Radarodometry::Pose2d& p) { const double c = std::cos(p.theta), s = std::sin(p.theta); return A{{c, -s, s, c, p.x, p.y}}; };
+    const auto mul = [](const A& a, const A& b) {
+      return A{{a[0] * b[0] + a[1] * b[2], a[0] * b[1] + a[1] * b[3], a[2] * b[0] + a[3] * b[2], a[2] * b[1] + a[3] * b[3],
+                a[0] * b[4] + a[1] * b[5] + a[4], a[2] * b[4] + a[3] * b[5] + a[5]}};
+    };
+    const A r = aff(ref);
+    const A inv{{r[0], r[2], r[1], r[3], -(r[0] * r[4] + r[2] * r[5]), -(r[1] * r[4] + r[3] * r[5])}};
+    const A m = mul(mul(inv, aff(src)), aff(off));
+    return A{{m[0], m[1], m[4], m[2], m[3], m[5]}};
+  }
+  parameters par_;
+  const CFEAR_Radarodometry::Pose2d Toffset_;
+  std::vector<double> quality_;
+  std::vector<double> residuals_;
+  bool valid_ = false;
+
+ protected:
+  // one cfear_p2p_quality call for (ref, src, Toffset); per_point: the nearest d of every source point, -1 without one
+  cfear_p2p_result Run(CFEAR_Radarodometry::Context& ctx, const PoseScan& ref, const PoseScan& src, std::vector<float>* per_point) const {
+    cfear_p2p_job j{};
+    j.ref_xyzi = ref.cloud.empty() ? nullptr : &ref.cloud[0].x;
+    j.src_xyzi = src.cloud.empty() ? nullptr : &src.cloud[0].x;
+    j.n_ref = (int32_t)ref.cloud.size(); j.n_src = (int32_t)src.cloud.size();
+    const std::array<double, 6> T = Tchange(ref.T, src.T, Toffset_);
+    for (int k = 0; k < 6; k++) j.T[k] = T[(size_t)k];
+    if (per_point) per_point->assign(src.cloud.size() + 1, -1.0f);
+    cfear_p2p_result r{};
+    ctx.check(cfear_p2p_quality(ctx.get(), &j, par_.radius, &r, per_point ? per_point->data() : nullptr));
+    if (per_point) per_point->resize(src.cloud.size());
+    return r;
+  }
+};
+typedef std::shared_ptr<AlignmentQuality> AlignmentQuality_S;
+
+class p2pQuality : public AlignmentQuality {
+ public:
+  p2pQuality(PoseScan_S ref, PoseScan_S src, const AlignmentQuality::parameters& par,
+             const CFEAR_Radarodometry::Pose2d Toffset = CFEAR_Radarodometry::Pose2d{0, 0, 0})
+      : p2pQuality(CFEAR_Radarodometry::Context::Default(), ref, src, par, Toffset) {}
+  p2pQuality(CFEAR_Radarodometry::Context& ctx, PoseScan_S ref, PoseScan_S src, const AlignmentQuality::parameters& par,
+             const CFEAR_Radarodometry::Pose2d Toffset = CFEAR_Radarodometry::Pose2d{0, 0, 0})
+      : AlignmentQuality(par, Toffset) {
+    std::vector<float> pp;
+    record_ = Run(ctx, *ref, *src, &pp);
+    for (float d : pp)
+      if (d >= 0.0f) residuals_.push_back((double)d);                          // :283-285, source order
+    quality_ = {record_.mean, 0, 0};                                           // GetQualityMeasure (:235-248): sum / (matched + 3)
+  }
+  std::vector<double> GetResiduals() override { return residuals_; }
+  std::vector<double> GetQualityMeasure() override { return quality_; }
+  cfear_p2p_result record_{};
+};
+
+class keypointRepetability : public AlignmentQuality {
+ public:
+  keypointRepetability(PoseScan_S ref, PoseScan_S src, const AlignmentQuality::parameters& par,
+                       const CFEAR_Radarodometry::Pose2d Toffset = CFEAR_Radarodometry::Pose2d{0, 0, 0})
+      : keypointRepetability(CFEAR_Radarodometry::Context::Default(), ref, src, par, Toffset) {}
+  keypointRepetability(CFEAR_Radarodometry::Context& ctx, PoseScan_S ref, PoseScan_S src, const AlignmentQuality::parameters& par,
+                       const CFEAR_Radarodometry::Pose2d Toffset = CFEAR_Radarodometry::Pose2d{0, 0, 0})
+      : AlignmentQuality(par, Toffset) {
+    record_ = Run(ctx, *ref, *src, nullptr);
+    const double matched = (double)record_.matched, total = (double)record_.n_src;
+    quality_ = {matched / total, matched, total};                               // NaN for an empty source cloud, as 0.0 / 0.0 there
+  }
+  cfear_p2p_result record_{};
+};
+
+// One row of eval.txt (ScanEvaluator.h:21-52 declares the class; the rules are stated in tests/p2p_cpu.py): the pair's
+// 1-based index, the two pose ids, the planar distance between the poses, the measure's three values, the offset and
+// whether it counts as aligned (its absolute values add up to less than 1e-4).
+class datapoint {
+ public:
+  double distance_;
+  std::vector<double> residuals_;
+  std::vector<double> perturbation_ = {0, 0, 0};
+  std::vector<double> score_ = {0, 0, 0};
+  int index_, ref_id_, src_id_;
+  datapoint(const int index, const std::vector<double>& residuals, const std::vector<double>& perturbation,
+            const std::vector<double>& score, PoseScan_S& ref, PoseScan_S& src)
+      : residuals_(residuals), perturbation_(perturbation), score_(score), index_(index), ref_id_(ref->pose_id), src_id_(src->pose_id) {
+    const double dx = ref->T.x - src->T.x, dy = ref->T.y - src->T.y;
+    distance_ = std::sqrt(dx * dx + dy * dy);
+  }
+  // the column names of eval.txt; the fifth carries the reference's leading space
+  static std::vector<std::string> HeaderToString() {
+    static const char* const kColumns[11] = {"index", "ref_id", "src_id", "distance", " score1", "score2", "score3",
+                                             "aligned", "error x", "error y", "error theta"};
+    return std::vector<std::string>(kColumns, kColumns + 11);
+  }
+  // the row in the header's order: integers as %d, doubles as %f (std::to_string), aligned as 1 / 0
+  const std::vector<std::string> ValsToString() {
+    std::vector<std::string> row;
+    for (int v : {index_, ref_id_, src_id_}) row.push_back(std::to_string(v));
+    row.push_back(std::to_string(distance_));
+    for (int k = 0; k < 3; k++) row.push_back(std::to_string(score_[(size_t)k]));
+    row.push_back(aligned() ? "1" : "0");
+    for (int k = 0; k < 3; k++) row.push_back(std::to_string(perturbation_[(size_t)k]));
+    return row;
+  }
+  bool aligned() { return aligned(perturbation_); }
+  static bool aligned(const std::vector<double>& perturbation) {
+    double l1 = 0.0;
+    for (size_t k = 0; k < perturbation.size(); k++) l1 += std::fabs(perturbation[k]);
+    return l1 < 1e-4;
+  }
+};
+
+// comma-joined, no trailing comma (what Utils.h declares as Vec2String)
+inline const std::string Vec2String(const std::vector<std::string>& vec) {
+  std::string joined;
+  for (size_t k = 0; k < vec.size(); k++) {
+    if (k) joined += ',';
+    joined += vec[k];
+  }
+  return joined;
+}
+
+// scanEvaluator (ScanEvaluator.h:53-137 declares it) over a sequence held in memory: every pair (scan[k - 1], scan[k]),
+// k >= scan_spacing, at the aligned offset and at offset_rotation_steps misaligned ones.  quality_par.method: "P2P" or
+// "keypoint_repetability" (CorAlRadarQuality has its own class above).  One cfear_p2p_quality call per pair and offset;
+// api.scanEvaluator puts the whole sequence into one batched call.
+class scanEvaluator {
+ public:
+  class parameters {                                                           // the defaults of ScanEvaluator.h:58-113
+   public:
+    parameters() {}
+    int scan_spacing = 1;
+    double range_error = 0.5;
+    double theta_range = 2 * M_PI / 4.0;
+    int offset_rotation_steps = 2;
+    double theta_error = 0.57 * M_PI / 180.0;
+    std::string output_directory = "";
+    std::string output_eval_file = "eval.txt";
+  };
+  scanEvaluator(std::vector<PoseScan_S>& reader, const parameters& eval_par, const AlignmentQuality::parameters& alignment_par)
+      : scanEvaluator(CFEAR_Radarodometry::Context::Default(), reader, eval_par, alignment_par) {}
+  scanEvaluator(CFEAR_Radarodometry::Context& ctx, std::vector<PoseScan_S>& reader, const parameters& eval_par,
+                const AlignmentQuality::parameters& alignment_par)
+      : par_(eval_par), quality_par_(alignment_par) {
+    // what the reference asserts of its parameters, and the measures this mirror serves
+    if (!(par_.range_error > 0.0 && par_.theta_range >= -2.220446049250313e-16 && par_.theta_error >= 0.0 && par_.scan_spacing >= 1))
+      throw CFEAR_Radarodometry::CfearError(CFEAR_ERR_INVALID_ARGUMENT, "scanEvaluator: parameters out of range");
+    const bool p2p = quality_par_.method == "P2P";
+    if (!p2p && quality_par_.method != "keypoint_repetability")
+      throw CFEAR_Radarodometry::CfearError(CFEAR_ERR_INVALID_ARGUMENT, "scanEvaluator: method must be P2P or keypoint_repetability");
+    CreatePerturbations();
+    for (size_t k = (size_t)par_.scan_spacing; k < reader.size(); k++) {        // pair number k - scan_spacing + 1
+      PoseScan_S& ref = reader[k - 1];
+      PoseScan_S& src = reader[k];
+      for (const std::vector<double>& off : vek_perturbation_) {
+        const CFEAR_Radarodometry::Pose2d Toffset{off[0], off[1], off[2]};
+        std::unique_ptr<AlignmentQuality> q;
+        if (p2p) q.reset(new p2pQuality(ctx, ref, src, quality_par_, Toffset));
+        else q.reset(new keypointRepetability(ctx, ref, src, quality_par_, Toffset));
+        datapoints_.emplace_back((int)(k - (size_t)par_.scan_spacing) + 1, q->GetResiduals(), off, q->GetQualityMeasure(), ref, src);
+      }
+    }
+  }
+  // the aligned offset first, then `steps` offsets of length range_error at the angles i / steps * theta_range, each with
+  // the rotation theta_error
+  void CreatePerturbations() {
+    const int steps = par_.offset_rotation_steps;
+    vek_perturbation_.assign(1, std::vector<double>(3, 0.0));
+    for (int i = 0; i < steps; i++) {
+      const double angle = (double)i / (double)steps * par_.theta_range;
+      vek_perturbation_.push_back({par_.range_error * std::cos(angle), par_.range_error * std::sin(angle), par_.theta_error});
+    }
+  }
+  void SaveEvaluation() { SaveEvaluation(par_.output_directory + "/" + par_.output_eval_file); }
+  void SaveEvaluation(const std::string& path) {                               // header line, then one line per datapoint
+    std::ofstream out(path);
+    out << Vec2String(datapoint::HeaderToString()) << "\n";
+    for (datapoint& d : datapoints_) out << Vec2String(d.ValsToString()) << "\n";
+  }
+  std::vector<std::vector<double>> vek_perturbation_;
+  std::vector<datapoint> datapoints_;
+
+ private:
+  const parameters par_;
+  const AlignmentQuality::parameters quality_par_;
+};
+
 // PythonClassifierInterface + LogisticRegression (alignmentinterface.h:32-119, alignmentinterface.cpp:14-279) without the
 // embedded interpreter: fit() minimises the objective of sklearn's LogisticRegression(class_weight="balanced") on the GPU
 // (cfear_logreg_fit_batch).  Eigen::MatrixXd X_ becomes row-major doubles with cols_ values a row.  Where the reference

@@ -125,6 +125,17 @@ CORAL_RESULT_DTYPE = np.dtype([("joint", "<f8"), ("sep", "<f8"), ("overlap", "<f
                                ("count_valid", "<i4"), ("status", "<i4"), ("pad", "<i4")])
 
 
+class P2pJob(C.Structure):        # cfear_p2p_job
+    _fields_ = [("ref_xyzi", C.c_void_p), ("src_xyzi", C.c_void_p), ("n_ref", C.c_int32), ("n_src", C.c_int32),
+                ("T", C.c_double * 6)]
+
+
+P2P_RESULT_DTYPE = np.dtype([("mean", "<f8"), ("sum", "<f8"), ("matched", "<i4"), ("n_src", "<i4"), ("status", "<i4"),
+                             ("pad", "<i4")])
+assert C.sizeof(P2pJob) == 72 and P2P_RESULT_DTYPE.itemsize == 32
+P2P_MAX_REF_POINTS, P2P_MAX_SRC_POINTS = 16384, 1048576
+
+
 class ScParams(C.Structure):
     _fields_ = [("num_ring", C.c_int32), ("num_sector", C.c_int32), ("max_radius", C.c_double),
                 ("search_ratio", C.c_double), ("desc_function", C.c_int32), ("pad", C.c_int32),
@@ -240,7 +251,7 @@ EXPORTS = [
     "cfear_candidate_pipe_create", "cfear_candidate_pipe_submit", "cfear_candidate_pipe_collect", "cfear_candidate_pipe_destroy", "cfear_candidate_pipe_stats",
     "cfear_eval_params_default", "cfear_eval_trajectories", "cfear_eval_check", "cfear_kitti_read", "cfear_kitti_write",
     "cfear_kitti_from_xyt", "cfear_cen2018_params_default", "cfear_filter_cen2018",
-    "cfear_logreg_params_default", "cfear_logreg_fit_batch",
+    "cfear_logreg_params_default", "cfear_logreg_fit_batch", "cfear_p2p_quality", "cfear_p2p_quality_batch",
 ]
 
 PIPE_GRAPH, PIPE_TIMING = 1, 2      # enum { CFEAR_PIPE_GRAPH, CFEAR_PIPE_TIMING }
@@ -405,6 +416,8 @@ def lib():
     L.cfear_coral_params_default.restype = None
     L.cfear_coral_quality.argtypes = [vp, C.POINTER(CoralJob), C.POINTER(CoralParams), vp, vp]
     L.cfear_coral_quality_batch.argtypes = [vp, C.POINTER(CoralJob), C.c_int32, C.POINTER(CoralParams), vp, vp]
+    L.cfear_p2p_quality.argtypes = [vp, C.POINTER(P2pJob), C.c_double, vp, vp]
+    L.cfear_p2p_quality_batch.argtypes = [vp, C.POINTER(P2pJob), C.c_int32, C.c_double, vp, vp]
     L.cfear_sc_params_default.argtypes = [C.POINTER(ScParams)]
     L.cfear_sc_params_default.restype = None
     L.cfear_sc_descriptors.argtypes = [vp, C.POINTER(ScCloud), C.c_int32, C.POINTER(ScParams), C.POINTER(C.c_double),

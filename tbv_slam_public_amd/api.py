@@ -11,6 +11,7 @@ with ROS / PCL / Eigen types replaced by NumPy arrays (host) or torch CUDA tenso
 Everything computes in libcfear_hip.so on the GPU; there is no CPU path in this package.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -795,9 +796,13 @@ class CorAlRadarQuality:
         self.count_valid = int(r["count_valid"])
         self.path = int(r["pad"])                     # CFEAR_CORAL_PATH_* (diagnostic)
         self.per_point = pp[0] if want_per_point else None
+        self.residuals_ = [0.0, 0.0, 0.0]                    # the base constructor's; CorAlRadarQuality adds none
 
     def GetQualityMeasure(self):
         return list(self.quality_)
+
+    def GetResiduals(self):
+        return list(self.residuals_)
 
 
 def _compose_xyt(a, b):
@@ -848,6 +853,300 @@ def coral_quality_batch(jobs, radius=1.0, weight_res_intensity=False, want_per_p
         return out, None
     offs = np.cumsum([0] + sizes)
     return out, [pp[offs[i]:offs[i + 1]] for i in range(n)]
+
+
+# ------------------------------------------------------------------------------------------------
+# P2P quality, keypoint repeatability, the quality factory and evaluate_scans (coral_alignment_quality)
+# ------------------------------------------------------------------------------------------------
+def _aff(p):
+    c, s = math.cos(float(p[2])), math.sin(float(p[2]))
+    return (c, -s, s, c, float(p[0]), float(p[1]))
+
+
+def _aff_mul(a, b):
+    return (a[0] * b[0] + a[1] * b[2], a[0] * b[1] + a[1] * b[3], a[2] * b[0] + a[3] * b[2], a[2] * b[1] + a[3] * b[3],
+            a[0] * b[4] + a[1] * b[5] + a[4], a[2] * b[4] + a[3] * b[5] + a[5])
+
+
+def p2p_tchange(ref_pose, src_pose, Toffset=(0.0, 0.0, 0.0)):
+    """Tchange = Tref.inverse() * Tsrc * Toffset (AlignmentQuality.cpp:260-264) of planar poses (x, y, theta) as the
+    row-major 2x3 float64 [6] a cfear_p2p_job carries.  The inverse is (R^T, -R^T t); every product is a plain fp64
+    multiply and add, left to right -- include/cfear_hip.hpp composes with the same formula."""
+    return np.array(_tchange(ref_pose, src_pose, Toffset), np.float64)
+
+
+def _tchange(ref_pose, src_pose, Toffset):
+    l0, l1, l2, l3, t0, t1 = _aff(ref_pose)
+    inv = (l0, l2, l1, l3, -(l0 * t0 + l2 * t1), -(l1 * t0 + l3 * t1))
+    m = _aff_mul(_aff_mul(inv, _aff(src_pose)), _aff(Toffset))
+    return (m[0], m[1], m[4], m[2], m[3], m[5])
+
+
+def p2p_quality_batch(jobs, radius=3.0, want_per_point=False, ctx=None, device_out=False):
+    """cfear_p2p_quality_batch: one launch; jobs that share a reference cloud share its sort.  jobs: list of (ref_cloud,
+    ref_pose, src_cloud, src_pose, Toffset), or of (ref_cloud, src_cloud, T) with T the composed float64 [6].  Clouds:
+    float32 [n, 4], NumPy or torch CUDA (used in place).
+    -> (P2P_RESULT_DTYPE array, list of float32 [n_src] rows or None); with device_out torch CUDA tensors instead (uint8
+    [n, 32] records to view on the host, one flat float32 tensor) and nothing is synchronised when the clouds are on the
+    device too."""
+    ctx = ctx or default_context()
+    n = len(jobs)
+    arr = (L.P2pJob * max(n, 1))()
+    keep, sizes = [], []
+    for i, job in enumerate(jobs):
+        if len(job) == 3:
+            rc, sc, T = job
+            T = np.asarray(T, np.float64).reshape(6)
+        else:
+            rc, rp, sc, sp, off = job
+            T = _tchange(rp, sp, off)
+        pr, nr, kr = _cloud_ptr(rc)
+        ps, ns, ks = _cloud_ptr(sc)
+        keep += [kr, ks]
+        arr[i].ref_xyzi, arr[i].src_xyzi, arr[i].n_ref, arr[i].n_src = pr, ps, nr, ns
+        arr[i].T[:] = [float(v) for v in T]
+        sizes.append(ns)
+    total = int(sum(sizes))
+    if device_out:
+        import torch
+        out = torch.zeros((n, L.P2P_RESULT_DTYPE.itemsize), dtype=torch.uint8, device="cuda")
+        pp = torch.zeros(max(total, 1), dtype=torch.float32, device="cuda") if want_per_point else None
+    else:
+        out = np.zeros(n, L.P2P_RESULT_DTYPE)
+        pp = np.zeros(max(total, 1), np.float32) if want_per_point else None
+    if n:
+        ctx.check(ctx._lib.cfear_p2p_quality_batch(ctx.h, arr, n, float(radius), _ptr(out)[0], _ptr(pp)[0]))
+    if not want_per_point:
+        return out, None
+    if device_out:
+        return out, pp[:total]
+    offs = np.cumsum([0] + sizes)
+    return out, [pp[offs[i]:offs[i + 1]] for i in range(n)]
+
+
+class AlignmentQualityParameters:
+    """AlignmentQuality::parameters (AlignmentQuality.h:53-86)."""
+
+    def __init__(self, method="P2L", radius=3.0, ent_cfg="any", weight_res_intensity=False, output_overlap=True, visualize=False):
+        self.method, self.radius, self.ent_cfg = method, float(radius), ent_cfg
+        self.weight_res_intensity, self.output_overlap, self.visualize = weight_res_intensity, output_overlap, visualize
+
+
+def _scan_cloud(scan):
+    return scan["cloud"] if "cloud" in scan else scan["cldPeaks"]
+
+
+class p2pQuality:
+    """p2pQuality(ref, src, par, Toffset) (AlignmentQuality.cpp:235-290).  A scan is a dict {"T": (x, y, theta), "cloud":
+    float32 [n, 4] (NumPy or torch CUDA)[, "type", "pose_id", "CFEAR"]}.  residuals_ keeps the base constructor's three
+    leading zeros (AlignmentQuality.h:92), so quality_[0] = sum / (matched + 3)."""
+
+    def __init__(self, ref, src, par=None, Toffset=(0.0, 0.0, 0.0), ctx=None, _record=None):
+        self.par_ = par or AlignmentQualityParameters(method="P2P")
+        if _record is None:
+            out, pp = p2p_quality_batch([(_scan_cloud(ref), ref["T"], _scan_cloud(src), src["T"], Toffset)], self.par_.radius, True, ctx)
+            _record = (out[0], pp[0])
+        r, pp = _record
+        self.record = r
+        self.residuals_ = [0.0, 0.0, 0.0] + [float(v) for v in pp[pp >= 0]]
+        self.quality_ = [float(r["mean"]), 0.0, 0.0]
+        self.valid_ = False                                   # never set by the reference
+
+    def GetResiduals(self):
+        return list(self.residuals_)
+
+    def GetQualityMeasure(self):
+        return list(self.quality_)
+
+
+class keypointRepetability:
+    """keypointRepetability(ref, src, par, Toffset) (AlignmentQuality.cpp:293-328): quality_ = {matched / n_src, matched,
+    n_src}; NaN for an empty source cloud, as 0.0 / 0.0 is there."""
+
+    def __init__(self, ref, src, par=None, Toffset=(0.0, 0.0, 0.0), ctx=None, _record=None):
+        self.par_ = par or AlignmentQualityParameters(method="keypoint_repetability")
+        if _record is None:
+            out, _ = p2p_quality_batch([(_scan_cloud(ref), ref["T"], _scan_cloud(src), src["T"], Toffset)], self.par_.radius, False, ctx)
+            _record = (out[0], None)
+        r = _record[0]
+        self.record = r
+        self.residuals_ = [0.0, 0.0, 0.0]
+        self.quality_ = _repeatability(r)
+        self.valid_ = False
+
+    def GetResiduals(self):
+        return list(self.residuals_)
+
+    def GetQualityMeasure(self):
+        return list(self.quality_)
+
+
+def _repeatability(r):
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return [float(np.float64(r["matched"]) / np.float64(r["n_src"])), float(r["matched"]), float(r["n_src"])]
+
+
+class CFEARQuality:
+    """CFEARQuality(ref, src, par, Toffset) (AlignmentQuality.cpp:330-354) over scans that carry "CFEAR": MapPointNormal."""
+
+    def __init__(self, ref, src, par, Toffset=(0.0, 0.0, 0.0), ctx=None):
+        if par.method not in L.COST:
+            raise ValueError("CFEARQuality: unknown cost %r" % (par.method,))
+        self.par_ = par
+        self.quality_ = [float(v) for v in cfear_quality_batch([(ref["CFEAR"], ref["T"], src["CFEAR"], src["T"], Toffset)], par.method, ctx)[0]]
+        self.residuals_ = [0.0, 0.0, 0.0]                      # the matcher's residual vector is not returned by the batched call
+        self.valid_ = True
+
+    def GetResiduals(self):
+        return list(self.residuals_)
+
+    def GetQualityMeasure(self):
+        return list(self.quality_)
+
+
+_CFEAR_TYPE, _P2P_TYPES, _CORAL_TYPES = "CFEARFeatures", ("BFARScan", "RawLidar", "kstrongStructuredRadar", "Cen2018Radar"), \
+    ("kstrongRadar", "kstrongStructuredRadar")
+
+
+def _quality_kind(scan_type, method):
+    """The measure AlignmentQualityFactory::CreateQualityType (AlignmentQuality.h:260-312) builds for a scan type and
+    pars.method: "CFEAR", "P2P", "keypoint_repetability" or "Coral"; raises where the reference prints "no quality metric
+    for scan typee" and exits, and for the measures that are not built here."""
+    if scan_type == _CFEAR_TYPE:
+        if method not in L.COST:
+            raise ValueError("CFEARFeatures: unknown cost %r" % (method,))
+        return "CFEAR"
+    if method == "P2P" and scan_type in _P2P_TYPES:
+        return "P2P"
+    if method == "keypoint_repetability" and scan_type == "BFARScan":
+        return "keypoint_repetability"
+    if method == "Coral" and scan_type in _CORAL_TYPES:
+        return "Coral"
+    if (scan_type == "RawLidar" and method in ("Coral", "P2D")) or scan_type == "CartesianRadar":
+        raise NotImplementedError("%s / %s: CorAl (lidar), p2dQuality and CorAlCartQuality are not built" % (scan_type, method))
+    raise ValueError("no quality metric for scan type %r with method %r" % (scan_type, method))
+
+
+def _scan_type(ref, src):
+    tr, ts = ref.get("type"), src.get("type")
+    if tr is None or tr != ts:
+        raise ValueError("no quality metric for scan types %r / %r" % (tr, ts))
+    return tr
+
+
+class AlignmentQualityFactory:
+    """AlignmentQualityFactory (AlignmentQuality.h:260-312): dispatch on the scans' "type" tag (the reference's PoseScan
+    subclass name) and pars.method."""
+
+    @staticmethod
+    def CreateQualityType(ref, src, pars, Toffset=(0.0, 0.0, 0.0), ctx=None):
+        kind = _quality_kind(_scan_type(ref, src), pars.method)
+        if kind == "CFEAR":
+            return CFEARQuality(ref, src, pars, Toffset, ctx)
+        if kind == "P2P":
+            return p2pQuality(ref, src, pars, Toffset, ctx)
+        if kind == "keypoint_repetability":
+            return keypointRepetability(ref, src, pars, Toffset, ctx)
+        if pars.ent_cfg not in ("any", 0):
+            raise NotImplementedError("CorAlRadarQuality: only ent_cfg = any is built")
+        return CorAlRadarQuality(_scan_cloud(ref), ref["T"], _scan_cloud(src), src["T"], Toffset, pars.radius,
+                                 pars.weight_res_intensity, False, ctx)
+
+
+class scanEvaluatorParameters:
+    """scanEvaluator::parameters (ScanEvaluator.h:58-113), the fields that reach the scores and eval.txt."""
+
+    def __init__(self, scan_spacing=1, range_error=0.5, theta_range=2 * math.pi / 4.0, offset_rotation_steps=2,
+                 theta_error=0.57 * math.pi / 180.0, output_directory="", output_eval_file="eval.txt"):
+        self.scan_spacing, self.range_error, self.theta_range = int(scan_spacing), float(range_error), float(theta_range)
+        self.offset_rotation_steps, self.theta_error = int(offset_rotation_steps), float(theta_error)
+        self.output_directory, self.output_eval_file = output_directory, output_eval_file
+
+
+class scanEvaluator:
+    """scanEvaluator (ScanEvaluator.cpp:4-114), the body of evaluate_scans: every pair (scan[k - 1], scan[k]), k >=
+    scan_spacing, is scored at the aligned offset and at offset_rotation_steps misaligned ones.  All (N - scan_spacing) x
+    (steps + 1) jobs go through ONE batched call of the measure the factory picks for the scans' type and quality_par.method
+    (p2p_quality_batch, coral_quality_batch or cfear_quality_batch); there is no loop over pairs.
+    datapoints_: dicts(index, ref_id, src_id, distance, score, aligned, perturbation, residuals)."""
+
+    HEADER = ["index", "ref_id", "src_id", "distance", " score1", "score2", "score3", "aligned", "error x", "error y", "error theta"]
+
+    def __init__(self, scans, eval_par=None, quality_par=None, ctx=None):
+        self.par_ = eval_par or scanEvaluatorParameters()
+        self.quality_par_ = quality_par or AlignmentQualityParameters()
+        p = self.par_
+        if not (p.range_error > 0.0 and p.theta_range >= -2.220446049250313e-16 and p.theta_error >= 0.0 and p.scan_spacing >= 1):
+            raise ValueError("scanEvaluator: InputSanityCheck")         # ScanEvaluator.cpp:47-56
+        self.vek_perturbation_ = []
+        self.CreatePerturbations()
+        self.datapoints_ = []
+        pairs = [(k, scans[k - 1], scans[k]) for k in range(p.scan_spacing, len(scans))]
+        if not pairs:
+            return
+        kind = _quality_kind(_scan_type(pairs[0][1], pairs[0][2]), self.quality_par_.method)
+        for _k, r, s in pairs:
+            if _scan_type(r, s) != pairs[0][1]["type"]:
+                raise ValueError("scanEvaluator: scans of different types")
+        vek, q = self.vek_perturbation_, self.quality_par_
+        nres = [[0.0, 0.0, 0.0]] * (len(pairs) * len(vek))
+        if kind in ("P2P", "keypoint_repetability"):
+            want_pp = kind == "P2P"
+            out, pp = p2p_quality_batch([(_scan_cloud(r), r["T"], _scan_cloud(s), s["T"], o) for _k, r, s in pairs for o in vek],
+                                        q.radius, want_pp, ctx)
+            if want_pp:
+                scores = [[float(v["mean"]), 0.0, 0.0] for v in out]
+                nres = [[0.0, 0.0, 0.0] + [float(x) for x in row[row >= 0]] for row in pp]
+            else:
+                scores = [_repeatability(v) for v in out]
+        elif kind == "Coral":
+            if q.ent_cfg not in ("any", 0):
+                raise NotImplementedError("CorAlRadarQuality: only ent_cfg = any is built")
+            out, _ = coral_quality_batch([(_scan_cloud(r), r["T"], _scan_cloud(s), s["T"], o) for _k, r, s in pairs for o in vek],
+                                         q.radius, q.weight_res_intensity, False, ctx)
+            scores = [[float(v["joint"]), float(v["sep"]), float(v["overlap"])] for v in out]
+        else:
+            X = cfear_quality_batch([(r["CFEAR"], r["T"], s["CFEAR"], s["T"], o) for _k, r, s in pairs for o in vek], q.method, ctx)
+            scores = [[float(x) for x in row] for row in X]
+        i = 0
+        for index, (k, r, s) in enumerate(pairs, 1):
+            dx, dy = float(r["T"][0]) - float(s["T"][0]), float(r["T"][1]) - float(s["T"][1])
+            for verr in vek:
+                self.datapoints_.append(dict(index=index, ref_id=int(r.get("pose_id", k - 1)), src_id=int(s.get("pose_id", k)),
+                                             distance=math.sqrt(dx * dx + dy * dy), score=scores[i], aligned=self.aligned(verr),
+                                             perturbation=list(verr), residuals=nres[i]))
+                i += 1
+
+    @staticmethod
+    def aligned(perturbation):                                           # datapoint::aligned (:4-10)
+        total = 0.0
+        for e in perturbation:
+            total += abs(e)
+        return total < 0.0001
+
+    def CreatePerturbations(self):                                       # :11-25
+        p = self.par_
+        steps = p.offset_rotation_steps
+        angles = [float(i) / float(steps) * p.theta_range for i in range(steps)]
+        self.vek_perturbation_ += [[0.0, 0.0, 0.0]] + [[p.range_error * math.cos(a), p.range_error * math.sin(a), p.theta_error]
+                                                       for a in angles]
+
+    @staticmethod
+    def ValsToString(d):                                                 # datapoint::ValsToString: std::to_string
+        return ["%d" % d["index"], "%d" % d["ref_id"], "%d" % d["src_id"], "%f" % d["distance"], "%f" % d["score"][0],
+                "%f" % d["score"][1], "%f" % d["score"][2], "%d" % int(d["aligned"]), "%f" % d["perturbation"][0],
+                "%f" % d["perturbation"][1], "%f" % d["perturbation"][2]]
+
+    def EvaluationText(self):
+        """eval.txt: datapoint::HeaderToString(), then one row per datapoint, joined by Vec2String (Utils.cpp:596-604)."""
+        return "".join(",".join(v) + "\n" for v in [self.HEADER] + [self.ValsToString(d) for d in self.datapoints_])
+
+    def SaveEvaluation(self, path=None):                                 # :26-46
+        assert self.datapoints_
+        path = path or os.path.join(self.par_.output_directory, self.par_.output_eval_file)
+        with open(path, "w") as f:
+            f.write(self.EvaluationText())
+        return path
 
 
 # ------------------------------------------------------------------------------------------------

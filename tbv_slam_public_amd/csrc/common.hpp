@@ -46,6 +46,8 @@ enum WsSlot : int {
   kWsEval = 16,           // trajectory evaluation: staged and normalised poses, distances, tables, staged outputs
   kWsPgo = 17,            // batched pose-graph optimisation: one chunk's poses, tables and solver state
   kWsLogreg = 18,         // classifier fits: staged rows, labels and masks, job records, results
+  kWsP2p = 19,            // p2p quality: group and job records, staged results and per-point minima
+  kWsP2pScratch = 20,     // p2p quality: sorted reference clouds that do not fit the LDS
 };
 
 struct cfear_ctx {
@@ -58,7 +60,7 @@ struct cfear_ctx {
   std::vector<hipEvent_t> event_pool;
   // grow-only device workspaces (indexed by WsSlot so stages of one pipeline do not alias)
   struct Ws { void* p = nullptr; size_t bytes = 0; };
-  Ws ws[19];
+  Ws ws[21];
   // pinned host staging for small read-backs
   void* pinned = nullptr;
   size_t pinned_bytes = 0;
