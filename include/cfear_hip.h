@@ -286,6 +286,36 @@ int cfear_scan_get_cells(const cfear_scan* scan, cfear_cell* out_host, int32_t c
  * the cell whose float mean is nearest to float(p) (FLANN L2_Simple in float, lowest index on ties) if that squared
  * distance is < d * d, else -1 (the reference returns an empty vector).  queries_xy / idx both host or both device. */
 int cfear_scan_closest_idx(const cfear_scan* scan, const double* queries_xy, int32_t n_queries, double d, int32_t* idx);
+/* Diagnostic: the route the surface-point kernels served this scan on (CFEAR_SURF_PATH_*), 0 for a scan that did not come
+ * from them (cfear_scan_from_cells).  The thresholds between the routes are LDS arithmetic inside the kernels; the word
+ * lets a test assert where its input ran.  A scan handed out by cfear_odometry_get_scan carries the word of the stream's
+ * last frame.                                                                                                        */
+int cfear_scan_surface_path(const cfear_scan* scan, uint32_t* path);
+#define CFEAR_SURF_PATH_KIND_MASK 3u         /* which kernels made the cells:                                          */
+#define CFEAR_SURF_PATH_FAST 1u              /*   the fast pipeline (prep, sort, finish)                               */
+#define CFEAR_SURF_PATH_SINGLE 2u            /*   the single-kernel path with its LDS sort (a hand-over)               */
+#define CFEAR_SURF_PATH_GLOBAL 3u            /*   the global-memory path (more than 16 384 points off the fast path)   */
+#define CFEAR_SURF_PATH_ROWS 0x4u            /* rows mode: the cloud arrived as per-row key lists                      */
+#define CFEAR_SURF_PATH_K64 0x8u             /* fast: 64 points per thread (more than 16 384 points), else 32          */
+#define CFEAR_SURF_PATH_WFLOAT 0x10u         /* fast: float weights, else one byte per weight                          */
+#define CFEAR_SURF_PATH_SLABS 0x20u          /* fast: several slabs (their number is in the SLAB_COUNT field)          */
+#define CFEAR_SURF_PATH_READ2 0x40u          /* fast: grid beyond 65 536 cells, the points were read a second time     */
+#define CFEAR_SURF_PATH_TIER16 0x80u         /* fast: some slab held voxels of the 16-lane tier (C > 64 candidates)    */
+#define CFEAR_SURF_PATH_TIER4 0x100u         /*   ... of the 4-lane tier (16 < C <= 64)                                */
+#define CFEAR_SURF_PATH_TIER1 0x200u         /*   ... of the 1-lane tier (6 <= C <= 16)                                */
+#define CFEAR_SURF_PATH_TOP_BUCKET 0x400u    /* fast: a voxel with more than 4 096 candidates (saturated top bucket)   */
+#define CFEAR_SURF_PATH_CEN_SCRATCH 0x800u   /* fast: a split voxel's centroid went through scratch (LDS list full)    */
+#define CFEAR_SURF_PATH_PREPARED 0x1000u     /* hand-over: the cloud arrived compact and compensated                   */
+#define CFEAR_SURF_PATH_REASON_SHIFT 13      /* hand-over: why the fast pipeline did not take the scan                 */
+#define CFEAR_SURF_PATH_REASON_MASK 0xE000u
+#define CFEAR_SURF_REASON_REACH 1u           /*   downsample factor != 1 (more than one voxel per radius)              */
+#define CFEAR_SURF_REASON_ROTATION 2u        /*   compensation by more than 1e5 rad (or NaN)                           */
+#define CFEAR_SURF_REASON_POINTS 3u          /*   more than 32 768 points                                              */
+#define CFEAR_SURF_REASON_CELLS 4u           /*   grid beyond 2^18 cells                                               */
+#define CFEAR_SURF_REASON_ORDER 5u           /*   occupancy, voxel cursors and order array exceed the LDS budget       */
+#define CFEAR_SURF_REASON_ROWS3 6u           /*   three grid rows exceed the staging area                              */
+#define CFEAR_SURF_PATH_SLAB_COUNT_SHIFT 16  /* fast: slabs, saturating at 255                                         */
+#define CFEAR_SURF_PATH_SLAB_COUNT_MASK 0xFF0000u
 int cfear_scan_destroy(cfear_scan* scan);
 
 /* ---- M: registration -----------------------------------------------------------------------

@@ -364,6 +364,8 @@ class MapPointNormal {
     ctx_.check(cfear_scan_closest_idx(scan_, q, 1, d, &idx));
     return idx >= 0 ? std::vector<int>{idx} : std::vector<int>{};
   }
+  // the route the surface-point kernels served this scan on (CFEAR_SURF_PATH_*; 0 for a scan made from cells): diagnostic
+  uint32_t SurfacePath() const { uint32_t p = 0; ctx_.check(cfear_scan_surface_path(scan_, &p)); return p; }
   const cfear_scan* device() const { return scan_; }
  private:
   const std::vector<cfear_cell>& cached() { if (cache_.empty()) cache_ = GetCells(); return cache_; }

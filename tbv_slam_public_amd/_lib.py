@@ -21,6 +21,14 @@ P2P, P2L, P2D = 0, 1, 2
 LOSS = {"None": 0, "Huber": 1, "Cauchy": 2, "SoftLOne": 3, "Combined": 4, "Tukey": 5}
 COST = {"P2P": 0, "P2L": 1, "P2D": 2}
 
+# CFEAR_SURF_PATH_*: the route word of the surface-point kernels (cfear_scan_surface_path)
+SURF_PATH_KIND_MASK, SURF_PATH_FAST, SURF_PATH_SINGLE, SURF_PATH_GLOBAL = 3, 1, 2, 3
+SURF_PATH_ROWS, SURF_PATH_K64, SURF_PATH_WFLOAT, SURF_PATH_SLABS, SURF_PATH_READ2 = 0x4, 0x8, 0x10, 0x20, 0x40
+SURF_PATH_TIER16, SURF_PATH_TIER4, SURF_PATH_TIER1, SURF_PATH_TOP_BUCKET, SURF_PATH_CEN_SCRATCH = 0x80, 0x100, 0x200, 0x400, 0x800
+SURF_PATH_PREPARED, SURF_PATH_REASON_SHIFT, SURF_PATH_REASON_MASK = 0x1000, 13, 0xE000
+SURF_REASON_REACH, SURF_REASON_ROTATION, SURF_REASON_POINTS, SURF_REASON_CELLS, SURF_REASON_ORDER, SURF_REASON_ROWS3 = 1, 2, 3, 4, 5, 6
+SURF_PATH_SLAB_COUNT_SHIFT, SURF_PATH_SLAB_COUNT_MASK = 16, 0xFF0000
+
 
 class CfearError(RuntimeError):
     def __init__(self, status, msg=""):
@@ -229,7 +237,7 @@ EXPORTS = [
     "cfear_get_cost_batch", "cfear_cov_sampling_params_default", "cfear_covariance_by_sampling",
     "cfear_covariance_by_sampling_batch", "cfear_coral_params_default", "cfear_coral_quality",
     "cfear_coral_quality_batch", "cfear_sc_params_default", "cfear_sc_descriptors", "cfear_sc_distance_batch",
-    "cfear_polar_rotate_ccw", "cfear_scan_closest_idx",
+    "cfear_polar_rotate_ccw", "cfear_scan_closest_idx", "cfear_scan_surface_path",
     "cfear_sc_manager_params_default", "cfear_sc_manager_create", "cfear_sc_manager_add", "cfear_sc_manager_detect",
     "cfear_sc_manager_size", "cfear_sc_manager_destroy", "cfear_sc_raw_params_default", "cfear_sc_raw_descriptors",
     "cfear_sc_manager_add_raw", "cfear_sc_local_map_descriptors", "cfear_sc_detect_sequence",
@@ -439,6 +447,7 @@ def lib():
     L.cfear_sc_manager_size.argtypes = [vp]
     L.cfear_sc_manager_destroy.argtypes = [vp]
     L.cfear_scan_closest_idx.argtypes = [vp, vp, C.c_int32, C.c_double, vp]
+    L.cfear_scan_surface_path.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.cfear_polar_rotate_ccw.argtypes = [vp, vp, C.POINTER(PolarDesc), vp, C.c_int32, C.c_int64]
     L.cfear_verify_params_default.argtypes = [C.POINTER(VerifyParams)]
     L.cfear_verify_params_default.restype = None

@@ -406,6 +406,13 @@ class MapPointNormal:
     def GetSize(self):
         return self.ctx._lib.cfear_scan_size(self._h)
 
+    @property
+    def path(self):
+        """The route the surface-point kernels served this scan on (L.SURF_PATH_*; 0 for a map made from cells)."""
+        p = C.c_uint32()
+        self.ctx.check(self.ctx._lib.cfear_scan_surface_path(self._h, C.byref(p)))
+        return int(p.value)
+
     def GetClosestIdx(self, p, d):
         """GetClosestIdx(p, d) (pointnormal.cpp:238-254): [index of the nearest cell mean] or [] beyond d.
         p may also be an array [n, 2] of points (NumPy or torch CUDA float64): -> int32 [n], -1 where none."""

@@ -235,6 +235,7 @@ struct cfear_scan {
   void* slab;
   ScanView view;
   int32_t n_cells_host;    // -1 until read back
+  uint32_t surf_path = 0;  // CFEAR_SURF_PATH_* of the surface-point launch that made the cells (0: none did)
   int32_t refs = 1;        // the caller's handle + one per scan table that names it (handles are used from one host thread)
 };
 void cfear_scan_retain(cfear_scan* scan);   // cfear_scan_destroy drops one reference; the slab is recycled with the last
@@ -304,7 +305,9 @@ int cfear_trig_tables(cfear_ctx* ctx, int rows, double** d_cos, double** d_sin);
 // max_cell_cap: the largest cell capacity (ScanView::cap) among the jobs' output slabs
 int cfear_surface_launch(cfear_ctx* ctx, const void* d_jobs, int n_jobs, const cfear_feature_params* par,
                          char* d_scratch, int32_t* d_status, int32_t* d_ncells_out, int max_cell_cap, int cap_points,
-                         const cfear_surface_polar* polar = nullptr);
+                         const cfear_surface_polar* polar = nullptr, uint32_t* d_path_out = nullptr);
+// the route word (CFEAR_SURF_PATH_*) of job `job` of the last launch over d_scratch, read from its scratch header (waits for the stream)
+int cfear_surface_read_path(cfear_ctx* ctx, const char* d_scratch, int cap_points, int job, uint32_t* path);
 size_t cfear_reg_job_bytes();
 int cfear_reg_max_scans();
 void cfear_reg_fill_job(void* dst, const ScanView* views, int n_scans, const double* poses_xyt);

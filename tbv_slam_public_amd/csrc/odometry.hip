@@ -909,7 +909,14 @@ extern "C" int cfear_odometry_get_scan(cfear_odometry* od, int32_t stream, cfear
   if (od->last_slab[stream] < 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "stream %d: no frame processed yet", stream);
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const ScanView& v = od->views[(size_t)stream * od->slabs_per_stream + od->last_slab[stream]];
-  return cfear_scan_clone_view(ctx, v, od->h_ncells[stream], out);
+  const int rc = cfear_scan_clone_view(ctx, v, od->h_ncells[stream], out);
+  if (rc != CFEAR_OK) return rc;
+  // the route word of the stream's last frame: its scratch header stays as the kernels left it until the next process()
+  uint32_t path = 0;
+  const int rc_path = cfear_surface_read_path(ctx, od->d_surf_scratch, od->cap_points, stream, &path);
+  if (rc_path != CFEAR_OK) { cfear_scan_destroy(*out); *out = nullptr; return rc_path; }
+  (*out)->surf_path = path;
+  return CFEAR_OK;
 }
 
 static int copy_cloud_out(cfear_odometry* od, const float* d_src, int n, float* xyzi, int32_t cap, int32_t* n_out) {

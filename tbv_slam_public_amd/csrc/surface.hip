@@ -68,6 +68,7 @@ struct SurfCommon {
   size_t scratch_stride;
   int32_t* status;                            // [n_jobs] CFEAR_OK / error
   int32_t* ncells_out;                        // [n_jobs] dense copy of the cell counts (nullable)
+  uint32_t* path_out;                         // [n_jobs] dense copy of SurfHdr::path (nullable), stored with the status
   const double* cos_t;                        // rows mode: [rows] azimuth tables (host-computed doubles) and range_res
   const double* sin_t;
   double range_res, range_off;                // rho = range_off + range_res * bin
@@ -108,7 +109,9 @@ constexpr int kScanCreateMaxPoints = 1 << 20;  // cfear_scan_create: clouds beyo
 struct SurfHdr {                              // written by surface_sort_kernel, read by the kernels behind it
   int32_t route;                              // kRouteFast: sorted, cells pending | kRouteFallback | kRouteDone (finished / failed)
   int32_t n, V, dbx, dby, pad[3];
+  uint32_t path;                              // CFEAR_SURF_PATH_*: the route that served the scan (diagnostic; cfear_scan_surface_path)
 };
+__host__ __device__ inline uint32_t surf_reason(uint32_t r) { return r << CFEAR_SURF_PATH_REASON_SHIFT; }
 
 // cap = the largest point count a scan of this launch may have (>= kMaxPoints); clouds beyond kMaxPoints take the
 // big-cloud path, which also keeps its 64-bit sort keys here (2 x next_pow2 entries).
@@ -490,6 +493,7 @@ __device__ void surface_big_tail(const SurfJob& job, const SurfCommon& cm, const
   if (tid == 0) {
     scr.hdr->route = kRouteFast;                        // moments computed; cells + compaction + x-sort pending
     scr.hdr->n = n; scr.hdr->V = V; scr.hdr->dbx = dbx; scr.hdr->dby = dby;
+    scr.hdr->path = scr.hdr->path | CFEAR_SURF_PATH_GLOBAL;   // (the hand-over wrote SINGLE, reason, prepared and rows)
   }
 }
 
@@ -502,8 +506,10 @@ __device__ void surface_points_job(const SurfJob* __restrict__ jobs, const SurfC
   int* sh_misc = (int*)(smem + kLdsSmallOff + 256 + 64);              // [8]
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   SurfJob job = jobs[job_id];
+  uint32_t path = CFEAR_SURF_PATH_SINGLE;
   if (cm.fallback) {                                                  // handed over by surface_sort_kernel
     const SurfHdr h = *scratch_of(cm.scratch + (size_t)job_id * cm.scratch_stride, cm.scratch_cap).hdr;
+    path = h.path;
     if (h.pad[0]) {                                                   // xyzi already holds the compact, compensated cloud
       job.row_pts = nullptr; job.n_ptr = nullptr; job.n_host = h.n; job.compensate = 0;
     }
@@ -813,6 +819,7 @@ __device__ void surface_points_job(const SurfJob* __restrict__ jobs, const SurfC
     *job.out.n_cells = total <= job.out.cap ? total : job.out.cap;
     *status = total <= job.out.cap ? CFEAR_OK : CFEAR_ERR_CAPACITY;
     if (cm.ncells_out) cm.ncells_out[job_id] = total <= job.out.cap ? total : job.out.cap;
+    if (cm.path_out) cm.path_out[job_id] = path;
   }
 }
 
@@ -860,22 +867,27 @@ __global__ __launch_bounds__(kFastThreads) void surface_prep_kernel(const SurfJo
   auto done = [&](int st) {                                            // nothing (more) to do for this scan
     if (tid == 0) {
       scr.hdr->route = kRouteDone;
+      scr.hdr->path = 0u;
+      if (cm.path_out) cm.path_out[job_id] = 0u;
       *job.out.n_cells = 0; *status = st;
       if (cm.ncells_out) cm.ncells_out[job_id] = 0;
     }
   };
-  auto hand_over = [&](int n, int prepared) {                          // to the single-kernel path
+  constexpr uint32_t kRowsBit = ROWS ? CFEAR_SURF_PATH_ROWS : 0u;
+  auto hand_over = [&](int n, int prepared, uint32_t reason) {         // to the single-kernel path
     if (tid == 0) {
       scr.hdr->route = kRouteFallback;
       scr.hdr->n = n;
       scr.hdr->pad[0] = prepared;                                      // 1: xyzi already holds the compact, compensated cloud
+      scr.hdr->path = CFEAR_SURF_PATH_SINGLE | (job.row_pts ? CFEAR_SURF_PATH_ROWS : 0u) | surf_reason(reason) |
+                      (prepared ? CFEAR_SURF_PATH_PREPARED : 0u);
       const int w = atomicAdd(&cm.fallback[0], 1);
       if (w < cm.n_jobs) cm.fallback[1 + w] = job_id;         // (a stale count can never index past the list)
     }
   };
-  if (!cm.fast_ok || (job.row_pts != nullptr) != ROWS) { hand_over(0, 0); return; }
+  if (!cm.fast_ok || (job.row_pts != nullptr) != ROWS) { hand_over(0, 0, cm.fast_ok ? 0u : CFEAR_SURF_REASON_REACH); return; }
   // rotations beyond the reduced sincos' range (never a real motion; also NaN): the single-kernel path uses libm
-  if (job.compensate && !(fabs(job.mot[2]) <= 1e5)) { hand_over(0, 0); return; }
+  if (job.compensate && !(fabs(job.mot[2]) <= 1e5)) { hand_over(0, 0, CFEAR_SURF_REASON_ROTATION); return; }
   // ---- (a) point count; rows mode: exclusive prefix of the row counts ------------------------------------------
   int n = job.n_ptr ? *job.n_ptr : job.n_host;
   int32_t* rowoff = (int32_t*)smem;
@@ -901,7 +913,7 @@ __global__ __launch_bounds__(kFastThreads) void surface_prep_kernel(const SurfJo
   }
   if (n <= 0) { done(CFEAR_ERR_EMPTY_CLOUD); return; }
   if (n > cm.scratch_cap) { done(CFEAR_ERR_CAPACITY); return; }
-  if (n > kFastMaxPoints) { hand_over(n, 0); return; }     // big cloud: global-memory path of the single-kernel workgroup
+  if (n > kFastMaxPoints) { hand_over(n, 0, CFEAR_SURF_REASON_POINTS); return; }     // big cloud: global-memory path of the single-kernel workgroup
   float4* pts = job.xyzi;
   // ---- (b) polar -> Cartesian (rows mode), motion compensation, bounding box ------------------------------------
   // rows mode: the azimuth row of every point as a u16 table behind rowoff (one thread per row fills its <= k slots;
@@ -981,9 +993,10 @@ __global__ __launch_bounds__(kFastThreads) void surface_prep_kernel(const SurfJo
   if (div_bx * div_by > 0x7fffffffLL || div_by > kMaxGridRows) { done(CFEAR_ERR_CAPACITY); return; }   // non-finite / absurd points
   const int dbx = (int)div_bx, dby = (int)div_by;
   const int ncells = dbx * dby;
-  if (ncells > kFastMaxCells) { hand_over(n, 1); return; }
+  if (ncells > kFastMaxCells) { hand_over(n, 1, CFEAR_SURF_REASON_CELLS); return; }
   if (tid == 0) {                                                      // hand-off to surface_sort_kernel
     scr.hdr->route = kRoutePrepped;
+    scr.hdr->path = kRowsBit;
     scr.hdr->n = n; scr.hdr->dbx = dbx; scr.hdr->dby = dby; scr.hdr->pad[1] = min_bx; scr.hdr->pad[2] = min_by;
   }
 }
@@ -1009,11 +1022,12 @@ __device__ __forceinline__ void surface_sort_job(const SurfJob* __restrict__ job
   if (scr.hdr->route != kRoutePrepped) return;                         // failed, empty, handed to the single-kernel path -- or done (second launch)
   if (KPER * NT < kFastMaxPoints && scr.hdr->n > KPER * NT) return;    // (a larger scan than this instantiation holds: the mixed kernel's)
   const SurfJob job = jobs[job_id];
-  auto hand_over = [&](int n, int prepared) {                          // to the single-kernel path
-    if (tid == 0) {
+  auto hand_over = [&](int n, uint32_t reason) {                       // to the single-kernel path; xyzi already holds the compact,
+    if (tid == 0) {                                                    // compensated cloud (pad[0] = 1)
       scr.hdr->route = kRouteFallback;
       scr.hdr->n = n;
-      scr.hdr->pad[0] = prepared;                                      // 1: xyzi already holds the compact, compensated cloud
+      scr.hdr->pad[0] = 1;
+      scr.hdr->path = CFEAR_SURF_PATH_SINGLE | CFEAR_SURF_PATH_PREPARED | (job.row_pts ? CFEAR_SURF_PATH_ROWS : 0u) | surf_reason(reason);
       const int w = atomicAdd(&cm.fallback[0], 1);
       if (w < cm.n_jobs) cm.fallback[1 + w] = job_id;         // (a stale count can never index past the list)
     }
@@ -1037,7 +1051,9 @@ __device__ __forceinline__ void surface_sort_job(const SurfJob* __restrict__ job
   uint32_t* occ = (uint32_t*)smem;
   unsigned short* wpref = (unsigned short*)(smem + (size_t)nw32 * 4);
   const size_t ord_bytes = ((size_t)nw32 * 6 + 15) & ~(size_t)15;
-  if (ord_bytes + 8192 > kFastLds - 512) { hand_over(n, 1); return; }
+  // (no budget test here: behind kFastMaxCells the occupancy tables take at most 49 168 bytes, and the test that V and n are
+  // known for follows in phase (d))
+  static_assert((((size_t)(kFastMaxCells / 32 + 1) * 6 + 15) & ~(size_t)15) + 8192 <= kFastLds - 512, "occupancy tables of the largest fast grid fit");
   __syncthreads();                                                   // rowoff is dead
   for (int w = tid; w < nw32; w += NT) occ[w] = 0u;
   __syncthreads();
@@ -1098,7 +1114,7 @@ __device__ __forceinline__ void surface_sort_job(const SurfJob* __restrict__ job
   // LDS budget: occupancy | voxel cursors u16[V + 2] | order u16[n] (later: staged points)
   const size_t vs_off = ord_bytes, vs_bytes = (((size_t)V + 2) * 2 + 15) & ~(size_t)15;
   const size_t ord2_off = vs_off + vs_bytes;
-  if (ord2_off + (((size_t)n * 2 + 15) & ~(size_t)15) > kFastLds - 512) { hand_over(n, 1); return; }
+  if (ord2_off + (((size_t)n * 2 + 15) & ~(size_t)15) > kFastLds - 512) { hand_over(n, CFEAR_SURF_REASON_ORDER); return; }
   unsigned short* vs16 = (unsigned short*)(smem + vs_off);
   uint32_t* vs32 = (uint32_t*)(smem + vs_off);
   unsigned short* order = (unsigned short*)(smem + ord2_off);
@@ -1276,6 +1292,9 @@ __device__ __forceinline__ void surface_sort_job(const SurfJob* __restrict__ job
   constexpr int kSlabVoxels = 4 * NT;                                  // voxels per slab: their (bucket, slot) stay in registers
   // Staged point: (x, y) + weight.  Radar intensities are integers, so max(I - 60, 0) normally fits ONE byte (9 bytes
   // per point); clouds with other intensities keep a float weight.
+  uint32_t path = CFEAR_SURF_PATH_FAST | (job.row_pts ? CFEAR_SURF_PATH_ROWS : 0u) | (KPER == 64 ? CFEAR_SURF_PATH_K64 : 0u) |
+                  (wbyte ? 0u : CFEAR_SURF_PATH_WFLOAT) | (ncells > 65536 ? CFEAR_SURF_PATH_READ2 : 0u);   // block-uniform
+  int n_slabs = 0;
   auto cells_phase = [&](auto wb_tag) -> bool {                        // compiled for both weight formats
   constexpr bool WB = decltype(wb_tag)::value;
   constexpr int PB = WB ? 9 : 12;
@@ -1290,7 +1309,7 @@ __device__ __forceinline__ void surface_sort_job(const SurfJob* __restrict__ job
       return nv <= kSlabVoxels && (size_t)((np + 3) & ~3) * PB + (size_t)nv * 6 + 48 <= avail;
     };
     int lo = single ? dby : ya + 1, hi = dby;                         // largest yb in [ya + 1, dby] that fits (one-slab scan: known)
-    if (!single && !fits(lo)) { hand_over(n, 1); return false; }      // three grid rows exceed the staging area
+    if (!single && !fits(lo)) { hand_over(n, CFEAR_SURF_REASON_ROWS3); return false; }   // three grid rows exceed the staging area
     while (lo < hi) {
       const int mid = (lo + hi + 1) >> 1;
       if (fits(mid)) lo = mid; else hi = mid - 1;
@@ -1353,6 +1372,7 @@ __device__ __forceinline__ void surface_sort_job(const SurfJob* __restrict__ job
         if (C >= 6) {
           kb[u] = min(12, 32 - __clz(C - 1));
           slot[u] = atomicAdd(&bucket[kb[u]], 1);
+          if (C > 4096) bucket[13] = 1;                                   // the top bucket is saturated (route word only)
         } else {
           gstore<int32_t>(scr.coff + v, 0);                               // cannot reach 6 neighbours (pointnormal.cpp:291)
         }
@@ -1376,6 +1396,9 @@ __device__ __forceinline__ void surface_sort_job(const SurfJob* __restrict__ job
       }
     }
     const int n16 = boff[6], n4 = boff[4], nlist = boff[2];             // C > 64 | 16 < C <= 64 | 6 <= C <= 16
+    n_slabs++;
+    path |= (n16 > 0 ? CFEAR_SURF_PATH_TIER16 : 0u) | (n4 > n16 ? CFEAR_SURF_PATH_TIER4 : 0u) | (nlist > n4 ? CFEAR_SURF_PATH_TIER1 : 0u) |
+            (bucket[13] ? CFEAR_SURF_PATH_TOP_BUCKET : 0u) | (n4 > cen_cap ? CFEAR_SURF_PATH_CEN_SCRATCH : 0u);
     __syncthreads();
     STAMP(12);
     // -- centroids of the split voxels: sequential float sums in sorted (= input) order, bit-exact with
@@ -1466,6 +1489,7 @@ __device__ __forceinline__ void surface_sort_job(const SurfJob* __restrict__ job
   if (tid == 0) {
     scr.hdr->route = kRouteFast;                                       // cells computed; compaction + x-sort pending
     scr.hdr->n = n; scr.hdr->V = V; scr.hdr->dbx = dbx; scr.hdr->dby = dby;
+    scr.hdr->path = path | (n_slabs > 1 ? CFEAR_SURF_PATH_SLABS : 0u) | ((uint32_t)min(n_slabs, 255) << CFEAR_SURF_PATH_SLAB_COUNT_SHIFT);
   }
 }
 
@@ -1538,6 +1562,7 @@ __global__ __launch_bounds__(kFinishThreads) void surface_finish_kernel(const Su
     *job.out.n_cells = total <= cap ? total : cap;
     cm.status[job_id] = total <= cap ? CFEAR_OK : CFEAR_ERR_CAPACITY;
     if (cm.ncells_out) cm.ncells_out[job_id] = total <= cap ? total : cap;
+    if (cm.path_out) cm.path_out[job_id] = scr.hdr->path;
   }
 }
 
@@ -1606,7 +1631,7 @@ void cfear_surface_fill_job(void* dst, float* d_xyzi, const int32_t* d_n, int32_
 
 int cfear_surface_launch(cfear_ctx* ctx, const void* d_jobs, int n_jobs, const cfear_feature_params* par,
                          char* d_scratch, int32_t* d_status, int32_t* d_ncells_out, int max_cell_cap, int cap_points,
-                         const cfear_surface_polar* polar) {
+                         const cfear_surface_polar* polar, uint32_t* d_path_out) {
   if (par->radius <= 0.f || !(par->downsample_factor > 0.0))
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "radius / downsample_factor must be > 0");
   SurfCommon cm;
@@ -1626,6 +1651,7 @@ int cfear_surface_launch(cfear_ctx* ctx, const void* d_jobs, int n_jobs, const c
   cm.scratch_stride = scratch_bytes_per_scan(cm.scratch_cap);
   cm.status = d_status;
   cm.ncells_out = d_ncells_out;
+  cm.path_out = d_path_out;
   cm.cos_t = polar ? polar->cos_t : nullptr;
   cm.sin_t = polar ? polar->sin_t : nullptr;
   cm.range_res = polar ? polar->range_res : 0.0;
@@ -1760,27 +1786,41 @@ extern "C" int cfear_scan_create(cfear_ctx* ctx, float* xyzi, int32_t n, const c
   cfear_scan* s = nullptr;
   CFEAR_CHECK(cfear_scan_alloc(ctx, n, &s));          // at most one cell per point
   std::unique_ptr<cfear_scan, int (*)(cfear_scan*)> owned(s, cfear_scan_destroy);   // on every error, after the drain
-  int32_t hst[2] = {0, 0};                         // status, cells
+  int32_t hst[3] = {0, 0, 0};                      // status, route word (one read-back), cells
   HostStage st(ctx, kWsSurface);
   float* d;
   void* d_job;
   int32_t* d_status;
   st.in(d, xyzi, (size_t)n * 16, par->compensate != 0);     // compensated in place: back to a host caller
   st.piece(d_job, sizeof(SurfJob));
-  st.piece(d_status, 4);
+  st.piece(d_status, 8);                           // status | route word
   char* d_scratch = (char*)cfear_workspace(ctx, kWsSurfaceScratch, cfear_surface_scratch_bytes(n));
   if (!d_scratch) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
   CFEAR_CHECK(st.carve());
   void* hjob = st.record(sizeof(SurfJob));
   cfear_surface_fill_job(hjob, d, nullptr, n, par->compensate, par->mot, s->view);
   CFEAR_CHECK(st.upload(d_job, hjob, sizeof(SurfJob)));
-  CFEAR_CHECK(cfear_surface_launch(ctx, d_job, 1, par, d_scratch, d_status, nullptr, n, n));
-  st.back(&hst[0], d_status, 4);
-  st.back(&hst[1], s->view.n_cells, 4);
+  CFEAR_CHECK(cfear_surface_launch(ctx, d_job, 1, par, d_scratch, d_status, nullptr, n, n, nullptr, (uint32_t*)(d_status + 1)));
+  st.back(&hst[0], d_status, 8);
+  st.back(&hst[2], s->view.n_cells, 4);
   CFEAR_CHECK(st.finish());
   if (hst[0] != CFEAR_OK) return cfear_set_error(ctx, hst[0], "surface point extraction failed: %s", cfear_status_string(hst[0]));
-  s->n_cells_host = hst[1];
+  s->n_cells_host = hst[2];
+  s->surf_path = (uint32_t)hst[1];
   *out = owned.release();
+  return CFEAR_OK;
+}
+
+extern "C" int cfear_scan_surface_path(const cfear_scan* scan, uint32_t* path) {
+  if (!scan || !path) return CFEAR_ERR_INVALID_ARGUMENT;
+  *path = scan->surf_path;
+  return CFEAR_OK;
+}
+
+int cfear_surface_read_path(cfear_ctx* ctx, const char* d_scratch, int cap_points, int job, uint32_t* path) {
+  const char* hdr = d_scratch + (size_t)job * cfear_surface_scratch_bytes(cap_points);
+  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(path, hdr + offsetof(SurfHdr, path), 4, hipMemcpyDeviceToHost, ctx->stream));
+  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return CFEAR_OK;
 }
 

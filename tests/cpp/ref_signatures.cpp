@@ -65,6 +65,11 @@ int main(int argc, char** argv) {
     MapNormalPtr moved = m0->TransformMap(Pose2dToAffine3d(Pose2d{1.0, 2.0, 0.25}));
     if (moved->GetSize() != m0->GetSize() || !(moved->GetCell(0).nsamples == m0->GetCell(0).nsamples)) return 4;
     if (m0->GetScan() != cloud[0]) return 4;                                   // GetScan (pointnormal.h:170)
+    // the route word: a k-strongest scan runs on the fast pipeline, a map made from cells on none
+    int (*surface_path)(const cfear_scan*, uint32_t*) = &cfear_scan_surface_path;
+    uint32_t path0 = 0;
+    if (surface_path(m0->device(), &path0) != CFEAR_OK || path0 != m0->SurfacePath()) return 4;
+    if ((path0 & CFEAR_SURF_PATH_KIND_MASK) != CFEAR_SURF_PATH_FAST || moved->SurfacePath() != 0u) return 4;
     MapPointNormal::PublishMap("/current_normals", m1, T_vek.back(), "world", 1);   // a no-op here (RViz markers)
     // soft_constraints = true is refused loudly, never ignored (n_scan_normal.cpp:371-375 is undefined behaviour there)
     bool refused = false;

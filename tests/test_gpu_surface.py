@@ -2,6 +2,8 @@
 import numpy as np
 import pytest
 
+from tests.surface_routes import cmp_cells as _cmp_cells, describe, predict, KIND_MASK, FAST, SINGLE
+
 pytestmark = pytest.mark.gpu
 
 
@@ -11,18 +13,6 @@ def _cloud(seed, frame=0, k=40, range_res=0.0438):
     imgs, _, _ = synth.scene_v1(seed, frame + 1, range_res=range_res)
     sr, si, sc = O.kstrongest(imgs[frame], k, 60)
     return O.kstrongest_cloud(sr, si, sc, range_res, 2.5)
-
-
-def _cmp_cells(got, exp):
-    assert got.shape[0] == exp.shape[0]
-    np.testing.assert_array_equal(got["nsamples"], exp["nsamples"])
-    # fp64 sums are reduced in a different (tree) order on the GPU: rounding-level differences only
-    np.testing.assert_allclose(got["mean"], exp["mean"], rtol=0, atol=1e-9)
-    np.testing.assert_allclose(got["cov"], exp["cov"], rtol=1e-9, atol=1e-10)
-    np.testing.assert_allclose(got["normal"], exp["normal"], rtol=0, atol=1e-7)
-    np.testing.assert_allclose(got["scale"], exp["scale"], rtol=1e-8)
-    np.testing.assert_allclose(got["avg_intensity"], exp["avg_intensity"], rtol=1e-12)
-    np.testing.assert_allclose(got["lambda_min"], exp["lambda_min"], rtol=1e-8, atol=1e-12)
 
 
 def test_compensate_matches_oracle():
@@ -156,9 +146,10 @@ def test_surface_points_large_clouds(n):
     _cmp_cells(got, exp)
 
 
-def test_surface_points_small_voxels_and_downsampling_take_the_single_kernel_path():
-    """Voxel grids with more than 16384 cells (radius 1 m over a 250 m scan) and downsample factors != 1 (several voxels
-    per radius) are handed from the fast pipeline to the single-kernel path: same cells as the oracle."""
+def test_surface_points_small_voxels_and_downsampling():
+    """Radius 1 m over a 250 m scan is a grid of some 86 000 cells: more than 65 536 (the fast pipeline reads the points a
+    second time) but within its 2^18, so that case stays on the fast pipeline; downsample factors != 1 (several voxels per
+    radius) are handed to the single-kernel path.  The route word says which ran; same cells as the oracle on both."""
     from oracle import pyoracle as O
     from tbv_slam_public_amd import api, synth
     imgs, _, _ = synth.scene_v1(8, 1)
@@ -169,9 +160,12 @@ def test_surface_points_small_voxels_and_downsampling_take_the_single_kernel_pat
         old = api.MapPointNormal.downsample_factor
         api.MapPointNormal.downsample_factor = factor
         try:
-            got = api.MapPointNormal(cloud, radius, (0, 0), True).GetCells()
+            m = api.MapPointNormal(cloud, radius, (0, 0), True)
+            got = m.GetCells()
         finally:
             api.MapPointNormal.downsample_factor = old
+        assert m.path == predict(cloud, radius, factor), (describe(m.path), describe(predict(cloud, radius, factor)))
+        assert m.path & KIND_MASK == (FAST if factor == 1.0 else SINGLE), describe(m.path)
         assert exp.shape[0] > 50
         _cmp_cells(got, exp)
 
