@@ -576,6 +576,71 @@ int cfear_p2p_quality(cfear_ctx* ctx, const cfear_p2p_job* job, double radius, c
 int cfear_p2p_quality_batch(cfear_ctx* ctx, const cfear_p2p_job* jobs, int32_t n_jobs, double radius,
                             cfear_p2p_result* results, float* per_point);
 
+/* ---- caller: the Cartesian radar image and CorAlCartQuality -------------------------------------------
+ * Replaces CartesianRadar (coral_alignment_quality/src/alignment_checker/ScanType.cpp:191-209), radar_polar_to_cartesian and
+ * RotoTranslation (Utils.cpp:255-339) and CorAlCartQuality (AlignmentQuality.cpp:356-386), the measure
+ * AlignmentQualityFactory::CreateQualityType (AlignmentQuality.h:260-312) builds for CartesianRadar scans (evaluate_scans
+ * --scan-type kstrongCart) whatever pars.method says.
+ *   cfear_polar_to_cartesian   f = float(u8) * float(1 / 255.0) (convertTo), then cv::remap with the float maps of Utils.cpp:
+ *                              258-308: per Cartesian pixel a range bin and an azimuth index, quantised to 1/32 pixel with
+ *                              cvRound (half to even), bilinear in float ((S00 w0 + S01 w1) + S10 w2) + S11 w3, taps outside
+ *                              the sweep read 0.  The maps depend on (rows, W, radar_resolution, cart_resolution) only: the
+ *                              HOST builds them (its libm's atan2f) once per geometry and the context keeps them.
+ *   cfear_cart_quality_batch   per job RotoTranslation of the source image by (x, y, yaw) -- warpAffine with
+ *                              getRotationMatrix2D about ((W - 1) / 2, (W - 1) / 2), then warpAffine of ITS OUTPUT by
+ *                              (float(x) / image_res, float(y) / image_res) pixels; both with OpenCV's integer maps (the
+ *                              matrix inverted in double, 10 fraction bits, + 16 >> 5: 1/32 pixel rounded half UP), bilinear,
+ *                              border 0 -- and abs_diff = the sum of |warped - ref| over the W x W floats, added in double.
+ *                              quality_ = {abs_diff, 0, 0}.
+ * Quirks of the reference, kept:
+ *   - the azimuth index of a pixel lies in [-1, rows - 1) and the cross-over interpolation is commented out (Utils.cpp:
+ *     316-319): for an index below 0 row -1 reads zeros, so the seam behind the last azimuth is darkened;
+ *   - RotoTranslation hands the yaw, in RADIANS, to getRotationMatrix2D, which takes degrees: a yaw of 0.5 rotates by 0.5
+ *     degrees.  The entry point takes the yaw as the reference has it and does the same;
+ *   - CorAlCartQuality takes Tsrc AND Tref from the source scan (AlignmentQuality.cpp:363-364), so Tchange = Tsrc^-1 Tsrc
+ *     Toffset; and the CartesianRadar constructor calls radar_polar_to_cartesian with its default arguments (0.04328, 0.2384,
+ *     300) whatever pars says, while CorAlCartQuality reads cart_resolution_ from pars.  Both are the callers' business:
+ *     include/cfear_hip.hpp and api.py reproduce them, the entry points take explicit values and (x, y, yaw) per job.
+ * NOT PINNED: the arithmetic of remap, warpAffine, getRotationMatrix2D and convertTo is restated from knowledge of OpenCV
+ * 4.2's imgproc (tests/cart_cpu.py is the definition); no OpenCV build was compared.  cv::sum's order of additions is not
+ * restated either: abs_diff is added per thread with a fixed stride, then over a fixed tree, an order that depends on W
+ * only, so it is within 2 W^2 2^-53, relatively, of any other order and a job's record does not depend on the batch.  */
+typedef struct cfear_cart_params {
+  float radar_resolution;               /* 0.04328 */
+  float cart_resolution;                /* 0.2384 */
+  int32_t cart_pixel_width;             /* 300 */
+  int32_t pad;
+} cfear_cart_params;                    /* 16 bytes */
+void cfear_cart_params_default(cfear_cart_params* par);
+
+/* polar: batch sweeps (rows = azimuths, rows >= 2); cart: float [batch][W][W]; both host or both device memory.
+ * CFEAR_ERR_INVALID_ARGUMENT: W < 1 or > CFEAR_CART_MAX_WIDTH, rows < 2, rows or cols > 32767 (the reference's `short`
+ * coordinates), a resolution that is not finite and > 0.  With device memory the call is only enqueued.                */
+#define CFEAR_CART_MAX_WIDTH 4096
+int cfear_polar_to_cartesian(cfear_ctx* ctx, const uint8_t* polar, const cfear_polar_desc* desc, const cfear_cart_params* par,
+                             float* cart);
+
+typedef struct cfear_cart_job {
+  const float* src;                     /* [W][W] the image that is warped, host or device              */
+  const float* ref;                     /* [W][W] the image it is compared with, host or device         */
+  double x, y, yaw;                     /* Affine3dToEigVectorXYeZ(Tchange)                             */
+} cfear_cart_job;                       /* 40 bytes */
+
+typedef struct cfear_cart_result {
+  double abs_diff;                      /* CorAlCartQuality quality_[0]                                 */
+  int32_t status;                       /* CFEAR_OK / CFEAR_ERR_INVALID_ARGUMENT                        */
+  int32_t pad;
+} cfear_cart_result;                    /* 16 bytes */
+
+/* results [n_jobs] and warped (optional: float [n_jobs][W][W], the warped source images) may each be host or device
+ * memory; images shared between jobs are uploaded once.  A job whose pose is not finite, or whose |x| or |y| over
+ * image_res exceeds 2^20 pixels (which keeps OpenCV's saturate_cast<int> out of play), gets status
+ * CFEAR_ERR_INVALID_ARGUMENT, a zero abs_diff and a zero warped image; the call completes and returns CFEAR_OK, the other
+ * records are valid.  The call itself fails with CFEAR_ERR_INVALID_ARGUMENT for a null image, W out of range or an
+ * image_res that is not finite and > 0.  With device memory throughout the call is only enqueued.                   */
+int cfear_cart_quality_batch(cfear_ctx* ctx, const cfear_cart_job* jobs, int32_t n_jobs, int32_t cart_pixel_width,
+                             float image_res, cfear_cart_result* results, float* warped);
+
 /* ---- before the path: radar Scan Context (loop-candidate generation) ------------------------------
  * Replaces the arithmetic of RSCManager / SCManager (place_recognition_radar/src/place_recognition_radar/
  * RadarScancontext.cpp:59-131, 156-180; Scancontext.cpp:60-268): the ring x sector descriptor of a

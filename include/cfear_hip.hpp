@@ -908,6 +908,87 @@ class keypointRepetability : public AlignmentQuality {
   cfear_p2p_result record_{};
 };
 
+// CartesianRadar (ScanType.h:160-178, ScanType.cpp:191-209): the sweep resampled into a W x W float image by
+// cfear_polar_to_cartesian.  The reference's constructor calls radar_polar_to_cartesian with its DEFAULT arguments (0.04328,
+// 0.2384, 300) whatever pars says and only stores pars.cart_resolution / cart_pixel_width, which CorAlCartQuality reads; so
+// does this one (image_params overrides the geometry of the image for callers that want another).
+class CartesianRadar : public PoseScan {
+ public:
+  struct Parameters {                                                          // PoseScan::Parameters, ScanType.h:55-91
+    double sensor_min_distance = 2.5;
+    float cart_resolution = 0.2384f;
+    int cart_pixel_width = 300;
+  };
+  CartesianRadar(CFEAR_Radarodometry::Context& ctx, const Parameters& pars, const uint8_t* image, int rows, int cols, int stride,
+                 const CFEAR_Radarodometry::Pose2d& pose = CFEAR_Radarodometry::Pose2d{0, 0, 0}, const cfear_cart_params* image_params = nullptr)
+      : sensor_min_distance(pars.sensor_min_distance), cart_resolution_(pars.cart_resolution), cart_pixel_width_(pars.cart_pixel_width) {
+    T = pose;
+    cfear_polar_desc d{rows, cols, stride, 1, 0};
+    cfear_cart_params p;
+    cfear_cart_params_default(&p);
+    if (image_params) p = *image_params;
+    width_ = p.cart_pixel_width;
+    cart_.assign((size_t)(width_ > 0 ? width_ : 0) * (size_t)(width_ > 0 ? width_ : 0), 0.0f);
+    ctx.check(cfear_polar_to_cartesian(ctx.get(), image, &d, &p, cart_.data()));
+  }
+#ifdef CFEAR_HIP_HAVE_CV_BRIDGE
+  // the reference's constructor shape (ScanType.cpp:191); Tmotion is not read there either
+  CartesianRadar(const Parameters& pars, cv_bridge::CvImagePtr& polar, const Eigen::Affine3d& T, const Eigen::Affine3d& Tmotion)
+      : CartesianRadar(CFEAR_Radarodometry::Context::Default(), pars, polar->image.data, polar->image.rows, polar->image.cols,
+                       (int)polar->image.step, CFEAR_Radarodometry::Affine3dToPose2d(T)) { (void)Tmotion; }
+#endif
+  const std::string ToString() { return "CartesianRadar"; }
+  std::vector<float> cart_;                                                    // [width_][width_]
+  int width_ = 0;
+  double sensor_min_distance, cart_resolution_;
+  int cart_pixel_width_;
+};
+typedef std::shared_ptr<CartesianRadar> CartesianRadar_S;
+
+// CorAlCartQuality (AlignmentQuality.h:184-200, AlignmentQuality.cpp:356-386): quality_ = {sum |RotoTranslation(src.cart,
+// Tchange, ref.cart_resolution_) - ref.cart|, 0, 0}.  The reference takes Tsrc AND Tref from the source scan (:363-364), so
+// Tchange = Tsrc^-1 Tsrc Toffset and the reference scan's pose is not read; RotoTranslation then hands the yaw, in radians,
+// to getRotationMatrix2D as degrees (cfear_cart_quality_batch does the same).
+class CorAlCartQuality : public AlignmentQuality {
+ public:
+  CorAlCartQuality(CartesianRadar_S ref, CartesianRadar_S src, const AlignmentQuality::parameters& par,
+                   const CFEAR_Radarodometry::Pose2d Toffset = CFEAR_Radarodometry::Pose2d{0, 0, 0})
+      : CorAlCartQuality(CFEAR_Radarodometry::Context::Default(), ref, src, par, Toffset) {}
+  CorAlCartQuality(CFEAR_Radarodometry::Context& ctx, CartesianRadar_S ref, CartesianRadar_S src, const AlignmentQuality::parameters& par,
+                   const CFEAR_Radarodometry::Pose2d Toffset = CFEAR_Radarodometry::Pose2d{0, 0, 0})
+      : AlignmentQuality(par, Toffset) {
+    if (ref->width_ != src->width_ || src->width_ <= 0)
+      throw CFEAR_Radarodometry::CfearError(CFEAR_ERR_INVALID_ARGUMENT, "CorAlCartQuality: images of different widths");
+    const std::array<double, 6> T = Tchange(src->T, src->T, Toffset_);         // both from the SOURCE scan
+    cfear_cart_job j{};
+    j.src = src->cart_.data(); j.ref = ref->cart_.data();
+    j.x = T[2]; j.y = T[5]; j.yaw = std::atan2(T[3], T[4]);                    // Affine3dToEigVectorXYeZ of a planar pose
+    ctx.check(cfear_cart_quality_batch(ctx.get(), &j, 1, src->width_, (float)ref->cart_resolution_, &record_, nullptr));
+    if (record_.status != CFEAR_OK)
+      throw CFEAR_Radarodometry::CfearError(record_.status, "CorAlCartQuality: the pose offset is not finite or beyond 2^20 pixels");
+    quality_ = {record_.abs_diff, 0, 0};
+  }
+  cfear_cart_result record_{};
+};
+
+// AlignmentQualityFactory (AlignmentQuality.h:260-312), the branches this header has classes for: two CartesianRadar scans
+// give CorAlCartQuality whatever pars.method says; plain PoseScans give p2pQuality or keypointRepetability by pars.method.
+class AlignmentQualityFactory {
+ public:
+  static AlignmentQuality_S CreateQualityType(CFEAR_Radarodometry::Context& ctx, CartesianRadar_S ref, CartesianRadar_S src,
+                                              const AlignmentQuality::parameters& pars,
+                                              const CFEAR_Radarodometry::Pose2d& Toffset = CFEAR_Radarodometry::Pose2d{0, 0, 0}) {
+    return AlignmentQuality_S(new CorAlCartQuality(ctx, ref, src, pars, Toffset));
+  }
+  static AlignmentQuality_S CreateQualityType(CFEAR_Radarodometry::Context& ctx, PoseScan_S ref, PoseScan_S src,
+                                              const AlignmentQuality::parameters& pars,
+                                              const CFEAR_Radarodometry::Pose2d& Toffset = CFEAR_Radarodometry::Pose2d{0, 0, 0}) {
+    if (pars.method == "P2P") return AlignmentQuality_S(new p2pQuality(ctx, ref, src, pars, Toffset));
+    if (pars.method == "keypoint_repetability") return AlignmentQuality_S(new keypointRepetability(ctx, ref, src, pars, Toffset));
+    throw CFEAR_Radarodometry::CfearError(CFEAR_ERR_INVALID_ARGUMENT, "no quality metric for scan type with method " + pars.method);
+  }
+};
+
 // One row of eval.txt (ScanEvaluator.h:21-52 declares the class; the rules are stated in tests/p2p_cpu.py): the pair's
 // 1-based index, the two pose ids, the planar distance between the poses, the measure's three values, the offset and
 // whether it counts as aligned (its absolute values add up to less than 1e-4).

@@ -144,6 +144,19 @@ assert C.sizeof(P2pJob) == 72 and P2P_RESULT_DTYPE.itemsize == 32
 P2P_MAX_REF_POINTS, P2P_MAX_SRC_POINTS = 16384, 1048576
 
 
+class CartParams(C.Structure):    # cfear_cart_params
+    _fields_ = [("radar_resolution", C.c_float), ("cart_resolution", C.c_float), ("cart_pixel_width", C.c_int32), ("pad", C.c_int32)]
+
+
+class CartJob(C.Structure):       # cfear_cart_job
+    _fields_ = [("src", C.c_void_p), ("ref", C.c_void_p), ("x", C.c_double), ("y", C.c_double), ("yaw", C.c_double)]
+
+
+CART_RESULT_DTYPE = np.dtype([("abs_diff", "<f8"), ("status", "<i4"), ("pad", "<i4")])
+assert C.sizeof(CartParams) == 16 and C.sizeof(CartJob) == 40 and CART_RESULT_DTYPE.itemsize == 16
+CART_MAX_WIDTH = 4096
+
+
 class ScParams(C.Structure):
     _fields_ = [("num_ring", C.c_int32), ("num_sector", C.c_int32), ("max_radius", C.c_double),
                 ("search_ratio", C.c_double), ("desc_function", C.c_int32), ("pad", C.c_int32),
@@ -260,6 +273,7 @@ EXPORTS = [
     "cfear_eval_params_default", "cfear_eval_trajectories", "cfear_eval_check", "cfear_kitti_read", "cfear_kitti_write",
     "cfear_kitti_from_xyt", "cfear_cen2018_params_default", "cfear_filter_cen2018",
     "cfear_logreg_params_default", "cfear_logreg_fit_batch", "cfear_p2p_quality", "cfear_p2p_quality_batch",
+    "cfear_cart_params_default", "cfear_polar_to_cartesian", "cfear_cart_quality_batch",
 ]
 
 PIPE_GRAPH, PIPE_TIMING = 1, 2      # enum { CFEAR_PIPE_GRAPH, CFEAR_PIPE_TIMING }
@@ -426,6 +440,10 @@ def lib():
     L.cfear_coral_quality_batch.argtypes = [vp, C.POINTER(CoralJob), C.c_int32, C.POINTER(CoralParams), vp, vp]
     L.cfear_p2p_quality.argtypes = [vp, C.POINTER(P2pJob), C.c_double, vp, vp]
     L.cfear_p2p_quality_batch.argtypes = [vp, C.POINTER(P2pJob), C.c_int32, C.c_double, vp, vp]
+    L.cfear_cart_params_default.argtypes = [C.POINTER(CartParams)]
+    L.cfear_cart_params_default.restype = None
+    L.cfear_polar_to_cartesian.argtypes = [vp, vp, C.POINTER(PolarDesc), C.POINTER(CartParams), vp]
+    L.cfear_cart_quality_batch.argtypes = [vp, C.POINTER(CartJob), C.c_int32, C.c_int32, C.c_float, vp, vp]
     L.cfear_sc_params_default.argtypes = [C.POINTER(ScParams)]
     L.cfear_sc_params_default.restype = None
     L.cfear_sc_descriptors.argtypes = [vp, C.POINTER(ScCloud), C.c_int32, C.POINTER(ScParams), C.POINTER(C.c_double),

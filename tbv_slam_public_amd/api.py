@@ -1011,14 +1011,155 @@ class CFEARQuality:
         return list(self.quality_)
 
 
+# ------------------------------------------------------------------------------------------------
+# The Cartesian radar image and CorAlCartQuality (ScanType.cpp:191-209, Utils.cpp:255-339, AlignmentQuality.cpp:356-386)
+# ------------------------------------------------------------------------------------------------
+def cart_params(**kw):
+    """cfear_cart_params with radar_polar_to_cartesian's default arguments (radar_resolution 0.04328, cart_resolution 0.2384,
+    cart_pixel_width 300), overridden by keyword."""
+    p = L.CartParams()
+    L.lib().cfear_cart_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in ("radar_resolution", "cart_resolution", "cart_pixel_width"):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def polar_to_cartesian(images, params=None, ctx=None):
+    """convertTo(CV_32F, 1 / 255.0) + radar_polar_to_cartesian for a uint8 sweep [rows, cols] or a batch [b, rows, cols]
+    (rows = azimuths) -> float32 [W, W] / [b, W, W]; NumPy -> NumPy, torch CUDA -> torch CUDA (a torch view with a row pitch
+    or a batch stride is used in place, and the call is only enqueued).  The fixed-point map of the geometry is built on the
+    host once and kept in the context."""
+    ctx = ctx or default_context()
+    par = params or cart_params()
+    d, batch, rows, cols = _desc(images)
+    W = int(par.cart_pixel_width)
+    shape = (W, W) if images.ndim == 2 else (batch, W, W)
+    if _is_torch(images):
+        import torch
+        assert images.dtype == torch.uint8 and images.stride(-1) == 1
+        d.stride = images.stride(-2)
+        d.batch_stride = images.stride(0) if images.ndim == 3 else rows * d.stride
+        out = torch.empty(tuple(max(v, 0) for v in shape), dtype=torch.float32, device=images.device)
+        p = images.data_ptr()
+    else:
+        images = np.ascontiguousarray(images, dtype=np.uint8)
+        out = np.empty(tuple(max(v, 0) for v in shape), np.float32)
+        p = _ptr(images)[0]
+    ctx.check(ctx._lib.cfear_polar_to_cartesian(ctx.h, p, C.byref(d), C.byref(par), _ptr(out)[0]))
+    return out
+
+
+def _image_ptr(img):
+    if _is_torch(img):
+        import torch
+        assert img.dtype == torch.float32 and img.is_contiguous() and img.ndim == 2 and img.shape[0] == img.shape[1]
+        return img.data_ptr(), int(img.shape[0]), img
+    a = np.ascontiguousarray(img, dtype=np.float32)
+    assert a.ndim == 2 and a.shape[0] == a.shape[1]
+    return a.ctypes.data, int(a.shape[0]), a
+
+
+def cart_quality_batch(jobs, image_res, want_warped=False, ctx=None, device_out=False):
+    """cfear_cart_quality_batch: one launch.  jobs: list of (src_image, ref_image, (x, y, yaw)); images float32 [W, W], NumPy
+    or torch CUDA (used in place; an image object named by several jobs is uploaded once).  The yaw is handed to
+    getRotationMatrix2D as the reference does: radians, read as degrees.
+    -> (CART_RESULT_DTYPE array, float32 [n, W, W] warped source images or None); a job with a non-finite pose or an offset
+    beyond 2^20 pixels has status ERR_INVALID_ARGUMENT and zeros.  device_out: torch CUDA tensors (uint8 [n, 16] records)."""
+    ctx = ctx or default_context()
+    n = len(jobs)
+    arr = (L.CartJob * max(n, 1))()
+    keep, W, seen = [], None, {}
+    for i, (src, ref, pose) in enumerate(jobs):
+        for name, img in (("src", src), ("ref", ref)):
+            if id(img) not in seen:                             # np.ascontiguousarray may copy: one copy per object
+                seen[id(img)] = _image_ptr(img)
+                keep.append(img)
+            ptr, w, _k = seen[id(img)]
+            if W is None:
+                W = w
+            if w != W:
+                raise ValueError("cart_quality_batch: images of different widths")
+            setattr(arr[i], name, ptr)
+        arr[i].x, arr[i].y, arr[i].yaw = float(pose[0]), float(pose[1]), float(pose[2])
+    W = W or 1
+    if device_out:
+        import torch
+        out = torch.zeros((n, L.CART_RESULT_DTYPE.itemsize), dtype=torch.uint8, device="cuda")
+        warped = torch.zeros((n, W, W), dtype=torch.float32, device="cuda") if want_warped else None
+    else:
+        out = np.zeros(n, L.CART_RESULT_DTYPE)
+        warped = np.zeros((n, W, W), np.float32) if want_warped else None
+    if n:
+        ctx.check(ctx._lib.cfear_cart_quality_batch(ctx.h, arr, n, W, float(image_res), _ptr(out)[0], _ptr(warped)[0]))
+    return out, warped
+
+
+class PoseScanParameters:
+    """PoseScan::Parameters (ScanType.h:55-91), the members CartesianRadar reads."""
+
+    def __init__(self, scan_type="kstrongCart", sensor_min_distance=2.5, range_res=0.04328, cart_resolution=0.2384, cart_pixel_width=300):
+        self.scan_type, self.sensor_min_distance, self.range_res = scan_type, float(sensor_min_distance), float(range_res)
+        self.cart_resolution, self.cart_pixel_width = float(np.float32(cart_resolution)), int(cart_pixel_width)
+
+
+def CartesianRadar(pars, polar, T, pose_id=0, ctx=None, image_params=None):
+    """CartesianRadar(pars, polar, T) (ScanType.cpp:191-209) -> a scan dict {"type": "CartesianRadar", "T", "pose_id", "cart":
+    float32 [W, W], "cart_resolution", "cart_pixel_width"}.  The reference's constructor calls radar_polar_to_cartesian with
+    its DEFAULT arguments (0.04328, 0.2384, 300) whatever pars says, and only stores pars.cart_resolution / cart_pixel_width
+    for CorAlCartQuality to read; so does this.  image_params (a cart_params()) overrides the geometry of the image."""
+    pars = pars or PoseScanParameters()
+    return {"type": "CartesianRadar", "T": tuple(float(v) for v in T), "pose_id": int(pose_id),
+            "cart": polar_to_cartesian(polar, image_params, ctx), "cart_resolution": pars.cart_resolution,
+            "cart_pixel_width": pars.cart_pixel_width}
+
+
+def cart_pose_offset(src_pose, Toffset=(0.0, 0.0, 0.0), ref_pose=None):
+    """(x, y, yaw) of CorAlCartQuality's Tchange.  The reference takes Tsrc AND Tref from the source scan
+    (AlignmentQuality.cpp:363-364): Tchange = Tsrc^-1 Tsrc Toffset, ref_pose is not read.  Composed like p2p_tchange; the
+    yaw is eulerAngles(0, 1, 2)[2] of a planar rotation, atan2(m10, m11)."""
+    T = _tchange(src_pose, src_pose, Toffset)
+    return float(T[2]), float(T[5]), math.atan2(T[3], T[4])
+
+
+def _cart_job(ref, src, Toffset):
+    return (src["cart"], ref["cart"], cart_pose_offset(src["T"], Toffset, ref["T"]))
+
+
+class CorAlCartQuality:
+    """CorAlCartQuality(ref, src, par, Toffset) (AlignmentQuality.cpp:356-386) over two CartesianRadar scans: quality_ =
+    {sum |RotoTranslation(src.cart, Tchange, ref.cart_resolution) - ref.cart|, 0, 0}; residuals_ stays {0, 0, 0}."""
+
+    def __init__(self, ref, src, par=None, Toffset=(0.0, 0.0, 0.0), ctx=None, _record=None):
+        self.par_ = par or AlignmentQualityParameters()
+        if _record is None:
+            _record = cart_quality_batch([_cart_job(ref, src, Toffset)], ref.get("cart_resolution", 0.2384), False, ctx)[0][0]
+        if int(_record["status"]) != L.OK:
+            raise L.CfearError(int(_record["status"]), "CorAlCartQuality: the pose offset is not finite or beyond 2^20 pixels")
+        self.record = _record
+        self.residuals_ = [0.0, 0.0, 0.0]
+        self.quality_ = [float(_record["abs_diff"]), 0.0, 0.0]
+        self.valid_ = False                                   # never set by the reference
+
+    def GetResiduals(self):
+        return list(self.residuals_)
+
+    def GetQualityMeasure(self):
+        return list(self.quality_)
+
+
 _CFEAR_TYPE, _P2P_TYPES, _CORAL_TYPES = "CFEARFeatures", ("BFARScan", "RawLidar", "kstrongStructuredRadar", "Cen2018Radar"), \
     ("kstrongRadar", "kstrongStructuredRadar")
 
 
 def _quality_kind(scan_type, method):
     """The measure AlignmentQualityFactory::CreateQualityType (AlignmentQuality.h:260-312) builds for a scan type and
-    pars.method: "CFEAR", "P2P", "keypoint_repetability" or "Coral"; raises where the reference prints "no quality metric
-    for scan typee" and exits, and for the measures that are not built here."""
+    pars.method: "CFEAR", "P2P", "keypoint_repetability", "Coral" or "CorAlCart" (CartesianRadar scans, whatever the method);
+    raises where the reference prints "no quality metric for scan typee" and exits, and for the two measures that are empty
+    stubs in the reference."""
+    if scan_type == "CartesianRadar":
+        return "CorAlCart"
     if scan_type == _CFEAR_TYPE:
         if method not in L.COST:
             raise ValueError("CFEARFeatures: unknown cost %r" % (method,))
@@ -1029,8 +1170,8 @@ def _quality_kind(scan_type, method):
         return "keypoint_repetability"
     if method == "Coral" and scan_type in _CORAL_TYPES:
         return "Coral"
-    if (scan_type == "RawLidar" and method in ("Coral", "P2D")) or scan_type == "CartesianRadar":
-        raise NotImplementedError("%s / %s: CorAl (lidar), p2dQuality and CorAlCartQuality are not built" % (scan_type, method))
+    if scan_type == "RawLidar" and method in ("Coral", "P2D"):
+        raise NotImplementedError("%s / %s: CorAl (lidar) and p2dQuality are not built" % (scan_type, method))
     raise ValueError("no quality metric for scan type %r with method %r" % (scan_type, method))
 
 
@@ -1054,6 +1195,8 @@ class AlignmentQualityFactory:
             return p2pQuality(ref, src, pars, Toffset, ctx)
         if kind == "keypoint_repetability":
             return keypointRepetability(ref, src, pars, Toffset, ctx)
+        if kind == "CorAlCart":
+            return CorAlCartQuality(ref, src, pars, Toffset, ctx)
         if pars.ent_cfg not in ("any", 0):
             raise NotImplementedError("CorAlRadarQuality: only ent_cfg = any is built")
         return CorAlRadarQuality(_scan_cloud(ref), ref["T"], _scan_cloud(src), src["T"], Toffset, pars.radius,
@@ -1074,7 +1217,7 @@ class scanEvaluator:
     """scanEvaluator (ScanEvaluator.cpp:4-114), the body of evaluate_scans: every pair (scan[k - 1], scan[k]), k >=
     scan_spacing, is scored at the aligned offset and at offset_rotation_steps misaligned ones.  All (N - scan_spacing) x
     (steps + 1) jobs go through ONE batched call of the measure the factory picks for the scans' type and quality_par.method
-    (p2p_quality_batch, coral_quality_batch or cfear_quality_batch); there is no loop over pairs.
+    (p2p_quality_batch, coral_quality_batch, cart_quality_batch or cfear_quality_batch); there is no loop over pairs.
     datapoints_: dicts(index, ref_id, src_id, distance, score, aligned, perturbation, residuals)."""
 
     HEADER = ["index", "ref_id", "src_id", "distance", " score1", "score2", "score3", "aligned", "error x", "error y", "error theta"]
@@ -1106,6 +1249,15 @@ class scanEvaluator:
                 nres = [[0.0, 0.0, 0.0] + [float(x) for x in row[row >= 0]] for row in pp]
             else:
                 scores = [_repeatability(v) for v in out]
+        elif kind == "CorAlCart":
+            res = {float(np.float32(r.get("cart_resolution", 0.2384))) for _k, r, _s in pairs}
+            if len(res) != 1:
+                raise ValueError("scanEvaluator: CartesianRadar scans of different cart_resolution")
+            out, _ = cart_quality_batch([_cart_job(r, s, o) for _k, r, s in pairs for o in vek], res.pop(), False, ctx)
+            for v in out:
+                if int(v["status"]) != L.OK:
+                    raise L.CfearError(int(v["status"]), "CorAlCartQuality: the pose offset is not finite or beyond 2^20 pixels")
+            scores = [[float(v["abs_diff"]), 0.0, 0.0] for v in out]
         elif kind == "Coral":
             if q.ent_cfg not in ("any", 0):
                 raise NotImplementedError("CorAlRadarQuality: only ent_cfg = any is built")

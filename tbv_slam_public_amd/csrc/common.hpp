@@ -48,6 +48,8 @@ enum WsSlot : int {
   kWsLogreg = 18,         // classifier fits: staged rows, labels and masks, job records, results
   kWsP2p = 19,            // p2p quality: group and job records, staged results and per-point minima
   kWsP2pScratch = 20,     // p2p quality: sorted reference clouds that do not fit the LDS
+  kWsCart = 21,           // Cartesian image / CorAlCart quality: staged images, job records, partial sums, staged outputs
+  kWsCartMap = 22,        // the fixed-point polar -> Cartesian map of the last geometry (cfear_ctx::cart_map_*)
 };
 
 struct cfear_ctx {
@@ -60,7 +62,7 @@ struct cfear_ctx {
   std::vector<hipEvent_t> event_pool;
   // grow-only device workspaces (indexed by WsSlot so stages of one pipeline do not alias)
   struct Ws { void* p = nullptr; size_t bytes = 0; };
-  Ws ws[21];
+  Ws ws[23];
   // pinned host staging for small read-backs
   void* pinned = nullptr;
   size_t pinned_bytes = 0;
@@ -71,6 +73,9 @@ struct cfear_ctx {
   std::vector<Slab> free_slabs;
   int64_t live_scans = 0;
   int trig_rows = 0;       // rows the cos/sin tables in ws[kWsTrig] were built for
+  // geometry the map in ws[kWsCartMap] was built for (cartesian.hip); cart_map_w = 0: none
+  int cart_map_rows = 0, cart_map_w = 0;
+  float cart_map_radar_res = 0.f, cart_map_cart_res = 0.f;
   int n_cu = 256;          // compute units of the device (cfear_ctx_create)
   int64_t opt[CFEAR_OPT_COUNT] = {1, 0, 0, 0};   // cfear_ctx_set_option (test / measurement hooks; include/cfear_hip.h)
   bool surf_list_dirty = true;   // the surface pipeline's hand-over counter may be non-zero (see cfear_surface_launch)
