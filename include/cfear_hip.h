@@ -547,8 +547,11 @@ typedef struct cfear_p2p_result {
   int32_t matched;                      /* source points with a neighbour: keypointRepetability quality_[1] */
   int32_t n_src;                        /* keypointRepetability quality_[2]                             */
   int32_t status;                       /* CFEAR_OK / CFEAR_ERR_EMPTY_CLOUD / CFEAR_ERR_CAPACITY        */
-  int32_t pad;
+  int32_t pad;                          /* diagnostic: CFEAR_CORAL_PATH_* of a served job, 0 otherwise  */
 } cfear_p2p_result;                     /* 32 bytes */
+/* pad, as cfear_coral_result.pad: which path of the grid index over the job's REFERENCE cloud served it (same bits, same
+ * meanings: sorted points in the global scratch, binary-search lookup, sort kind).  The kernel chooses it from the shape of
+ * that cloud; results do not depend on it and callers should not.                                                          */
 
 /* Limits.  One workgroup sorts a reference cloud into a uniform grid of radius * 1.0001 cells over its bounding box and
  * serves every job of the batch that names it (same pointer, same n_ref): the perturbations of a scan pair cost one sort.

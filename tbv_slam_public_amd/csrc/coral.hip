@@ -31,11 +31,6 @@ namespace {
 
 constexpr int kCoralThreads = kGridSortThreads;
 constexpr int kCoralMaxPoints = kGridSortMaxPoints;      // merged points per job
-constexpr int kCoralMaxGridRows = 4096;
-constexpr int kCoralPerThread = kCoralMaxPoints / kCoralThreads;
-constexpr size_t kCoralRowbegOff = (size_t)kCoralMaxPoints * 8 + 16;
-constexpr size_t kCoralSmallOff = (kCoralRowbegOff + (size_t)(kCoralMaxGridRows + 1) * 4 + 15) / 16 * 16;
-constexpr size_t kCoralLdsTotal = kCoralSmallOff + 1024;
 
 // (struct CoralJob: common.hpp -- verify.hip's kernels write job records too)
 
@@ -75,32 +70,7 @@ __device__ __forceinline__ float2 tf_point(const float4 p, const Aff2d& T) {
   return make_float2((float)(((T.l0 * x + T.l1 * y) + 0.0 * z) + T.t0), (float)(((T.l2 * x + T.l3 * y) + 0.0 * z) + T.t1));
 }
 
-__device__ __forceinline__ int lower_bound_u32(const uint32_t* a, int lo, int hi, uint32_t key) {
-  while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] < key) lo = mid + 1; else hi = mid; }
-  return lo;
-}
-__device__ __forceinline__ int upper_bound_u32(const uint32_t* a, int lo, int hi, uint32_t key) {
-  while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] <= key) lo = mid + 1; else hi = mid; }
-  return lo;
-}
-
 struct Moments { int n; double sx, sy, sxx, sxy, syy; };
-// all-reduce over aligned groups of G lanes (G = 4: quad, G = 16: DPP row); every lane ends with the same sum
-template <int G> __device__ __forceinline__ int group_sum_i32(int v) {
-  if (G >= 2) v += __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
-  if (G >= 4) v += __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xf, 0xf, false);   // quad_perm [2,3,0,1]
-  if (G == 16) {
-    v += __builtin_amdgcn_update_dpp(v, v, 0x141, 0xf, 0xf, false);          // row_half_mirror
-    v += __builtin_amdgcn_update_dpp(v, v, 0x140, 0xf, 0xf, false);          // row_mirror
-  }
-  return v;
-}
-template <int G> __device__ __forceinline__ double group_sum_f64(double v) {
-  if (G >= 2) v += dpp_f64<0xB1>(v);
-  if (G >= 4) v += dpp_f64<0x4E>(v);
-  if (G == 16) { v += dpp_f64<0x141>(v); v += dpp_f64<0x140>(v); }
-  return v;
-}
 typedef float v4f __attribute__((ext_vector_type(4)));
 #define CFEAR_LDS __attribute__((address_space(3)))
 
@@ -124,14 +94,11 @@ __device__ __forceinline__ void fail_job(const CoralCommon& cm, int status) {
   }
 }
 
-constexpr int kCoralSweepLanes = 1;                           // lanes per point of the work list in pass B (2: equal, 4: slower)
-
 __global__ __launch_bounds__(kCoralThreads) void coral_kernel(const CoralJob* __restrict__ jobs, const CoralCommon cm) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  float (*red_f)[16] = (float (*)[16])(smem + kCoralSmallOff);          // [4][16]
-  int* red_i = (int*)(smem + kCoralSmallOff + 256);                     // [16]
-  double* red_d = (double*)(smem + kCoralSmallOff + 384);               // [16][3] + counts
-  int* red_c = (int*)(smem + kCoralSmallOff + 384 + 16 * 3 * 8);        // [16]
+  int* red_i = (int*)(smem + kGridSmallOff + 256);                      // [16] (the index builder's; free afterwards)
+  double* red_d = (double*)(smem + kGridSmallOff + 384);                // [16][3] + counts
+  int* red_c = (int*)(smem + kGridSmallOff + 384 + 16 * 3 * 8);         // [16]
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const CoralJob job = jobs[blockIdx.x];
   const int n_src = job.n_src_ptr ? *job.n_src_ptr : job.n_src;
@@ -140,8 +107,8 @@ __global__ __launch_bounds__(kCoralThreads) void coral_kernel(const CoralJob* __
   if (n_src <= 0 || n_ref <= 0) { fail_job(cm, CFEAR_ERR_EMPTY_CLOUD); return; }         // assert(size() > 0) (:118)
   if (n > cm.cap || n > kCoralMaxPoints) { fail_job(cm, CFEAR_ERR_CAPACITY); return; }
   char* scr = cm.scratch + (size_t)blockIdx.x * cm.scratch_stride;
-  float4* spt = (float4*)scr;                                  // sorted merged points (x, y, intensity, original index)
-  double* jres = (double*)(spt + cm.cap);
+  float4* scr_pts = (float4*)scr;                              // the sorted merged points, when they do not fit the LDS
+  double* jres = (double*)(scr_pts + cm.cap);
   double* sres = jres + cm.cap;
   double* wres = sres + cm.cap;
   int32_t* vres = (int32_t*)(wres + cm.cap);
@@ -156,7 +123,9 @@ __global__ __launch_bounds__(kCoralThreads) void coral_kernel(const CoralJob* __
   const Aff2d Tref = aff_xyt(job.ref_pose);
   const Aff2d Tsrc = aff_compose(aff_xyt(job.src_pose), aff_xyt(job.offset));            // src->GetAffine() * Toffset (:101)
   auto point = [&](int i) -> float2 {                          // merged index: source points first (:132, :155)
-    return i < n_src ? tf_point(gload_f4(job.src + i), Tsrc) : tf_point(gload_f4(job.ref + (i - n_src)), Tref);   // (global_load: gload's comment in common.hpp)
+    const bool s = i < n_src;                                  // (the transform selected field by field: both stay in registers)
+    const Aff2d T{s ? Tsrc.l0 : Tref.l0, s ? Tsrc.l1 : Tref.l1, s ? Tsrc.l2 : Tref.l2, s ? Tsrc.l3 : Tref.l3, s ? Tsrc.t0 : Tref.t0, s ? Tsrc.t1 : Tref.t1};
+    return tf_point(gload_f4(s ? job.src + i : job.ref + (i - n_src)), T);   // (global_load: gload's comment in common.hpp)
   };
   // ---- 1. bounding box of the merged cloud ------------------------------------------------------
   float mnx = FLT_MAX, mny = FLT_MAX, mxx = -FLT_MAX, mxy = -FLT_MAX;
@@ -165,21 +134,11 @@ __global__ __launch_bounds__(kCoralThreads) void coral_kernel(const CoralJob* __
     mnx = fminf(mnx, p.x); mxx = fmaxf(mxx, p.x);
     mny = fminf(mny, p.y); mxy = fmaxf(mxy, p.y);
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    mnx = fminf(mnx, __shfl_xor(mnx, o)); mxx = fmaxf(mxx, __shfl_xor(mxx, o));
-    mny = fminf(mny, __shfl_xor(mny, o)); mxy = fmaxf(mxy, __shfl_xor(mxy, o));
-  }
-  if (lane == 0) { red_f[0][wave] = mnx; red_f[1][wave] = mxx; red_f[2][wave] = mny; red_f[3][wave] = mxy; }
-  __syncthreads();
-  mnx = red_f[0][0]; mxx = red_f[1][0]; mny = red_f[2][0]; mxy = red_f[3][0];
-  for (int wv = 1; wv < 16; wv++) {
-    mnx = fminf(mnx, red_f[0][wv]); mxx = fmaxf(mxx, red_f[1][wv]);
-    mny = fminf(mny, red_f[2][wv]); mxy = fmaxf(mxy, red_f[3][wv]);
-  }
+  block_bbox_f32(smem, mnx, mxx, mny, mxy, [] { __syncthreads(); });
   const int min_bx = (int)floorf(mnx * cm.inv_cell), max_bx = (int)floorf(mxx * cm.inv_cell);
   const int min_by = (int)floorf(mny * cm.inv_cell), max_by = (int)floorf(mxy * cm.inv_cell);
   const long long div_bx = (long long)max_bx - min_bx + 1, div_by = (long long)max_by - min_by + 1;
-  if (!(mnx == mnx) || !(mny == mny) || div_bx * div_by > 0x7fffffffLL || div_by > kCoralMaxGridRows) {
+  if (!(mnx == mnx) || !(mny == mny) || div_bx * div_by > 0x7fffffffLL || div_by > kGridMaxRows) {
     fail_job(cm, CFEAR_ERR_CAPACITY);
     return;
   }
@@ -189,118 +148,19 @@ __global__ __launch_bounds__(kCoralThreads) void coral_kernel(const CoralJob* __
     iy = (int)(floorf(p.y * cm.inv_cell) - (float)min_by);
   };
   CORAL_T(1);
-  // ---- 2. sort by (cell, index) ------------------------------------------------------------------
-  unsigned long long* keys = (unsigned long long*)smem;
-  int npad = grid_sort_rows_block(smem, n, dbx, dby, (uint32_t*)(smem + kCoralRowbegOff), red_i, red_c, 512,
-                                  [&](int i, int& ix, int& iy) { cell_xy(point(i), ix, iy); });
-  int path = 0;                                        // cfear_coral_result.pad: CFEAR_CORAL_PATH_* (diagnostic)
-  if (npad == 0) {                                     // crowded grid row or a large cloud: generic block sort
-    int ib, vb;
-    path = grid_sort_is_radix(n, (long long)dbx * dby, ib, vb) ? CFEAR_CORAL_PATH_SORT_RADIX : CFEAR_CORAL_PATH_SORT_BITONIC;
-    npad = grid_sort_block(smem, n, (long long)dbx * dby, red_i, [&](int i) {
-      int ix, iy;
-      cell_xy(point(i), ix, iy);
-      return (uint32_t)(ix + iy * dbx);
-    });
-  }
-  CORAL_T(2);
-  // ---- 3. sorted points -> scratch; cell table (key, start) -> LDS ---------------------------------
-  const int per = npad / kCoralThreads;                 // 1..16 consecutive sorted elements per thread
-  unsigned long long mine[kCoralPerThread];
-  const unsigned prev_cell = (tid * per > 0) ? (unsigned)(keys[tid * per - 1] >> 32) : 0xFFFFFFFFu;
-  int heads = 0;
-#pragma unroll
-  for (int q = 0; q < kCoralPerThread; q++) {
-    const int e = tid * per + q;
-    mine[q] = (q < per && e < n) ? keys[e] : ~0ull;
-  }
-  {
-    unsigned pv = prev_cell;
-#pragma unroll
-    for (int q = 0; q < kCoralPerThread; q++) {
-      const int e = tid * per + q;
-      if (q < per && e < n) {
-        const unsigned vx = (unsigned)(mine[q] >> 32);
-        heads += (e == 0 || vx != pv);
-        pv = vx;
-      }
-    }
-  }
-  const int incl = wave_incl_scan_i32(heads);
-  if (lane == 63) red_i[wave] = incl;
-  __syncthreads();                                      // also: every thread has read its keys
-  int voff = incl - heads;
-  for (int wv = 0; wv < wave; wv++) voff += red_i[wv];
-  int V = 0;
-  for (int wv = 0; wv < 16; wv++) V += red_i[wv];
-  const size_t Vp = ((size_t)V + 4) & ~(size_t)3;
-  uint32_t* cell_key = (uint32_t*)smem;                 // [V]
-  int32_t* cell_start = (int32_t*)(smem + Vp * 4);      // [V + 1]
-  int32_t* rowbeg = (int32_t*)(smem + kCoralRowbegOff); // [dby + 1]
-  // The sorted points follow the cell table in LDS when they fit (the usual case: a few thousand peaks), so the
-  // neighbour sweep of step 4 reads them at LDS latency; larger clouds keep them in the per-job global scratch.
-  const size_t spt_off = (Vp * 4 + ((size_t)V + 1) * 4 + 15) & ~(size_t)15;
-  const bool spt_in_lds = spt_off + (size_t)n * 16 <= kCoralRowbegOff;
-  if (spt_in_lds) spt = (float4*)(smem + spt_off);
-  {
-    unsigned pv = prev_cell;
-    int ord = voff;
-#pragma unroll
-    for (int q = 0; q < kCoralPerThread; q++) {
-      const int e = tid * per + q;
-      if (q < per && e < n) {
-        const unsigned vx = (unsigned)(mine[q] >> 32);
-        const int idx = (int)(unsigned)(mine[q] & 0xFFFFFFFFu);
-        if (e == 0 || vx != pv) { cell_key[ord] = vx; cell_start[ord] = e; ord++; }
-        pv = vx;
+  // ---- 2, 3. the grid index (gridsort.hpp): sort by (cell, index), cell table, sorted points (x, y, intensity, original
+  //      index) in LDS or in the scratch, bitmap or row table.  g.path: cfear_coral_result.pad (diagnostic) -------------
+  const GridIndex g = grid_index_build(
+      smem, n, dbx, dby, scr_pts, [&](int i, int& ix, int& iy) { cell_xy(point(i), ix, iy); },
+      [&](int, int idx) {
         const float2 p = point(idx);
         const float inten = idx < n_src ? gload<float>(&job.src[idx].w) : gload<float>(&job.ref[idx - n_src].w);
-        spt[e] = make_float4(p.x, p.y, inten, __int_as_float(idx));
+        return make_float4(p.x, p.y, inten, __int_as_float(idx));
       }
-    }
-  }
-  if (tid == 0) cell_start[V] = n;
-  __threadfence_block();
-  __syncthreads();
-  // ---- 3b. O(1) cell look-ups: ONE BIT per grid cell + the occupied cells before every 32-cell word (the map
-  //      surface_sort_kernel uses): the points before cell c = cell_start[wpref[c / 32] + popcount(occ[c / 32] below c)] --
-  //      two LDS reads and one dependent read instead of two binary searches over the row's cells (ten dependent reads) per
-  //      grid row and point.  Kept behind the sorted points when it fits the LDS (grids up to ~3 x 10^5 cells for the usual
-  //      peak clouds); otherwise the binary searches below. ---------------------------------------------------------
-  const long long ncells_ll = (long long)dbx * dby;
-  const size_t occ_off = spt_in_lds ? ((spt_off + (size_t)n * 16 + 15) & ~(size_t)15) : spt_off;
-  const long long nw32_ll = (ncells_ll >> 5) + 1;
-  const bool bitmap = occ_off + (size_t)nw32_ll * 6 + 16 <= kCoralRowbegOff;
-  uint32_t* occ = (uint32_t*)(smem + occ_off);
-  const int nw32 = bitmap ? (int)nw32_ll : 0;
-  path |= (spt_in_lds ? 0 : CFEAR_CORAL_PATH_SCRATCH) | (bitmap ? 0 : CFEAR_CORAL_PATH_BSEARCH);
-  unsigned short* wpref = (unsigned short*)(occ + nw32);
-  if (!bitmap) {                                        // first cell of every grid row, for the binary searches
-    for (int y = tid; y <= dby; y += kCoralThreads)
-      rowbeg[y] = lower_bound_u32(cell_key, 0, V, (uint32_t)((long long)y * dbx));
-    __syncthreads();
-  }
-  if (bitmap) {
-    for (int w = tid; w < nw32; w += kCoralThreads) occ[w] = 0u;
-    __syncthreads();
-    for (int o = tid; o < V; o += kCoralThreads) { const uint32_t c = cell_key[o]; atomicOr(&occ[c >> 5], 1u << (c & 31)); }
-    __syncthreads();
-    const int perw = (nw32 + kCoralThreads - 1) / kCoralThreads;
-    const int w0 = min(nw32, tid * perw), w1 = min(nw32, w0 + perw);
-    int to = 0;
-    for (int w = w0; w < w1; w++) to += __popc(occ[w]);
-    const int inclw = wave_incl_scan_i32(to);
-    if (lane == 63) red_c[wave] = inclw;
-    __syncthreads();
-    int runw = inclw - to;
-    for (int wv = 0; wv < wave; wv++) runw += red_c[wv];
-    for (int w = w0; w < w1; w++) { wpref[w] = (unsigned short)runw; runw += __popc(occ[w]); }
-    __syncthreads();
-  }
-  auto pbefore = [&](int c) -> int {                            // points in cells < c, 0 <= c <= ncells
-    const int w = c >> 5;
-    return cell_start[(int)wpref[w] + __popc(occ[w] & ((1u << (c & 31)) - 1u))];
-  };
+#ifdef CFEAR_CORAL_TIMING
+      , &tq[2]
+#endif
+  );
   // the three candidate runs of a query in cell (ix, iy): rows iy - 1 .. iy + 1, columns ix - 1 .. ix + 1 (empty outside the grid)
   auto runs_of = [&](int ix, int iy, int* r0, int* r1) {
     const int x0 = max(ix - 1, 0), x1 = min(ix + 1, dbx - 1);
@@ -309,18 +169,23 @@ __global__ __launch_bounds__(kCoralThreads) void coral_kernel(const CoralJob* __
       const int yy = iy - 1 + d;
       const bool in = yy >= 0 && yy < dby;
       const int cy = in ? yy : 0;
-      const int a = pbefore(cy * dbx + x0), b = pbefore(cy * dbx + x1 + 1);
+      int a, b;
+      g.run(cy, cy * dbx + x0, cy * dbx + x1 + 1, a, b);
       r0[d] = in ? a : 0; r1[d] = in ? b : 0;
     }
   };
   CORAL_T(3);
-  int* n_work = red_i;                                          // LDS counter (red_i is free after the sort)
+  int* n_work = red_i;                                          // LDS counter
   if (tid == 0) *n_work = 0;
   __syncthreads();
+  // ---- 4. moments of the source / reference neighbours of every point -> entropies -----------------------------
+  // Both passes are instantiated per address space of the sorted points (ds_read_b128 when they sit in LDS) and visit the
+  // candidates in one order whatever the lookup, so the fp64 sums do not depend on the path.
   // Pass A (cheap, every point): does the point have ANY neighbour of the other cloud within the radius (overlap_req_ = 1,
   // :138, :160)?  Float distance tests only, first hit ends the search.  Points without one are final (100, 100,
-  // invalid); the others go to a work list.  Pass B (expensive, work list only): fp64 moments and entropies.
-  auto find_overlap_bm = [&](auto* SP) {
+  // invalid); the others go to a work list.  Pass B (expensive, work list only): fp64 moments and entropies -- typically
+  // a quarter to a half of the points, spread evenly over the workgroup.
+  auto find_overlap = [&](auto* SP) {
     for (int e0 = 0; e0 < n; e0 += kCoralThreads) {
       const int e = e0 + tid;
       bool hit = false;
@@ -356,152 +221,16 @@ __global__ __launch_bounds__(kCoralThreads) void coral_kernel(const CoralJob* __
   // Pass B: one lane per point of the work list.  (Lane groups for the heavy neighbourhoods -- sixteen lanes per point with
   // more than 48 candidates, four above 12, DPP all-reduces of the partial moments -- were measured in round 4: the jobs
   // that take 2.5 x the sweep time of the rest are not held up by a few heavy lanes, they simply visit more candidates; the
-  // classification pass cost more than the balance gained: 55 k cycles against 50 k per job.)
-  auto sweep_bm = [&](auto* SP, const int W) {
-    const int* work2 = work;
-    const int n16 = 0, n4 = 0;
-    auto tier = [&](auto g_tag, const int lbeg, const int lend) {
-      constexpr int G = decltype(g_tag)::value;
-      const int sub = tid & (G - 1);
-      for (int k0 = lbeg; k0 < lend; k0 += kCoralThreads / G) {
-        const int k = k0 + tid / G;
-        const bool act = k < lend;                               // (whole groups stay in the loop for the DPP sums)
-        const int e = act ? gload<int32_t>(work2 + k) : 0;
-        const v4f q = SP[e];
-        const int idx = __float_as_int(q.w);
-        const bool q_is_src = idx < n_src;
-        int ix, iy, r0[3], r1[3];
-        cell_xy(make_float2(q.x, q.y), ix, iy);
-        runs_of(ix, iy, r0, r1);
-        Moments ms{0, 0, 0, 0, 0, 0}, mr{0, 0, 0, 0, 0, 0};
-        const double qx = (double)q.x, qy = (double)q.y;
-        auto visit = [&](const v4f c) {
-          const float dxf = __fsub_rn(q.x, c.x), dyf = __fsub_rn(q.y, c.y);
-          const float d2 = __fadd_rn(__fmul_rn(dxf, dxf), __fmul_rn(dyf, dyf));  // FLANN L2_Simple
-          if (d2 < cm.r2) {                                                       // RadiusResultSet: strict <
-            const double dx = (double)c.x - qx, dy = (double)c.y - qy;
-            if (__float_as_int(c.w) < n_src) {
-              ms.n++; ms.sx += dx; ms.sy += dy; ms.sxx += dx * dx; ms.sxy += dx * dy; ms.syy += dy * dy;
-            } else {
-              mr.n++; mr.sx += dx; mr.sy += dy; mr.sxx += dx * dx; mr.sxy += dx * dy; mr.syy += dy * dy;
-            }
-          }
-        };
-        if (act) {                                               // the three runs as ONE sequence, two loads in flight
-          const int n0 = r1[0] - r0[0], n01 = n0 + (r1[1] - r0[1]), C = n01 + (r1[2] - r0[2]);
-          auto at = [&](int j) { return j < n0 ? r0[0] + j : (j < n01 ? r0[1] + (j - n0) : r0[2] + (j - n01)); };
-          for (int j = sub; j < C; j += 2 * G) {
-            const bool two = j + G < C;
-            const v4f c0 = SP[at(j)], c1 = SP[at(two ? j + G : j)];
-            visit(c0);
-            if (two) visit(c1);
-          }
-        }
-        if (G > 1) {
-          ms.n = group_sum_i32<G>(ms.n); mr.n = group_sum_i32<G>(mr.n);
-          ms.sx = group_sum_f64<G>(ms.sx); ms.sy = group_sum_f64<G>(ms.sy); ms.sxx = group_sum_f64<G>(ms.sxx);
-          ms.sxy = group_sum_f64<G>(ms.sxy); ms.syy = group_sum_f64<G>(ms.syy);
-          mr.sx = group_sum_f64<G>(mr.sx); mr.sy = group_sum_f64<G>(mr.sy); mr.sxx = group_sum_f64<G>(mr.sxx);
-          mr.sxy = group_sum_f64<G>(mr.sxy); mr.syy = group_sum_f64<G>(mr.syy);
-        }
-        if (act && sub == 0) {
-          double jr = 100.0, sr = 100.0, w = 0.0;
-          int valid = 0;
-          const Moments& own = q_is_src ? ms : mr;
-          const Moments& other = q_is_src ? mr : ms;
-          if (other.n >= 1) {                                                         // overlap_req_ = 1 (:138, :160)
-            const Moments mj{ms.n + mr.n, ms.sx + mr.sx, ms.sy + mr.sy, ms.sxx + mr.sxx, ms.sxy + mr.sxy, ms.syy + mr.syy};
-            double s00, s01, s11, j00, j01, j11;
-            if (cov_from_moments(own, s00, s01, s11) && cov_from_moments(mj, j00, j01, j11)) {
-              const double det_j = j00 * j11 - j01 * j01;                             // ComputeEntropy (:80-98)
-              const double det_s = s00 * s11 - s01 * s01;
-              if (!(isnan(det_s) || isnan(det_j))) {
-                const double sep_entropy = 1.0 / 2.0 * log(2.0 * M_PI * exp(1.0) * det_s + 0.00000001);
-                const double joint_entropy = 1.0 / 2.0 * log(2.0 * M_PI * exp(1.0) * det_j + 0.00000001);
-                if (!(isnan(sep_entropy) || isnan(joint_entropy))) {
-                  w = cm.weight_res_intensity ? (double)q.z : 1.0;                    // :180
-                  jr = w * joint_entropy; sr = w * sep_entropy; valid = 1;
-                }
-              }
-            }
-          }
-          gstore<double>(jres + idx, jr); gstore<double>(sres + idx, sr); gstore<double>(wres + idx, valid ? w : 0.0); gstore<int32_t>(vres + idx, valid);
-        }
-      }
-    };
-    (void)n16;
-    tier(std::integral_constant<int, kCoralSweepLanes>{}, n4, W);
-  };
-  if (bitmap) {
-    if (spt_in_lds) find_overlap_bm((CFEAR_LDS const v4f*)spt);
-    else find_overlap_bm((const v4f*)spt);
-    __threadfence_block();
-    __syncthreads();
-    const int Wb = *n_work;
-    CORAL_T(4);
-    __syncthreads();                                            // (red_c / red_i are reused by the sweep's counters)
-    if (spt_in_lds) sweep_bm((CFEAR_LDS const v4f*)spt, Wb);
-    else sweep_bm((const v4f*)spt, Wb);
-  } else {
-  // ---- 4. moments of the source / reference neighbours of every point -> entropies -----------------------------
-  // Instantiated per address space of the sorted points (ds_read_b128 when they sit in LDS); candidates are fetched
-  // two at a time so the second load is in flight while the first is tested.
-  // Pass A (cheap, every point): does the point have ANY neighbour of the other cloud within the radius
-  // (overlap_req_ = 1, :138, :160)?  Float distance tests only, first hit ends the search.  Points without one are
-  // final (100, 100, invalid); the others go to a work list.  Pass B (expensive, work list only): fp64 moments and
-  // entropies -- typically a quarter to a half of the points, spread evenly over the workgroup.
-  auto find_overlap = [&](auto* SP) {
-    for (int e0 = 0; e0 < n; e0 += kCoralThreads) {
-      const int e = e0 + tid;
-      bool hit = false;
-      if (e < n) {
-        const v4f q = SP[e];
-        const int idx = __float_as_int(q.w);
-        const bool q_is_src = idx < n_src;
-        int ix, iy;
-        cell_xy(make_float2(q.x, q.y), ix, iy);
-        const int x0 = max(ix - 1, 0), x1 = min(ix + 1, dbx - 1);
-        for (int yy = max(iy - 1, 0); yy <= min(iy + 1, dby - 1) && !hit; yy++) {
-          const uint32_t klo = (uint32_t)(yy * dbx + x0), khi = (uint32_t)(yy * dbx + x1);
-          const int a = lower_bound_u32(cell_key, rowbeg[yy], rowbeg[yy + 1], klo);
-          const int b = upper_bound_u32(cell_key, rowbeg[yy], rowbeg[yy + 1], khi);
-          const int p1 = cell_start[b];
-          auto test = [&](const v4f c) {
-            const float dxf = __fsub_rn(q.x, c.x), dyf = __fsub_rn(q.y, c.y);
-            const float d2 = __fadd_rn(__fmul_rn(dxf, dxf), __fmul_rn(dyf, dyf));
-            return (d2 < cm.r2) && ((__float_as_int(c.w) < n_src) != q_is_src);
-          };
-          int p = cell_start[a];
-          for (; p + 3 < p1 && !hit; p += 4) {                  // four independent loads per exit test
-            const v4f c0 = SP[p], c1 = SP[p + 1], c2 = SP[p + 2], c3 = SP[p + 3];
-            hit = ((int)test(c0) | (int)test(c1) | (int)test(c2) | (int)test(c3)) != 0;
-          }
-          for (; p < p1 && !hit; p++) hit = test(SP[p]);
-        }
-        if (!hit) { jres[idx] = 100.0; sres[idx] = 100.0; wres[idx] = 0.0; vres[idx] = 0; }
-      }
-      const unsigned long long m = __ballot(hit);                // wave-aggregated append
-      int base = 0;
-      if (lane == 0 && m) base = atomicAdd(n_work, __popcll(m));
-      base = __shfl(base, 0);
-      if (hit) work[base + __popcll(m & ((1ull << lane) - 1ull))] = e;
-    }
-  };
-  if (spt_in_lds) find_overlap((CFEAR_LDS const v4f*)spt);
-  else find_overlap((const v4f*)spt);
-  __threadfence_block();
-  __syncthreads();
-  const int W = *n_work;
-  CORAL_T(4);
-  auto sweep = [&](auto* SP) {
+  // classification pass cost more than the balance gained: 55 k cycles against 50 k per job.  Two lanes per point: equal.)
+  auto sweep = [&](auto* SP, const int W) {
     for (int k = tid; k < W; k += kCoralThreads) {
-      const int e = work[k];
+      const int e = gload<int32_t>(work + k);
       const v4f q = SP[e];
       const int idx = __float_as_int(q.w);
       const bool q_is_src = idx < n_src;
-      int ix, iy;
+      int ix, iy, r0[3], r1[3];
       cell_xy(make_float2(q.x, q.y), ix, iy);
-      const int x0 = max(ix - 1, 0), x1 = min(ix + 1, dbx - 1);
+      runs_of(ix, iy, r0, r1);
       Moments ms{0, 0, 0, 0, 0, 0}, mr{0, 0, 0, 0, 0, 0};
       const double qx = (double)q.x, qy = (double)q.y;
       auto visit = [&](const v4f c) {
@@ -516,18 +245,15 @@ __global__ __launch_bounds__(kCoralThreads) void coral_kernel(const CoralJob* __
           }
         }
       };
-      for (int yy = max(iy - 1, 0); yy <= min(iy + 1, dby - 1); yy++) {
-        const uint32_t klo = (uint32_t)(yy * dbx + x0), khi = (uint32_t)(yy * dbx + x1);
-        const int a = lower_bound_u32(cell_key, rowbeg[yy], rowbeg[yy + 1], klo);
-        const int b = upper_bound_u32(cell_key, rowbeg[yy], rowbeg[yy + 1], khi);
-        const int p1 = cell_start[b];
-        int p = cell_start[a];
-        for (; p + 1 < p1; p += 2) {
-          const v4f c0 = SP[p], c1 = SP[p + 1];
+      {                                                          // the three runs as ONE sequence, rows in order, two loads in flight
+        const int n0 = r1[0] - r0[0], n01 = n0 + (r1[1] - r0[1]), C = n01 + (r1[2] - r0[2]);
+        auto at = [&](int j) { return j < n0 ? r0[0] + j : (j < n01 ? r0[1] + (j - n0) : r0[2] + (j - n01)); };
+        for (int j = 0; j < C; j += 2) {
+          const bool two = j + 1 < C;
+          const v4f c0 = SP[at(j)], c1 = SP[at(two ? j + 1 : j)];
           visit(c0);
-          visit(c1);
+          if (two) visit(c1);
         }
-        if (p < p1) visit(SP[p]);
       }
       double jr = 100.0, sr = 100.0, w = 0.0;
       int valid = 0;
@@ -549,12 +275,17 @@ __global__ __launch_bounds__(kCoralThreads) void coral_kernel(const CoralJob* __
           }
         }
       }
-      jres[idx] = jr; sres[idx] = sr; wres[idx] = valid ? w : 0.0; vres[idx] = valid;
+      gstore<double>(jres + idx, jr); gstore<double>(sres + idx, sr); gstore<double>(wres + idx, valid ? w : 0.0); gstore<int32_t>(vres + idx, valid);
     }
   };
-  if (spt_in_lds) sweep((CFEAR_LDS const v4f*)spt);
-  else sweep((const v4f*)spt);
-  }
+  if (g.spt_in_lds) find_overlap((CFEAR_LDS const v4f*)g.spt);
+  else find_overlap((const v4f*)g.spt);
+  __threadfence_block();
+  __syncthreads();
+  const int W = *n_work;
+  CORAL_T(4);
+  if (g.spt_in_lds) sweep((CFEAR_LDS const v4f*)g.spt, W);
+  else sweep((const v4f*)g.spt, W);
   __threadfence_block();
   __syncthreads();
   CORAL_T(5);
@@ -578,7 +309,7 @@ __global__ __launch_bounds__(kCoralThreads) void coral_kernel(const CoralJob* __
       cfear_coral_result& r = cm.results[blockIdx.x];
       r.joint = joint; r.sep = sep; r.overlap = overlap;                        // quality_ = {joint_, sep_, overlap_}
       r.valid = overlap < 0.1 ? 0 : 1;                                          // :197-204
-      r.count_valid = count_valid; r.status = CFEAR_OK; r.pad = path;
+      r.count_valid = count_valid; r.status = CFEAR_OK; r.pad = g.path;
     }
   }
 #ifdef CFEAR_CORAL_TIMING
@@ -597,32 +328,41 @@ __global__ __launch_bounds__(kCoralThreads) void coral_kernel(const CoralJob* __
 
 int cfear_coral_max_points() { return kCoralMaxPoints; }
 
+// The launch both entry points share: the kernel's constants, the per-job scratch (bounded to 1 GiB per launch, so a large
+// batch takes several launches) and the LDS allowance.  d_per_point: nullable, [n_jobs][cap][3].
+static int coral_launch(cfear_ctx* ctx, const CoralJob* d_jobs, int n_jobs, int cap, const cfear_coral_params* par,
+                        cfear_coral_result* d_results, double* d_per_point) {
+  CoralCommon cm;
+  cm.radius = par->radius;
+  cm.r2 = (float)(par->radius * par->radius);            // radiusSearch passes float(radius * radius) to FLANN
+  cm.inv_cell = (float)(1.0 / (par->radius * 1.0001));   // cell a hair wider than the radius: float rounding of
+                                                         // x * inv_cell can never put a neighbour two cells away
+  cm.weight_res_intensity = par->weight_res_intensity;
+  cm.cap = std::max(cap, 1);
+  cm.scratch_stride = coral_scratch_bytes(cm.cap);
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_jobs, ((size_t)1 << 30) / cm.scratch_stride));
+  cm.scratch = (char*)cfear_workspace(ctx, kWsCoralScratch, cm.scratch_stride * (size_t)chunk);
+  if (!cm.scratch) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
+  CFEAR_CHECK(cfear_allow_lds(ctx, (const void*)coral_kernel, kGridLdsTotal));
+  {
+    ProfScope ps(ctx, "coral_quality");
+    for (int j0 = 0; j0 < n_jobs; j0 += chunk) {
+      const int nj = std::min(chunk, n_jobs - j0);
+      cm.results = d_results + j0;
+      cm.per_point = d_per_point ? d_per_point + (size_t)j0 * cm.cap * 3 : nullptr;
+      hipLaunchKernelGGL(coral_kernel, dim3(nj), dim3(kCoralThreads), kGridLdsTotal, ctx->stream, d_jobs + j0, cm);
+    }
+  }
+  CFEAR_HIP_CHECK(ctx, hipGetLastError());
+  return CFEAR_OK;
+}
+
 int cfear_coral_launch_device(cfear_ctx* ctx, const CoralJob* d_jobs, int n_jobs, int cap, const cfear_coral_params* par,
                               cfear_coral_result* d_results) {
   if (!(par->radius > 0.0)) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "radius must be > 0");
   if (n_jobs <= 0) return CFEAR_OK;
   if (cap > kCoralMaxPoints) return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "a job's %d points exceed %d", cap, kCoralMaxPoints);
-  CoralCommon cm;
-  cm.radius = par->radius;
-  cm.r2 = (float)(par->radius * par->radius);            // radiusSearch passes float(radius * radius) to FLANN
-  cm.inv_cell = (float)(1.0 / (par->radius * 1.0001));
-  cm.weight_res_intensity = par->weight_res_intensity;
-  cm.cap = std::max(cap, 1);
-  cm.scratch_stride = coral_scratch_bytes(cm.cap);
-  cm.per_point = nullptr;
-  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_jobs, ((size_t)1 << 30) / cm.scratch_stride));
-  char* scr = (char*)cfear_workspace(ctx, kWsCoralScratch, cm.scratch_stride * (size_t)chunk);
-  if (!scr) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-  cm.scratch = scr;
-  { const int rc_lds = cfear_allow_lds(ctx, (const void*)coral_kernel, 160 * 1024); if (rc_lds != CFEAR_OK) return rc_lds; }
-  ProfScope ps(ctx, "coral_quality");
-  for (int j0 = 0; j0 < n_jobs; j0 += chunk) {
-    const int nj = std::min(chunk, n_jobs - j0);
-    cm.results = d_results + j0;
-    hipLaunchKernelGGL(coral_kernel, dim3(nj), dim3(kCoralThreads), kCoralLdsTotal, ctx->stream, d_jobs + j0, cm);
-  }
-  CFEAR_HIP_CHECK(ctx, hipGetLastError());
-  return CFEAR_OK;
+  return coral_launch(ctx, d_jobs, n_jobs, cap, par, d_results, nullptr);
 }
 
 extern "C" void cfear_coral_params_default(cfear_coral_params* p) {
@@ -655,16 +395,6 @@ int cfear_coral_enqueue(cfear_ctx* ctx, const cfear_coral_job* jobs, int32_t n_j
     st.cloud_in(jb.ref_xyzi, jb.n_ref);
     st.cloud_in(jb.src_xyzi, jb.n_src);
   }
-  CoralCommon cm;
-  cm.radius = par->radius;
-  cm.r2 = (float)(par->radius * par->radius);            // radiusSearch passes float(radius * radius) to FLANN
-  cm.inv_cell = (float)(1.0 / (par->radius * 1.0001));   // cell a hair wider than the radius: float rounding of
-                                                         // x * inv_cell can never put a neighbour two cells away
-  cm.weight_res_intensity = par->weight_res_intensity;
-  cm.cap = cap;
-  cm.scratch_stride = coral_scratch_bytes(cap);
-  // scratch bounded to 1 GiB per launch
-  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_jobs, ((size_t)1 << 30) / cm.scratch_stride));
   const size_t jb_bytes = (size_t)n_jobs * sizeof(CoralJob);
   CoralJob* d_jobs;
   cfear_coral_result* d_res;
@@ -672,8 +402,6 @@ int cfear_coral_enqueue(cfear_ctx* ctx, const cfear_coral_job* jobs, int32_t n_j
   st.piece(d_jobs, jb_bytes);
   st.piece(d_res, (size_t)n_jobs * sizeof(cfear_coral_result));
   if (want_per_point) st.piece(d_pp, (size_t)n_jobs * cap * 3 * sizeof(double));
-  char* scr = (char*)cfear_workspace(ctx, kWsCoralScratch, cm.scratch_stride * (size_t)chunk);
-  if (!scr) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
   CFEAR_CHECK(st.carve());
   CoralJob* hj = (CoralJob*)st.record(jb_bytes);
   for (int j = 0; j < n_jobs; j++) {
@@ -685,19 +413,8 @@ int cfear_coral_enqueue(cfear_ctx* ctx, const cfear_coral_job* jobs, int32_t n_j
     o.n_ref = jb.n_ref; o.n_src = jb.n_src;
     for (int k = 0; k < 3; k++) { o.ref_pose[k] = jb.ref_pose[k]; o.src_pose[k] = jb.src_pose[k]; o.offset[k] = jb.offset[k]; }
   }
-  cm.scratch = scr;
   CFEAR_CHECK(st.upload(d_jobs, hj, jb_bytes));
-  { const int rc_lds = cfear_allow_lds(ctx, (const void*)coral_kernel, 160 * 1024); if (rc_lds != CFEAR_OK) return rc_lds; }
-  {
-    ProfScope ps(ctx, "coral_quality");
-    for (int j0 = 0; j0 < n_jobs; j0 += chunk) {
-      const int nj = std::min(chunk, n_jobs - j0);
-      cm.results = d_res + j0;
-      cm.per_point = d_pp ? d_pp + (size_t)j0 * cap * 3 : nullptr;
-      hipLaunchKernelGGL(coral_kernel, dim3(nj), dim3(kCoralThreads), kCoralLdsTotal, ctx->stream, d_jobs + j0, cm);
-    }
-  }
-  CFEAR_HIP_CHECK(ctx, hipGetLastError());
+  CFEAR_CHECK(coral_launch(ctx, d_jobs, n_jobs, cap, par, d_res, d_pp));
   pend.n_jobs = n_jobs; pend.cap = cap; pend.d_res = d_res; pend.d_pp = d_pp;
   return CFEAR_OK;
 }

@@ -1,5 +1,6 @@
 // gridsort.hpp -- block-wide LDS sort of (grid cell, point index) pairs, shared by the kernels that
-// replace a PCL voxel grid / kd-tree radius search with a sort-based uniform grid (surface.hip, coral.hip).
+// replace a PCL voxel grid / kd-tree radius search with a sort-based uniform grid (surface.hip, coral.hip, p2p.hip),
+// and the neighbour index coral.hip and p2p.hip build from the sorted keys (GridIndex, at the end).
 #pragma once
 #include "common.hpp"
 
@@ -190,5 +191,195 @@ __device__ int grid_sort_block(uint8_t* smem, int n, long long n_cells, int* red
     }
   }
   return npad;
+}
+
+__device__ __forceinline__ int lower_bound_u32(const uint32_t* a, int lo, int hi, uint32_t key) {
+  while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] < key) lo = mid + 1; else hi = mid; }
+  return lo;
+}
+__device__ __forceinline__ int upper_bound_u32(const uint32_t* a, int lo, int hi, uint32_t key) {
+  while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] <= key) lo = mid + 1; else hi = mid; }
+  return lo;
+}
+
+// ---- The grid index of coral.hip and p2p.hip: what replaces a FLANN radius search over one cloud. -----------------------
+// One 1024-thread workgroup sorts n <= 16384 points by (cell, index) and keeps, in its dynamic LDS:
+//   [0, kGridRowbegOff)   the sort's keys, afterwards: cell_key [V] | cell_start [V + 1] | the sorted points (float4 [n],
+//                         when they fit; else in the caller's global scratch) | occ, wpref (when they fit)
+//   kGridRowbegOff        rowbeg [dby + 1]: the row sort's counters, afterwards the first occupied cell of every grid row
+//                         (only without the bitmap)
+//   kGridSmallOff         1 KiB of small reductions: float [4][16] (block_bbox_f32), int [16] at + 256 and + 320 (the sort
+//                         and the builder; free once the index is built); the caller's own start at + 384
+constexpr int kGridMaxRows = 4096;
+constexpr int kGridPerThread = kGridSortMaxPoints / kGridSortThreads;
+constexpr size_t kGridRowbegOff = (size_t)kGridSortMaxPoints * 8 + 16;
+constexpr size_t kGridSmallOff = (kGridRowbegOff + (size_t)(kGridMaxRows + 1) * 4 + 15) / 16 * 16;
+constexpr size_t kGridLdsTotal = kGridSmallOff + 1024;
+
+// The bounding box of the workgroup's points from every thread's own minima and maxima: wave shuffles, 16 partials in
+// LDS, then every thread reads them.  `barrier` is the one block barrier in between (__syncthreads, or a vote of the
+// caller's that is one).
+template <typename Barrier>
+__device__ __forceinline__ void block_bbox_f32(uint8_t* smem, float& mnx, float& mxx, float& mny, float& mxy, Barrier barrier) {
+  float (*red_f)[16] = (float (*)[16])(smem + kGridSmallOff);          // [4][16]
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int o = 32; o > 0; o >>= 1) {
+    mnx = fminf(mnx, __shfl_xor(mnx, o)); mxx = fmaxf(mxx, __shfl_xor(mxx, o));
+    mny = fminf(mny, __shfl_xor(mny, o)); mxy = fmaxf(mxy, __shfl_xor(mxy, o));
+  }
+  if (lane == 0) { red_f[0][wave] = mnx; red_f[1][wave] = mxx; red_f[2][wave] = mny; red_f[3][wave] = mxy; }
+  barrier();
+  mnx = red_f[0][0]; mxx = red_f[1][0]; mny = red_f[2][0]; mxy = red_f[3][0];
+  for (int wv = 1; wv < 16; wv++) {
+    mnx = fminf(mnx, red_f[0][wv]); mxx = fmaxf(mxx, red_f[1][wv]);
+    mny = fminf(mny, red_f[2][wv]); mxy = fmaxf(mxy, red_f[3][wv]);
+  }
+}
+
+struct GridIndex {
+  int V, dbx, dby;                      // occupied cells; grid columns and rows
+  int path;                             // CFEAR_CORAL_PATH_* (cfear_hip.h): which sort, home of the points and lookup
+  bool spt_in_lds, bitmap;
+  float4* spt;                          // the sorted points: LDS (spt_in_lds) or the caller's scratch
+  const uint32_t* cell_key;             // [V] occupied cells, ascending
+  const int32_t* cell_start;            // [V + 1] first sorted point of every occupied cell; [V] = n
+  const int32_t* rowbeg;                // [dby + 1], without the bitmap
+  const uint32_t* occ;                  // one bit per grid cell, with the bitmap
+  const unsigned short* wpref;          // occupied cells before every 32-cell word of occ
+  // [a, b): the sorted points in the cells [c0, c1) of grid row y (c0 <= c1, both inside the row or at its end).  With
+  // the bitmap: points before cell c = cell_start[wpref[c / 32] + popcount(occ[c / 32] below c)], two LDS reads and one
+  // dependent read; without: two binary searches over the row's occupied cells.
+  __device__ __forceinline__ void run(int y, int c0, int c1, int& a, int& b) const {
+    if (bitmap) {
+      const int w0 = c0 >> 5, w1 = c1 >> 5;
+      a = cell_start[(int)wpref[w0] + __popc(occ[w0] & ((1u << (c0 & 31)) - 1u))];
+      b = cell_start[(int)wpref[w1] + __popc(occ[w1] & ((1u << (c1 & 31)) - 1u))];
+    } else {
+      a = cell_start[lower_bound_u32(cell_key, rowbeg[y], rowbeg[y + 1], (uint32_t)c0)];
+      b = cell_start[lower_bound_u32(cell_key, rowbeg[y], rowbeg[y + 1], (uint32_t)c1)];
+    }
+  }
+};
+
+// Builds the index over n points in a dbx x dby grid (dby <= kGridMaxRows, dbx * dby < 2^31).  cell_xy(i, ix, iy) ->
+// column / row of point i; emit(e, idx) -> the float4 stored at sorted position e for point idx; scratch: room for n
+// float4 in global memory, used when the sorted points do not fit the LDS (may be null where the caller knows they do).
+// t_sorted: optional, receives the cycle counter after the sort (a caller's phase timing).  Block-wide collective; on return
+// the index is visible to every thread.
+template <typename CellXY, typename Emit>
+__device__ __forceinline__ GridIndex grid_index_build(uint8_t* smem, int n, int dbx, int dby, float4* scratch, CellXY cell_xy, Emit emit,
+                                                      long long* t_sorted = nullptr) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  int* red_i = (int*)(smem + kGridSmallOff + 256);                      // [16]
+  int* red_c = (int*)(smem + kGridSmallOff + 320);                      // [16]
+  GridIndex g;
+  g.dbx = dbx; g.dby = dby;
+  // ---- sort by (cell, index) ---------------------------------------------------------------------------------------
+  unsigned long long* keys = (unsigned long long*)smem;
+  int npad = grid_sort_rows_block(smem, n, dbx, dby, (uint32_t*)(smem + kGridRowbegOff), red_i, red_c, 512, cell_xy);
+  int path = 0;
+  if (npad == 0) {                                     // crowded grid row or a large cloud: generic block sort
+    int ib, vb;
+    path = grid_sort_is_radix(n, (long long)dbx * dby, ib, vb) ? CFEAR_CORAL_PATH_SORT_RADIX : CFEAR_CORAL_PATH_SORT_BITONIC;
+    npad = grid_sort_block(smem, n, (long long)dbx * dby, red_i, [&](int i) {
+      int ix, iy;
+      cell_xy(i, ix, iy);
+      return (uint32_t)(ix + iy * dbx);
+    });
+  }
+  if (t_sorted) *t_sorted = __builtin_readcyclecounter();
+  // ---- cell table (key, start) -> LDS; sorted points -> LDS or scratch -----------------------------------------------
+  const int per = npad / kGridSortThreads;              // 1..16 consecutive sorted elements per thread
+  unsigned long long mine[kGridPerThread];
+  const unsigned prev_cell = (tid * per > 0) ? (unsigned)(keys[tid * per - 1] >> 32) : 0xFFFFFFFFu;
+  int heads = 0;
+#pragma unroll
+  for (int q = 0; q < kGridPerThread; q++) {
+    const int e = tid * per + q;
+    mine[q] = (q < per && e < n) ? keys[e] : ~0ull;
+  }
+  {
+    unsigned pv = prev_cell;
+#pragma unroll
+    for (int q = 0; q < kGridPerThread; q++) {
+      const int e = tid * per + q;
+      if (q < per && e < n) {
+        const unsigned vx = (unsigned)(mine[q] >> 32);
+        heads += (e == 0 || vx != pv);
+        pv = vx;
+      }
+    }
+  }
+  const int incl = wave_incl_scan_i32(heads);
+  if (lane == 63) red_i[wave] = incl;
+  __syncthreads();                                      // also: every thread has read its keys
+  int voff = incl - heads;
+  for (int wv = 0; wv < wave; wv++) voff += red_i[wv];
+  int V = 0;
+  for (int wv = 0; wv < 16; wv++) V += red_i[wv];
+  const size_t Vp = ((size_t)V + 4) & ~(size_t)3;
+  uint32_t* cell_key = (uint32_t*)smem;                 // [V]
+  int32_t* cell_start = (int32_t*)(smem + Vp * 4);      // [V + 1]
+  int32_t* rowbeg = (int32_t*)(smem + kGridRowbegOff);  // [dby + 1]
+  // The sorted points follow the cell table in LDS when they fit (the usual case: a few thousand peaks), so the
+  // neighbour sweep reads them at LDS latency; larger clouds keep them in the global scratch.
+  const size_t spt_off = (Vp * 4 + ((size_t)V + 1) * 4 + 15) & ~(size_t)15;
+  const bool spt_in_lds = spt_off + (size_t)n * 16 <= kGridRowbegOff;
+  float4* spt = spt_in_lds ? (float4*)(smem + spt_off) : scratch;
+  {
+    unsigned pv = prev_cell;
+    int ord = voff;
+#pragma unroll
+    for (int q = 0; q < kGridPerThread; q++) {
+      const int e = tid * per + q;
+      if (q < per && e < n) {
+        const unsigned vx = (unsigned)(mine[q] >> 32);
+        const int idx = (int)(unsigned)(mine[q] & 0xFFFFFFFFu);
+        if (e == 0 || vx != pv) { cell_key[ord] = vx; cell_start[ord] = e; ord++; }
+        pv = vx;
+        spt[e] = emit(e, idx);
+      }
+    }
+  }
+  if (tid == 0) cell_start[V] = n;
+  __threadfence_block();
+  __syncthreads();
+  // ---- O(1) cell look-ups: ONE BIT per grid cell + the occupied cells before every 32-cell word (the map
+  //      surface_sort_kernel uses), instead of two binary searches over the row's cells (ten dependent reads) per grid row
+  //      and point.  Kept behind the sorted points when it fits the LDS (grids up to ~3 x 10^5 cells for the usual peak
+  //      clouds); otherwise the first occupied cell of every grid row, for the binary searches. ------------------------
+  const long long ncells_ll = (long long)dbx * dby;
+  const size_t occ_off = spt_in_lds ? ((spt_off + (size_t)n * 16 + 15) & ~(size_t)15) : spt_off;
+  const long long nw32_ll = (ncells_ll >> 5) + 1;
+  const bool bitmap = occ_off + (size_t)nw32_ll * 6 + 16 <= kGridRowbegOff;
+  uint32_t* occ = (uint32_t*)(smem + occ_off);
+  const int nw32 = bitmap ? (int)nw32_ll : 0;
+  unsigned short* wpref = (unsigned short*)(occ + nw32);
+  if (!bitmap) {
+    for (int y = tid; y <= dby; y += kGridSortThreads)
+      rowbeg[y] = lower_bound_u32(cell_key, 0, V, (uint32_t)((long long)y * dbx));
+    __syncthreads();
+  } else {
+    for (int w = tid; w < nw32; w += kGridSortThreads) occ[w] = 0u;
+    __syncthreads();
+    for (int o = tid; o < V; o += kGridSortThreads) { const uint32_t c = cell_key[o]; atomicOr(&occ[c >> 5], 1u << (c & 31)); }
+    __syncthreads();
+    const int perw = (nw32 + kGridSortThreads - 1) / kGridSortThreads;
+    const int w0 = min(nw32, tid * perw), w1 = min(nw32, w0 + perw);
+    int to = 0;
+    for (int w = w0; w < w1; w++) to += __popc(occ[w]);
+    const int inclw = wave_incl_scan_i32(to);
+    if (lane == 63) red_c[wave] = inclw;
+    __syncthreads();
+    int runw = inclw - to;
+    for (int wv = 0; wv < wave; wv++) runw += red_c[wv];
+    for (int w = w0; w < w1; w++) { wpref[w] = (unsigned short)runw; runw += __popc(occ[w]); }
+    __syncthreads();
+  }
+  g.V = V;
+  g.path = path | (spt_in_lds ? 0 : CFEAR_CORAL_PATH_SCRATCH) | (bitmap ? 0 : CFEAR_CORAL_PATH_BSEARCH);
+  g.spt_in_lds = spt_in_lds; g.bitmap = bitmap; g.spt = spt;
+  g.cell_key = cell_key; g.cell_start = cell_start; g.rowbeg = rowbeg; g.occ = occ; g.wpref = wpref;
+  return g;
 }
 #endif

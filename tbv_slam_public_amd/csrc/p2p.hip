@@ -7,8 +7,8 @@
 //   GetQualityMeasure: mean over residuals_, which starts as {0, 0, 0}              :235-248, AlignmentQuality.h:92
 //
 // Kernel design: ONE persistent 1024-thread workgroup per reference cloud.  It sorts the cloud once into a uniform grid
-// of radius * 1.0001 cells over its bounding box (gridsort.hpp; the layout of coral.hip: cell table, sorted points and an
-// occupancy bitmap in LDS) and then serves every job that names the cloud -- the perturbations of a scan pair share
+// of radius * 1.0001 cells over its bounding box (gridsort.hpp's GridIndex, which coral.hip uses too: cell table, sorted points
+// and an occupancy bitmap in LDS) and then serves every job that names the cloud -- the perturbations of a scan pair share
 // both clouds, so the sort is paid once per pair.  Per job each lane takes one source point, transforms it
 // (pcl::transformPointCloud's rounding), and takes the float minimum of FLANN's L2_Simple distance over the cells the
 // ball can reach.  The cells are found from the interval [q - r_up, q + r_up] itself, not from "the 3 x 3 block": the cell
@@ -30,12 +30,7 @@ namespace {
 constexpr int kP2pThreads = kGridSortThreads;
 constexpr int kP2pMaxRef = kGridSortMaxPoints;           // CFEAR_P2P_MAX_REF_POINTS
 constexpr int kP2pMaxSrc = 1 << 20;                      // CFEAR_P2P_MAX_SRC_POINTS
-constexpr int kP2pMaxGridRows = 4096;
 constexpr float kP2pMaxCellIndex = 4194304.0f;           // |floorf(v * inv_cell)| below 2^22: exact in float, safe as int
-constexpr int kP2pPerThread = kP2pMaxRef / kP2pThreads;
-constexpr size_t kP2pRowbegOff = (size_t)kP2pMaxRef * 8 + 16;
-constexpr size_t kP2pSmallOff = (kP2pRowbegOff + (size_t)(kP2pMaxGridRows + 1) * 4 + 15) / 16 * 16;
-constexpr size_t kP2pLdsTotal = kP2pSmallOff + 1024;
 static_assert(kP2pMaxRef == CFEAR_P2P_MAX_REF_POINTS && kP2pMaxSrc == CFEAR_P2P_MAX_SRC_POINTS, "limits stated in cfear_hip.h");
 
 struct P2pJobDev {                    // one job, in the order of its group
@@ -60,27 +55,19 @@ struct P2pCommon {
 typedef float v4f __attribute__((ext_vector_type(4)));
 #define CFEAR_LDS __attribute__((address_space(3)))
 
-__device__ __forceinline__ int lower_bound_u32(const uint32_t* a, int lo, int hi, uint32_t key) {
-  while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] < key) lo = mid + 1; else hi = mid; }
-  return lo;
-}
-
-__device__ __forceinline__ void write_record(const P2pCommon& cm, int out, double sum, int matched, int n_src, int status) {
+__device__ __forceinline__ void write_record(const P2pCommon& cm, int out, double sum, int matched, int n_src, int status, int path = 0) {
   cfear_p2p_result r;
   r.sum = sum; r.mean = sum / (double)(matched + 3);     // residuals_ = {0, 0, 0} + the matches (AlignmentQuality.h:92)
-  r.matched = matched; r.n_src = n_src; r.status = status; r.pad = 0;
+  r.matched = matched; r.n_src = n_src; r.status = status; r.pad = path;           // path: CFEAR_CORAL_PATH_* of a served job (diagnostic)
   cm.results[out] = r;
 }
 
 __global__ __launch_bounds__(kP2pThreads) void p2p_kernel(const P2pGroupDev* __restrict__ groups, const P2pJobDev* __restrict__ jobs,
                                                           const P2pCommon cm) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  float (*red_f)[16] = (float (*)[16])(smem + kP2pSmallOff);            // [4][16]
-  int* red_i = (int*)(smem + kP2pSmallOff + 256);                       // [16]
-  int* red_c = (int*)(smem + kP2pSmallOff + 320);                       // [16]
-  double* red_d = (double*)(smem + kP2pSmallOff + 384);                 // [2][16]
-  int* red_m = (int*)(smem + kP2pSmallOff + 640);                       // [2][16]
-  int* red_b = (int*)(smem + kP2pSmallOff + 768);                       // [2][16]
+  double* red_d = (double*)(smem + kGridSmallOff + 384);                // [2][16]
+  int* red_m = (int*)(smem + kGridSmallOff + 640);                      // [2][16]
+  int* red_b = (int*)(smem + kGridSmallOff + 768);                      // [2][16]
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const P2pGroupDev g = groups[blockIdx.x];
   const int n = g.n_ref;
@@ -108,17 +95,7 @@ __global__ __launch_bounds__(kP2pThreads) void p2p_kernel(const P2pGroupDev* __r
     mnx = fminf(mnx, p.x); mxx = fmaxf(mxx, p.x);
     mny = fminf(mny, p.y); mxy = fmaxf(mxy, p.y);
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    mnx = fminf(mnx, __shfl_xor(mnx, o)); mxx = fmaxf(mxx, __shfl_xor(mxx, o));
-    mny = fminf(mny, __shfl_xor(mny, o)); mxy = fmaxf(mxy, __shfl_xor(mxy, o));
-  }
-  if (lane == 0) { red_f[0][wave] = mnx; red_f[1][wave] = mxx; red_f[2][wave] = mny; red_f[3][wave] = mxy; }
-  nan_ref = __syncthreads_or(nan_ref);
-  mnx = red_f[0][0]; mxx = red_f[1][0]; mny = red_f[2][0]; mxy = red_f[3][0];
-  for (int wv = 1; wv < 16; wv++) {
-    mnx = fminf(mnx, red_f[0][wv]); mxx = fmaxf(mxx, red_f[1][wv]);
-    mny = fminf(mny, red_f[2][wv]); mxy = fmaxf(mxy, red_f[3][wv]);
-  }
+  block_bbox_f32(smem, mnx, mxx, mny, mxy, [&] { nan_ref = __syncthreads_or(nan_ref); });
   const float f_min_bx = floorf(mnx * cm.inv_cell), f_max_bx = floorf(mxx * cm.inv_cell);
   const float f_min_by = floorf(mny * cm.inv_cell), f_max_by = floorf(mxy * cm.inv_cell);
   // (written so that an infinite extent fails the test as well)
@@ -127,7 +104,7 @@ __global__ __launch_bounds__(kP2pThreads) void p2p_kernel(const P2pGroupDev* __r
   if (nan_ref || !in_range) { fail_group(CFEAR_ERR_CAPACITY); return; }
   const int min_bx = (int)f_min_bx, min_by = (int)f_min_by;
   const long long div_bx = (long long)f_max_bx - min_bx + 1, div_by = (long long)f_max_by - min_by + 1;
-  if (div_bx * div_by > 0x7fffffffLL || div_by > kP2pMaxGridRows) { fail_group(CFEAR_ERR_CAPACITY); return; }
+  if (div_bx * div_by > 0x7fffffffLL || div_by > kGridMaxRows) { fail_group(CFEAR_ERR_CAPACITY); return; }
   const int dbx = (int)div_bx, dby = (int)div_by;
   // the cell of a coordinate, relative to the grid's first cell and clamped to one cell outside it: monotone in v
   auto cell_x = [&](float v) { return (int)(fminf(fmaxf(floorf(v * cm.inv_cell), f_min_bx - 1.0f), f_max_bx + 1.0f) - f_min_bx); };
@@ -136,111 +113,13 @@ __global__ __launch_bounds__(kP2pThreads) void p2p_kernel(const P2pGroupDev* __r
     ix = cell_x(gload<float>(&g.ref[i].x));
     iy = cell_y(gload<float>(&g.ref[i].y));
   };
-  // ---- 2. sort by (cell, index) ------------------------------------------------------------------------------------
-  unsigned long long* keys = (unsigned long long*)smem;
-  int npad = grid_sort_rows_block(smem, n, dbx, dby, (uint32_t*)(smem + kP2pRowbegOff), red_i, red_c, 512, ref_cell);
-  if (npad == 0)                                       // crowded grid row or a large cloud: generic block sort
-    npad = grid_sort_block(smem, n, (long long)dbx * dby, red_i, [&](int i) {
-      int ix, iy;
-      ref_cell(i, ix, iy);
-      return (uint32_t)(ix + iy * dbx);
-    });
-  // ---- 3. sorted points -> LDS or scratch; cell table (key, start) -> LDS ------------------------------------------
-  const int per = npad / kP2pThreads;                   // 1..16 consecutive sorted elements per thread
-  unsigned long long mine[kP2pPerThread];
-  const unsigned prev_cell = (tid * per > 0) ? (unsigned)(keys[tid * per - 1] >> 32) : 0xFFFFFFFFu;
-  int heads = 0;
-#pragma unroll
-  for (int q = 0; q < kP2pPerThread; q++) {
-    const int e = tid * per + q;
-    mine[q] = (q < per && e < n) ? keys[e] : ~0ull;
-  }
-  {
-    unsigned pv = prev_cell;
-#pragma unroll
-    for (int q = 0; q < kP2pPerThread; q++) {
-      const int e = tid * per + q;
-      if (q < per && e < n) {
-        const unsigned vx = (unsigned)(mine[q] >> 32);
-        heads += (e == 0 || vx != pv);
-        pv = vx;
-      }
-    }
-  }
-  const int incl = wave_incl_scan_i32(heads);
-  if (lane == 63) red_i[wave] = incl;
-  __syncthreads();                                      // also: every thread has read its keys
-  int voff = incl - heads;
-  for (int wv = 0; wv < wave; wv++) voff += red_i[wv];
-  int V = 0;
-  for (int wv = 0; wv < 16; wv++) V += red_i[wv];
-  const size_t Vp = ((size_t)V + 4) & ~(size_t)3;
-  uint32_t* cell_key = (uint32_t*)smem;                 // [V]
-  int32_t* cell_start = (int32_t*)(smem + Vp * 4);      // [V + 1]
-  int32_t* rowbeg = (int32_t*)(smem + kP2pRowbegOff);   // [dby + 1]
-  const size_t spt_off = (Vp * 4 + ((size_t)V + 1) * 4 + 15) & ~(size_t)15;
-  const bool spt_in_lds = spt_off + (size_t)n * 16 <= kP2pRowbegOff;
-  float4* spt = spt_in_lds ? (float4*)(smem + spt_off) : (float4*)(cm.scratch + (size_t)blockIdx.x * cm.cap * 16);
-  {
-    unsigned pv = prev_cell;
-    int ord = voff;
-#pragma unroll
-    for (int q = 0; q < kP2pPerThread; q++) {
-      const int e = tid * per + q;
-      if (q < per && e < n) {
-        const unsigned vx = (unsigned)(mine[q] >> 32);
-        const int idx = (int)(unsigned)(mine[q] & 0xFFFFFFFFu);
-        if (e == 0 || vx != pv) { cell_key[ord] = vx; cell_start[ord] = e; ord++; }
-        pv = vx;
-        const float4 p = gload_f4(g.ref + idx);
-        spt[e] = make_float4(p.x, p.y, p.z, 0.0f);
-      }
-    }
-  }
-  if (tid == 0) cell_start[V] = n;
-  __threadfence_block();
-  __syncthreads();
-  // ---- 3b. O(1) cell look-ups: one bit per grid cell + the occupied cells before every 32-cell word (coral.hip 3b);
-  //      binary searches over the occupied cells of a grid row when the bitmap does not fit the LDS ------------------
-  const long long ncells_ll = (long long)dbx * dby;
-  const size_t occ_off = spt_in_lds ? ((spt_off + (size_t)n * 16 + 15) & ~(size_t)15) : spt_off;
-  const long long nw32_ll = (ncells_ll >> 5) + 1;
-  const bool bitmap = occ_off + (size_t)nw32_ll * 6 + 16 <= kP2pRowbegOff;
-  uint32_t* occ = (uint32_t*)(smem + occ_off);
-  const int nw32 = bitmap ? (int)nw32_ll : 0;
-  unsigned short* wpref = (unsigned short*)(occ + nw32);
-  if (!bitmap) {                                        // first occupied cell of every grid row
-    for (int y = tid; y <= dby; y += kP2pThreads)
-      rowbeg[y] = lower_bound_u32(cell_key, 0, V, (uint32_t)((long long)y * dbx));
-    __syncthreads();
-  } else {
-    for (int w = tid; w < nw32; w += kP2pThreads) occ[w] = 0u;
-    __syncthreads();
-    for (int o = tid; o < V; o += kP2pThreads) { const uint32_t c = cell_key[o]; atomicOr(&occ[c >> 5], 1u << (c & 31)); }
-    __syncthreads();
-    const int perw = (nw32 + kP2pThreads - 1) / kP2pThreads;
-    const int w0 = min(nw32, tid * perw), w1 = min(nw32, w0 + perw);
-    int to = 0;
-    for (int w = w0; w < w1; w++) to += __popc(occ[w]);
-    const int inclw = wave_incl_scan_i32(to);
-    if (lane == 63) red_c[wave] = inclw;
-    __syncthreads();
-    int runw = inclw - to;
-    for (int wv = 0; wv < wave; wv++) runw += red_c[wv];
-    for (int w = w0; w < w1; w++) { wpref[w] = (unsigned short)runw; runw += __popc(occ[w]); }
-    __syncthreads();
-  }
-  // sorted points in the cells [c0, c1) of one grid row (c0 <= c1, both inside the row or at its end)
-  auto run_of = [&](int y, int c0, int c1, int& a, int& b) {
-    if (bitmap) {
-      const int w0 = c0 >> 5, w1 = c1 >> 5;
-      a = cell_start[(int)wpref[w0] + __popc(occ[w0] & ((1u << (c0 & 31)) - 1u))];
-      b = cell_start[(int)wpref[w1] + __popc(occ[w1] & ((1u << (c1 & 31)) - 1u))];
-    } else {
-      a = cell_start[lower_bound_u32(cell_key, rowbeg[y], rowbeg[y + 1], (uint32_t)c0)];
-      b = cell_start[lower_bound_u32(cell_key, rowbeg[y], rowbeg[y + 1], (uint32_t)c1)];
-    }
-  };
+  // ---- 2, 3. the grid index (gridsort.hpp): sort by (cell, index), cell table, sorted points (x, y, z, 0) in LDS or in
+  //      the scratch, bitmap or row table -------------------------------------------------------------------------------
+  const GridIndex grid = grid_index_build(smem, n, dbx, dby, cm.scratch ? (float4*)(cm.scratch + (size_t)blockIdx.x * cm.cap * 16) : nullptr,
+                                          ref_cell, [&](int, int idx) {
+                                            const float4 p = gload_f4(g.ref + idx);
+                                            return make_float4(p.x, p.y, p.z, 0.0f);
+                                          });
   // ---- 4. the jobs of this cloud, one after the other; one source point per lane -----------------------------------
   auto serve = [&](auto* SP) {
     for (int j = g.job0; j < g.job1; j++) {
@@ -279,7 +158,7 @@ __global__ __launch_bounds__(kP2pThreads) void p2p_kernel(const P2pGroupDev* __r
         if (finite && x0 <= x1)
           for (int yy = y0; yy <= y1; yy++) {
             int a, b;
-            run_of(yy, yy * dbx + x0, yy * dbx + x1 + 1, a, b);
+            grid.run(yy, yy * dbx + x0, yy * dbx + x1 + 1, a, b);
             for (; a + 1 < b; a += 2) {
               const v4f c0 = SP[a], c1 = SP[a + 1];
               visit(c0);
@@ -303,12 +182,12 @@ __global__ __launch_bounds__(kP2pThreads) void p2p_kernel(const P2pGroupDev* __r
         const int out = gload<int32_t>(&jb->out);
         if (ns <= 0) write_record(cm, out, 0.0, 0, 0, CFEAR_ERR_EMPTY_CLOUD);
         else if (b) write_record(cm, out, 0.0, 0, ns, CFEAR_ERR_CAPACITY);
-        else write_record(cm, out, s, m, ns, CFEAR_OK);
+        else write_record(cm, out, s, m, ns, CFEAR_OK, grid.path);
       }
     }
   };
-  if (spt_in_lds) serve((CFEAR_LDS const v4f*)spt);
-  else serve((const v4f*)spt);
+  if (grid.spt_in_lds) serve((CFEAR_LDS const v4f*)grid.spt);
+  else serve((const v4f*)grid.spt);
 }
 
 }  // namespace
@@ -359,7 +238,7 @@ extern "C" int cfear_p2p_quality_batch(cfear_ctx* ctx, const cfear_p2p_job* jobs
   if (per_point && pp_total) st.out(d_pp, per_point, pp_total * sizeof(float));
   // the sorted cloud of a workgroup leaves the LDS above ~5460 points (24 bytes a point with its cell table)
   const size_t scratch_stride = (size_t)cap * 16;
-  const bool need_scratch = (size_t)cap * 24 + 64 > kP2pRowbegOff;
+  const bool need_scratch = (size_t)cap * 24 + 64 > kGridRowbegOff;
   // with a scratch, a launch holds two workgroups per compute unit: the slot is grow-only, and more than the resident
   // workgroups' worth of it buys nothing (at most 2 n_cu x 256 KiB)
   const size_t chunk = need_scratch ? std::max<size_t>(1, std::min<size_t>(n_groups, 2 * (size_t)std::max(ctx->n_cu, 1))) : n_groups;
@@ -398,13 +277,13 @@ extern "C" int cfear_p2p_quality_batch(cfear_ctx* ctx, const cfear_p2p_job* jobs
   cm.cap = cap;
   cm.results = d_res;
   cm.per_point = d_pp;
-  CFEAR_CHECK(cfear_allow_lds(ctx, (const void*)p2p_kernel, kP2pLdsTotal));   // (+ the static word of __syncthreads_or)
+  CFEAR_CHECK(cfear_allow_lds(ctx, (const void*)p2p_kernel, kGridLdsTotal));   // (+ the static word of __syncthreads_or)
   {
     ProfScope ps(ctx, "p2p_quality");
     for (size_t g0 = 0; g0 < n_groups; g0 += chunk) {
       const size_t ng = std::min(chunk, n_groups - g0);
       cm.scratch = scr;
-      hipLaunchKernelGGL(p2p_kernel, dim3((unsigned)ng), dim3(kP2pThreads), kP2pLdsTotal, ctx->stream,
+      hipLaunchKernelGGL(p2p_kernel, dim3((unsigned)ng), dim3(kP2pThreads), kGridLdsTotal, ctx->stream,
                          (const P2pGroupDev*)d_rec + g0, (const P2pJobDev*)(d_rec + grp_bytes), cm);
     }
   }

@@ -313,15 +313,6 @@ __device__ __forceinline__ int finish_cell(const Moments& m, const double cx, co
   return 1;
 }
 
-__device__ __forceinline__ int lower_bound_u32(const uint32_t* a, int lo, int hi, uint32_t key) {
-  while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] < key) lo = mid + 1; else hi = mid; }
-  return lo;
-}
-__device__ __forceinline__ int upper_bound_u32(const uint32_t* a, int lo, int hi, uint32_t key) {
-  while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] <= key) lo = mid + 1; else hi = mid; }
-  return lo;
-}
-
 // The matcher's search structure of a scan (ScanView::grid): the float means bucketed into a uniform kScanGrid x kScanGrid
 // grid over the scan's own extent, built ONCE per scan -- the counterpart of ComputeSearchTreeFromCells (pointnormal.cpp:
 // 151-162), which builds the reference's kd-tree once per MapPointNormal.  A registration copies the block into LDS

@@ -1,18 +1,19 @@
 """CorAl test geometries and the helpers the geometry tests share: cloud builders with fixed seeds, a restatement of the
-thresholds by which coral_kernel (tbv_slam_public_amd/csrc/coral.hip) picks its sort, the home of the sorted points and
-the cell lookup -- used ONLY to choose inputs; the tests assert the path bits the kernel reports -- and exact_coral, the
-per-point entropies from exact rational covariances."""
+thresholds by which the grid index of coral_kernel and p2p_kernel (grid_index_build, tbv_slam_public_amd/csrc/gridsort.hpp)
+picks its sort, the home of the sorted points and the cell lookup -- used ONLY to choose inputs; the tests assert the path
+bits the kernels report -- and exact_coral, the per-point entropies from exact rational covariances."""
 import math
 from decimal import Decimal, localcontext
 from fractions import Fraction
 
 import numpy as np
 
-# ---- the kernel's limits and path bits (include/cfear_hip.h: CFEAR_CORAL_PATH_*, cfear_coral_result.pad) -------------
-MAX_POINTS = 16384                     # kCoralMaxPoints = kGridSortMaxPoints
-MAX_GRID_ROWS = 4096                   # kCoralMaxGridRows
+# ---- the index's limits and path bits (include/cfear_hip.h: CFEAR_CORAL_PATH_*, the pad of cfear_coral_result and of
+#      cfear_p2p_result) ---------------------------------------------------------------------------------------------------
+MAX_POINTS = 16384                     # kGridSortMaxPoints
+MAX_GRID_ROWS = 4096                   # kGridMaxRows
 MAX_CELLS = 2 ** 31 - 1
-ROWBEG_OFF = MAX_POINTS * 8 + 16       # kCoralRowbegOff: LDS bytes for cell table + sorted points + occupancy bitmap
+ROWBEG_OFF = MAX_POINTS * 8 + 16       # kGridRowbegOff: LDS bytes for cell table + sorted points + occupancy bitmap
 PATH_SCRATCH, PATH_BSEARCH = 1, 2      # bit 0: sorted points in the global scratch; bit 1: binary-search lookup
 SORT_ROWS, SORT_RADIX, SORT_BITONIC = 0, 1, 2          # bits 2-3
 
@@ -32,10 +33,12 @@ def scratch_bytes(cap):
 
 
 def predict_path(n, V, dbx, dby, max_row=0):
-    """The path coral_kernel takes for n merged points in V occupied cells of a dbx x dby grid whose fullest grid row
-    holds max_row points: path bits, or None where the kernel refuses the job (CFEAR_ERR_CAPACITY).  Mirrors
-    coral.hip: the refusals at the top of coral_kernel and after its bounding box; the sort (grid_sort_rows_block's
-    entry test and crowded-row test with max_row 512, grid_sort_is_radix in gridsort.hpp); `spt_in_lds`; `bitmap`."""
+    """The path the grid index takes for n points (CorAl: the merged cloud; P2P: the reference cloud) in V occupied cells
+    of a dbx x dby grid whose fullest grid row holds max_row points: path bits, or None where both kernels refuse the
+    cloud for its size or grid (CFEAR_ERR_CAPACITY; their other refusals are their own).  Mirrors the refusals at the
+    top of coral_kernel / p2p_kernel and after their bounding boxes, and gridsort.hpp: the sort (grid_sort_rows_block's
+    entry test and crowded-row test with max_row 512, grid_sort_is_radix); `spt_in_lds` and `bitmap` of
+    grid_index_build."""
     ncells = dbx * dby
     if n > MAX_POINTS or dby > MAX_GRID_ROWS or ncells > MAX_CELLS:
         return None
@@ -65,17 +68,26 @@ def merged_points(ref, src, ref_pose, src_pose, offset=(0.0, 0.0, 0.0)):
             _tf(np.asarray(ref, np.float32), np.asarray(ref_pose, float)))
 
 
-def grid_of(ref, src, ref_pose, src_pose, offset=(0.0, 0.0, 0.0), radius=1.0):
-    """The kernel's grid over the merged cloud (cell = radius * 1.0001, float arithmetic as cell_xy):
-    dict(n, V, dbx, dby, max_row) -- predict_path's arguments."""
-    ps, pr = merged_points(ref, src, ref_pose, src_pose, offset)
-    P = np.concatenate([ps, pr])
+def grid_of_points(P, radius=1.0):
+    """The grid of both kernels over the float32 points P [n, >= 2] (cell = radius * 1.0001, float arithmetic as the
+    kernels' cell functions): dict(n, V, dbx, dby, max_row) -- predict_path's arguments."""
     inv = np.float32(1.0 / (radius * 1.0001))
     bx, by = np.floor(P[:, 0] * inv), np.floor(P[:, 1] * inv)
     ix = (bx - np.float32(bx.min())).astype(np.int64)
     iy = (by - np.float32(by.min())).astype(np.int64)
     dbx, dby = int(ix.max()) + 1, int(iy.max()) + 1
     return dict(n=len(P), V=len(np.unique(iy * dbx + ix)), dbx=dbx, dby=dby, max_row=int(np.bincount(iy).max()))
+
+
+def grid_of(ref, src, ref_pose, src_pose, offset=(0.0, 0.0, 0.0), radius=1.0):
+    """CorAl's grid: over the merged cloud."""
+    ps, pr = merged_points(ref, src, ref_pose, src_pose, offset)
+    return grid_of_points(np.concatenate([ps, pr]), radius)
+
+
+def grid_of_cloud(ref, radius):
+    """P2P's grid: over the reference cloud alone, as it is given."""
+    return grid_of_points(np.asarray(ref, np.float32), radius)
 
 
 def predict(ref, src, ref_pose, src_pose, offset=(0.0, 0.0, 0.0), radius=1.0):

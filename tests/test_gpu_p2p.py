@@ -5,7 +5,10 @@ per_point, matched and n_src are compared bit for bit.  sum: the kernel adds per
 tree, the definition adds serially; both are sums of n <= n_src non-negative doubles, each within (n - 1) u of the true sum,
 u = 2^-53, so they differ by at most 2 n_src 2^-53 relatively.  mean = sum / (matched + 3) is checked as that very division
 of the kernel's own sum (IEEE, correctly rounded on both sides), and against the definition's mean with one more rounding on
-either side: (2 n_src + 2) 2^-53."""
+either side: (2 n_src + 2) 2^-53.
+
+Every checked record also carries, in `pad`, the path of the grid index that served it (CFEAR_CORAL_PATH_*), asserted against
+tests/coral_geometry.py::predict_path for the job's reference cloud; test_path_word lists the paths the tests here reach."""
 import math
 import os
 import subprocess
@@ -13,6 +16,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import coral_geometry as G
 from tests import p2p_cpu as R
 
 pytestmark = pytest.mark.gpu
@@ -48,6 +52,9 @@ def _check_record(rec, pp, ref, src, T, radius, tag=""):
     print("%s n_ref %d n_src %d matched %d/%d sum %.17g vs %.17g mean %.17g vs %.17g" % (
         tag, len(ref), n, rec["matched"], want["matched"], rec["sum"], want["sum"], rec["mean"], want["mean"]))
     assert rec["status"] == 0, (tag, rec["status"])
+    path = G.predict_path(**G.grid_of_cloud(ref, radius))
+    print("%s path %s, predicted %s" % (tag, G.describe(int(rec["pad"])), "a refusal" if path is None else G.describe(path)))
+    assert int(rec["pad"]) == path, tag
     assert np.array_equal(np.asarray(pp).view(np.uint32), want["per_point"].view(np.uint32)), tag
     assert (int(rec["matched"]), int(rec["n_src"])) == (want["matched"], n), tag
     assert abs(float(rec["sum"]) - want["sum"]) <= 2 * n * U * want["sum"], tag
@@ -73,13 +80,14 @@ def test_sizes(n_ref):
     for n_src in SIZES:
         ref, src = _pair(rng, n_ref, n_src, 20.0)
         jobs.append((ref, src, T))
-    got = _run_and_check(jobs, 3.0, "sizes")
+    got = _run_and_check(jobs, 3.0, "sizes")                                         # (every record's pad: _check_record)
     assert n_ref < 63 or sum(w["matched"] for w in got) > 0
 
 
 def test_cluster_inside_one_cell():
     rng = np.random.default_rng(7)
     ref = (rng.uniform(0.1, 2.9, (5000, 4)) * [1, 1, 0.1, 1]).astype(F)         # one 3 m cell, one crowded grid row
+    assert G.predict_path(**G.grid_of_cloud(ref, 3.0)) == G.path_bits(0, 0, G.SORT_RADIX)
     src = (rng.uniform(-1.0, 4.0, (777, 4)) * [1, 1, 0.1, 1]).astype(F)
     got = _run_and_check([(ref, src, IDENT)], 3.0, "cluster")
     assert got[0]["matched"] == 777
@@ -91,6 +99,8 @@ def test_cloud_spread_over_390_m(radius):
     ref, src = _pair(rng, 1000, 1000, 390.0, jitter=radius / 2)
     ref[0, :2], ref[1, :2] = (-390.0, -390.0), (390.0, 390.0)
     src[0, :3], src[1, :3] = (-389.9, -390.1, 0.0), (390.2, 389.9, 0.0)             # matches at the corners of the grid and outside it
+    # 260 x 260 cells fit the bitmap, 1560 x 1560 do not
+    assert G.predict_path(**G.grid_of_cloud(ref, radius)) == G.path_bits(0, radius == 0.5, G.SORT_ROWS)
     got = _run_and_check([(ref, src, IDENT)], radius, "spread")
     assert got[0]["matched"] > 300
 
@@ -99,22 +109,75 @@ def test_largest_clouds():
     """16 384 points each: the bitonic sort, the sorted cloud in the global scratch, sixteen source points per lane"""
     rng = np.random.default_rng(15)
     ref, src = _pair(rng, 16384, 16384, 150.0)
+    assert G.predict_path(**G.grid_of_cloud(ref, 3.0)) == G.path_bits(1, 0, G.SORT_BITONIC)
     got = _run_and_check([(ref, src, R.tchange((1.0, 2.0, 0.3), (1.2, 2.1, 0.31)))], 3.0, "largest")
     assert got[0]["matched"] > 8000
 
 
+def _path_cases():
+    """name -> (ref, src, radius, wanted path bits): the smallest clouds that reach each bit of the path word, chosen on the
+    CPU with predict_path.  The sorted points leave the LDS when 16 n + 8 V > 131 088 bytes; the bitmap needs 6 bytes per 32
+    grid cells behind them; the row sort declines above 512 points in a grid row or 8192 points, the radix sort above 8192."""
+    B = G.path_bits
+    rng = np.random.default_rng(30)
+    out = {}
+
+    def pair(n_ref, n_src, span, jitter=0.5):
+        return _pair(rng, n_ref, n_src, span, jitter=jitter)
+
+    out["lds_bitmap_rows"] = (*pair(1500, 300, 20.0), 1.0, B(0, 0, G.SORT_ROWS))
+    out["scratch_bitmap_rows"] = (*pair(8000, 300, 40.0), 1.0, B(1, 0, G.SORT_ROWS))         # ~4600 of 80 x 80 cells occupied
+    ref, src = pair(1000, 300, 390.0, 0.2)                                                    # 1560 x 1560 cells at radius 0.5
+    out["lds_bsearch_rows"] = (ref, src, 0.5, B(0, 1, G.SORT_ROWS))
+    ref, src = pair(8000, 300, 40.0)
+    ref[0, :2], ref[1, :2] = (-1500.0, -1500.0), (1500.0, 1500.0)                            # 3000 x 3000 cells
+    out["scratch_bsearch_rows"] = (ref, src, 1.0, B(1, 1, G.SORT_ROWS))
+    ref, src = pair(1500, 300, 20.0)
+    ref[:600, 1] = rng.uniform(0.1, 0.9, 600).astype(F)                                      # 600 points in one grid row
+    out["lds_bitmap_radix"] = (ref, src, 1.0, B(0, 0, G.SORT_RADIX))
+    out["scratch_bitmap_bitonic"] = (*pair(8200, 300, 40.0), 1.0, B(1, 0, G.SORT_BITONIC))
+    return out
+
+
+PATH_CASES = _path_cases()
+
+
+@pytest.mark.parametrize("name", sorted(PATH_CASES))
+def test_path_word(name):
+    """cfear_p2p_result.pad names the path that served the job.  Between them, these cases and test_cluster_inside_one_cell,
+    test_cloud_spread_over_390_m and test_largest_clouds show every bit: LDS and scratch, bitmap and binary search, and the
+    row, radix and bitonic sorts."""
+    ref, src, radius, want = PATH_CASES[name]
+    assert G.predict_path(**G.grid_of_cloud(ref, radius)) == want, G.describe(want)          # the input is what its name says
+    out, pp = _api().p2p_quality_batch([(ref, src, IDENT)], radius, want_per_point=True)
+    got = _check_record(out[0], pp[0], ref, src, IDENT, radius, name)                         # pad against the prediction, which is `want`
+    assert got["matched"] > 100
+
+
+def test_path_word_cases_cover_every_bit():
+    words = [c[3] for c in PATH_CASES.values()]
+    assert {w & 1 for w in words} == {0, 1} and {(w >> 1) & 1 for w in words} == {0, 1}
+    assert {(w >> 2) & 3 for w in words} == {G.SORT_ROWS, G.SORT_RADIX, G.SORT_BITONIC}
+
+
 def test_more_large_clouds_than_one_launch_holds():
-    """520 distinct reference clouds too large for the LDS: the scratch holds two workgroups per compute unit (512 on an
-    MI355X), so the batch takes a second launch.  The clouds are copies, so one definition run serves every job; an
-    infinite source point is scanned nowhere and has no neighbour."""
+    """520 distinct reference clouds for which the HOST reserves the scratch (it sizes it from 24 bytes a point, the most a
+    point can take with its cell table: 5600 points -> 134 464 > 131 088): the scratch holds two workgroups per compute
+    unit (512 on an MI355X), so the batch takes a second launch.  That two-launch logic is what this test pins.  The
+    KERNEL decides from the occupied cells it finds -- 3197 here, 115 200 bytes with the points -- and keeps these clouds
+    in LDS: the path word says lds/bitmap/rows, asserted below (the scratch path itself: test_path_word,
+    test_largest_clouds).  The clouds are copies, so one definition run serves every job; an infinite source point is
+    scanned nowhere and has no neighbour."""
     rng = np.random.default_rng(17)
     ref, src = _pair(rng, 5600, 40, 100.0)
     src[3, 0], src[4, 1] = np.inf, -np.inf
     T = R.tchange((0, 0, 0), (0, 0, 0.001))          # a rotation: an infinite coordinate stays infinite (under the identity 0 * inf is NaN)
     refs = np.ascontiguousarray(np.broadcast_to(ref, (520,) + ref.shape))
     jobs = [(refs[k], src, T) for k in range(520)]
+    assert G.predict_path(**G.grid_of_cloud(ref, 3.0)) == G.path_bits(0, 0, G.SORT_ROWS) and len(ref) * 24 + 64 > G.ROWBEG_OFF
     out, pp = _api().p2p_quality_batch(jobs, 3.0, want_per_point=True)
     want = _check_record(out[0], pp[0], ref, src, T, 3.0, "launches[0]")
+    assert int(out[0]["pad"]) == G.path_bits(0, 0, G.SORT_ROWS)
     assert np.all(np.isinf(R.transform(src, T)[3:5, :2]))
     assert want["matched"] > 20 and want["per_point"][3] == want["per_point"][4] == -1
     assert all(out[k].tobytes() == out[0].tobytes() for k in range(520))
