@@ -211,6 +211,77 @@ int cfear_filter_cacfar(cfear_ctx* ctx, const uint8_t* polar, const cfear_polar_
                         const cfear_cacfar_params* par, float* xyzi, int32_t* n_points,
                         int32_t cap_points, uint8_t* det_mask);
 
+/* Which CA-CFAR kernel a call launches, and with which geometry: the selection cfear_filter_cacfar,
+ * cfear_filter_cacfar_rowkeys and the batched odometry make from the filter's parameters and the row length, reported so
+ * that a test can name the kernel instantiation its input reaches.  Pure host code: no context, no device, no GPU call.
+ *   desc   the images as the filter call gets them (with CFEAR_ROWKEYS_BINS_MAJOR: rows = range bins, cols = azimuths)
+ *   flags  CFEAR_ROWKEYS_BINS_MAJOR      the fused decode (cacfar_cols_kernel); implies the key output
+ *          CFEAR_CACFAR_PLAN_KEYS        the key output of cfear_filter_cacfar_rowkeys / the batched odometry
+ *                                        (cfear_filter_cacfar, the bitmap output, passes neither)
+ *          CFEAR_CACFAR_PLAN_BASE(addr)  the image address modulo 16 (0 when omitted): rows are read in 16-byte pieces
+ *                                        only from 4-byte boundaries, the fused decode wants 16
+ * A row is cut into nch chunks of 256 D bins (D dwords per lane), the last one of 256 DL bins; colsp = the bins of all chunks.
+ *   bin_lo, bin_hi  the bins that can pass the range window (min_distance < range_res bin < max_distance), [lo, hi); both 0
+ *                   when nothing can pass (the window is empty, or z_min >= 255)
+ *   need_cols       the bins the arithmetic of [bin_lo, bin_hi) reads: min(row length, bin_hi - 1 + guard + window), rounded
+ *                   up to 16; nothing beyond is loaded
+ *   lut_ok          the integer decision table exists (a finite scaling > 0 that fits it); pre_on: the lower-bound pre-filter
+ *                   runs (lut_ok, guard + window <= 1024 and an aligned quad inside a window of every bin of an 8-bin block)
+ *   wide            rows kernel, D = 4 only: more than four chunks (the eight-chunk instantiation)
+ *   pad_lo, pad_hi  guard entries of the prefix table before bin 0 / beyond the row; lds_bytes: the launch's dynamic LDS
+ *   table_index     the entry of the dispatch table the launcher takes its kernel from -- the launcher reads THIS plan, so
+ *                   the report cannot differ from the launch.  Rows kernel (cols_route = 0), template arguments
+ *                   <D, NCH, DL, KEYS, PRE>:
+ *                      0 ..  7  D = 4:  4 wide + 2 keys + pre                        <4, 4 | 8, 4, keys, pre>
+ *                      8 .. 11  D = 6, whole chunks:  8 + 2 (nch > 2) + keys         <6, 2 | 6, 6, keys, 1>
+ *                     12 .. 13  D = 6, DL = 4 (two chunks):  12 + keys               <6, 2, 4, keys, 1>
+ *                     14 .. 17  D = 8, whole chunks:  14 + 2 (nch > 2) + keys        <8, 2 | 4, 8, keys, 1>
+ *                     18 .. 19  D = 8, DL = 6 (two chunks):  18 + keys               <8, 2, 6, keys, 1>
+ *                   fused decode (cols_route = 1), <D, NCH, DL, PRE>:
+ *                      0 .. 1   D = 4:  pre            <4, 4, 4, pre>
+ *                      2, 3     D = 6:  DL = 4, 6      <6, 2, DL, 1>
+ *                      4, 5     D = 8:  DL = 6, 8      <8, 2, DL, 1>
+ *                   (D = 6 / 8 exist with the pre-filter only.  A shorter last chunk of D = 6, DL = 2 and of D = 8, DL = 2 / 4
+ *                   never costs less than a geometry tried before it, so no parameter set selects it and none is built.)
+ *   piece_rows      rows route: how many of the batch * rows rows are read from memory in 16-byte pieces; the others (rows on
+ *                   addresses or strides that are no multiple of 4, and rows of a ragged image -- cols % 16 != 0 -- whose
+ *                   last piece would end beyond rows * stride) are copied byte by byte.  total_rows = batch * rows.
+ *   cols_supported  with CFEAR_ROWKEYS_BINS_MAJOR: the fused decode takes this geometry (azimuths % 16 == 0, bins % 16 == 0,
+ *                   stride, batch_stride and address multiples of 16, rows * stride < 2^31, colsp <= 4096 and
+ *                   lds_bytes <= 160 KiB - 256); where it is 0 cfear_filter_cacfar_rowkeys refuses the call and the batched
+ *                   odometry rotates first.  0 without the flag.
+ * Returns CFEAR_ERR_INVALID_ARGUMENT for a null pointer, a bad descriptor (as the filter calls refuse it) or bad
+ * parameters (window_size < 1, nb_guard_cells < 0, range_res <= 0).                                                          */
+#define CFEAR_CACFAR_PLAN_KEYS 0x100
+#define CFEAR_CACFAR_PLAN_BASE(addr) ((int32_t)(((uintptr_t)(addr)) & 15) << 12)
+struct cfear_cacfar_plan {
+  int32_t D, DL, nch, wide;
+  int32_t pre_on, lut_ok;
+  int32_t need_cols, colsp, bin_lo, bin_hi;
+  int32_t pad_lo, pad_hi;
+  int32_t keys, cols_route, cols_supported, table_index;
+  int64_t lds_bytes, piece_rows, total_rows;
+};
+int cfear_cacfar_plan(const cfear_polar_desc* desc, const cfear_cacfar_params* par, int32_t flags, struct cfear_cacfar_plan* out);
+
+/* The CA-CFAR filter stage of the batched odometry on its own (device memory only): what cfear_odometry_process runs ahead of
+ * the surface-point stage when filter_type = CFEAR_FILTER_CACFAR.  Per azimuth row the detections of
+ * AzimuthCACFAR::getFilteredPointCloud (cfar.cpp:35-71) as packed keys instead of a cloud:
+ *   row_keys   uint32 [batch][azimuths][kcap]  key = intensity << 24 | range bin (intensity = the bin's byte; the bin fits 13
+ *                                              bits); a row's keys are in ASCENDING BIN order, the order of cfar.cpp's loop
+ *   row_counts int32  [batch][azimuths][2]     {detections of the row, 0}
+ * A row with more than kcap detections leaves its full count in row_counts and its FIRST kcap keys (the kcap smallest bins);
+ * the others are dropped (the batched odometry reports such a scan with CFEAR_ERR_CAPACITY).  Entries of row_keys beyond
+ * min(count, kcap) are not written.  The surface-point stage places a key's point at range_res * bin (the bin's edge,
+ * cfar.cpp:43) and azimuth row / azimuths * 2 pi.
+ * flags: CFEAR_ROWKEYS_BINS_MAJOR -- the images are [range bins][azimuths] and row r of the result is source column
+ * cols - 1 - r (cv::ROTATE_90_COUNTERCLOCKWISE), decoded inside the filter; a geometry for which cfear_cacfar_plan reports
+ * cols_supported = 0 returns CFEAR_ERR_INVALID_ARGUMENT (rotate with cfear_polar_rotate_ccw first, as the odometry does).
+ * Other flag bits are refused.  kcap >= 1.                                                                                  */
+int cfear_filter_cacfar_rowkeys(cfear_ctx* ctx, const uint8_t* polar, const cfear_polar_desc* desc,
+                                const cfear_cacfar_params* par, int32_t flags, uint32_t* row_keys, int32_t* row_counts,
+                                int32_t kcap);
+
 /* Cen and Newman's 2018 landmark detector: replaces cen2018features (coral_alignment_quality/src/alignment_checker/
  * Utils.cpp:348-434) and the cloud loop of Cen2018Radar (ScanType.cpp:68-88).  Per azimuth row: f = v / 255, q = f - mean(f)
  * (serial float sum), p = q filtered with 3 * sigma_gauss Gaussian taps (BORDER_REFLECT101), sigma = sqrt(mean of 2 q^2 over

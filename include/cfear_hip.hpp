@@ -247,6 +247,19 @@ class StructuredKStrongest {
   PointCloud all_, peaks_;
 };
 
+// AzimuthCACFAR as the batched odometry runs it (no counterpart in the reference): the kernel selection of a call, and the
+// filter stage on its own with per-row keys in device memory (cfear_hip.h: cfear_cacfar_plan, cfear_filter_cacfar_rowkeys)
+inline struct cfear_cacfar_plan cacfar_plan(const cfear_polar_desc& desc, const cfear_cacfar_params& par, int32_t flags = 0) {
+  struct cfear_cacfar_plan out;
+  const int st = ::cfear_cacfar_plan(&desc, &par, flags, &out);
+  if (st != CFEAR_OK) throw CfearError(st, cfear_status_string(st));
+  return out;
+}
+inline void filter_cacfar_rowkeys(Context& ctx, const uint8_t* d_image, const cfear_polar_desc& desc, const cfear_cacfar_params& par,
+                                  int32_t flags, uint32_t* d_row_keys, int32_t* d_row_counts, int32_t kcap) {
+  ctx.check(cfear_filter_cacfar_rowkeys(ctx.get(), d_image, &desc, &par, flags, d_row_keys, d_row_counts, kcap));
+}
+
 // k_strongest_filter (radar_filters.cpp:40-78, with InsertStrongestK :25-38): the legacy filter CorAl's kstrongRadar calls;
 // APPENDS to cloud
 inline void k_strongest_filter(Context& ctx, const uint8_t* image, int rows, int cols, int stride, PointCloud& cloud, int k_strongest,

@@ -58,6 +58,15 @@ class CacfarParams(C.Structure):
                 ("max_distance", C.c_double)]
 
 
+class CacfarPlan(C.Structure):     # struct cfear_cacfar_plan
+    _fields_ = [(n, C.c_int32) for n in ("D", "DL", "nch", "wide", "pre_on", "lut_ok", "need_cols", "colsp", "bin_lo", "bin_hi",
+                                         "pad_lo", "pad_hi", "keys", "cols_route", "cols_supported", "table_index")] + \
+               [(n, C.c_int64) for n in ("lds_bytes", "piece_rows", "total_rows")]
+
+
+ROWKEYS_BINS_MAJOR, CACFAR_PLAN_KEYS = 1, 0x100      # CFEAR_ROWKEYS_BINS_MAJOR, CFEAR_CACFAR_PLAN_KEYS
+
+
 class Cen2018Params(C.Structure):
     _fields_ = [("zq", C.c_float), ("sigma_gauss", C.c_int32), ("min_range_bins", C.c_int32), ("pad", C.c_int32),
                 ("range_res", C.c_double)]
@@ -274,6 +283,7 @@ EXPORTS = [
     "cfear_kitti_from_xyt", "cfear_cen2018_params_default", "cfear_filter_cen2018",
     "cfear_logreg_params_default", "cfear_logreg_fit_batch", "cfear_p2p_quality", "cfear_p2p_quality_batch",
     "cfear_cart_params_default", "cfear_polar_to_cartesian", "cfear_cart_quality_batch",
+    "cfear_cacfar_plan", "cfear_filter_cacfar_rowkeys",
 ]
 
 PIPE_GRAPH, PIPE_TIMING = 1, 2      # enum { CFEAR_PIPE_GRAPH, CFEAR_PIPE_TIMING }
@@ -411,6 +421,8 @@ def lib():
                                           C.POINTER(KStrongOut)]
     L.cfear_filter_cacfar.argtypes = [vp, vp, C.POINTER(PolarDesc), C.POINTER(CacfarParams), vp, vp,
                                       C.c_int32, vp]
+    L.cfear_cacfar_plan.argtypes = [C.POINTER(PolarDesc), C.POINTER(CacfarParams), C.c_int32, C.POINTER(CacfarPlan)]
+    L.cfear_filter_cacfar_rowkeys.argtypes = [vp, vp, C.POINTER(PolarDesc), C.POINTER(CacfarParams), C.c_int32, vp, vp, C.c_int32]
     L.cfear_cen2018_params_default.argtypes = [C.POINTER(Cen2018Params)]
     L.cfear_cen2018_params_default.restype = None
     L.cfear_filter_cen2018.argtypes = [vp, vp, C.POINTER(PolarDesc), C.POINTER(Cen2018Params), vp, vp, C.c_int32, vp, vp, vp]

@@ -234,7 +234,8 @@ def filter_kstrongest_rowkeys(img, k, z_min, range_res, min_distance, bins_major
 
 def filter_cacfar(img, window_size, nb_guard_cells, false_alarm_rate, range_res, z_min, min_distance,
                   max_distance=400.0, cap_points=None, want_mask=False, ctx=None):
-    """AzimuthCACFAR::getFilteredPointCloud (cfar.cpp:35-71).  Returns dict(xyzi, n_points[, det_mask])."""
+    """AzimuthCACFAR::getFilteredPointCloud (cfar.cpp:35-71).  Returns dict(xyzi, n_points[, det_mask]).  A torch CUDA view
+    with a row pitch or a batch stride is used in place."""
     ctx = ctx or default_context()
     d, batch, rows, cols = _desc(img)
     cap = int(cap_points or rows * cols)
@@ -242,6 +243,9 @@ def filter_cacfar(img, window_size, nb_guard_cells, false_alarm_rate, range_res,
                          float(z_min), float(min_distance), float(max_distance))
     if _is_torch(img):
         import torch
+        assert img.dtype == torch.uint8 and img.stride(-1) == 1
+        d.stride = img.stride(-2)
+        d.batch_stride = img.stride(0) if img.ndim == 3 else rows * d.stride
         xyzi = torch.empty((batch, cap, 4), dtype=torch.float32, device=img.device)
         npts = torch.empty((batch,), dtype=torch.int32, device=img.device)
         mask = torch.empty((batch, rows, cols), dtype=torch.uint8, device=img.device) if want_mask else None
@@ -250,12 +254,55 @@ def filter_cacfar(img, window_size, nb_guard_cells, false_alarm_rate, range_res,
         xyzi = np.empty((batch, cap, 4), np.float32)
         npts = np.empty((batch,), np.int32)
         mask = np.empty((batch, rows, cols), np.uint8) if want_mask else None
-    ctx.check(ctx._lib.cfear_filter_cacfar(ctx.h, _ptr(img)[0], C.byref(d), C.byref(par), _ptr(xyzi)[0],
+    ctx.check(ctx._lib.cfear_filter_cacfar(ctx.h, img.data_ptr() if _is_torch(img) else _ptr(img)[0], C.byref(d), C.byref(par), _ptr(xyzi)[0],
                                            _ptr(npts)[0], cap, _ptr(mask)[0]))
     res = dict(xyzi=xyzi, n_points=npts)
     if want_mask:
         res["det_mask"] = mask
     return res
+
+
+def cacfar_plan(rows, cols, window_size, nb_guard_cells, false_alarm_rate, range_res, z_min, min_distance, max_distance=400.0,
+                keys=False, bins_major=False, stride=None, batch=1, batch_stride=None, base=0):
+    """cfear_cacfar_plan: which CA-CFAR kernel instantiation a call launches and with which geometry, as a dict of the
+    struct's fields (include/cfear_hip.h).  Host code only: needs no GPU and no context.  rows, cols (, stride, batch,
+    batch_stride): the images as the filter call gets them (bins_major: [range bins][azimuths]); keys: the key output
+    (filter_cacfar_rowkeys, the batched odometry) instead of the bitmap of filter_cacfar; base: the image address."""
+    d = L.PolarDesc()
+    d.rows, d.cols, d.batch = int(rows), int(cols), int(batch)
+    d.stride = int(cols if stride is None else stride)
+    d.batch_stride = int(d.rows * d.stride if batch_stride is None else batch_stride)
+    par = L.CacfarParams(int(window_size), int(nb_guard_cells), float(false_alarm_rate), float(range_res),
+                         float(z_min), float(min_distance), float(max_distance))
+    flags = (L.ROWKEYS_BINS_MAJOR if bins_major else 0) | (L.CACFAR_PLAN_KEYS if keys else 0) | ((int(base) & 15) << 12)
+    out = L.CacfarPlan()
+    rc = L.lib().cfear_cacfar_plan(C.byref(d), C.byref(par), flags, C.byref(out))
+    if rc != 0:
+        raise L.CfearError(rc, "cfear_cacfar_plan: bad descriptor or parameters")
+    return {name: int(getattr(out, name)) for name, _ in L.CacfarPlan._fields_}
+
+
+def filter_cacfar_rowkeys(img, window_size, nb_guard_cells, false_alarm_rate, range_res, z_min, min_distance,
+                          max_distance=400.0, kcap=1024, bins_major=False, ctx=None):
+    """cfear_filter_cacfar_rowkeys: the batched odometry's CA-CFAR stage on its own, for a torch CUDA uint8 image
+    [rows, cols] or batch [b, rows, cols] (a view with a row pitch / batch stride is used in place); bins_major: the
+    images are [range bins][azimuths] and are decoded by the filter itself.
+    Returns (row_keys uint32-as-int32 [b, azimuths, kcap] (intensity << 24 | bin, ascending bins; zero beyond a row's
+    min(count, kcap)), row_counts int32 [b, azimuths, 2] ({detections, 0})) as CUDA tensors."""
+    import torch
+    ctx = ctx or default_context()
+    d, batch, rows, cols = _desc(img)
+    assert img.dtype == torch.uint8 and img.stride(-1) == 1
+    d.stride = img.stride(-2)
+    d.batch_stride = img.stride(0) if img.ndim == 3 else rows * d.stride
+    az = cols if bins_major else rows
+    par = L.CacfarParams(int(window_size), int(nb_guard_cells), float(false_alarm_rate), float(range_res),
+                         float(z_min), float(min_distance), float(max_distance))
+    keys = torch.zeros((batch, az, int(kcap)), dtype=torch.int32, device=img.device)
+    cnt = torch.zeros((batch, az, 2), dtype=torch.int32, device=img.device)
+    ctx.check(ctx._lib.cfear_filter_cacfar_rowkeys(ctx.h, img.data_ptr(), C.byref(d), C.byref(par), 1 if bins_major else 0,
+                                                   _ptr(keys)[0], _ptr(cnt)[0], int(kcap)))
+    return keys, cnt
 
 
 def cen2018_params(**kw):

@@ -23,6 +23,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "row_pieces.hpp"
 
 namespace {
 
@@ -63,8 +64,8 @@ __device__ __forceinline__ uint32_t swar_ge(uint32_t x, uint32_t tl4, bool thi) 
 
 // Reads the row into registers: lane L of chunk c owns bytes [(c*64+L)*16, +16).  Lanes whose chunk
 // lies entirely past the row end hold zeros and issue no loads.
-// tail_safe: the 16 bytes of the row's LAST, partial piece may be read whole (they end inside the image: every row but an
-// image's last one) -- the bytes beyond the row are then cleared in registers.  Without it the piece is gathered byte by byte:
+// tail_safe: the 16 bytes of the row's LAST, partial piece may be read whole (they end inside the image:
+// cfear_piece_inside_image, row_pieces.hpp) -- the bytes beyond the row are then cleared in registers.  Without it the piece is gathered byte by byte:
 // sixteen dependent predicated loads on one lane that the whole wavefront waits for (Oxford's native 3768 bins end 8 bytes into
 // a piece: 0.220 instead of 0.159 ms per 512 sweeps until round 6).
 template <int NCHUNK, bool VEC>
@@ -182,7 +183,7 @@ __device__ __forceinline__ void kstrong_row(const KStrongArgs& a, const int r, c
       w[c * 4] = v.x; w[c * 4 + 1] = v.y; w[c * 4 + 2] = v.z; w[c * 4 + 3] = v.w;
     }
   } else {
-    load_row<NCHUNK, VEC>(rowp, a.cols, lane, w, r + 1 < a.rows);
+    load_row<NCHUNK, VEC>(rowp, a.cols, lane, w, cfear_piece_inside_image(r, a.cols & ~15, a.rows, a.stride));
 #pragma unroll
     for (int c = 0; c < NCHUNK; c++)                 // stage the row: candidate bytes are fetched by position
       *(uint4*)(rowbuf + (c * 64 + lane) * 16) = make_uint4(w[c * 4], w[c * 4 + 1], w[c * 4 + 2], w[c * 4 + 3]);
@@ -1455,14 +1456,15 @@ __global__ __launch_bounds__(256) void cacfar_rows_kernel(const CfarArgs a) {
   int cb = (int)(grow / a.rows), cr = (int)(grow - (long long)cb * a.rows);
   auto row_ptr = [&](int b, int r) -> const uint8_t* { return a.polar + (long long)b * a.batch_stride + (long long)r * a.stride; };
   // Rows are read in 16-byte pieces wherever they start on a 4-byte boundary (global_load_dwordx4 asks for no more).  A row whose
-  // length is not a multiple of 16 (Oxford's native 3768 bins) ends inside its last piece: that piece is read whole -- it ends
-  // inside the image for every row but the image's last -- and the bytes beyond the row are cleared in registers (mask_tail), as
-  // the byte-wise copy below leaves them.  Only rows on odd addresses and the last row of a ragged image are copied into LDS byte
-  // by byte, zero-padded, and take their pieces from there (no prefetch).  (Until round 6 every ragged or 8-byte-aligned row took
+  // length is not a multiple of 16 (Oxford's native 3768 bins) ends inside its last piece: that piece is read whole where it ends
+  // inside the image (cfear_cfar_row_direct, row_pieces.hpp: every row but the image's last, and with a stride below 16 bytes not
+  // the rows just before it either) and the bytes beyond the row are cleared in registers (mask_tail), as the byte-wise copy
+  // below leaves them.  Only rows on odd addresses and those last rows of a ragged image are copied into LDS byte by byte,
+  // zero-padded, and take their pieces from there (no prefetch).  (Until round 6 every ragged or 8-byte-aligned row took
   // the byte copy: 1.42 instead of 0.43 ms per 512 sweeps of 3768 bins.)
   const bool ragged = (a.cols & 15) != 0;
   auto is_direct = [&](const uint8_t* p, const int row) -> bool {
-    return (((uintptr_t)p) & 3) == 0 && (a.stride & 3) == 0 && !(ragged && row == a.rows - 1);
+    return cfear_cfar_row_direct((unsigned)((uintptr_t)p & 3), row, a.rows, a.stride, a.need_cols);
   };
   // a lane's LB bytes of a chunk: 16-byte pieces where LB is a multiple of 16 (D = 4, 8), 8-byte pieces otherwise (D = 6:
   // 24 lane is only 8-byte aligned, and ds_write_b128 wants 16)
@@ -2310,9 +2312,12 @@ static void cfar_derive(CfarArgs& a, const cfear_cacfar_params* par, int rows, i
     for (int d : {6, 8}) {
       const int n = std::max(1, (a.need_cols + 256 * d - 1) / (256 * d));
       if (cost(n, d, d) < best) { best = cost(n, d, d); D = d; DL = d; nch = n; }
-      if (n == 2)                                          // two chunks: the second may be shorter
-        for (int dl = 2; dl < d; dl += 2)
-          if (256 * d + 256 * dl >= a.need_cols && cost(2, d, dl) < best) { best = cost(2, d, dl); D = d; DL = dl; nch = 2; }
+      if (n == 2) {                                        // two chunks: the second may be two dwords shorter.  (Shorter still --
+        const int dl = d - 2;                              // 6 | 2, 8 | 2, 8 | 4 -- never costs LESS than a geometry tried before it:
+                                                           // 4 x 2, 6 | 4 and 6 x 2 cover the same bins at the same cost, so those
+                                                           // were never selected and are not built; tests/test_cacfar_plan_cpu.py)
+        if (256 * d + 256 * dl >= a.need_cols && cost(2, d, dl) < best) { best = cost(2, d, dl); D = d; DL = dl; nch = 2; }
+      }
     }
   }
   a.colsp = (nch - 1) * 256 * D + 256 * DL;
@@ -2322,16 +2327,108 @@ static size_t cfar_cols_lds(const CfarArgs& a, int D) {
   return 1024 + (size_t)kCfarTile * ((size_t)a.need_cols + 16) + (size_t)kCfarColsWaves * cfar_cols_wave_lds(a.colsp, a.pad_lo, a.pad_hi, 256 * D);
 }
 
-// [range bins][azimuths] sources through cacfar_cols_kernel: sd = the SOURCE images (rows = bins, cols = azimuths).
-bool cfear_cacfar_cols_supported(const uint8_t* d_src, const cfear_polar_desc* sd, const cfear_cacfar_params* par) {
-  if (sd->cols % kCfarTile != 0 || sd->rows % 16 != 0 || sd->stride % 16 != 0 || (uintptr_t)d_src % 16 != 0 ||
-      (sd->batch > 1 && sd->batch_stride % 16 != 0) || (int64_t)sd->rows * sd->stride >= ((int64_t)1 << 31))
-    return false;
+// ---- the dispatch tables: every CA-CFAR kernel that is built, and nothing else launches one ---------------------------------
+// cfear_cacfar_plan (cfear_hip.h) documents the indices; cfar_rows_index / cfar_cols_index return -1 for a geometry that is
+// not built (cfar_derive selects none: tests/test_cacfar_plan_cpu.py sweeps it).
+using CfarRowsFn = void (*)(const CfarArgs);
+using CfarColsFn = void (*)(const CfarArgs, int);
+constexpr int kCfarRowsEntries = 20, kCfarColsEntries = 6;
+static const CfarRowsFn kCfarRowsTable[kCfarRowsEntries] = {
+    // D = 4: [wide][keys][pre]
+    cacfar_rows_kernel<4, 4, 4, false, false>, cacfar_rows_kernel<4, 4, 4, false, true>,
+    cacfar_rows_kernel<4, 4, 4, true, false>, cacfar_rows_kernel<4, 4, 4, true, true>,
+    cacfar_rows_kernel<4, 8, 4, false, false>, cacfar_rows_kernel<4, 8, 4, false, true>,
+    cacfar_rows_kernel<4, 8, 4, true, false>, cacfar_rows_kernel<4, 8, 4, true, true>,
+    // D = 6, whole chunks: [nch > 2][keys]; DL = 4: [keys]
+    cacfar_rows_kernel<6, 2, 6, false, true>, cacfar_rows_kernel<6, 2, 6, true, true>,
+    cacfar_rows_kernel<6, 6, 6, false, true>, cacfar_rows_kernel<6, 6, 6, true, true>,
+    cacfar_rows_kernel<6, 2, 4, false, true>, cacfar_rows_kernel<6, 2, 4, true, true>,
+    // D = 8, whole chunks: [nch > 2][keys]; DL = 6: [keys]
+    cacfar_rows_kernel<8, 2, 8, false, true>, cacfar_rows_kernel<8, 2, 8, true, true>,
+    cacfar_rows_kernel<8, 4, 8, false, true>, cacfar_rows_kernel<8, 4, 8, true, true>,
+    cacfar_rows_kernel<8, 2, 6, false, true>, cacfar_rows_kernel<8, 2, 6, true, true>};
+static const CfarColsFn kCfarColsTable[kCfarColsEntries] = {
+    cacfar_cols_kernel<4, 4, 4, false>, cacfar_cols_kernel<4, 4, 4, true>,
+    cacfar_cols_kernel<6, 2, 4, true>, cacfar_cols_kernel<6, 2, 6, true>,       // (colsp <= 4096: at most two chunks of 1536)
+    cacfar_cols_kernel<8, 2, 6, true>, cacfar_cols_kernel<8, 2, 8, true>};
+
+static int cfar_rows_index(int D, int DL, int nch, bool keys, bool pre) {
+  const int k = keys ? 1 : 0;
+  if (D == 4) return DL == 4 && nch <= 8 ? (nch > 4 ? 4 : 0) + 2 * k + (pre ? 1 : 0) : -1;
+  if (!pre) return -1;                                       // (without the pre-filter only D = 4 is built)
+  if (D == 6) return DL == 6 ? (nch <= 6 ? 8 + (nch > 2 ? 2 : 0) + k : -1) : (DL == 4 && nch == 2 ? 12 + k : -1);
+  if (D == 8) return DL == 8 ? (nch <= 4 ? 14 + (nch > 2 ? 2 : 0) + k : -1) : (DL == 6 && nch == 2 ? 18 + k : -1);
+  return -1;
+}
+static int cfar_cols_index(int D, int DL, int nch, bool pre) {
+  if (D == 4) return DL == 4 && nch <= 4 ? (pre ? 1 : 0) : -1;
+  if (!pre || nch > 2 || (DL != D && nch != 2)) return -1;
+  if (D == 6) return DL == 4 ? 2 : (DL == 6 ? 3 : -1);
+  if (D == 8) return DL == 6 ? 4 : (DL == 8 ? 5 : -1);
+  return -1;
+}
+
+// The one selection: everything cfear_cacfar_device launches follows from the plan this fills (and `a`, the kernel arguments
+// that follow from the parameters).  desc as the caller hands it over (cols_route: the [range bins][azimuths] SOURCE images);
+// base_mod16 = the image address modulo 16.
+static void cfar_plan(CfarArgs& a, const cfear_polar_desc* desc, const cfear_cacfar_params* par, bool keys, bool cols_route,
+                      unsigned base_mod16, struct cfear_cacfar_plan& p) {
+  const int rows = cols_route ? desc->cols : desc->rows, cols = cols_route ? desc->rows : desc->cols, batch = desc->batch;
+  int D, DL, nch;
+  cfar_derive(a, par, rows, cols, D, DL, nch);
+  memset(&p, 0, sizeof(p));
+  p.D = D; p.DL = DL; p.nch = nch;
+  p.pre_on = a.pre_on; p.lut_ok = a.lut_ok;
+  p.need_cols = a.need_cols; p.colsp = a.colsp; p.bin_lo = a.bin_lo; p.bin_hi = a.bin_hi;
+  p.pad_lo = a.pad_lo; p.pad_hi = a.pad_hi;
+  p.keys = keys ? 1 : 0; p.cols_route = cols_route ? 1 : 0;
+  p.total_rows = (int64_t)batch * rows;
+  const int64_t batch_stride = batch > 1 ? desc->batch_stride : (int64_t)desc->rows * desc->stride;
+  if (cols_route) {
+    p.table_index = cfar_cols_index(D, DL, nch, a.pre_on != 0);
+    p.lds_bytes = (int64_t)cfar_cols_lds(a, D);
+    const bool geometry = desc->cols % kCfarTile == 0 && desc->rows % 16 == 0 && desc->stride % 16 == 0 && base_mod16 == 0 &&
+                          !(batch > 1 && desc->batch_stride % 16 != 0) && (int64_t)desc->rows * desc->stride < ((int64_t)1 << 31);
+    p.cols_supported = geometry && p.table_index >= 0 && a.colsp <= 4096 && p.lds_bytes <= 160 * 1024 - 256;
+    return;
+  }
+  p.wide = D == 4 && nch > 4;
+  p.table_index = cfar_rows_index(D, DL, nch, keys, a.pre_on != 0);
+  p.lds_bytes = (int64_t)(1024 + (size_t)kRowsPerBlock * cfar_wave_lds(a.colsp, a.pad_lo, a.pad_hi, keys, 256 * D));
+  // rows read in 16-byte pieces: the kernel's own test (cfear_cfar_row_direct), image by image
+  int64_t inside = 0;                                        // rows of an image whose last piece ends inside it
+  for (int r = 0; r < rows; r++) inside += cfear_cfar_row_direct(0u, r, rows, desc->stride, a.need_cols) ? 1 : 0;
+  if ((batch_stride & 3) == 0) p.piece_rows = (base_mod16 & 3) == 0 ? inside * batch : 0;
+  else
+    for (int b = 0; b < batch; b++) p.piece_rows += (((int64_t)base_mod16 + (int64_t)b * batch_stride) & 3) == 0 ? inside : 0;
+}
+
+static int cfar_check_params(const cfear_cacfar_params* par) {
+  return par && par->window_size >= 1 && par->nb_guard_cells >= 0 && par->range_res > 0.f;
+}
+
+extern "C" int cfear_cacfar_plan(const cfear_polar_desc* desc, const cfear_cacfar_params* par, int32_t flags,
+                                 struct cfear_cacfar_plan* out) {
+  if (!desc || !par || !out || (flags & ~(CFEAR_ROWKEYS_BINS_MAJOR | CFEAR_CACFAR_PLAN_KEYS | (15 << 12))) != 0)
+    return CFEAR_ERR_INVALID_ARGUMENT;
+  const bool cols_route = (flags & CFEAR_ROWKEYS_BINS_MAJOR) != 0;
+  if (desc->rows <= 0 || desc->cols <= 0 || desc->stride < desc->cols || desc->batch <= 0 ||
+      (desc->batch > 1 && desc->batch_stride < (int64_t)desc->rows * desc->stride) ||
+      (cols_route ? desc->rows : desc->cols) > kMaxCols || !cfar_check_params(par))
+    return CFEAR_ERR_INVALID_ARGUMENT;
   CfarArgs a;
   memset(&a, 0, sizeof(a));
-  int D, DL, nch;
-  cfar_derive(a, par, sd->cols, sd->rows, D, DL, nch);
-  return a.colsp <= 4096 && cfar_cols_lds(a, D) <= 160 * 1024 - 256;
+  cfar_plan(a, desc, par, cols_route || (flags & CFEAR_CACFAR_PLAN_KEYS) != 0, cols_route, (unsigned)(flags >> 12) & 15u, *out);
+  return CFEAR_OK;
+}
+
+// [range bins][azimuths] sources through cacfar_cols_kernel: sd = the SOURCE images (rows = bins, cols = azimuths).
+bool cfear_cacfar_cols_supported(const uint8_t* d_src, const cfear_polar_desc* sd, const cfear_cacfar_params* par) {
+  CfarArgs a;
+  memset(&a, 0, sizeof(a));
+  struct cfear_cacfar_plan p;
+  cfar_plan(a, sd, par, true, true, (unsigned)((uintptr_t)d_src & 15), p);
+  return p.cols_supported != 0;
 }
 
 // Device-side CA-CFAR entry (also used by the odometry pipeline).  With `fused` the rows kernel leaves per-row key lists for
@@ -2342,18 +2439,21 @@ int cfear_cacfar_device(cfear_ctx* ctx, const uint8_t* d_polar, const cfear_pola
                         int32_t cap_points, uint8_t* d_det_mask, const cfear_cacfar_fused* fused) {
   const bool keys = fused && fused->row_keys;
   const bool cols_route = keys && fused->bins_major;
-  if (cols_route && !cfear_cacfar_cols_supported(d_polar, desc, par))
-    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "fused CA-CFAR decode: unsupported image geometry");
-  const int rows = cols_route ? desc->cols : desc->rows, cols = cols_route ? desc->rows : desc->cols, batch = desc->batch;
-  const int words = (cols + 63) / 64;
   CfarArgs a;
   memset(&a, 0, sizeof(a));
+  struct cfear_cacfar_plan plan;
+  cfar_plan(a, desc, par, keys, cols_route, (unsigned)((uintptr_t)d_polar & 15), plan);
+  if (cols_route && !plan.cols_supported)
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "fused CA-CFAR decode: unsupported image geometry");
+  if (plan.table_index < 0 || plan.table_index >= (cols_route ? kCfarColsEntries : kCfarRowsEntries))   // a missing kernel is an error
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "CA-CFAR: no kernel for D = %d, DL = %d, %d chunks", plan.D, plan.DL, plan.nch);
+  const int rows = cols_route ? desc->cols : desc->rows, cols = cols_route ? desc->rows : desc->cols, batch = desc->batch;
+  const int words = (cols + 63) / 64;
+  const int D = plan.D;
   a.polar = d_polar; a.stride = desc->stride; a.batch = batch;
   a.batch_stride = batch > 1 ? desc->batch_stride : (int64_t)desc->rows * desc->stride;
   a.total_rows = (long long)batch * rows;
   a.words = words;
-  int D, DL, nch;
-  cfar_derive(a, par, rows, cols, D, DL, nch);
   if (keys) {
     a.row_keys = fused->row_keys; a.row_cnt = fused->row_cnt; a.kcap = fused->kcap;
   } else {
@@ -2365,19 +2465,8 @@ int cfear_cacfar_device(cfear_ctx* ctx, const uint8_t* d_polar, const cfear_pola
   }
   a.list_cap = cols_route ? cfar_cols_list_cap(256 * D) : 256 * D + kCfarListSlack;
   if (cols_route) {
-    using ColsFn = void (*)(const CfarArgs, int);
-    const bool pre = a.pre_on != 0;
-    ColsFn fn = nullptr;
-    if (D == 4) {
-      fn = pre ? cacfar_cols_kernel<4, 4, 4, true> : cacfar_cols_kernel<4, 4, 4, false>;
-    } else if (D == 6) {
-      static const ColsFn f6s[2] = {cacfar_cols_kernel<6, 2, 2, true>, cacfar_cols_kernel<6, 2, 4, true>};
-      fn = DL != D ? f6s[DL / 2 - 1] : (ColsFn)cacfar_cols_kernel<6, 2, 6, true>;   // (colsp <= 4096: at most two chunks of 1536)
-    } else {
-      static const ColsFn f8s[3] = {cacfar_cols_kernel<8, 2, 2, true>, cacfar_cols_kernel<8, 2, 4, true>, cacfar_cols_kernel<8, 2, 6, true>};
-      fn = DL != D ? f8s[DL / 2 - 1] : (ColsFn)cacfar_cols_kernel<8, 2, 8, true>;
-    }
-    const size_t lds = cfar_cols_lds(a, D);
+    const CfarColsFn fn = kCfarColsTable[plan.table_index];
+    const size_t lds = (size_t)plan.lds_bytes;
     { const int rc_lds = cfear_allow_lds(ctx, (const void*)fn, lds); if (rc_lds != CFEAR_OK) return rc_lds; }
     const int n_cu = ctx->n_cu;
     const int tiles = rows / kCfarTile;
@@ -2390,30 +2479,8 @@ int cfear_cacfar_device(cfear_ctx* ctx, const uint8_t* d_polar, const cfear_pola
     return CFEAR_OK;
   }
   {
-    const bool pre = a.pre_on != 0;
-    using KernelFn = void (*)(const CfarArgs);
-    KernelFn fn = nullptr;
-    if (D == 4) {
-      const bool wide = nch > 4;
-      static const KernelFn f4[2][2][2] = {   // [wide][keys][pre]
-          {{cacfar_rows_kernel<4, 4, 4, false, false>, cacfar_rows_kernel<4, 4, 4, false, true>}, {cacfar_rows_kernel<4, 4, 4, true, false>, cacfar_rows_kernel<4, 4, 4, true, true>}},
-          {{cacfar_rows_kernel<4, 8, 4, false, false>, cacfar_rows_kernel<4, 8, 4, false, true>}, {cacfar_rows_kernel<4, 8, 4, true, false>, cacfar_rows_kernel<4, 8, 4, true, true>}}};
-      fn = f4[wide ? 1 : 0][keys ? 1 : 0][pre ? 1 : 0];
-    } else if (D == 6) {
-      static const KernelFn f6[2][2] = {{cacfar_rows_kernel<6, 2, 6, false, true>, cacfar_rows_kernel<6, 2, 6, true, true>},
-                                        {cacfar_rows_kernel<6, 6, 6, false, true>, cacfar_rows_kernel<6, 6, 6, true, true>}};
-      static const KernelFn f6s[2][2] = {{cacfar_rows_kernel<6, 2, 2, false, true>, cacfar_rows_kernel<6, 2, 2, true, true>},
-                                         {cacfar_rows_kernel<6, 2, 4, false, true>, cacfar_rows_kernel<6, 2, 4, true, true>}};
-      fn = DL != D ? f6s[DL / 2 - 1][keys ? 1 : 0] : f6[nch > 2 ? 1 : 0][keys ? 1 : 0];
-    } else {
-      static const KernelFn f8[2][2] = {{cacfar_rows_kernel<8, 2, 8, false, true>, cacfar_rows_kernel<8, 2, 8, true, true>},
-                                        {cacfar_rows_kernel<8, 4, 8, false, true>, cacfar_rows_kernel<8, 4, 8, true, true>}};
-      static const KernelFn f8s[3][2] = {{cacfar_rows_kernel<8, 2, 2, false, true>, cacfar_rows_kernel<8, 2, 2, true, true>},
-                                         {cacfar_rows_kernel<8, 2, 4, false, true>, cacfar_rows_kernel<8, 2, 4, true, true>},
-                                         {cacfar_rows_kernel<8, 2, 6, false, true>, cacfar_rows_kernel<8, 2, 6, true, true>}};
-      fn = DL != D ? f8s[DL / 2 - 1][keys ? 1 : 0] : f8[nch > 2 ? 1 : 0][keys ? 1 : 0];
-    }
-    const size_t rows_lds = 1024 + (size_t)kRowsPerBlock * cfar_wave_lds(a.colsp, a.pad_lo, a.pad_hi, keys, 256 * D);
+    const CfarRowsFn fn = kCfarRowsTable[plan.table_index];
+    const size_t rows_lds = (size_t)plan.lds_bytes;
     if (rows_lds > 64 * 1024)
       { const int rc_lds = cfear_allow_lds(ctx, (const void*)fn, rows_lds); if (rc_lds != CFEAR_OK) return rc_lds; }
     // persistent wavefronts: as many workgroups as the chip holds at this LDS footprint (160 KiB per CU)
@@ -2440,6 +2507,27 @@ int cfear_cacfar_device(cfear_ctx* ctx, const uint8_t* d_polar, const cfear_pola
   }
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
   return CFEAR_OK;
+}
+
+extern "C" int cfear_filter_cacfar_rowkeys(cfear_ctx* ctx, const uint8_t* polar, const cfear_polar_desc* desc,
+                                           const cfear_cacfar_params* par, int32_t flags, uint32_t* row_keys,
+                                           int32_t* row_counts, int32_t kcap) {
+  if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
+  if (!polar || !par || !row_keys || !row_counts) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
+  if ((flags & ~CFEAR_ROWKEYS_BINS_MAJOR) != 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "unknown flags");
+  const bool bins_major = (flags & CFEAR_ROWKEYS_BINS_MAJOR) != 0;
+  if (!desc || desc->rows <= 0 || desc->cols <= 0 || desc->stride < desc->cols || desc->batch <= 0 ||
+      (desc->batch > 1 && desc->batch_stride < (int64_t)desc->rows * desc->stride) ||
+      (bins_major ? desc->rows : desc->cols) > kMaxCols)
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "bad polar descriptor");
+  if (!cfar_check_params(par)) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "bad CFAR parameters");
+  if (kcap < 1) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "kcap must be >= 1");
+  if (!cfear_is_device_ptr(polar) || !cfear_is_device_ptr(row_keys) || !cfear_is_device_ptr(row_counts))
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "images and outputs must be device memory");
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  cfear_cacfar_fused fz;
+  fz.row_keys = row_keys; fz.row_cnt = row_counts; fz.kcap = kcap; fz.bins_major = bins_major;
+  return cfear_cacfar_device(ctx, polar, desc, par, nullptr, nullptr, 0, nullptr, &fz);
 }
 
 extern "C" int cfear_filter_cacfar(cfear_ctx* ctx, const uint8_t* polar, const cfear_polar_desc* desc,

@@ -196,7 +196,8 @@ def test_cacfar_rotated_input_takes_the_fused_decode(case):
     before Process()): from 16 streams on the decode is fused into the filter -- cacfar_cols_kernel transposes 16-azimuth tiles
     into LDS and runs the row algorithm there, no rotated copy -- and the frames must equal (a) the same sweeps fed
     pre-rotated, field by field, and (b) the oracle's CA-CFAR of np.rot90(sweep) followed by its fuser.  The cases move the
-    range window so that the reachable bins need every chunk geometry (D = 4 / 6 / 8 dwords per lane, shorter last chunk)."""
+    range window, and with it the reachable bins and the chunk geometry; which instantiation of cacfar_cols_kernel a parameter
+    set reaches, and that each one is right key by key, is pinned by tests/test_gpu_cacfar_matrix.py (tests/cacfar_cases.py)."""
     import torch
     from oracle import pyoracle as O
     from tbv_slam_public_amd import api, synth
