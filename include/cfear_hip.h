@@ -1303,6 +1303,56 @@ typedef struct cfear_logreg_result {
 int cfear_logreg_fit_batch(cfear_ctx* ctx, const cfear_logreg_job* jobs, int32_t n_jobs, const cfear_logreg_params* par,
                            cfear_logreg_result* results);
 
+/* ---- after the path: loop candidates without descriptors (GTVicinityClosure, MiniClosure) ----------------------------
+ * The two candidate generators of the reference's loop-closure thread that read only poses and odometry:
+ * GTVicinityClosure::SearchAndAddConstraint (tbv_slam/src/tbv_slam/loopclosure.cpp:394-467), which finds the pairs the
+ * loop classifiers are trained and evaluated on, and MiniClosure::SearchAndAddConstraint (:469-552, --miniloop-enabled).
+ * For each origin node i of each graph, over the later nodes j = i + 1 .. n - 1, in fp64 (csrc/closure.hip):
+ *     trav = trav + step[j - 1]                        trav starts at 0.0 for every origin: the reference's serial sum
+ *     eucl = sqrt((dx * dx + dy * dy) + dz * dz)       p_i - p_j
+ *     GTVicinity:  if eucl <= max_d_close and min_d_travel <= trav and trav <= max_d_travel:
+ *                      rel = eucl / trav;  if rel < best: best = rel, to = j
+ *     MiniClosure: if trav < min_d_travel: continue
+ *                  if trav > max_d_travel: exhausted = 1; break
+ *                  if eucl <= max_d_close: rel = eucl / trav;  if rel < best: best = rel, to = j
+ * best starts at DBL_MAX, so the first j wins a tie and an infinite or NaN rel (eucl / 0 with min_d_travel = 0) never
+ * wins.  This is the reference's FIRST SearchAndAddConstraint() call from fresh state on a complete graph (nothing
+ * attempted yet, itr_current = begin); continuing a streaming closure thread is the caller's business, and `exhausted`
+ * (origin_attempted_ would be set) is what it needs for that.  Every emitted pair also gets loopclosure::VerifyByOdometry
+ * (:776-806) in the arithmetic of cfear_verify_by_odometry.                                                             */
+#define CFEAR_CLOSURE_GTVICINITY 0
+#define CFEAR_CLOSURE_MINI 1
+#define CFEAR_CLOSURE_ORIGINS 64        /* origins (lanes) per workgroup of the sweep                                 */
+#define CFEAR_CLOSURE_TILE 256          /* later nodes staged per LDS tile; both exported so that tests can straddle them */
+typedef struct cfear_closure_params {
+  int32_t mode;                         /* CFEAR_CLOSURE_GTVICINITY or CFEAR_CLOSURE_MINI                             */
+  int32_t verify_via_odometry;          /* 1 (loopclosure.h:122); 0: odom_bounds of every pair is 1                  */
+  double min_d_travel, max_d_travel, max_d_close;   /* 40, 4200, 15 (loopclosure.h:84-86) / 25, 500, 15 (:95-97)     */
+  double odom_sigma_error;              /* 0.03 (:123)                                                               */
+} cfear_closure_params;                 /* 40 bytes */
+void cfear_closure_params_default(cfear_closure_params* p, int32_t mode);
+typedef struct cfear_closure_candidate {   /* one per origin node */
+  int32_t to;                           /* index within the graph of the chosen later node, -1 = none                */
+  int32_t exhausted;                    /* MiniClosure: origin_attempted_ would be set; 0 in GTVicinity mode         */
+  double eucl, trav, rel;               /* of the winner; 0 when to == -1                                            */
+  double odom_bounds;                   /* VerifyByOdometry(from = to-node, to = origin); 0 when to == -1 or rel_xyt == NULL */
+} cfear_closure_candidate;              /* 40 bytes */
+/* n_graphs graphs in one call.  Graph g owns nodes [node_offsets[g], node_offsets[g + 1]) of the flat arrays; node_offsets
+ * holds n_graphs + 1 entries, starts at 0 and ends at n_nodes.  positions [n_nodes][3], steps [n_nodes], rel_xyt
+ * [n_nodes][3] (optional) and out [n_nodes] all hold ONE ENTRY PER NODE, so the one offset table serves them all:
+ * steps[k] is the norm of t_be.p of the odometry constraint from flat node k to k + 1 as the caller computed it (its
+ * rounding holds), rel_xyt[k] is ConstraintsHandler::RelativeMotion of the same two nodes as a planar (x, y, theta); the
+ * entry of each graph's LAST node is ignored in both.  out[k].to counts within the graph.  Graphs of 0 or 1 nodes are
+ * legal and emit nothing.  All arrays are host memory; the call returns when out is written.  A graph's records are
+ * bit-identical whatever else the batch holds and wherever the graph sits in it.  Refused with
+ * CFEAR_ERR_INVALID_ARGUMENT before anything is launched or written, *failed_graph (optional; -1 otherwise) and
+ * cfear_last_error naming the graph: offsets that do not start at 0 (graph 0), do not end at n_nodes (the last graph) or
+ * decrease; a used step that is negative or not finite; a position that is not finite.  Also refused, with
+ * *failed_graph = -1: an unknown mode, a threshold that is NaN, null or device pointers.                              */
+int cfear_closure_candidates_batch(cfear_ctx* ctx, const double* positions, const double* steps, const double* rel_xyt,
+                                   const int64_t* node_offsets, int64_t n_nodes, int32_t n_graphs, const cfear_closure_params* par,
+                                   cfear_closure_candidate* out, int32_t* failed_graph);
+
 #ifdef __cplusplus
 }
 #endif

@@ -284,6 +284,7 @@ EXPORTS = [
     "cfear_logreg_params_default", "cfear_logreg_fit_batch", "cfear_p2p_quality", "cfear_p2p_quality_batch",
     "cfear_cart_params_default", "cfear_polar_to_cartesian", "cfear_cart_quality_batch",
     "cfear_cacfar_plan", "cfear_filter_cacfar_rowkeys",
+    "cfear_closure_params_default", "cfear_closure_candidates_batch",
 ]
 
 PIPE_GRAPH, PIPE_TIMING = 1, 2      # enum { CFEAR_PIPE_GRAPH, CFEAR_PIPE_TIMING }
@@ -379,6 +380,24 @@ LOGREG_RESULT_DTYPE = np.dtype([("intercept", "<f8"), ("coef", "<f8", (LOGREG_MA
                                 ("grad_inf", "<f8"), ("balanced_accuracy", "<f8"), ("n_used", "<i8"), ("n_pos", "<i8"),
                                 ("confusion", "<i8", (4,)), ("iterations", "<i4"), ("status", "<i4")])
 assert C.sizeof(LogregParams) == 24 and C.sizeof(LogregJob) == 48 and LOGREG_RESULT_DTYPE.itemsize == 152
+
+CLOSURE_MODE = {"gtvicinity": 0, "mini": 1}      # CFEAR_CLOSURE_GTVICINITY, CFEAR_CLOSURE_MINI
+CLOSURE_ORIGINS, CLOSURE_TILE = 64, 256           # CFEAR_CLOSURE_ORIGINS, CFEAR_CLOSURE_TILE
+
+
+class ClosureParams(C.Structure):   # cfear_closure_params
+    _fields_ = [("mode", C.c_int32), ("verify_via_odometry", C.c_int32), ("min_d_travel", C.c_double),
+                ("max_d_travel", C.c_double), ("max_d_close", C.c_double), ("odom_sigma_error", C.c_double)]
+
+
+class ClosureCandidate(C.Structure):    # cfear_closure_candidate
+    _fields_ = [("to", C.c_int32), ("exhausted", C.c_int32), ("eucl", C.c_double), ("trav", C.c_double), ("rel", C.c_double),
+                ("odom_bounds", C.c_double)]
+
+
+CLOSURE_CANDIDATE_DTYPE = np.dtype([("to", "<i4"), ("exhausted", "<i4"), ("eucl", "<f8"), ("trav", "<f8"), ("rel", "<f8"),
+                                    ("odom_bounds", "<f8")])
+assert C.sizeof(ClosureParams) == 40 and C.sizeof(ClosureCandidate) == 40 == CLOSURE_CANDIDATE_DTYPE.itemsize
 
 _LIB = None
 
@@ -553,5 +572,9 @@ def lib():
     L.cfear_logreg_params_default.argtypes = [C.POINTER(LogregParams)]
     L.cfear_logreg_params_default.restype = None
     L.cfear_logreg_fit_batch.argtypes = [vp, C.POINTER(LogregJob), C.c_int32, C.POINTER(LogregParams), vp]
+    L.cfear_closure_params_default.argtypes = [C.POINTER(ClosureParams), C.c_int32]
+    L.cfear_closure_params_default.restype = None
+    L.cfear_closure_candidates_batch.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int32, C.POINTER(ClosureParams), vp,
+                                                 C.POINTER(C.c_int32)]
     _LIB = L
     return L

@@ -2643,6 +2643,127 @@ def pose_graph_prefixes(poses, ids, constraints):
 
 
 # ------------------------------------------------------------------------------------------------
+# loop candidates without descriptors: GTVicinityClosure / MiniClosure (tbv_slam/src/tbv_slam/loopclosure.cpp:394-552)
+# ------------------------------------------------------------------------------------------------
+def closure_params(mode="gtvicinity", **kw):
+    """cfear_closure_params with the reference's defaults for `mode` ("gtvicinity": loopclosure.h:84-86, "mini": :95-97);
+    keyword overrides: min_d_travel, max_d_travel, max_d_close, verify_via_odometry, odom_sigma_error."""
+    if mode not in L.CLOSURE_MODE:
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "mode must be one of %s, got %r" % (sorted(L.CLOSURE_MODE), mode))
+    p = L.ClosureParams()
+    L.lib().cfear_closure_params_default(C.byref(p), L.CLOSURE_MODE[mode])
+    for k, v in kw.items():
+        if k == "mode" or not hasattr(p, k):
+            raise L.CfearError(L.ERR_INVALID_ARGUMENT, "unknown cfear_closure_params field %r" % k)
+        setattr(p, k, type(getattr(p, k))(v))
+    return p
+
+
+def _closure_graph_arrays(graph, where):
+    """One graph as the arrays cfear_closure_candidates_batch reads -> positions [n, 3], steps [n], rel_xyt [n, 3] or None."""
+    if len(graph) not in (2, 3):
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "%s: (poses, constraints) or (positions, steps[, rel_xyt]) is needed" % where)
+    second = graph[1]
+    from_constraints = len(graph) == 2 and not isinstance(second, np.ndarray) and (len(second) == 0 or isinstance(second[0], dict))
+    pos = np.asarray(graph[0], np.float64)
+    if pos.ndim != 2 or pos.shape[1] not in ((3, 7) if from_constraints else (3,)):
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "%s: %s, got %s" % (
+            where, "poses must be [n, 7] (p, q) or [n, 3] (x, y, theta)" if from_constraints else "positions must be [n, 3]", pos.shape))
+    n = pos.shape[0]
+    if not from_constraints:
+        steps = np.asarray(second, np.float64).reshape(-1)
+        rel = None if len(graph) == 2 or graph[2] is None else np.asarray(graph[2], np.float64).reshape(-1, 3)
+        for name, arr in (("steps", steps), ("rel_xyt", rel)):
+            if arr is not None and arr.shape[0] not in (n, max(n - 1, 0)):
+                raise L.CfearError(L.ERR_INVALID_ARGUMENT, "%s: %d %s for %d nodes (one per node, or one per step)" % (where, arr.shape[0], name, n))
+        pad = lambda a: a if a.shape[0] == n else np.concatenate([a, np.zeros((1,) + a.shape[1:])])
+        return np.ascontiguousarray(pos), pad(steps), None if rel is None else pad(rel)
+    # node k is pose k; the odometry constraint between k and k + 1 (either direction: ConstraintsHandler's key is the
+    # unordered pair) gives RelativeMotion(k, k + 1) = its t_be as it stands, and the step its translation's norm
+    positions = np.zeros((n, 3))
+    positions[:, :(2 if pos.shape[1] == 3 else 3)] = pos[:, :(2 if pos.shape[1] == 3 else 3)]
+    steps, rel, seen = np.zeros(n), np.zeros((n, 3)), np.zeros(n, bool)
+    for j, c in enumerate(second):
+        try:
+            if int(c.get("type", 0)) != 0:
+                continue
+            a, b = int(c["id_begin"]), int(c["id_end"])
+            t = np.asarray(c["t_be"], np.float64).reshape(-1)
+            if t.size not in (3, 7):
+                raise ValueError("t_be must hold 3 or 7 values")
+        except (KeyError, ValueError, TypeError, OverflowError) as e:
+            raise L.CfearError(L.ERR_INVALID_ARGUMENT, "%s: constraint %d: %s" % (where, j, e))
+        k = min(a, b)
+        if abs(a - b) != 1 or k < 0 or k + 1 >= n:
+            raise L.CfearError(L.ERR_INVALID_ARGUMENT, "%s: odometry constraint %d joins nodes %d and %d (node ids are 0 .. n - 1, consecutive)" % (where, j, a, b))
+        x, y, z = (float(t[0]), float(t[1]), 0.0 if t.size == 3 else float(t[2]))
+        steps[k] = np.sqrt((x * x + y * y) + z * z)
+        if t.size == 3:
+            rel[k] = t
+        else:
+            pz, out = _pose3d(t), (C.c_double * 3)()
+            L.lib().cfear_pose3d_to_xyt(C.byref(pz), out)
+            rel[k] = list(out)
+        seen[k] = True
+    if n > 1 and not seen[:n - 1].all():
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "%s: no odometry constraint between nodes %d and %d" % (
+            where, int(np.argmin(seen[:n - 1])), int(np.argmin(seen[:n - 1])) + 1))
+    return positions, steps, rel
+
+
+def closure_candidates(graphs, mode="gtvicinity", ctx=None, **params):
+    """cfear_closure_candidates_batch: the loop candidates GTVicinityClosure (mode="gtvicinity", the pairs the reference trains
+    and evaluates its loop classifiers on) or MiniClosure (mode="mini", --miniloop-enabled) proposes for every graph of
+    `graphs` in ONE device call -- the reference's first SearchAndAddConstraint() from fresh state on a complete graph.
+    A graph is (poses, constraints): poses [n, 7] (p, q) or [n, 3] (x, y, theta), node ids 0 .. n - 1, and the odometry
+    constraints as OdometryKeyframeFuser.constraint() returns them (other types are skipped); or (positions [n, 3], steps
+    [n or n - 1][, rel_xyt [n or n - 1, 3]]) with steps[k] / rel_xyt[k] the odometry from node k to k + 1.  Without rel_xyt
+    (then for every graph) odom_bounds stays 0.  Keyword overrides: closure_params().  Returns one CLOSURE_CANDIDATE_DTYPE
+    array per graph, a record per origin node: to (-1: none), exhausted, eucl, trav, rel, odom_bounds.  A graph the call
+    refuses raises CfearError with .graph = its index."""
+    p = closure_params(mode, **params)
+    arrs = [_closure_graph_arrays(g, "graph %d" % k) for k, g in enumerate(graphs)]
+    if not arrs:
+        return []
+    with_rel = [a[2] is not None for a in arrs]
+    if any(with_rel) and not all(with_rel):
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "rel_xyt for every graph or for none")
+    off = np.concatenate([[0], np.cumsum([a[0].shape[0] for a in arrs])]).astype(np.int64)
+    pos = np.ascontiguousarray(np.concatenate([a[0] for a in arrs], 0))
+    steps = np.ascontiguousarray(np.concatenate([a[1] for a in arrs]))
+    rel = np.ascontiguousarray(np.concatenate([a[2] for a in arrs], 0)) if all(with_rel) else None
+    out = np.zeros(int(off[-1]), L.CLOSURE_CANDIDATE_DTYPE)
+    ctx = ctx or default_context()
+    bad = C.c_int32(-1)
+    rc = ctx._lib.cfear_closure_candidates_batch(ctx.h, pos.ctypes.data, steps.ctypes.data, None if rel is None else rel.ctypes.data,
+                                                 off.ctypes.data, int(off[-1]), len(arrs), C.byref(p), out.ctypes.data, C.byref(bad))
+    if rc != L.OK:
+        err = L.CfearError(rc, ctx._lib.cfear_last_error(ctx.h).decode())
+        err.graph = int(bad.value)
+        raise err
+    return [out[off[g]:off[g + 1]].copy() for g in range(len(arrs))]
+
+
+def closure_verify_jobs(cands, nodes, poses_xyt, group_base=0):
+    """One graph's closure_candidates records as verify_loop_candidates / prepare_verify_batch input: a dict per origin that
+    got a candidate, in origin order.  nodes: a dict(scan=MapPointNormal, peaks=float32 [n, 4]) per graph node;
+    poses_xyt [n, 3].  As the reference hands its pairs on (loopclosure.cpp:451-452, 538-539): from = max(origin, to),
+    to = min(origin, to); sc_sim = 0 as CreateMiniloopConstraint sets it; odom_bounds from the record; group = group_base +
+    origin.  t_be_guess is the identity: the reference passes a default-constructed Pose3d there, which types.h:48 leaves
+    uninitialised, so the identity is this project's choice, not a restatement."""
+    poses_xyt = np.asarray(poses_xyt, np.float64).reshape(-1, 3)
+    jobs = []
+    for i, c in enumerate(cands):
+        if c["to"] < 0:
+            continue
+        fr, to = max(i, int(c["to"])), min(i, int(c["to"]))
+        jobs.append({"from": fr, "to": to, "from_scan": nodes[fr]["scan"], "to_scan": nodes[to]["scan"], "from_peaks": nodes[fr]["peaks"],
+                     "to_peaks": nodes[to]["peaks"], "from_pose": poses_xyt[fr], "t_be_guess": (0.0, 0.0, 0.0), "sc_sim": 0.0,
+                     "odom_bounds": float(c["odom_bounds"]), "group": int(group_base) + i})
+    return jobs
+
+
+# ------------------------------------------------------------------------------------------------
 # trajectory evaluation: the KITTI odometry metric (radar_kitti_benchmark/python/kitti_odometry.py)
 # ------------------------------------------------------------------------------------------------
 def eval_params(step_size=10, alignment="6dof", lengths=None):

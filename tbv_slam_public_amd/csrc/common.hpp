@@ -50,6 +50,7 @@ enum WsSlot : int {
   kWsP2pScratch = 20,     // p2p quality: sorted reference clouds that do not fit the LDS
   kWsCart = 21,           // Cartesian image / CorAlCart quality: staged images, job records, partial sums, staged outputs
   kWsCartMap = 22,        // the fixed-point polar -> Cartesian map of the last geometry (cfear_ctx::cart_map_*)
+  kWsClosure = 23,        // vicinity closure: staged positions, steps and motions, the block table, staged candidates
 };
 
 struct cfear_ctx {
@@ -62,7 +63,7 @@ struct cfear_ctx {
   std::vector<hipEvent_t> event_pool;
   // grow-only device workspaces (indexed by WsSlot so stages of one pipeline do not alias)
   struct Ws { void* p = nullptr; size_t bytes = 0; };
-  Ws ws[23];
+  Ws ws[24];
   // pinned host staging for small read-backs
   void* pinned = nullptr;
   size_t pinned_bytes = 0;
