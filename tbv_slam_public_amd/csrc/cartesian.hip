@@ -268,7 +268,7 @@ extern "C" int cfear_polar_to_cartesian(cfear_ctx* ctx, const uint8_t* polar, co
     ctx->cart_map_w = W; ctx->cart_map_rows = rows;
     ctx->cart_map_radar_res = par->radar_resolution; ctx->cart_map_cart_res = par->cart_resolution;
   }
-  a.map = (const unsigned long long*)ctx->ws[kWsCartMap].p;
+  a.map = (const unsigned long long*)ctx->ws[kWsCartMap].p.get();
   a.rows = rows; a.cols = desc->cols; a.stride = dd.stride; a.W = W; a.batch = batch;
   a.batch_stride = batch > 1 ? dd.batch_stride : (long long)rows * dd.stride;
   a.k255 = (float)(1 / 255.0);

@@ -8,20 +8,53 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/cfear_hip.h"
+#include "owned.hpp"
 
 #define CFEAR_WAVE 64
 
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
+// Owners of everything that outlives a call (a call's own memory goes through HostStage below): members of the handle
+// structs, released by the struct's destructor in reverse declaration order -- so a struct declares the streams it owns
+// before the buffers and events used on them, and its *_destroy synchronises those streams before it deletes the object.
+// Kernels and HIP calls take the raw pointer (get()).
+template <class T> using DevBuf = Owned<T, hipFree>;                  // device memory
+template <class T> using PinnedBuf = Owned<T[], hipHostFree>;         // pinned host memory, indexed on the host
+using Event = Owned<std::remove_pointer_t<hipEvent_t>, hipEventDestroy>;
+using Stream = Owned<std::remove_pointer_t<hipStream_t>, hipStreamDestroy>;
+using GraphExec = Owned<std::remove_pointer_t<hipGraphExec_t>, hipGraphExecDestroy>;
+// The makers return an empty owner on failure and clear the sticky HIP error; 0 bytes allocate 256.
+template <class T> DevBuf<T> dev_alloc(size_t bytes) {
+  void* p = nullptr;
+  if (hipMalloc(&p, bytes ? bytes : 256) != hipSuccess) { (void)hipGetLastError(); p = nullptr; }
+  return DevBuf<T>((T*)p);
+}
+template <class T> PinnedBuf<T> pinned_alloc(size_t bytes) {
+  void* p = nullptr;
+  if (hipHostMalloc(&p, bytes ? bytes : 256, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); p = nullptr; }
+  return PinnedBuf<T>((T*)p);
+}
+inline Event make_event(unsigned flags) {
+  hipEvent_t e = nullptr;
+  if (hipEventCreateWithFlags(&e, flags) != hipSuccess) { (void)hipGetLastError(); e = nullptr; }
+  return Event(e);
+}
+inline Stream make_stream_nonblocking() {
+  hipStream_t s = nullptr;
+  if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); s = nullptr; }
+  return Stream(s);
+}
+
 struct ProfRow {
   const char* name;
   double total_ms = 0.0;
   int64_t launches = 0;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
+  std::vector<std::pair<Event, Event>> pending;
 };
 
 // Workspace slots (cfear_ctx::ws).  Stages that are live at the same time use different slots; a slot with several users is
@@ -55,22 +88,22 @@ enum WsSlot : int {
 
 struct cfear_ctx {
   int device = 0;
+  Stream owned_stream;        // empty when the caller supplied the stream; declared first, so everything below goes before it
   hipStream_t stream = nullptr;
-  bool own_stream = false;
   std::string last_error;
   int profile = 0;            // 0 off, 1 every kernel family, 2 the polar filter's row kernels only (the HBM-bound launch)
   std::vector<ProfRow> prof;
-  std::vector<hipEvent_t> event_pool;
+  std::vector<Event> event_pool;
   // grow-only device workspaces (indexed by WsSlot so stages of one pipeline do not alias)
-  struct Ws { void* p = nullptr; size_t bytes = 0; };
+  struct Ws { DevBuf<void> p; size_t bytes = 0; };
   Ws ws[24];
   // pinned host staging for small read-backs
-  void* pinned = nullptr;
+  PinnedBuf<char> pinned;
   size_t pinned_bytes = 0;
-  hipEvent_t pinned_ev = nullptr;   // recorded behind the last asynchronous reader of `pinned` (HostStage::pinned)
+  Event pinned_ev;                  // recorded behind the last asynchronous reader of `pinned` (HostStage::pinned)
   bool pinned_busy = false;
   // free list of scan slabs (capacity -> device pointers) so streaming does not hipMalloc
-  struct Slab { void* p; int cap; };
+  struct Slab { DevBuf<void> p; int cap; };
   std::vector<Slab> free_slabs;
   int64_t live_scans = 0;
   int trig_rows = 0;       // rows the cos/sin tables in ws[kWsTrig] were built for
@@ -238,7 +271,7 @@ constexpr float kScanGridMinEdge = 2.0f;                       // cell edge floo
 
 struct cfear_scan {
   cfear_ctx* ctx;
-  void* slab;
+  DevBuf<void> slab;       // moves to cfear_ctx::free_slabs with the last reference
   ScanView view;
   int32_t n_cells_host;    // -1 until read back
   uint32_t surf_path = 0;  // CFEAR_SURF_PATH_* of the surface-point launch that made the cells (0: none did)

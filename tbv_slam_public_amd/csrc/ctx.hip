@@ -27,50 +27,39 @@ bool cfear_is_device_ptr(const void* p) {
 
 void* cfear_workspace(cfear_ctx* ctx, WsSlot slot, size_t bytes) {
   cfear_ctx::Ws& w = ctx->ws[slot];
-  if (w.bytes >= bytes && w.p) return w.p;
+  if (w.bytes >= bytes && w.p) return w.p.get();
   if (w.p) {
     (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(w.p);
-    w.p = nullptr;
+    w.p.reset();
     w.bytes = 0;
   }
   size_t want = bytes + bytes / 4 + 4096;
-  if (hipMalloc(&w.p, want) != hipSuccess) {
-    (void)hipGetLastError();
-    w.p = nullptr;
-    return nullptr;
-  }
+  w.p = dev_alloc<void>(want);
+  if (!w.p) return nullptr;
   w.bytes = want;
-  return w.p;
+  return w.p.get();
 }
 
 // The context's pinned staging of at least `bytes`.  A call that leaves an asynchronous reader of it in flight (no
 // synchronisation before it returns) calls cfear_pinned_mark() behind that reader; cfear_pinned() then waits for it before it
 // hands the buffer out again.
 static void cfear_pinned_mark(cfear_ctx* ctx) {
-  if (!ctx->pinned_ev && hipEventCreateWithFlags(&ctx->pinned_ev, hipEventDisableTiming) != hipSuccess) {
-    (void)hipGetLastError();
-    ctx->pinned_ev = nullptr;
+  if (!ctx->pinned_ev && !(ctx->pinned_ev = make_event(hipEventDisableTiming))) {
     (void)hipStreamSynchronize(ctx->stream);               // no event: the copy is simply waited for here
     return;
   }
-  ctx->pinned_busy = hipEventRecord(ctx->pinned_ev, ctx->stream) == hipSuccess;
+  ctx->pinned_busy = hipEventRecord(ctx->pinned_ev.get(), ctx->stream) == hipSuccess;
   if (!ctx->pinned_busy) (void)hipStreamSynchronize(ctx->stream);
 }
 
 static void* cfear_pinned(cfear_ctx* ctx, size_t bytes) {
-  if (ctx->pinned_busy) { (void)hipEventSynchronize(ctx->pinned_ev); ctx->pinned_busy = false; }
-  if (ctx->pinned_bytes >= bytes && ctx->pinned) return ctx->pinned;
-  if (ctx->pinned) { (void)hipStreamSynchronize(ctx->stream); (void)hipHostFree(ctx->pinned); ctx->pinned = nullptr; }
+  if (ctx->pinned_busy) { (void)hipEventSynchronize(ctx->pinned_ev.get()); ctx->pinned_busy = false; }
+  if (ctx->pinned_bytes >= bytes && ctx->pinned) return ctx->pinned.get();
+  if (ctx->pinned) { (void)hipStreamSynchronize(ctx->stream); ctx->pinned.reset(); }
   size_t want = bytes + 4096;
-  if (hipHostMalloc(&ctx->pinned, want, hipHostMallocDefault) != hipSuccess) {
-    (void)hipGetLastError();
-    ctx->pinned = nullptr;
-    ctx->pinned_bytes = 0;
-    return nullptr;
-  }
-  ctx->pinned_bytes = want;
-  return ctx->pinned;
+  ctx->pinned = pinned_alloc<char>(want);
+  ctx->pinned_bytes = ctx->pinned ? want : 0;
+  return ctx->pinned.get();
 }
 
 bool HostStage::is_host(const void* p) {
@@ -204,20 +193,15 @@ int cfear_allow_lds(cfear_ctx* ctx, const void* kernel, size_t bytes) {
 int cfear_prof_row(cfear_ctx* ctx, const char* name) {
   for (size_t i = 0; i < ctx->prof.size(); i++)
     if (ctx->prof[i].name == name || strcmp(ctx->prof[i].name, name) == 0) return (int)i;
-  ProfRow r;
-  r.name = name;
-  ctx->prof.push_back(r);
+  ctx->prof.emplace_back();
+  ctx->prof.back().name = name;
   return (int)ctx->prof.size() - 1;
 }
 
-static hipEvent_t prof_event(cfear_ctx* ctx) {
-  if (!ctx->event_pool.empty()) {
-    hipEvent_t e = ctx->event_pool.back();
-    ctx->event_pool.pop_back();
-    return e;
-  }
-  hipEvent_t e = nullptr;
-  (void)hipEventCreate(&e);
+static Event prof_event(cfear_ctx* ctx) {
+  if (ctx->event_pool.empty()) return make_event(hipEventDefault);
+  Event e = std::move(ctx->event_pool.back());
+  ctx->event_pool.pop_back();
   return e;
 }
 
@@ -225,27 +209,27 @@ static void prof_resolve(cfear_ctx* ctx) {
   for (auto& r : ctx->prof) {
     for (auto& p : r.pending) {
       float ms = 0.f;
-      if (hipEventSynchronize(p.second) == hipSuccess && hipEventElapsedTime(&ms, p.first, p.second) == hipSuccess) {
+      if (hipEventSynchronize(p.second.get()) == hipSuccess && hipEventElapsedTime(&ms, p.first.get(), p.second.get()) == hipSuccess) {
         r.total_ms += ms;
         r.launches++;
       }
-      ctx->event_pool.push_back(p.first);
-      ctx->event_pool.push_back(p.second);
+      ctx->event_pool.push_back(std::move(p.first));
+      ctx->event_pool.push_back(std::move(p.second));
     }
     r.pending.clear();
   }
 }
 
 void cfear_prof_begin(cfear_ctx* ctx, int row) {
-  hipEvent_t a = prof_event(ctx), b = prof_event(ctx);
-  (void)hipEventRecord(a, ctx->stream);
-  ctx->prof[row].pending.emplace_back(a, b);
+  Event a = prof_event(ctx), b = prof_event(ctx);
+  (void)hipEventRecord(a.get(), ctx->stream);
+  ctx->prof[row].pending.emplace_back(std::move(a), std::move(b));
   if (ctx->prof[row].pending.size() > 4096) prof_resolve(ctx);
 }
 
 void cfear_prof_end(cfear_ctx* ctx, int row) {
   if (ctx->prof[row].pending.empty()) return;
-  (void)hipEventRecord(ctx->prof[row].pending.back().second, ctx->stream);
+  (void)hipEventRecord(ctx->prof[row].pending.back().second.get(), ctx->stream);
 }
 
 // ---- scan slabs ---------------------------------------------------------------------------------
@@ -284,22 +268,22 @@ ScanView cfear_scan_view(void* slab, int cap) {
 }
 
 int cfear_scan_alloc(cfear_ctx* ctx, int cap, cfear_scan** out) {
-  void* slab = nullptr;
+  DevBuf<void> slab;
   // reuse a freed slab of sufficient capacity (streaming odometry creates one scan per frame)
   int best = -1;
   for (size_t i = 0; i < ctx->free_slabs.size(); i++)
     if (ctx->free_slabs[i].cap >= cap && (best < 0 || ctx->free_slabs[i].cap < ctx->free_slabs[best].cap)) best = (int)i;
   if (best >= 0) {
-    slab = ctx->free_slabs[best].p;
+    slab = std::move(ctx->free_slabs[best].p);
     cap = ctx->free_slabs[best].cap;
     ctx->free_slabs.erase(ctx->free_slabs.begin() + best);
-  } else {
-    CFEAR_HIP_CHECK(ctx, hipMalloc(&slab, cfear_scan_slab_bytes(cap)));
+  } else if (!(slab = dev_alloc<void>(cfear_scan_slab_bytes(cap)))) {
+    return cfear_set_error(ctx, CFEAR_ERR_HIP, "scan slab: hipMalloc failed");
   }
   cfear_scan* s = new cfear_scan();
   s->ctx = ctx;
-  s->slab = slab;
-  s->view = cfear_scan_view(slab, cap);
+  s->view = cfear_scan_view(slab.get(), cap);
+  s->slab = std::move(slab);
   s->n_cells_host = -1;
   ctx->live_scans++;
   *out = s;
@@ -366,21 +350,17 @@ int cfear_ctx_create(int device, void* hip_stream, cfear_ctx** out) {
   }
   if (device < 0 || device >= ndev) return CFEAR_ERR_INVALID_ARGUMENT;
   if (hipSetDevice(device) != hipSuccess) return CFEAR_ERR_HIP;
-  cfear_ctx* ctx = new cfear_ctx();
+  std::unique_ptr<cfear_ctx> ctx(new cfear_ctx());
   ctx->device = device;
   if (hip_stream) {
     ctx->stream = (hipStream_t)hip_stream;
-    ctx->own_stream = false;
   } else {
-    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
-      delete ctx;
-      return CFEAR_ERR_HIP;
-    }
-    ctx->own_stream = true;
+    if (!(ctx->owned_stream = make_stream_nonblocking())) return CFEAR_ERR_HIP;
+    ctx->stream = ctx->owned_stream.get();
   }
   (void)hipDeviceGetAttribute(&ctx->n_cu, hipDeviceAttributeMultiprocessorCount, device);
   if (ctx->n_cu < 1) ctx->n_cu = 256;
-  *out = ctx;
+  *out = ctx.release();
   return CFEAR_OK;
 }
 
@@ -416,13 +396,7 @@ int cfear_ctx_destroy(cfear_ctx* ctx) {
   if (!ctx) return CFEAR_OK;
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
-  prof_resolve(ctx);
-  for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
-  for (auto& w : ctx->ws) if (w.p) (void)hipFree(w.p);
-  for (auto& s : ctx->free_slabs) (void)hipFree(s.p);
-  if (ctx->pinned) (void)hipHostFree(ctx->pinned);
-  if (ctx->pinned_ev) (void)hipEventDestroy(ctx->pinned_ev);
-  if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
+  prof_resolve(ctx);                                       // hands the timing events back to the pool
   delete ctx;
   return CFEAR_OK;
 }
@@ -568,7 +542,7 @@ int cfear_scan_destroy(cfear_scan* scan) {
   cfear_ctx* ctx = scan->ctx;
   // the slab may still be read by enqueued kernels of this stream; later users are on the same
   // stream, so recycling it is ordered.
-  ctx->free_slabs.push_back(cfear_ctx::Slab{scan->slab, scan->view.cap});
+  ctx->free_slabs.push_back(cfear_ctx::Slab{std::move(scan->slab), scan->view.cap});
   ctx->live_scans--;
   delete scan;
   return CFEAR_OK;

@@ -1891,8 +1891,8 @@ __global__ __launch_bounds__(256) void legacy_cloud_kernel(const int32_t* __rest
 // coordinates are bit-exact with the reference; cached per context.
 int cfear_trig_tables(cfear_ctx* ctx, int rows, double** d_cos, double** d_sin) {
   if (ctx->trig_rows == rows && ctx->ws[2].p) {      // tables are cached per context
-    *d_cos = (double*)ctx->ws[2].p;
-    *d_sin = (double*)ctx->ws[2].p + rows;
+    *d_cos = (double*)ctx->ws[2].p.get();
+    *d_sin = (double*)ctx->ws[2].p.get() + rows;
     return CFEAR_OK;
   }
   HostStage st(ctx, kWsTrig);

@@ -1602,7 +1602,7 @@ extern "C" int cfear_register_batch(cfear_ctx* ctx, const cfear_reg_job* jobs, i
 // until the table goes too, so a candidate can never read another scan's cells through a recycled slab.
 struct cfear_scan_table {
   cfear_ctx* ctx = nullptr;
-  ScanView* d_views = nullptr;          // [n] device
+  DevBuf<ScanView> d_views;             // [n] device
   std::vector<int32_t> n_cells;         // host copy of the cell counts (launch geometry)
   std::vector<cfear_scan*> scans;       // referenced handles
 };
@@ -1644,11 +1644,9 @@ extern "C" int cfear_scan_table_create(cfear_ctx* ctx, const cfear_scan* const* 
     views[i] = scans[i]->view;
     t->n_cells[(size_t)i] = nc;
   }
-  CFEAR_HIP_CHECK(ctx, hipMalloc((void**)&t->d_views, vb));
-  if (st.upload(t->d_views, views, vb) != CFEAR_OK || st.finish() != CFEAR_OK) {
-    (void)hipFree(t->d_views);
+  if (!(t->d_views = dev_alloc<ScanView>(vb))) return cfear_set_error(ctx, CFEAR_ERR_HIP, "scan table: hipMalloc failed");
+  if (st.upload(t->d_views.get(), views, vb) != CFEAR_OK || st.finish() != CFEAR_OK)
     return cfear_set_error(ctx, CFEAR_ERR_HIP, "scan table upload failed");
-  }
   t->scans.resize((size_t)n_scans);
   for (int i = 0; i < n_scans; i++) { t->scans[(size_t)i] = const_cast<cfear_scan*>(scans[i]); cfear_scan_retain(t->scans[(size_t)i]); }
   *out = t.release();
@@ -1661,7 +1659,6 @@ extern "C" int cfear_scan_table_destroy(cfear_scan_table* t) {
   if (!t) return CFEAR_OK;
   (void)hipSetDevice(t->ctx->device);
   (void)hipStreamSynchronize(t->ctx->stream);
-  if (t->d_views) (void)hipFree(t->d_views);
   for (cfear_scan* s : t->scans) (void)cfear_scan_destroy(s);          // drops the table's reference
   delete t;
   return CFEAR_OK;
@@ -1692,7 +1689,7 @@ int cfear_candidates_expand(cfear_ctx* ctx, hipStream_t stream, const cfear_scan
   // form, every candidate does) -- one evaluation per batch, not per candidate (4096 candidates: 0.1 ms of host time)
   sz.add(2, scan_grid_pad(max_tar), scan_grid_pad(max_tar), max_src);
   geom->pairs_cap = sz.pairs_cap; geom->hint = sz.hint(n);
-  hipLaunchKernelGGL(expand_candidates_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const ScanView*)table->d_views,
+  hipLaunchKernelGGL(expand_candidates_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const ScanView*)table->d_views.get(),
                      (const cfear_candidate*)h_stage, n, d_jobs, reg_job_stride(2), d_trailer, trailer_status);
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
   return CFEAR_OK;
@@ -1870,13 +1867,15 @@ extern "C" int cfear_covariance_by_sampling(cfear_ctx* ctx, const cfear_scan* co
 struct cfear_cost {
   cfear_ctx* ctx;
   cfear_reg_params par;
-  void* d_job = nullptr;       // RegJob
-  char* d_scratch = nullptr;   // slots
-  double* d_out = nullptr;     // raw_r | raw_j | rob_r | neq
+  DevBuf<char> d_job;          // RegJob
+  DevBuf<char> d_scratch;      // slots
+  DevBuf<double> d_out;        // raw_r | raw_j | rob_r | neq
   int pairs_cap = 0, n_src = 0, n_slots = 0, n_blocks = 0, n_scans = 0;
   std::vector<double> h_w;     // slot weights (host copy), < 0 = no association
   std::vector<int32_t> h_tidx; // matched target cell per slot
 };
+
+using CostHandle = std::unique_ptr<cfear_cost, FreeWith<cfear_cost_destroy>>;   // selects the device and drains the stream first
 
 extern "C" int cfear_cost_prepare(cfear_ctx* ctx, const cfear_scan* const* scans, int32_t n_scans,
                                   const double* poses_xyt, const cfear_reg_params* par, int32_t itr, cfear_cost** out) {
@@ -1889,38 +1888,37 @@ extern "C" int cfear_cost_prepare(cfear_ctx* ctx, const cfear_scan* const* scans
   unsigned char* hjob = (unsigned char*)st.record(sizeof(RegJob));
   JobSizes sz(par);
   CFEAR_CHECK(gather_job(ctx, scans, n_scans, poses_xyt, hjob, sz));
-  cfear_cost* c = new cfear_cost();
+  CostHandle c(new cfear_cost());
   c->ctx = ctx; c->par = *par; c->pairs_cap = sz.pairs_cap; c->n_scans = n_scans;
   c->n_src = cfear_scan_size(scans[n_scans - 1]);
   c->n_slots = (n_scans - 1) * c->n_src;
-  auto fail = [&](int status, const char* msg) { cfear_cost_destroy(c); return cfear_set_error(ctx, status, "%s", msg); };
-  if (hipMalloc(&c->d_job, sizeof(RegJob) + 256) != hipSuccess) return fail(CFEAR_ERR_HIP, "hipMalloc failed");
-  if (hipMalloc((void**)&c->d_scratch, slots_bytes(c->pairs_cap)) != hipSuccess) return fail(CFEAR_ERR_HIP, "hipMalloc failed");
-  if (hipMalloc((void**)&c->d_out, ((size_t)c->pairs_cap * 10 + 16) * sizeof(double)) != hipSuccess) return fail(CFEAR_ERR_HIP, "hipMalloc failed");
-  if (st.upload(c->d_job, hjob, sizeof(RegJob)) != CFEAR_OK) return fail(CFEAR_ERR_HIP, "memcpy failed");
+  if (!(c->d_job = dev_alloc<char>(sizeof(RegJob) + 256)) || !(c->d_scratch = dev_alloc<char>(slots_bytes(c->pairs_cap))) ||
+      !(c->d_out = dev_alloc<double>(((size_t)c->pairs_cap * 10 + 16) * sizeof(double))))
+    return cfear_set_error(ctx, CFEAR_ERR_HIP, "hipMalloc failed");
+  if (st.upload(c->d_job.get(), hjob, sizeof(RegJob)) != CFEAR_OK) return cfear_set_error(ctx, CFEAR_ERR_HIP, "memcpy failed");
   MatchCommon cm{};
   cm.par = *par; cm.angle_outlier = std::cos(M_PI / 6.0);
-  cm.scratch = c->d_scratch; cm.scratch_stride = 0;
+  cm.scratch = c->d_scratch.get(); cm.scratch_stride = 0;
   cm.job_stride = sizeof(RegJob);
   cm.pairs_cap = c->pairs_cap; cm.results = nullptr;
   cm.dense_fields = reg_dense_fields(par->cost);
   cm.lds_total = (uint32_t)(kLdsCu - 256);
-  int32_t* d_nb = (int32_t*)((char*)c->d_job + sizeof(RegJob));
-  if (cfear_allow_lds(ctx, (const void*)assoc_kernel, kLdsCu) != CFEAR_OK) return fail(CFEAR_ERR_HIP, "hipFuncSetAttribute failed");
-  hipLaunchKernelGGL(assoc_kernel, dim3(1), dim3(256), (size_t)cm.lds_total, ctx->stream, (const RegJob*)c->d_job, cm, (int)itr, d_nb);
-  if (hipGetLastError() != hipSuccess) return fail(CFEAR_ERR_HIP, "assoc_kernel launch failed");
+  int32_t* d_nb = (int32_t*)(c->d_job.get() + sizeof(RegJob));
+  if (cfear_allow_lds(ctx, (const void*)assoc_kernel, kLdsCu) != CFEAR_OK) return cfear_set_error(ctx, CFEAR_ERR_HIP, "hipFuncSetAttribute failed");
+  hipLaunchKernelGGL(assoc_kernel, dim3(1), dim3(256), (size_t)cm.lds_total, ctx->stream, (const RegJob*)c->d_job.get(), cm, (int)itr, d_nb);
+  if (hipGetLastError() != hipSuccess) return cfear_set_error(ctx, CFEAR_ERR_HIP, "assoc_kernel launch failed");
   c->h_w.assign(std::max(c->n_slots, 1), -1.0);
   c->h_tidx.assign(std::max(c->n_slots, 1), -1);
   int32_t nb = 0;
   st.fetch(&nb, d_nb, 4);
   if (c->n_slots > 0) {
-    st.fetch(c->h_w.data(), (double*)c->d_scratch + 5 * (size_t)c->pairs_cap, (size_t)c->n_slots * 8);
-    st.fetch(c->h_tidx.data(), (double*)c->d_scratch + 6 * (size_t)c->pairs_cap, (size_t)c->n_slots * 4);
+    st.fetch(c->h_w.data(), (double*)c->d_scratch.get() + 5 * (size_t)c->pairs_cap, (size_t)c->n_slots * 8);
+    st.fetch(c->h_tidx.data(), (double*)c->d_scratch.get() + 6 * (size_t)c->pairs_cap, (size_t)c->n_slots * 4);
   }
-  if (st.wait() != CFEAR_OK) return fail(CFEAR_ERR_HIP, "read-back failed");
-  if (nb < 0) return fail(CFEAR_ERR_CAPACITY, "association capacity exceeded");
+  if (st.wait() != CFEAR_OK) return cfear_set_error(ctx, CFEAR_ERR_HIP, "read-back failed");
+  if (nb < 0) return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "association capacity exceeded");
   c->n_blocks = nb;
-  *out = c;
+  *out = c.release();
   return CFEAR_OK;
 }
 
@@ -1934,15 +1932,16 @@ namespace {
 int run_eval(cfear_cost* c, const double x[3], bool want_raw) {
   cfear_ctx* ctx = c->ctx;
   MatchCommon cm{};
-  cm.par = c->par; cm.scratch = c->d_scratch; cm.job_stride = sizeof(RegJob);
+  cm.par = c->par; cm.scratch = c->d_scratch.get(); cm.job_stride = sizeof(RegJob);
   cm.pairs_cap = c->pairs_cap;
   EvalOut o;
   const size_t sc = (size_t)c->pairs_cap;
-  o.raw_r = want_raw ? c->d_out : nullptr;
-  o.raw_j = want_raw ? c->d_out + 2 * sc : nullptr;
-  o.rob_r = c->d_out + 8 * sc;
-  o.neq = c->d_out + 10 * sc;
-  hipLaunchKernelGGL(eval_kernel, dim3(1), dim3(256), kFixedLds, ctx->stream, (const RegJob*)c->d_job, cm, x[0], x[1], x[2], o);
+  double* d_out = c->d_out.get();
+  o.raw_r = want_raw ? d_out : nullptr;
+  o.raw_j = want_raw ? d_out + 2 * sc : nullptr;
+  o.rob_r = d_out + 8 * sc;
+  o.neq = d_out + 10 * sc;
+  hipLaunchKernelGGL(eval_kernel, dim3(1), dim3(256), kFixedLds, ctx->stream, (const RegJob*)c->d_job.get(), cm, x[0], x[1], x[2], o);
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
   return CFEAR_OK;
 }
@@ -1985,8 +1984,8 @@ extern "C" int cfear_cost_evaluate(cfear_cost* c, const double x[3], double* res
   std::vector<double> r(2 * (size_t)std::max(c->n_slots, 1)), j(6 * (size_t)std::max(c->n_slots, 1));
   HostStage st(ctx, kWsRegJobs);
   if (c->n_slots > 0) {
-    st.fetch(r.data(), c->d_out, (size_t)c->n_slots * 16);
-    st.fetch(j.data(), c->d_out + 2 * sc, (size_t)c->n_slots * 48);
+    st.fetch(r.data(), c->d_out.get(), (size_t)c->n_slots * 16);
+    st.fetch(j.data(), c->d_out.get() + 2 * sc, (size_t)c->n_slots * 48);
   }
   CFEAR_CHECK(st.wait());
   compact_blocks(c, r.data(), j.data(), residuals, INT32_MAX, jacobian);
@@ -2001,7 +2000,7 @@ extern "C" int cfear_cost_normal_eq(cfear_cost* c, const double x[3], double H[9
   if (rc != CFEAR_OK) return rc;
   double neq[10];
   HostStage st(ctx, kWsRegJobs);
-  st.fetch(neq, c->d_out + 10 * (size_t)c->pairs_cap, sizeof(neq));
+  st.fetch(neq, c->d_out.get() + 10 * (size_t)c->pairs_cap, sizeof(neq));
   CFEAR_CHECK(st.wait());
   if (cost) *cost = neq[0];
   if (g) { g[0] = neq[1]; g[1] = neq[2]; g[2] = neq[3]; }
@@ -2017,9 +2016,6 @@ extern "C" int cfear_cost_destroy(cfear_cost* c) {
   if (!c) return CFEAR_OK;
   (void)hipSetDevice(c->ctx->device);
   (void)hipStreamSynchronize(c->ctx->stream);
-  if (c->d_job) (void)hipFree(c->d_job);
-  if (c->d_scratch) (void)hipFree(c->d_scratch);
-  if (c->d_out) (void)hipFree(c->d_out);
   delete c;
   return CFEAR_OK;
 }
@@ -2030,25 +2026,24 @@ extern "C" int cfear_get_cost(cfear_ctx* ctx, const cfear_scan* const* scans, in
   if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
   if (!cost || !n_residuals || !score) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
   *cost = 0.0; *n_residuals = 0; *score = 0.0;
-  cfear_cost* c = nullptr;
-  int rc = cfear_cost_prepare(ctx, scans, n_scans, poses_xyt, par, par ? par->itr : 0, &c);   // radius by itr_ (:220)
+  cfear_cost* prepared = nullptr;
+  int rc = cfear_cost_prepare(ctx, scans, n_scans, poses_xyt, par, par ? par->itr : 0, &prepared);   // radius by itr_ (:220)
   if (rc != CFEAR_OK) return rc;
-  const int nres = cfear_cost_num_residuals(c);
-  if (nres <= 1) { cfear_cost_destroy(c); return CFEAR_ERR_TOO_FEW_RESIDUALS; }           // :200-203
+  const CostHandle c(prepared);
+  const int nres = cfear_cost_num_residuals(c.get());
+  if (nres <= 1) return CFEAR_ERR_TOO_FEW_RESIDUALS;                                       // :200-203
   const double* x = poses_xyt + 3 * (n_scans - 1);
-  rc = run_eval(c, x, false);
-  if (rc != CFEAR_OK) { cfear_cost_destroy(c); return rc; }
+  CFEAR_CHECK(run_eval(c.get(), x, false));
   const size_t sc = (size_t)c->pairs_cap;
   std::vector<double> r(2 * (size_t)c->n_slots);
   double neq[10];
   HostStage st(ctx, kWsRegJobs);
-  st.fetch(r.data(), c->d_out + 8 * sc, (size_t)c->n_slots * 16);
-  st.fetch(neq, c->d_out + 10 * sc, sizeof(neq));
-  if (st.wait() != CFEAR_OK) { cfear_cost_destroy(c); return cfear_set_error(ctx, CFEAR_ERR_HIP, "read-back failed"); }
-  compact_blocks(c, r.data(), nullptr, residuals, cap, nullptr);
+  st.fetch(r.data(), c->d_out.get() + 8 * sc, (size_t)c->n_slots * 16);
+  st.fetch(neq, c->d_out.get() + 10 * sc, sizeof(neq));
+  if (st.wait() != CFEAR_OK) return cfear_set_error(ctx, CFEAR_ERR_HIP, "read-back failed");
+  compact_blocks(c.get(), r.data(), nullptr, residuals, cap, nullptr);
   *cost = neq[0];
   *n_residuals = nres;
   *score = neq[0] / (double)std::max(nres, 1);                                            // :209
-  cfear_cost_destroy(c);
   return CFEAR_OK;
 }

@@ -76,7 +76,7 @@ extern "C" int cfear_acc_vel_sanity_check(const double tmot_prev_xy[2], const do
 namespace {
 
 struct Keyframe { int slab; Aff2 pose; uint64_t idx = 0; };
-struct Stream {
+struct StreamState {
   Aff2 T_prev = aff_identity(), Tmot = aff_identity(), Tcurrent = aff_identity();
   std::vector<Keyframe> keyframes;
   std::vector<int> free_slabs;
@@ -100,6 +100,7 @@ constexpr int kDecodeHold = 32;
 
 struct cfear_odometry {
   cfear_ctx* ctx = nullptr;
+  Stream copy_stream;                  // uploads the registration jobs while the surface kernel runs (first: the buffers and events used on it go before it)
   int n_streams = 0;
   cfear_polar_desc desc{};             // layout the filters see: rows = azimuths
   cfear_polar_desc in_desc{};          // layout of the caller's images (differs when par.rotate_ccw)
@@ -107,20 +108,20 @@ struct cfear_odometry {
   int cap_points = 0, cell_cap = 0, slabs_per_stream = 0;
   size_t slab_bytes = 0;
   // device memory (one allocation each)
-  uint8_t* d_polar = nullptr;          // staging when the caller passes host images
-  uint8_t* d_rot = nullptr;            // rotated images (par.rotate_ccw)
+  DevBuf<uint8_t> d_polar;             // staging when the caller passes host images
+  DevBuf<uint8_t> d_rot;               // rotated images (par.rotate_ccw)
   bool fused_decode = false;           // par.rotate_ccw: the filter stage decodes the source itself where it pays (no d_rot)
   // ... which it does on radar-like sweeps (a few dozen bins >= z_min per azimuth): the candidate lists cost time per
   // candidate, the rotation kernel + row sweep do not.  The decode reports the batch's candidates; beyond kDecodeDense per
   // azimuth the next kDecodeHold frames take the two-kernel route, then one frame probes again.
-  uint32_t* d_decode_stats = nullptr;  // [2 buffers][64]
-  uint32_t* h_decode_stats = nullptr;  // pinned copy
+  DevBuf<uint32_t> d_decode_stats;     // [2 buffers][64]
+  PinnedBuf<uint32_t> h_decode_stats;  // pinned copy
   bool decode_measured[2] = {false, false};
   int decode_hold = 0;
-  char* d_sel = nullptr;               // sel_range | sel_intensity | sel_count
-  float* d_xyzi2[2] = {nullptr, nullptr};    // filter outputs are double-buffered: the next frame's filter
-  int32_t* d_npts2[2] = {nullptr, nullptr};  //   may run while the host applies this frame's policy
-  float* d_xyzi = nullptr;                   // buffer of the frame being processed
+  DevBuf<char> d_sel;                  // sel_range | sel_intensity | sel_count
+  DevBuf<float> d_xyzi2[2];                  // filter outputs are double-buffered: the next frame's filter
+  DevBuf<int32_t> d_npts2[2];                //   may run while the host applies this frame's policy
+  float* d_xyzi = nullptr;                   // buffer of the frame being processed (not owned, like d_npts, d_pk, d_npk)
   int32_t* d_npts = nullptr;
   // fused filter output (k-strongest without keep_nodes, k <= 64): per-row points + counts written by the polar sweep
   // itself; the surface-point kernel compacts them, so neither sel_* arrays nor a cloud kernel exist in this mode
@@ -128,89 +129,59 @@ struct cfear_odometry {
   // the same hand-over for CA-CFAR (no keep_nodes): cacfar_rows_kernel leaves per-row keys with a row capacity row_k
   bool fused_cfar = false;
   int row_k = 0;                                 // keys per row in d_rowpts2: k (k-strongest) or the CA-CFAR row capacity
-  uint32_t* d_rowpts2[2] = {nullptr, nullptr};   // [B][rows][k] packed keys (intensity << 24 | range bin)
-  int32_t* d_rowcnt2[2] = {nullptr, nullptr};   // [B][rows][2]
-  int64_t* d_offsets2[2] = {nullptr, nullptr};  // [B] image offsets of the sweep in each filter buffer (process_offsets)
-  int64_t* h_offsets = nullptr;              // pinned staging, [2][B]
+  DevBuf<uint32_t> d_rowpts2[2];                 // [B][rows][k] packed keys (intensity << 24 | range bin)
+  DevBuf<int32_t> d_rowcnt2[2];                 // [B][rows][2]
+  DevBuf<int64_t> d_offsets2[2];                // [B] image offsets of the sweep in each filter buffer (process_offsets)
+  PinnedBuf<int64_t> h_offsets;              // pinned staging, [2][B]
   std::vector<int64_t> prefetched_offsets;   // offsets the prefetched filter output was computed from
   // par.keep_nodes: the peaks cloud of every frame (cloud_peaks_ of RadarScan), double-buffered like the cloud
-  float* d_pk2[2] = {nullptr, nullptr};
-  int32_t* d_npk2[2] = {nullptr, nullptr};
+  DevBuf<float> d_pk2[2];
+  DevBuf<int32_t> d_npk2[2];
   float* d_pk = nullptr;
   int32_t* d_npk = nullptr;
-  double* d_mot = nullptr;                   // [B][3] TprevMot of this frame (peaks compensation)
-  double* h_mot = nullptr;
-  int32_t* h_npk = nullptr;
+  DevBuf<double> d_mot;                      // [B][3] TprevMot of this frame (peaks compensation)
+  PinnedBuf<double> h_mot;
+  PinnedBuf<int32_t> h_npk;
   std::vector<int> last_slab;                // slab that holds each stream's last processed scan
   int cur_buf = 0;
   const uint8_t* prefetched = nullptr;       // polar pointer whose filter output sits in buffer cur_buf ^ 1
-  hipEvent_t ev_results = nullptr;
-  hipStream_t copy_stream = nullptr;         // uploads the registration jobs while the surface kernel runs
-  hipEvent_t ev_jobs = nullptr;
-  char* d_slabs = nullptr;
-  char* d_surf_jobs = nullptr;
-  char* d_reg_jobs = nullptr;
+  Event ev_results;
+  Event ev_jobs;                             // the job upload on copy_stream
+  DevBuf<char> d_slabs, d_surf_jobs, d_reg_jobs;
   // what a frame returns to the host lives in ONE device block (and one pinned block): results | status | n_cells |
   // n_points -- one read-back per frame instead of four small copies queued between the matcher and the next sweep
-  char* d_out = nullptr;
-  char* h_out = nullptr;
+  DevBuf<char> d_out;
+  PinnedBuf<char> h_out;
   size_t out_bytes = 0;
+  // pointers into d_out / h_out (not owned)
   int32_t* d_npts_out = nullptr;       // n_points slot of the block (rows mode: written by surface_prep_kernel)
   cfear_reg_result* d_results = nullptr;
   int32_t* d_status = nullptr;
   int32_t* d_ncells = nullptr;         // gathered n_cells of the current scans
-  char* d_surf_scratch = nullptr;
-  char* d_reg_scratch = nullptr;
+  DevBuf<char> d_surf_scratch, d_reg_scratch;
   // pinned host mirrors
-  char* h_surf_jobs = nullptr;
-  char* h_reg_jobs = nullptr;
+  PinnedBuf<char> h_surf_jobs, h_reg_jobs;
   cfear_reg_result* h_results = nullptr;
   int32_t* h_status = nullptr;
   int32_t* h_npts = nullptr;
   int32_t* h_ncells = nullptr;
   // covariance by cost sampling (optional): n^3 GetCost records per stream and the cached fit
-  cfear_reg_result* d_samples = nullptr;
-  cfear_reg_result* h_samples = nullptr;
+  DevBuf<cfear_reg_result> d_samples;
+  PinnedBuf<cfear_reg_result> h_samples;
   CovFit fit;
   std::vector<double> cov;             // [n_streams][36] cov_current
   std::vector<int32_t> cov_sampled;    // [n_streams]
-  std::vector<Stream> streams;
+  std::vector<StreamState> streams;
   int big_regs = 0;                    // > 0: recent frames held registrations too large for 80 KB of LDS -> keep the second launch on
   std::vector<double> cost_est, cost_tmp;   // per stream: work of its last registration (residuals x iterations): orders the next batch
   std::vector<int> job_slot;                 // per stream: class | rank inside the class << 3 of this frame's registration (-1: none)
   std::vector<ScanView> views;         // [n_streams * slabs_per_stream]
 };
 
-namespace {
-
-template <typename T>
-bool dalloc(T** p, size_t bytes) {
-  if (hipMalloc((void**)p, bytes ? bytes : 256) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; }
-  return true;
-}
-template <typename T>
-bool halloc(T** p, size_t bytes) {
-  if (hipHostMalloc((void**)p, bytes ? bytes : 256, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; }
-  return true;
-}
-
-}  // namespace
-
 extern "C" int cfear_odometry_destroy(cfear_odometry* od) {
   if (!od) return CFEAR_OK;
   (void)hipSetDevice(od->ctx->device);
   (void)hipStreamSynchronize(od->ctx->stream);
-  if (od->ev_results) (void)hipEventDestroy(od->ev_results);
-  if (od->ev_jobs) (void)hipEventDestroy(od->ev_jobs);
-  if (od->copy_stream) (void)hipStreamDestroy(od->copy_stream);
-  void* dev2[] = {od->d_rowpts2[0], od->d_rowpts2[1], od->d_rowcnt2[0], od->d_rowcnt2[1], od->d_offsets2[0], od->d_offsets2[1]};
-  for (void* p : dev2) if (p) (void)hipFree(p);
-  if (od->h_offsets) (void)hipHostFree(od->h_offsets);
-  void* dev[] = {od->d_decode_stats, od->d_pk2[0], od->d_pk2[1], od->d_npk2[0], od->d_npk2[1], od->d_mot, od->d_polar, od->d_rot, od->d_sel, od->d_xyzi2[0], od->d_xyzi2[1], od->d_npts2[0], od->d_npts2[1], od->d_slabs, od->d_surf_jobs, od->d_reg_jobs,
-                 od->d_out, od->d_surf_scratch, od->d_reg_scratch, od->d_samples};
-  for (void* p : dev) if (p) (void)hipFree(p);
-  void* host[] = {od->h_mot, od->h_npk, od->h_surf_jobs, od->h_reg_jobs, od->h_out, od->h_samples, od->h_decode_stats};
-  for (void* p : host) if (p) (void)hipHostFree(p);
   delete od;
   return CFEAR_OK;
 }
@@ -246,7 +217,7 @@ extern "C" int cfear_odometry_create(cfear_ctx* ctx, int32_t n_streams, const cf
     }
   }
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  cfear_odometry* od = new cfear_odometry();
+  std::unique_ptr<cfear_odometry, FreeWith<cfear_odometry_destroy>> od(new cfear_odometry());
   od->ctx = ctx; od->n_streams = n_streams; od->desc = *desc; od->in_desc = *desc; od->par = *par;
   if (par->rotate_ccw) {               // radarDriver::Callback (radar_driver.cpp:74-90): [bins][azimuths] -> rows = azimuths
     od->desc.rows = desc->cols;
@@ -262,7 +233,10 @@ extern "C" int cfear_odometry_create(cfear_ctx* ctx, int32_t n_streams, const cf
   od->slabs_per_stream = par->submap_scan_size + 2;
   od->slab_bytes = cfear_scan_slab_bytes(od->cell_cap);
   const size_t nsel = (size_t)B * rows * std::max(k, 1);
+  // one buffer each; after the first failure nothing more is allocated
   bool ok = true;
+  auto dev = [&ok](auto& buf, size_t bytes) { ok = ok && (buf = dev_alloc<typename std::decay_t<decltype(buf)>::element_type>(bytes)); };
+  auto pin = [&ok](auto& buf, size_t bytes) { ok = ok && (buf = pinned_alloc<typename std::decay_t<decltype(buf)>::element_type>(bytes)); };
   od->fused = par->filter_type == CFEAR_FILTER_KSTRONG && !par->keep_nodes && k <= 64 && rows <= 4096 &&
               rows * k <= cfear_surface_max_points();
   od->row_k = k;
@@ -270,8 +244,8 @@ extern "C" int cfear_odometry_create(cfear_ctx* ctx, int32_t n_streams, const cf
   // A/B runs and the tests that compare the two)
   od->fused_decode = od->fused && par->rotate_ccw && ctx->opt[CFEAR_OPT_FUSED_DECODE] != 0;
   if (od->fused_decode) {
-    ok = ok && dalloc(&od->d_decode_stats, 2 * 64 * 4);
-    ok = ok && halloc(&od->h_decode_stats, 2 * 64 * 4);
+    dev(od->d_decode_stats, 2 * 64 * 4);
+    pin(od->h_decode_stats, 2 * 64 * 4);
   }
   // CA-CFAR puts no bound on a row's detections either: 1024 keys per row (a row beyond that marks its scan
   // CFEAR_ERR_CAPACITY, like a sweep beyond cap_points)
@@ -279,43 +253,42 @@ extern "C" int cfear_odometry_create(cfear_ctx* ctx, int32_t n_streams, const cf
   if (od->fused_cfar) {
     od->row_k = std::min((od->desc.cols + 3) / 4 * 4, 1024);
     for (int i = 0; i < 2; i++) {
-      ok = ok && dalloc(&od->d_rowpts2[i], (size_t)B * rows * od->row_k * 4);
-      ok = ok && dalloc(&od->d_rowcnt2[i], (size_t)B * rows * 8);
+      dev(od->d_rowpts2[i], (size_t)B * rows * od->row_k * 4);
+      dev(od->d_rowcnt2[i], (size_t)B * rows * 8);
     }
   }
   if (od->fused) {
     for (int i = 0; i < 2; i++) {
-      ok = ok && dalloc(&od->d_rowpts2[i], nsel * 4);
-      ok = ok && dalloc(&od->d_rowcnt2[i], (size_t)B * rows * 8);
-      ok = ok && dalloc(&od->d_offsets2[i], (size_t)B * 8);
+      dev(od->d_rowpts2[i], nsel * 4);
+      dev(od->d_rowcnt2[i], (size_t)B * rows * 8);
+      dev(od->d_offsets2[i], (size_t)B * 8);
     }
-    ok = ok && halloc(&od->h_offsets, (size_t)B * 8 * 2);
+    pin(od->h_offsets, (size_t)B * 8 * 2);
   } else {
-    ok = ok && dalloc(&od->d_sel, nsel * 4 + 2 * (nsel + 256) + (size_t)B * rows * 4 + 1024);   // + is_peak (keep_nodes)
+    dev(od->d_sel, nsel * 4 + 2 * (nsel + 256) + (size_t)B * rows * 4 + 1024);   // + is_peak (keep_nodes)
   }
   if (par->keep_nodes) {
     for (int i = 0; i < 2; i++) {
-      ok = ok && dalloc(&od->d_pk2[i], (size_t)B * od->cap_points * 16);
-      ok = ok && dalloc(&od->d_npk2[i], (size_t)B * 4);
+      dev(od->d_pk2[i], (size_t)B * od->cap_points * 16);
+      dev(od->d_npk2[i], (size_t)B * 4);
     }
-    ok = ok && dalloc(&od->d_mot, (size_t)B * 3 * sizeof(double));
-    ok = ok && halloc(&od->h_mot, (size_t)B * 3 * sizeof(double));
-    ok = ok && halloc(&od->h_npk, (size_t)B * 4);
+    dev(od->d_mot, (size_t)B * 3 * sizeof(double));
+    pin(od->h_mot, (size_t)B * 3 * sizeof(double));
+    pin(od->h_npk, (size_t)B * 4);
   }
   od->last_slab.assign(B, -1);
   for (int i = 0; i < 2; i++) {
-    ok = ok && dalloc(&od->d_xyzi2[i], (size_t)B * od->cap_points * 16);
-    ok = ok && dalloc(&od->d_npts2[i], (size_t)B * 4);
+    dev(od->d_xyzi2[i], (size_t)B * od->cap_points * 16);
+    dev(od->d_npts2[i], (size_t)B * 4);
   }
-  ok = ok && hipEventCreateWithFlags(&od->ev_results, hipEventDisableTiming) == hipSuccess;
-  ok = ok && hipEventCreateWithFlags(&od->ev_jobs, hipEventDisableTiming) == hipSuccess;
-  ok = ok && hipStreamCreateWithFlags(&od->copy_stream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && dalloc(&od->d_slabs, (size_t)B * od->slabs_per_stream * od->slab_bytes);
-  ok = ok && dalloc(&od->d_surf_jobs, (size_t)B * cfear_surface_job_bytes());
-  ok = ok && dalloc(&od->d_reg_jobs, (size_t)B * cfear_reg_job_bytes());
+  ok = ok && (od->ev_results = make_event(hipEventDisableTiming)) && (od->ev_jobs = make_event(hipEventDisableTiming)) &&
+       (od->copy_stream = make_stream_nonblocking());
+  dev(od->d_slabs, (size_t)B * od->slabs_per_stream * od->slab_bytes);
+  dev(od->d_surf_jobs, (size_t)B * cfear_surface_job_bytes());
+  dev(od->d_reg_jobs, (size_t)B * cfear_reg_job_bytes());
   od->out_bytes = (size_t)B * (sizeof(cfear_reg_result) + 12);
-  ok = ok && dalloc(&od->d_out, od->out_bytes);
-  ok = ok && halloc(&od->h_out, od->out_bytes);
+  dev(od->d_out, od->out_bytes);
+  pin(od->h_out, od->out_bytes);
   if (ok) {
     auto carve = [&](char* base) {
       struct P { cfear_reg_result* r; int32_t *st, *nc, *np; } q;
@@ -324,35 +297,35 @@ extern "C" int cfear_odometry_create(cfear_ctx* ctx, int32_t n_streams, const cf
       q.nc = q.st + B; q.np = q.nc + B;
       return q;
     };
-    const auto d = carve(od->d_out), h = carve(od->h_out);
+    const auto d = carve(od->d_out.get()), h = carve(od->h_out.get());
     od->d_results = d.r; od->d_status = d.st; od->d_ncells = d.nc; od->d_npts_out = d.np;
     od->h_results = h.r; od->h_status = h.st; od->h_ncells = h.nc; od->h_npts = h.np;
   }
-  ok = ok && dalloc(&od->d_surf_scratch, (size_t)B * cfear_surface_scratch_bytes(od->cap_points));
-  ok = ok && dalloc(&od->d_reg_scratch, (size_t)B * cfear_register_scratch_bytes(par->submap_scan_size * od->cell_cap));
-  ok = ok && halloc(&od->h_surf_jobs, (size_t)B * cfear_surface_job_bytes());
-  ok = ok && halloc(&od->h_reg_jobs, (size_t)B * cfear_reg_job_bytes());
+  dev(od->d_surf_scratch, (size_t)B * cfear_surface_scratch_bytes(od->cap_points));
+  dev(od->d_reg_scratch, (size_t)B * cfear_register_scratch_bytes(par->submap_scan_size * od->cell_cap));
+  pin(od->h_surf_jobs, (size_t)B * cfear_surface_job_bytes());
+  pin(od->h_reg_jobs, (size_t)B * cfear_reg_job_bytes());
   if (par->estimate_cov_by_sampling) {
     od->fit.prepare(par->cov_sampling.samples_per_axis, par->cov_sampling.xy_range * 0.5, par->cov_sampling.yaw_range * 0.5);
-    ok = ok && dalloc(&od->d_samples, (size_t)B * od->fit.m * sizeof(cfear_reg_result));
-    ok = ok && halloc(&od->h_samples, (size_t)B * od->fit.m * sizeof(cfear_reg_result));
+    dev(od->d_samples, (size_t)B * od->fit.m * sizeof(cfear_reg_result));
+    pin(od->h_samples, (size_t)B * od->fit.m * sizeof(cfear_reg_result));
   }
   od->cov.assign((size_t)B * 36, 0.0);
   for (int b = 0; b < B; b++)
     for (int k = 0; k < 6; k++) od->cov[(size_t)b * 36 + k * 7] = 1.0;       // cov_current = Identity (:36)
   od->cov_sampled.assign(B, 0);
-  if (!ok) { cfear_odometry_destroy(od); return cfear_set_error(ctx, CFEAR_ERR_HIP, "odometry buffers: allocation failed"); }
+  if (!ok) return cfear_set_error(ctx, CFEAR_ERR_HIP, "odometry buffers: allocation failed");
   od->streams.resize(B);
   od->cost_est.assign(B, 0.0);
   od->views.resize((size_t)B * od->slabs_per_stream);
   for (int b = 0; b < B; b++) {
     for (int s = 0; s < od->slabs_per_stream; s++) {
       od->views[(size_t)b * od->slabs_per_stream + s] =
-          cfear_scan_view(od->d_slabs + ((size_t)b * od->slabs_per_stream + s) * od->slab_bytes, od->cell_cap);
+          cfear_scan_view(od->d_slabs.get() + ((size_t)b * od->slabs_per_stream + s) * od->slab_bytes, od->cell_cap);
       od->streams[b].free_slabs.push_back(od->slabs_per_stream - 1 - s);
     }
   }
-  *out = od;
+  *out = od.release();
   return CFEAR_OK;
 }
 
@@ -368,23 +341,23 @@ static int run_filter(cfear_odometry* od, const uint8_t* polar, int buf, const i
     if (!od->fused || par.rotate_ccw || !cfear_is_device_ptr(polar))
       return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "image offsets need device images, the k-strongest filter "
                              "(k <= 64, no keep_nodes) and rows = azimuths");
-    int64_t* h = od->h_offsets + (size_t)buf * B;
+    int64_t* h = od->h_offsets.get() + (size_t)buf * B;
     memcpy(h, offsets, (size_t)B * 8);
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(od->d_offsets2[buf], h, (size_t)B * 8, hipMemcpyHostToDevice, ctx->stream));
-    d_offsets = od->d_offsets2[buf];
+    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(od->d_offsets2[buf].get(), h, (size_t)B * 8, hipMemcpyHostToDevice, ctx->stream));
+    d_offsets = od->d_offsets2[buf].get();
   }
   if (!cfear_is_device_ptr(polar)) {
     const size_t img_bytes = (size_t)od->in_desc.rows * od->in_desc.stride;
-    if (!od->d_polar && !dalloc(&od->d_polar, img_bytes * B)) return cfear_set_error(ctx, CFEAR_ERR_HIP, "staging allocation failed");
+    if (!od->d_polar && !(od->d_polar = dev_alloc<uint8_t>(img_bytes * B))) return cfear_set_error(ctx, CFEAR_ERR_HIP, "staging allocation failed");
     const int64_t bs = B > 1 ? od->in_desc.batch_stride : (int64_t)img_bytes;
     if (bs == (int64_t)img_bytes) {          // a dense batch crosses PCIe as one copy
-      CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(od->d_polar, polar, img_bytes * B, hipMemcpyHostToDevice, ctx->stream));
+      CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(od->d_polar.get(), polar, img_bytes * B, hipMemcpyHostToDevice, ctx->stream));
     } else {
       for (int b = 0; b < B; b++)
-        CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(od->d_polar + (size_t)b * img_bytes, polar + (size_t)b * bs, img_bytes,
+        CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(od->d_polar.get() + (size_t)b * img_bytes, polar + (size_t)b * bs, img_bytes,
                                             hipMemcpyHostToDevice, ctx->stream));
     }
-    d_polar = od->d_polar;
+    d_polar = od->d_polar.get();
     dd.batch_stride = (int64_t)img_bytes;
   }
   od->decode_measured[buf] = false;
@@ -393,12 +366,12 @@ static int run_filter(cfear_odometry* od, const uint8_t* polar, int buf, const i
     cfear_kstrong_params kp = par.kstrong;
     kp.want_peaks = 0;
     cfear_kstrong_fused fz;
-    fz.row_keys = od->d_rowpts2[buf];
-    fz.row_valid = od->d_rowcnt2[buf];
-    fz.cand_stats = od->d_decode_stats + 64 * buf;
+    fz.row_keys = od->d_rowpts2[buf].get();
+    fz.row_valid = od->d_rowcnt2[buf].get();
+    fz.cand_stats = od->d_decode_stats.get() + 64 * buf;
     const int rc = cfear_kstrong_cols_device(ctx, d_polar, &dd, &kp, &fz);
     if (rc != CFEAR_OK) return rc;
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(od->h_decode_stats + 64 * buf, fz.cand_stats, 64 * 4, hipMemcpyDeviceToHost, ctx->stream));
+    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(od->h_decode_stats.get() + 64 * buf, fz.cand_stats, 64 * 4, hipMemcpyDeviceToHost, ctx->stream));
     od->decode_measured[buf] = true;                         // read once this buffer's frame has been synchronised
     return CFEAR_OK;
   }
@@ -408,27 +381,27 @@ static int run_filter(cfear_odometry* od, const uint8_t* polar, int buf, const i
       cfear_cacfar_cols_supported(d_polar, &dd, &par.cacfar)) {
     cfear_cacfar_params cp = par.cacfar;
     cfear_cacfar_fused fz;
-    fz.row_keys = od->d_rowpts2[buf]; fz.row_cnt = od->d_rowcnt2[buf]; fz.kcap = od->row_k; fz.bins_major = true;
+    fz.row_keys = od->d_rowpts2[buf].get(); fz.row_cnt = od->d_rowcnt2[buf].get(); fz.kcap = od->row_k; fz.bins_major = true;
     return cfear_cacfar_device(ctx, d_polar, &dd, &cp, nullptr, nullptr, od->cap_points, nullptr, &fz);
   }
   if (par.rotate_ccw) {
     const size_t rot_bytes = (size_t)od->desc.rows * od->desc.stride;
-    if (!od->d_rot && !dalloc(&od->d_rot, rot_bytes * B)) return cfear_set_error(ctx, CFEAR_ERR_HIP, "rotation buffer allocation failed");
-    const int rc = cfear_rotate_ccw_device(ctx, d_polar, &dd, od->d_rot, od->desc.stride, (int64_t)rot_bytes);
+    if (!od->d_rot && !(od->d_rot = dev_alloc<uint8_t>(rot_bytes * B))) return cfear_set_error(ctx, CFEAR_ERR_HIP, "rotation buffer allocation failed");
+    const int rc = cfear_rotate_ccw_device(ctx, d_polar, &dd, od->d_rot.get(), od->desc.stride, (int64_t)rot_bytes);
     if (rc != CFEAR_OK) return rc;
-    d_polar = od->d_rot;
+    d_polar = od->d_rot.get();
     dd = od->desc;
   }
   if (par.filter_type == CFEAR_FILTER_CACFAR) {
     cfear_cacfar_params cp = par.cacfar;
     if (par.keep_nodes)    // CA-CFAR produces no peaks cloud (radar_driver.cpp:52-56)
-      CFEAR_HIP_CHECK(ctx, hipMemsetAsync(od->d_npk2[buf], 0, (size_t)B * 4, ctx->stream));
+      CFEAR_HIP_CHECK(ctx, hipMemsetAsync(od->d_npk2[buf].get(), 0, (size_t)B * 4, ctx->stream));
     if (od->fused_cfar) {
       cfear_cacfar_fused fz;
-      fz.row_keys = od->d_rowpts2[buf]; fz.row_cnt = od->d_rowcnt2[buf]; fz.kcap = od->row_k;
+      fz.row_keys = od->d_rowpts2[buf].get(); fz.row_cnt = od->d_rowcnt2[buf].get(); fz.kcap = od->row_k;
       return cfear_cacfar_device(ctx, d_polar, &dd, &cp, nullptr, nullptr, od->cap_points, nullptr, &fz);
     }
-    return cfear_cacfar_device(ctx, d_polar, &dd, &cp, od->d_xyzi2[buf], od->d_npts2[buf], od->cap_points, nullptr);
+    return cfear_cacfar_device(ctx, d_polar, &dd, &cp, od->d_xyzi2[buf].get(), od->d_npts2[buf].get(), od->cap_points, nullptr);
   }
   const size_t nsel = (size_t)B * rows * k;
   cfear_kstrong_out o{};
@@ -436,23 +409,23 @@ static int run_filter(cfear_odometry* od, const uint8_t* polar, int buf, const i
     cfear_kstrong_params kp = par.kstrong;
     kp.want_peaks = 0;
     cfear_kstrong_fused fz;
-    fz.row_keys = od->d_rowpts2[buf];
-    fz.row_valid = od->d_rowcnt2[buf];
+    fz.row_keys = od->d_rowpts2[buf].get();
+    fz.row_valid = od->d_rowcnt2[buf].get();
     fz.image_offsets = d_offsets;
     return cfear_kstrong_device(ctx, d_polar, &dd, &kp, &o, par.rotate_ccw != 0, &fz);
   }
-  o.sel_range = (int32_t*)od->d_sel;
-  o.sel_intensity = (uint8_t*)(od->d_sel + nsel * 4);
-  o.sel_count = (int32_t*)(od->d_sel + nsel * 4 + (nsel + 255) / 256 * 256);
-  o.xyzi = od->d_xyzi2[buf];
-  o.n_points = od->d_npts2[buf];
+  o.sel_range = (int32_t*)od->d_sel.get();
+  o.sel_intensity = (uint8_t*)(od->d_sel.get() + nsel * 4);
+  o.sel_count = (int32_t*)(od->d_sel.get() + nsel * 4 + (nsel + 255) / 256 * 256);
+  o.xyzi = od->d_xyzi2[buf].get();
+  o.n_points = od->d_npts2[buf].get();
   cfear_kstrong_params kp = par.kstrong;
   kp.want_peaks = 0;     // the peaks cloud feeds CorAl / Scan Context, not the matcher
   if (par.keep_nodes) {  // ... unless the caller builds graph nodes from this pipeline (RadarScan::cloud_peaks_)
     kp.want_peaks = 1;
-    o.is_peak = (uint8_t*)(od->d_sel + nsel * 4 + (nsel + 255) / 256 * 256 + (size_t)B * rows * 4 + 256);
-    o.xyzi_peaks = od->d_pk2[buf];
-    o.n_peaks = od->d_npk2[buf];
+    o.is_peak = (uint8_t*)(od->d_sel.get() + nsel * 4 + (nsel + 255) / 256 * 256 + (size_t)B * rows * 4 + 256);
+    o.xyzi_peaks = od->d_pk2[buf].get();
+    o.n_peaks = od->d_npk2[buf].get();
   }
   if (od->cap_points != rows * k)
     return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "rows*k = %d exceeds %d points per scan", rows * k, od->cap_points);
@@ -566,10 +539,10 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
   int rc;
   if (clouds) {                                    // filtered clouds from the caller: no filter, no prefetch
     od->prefetched = nullptr;
-    rc = load_clouds(od, clouds, od->d_xyzi2[od->cur_buf], od->d_npts2[od->cur_buf], od->h_npts);
+    rc = load_clouds(od, clouds, od->d_xyzi2[od->cur_buf].get(), od->d_npts2[od->cur_buf].get(), od->h_npts);
     if (rc != CFEAR_OK) return rc;
     if (par.keep_nodes) {
-      rc = load_clouds(od, peaks, od->d_pk2[od->cur_buf], od->d_npk2[od->cur_buf], od->h_npk);
+      rc = load_clouds(od, peaks, od->d_pk2[od->cur_buf].get(), od->d_npk2[od->cur_buf].get(), od->h_npk.get());
       if (rc != CFEAR_OK) return rc;
     }
   } else if (od->prefetched == polar &&
@@ -583,17 +556,17 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
   }
   od->prefetched = nullptr;
   od->prefetched_offsets.clear();
-  od->d_xyzi = od->d_xyzi2[od->cur_buf];
-  od->d_npts = od->d_npts2[od->cur_buf];
-  od->d_pk = od->d_pk2[od->cur_buf];
-  od->d_npk = od->d_npk2[od->cur_buf];
+  od->d_xyzi = od->d_xyzi2[od->cur_buf].get();
+  od->d_npts = od->d_npts2[od->cur_buf].get();
+  od->d_pk = od->d_pk2[od->cur_buf].get();
+  od->d_npk = od->d_npk2[od->cur_buf].get();
   const bool rows_mode = (od->fused || od->fused_cfar) && !clouds;     // the filter left per-row points: the surface kernel compacts them
   // ---- C + N: compensate with the previous motion, surface points (odometrykeyframefuser.cpp:146-161)
   const size_t sjb = cfear_surface_job_bytes();
   for (int b = 0; b < B; b++)
     if (od->streams[b].free_slabs.empty()) return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "stream %d: no free scan slab", b);
   for (int b = 0; b < B; b++) {
-    Stream& st = od->streams[b];
+    StreamState& st = od->streams[b];
     st.cur_slab = st.free_slabs.back();
     st.free_slabs.pop_back();
     double mot[3];
@@ -601,20 +574,20 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
     od->last_slab[b] = st.cur_slab;
     if (par.keep_nodes) { od->h_mot[3 * b] = mot[0]; od->h_mot[3 * b + 1] = mot[1]; od->h_mot[3 * b + 2] = mot[2]; }
     if (rows_mode)
-      cfear_surface_fill_job_rows(od->h_surf_jobs + (size_t)b * sjb, od->d_xyzi + (size_t)b * od->cap_points * 4, od->d_npts_out + b,
-                                  od->d_rowpts2[od->cur_buf] + (size_t)b * od->desc.rows * od->row_k,
-                                  od->d_rowcnt2[od->cur_buf] + (size_t)b * od->desc.rows * 2, od->desc.rows,
+      cfear_surface_fill_job_rows(od->h_surf_jobs.get() + (size_t)b * sjb, od->d_xyzi + (size_t)b * od->cap_points * 4, od->d_npts_out + b,
+                                  od->d_rowpts2[od->cur_buf].get() + (size_t)b * od->desc.rows * od->row_k,
+                                  od->d_rowcnt2[od->cur_buf].get() + (size_t)b * od->desc.rows * 2, od->desc.rows,
                                   od->row_k, par.compensate, mot,
                                   od->views[(size_t)b * od->slabs_per_stream + st.cur_slab]);
     else
-      cfear_surface_fill_job(od->h_surf_jobs + (size_t)b * sjb, od->d_xyzi + (size_t)b * od->cap_points * 4,
+      cfear_surface_fill_job(od->h_surf_jobs.get() + (size_t)b * sjb, od->d_xyzi + (size_t)b * od->cap_points * 4,
                              od->d_npts + b, 0, par.compensate, mot, od->views[(size_t)b * od->slabs_per_stream + st.cur_slab]);
   }
   // From here on every stream holds a slab: an error exit must hand the slabs back, or submap_scan_size + 2 failed
   // calls would drain a stream's free list.
   auto fail = [&](int code) {
     for (int b = 0; b < B; b++) {
-      Stream& st = od->streams[b];
+      StreamState& st = od->streams[b];
       if (st.cur_slab >= 0) { st.free_slabs.push_back(st.cur_slab); st.cur_slab = -1; }
     }
     return code;
@@ -625,7 +598,7 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
     if (_e != hipSuccess)                                                                                     \
       return fail(cfear_set_error(ctx, CFEAR_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__)); \
   } while (0)
-  OD_CHECK(hipMemcpyAsync(od->d_surf_jobs, od->h_surf_jobs, (size_t)B * sjb, hipMemcpyHostToDevice, ctx->stream));
+  OD_CHECK(hipMemcpyAsync(od->d_surf_jobs.get(), od->h_surf_jobs.get(), (size_t)B * sjb, hipMemcpyHostToDevice, ctx->stream));
   cfear_feature_params fp{};
   fp.radius = par.res;
   fp.downsample_factor = par.downsample_factor;
@@ -645,7 +618,7 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
       sp.range_res = (double)par.kstrong.range_res; sp.range_off = sp.range_res / 2.0;
     }
   }
-  rc = cfear_surface_launch(ctx, od->d_surf_jobs, B, &fp, od->d_surf_scratch, od->d_status, od->d_ncells, od->cell_cap, od->cap_points, rows_mode ? &sp : nullptr);
+  rc = cfear_surface_launch(ctx, od->d_surf_jobs.get(), B, &fp, od->d_surf_scratch.get(), od->d_status, od->d_ncells, od->cell_cap, od->cap_points, rows_mode ? &sp : nullptr);
   if (rc != CFEAR_OK) return fail(rc);
   g_tl.mark(0);
   // ---- M: the registration jobs depend on host state only: they are built and uploaded (copy stream) while the
@@ -681,7 +654,7 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
   slot.assign((size_t)B, -1);
   int cls_n[5] = {0, 0, 0, 0, 0};
   for (int b = 0; b < B; b++) {
-    Stream& st = od->streams[b];
+    StreamState& st = od->streams[b];
     st.Tguess = par.use_guess ? aff_mul(st.T_prev, st.Tmot) : st.T_prev;      // :164-168
     st.job = -1;
     if (st.keyframes.empty()) continue;                                       // :171-177 first frame: no registration
@@ -693,7 +666,7 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
   for (int c = 0; c < 5; c++) { cls_off[c] = n_jobs; n_jobs += cls_n[c]; }
   for (int b = 0; b < B; b++) {
     if (slot[b] < 0) continue;
-    Stream& st = od->streams[b];
+    StreamState& st = od->streams[b];
     const int ns = (int)st.keyframes.size() + 1;                              // FormatScans :478-494
     for (int i = 0; i < ns - 1; i++) {
       views[i] = od->views[(size_t)b * od->slabs_per_stream + st.keyframes[i].slab];
@@ -702,19 +675,19 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
     views[ns - 1] = od->views[(size_t)b * od->slabs_per_stream + st.cur_slab];
     aff_to_xyt(st.Tguess, &poses[3 * (ns - 1)]);
     st.job = cls_off[slot[b] & 7] + (slot[b] >> 3);
-    cfear_reg_fill_job(od->h_reg_jobs + (size_t)st.job * rjb, views.data(), ns, poses.data());
+    cfear_reg_fill_job(od->h_reg_jobs.get() + (size_t)st.job * rjb, views.data(), ns, poses.data());
   }
   if (n_jobs > 0) {
-    OD_CHECK(hipMemcpyAsync(od->d_reg_jobs, od->h_reg_jobs, (size_t)n_jobs * rjb, hipMemcpyHostToDevice, od->copy_stream));
-    OD_CHECK(hipEventRecord(od->ev_jobs, od->copy_stream));
+    OD_CHECK(hipMemcpyAsync(od->d_reg_jobs.get(), od->h_reg_jobs.get(), (size_t)n_jobs * rjb, hipMemcpyHostToDevice, od->copy_stream.get()));
+    OD_CHECK(hipEventRecord(od->ev_jobs.get(), od->copy_stream.get()));
   }
   g_tl.mark(1);
   // the matcher over this frame's jobs (+ the cost samples around its results); big_pass adds the large forms
   auto launch_register = [&](bool big_pass) -> int {
     RegLaunchHint hint;
     hint.big_pass = big_pass;
-    int lrc = cfear_register_launch(ctx, od->d_reg_jobs, n_jobs, &par.reg, par.submap_scan_size * od->cell_cap,
-                                    od->d_reg_scratch, od->d_results, nullptr, rjb, hint);
+    int lrc = cfear_register_launch(ctx, od->d_reg_jobs.get(), n_jobs, &par.reg, par.submap_scan_size * od->cell_cap,
+                                    od->d_reg_scratch.get(), od->d_results, nullptr, rjb, hint);
     if (lrc != CFEAR_OK) return lrc;
     if (par.estimate_cov_by_sampling) {
       // approximateCovarianceBySampling (:203-208, 261-316): n^3 GetCost evaluations around the pose the
@@ -727,10 +700,10 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
       mode.yaw_half = par.cov_sampling.yaw_range * 0.5;
       mode.blocks_per_job = 1;                                    // one workgroup per stream: its scratch is reused
       mode.prior = od->d_results;
-      lrc = cfear_register_launch(ctx, od->d_reg_jobs, n_jobs, &par.reg, par.submap_scan_size * od->cell_cap,
-                                  od->d_reg_scratch, od->d_samples, &mode, rjb, hint);
+      lrc = cfear_register_launch(ctx, od->d_reg_jobs.get(), n_jobs, &par.reg, par.submap_scan_size * od->cell_cap,
+                                  od->d_reg_scratch.get(), od->d_samples.get(), &mode, rjb, hint);
       if (lrc != CFEAR_OK) return lrc;
-      if (hipMemcpyAsync(od->h_samples, od->d_samples, (size_t)n_jobs * od->fit.m * sizeof(cfear_reg_result),
+      if (hipMemcpyAsync(od->h_samples.get(), od->d_samples.get(), (size_t)n_jobs * od->fit.m * sizeof(cfear_reg_result),
                          hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
         return cfear_set_error(ctx, CFEAR_ERR_HIP, "sample read-back failed");
     }
@@ -738,23 +711,23 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
   };
   const bool launched_big = od->big_regs > 0;
   if (n_jobs > 0) {
-    OD_CHECK(hipStreamWaitEvent(ctx->stream, od->ev_jobs, 0));
+    OD_CHECK(hipStreamWaitEvent(ctx->stream, od->ev_jobs.get(), 0));
     rc = launch_register(launched_big);
     if (rc != CFEAR_OK) return fail(rc);
   }
   if (par.keep_nodes) {
     // Compensate(*cloud_peaks, TprevMot, ccw) (odometrykeyframefuser.cpp:149): off the critical path, behind the matcher
     if (par.compensate) {
-      OD_CHECK(hipMemcpyAsync(od->d_mot, od->h_mot, (size_t)B * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-      rc = cfear_compensate_batch_device(ctx, od->d_pk, (size_t)od->cap_points, od->d_npk, od->d_mot, B, od->cap_points, par.radar_ccw);
+      OD_CHECK(hipMemcpyAsync(od->d_mot.get(), od->h_mot.get(), (size_t)B * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+      rc = cfear_compensate_batch_device(ctx, od->d_pk, (size_t)od->cap_points, od->d_npk, od->d_mot.get(), B, od->cap_points, par.radar_ccw);
       if (rc != CFEAR_OK) return fail(rc);
     }
-    OD_CHECK(hipMemcpyAsync(od->h_npk, od->d_npk, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
+    OD_CHECK(hipMemcpyAsync(od->h_npk.get(), od->d_npk, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
   }
   if (!rows_mode)     // the point counts came from the filter / the caller: bring them into the block first
     OD_CHECK(hipMemcpyAsync(od->d_npts_out, od->d_npts, (size_t)B * 4, hipMemcpyDeviceToDevice, ctx->stream));
-  OD_CHECK(hipMemcpyAsync(od->h_out, od->d_out, od->out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  OD_CHECK(hipEventRecord(od->ev_results, ctx->stream));
+  OD_CHECK(hipMemcpyAsync(od->h_out.get(), od->d_out.get(), od->out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  OD_CHECK(hipEventRecord(od->ev_results.get(), ctx->stream));
   int prefetch_rc = CFEAR_OK;
   if (polar_next) {
     // (Tried twice: the sweep on its own low-priority stream.  Enqueued ahead of this frame's kernels it simply ran first
@@ -777,7 +750,7 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
     }
   }
   g_tl.mark(2);
-  OD_CHECK(hipEventSynchronize(od->ev_results));
+  OD_CHECK(hipEventSynchronize(od->ev_results.get()));
   g_tl.mark(3);
   if (n_jobs > 0 && !launched_big) {
     // A registration too large for the first form of a launch WITHOUT the large forms comes back as CFEAR_ERR_CAPACITY with
@@ -803,7 +776,7 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
   int first_error = CFEAR_OK;
   bool saw_big = false;
   for (int b = 0; b < B; b++) {
-    Stream& st = od->streams[b];
+    StreamState& st = od->streams[b];
     cfear_frame_info& fi = info[b];
     memset(&fi, 0, sizeof(fi));
     fi.n_points = od->h_npts[b];
@@ -913,7 +886,7 @@ extern "C" int cfear_odometry_get_scan(cfear_odometry* od, int32_t stream, cfear
   if (rc != CFEAR_OK) return rc;
   // the route word of the stream's last frame: its scratch header stays as the kernels left it until the next process()
   uint32_t path = 0;
-  const int rc_path = cfear_surface_read_path(ctx, od->d_surf_scratch, od->cap_points, stream, &path);
+  const int rc_path = cfear_surface_read_path(ctx, od->d_surf_scratch.get(), od->cap_points, stream, &path);
   if (rc_path != CFEAR_OK) { cfear_scan_destroy(*out); *out = nullptr; return rc_path; }
   (*out)->surf_path = path;
   return CFEAR_OK;
@@ -947,7 +920,7 @@ extern "C" int cfear_odometry_get_peaks(cfear_odometry* od, int32_t stream, floa
 
 extern "C" int cfear_odometry_get_constraint(cfear_odometry* od, int32_t stream, cfear_graph_constraint* out) {
   if (!od || !out || stream < 0 || stream >= od->n_streams) return CFEAR_ERR_INVALID_ARGUMENT;
-  const Stream& st = od->streams[stream];
+  const StreamState& st = od->streams[stream];
   if (!st.has_constraint) return cfear_set_error(od->ctx, CFEAR_ERR_INVALID_ARGUMENT, "stream %d: the last frame added no keyframe behind another one", stream);
   memset(out, 0, sizeof(*out));
   out->id_begin = st.c_from; out->id_end = st.c_to;

@@ -896,9 +896,9 @@ struct cfear_sc_manager {
   cfear_ctx* ctx = nullptr;
   cfear_sc_manager_params par{};
   int cells = 0;
-  double* d_db = nullptr;        // [cap][cells]
+  DevBuf<double> d_db;           // [cap][cells]
   int cap = 0, n = 0;
-  double* d_cur = nullptr;       // [n_aug][cells] current node and its augmentations
+  DevBuf<double> d_cur;          // [n_aug][cells] current node and its augmentations
   int n_aug = 1;
   int cur_aug = 1;               // entries of current_and_augments_: n_aug after add, 1 after add_raw (RadarScancontext.cpp:133-146)
   std::vector<std::vector<float>> ringkeys;          // polarcontext_invkeys_mat_
@@ -933,17 +933,15 @@ extern "C" int cfear_sc_manager_create(cfear_ctx* ctx, const cfear_sc_manager_pa
   if (rc != CFEAR_OK) return rc;
   if (par->num_candidates_from_tree < 1 || par->n_candidates < 1 || !(par->odom_sigma_error > 0))
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "bad scan-context manager parameters");
-  cfear_sc_manager* m = new cfear_sc_manager();
+  std::unique_ptr<cfear_sc_manager> m(new cfear_sc_manager());
   m->ctx = ctx; m->par = *par;
   m->cells = par->sc.num_ring * par->sc.num_sector;
   m->shifts = sc_aug_shifts(par->augment_sc != 0);
   m->n_aug = (int)m->shifts.size();
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (hipMalloc((void**)&m->d_cur, (size_t)m->n_aug * m->cells * sizeof(double)) != hipSuccess) {
-    delete m;
+  if (!(m->d_cur = dev_alloc<double>((size_t)m->n_aug * m->cells * sizeof(double))))
     return cfear_set_error(ctx, CFEAR_ERR_HIP, "hipMalloc failed");
-  }
-  *out = m;
+  *out = m.release();
   return CFEAR_OK;
 }
 
@@ -951,8 +949,6 @@ extern "C" int cfear_sc_manager_destroy(cfear_sc_manager* m) {
   if (!m) return CFEAR_OK;
   (void)hipSetDevice(m->ctx->device);
   (void)hipStreamSynchronize(m->ctx->stream);
-  if (m->d_db) (void)hipFree(m->d_db);
-  if (m->d_cur) (void)hipFree(m->d_cur);
   delete m;
   return CFEAR_OK;
 }
@@ -1007,17 +1003,15 @@ int sc_manager_commit(cfear_sc_manager* m, const std::vector<double>& rk, int n_
   const int R = m->par.sc.num_ring;
   if (m->n == m->cap) {                                      // grow the database (device to device)
     const int ncap = std::max(256, m->cap * 2);
-    double* nd = nullptr;
-    if (hipMalloc((void**)&nd, (size_t)ncap * m->cells * sizeof(double)) != hipSuccess)
-      return cfear_set_error(ctx, CFEAR_ERR_HIP, "descriptor database: hipMalloc failed");
+    DevBuf<double> nd = dev_alloc<double>((size_t)ncap * m->cells * sizeof(double));
+    if (!nd) return cfear_set_error(ctx, CFEAR_ERR_HIP, "descriptor database: hipMalloc failed");
     if (m->n > 0)
-      CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(nd, m->d_db, (size_t)m->n * m->cells * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+      CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(nd.get(), m->d_db.get(), (size_t)m->n * m->cells * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (m->d_db) (void)hipFree(m->d_db);
-    m->d_db = nd;
+    m->d_db = std::move(nd);                                  // only now: a failed copy above frees nd and keeps the database
     m->cap = ncap;
   }
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(m->d_db + (size_t)m->n * m->cells, m->d_cur, (size_t)m->cells * sizeof(double),
+  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(m->d_db.get() + (size_t)m->n * m->cells, m->d_cur.get(), (size_t)m->cells * sizeof(double),
                                       hipMemcpyDeviceToDevice, ctx->stream));
   m->n++;
   m->cur_aug = n_cur;
@@ -1055,7 +1049,7 @@ extern "C" int cfear_sc_manager_add(cfear_sc_manager* m, const float* xyzi, int3
   const int R = m->par.sc.num_ring;
   cfear_sc_cloud cloud{xyzi, n_points, 0};
   std::vector<double> rk((size_t)m->n_aug * R);
-  int rc = cfear_sc_descriptors(ctx, &cloud, 1, &m->par.sc, m->shifts.data(), m->n_aug, m->d_cur, rk.data(), nullptr);
+  int rc = cfear_sc_descriptors(ctx, &cloud, 1, &m->par.sc, m->shifts.data(), m->n_aug, m->d_cur.get(), rk.data(), nullptr);
   if (rc != CFEAR_OK) return rc;
   return sc_manager_commit(m, rk, m->n_aug, Todom);
 }
@@ -1068,7 +1062,7 @@ extern "C" int cfear_sc_manager_add_raw(cfear_sc_manager* m, const uint8_t* img,
   if (desc->batch != 1) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "add_raw takes one sweep (batch = 1)");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   std::vector<double> rk((size_t)m->par.sc.num_ring);
-  const int rc = cfear_sc_raw_descriptors(ctx, img, desc, &m->par.sc, raw, m->d_cur, rk.data(), nullptr);
+  const int rc = cfear_sc_raw_descriptors(ctx, img, desc, &m->par.sc, raw, m->d_cur.get(), rk.data(), nullptr);
   if (rc != CFEAR_OK) return rc;
   return sc_manager_commit(m, rk, 1, Todom);
 }
@@ -1130,7 +1124,7 @@ extern "C" int cfear_sc_manager_detect(cfear_sc_manager* m, cfear_sc_candidate* 
   if (np == 0) return CFEAR_OK;
   std::vector<double> dist(np);
   std::vector<int32_t> shift(np);
-  const int rc = cfear_sc_distance_batch(ctx, m->d_cur, m->cur_aug, m->d_db, m->n, pairs.data(), np, &m->par.sc, dist.data(),
+  const int rc = cfear_sc_distance_batch(ctx, m->d_cur.get(), m->cur_aug, m->d_db.get(), m->n, pairs.data(), np, &m->par.sc, dist.data(),
                                          shift.data());
   if (rc != CFEAR_OK) return rc;
   std::vector<cfear_sc_candidate> similar;

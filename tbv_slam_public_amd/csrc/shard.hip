@@ -269,28 +269,28 @@ struct cfear_candidate_pipe {
   const cfear_scan_table* table = nullptr;
   cfear_rccl_comm comm{};                 // nccl_comm == nullptr: no collective (world 1)
   int rank = 0, world = 1, depth = 2, max_total = 0, per_cap = 0;
-  hipStream_t xstream = nullptr;          // exchange stream: all_gather + read-back
-  hipStream_t pstream = nullptr;          // preparation stream: step k + 1's expand kernel runs beside step k's matcher
+  Stream xstream;                         // exchange stream: all_gather + read-back
+  Stream pstream;                         // preparation stream: step k + 1's expand kernel runs beside step k's matcher
   int use_graph = 0, timing = 0;
   int64_t next_ticket = 0;
   double exchange_ms = 0.0;               // CFEAR_PIPE_TIMING: sum over collected steps of (all_gather + read-back) on the exchange stream
   int64_t collected = 0;
   struct Slot {
-    cfear_candidate* h_cands = nullptr;   // pinned [per_cap]
-    char* h_recv = nullptr;               // pinned [world][per_cap * 72 + 8]
-    char* d_jobs = nullptr;               // device [per_cap] job records (reg_job_stride(2) bytes each)
-    char* d_send = nullptr;               // device [per_cap * 72 + 8]
-    char* d_recv = nullptr;               // device [world][...]
-    hipEvent_t prepared = nullptr, computed = nullptr, xbegin = nullptr, done = nullptr;
+    PinnedBuf<cfear_candidate> h_cands;   // pinned [per_cap]
+    PinnedBuf<char> h_recv;               // pinned [world][per_cap * 72 + 8]
+    DevBuf<char> d_jobs;                  // device [per_cap] job records (reg_job_stride(2) bytes each)
+    DevBuf<char> d_send;                  // device [per_cap * 72 + 8]
+    DevBuf<char> d_recv;                  // device [world][...]
+    Event prepared, computed, xbegin, done;
     int64_t ticket = -1;                  // the step in this slot (-1: free)
     int n_total = 0, status = CFEAR_OK;
-    hipGraphExec_t exec = nullptr;        // the captured compute chain ...
+    GraphExec exec;                       // the captured compute chain ...
     int g_n = -1, g_per = -1;             // ... of a block of g_n candidates (g_per slots per rank) with parameters g_par,
     cfear_reg_params g_par{};             //     whose nodes hold the context's workspaces as they were at capture
     const void* g_ws7 = nullptr;
     int g_pairs_cap = 0, g_hint = 0;
   };
-  std::vector<Slot> slots;
+  std::vector<Slot> slots;                // (behind the streams: the slots' buffers and events go first)
   size_t block_bytes() const { return (size_t)per_cap * sizeof(cfear_reg_result) + sizeof(ShardTrailer); }
 };
 
@@ -299,22 +299,8 @@ extern "C" int cfear_candidate_pipe_destroy(cfear_candidate_pipe* p) {
   if (!p) return CFEAR_OK;
   (void)hipSetDevice(p->ctx->device);
   (void)hipStreamSynchronize(p->ctx->stream);
-  if (p->xstream) (void)hipStreamSynchronize(p->xstream);
-  if (p->pstream) (void)hipStreamSynchronize(p->pstream);
-  for (auto& s : p->slots) {
-    if (s.exec) (void)hipGraphExecDestroy(s.exec);
-    if (s.h_cands) (void)hipHostFree(s.h_cands);
-    if (s.h_recv) (void)hipHostFree(s.h_recv);
-    if (s.d_send) (void)hipFree(s.d_send);
-    if (s.d_jobs) (void)hipFree(s.d_jobs);
-    if (s.prepared) (void)hipEventDestroy(s.prepared);
-    if (s.d_recv) (void)hipFree(s.d_recv);
-    if (s.computed) (void)hipEventDestroy(s.computed);
-    if (s.xbegin) (void)hipEventDestroy(s.xbegin);
-    if (s.done) (void)hipEventDestroy(s.done);
-  }
-  if (p->xstream) (void)hipStreamDestroy(p->xstream);
-  if (p->pstream) (void)hipStreamDestroy(p->pstream);
+  if (p->xstream) (void)hipStreamSynchronize(p->xstream.get());
+  if (p->pstream) (void)hipStreamSynchronize(p->pstream.get());
   delete p;
   return CFEAR_OK;
 }
@@ -329,7 +315,7 @@ extern "C" int cfear_candidate_pipe_create(cfear_ctx* ctx, const cfear_scan_tabl
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "world %d needs a cfear_rccl_comm of that size", world);
   *out = nullptr;
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  cfear_candidate_pipe* p = new cfear_candidate_pipe();
+  std::unique_ptr<cfear_candidate_pipe, FreeWith<cfear_candidate_pipe_destroy>> p(new cfear_candidate_pipe());
   p->ctx = ctx; p->table = table; p->rank = rank; p->world = world; p->depth = depth; p->max_total = max_candidates;
   p->per_cap = (max_candidates + world - 1) / world;
   p->use_graph = (flags & CFEAR_PIPE_GRAPH) ? 1 : 0;
@@ -337,27 +323,25 @@ extern "C" int cfear_candidate_pipe_create(cfear_ctx* ctx, const cfear_scan_tabl
   if (comm && comm->nccl_comm) { p->comm = *comm; p->comm.ctx = ctx; }
   p->slots.resize((size_t)depth);
   const size_t bb = (p->block_bytes() + 255) / 256 * 256;
-  bool ok = hipStreamCreateWithFlags(&p->xstream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipStreamCreateWithFlags(&p->pstream, hipStreamNonBlocking) == hipSuccess;
+  bool ok = (p->xstream = make_stream_nonblocking()) && (p->pstream = make_stream_nonblocking());
   for (auto& s : p->slots) {
-    ok = ok && hipHostMalloc((void**)&s.h_cands, (size_t)p->per_cap * sizeof(cfear_candidate), hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipHostMalloc((void**)&s.h_recv, bb * (size_t)world, hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipMalloc((void**)&s.d_send, bb) == hipSuccess;
-    ok = ok && hipMalloc((void**)&s.d_jobs, (size_t)p->per_cap * reg_job_stride(2) + 256) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&s.prepared, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipMalloc((void**)&s.d_recv, bb * (size_t)world) == hipSuccess;
-    ok = ok && hipMemsetAsync(s.d_send, 0, bb, ctx->stream) == hipSuccess;        // padding slots: zero once, never written
-    ok = ok && hipEventCreateWithFlags(&s.computed, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&s.done, p->timing ? hipEventDefault : hipEventDisableTiming) == hipSuccess;
-    if (p->timing) ok = ok && hipEventCreate(&s.xbegin) == hipSuccess;
+    ok = ok && (s.h_cands = pinned_alloc<cfear_candidate>((size_t)p->per_cap * sizeof(cfear_candidate)));
+    ok = ok && (s.h_recv = pinned_alloc<char>(bb * (size_t)world));
+    ok = ok && (s.d_send = dev_alloc<char>(bb));
+    ok = ok && (s.d_jobs = dev_alloc<char>((size_t)p->per_cap * reg_job_stride(2) + 256));
+    ok = ok && (s.prepared = make_event(hipEventDisableTiming));
+    ok = ok && (s.d_recv = dev_alloc<char>(bb * (size_t)world));
+    ok = ok && hipMemsetAsync(s.d_send.get(), 0, bb, ctx->stream) == hipSuccess;  // padding slots: zero once, never written
+    ok = ok && (s.computed = make_event(hipEventDisableTiming));
+    ok = ok && (s.done = make_event(p->timing ? hipEventDefault : hipEventDisableTiming));
+    if (p->timing) ok = ok && (s.xbegin = make_event(hipEventDefault));
   }
   ok = ok && hipStreamSynchronize(ctx->stream) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
-    cfear_candidate_pipe_destroy(p);
     return cfear_set_error(ctx, CFEAR_ERR_HIP, "candidate pipe: buffer / stream creation failed");
   }
-  *out = p;
+  *out = p.release();
   return CFEAR_OK;
 }
 
@@ -376,7 +360,7 @@ extern "C" int cfear_candidate_pipe_submit(cfear_candidate_pipe* p, const cfear_
   cfear_shard_range(n_total, p->world, p->rank, &lo, &hi, &per);
   const int n = hi - lo;
   const size_t rbytes = (size_t)per * sizeof(cfear_reg_result), bytes = rbytes + sizeof(ShardTrailer);
-  int32_t* d_trailer = (int32_t*)(s.d_send + rbytes);
+  int32_t* d_trailer = (int32_t*)(s.d_send.get() + rbytes);
   // From here on nothing returns before the collective: peers are on their way into it (see gather_records_status).
   int local_rc = CFEAR_OK;
   if (n > 0) {
@@ -386,58 +370,61 @@ extern "C" int cfear_candidate_pipe_submit(cfear_candidate_pipe* p, const cfear_
     bool idle = true;
     for (auto& o : p->slots) idle = idle && o.ticket < 0;
     CandGeometry geom;
-    local_rc = cfear_candidates_expand(ctx, idle ? ctx->stream : p->pstream, p->table, cands + lo, n, par, s.h_cands, s.d_jobs, d_trailer, CFEAR_OK, &geom);
-    if (!idle && local_rc == CFEAR_OK && (hipEventRecord(s.prepared, p->pstream) != hipSuccess || hipStreamWaitEvent(ctx->stream, s.prepared, 0) != hipSuccess))
+    local_rc = cfear_candidates_expand(ctx, idle ? ctx->stream : p->pstream.get(), p->table, cands + lo, n, par, s.h_cands.get(), s.d_jobs.get(), d_trailer, CFEAR_OK, &geom);
+    if (!idle && local_rc == CFEAR_OK && (hipEventRecord(s.prepared.get(), p->pstream.get()) != hipSuccess || hipStreamWaitEvent(ctx->stream, s.prepared.get(), 0) != hipSuccess))
       local_rc = cfear_set_error(ctx, CFEAR_ERR_HIP, "candidate pipe: event between the preparation and the compute stream failed");
     const int hint_bits = (geom.hint.small_pairs ? 1 : 0) | (geom.hint.big_pass ? 2 : 0) | (geom.hint.whole_cu ? 4 : 0);
     const bool graph = p->use_graph && ctx->profile == 0;         // (per-kernel events do not go into a capture)
-    const bool replay = graph && s.exec && s.g_n == n && memcmp(&s.g_par, par, sizeof(*par)) == 0 && s.g_ws7 == ctx->ws[7].p &&
+    const bool replay = graph && s.exec && s.g_n == n && memcmp(&s.g_par, par, sizeof(*par)) == 0 && s.g_ws7 == ctx->ws[7].p.get() &&
                         s.g_pairs_cap == geom.pairs_cap && s.g_hint == hint_bits;
     if (local_rc != CFEAR_OK) {
     } else if (replay) {
-      if (hipGraphLaunch(s.exec, ctx->stream) != hipSuccess) local_rc = cfear_set_error(ctx, CFEAR_ERR_HIP, "hipGraphLaunch failed");
+      if (hipGraphLaunch(s.exec.get(), ctx->stream) != hipSuccess) local_rc = cfear_set_error(ctx, CFEAR_ERR_HIP, "hipGraphLaunch failed");
     } else if (graph && s.g_n != -2) {
       // first step of this shape in this slot: run the matcher once directly (workspaces and LDS attributes settle outside a
       // capture), then capture the same launches for the steps to come
-      local_rc = cfear_candidates_match(ctx, s.d_jobs, n, par, &geom, (cfear_reg_result*)s.d_send);
+      local_rc = cfear_candidates_match(ctx, s.d_jobs.get(), n, par, &geom, (cfear_reg_result*)s.d_send.get());
       if (local_rc == CFEAR_OK && hipStreamSynchronize(ctx->stream) == hipSuccess) {
-        if (s.exec) { (void)hipGraphExecDestroy(s.exec); s.exec = nullptr; }
+        s.exec.reset();
         hipGraph_t g = nullptr;
+        hipGraphExec_t exec = nullptr;
         bool cap = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-        int crc = cap ? cfear_candidates_match(ctx, s.d_jobs, n, par, &geom, (cfear_reg_result*)s.d_send) : CFEAR_ERR_HIP;
+        int crc = cap ? cfear_candidates_match(ctx, s.d_jobs.get(), n, par, &geom, (cfear_reg_result*)s.d_send.get()) : CFEAR_ERR_HIP;
         if (cap && hipStreamEndCapture(ctx->stream, &g) != hipSuccess) crc = CFEAR_ERR_HIP;
-        if (crc == CFEAR_OK && g && hipGraphInstantiate(&s.exec, g, nullptr, nullptr, 0) == hipSuccess) {
-          s.g_n = n; s.g_per = per; s.g_par = *par; s.g_ws7 = ctx->ws[7].p; s.g_pairs_cap = geom.pairs_cap; s.g_hint = hint_bits;
+        if (crc == CFEAR_OK && g && hipGraphInstantiate(&exec, g, nullptr, nullptr, 0) == hipSuccess) {
+          s.exec.reset(exec);
+          s.g_n = n; s.g_per = per; s.g_par = *par; s.g_ws7 = ctx->ws[7].p.get(); s.g_pairs_cap = geom.pairs_cap; s.g_hint = hint_bits;
         } else {
           (void)hipGetLastError();
-          s.exec = nullptr; s.g_n = -2;                           // capture is not available here: direct launches from now on
+          s.g_n = -2;                          // capture is not available here: direct launches from now on
         }
         if (g) (void)hipGraphDestroy(g);
         // (the direct run above already produced this step's records)
       }
     } else {
-      local_rc = cfear_candidates_match(ctx, s.d_jobs, n, par, &geom, (cfear_reg_result*)s.d_send);
+      local_rc = cfear_candidates_match(ctx, s.d_jobs.get(), n, par, &geom, (cfear_reg_result*)s.d_send.get());
     }
   }
   if (n == 0 || local_rc != CFEAR_OK) {                           // an empty or failed block: zeros + the status
-    (void)hipMemsetAsync(s.d_send, 0, rbytes, ctx->stream);
+    (void)hipMemsetAsync(s.d_send.get(), 0, rbytes, ctx->stream);
     (void)hipMemsetD32Async((hipDeviceptr_t)d_trailer, local_rc, 1, ctx->stream);
     (void)hipMemsetD32Async((hipDeviceptr_t)(d_trailer + 1), 0, 1, ctx->stream);
   }
-  bool ok = hipEventRecord(s.computed, ctx->stream) == hipSuccess;
-  ok = ok && hipStreamWaitEvent(p->xstream, s.computed, 0) == hipSuccess;
-  if (p->timing) ok = ok && hipEventRecord(s.xbegin, p->xstream) == hipSuccess;
-  const char* d_all = s.d_send;
+  hipStream_t xstream = p->xstream.get();
+  bool ok = hipEventRecord(s.computed.get(), ctx->stream) == hipSuccess;
+  ok = ok && hipStreamWaitEvent(xstream, s.computed.get(), 0) == hipSuccess;
+  if (p->timing) ok = ok && hipEventRecord(s.xbegin.get(), xstream) == hipSuccess;
+  const char* d_all = s.d_send.get();
   if (p->comm.nccl_comm) {
-    rc = allgather_on(&p->comm, p->xstream, s.d_send, s.d_recv, bytes);
+    rc = allgather_on(&p->comm, xstream, s.d_send.get(), s.d_recv.get(), bytes);
     if (rc != 0) return rc;
-    d_all = s.d_recv;
+    d_all = s.d_recv.get();
   }
-  ok = ok && hipMemcpyAsync(s.h_recv, d_all, bytes * (size_t)p->world, hipMemcpyDeviceToHost, p->xstream) == hipSuccess;
-  ok = ok && hipEventRecord(s.done, p->xstream) == hipSuccess;
+  ok = ok && hipMemcpyAsync(s.h_recv.get(), d_all, bytes * (size_t)p->world, hipMemcpyDeviceToHost, xstream) == hipSuccess;
+  ok = ok && hipEventRecord(s.done.get(), xstream) == hipSuccess;
   // the next step's kernels write other slots' buffers, but a step that comes back to THIS slot must find its exchange over:
   // collect() waits for `done` before it frees the slot, so no device-side edge is needed
-  if (!ok) { (void)hipGetLastError(); (void)hipStreamSynchronize(ctx->stream); (void)hipStreamSynchronize(p->xstream);
+  if (!ok) { (void)hipGetLastError(); (void)hipStreamSynchronize(ctx->stream); (void)hipStreamSynchronize(xstream);
              return cfear_set_error(ctx, CFEAR_ERR_HIP, "candidate pipe: enqueue failed"); }
   s.ticket = p->next_ticket; s.n_total = n_total; s.status = local_rc;
   *ticket = p->next_ticket++;
@@ -450,16 +437,16 @@ extern "C" int cfear_candidate_pipe_collect(cfear_candidate_pipe* p, int64_t tic
   if (!results || ticket < 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
   cfear_candidate_pipe::Slot& s = p->slots[(size_t)(ticket % p->depth)];
   if (s.ticket != ticket) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "candidate pipe: ticket %lld is not in flight", (long long)ticket);
-  CFEAR_HIP_CHECK(ctx, hipEventSynchronize(s.done));
+  CFEAR_HIP_CHECK(ctx, hipEventSynchronize(s.done.get()));
   const int per = (s.n_total + p->world - 1) / p->world;
   const size_t bytes = (size_t)per * sizeof(cfear_reg_result) + sizeof(ShardTrailer);
   if (p->timing) {
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s.xbegin, s.done) == hipSuccess) p->exchange_ms += ms;
+    if (hipEventElapsedTime(&ms, s.xbegin.get(), s.done.get()) == hipSuccess) p->exchange_ms += ms;
   }
   p->collected++;
-  unpack_blocks(s.h_recv, bytes, s.n_total, (int32_t)sizeof(cfear_reg_result), p->world, results);
-  const int rc = first_rank_status(s.h_recv, bytes, p->world);
+  unpack_blocks(s.h_recv.get(), bytes, s.n_total, (int32_t)sizeof(cfear_reg_result), p->world, results);
+  const int rc = first_rank_status(s.h_recv.get(), bytes, p->world);
   const int mine = s.status;
   s.ticket = -1;
   if (rc == CFEAR_OK) {
@@ -468,7 +455,7 @@ extern "C" int cfear_candidate_pipe_collect(cfear_candidate_pipe* p, int64_t tic
     int64_t got = 0;
     for (int r = 0; r < p->world; r++) {
       ShardTrailer t;
-      memcpy(&t, s.h_recv + (size_t)r * bytes + (bytes - sizeof(ShardTrailer)), sizeof(t));
+      memcpy(&t, s.h_recv.get() + (size_t)r * bytes + (bytes - sizeof(ShardTrailer)), sizeof(t));
       got += t.n_records;
     }
     if (got != s.n_total) return cfear_set_error(ctx, CFEAR_ERR_HIP, "candidate pipe: the exchange returned %lld of %d records", (long long)got, s.n_total);
