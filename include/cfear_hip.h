@@ -158,6 +158,37 @@ typedef struct cfear_kstrong_out {
 int cfear_filter_kstrongest(cfear_ctx* ctx, const uint8_t* polar, const cfear_polar_desc* desc,
                             const cfear_kstrong_params* par, const cfear_kstrong_out* out);
 
+/* Which k-strongest row-sweep kernel a call launches: the selection the filter call above, the row-key call below and the
+ * batched odometry make from the descriptor, the parameters and the image address, reported so that a test can name the
+ * kernel instantiation its input reaches.  Pure host code: no context, no device, no GPU call.
+ *   desc          the images as the row sweep gets them (rows = azimuths)
+ *   base_address  the address of the first image's first byte in device memory; only its low four bits are looked at, so
+ *                 the address modulo 16 serves as well
+ * kstrongest_rows_kernel<NCHUNK, VEC, MASK>:
+ *   nchunk        1, 2, 4 or 8 chunks of 1024 bins per row (16 bytes per lane and chunk): the smallest that covers cols
+ *   vec           rows are read in 16-byte pieces: address, stride and batch stride are multiples of 4 (else byte by byte)
+ *   mask          uchar((int)z_min) == 0: zero padding would pass the candidate test, so the byte-validity masks are applied
+ *   table_index   4 log2(nchunk) + 2 vec + mask, 0 .. 15: the entry of the dispatch table the launcher takes its kernel
+ *                 from -- the launcher reads THIS plan, so the report cannot differ from the launch
+ *   u_zmin        the candidate threshold, (uint8_t)(int)z_min (radar_driver.cpp:58, radar_filters.cpp:212): 256 -> 0, 0.9 -> 0,
+ *                 300 -> 44, -1 -> 255;  thi: u_zmin >= 128 (the other form of the byte compare)
+ *   min_range_bin ceil(min_distance / range_res) (radar_filters.cpp:315): only kept bins beyond it enter the clouds
+ *   kpad          entries of a row's key list, max(k rounded up to 4, 64);  lds_bytes: the launch's dynamic LDS (four rows)
+ *   refused       0, or why the filter call refuses these arguments (everything else is 0 then): CFEAR_KSTRONG_REFUSED_*
+ * Returns CFEAR_ERR_INVALID_ARGUMENT for a null pointer only.                                                              */
+#define CFEAR_KSTRONG_REFUSED_DESC 1       /* a bad descriptor: rows, cols, batch < 1, stride < cols, overlapping images */
+#define CFEAR_KSTRONG_REFUSED_COLS 2       /* cols > 8192 */
+#define CFEAR_KSTRONG_REFUSED_K 3          /* k_strongest outside [1, 1024] */
+#define CFEAR_KSTRONG_REFUSED_RANGE_RES 4  /* range_res <= 0 */
+struct cfear_kstrong_plan {
+  int32_t nchunk, vec, mask, table_index;
+  int32_t u_zmin, thi, min_range_bin, kpad;
+  int32_t refused, pad;
+  int64_t lds_bytes;
+};
+int cfear_kstrong_plan(const cfear_polar_desc* desc, const cfear_kstrong_params* par, uint64_t base_address,
+                       struct cfear_kstrong_plan* out);
+
 /* The filter stage of the batched odometry on its own (device memory only): radarDriver::Callback's decode
  * (radar_driver.cpp:74-90), FilterKstrongest (radar_filters.cpp:209-237) and the selection of
  * getPeaksFilteredPointCloud(cloud, false) (radar_filters.cpp:309-337) in ONE pass over the sweep.  Per azimuth row the kept

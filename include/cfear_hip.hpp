@@ -259,6 +259,13 @@ inline void filter_cacfar_rowkeys(Context& ctx, const uint8_t* d_image, const cf
                                   int32_t flags, uint32_t* d_row_keys, int32_t* d_row_counts, int32_t kcap) {
   ctx.check(cfear_filter_cacfar_rowkeys(ctx.get(), d_image, &desc, &par, flags, d_row_keys, d_row_counts, kcap));
 }
+// the k-strongest row sweep's kernel selection (cfear_hip.h: cfear_kstrong_plan); a refused call is reported in .refused
+inline struct cfear_kstrong_plan kstrong_plan(const cfear_polar_desc& desc, const cfear_kstrong_params& par, uint64_t base_address = 0) {
+  struct cfear_kstrong_plan out;
+  const int st = ::cfear_kstrong_plan(&desc, &par, base_address, &out);
+  if (st != CFEAR_OK) throw CfearError(st, cfear_status_string(st));
+  return out;
+}
 
 // k_strongest_filter (radar_filters.cpp:40-78, with InsertStrongestK :25-38): the legacy filter CorAl's kstrongRadar calls;
 // APPENDS to cloud

@@ -135,23 +135,47 @@ def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t))
 
 
-def kstrongest(img, k, z_min):
-    img = np.ascontiguousarray(img, dtype=np.uint8)
+def _strided_u8(img, stride):
+    """(array to keep alive, pointer to the image's first byte, rows, cols, stride) of a 2-D uint8 image for the oracle's
+    (img, rows, cols, stride) arguments.  A uint8 view whose NumPy strides are (stride, 1) with stride >= cols -- a cv::Mat
+    ROI -- is handed over in place, so that what lies between its rows is what the oracle reads there, provided the buffer it
+    views holds rows * stride bytes from the view's first byte (orc_peaks reads all of them); stride= asserts exactly that.
+    Anything else is copied (stride = cols), as a contiguous image always was."""
     rows, cols = img.shape
+    pitched = img.dtype == np.uint8 and img.strides[1] == 1 and (rows == 1 or img.strides[0] >= cols)
+    want = int(stride) if stride is not None else (int(img.strides[0]) if pitched and rows > 1 else cols)
+    owner = img
+    while getattr(owner, "base", None) is not None:      # (as_strided puts a holder object between a view and its array)
+        owner = owner.base
+    first = img.ctypes.data
+    end = owner.ctypes.data + owner.nbytes if isinstance(owner, np.ndarray) and owner.flags["C_CONTIGUOUS"] else first
+    inside = pitched and want >= cols and (rows == 1 or img.strides[0] == want) and first + rows * want <= end
+    if stride is not None:
+        assert inside, "stride=%d: not a uint8 view with that row pitch and rows * stride bytes behind it" % stride
+    if not inside:
+        img, want = np.ascontiguousarray(img, dtype=np.uint8), cols
+    return img, C.cast(img.ctypes.data, C.POINTER(C.c_uint8)), rows, cols, want
+
+
+def kstrongest(img, k, z_min, stride=None):
+    """img: uint8 [rows, cols], contiguous or a view with a row pitch (or stride=, see _strided_u8)."""
+    img, ptr, rows, cols, stride = _strided_u8(img, stride)
     sr = np.empty((rows, k), np.int32)
     si = np.empty((rows, k), np.uint8)
     sc = np.empty(rows, np.int32)
-    rc = lib().orc_kstrongest(_p(img, C.c_uint8), rows, cols, cols, k, int(z_min), _p(sr, C.c_int32),
+    rc = lib().orc_kstrongest(ptr, rows, cols, stride, k, int(z_min), _p(sr, C.c_int32),
                               _p(si, C.c_uint8), _p(sc, C.c_int32))
     assert rc == 0
     return sr, si, sc
 
 
-def peaks(img, k, sel_range, sel_count):
-    img = np.ascontiguousarray(img, dtype=np.uint8)
-    rows, cols = img.shape
+def peaks(img, k, sel_range, sel_count, stride=None):
+    """AxialNonMaxSupress on a contiguous image or on a pitched view: the bytes it reads before and after a row are then the
+    parent buffer's padding, inside [0, rows * stride) of the view's first byte (0 outside) -- the view's buffer must hold
+    rows * stride bytes from there."""
+    img, ptr, rows, cols, stride = _strided_u8(img, stride)
     pk = np.empty((rows, k), np.uint8)
-    lib().orc_peaks(_p(img, C.c_uint8), rows, cols, cols, k, _p(sel_range, C.c_int32),
+    lib().orc_peaks(ptr, rows, cols, stride, k, _p(sel_range, C.c_int32),
                     _p(sel_count, C.c_int32), _p(pk, C.c_uint8))
     return pk
 

@@ -67,6 +67,15 @@ class CacfarPlan(C.Structure):     # struct cfear_cacfar_plan
 ROWKEYS_BINS_MAJOR, CACFAR_PLAN_KEYS = 1, 0x100      # CFEAR_ROWKEYS_BINS_MAJOR, CFEAR_CACFAR_PLAN_KEYS
 
 
+class KStrongPlan(C.Structure):    # struct cfear_kstrong_plan
+    _fields_ = [(n, C.c_int32) for n in ("nchunk", "vec", "mask", "table_index", "u_zmin", "thi", "min_range_bin", "kpad",
+                                         "refused", "pad")] + [("lds_bytes", C.c_int64)]
+
+
+# CFEAR_KSTRONG_REFUSED_*
+KSTRONG_REFUSED = {0: None, 1: "bad polar descriptor", 2: "cols > 8192", 3: "k_strongest outside [1, 1024]", 4: "range_res <= 0"}
+
+
 class Cen2018Params(C.Structure):
     _fields_ = [("zq", C.c_float), ("sigma_gauss", C.c_int32), ("min_range_bins", C.c_int32), ("pad", C.c_int32),
                 ("range_res", C.c_double)]
@@ -283,7 +292,7 @@ EXPORTS = [
     "cfear_kitti_from_xyt", "cfear_cen2018_params_default", "cfear_filter_cen2018",
     "cfear_logreg_params_default", "cfear_logreg_fit_batch", "cfear_p2p_quality", "cfear_p2p_quality_batch",
     "cfear_cart_params_default", "cfear_polar_to_cartesian", "cfear_cart_quality_batch",
-    "cfear_cacfar_plan", "cfear_filter_cacfar_rowkeys",
+    "cfear_cacfar_plan", "cfear_filter_cacfar_rowkeys", "cfear_kstrong_plan",
     "cfear_closure_params_default", "cfear_closure_candidates_batch",
 ]
 
@@ -441,6 +450,7 @@ def lib():
     L.cfear_filter_cacfar.argtypes = [vp, vp, C.POINTER(PolarDesc), C.POINTER(CacfarParams), vp, vp,
                                       C.c_int32, vp]
     L.cfear_cacfar_plan.argtypes = [C.POINTER(PolarDesc), C.POINTER(CacfarParams), C.c_int32, C.POINTER(CacfarPlan)]
+    L.cfear_kstrong_plan.argtypes = [C.POINTER(PolarDesc), C.POINTER(KStrongParams), C.c_uint64, C.POINTER(KStrongPlan)]
     L.cfear_filter_cacfar_rowkeys.argtypes = [vp, vp, C.POINTER(PolarDesc), C.POINTER(CacfarParams), C.c_int32, vp, vp, C.c_int32]
     L.cfear_cen2018_params_default.argtypes = [C.POINTER(Cen2018Params)]
     L.cfear_cen2018_params_default.restype = None

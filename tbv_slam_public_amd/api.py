@@ -34,6 +34,20 @@ def _ptr(x):
     return x.ctypes.data, x
 
 
+def _torch_ready(ctx, *arrays):
+    """Waits until the work torch has queued on its current stream -- the fill of a fresh tensor, the copy behind a
+    torch.stack -- is finished, when one of `arrays` is a torch tensor and `ctx` enqueues on a stream of its own.  A private
+    stream is non-blocking: without the wait a kernel of the context may read such a tensor before torch has written it, or
+    have its output overwritten by a fill that was queued first.  Nothing to do where the context shares torch's stream
+    (default_context()): there the stream orders the two."""
+    if not any(_is_torch(a) for a in arrays):
+        return
+    import torch
+    ts = int(torch.cuda.current_stream(ctx.device).cuda_stream) or 1      # torch's null stream: hipStreamLegacy
+    if ctx.stream_handle() != ts:
+        torch.cuda.current_stream(ctx.device).synchronize()
+
+
 class Context:
     """cfear_ctx: one per host thread / HIP stream.  `stream` = a hipStream_t handle to enqueue on; None or 0 (which is
     also what torch reports for its default stream) gives the context a PRIVATE non-blocking stream: work torch has queued
@@ -178,13 +192,17 @@ def polar_rotate_ccw(img, ctx=None):
 
 def filter_kstrongest(img, k, z_min, range_res, min_distance, want_peaks=False, ctx=None):
     """StructuredKStrongest (radar_filters.cpp:198-337) for a uint8 image [rows, cols] or a batch
-    [b, rows, cols] (NumPy -> NumPy results, torch CUDA tensor -> torch CUDA results).
+    [b, rows, cols] (NumPy -> NumPy results, torch CUDA tensor -> torch CUDA results; a torch view with a row pitch or a
+    batch stride is used in place).
     Returns dict(sel_range, sel_intensity, sel_count, is_peak, xyzi, n_points, xyzi_peaks, n_peaks)."""
     ctx = ctx or default_context()
     d, batch, rows, cols = _desc(img)
     par = L.KStrongParams(int(k), float(z_min), float(range_res), float(min_distance), int(bool(want_peaks)))
     if _is_torch(img):
         import torch
+        assert img.dtype == torch.uint8 and img.stride(-1) == 1
+        d.stride = img.stride(-2)
+        d.batch_stride = img.stride(0) if img.ndim == 3 else rows * d.stride
         dev = img.device
         mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
         res = dict(sel_range=mk((batch, rows, k), torch.int32), sel_intensity=mk((batch, rows, k), torch.uint8),
@@ -204,7 +222,7 @@ def filter_kstrongest(img, k, z_min, range_res, min_distance, want_peaks=False, 
     out = L.KStrongOut()
     for name in ("sel_range", "sel_intensity", "sel_count", "is_peak", "xyzi", "n_points", "xyzi_peaks", "n_peaks"):
         setattr(out, name, _ptr(res.get(name))[0])
-    p, _keep = _ptr(img)
+    p = img.data_ptr() if _is_torch(img) else _ptr(img)[0]
     ctx.check(ctx._lib.cfear_filter_kstrongest(ctx.h, p, C.byref(d), C.byref(par), C.byref(out)))
     return res
 
@@ -280,6 +298,25 @@ def cacfar_plan(rows, cols, window_size, nb_guard_cells, false_alarm_rate, range
     if rc != 0:
         raise L.CfearError(rc, "cfear_cacfar_plan: bad descriptor or parameters")
     return {name: int(getattr(out, name)) for name, _ in L.CacfarPlan._fields_}
+
+
+def kstrong_plan(rows, cols, k, z_min, range_res=0.0438, min_distance=2.5, stride=None, batch=1, batch_stride=None, base=0):
+    """cfear_kstrong_plan: which kstrongest_rows_kernel<NCHUNK, VEC, MASK> a call launches, as a dict of the struct's fields
+    (include/cfear_hip.h) with "refused" None or the reason the filter call refuses the arguments.  Host code only: needs no
+    GPU and no context.  rows, cols (, stride, batch, batch_stride): the images as the row sweep gets them; base: the address
+    of the first image (or that address modulo 16)."""
+    d = L.PolarDesc()
+    d.rows, d.cols, d.batch = int(rows), int(cols), int(batch)
+    d.stride = int(cols if stride is None else stride)
+    d.batch_stride = int(d.rows * d.stride if batch_stride is None else batch_stride)
+    par = L.KStrongParams(int(k), float(z_min), float(range_res), float(min_distance), 0)
+    out = L.KStrongPlan()
+    rc = L.lib().cfear_kstrong_plan(C.byref(d), C.byref(par), int(base) & 0xFFFFFFFFFFFFFFFF, C.byref(out))
+    if rc != 0:
+        raise L.CfearError(rc, "cfear_kstrong_plan: null argument")
+    res = {name: int(getattr(out, name)) for name, _ in L.KStrongPlan._fields_ if name != "pad"}
+    res["refused"] = L.KSTRONG_REFUSED[res["refused"]]
+    return res
 
 
 def filter_cacfar_rowkeys(img, window_size, nb_guard_cells, false_alarm_rate, range_res, z_min, min_distance,
@@ -1772,6 +1809,7 @@ def sc_descriptors(clouds, par=None, shifts_y=(0.0,), ctx=None, device_out=False
     rk = np.zeros((n, A, R), np.float64)
     sk = np.zeros((n, A, S), np.float64)
     sh = (C.c_double * A)(*[float(v) for v in shifts_y])
+    _torch_ready(ctx, desc, *clouds)
     ctx.check(ctx._lib.cfear_sc_descriptors(ctx.h, arr, n, C.byref(par), sh, A, _ptr(desc)[0], rk.ctypes.data,
                                             sk.ctypes.data))
     return desc, rk, sk
@@ -1788,6 +1826,7 @@ def sc_distance_batch(desc_q, desc_c, pairs, par=None, ctx=None):
     dist = np.zeros(pr.shape[0], np.float64)
     shift = np.zeros(pr.shape[0], np.int32)
     if pr.shape[0]:
+        _torch_ready(ctx, q, c)
         ctx.check(ctx._lib.cfear_sc_distance_batch(ctx.h, _ptr(q)[0], q.shape[0], _ptr(c)[0], c.shape[0],
                                                    pr.ctypes.data, pr.shape[0], C.byref(par), dist.ctypes.data,
                                                    shift.ctypes.data))
@@ -1852,6 +1891,7 @@ def sc_raw_descriptors(imgs, par=None, raw=None, ctx=None, device_out=False):
         desc = np.zeros((B, R, S), np.float64)
     rk = np.zeros((B, R), np.float64)
     sk = np.zeros((B, S), np.float64)
+    _torch_ready(ctx, desc, imgs)
     ctx.check(ctx._lib.cfear_sc_raw_descriptors(ctx.h, ptr, C.byref(d), C.byref(par), C.byref(raw), _ptr(desc)[0],
                                                 rk.ctypes.data, sk.ctypes.data))
     del keep
@@ -2105,6 +2145,7 @@ def sc_local_map_descriptors(clouds, poses_xyt=None, n_aggregate=1, centers=None
     rk = np.zeros((nc, A, R), np.float64)
     sk = np.zeros((nc, A, S), np.float64)
     sh = (C.c_double * A)(*[float(v) for v in shifts_y])
+    _torch_ready(ctx, desc, *clouds)
     ctx.check(ctx._lib.cfear_sc_local_map_descriptors(ctx.h, arr, len(clouds), ctr.ctypes.data, nc, int(n_aggregate), C.byref(par),
                                                       sh, A, _ptr(desc)[0], rk.ctypes.data, sk.ctypes.data))
     del keep

@@ -321,6 +321,9 @@ __device__ __forceinline__ void kstrong_row(const KStrongArgs& a, const int r, c
     //     each trial is one SWAR pass over the register-resident row (5 VALU per 4 bins); the first trial assumes
     //     a flat intensity distribution above the threshold, later ones bisect.  If two neighbouring thresholds
     //     bracket k the cut is known exactly (a plateau) and goes to the tie scan below.
+    //     Invariant: c_lo = #(>= lo) >= k > c_hi = #(>= hi), so on exit without a trial in [k, 256] the cut is T = lo with
+    //     c_lo >= k > c_hi.  A trial is tested for "< k" FIRST: k may exceed 256 (kMaxK = 1024), and a count in (256, k) is
+    //     below the cut, not above it (every row with k > 256 ends here, exactly).
     uint32_t bt[NCHUNK];
     int t_lane = c_lane, t_incl = c_incl, n_c = n_ge;
 #pragma unroll
@@ -346,8 +349,8 @@ __device__ __forceinline__ void kstrong_row(const KStrongArgs& a, const int r, c
         for (int c = 0; c < NCHUNK; c++) x_lane += __popc(bx[c]);
         const int x_incl = wave_incl_scan_i32(x_lane);
         const int cnt = __builtin_amdgcn_readlane(x_incl, 63);
-        if (cnt > 256) { lo = mid; c_lo = cnt; }
-        else if (cnt < k) { hi = mid; c_hi = cnt; }
+        if (cnt < k) { hi = mid; c_hi = cnt; }
+        else if (cnt > 256) { lo = mid; c_lo = cnt; }
         else {
 #pragma unroll
           for (int c = 0; c < NCHUNK; c++) bt[c] = bx[c];
@@ -1925,25 +1928,64 @@ int check_desc(cfear_ctx* ctx, const cfear_polar_desc* d) {
   return CFEAR_OK;
 }
 
-template <int NCHUNK>
-void launch_kstrong(cfear_ctx* ctx, const KStrongArgs& a, bool vec, bool mask, dim3 grid, size_t lds) {
-  if (vec) {
-    if (mask) hipLaunchKernelGGL((kstrongest_rows_kernel<NCHUNK, true, true>), grid, dim3(256), lds, ctx->stream, a);
-    else hipLaunchKernelGGL((kstrongest_rows_kernel<NCHUNK, true, false>), grid, dim3(256), lds, ctx->stream, a);
-  } else {
-    if (mask) hipLaunchKernelGGL((kstrongest_rows_kernel<NCHUNK, false, true>), grid, dim3(256), lds, ctx->stream, a);
-    else hipLaunchKernelGGL((kstrongest_rows_kernel<NCHUNK, false, false>), grid, dim3(256), lds, ctx->stream, a);
+// ---- the dispatch table of the row sweep: index 4 log2(NCHUNK) + 2 VEC + MASK, as cfear_kstrong_plan documents it ----------
+using KStrongFn = void (*)(const KStrongArgs);
+constexpr int kKStrongEntries = 16;
+#define CFEAR_KSTRONG_ROW4(N) \
+  kstrongest_rows_kernel<N, false, false>, kstrongest_rows_kernel<N, false, true>, kstrongest_rows_kernel<N, true, false>, \
+  kstrongest_rows_kernel<N, true, true>
+const KStrongFn kKStrongTable[kKStrongEntries] = {CFEAR_KSTRONG_ROW4(1), CFEAR_KSTRONG_ROW4(2), CFEAR_KSTRONG_ROW4(4), CFEAR_KSTRONG_ROW4(8)};
+#undef CFEAR_KSTRONG_ROW4
+
+// The one selection: everything cfear_kstrong_device launches follows from the plan this fills.  No validation here (the entry
+// points refuse what cfear_kstrong_plan reports as refused); base = the address of the first image.
+void kstrong_select(const cfear_polar_desc* desc, const cfear_kstrong_params* par, uint64_t base, struct cfear_kstrong_plan& p) {
+  memset(&p, 0, sizeof(p));
+  const int z_min_i = (int)par->z_min;                         // radar_driver.cpp:58 float -> int
+  p.u_zmin = (int)(uint8_t)z_min_i;                            // radar_filters.cpp:212 uchar(z_min_)
+  p.thi = p.u_zmin >= 128;
+  const int64_t batch_stride = desc->batch > 1 ? desc->batch_stride : (int64_t)desc->rows * desc->stride;
+  p.vec = (base % 4 == 0) && (desc->stride % 4 == 0) && (batch_stride % 4 == 0);
+  // Byte-validity masks only where a zero byte could pass a test, i.e. z_min == 0: load_row() zero-fills what lies beyond the row
+  // (ragged widths: Oxford's native 3768 bins end 8 bytes into a 16-byte piece), every threshold the kernel compares with is
+  // >= uchar(z_min), and the peaks' halo bytes are written behind the last re-read of the staged row.  (Until round 6 every
+  // width that is not a multiple of 16 took the masked instantiation: 1.84 instead of 1.25 ms per 4096 Oxford-native sweeps.)
+  p.mask = p.u_zmin == 0;
+  const int need = (desc->cols + 1023) / 1024;
+  const int lg = need <= 1 ? 0 : (need <= 2 ? 1 : (need <= 4 ? 2 : 3));
+  p.nchunk = 1 << lg;
+  p.table_index = 4 * lg + 2 * p.vec + p.mask;
+  {
+    const double range_res_ = (double)par->range_res, min_distance_ = (double)par->min_distance;
+    p.min_range_bin = (int)std::ceil(min_distance_ / range_res_);            // radar_filters.cpp:315
   }
+  p.kpad = std::max((par->k_strongest + 3) & ~3, 64);
+  // per wavefront: the raw row and its two 16-byte halos | scratch | the key list (kstrongest_rows_kernel carves the same)
+  p.lds_bytes = (int64_t)kRowsPerBlock * (p.nchunk * 1024 + 32 + kstrong_scratch_bytes(p.nchunk) + p.kpad * 4);
 }
 
 }  // namespace
+
+extern "C" int cfear_kstrong_plan(const cfear_polar_desc* desc, const cfear_kstrong_params* par, uint64_t base_address,
+                                  struct cfear_kstrong_plan* out) {
+  if (!desc || !par || !out) return CFEAR_ERR_INVALID_ARGUMENT;
+  memset(out, 0, sizeof(*out));
+  // what cfear_filter_kstrongest refuses, in its order (check_desc, k, range_res)
+  if (desc->rows <= 0 || desc->cols <= 0 || desc->stride < desc->cols || desc->batch <= 0 ||
+      (desc->batch > 1 && desc->batch_stride < (int64_t)desc->rows * desc->stride))
+    out->refused = CFEAR_KSTRONG_REFUSED_DESC;
+  else if (desc->cols > kMaxCols) out->refused = CFEAR_KSTRONG_REFUSED_COLS;
+  else if (par->k_strongest < 1 || par->k_strongest > kMaxK) out->refused = CFEAR_KSTRONG_REFUSED_K;
+  else if (!(par->range_res > 0.f)) out->refused = CFEAR_KSTRONG_REFUSED_RANGE_RES;
+  else kstrong_select(desc, par, base_address, *out);
+  return CFEAR_OK;
+}
 
 // Device-side entry used by cfear_filter_kstrongest and by the odometry pipeline: everything is
 // already in device memory; outputs that are nullptr are skipped.
 int cfear_kstrong_device(cfear_ctx* ctx, const uint8_t* d_polar, const cfear_polar_desc* desc,
                          const cfear_kstrong_params* par, const cfear_kstrong_out* o, bool dense_halo,
                          const cfear_kstrong_fused* fused) {
-  const int z_min_i = (int)par->z_min;                         // radar_driver.cpp:58 float -> int
   KStrongArgs a;
   a.row_keys = nullptr;
   a.image_offsets = fused ? (const long long*)fused->image_offsets : nullptr;
@@ -1955,44 +1997,31 @@ int cfear_kstrong_device(cfear_ctx* ctx, const uint8_t* d_polar, const cfear_pol
   a.rows = desc->rows; a.cols = desc->cols; a.stride = desc->stride; a.batch = desc->batch;
   a.batch_stride = desc->batch > 1 ? desc->batch_stride : (int64_t)desc->rows * desc->stride;
   a.k = par->k_strongest;
-  a.u_zmin = (int)(uint8_t)z_min_i;                            // radar_filters.cpp:212 uchar(z_min_)
+  struct cfear_kstrong_plan plan;                             // the threshold, vec, mask, nchunk and the LDS size: cfear_kstrong_plan's own
+  kstrong_select(desc, par, (uint64_t)(uintptr_t)d_polar, plan);
+  a.u_zmin = plan.u_zmin;
   a.want_peaks = par->want_peaks && (o->is_peak != nullptr);
   a.sel_range = o->sel_range; a.sel_intensity = o->sel_intensity; a.sel_count = o->sel_count;
   a.is_peak = o->is_peak;
   const bool want_cloud = o->xyzi || o->n_points || o->xyzi_peaks || o->n_peaks;
   a.row_valid = nullptr;
   a.dense_halo = (dense_halo && desc->stride != desc->cols) ? 1 : 0;
-  {
-    const double range_res_ = (double)par->range_res, min_distance_ = (double)par->min_distance;
-    a.min_range_bin = (int)std::ceil(min_distance_ / range_res_);            // radar_filters.cpp:315
-  }
+  a.min_range_bin = plan.min_range_bin;
   if (fused && fused->row_valid) {
     a.row_valid = fused->row_valid;
   } else if (want_cloud) {
     a.row_valid = (int32_t*)cfear_workspace(ctx, kWsFilterRows, (size_t)desc->batch * desc->rows * 8);
     if (!a.row_valid) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
   }
-  const bool vec = (((uintptr_t)d_polar) % 4 == 0) && (a.stride % 4 == 0) && (a.batch_stride % 4 == 0);
-  // Byte-validity masks only where a zero byte could pass a test, i.e. z_min == 0: load_row() zero-fills what lies beyond the row
-  // (ragged widths: Oxford's native 3768 bins end 8 bytes into a 16-byte piece), every threshold the kernel compares with is
-  // >= uchar(z_min), and the peaks' halo bytes are written behind the last re-read of the staged row.  (Until round 6 every
-  // width that is not a multiple of 16 took the masked instantiation: 1.84 instead of 1.25 ms per 4096 Oxford-native sweeps.)
-  const bool mask = a.u_zmin == 0;
-  const int nchunk = (a.cols + 1023) / 1024;
-  const int kpad = std::max((a.k + 3) & ~3, 64);
+  if (plan.table_index < 0 || plan.table_index >= kKStrongEntries || plan.nchunk * 1024 < a.cols)   // a missing kernel is an error
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "k-strongest: no kernel for %d bins", a.cols);
+  const KStrongFn fn = kKStrongTable[plan.table_index];
   {
     ProfScope ps(ctx, "kstrongest_rows");
     for (int b0 = 0; b0 < a.batch; b0 += 65535) {             // gridDim.y limit
       a.batch0 = b0;
       dim3 grid((unsigned)((a.rows + kRowsPerBlock - 1) / kRowsPerBlock), (unsigned)std::min(65535, a.batch - b0));
-      auto lds = [&](int nchunk_t) {
-        const int np = (nchunk_t + 1) / 2;
-        return (size_t)kRowsPerBlock * (nchunk_t * 1024 + 32 + std::max(1024, (np + 2) * 256) + kpad * 4);
-      };
-      if (nchunk <= 1) launch_kstrong<1>(ctx, a, vec, mask, grid, lds(1));
-      else if (nchunk <= 2) launch_kstrong<2>(ctx, a, vec, mask, grid, lds(2));
-      else if (nchunk <= 4) launch_kstrong<4>(ctx, a, vec, mask, grid, lds(4));
-      else launch_kstrong<8>(ctx, a, vec, mask, grid, lds(8));
+      hipLaunchKernelGGL(fn, grid, dim3(256), (size_t)plan.lds_bytes, ctx->stream, a);
     }
   }
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
