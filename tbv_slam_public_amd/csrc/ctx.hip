@@ -1,5 +1,6 @@
 // ctx.hip -- context, error reporting, profiling, workspaces and scan slabs of libcfear_hip.so.
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 
 #include "common.hpp"
@@ -173,6 +174,33 @@ void HostStage::drain() {
   else if (pinned_) cfear_pinned_mark(ctx_);                 // a kernel may be reading the record in place
   pending_ = false;
   pinned_ = nullptr;
+}
+
+// cos / sin of the azimuths (radar_filters.cpp:317), computed on the host in double so that the device's float
+// coordinates are bit-exact with the reference; cached per context.
+int cfear_trig_tables(cfear_ctx* ctx, int rows, double** d_cos, double** d_sin) {
+  if (ctx->trig_rows == rows && ctx->ws[kWsTrig].p) {      // tables are cached per context
+    *d_cos = (double*)ctx->ws[kWsTrig].p.get();
+    *d_sin = (double*)ctx->ws[kWsTrig].p.get() + rows;
+    return CFEAR_OK;
+  }
+  HostStage st(ctx, kWsTrig);
+  const size_t bytes = 2 * (size_t)rows * sizeof(double);
+  double* h = (double*)st.record(bytes);
+  for (int bearing = 0; bearing < rows; bearing++) {
+    const double theta = (double(bearing + 1) / rows) * 2. * M_PI;           // radar_filters.cpp:317
+    h[bearing] = std::cos(theta);
+    h[rows + bearing] = std::sin(theta);
+  }
+  double* d;
+  st.piece(d, bytes);
+  CFEAR_CHECK(st.carve());
+  CFEAR_CHECK(st.upload(d, h, bytes));
+  CFEAR_CHECK(st.finish());
+  ctx->trig_rows = rows;
+  *d_cos = d;
+  *d_sin = d + rows;
+  return CFEAR_OK;
 }
 
 int cfear_allow_lds(cfear_ctx* ctx, const void* kernel, size_t bytes) {

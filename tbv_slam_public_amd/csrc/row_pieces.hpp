@@ -1,5 +1,5 @@
-// When may a kernel read 16 bytes of an image row in one piece?  Plain C++ (no HIP header): the row kernels of filter.hip
-// include it, and tests/cpp/row_pieces_check.cpp checks it on the CPU against every small image.
+// When may a kernel read 16 bytes of an image row in one piece?  Plain C++ (no HIP header): the row kernels of kstrong.hip and
+// cacfar.hip include it (through polar_common.hpp), and tests/cpp/row_pieces_check.cpp checks it on the CPU against every small image.
 #pragma once
 
 #if defined(__HIPCC__)

@@ -1,5 +1,5 @@
 """The k-strongest matrix: one small input per kstrongest_rows_kernel<NCHUNK, VEC, MASK> instantiation and per selection
-path of kstrong_row (tbv_slam_public_amd/csrc/filter.hip), shared by tests/test_kstrong_plan_cpu.py (every case reaches the
+path of kstrong_row (tbv_slam_public_amd/csrc/kstrong.hip), shared by tests/test_kstrong_plan_cpu.py (every case reaches the
 instantiation it names: cfear_kstrong_plan, no GPU; every row reaches the path it names; the model below equals the oracle)
 and tests/test_gpu_kstrong_matrix.py (every case equals the oracle bit for bit on the strided view).
 

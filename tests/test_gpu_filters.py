@@ -408,7 +408,11 @@ def _rowkeys_check(keys, cnt, img_rows_major, k, z_min, range_res, min_distance)
 @pytest.mark.parametrize("bins,az,k,z_min,data", [
     (3360, 400, 12, 60, "scene"), (3360, 400, 40, 60, "dense"), (3360, 48, 40, 60, "uniform"), (1000, 64, 12, 100, "uniform"),
     (2000, 32, 7, 0, "uniform"), (1501, 16, 40, 200, "uniform"), (4096, 16, 64, 250, "uniform"), (37, 16, 5, 10, "uniform"),
-    (3360, 40, 12, 60, "uniform"), (5000, 16, 12, 100, "uniform")])
+    (3360, 40, 12, 60, "uniform"), (5000, 16, 12, 100, "uniform"),
+    # one row per kstrongest_cols_kernel<NCHUNK, MASK> (the forced tile sweep runs it on every tile): NCHUNK covers
+    # ceil(bins / 1024), MASK = bins % 16 != 0 (z_min > 0) -- <1, no>, <1, yes>, <2, no>, <2, yes>, <4, no>, <4, yes>
+    (64, 16, 5, 10, "uniform"), (72, 16, 5, 10, "uniform"), (1040, 16, 5, 10, "uniform"), (1032, 16, 5, 10, "uniform"),
+    (2064, 16, 5, 10, "uniform"), (2056, 16, 5, 10, "uniform")])
 def test_rowkeys_fused_decode_matches_oracle_and_two_pass(bins, az, k, z_min, data):
     """[range bins][azimuths] sweeps (every sensor but Oxford's, radar_driver.cpp:74-90): the fused decode lists the bins
     >= z_min per azimuth in one streaming pass, picks the k strongest of each list, and sweeps the 16-column tiles of
@@ -509,3 +513,60 @@ def test_rowkeys_fuzz_geometries_parameters_and_routes():
         api.default_context().synchronize()
         for o in outs:
             _rowkeys_check(*o, rot, k, z_min, 0.0438, md)
+
+
+def test_bad_polar_descriptors_are_refused_with_the_same_words_by_every_entry_point():
+    """One descriptor check behind every polar entry point (polar_common.hpp): the status and the cfear_last_error text of
+    cfear_filter_kstrongest, cfear_filter_kstrongest_rowkeys, cfear_filter_cacfar, cfear_filter_cacfar_rowkeys,
+    cfear_filter_kstrongest_legacy and cfear_polar_rotate_ccw for hand-built descriptors of a 4 x 16 device image.  Every
+    call is refused before anything is launched or read."""
+    import ctypes as C
+    import torch
+    from tbv_slam_public_amd import api, _lib as L
+    ctx = api.default_context()
+    lib = ctx._lib
+    img = torch.zeros((4, 16), dtype=torch.uint8, device="cuda")
+    out = torch.zeros(4096, dtype=torch.uint8, device="cuda")          # stands in for every output: nothing is written
+    p, o = img.data_ptr(), out.data_ptr()
+    geometry = {"rows = 0": L.PolarDesc(0, 16, 16, 1, 64), "cols = 0": L.PolarDesc(4, 0, 16, 1, 64),
+                "stride < cols": L.PolarDesc(4, 16, 15, 1, 64), "batch = 0": L.PolarDesc(4, 16, 16, 0, 64),
+                "batch_stride < rows * stride": L.PolarDesc(4, 16, 16, 2, 63)}
+    wide = {"8193 bins": L.PolarDesc(4, 8193, 8193, 1, 4 * 8193)}
+    wide_bins_major = {"8193 bins, bins-major": L.PolarDesc(8193, 16, 16, 1, 8193 * 16)}
+    kp = L.KStrongParams(5, 10.0, 0.0438, 2.5, 0)
+    cp = L.CacfarParams(8, 2, 0.01, 0.0438, 60.0, 2.5, 400.0)
+    ko = L.KStrongOut(o, o, o, None, None, None, None, None)
+    BAD, WIDE = "bad polar descriptor", "cols > 8192 unsupported"
+    entries = [
+        ("cfear_filter_kstrongest", lambda d, fl: lib.cfear_filter_kstrongest(ctx.h, p, C.byref(d), C.byref(kp), C.byref(ko)), WIDE),
+        ("cfear_filter_cacfar", lambda d, fl: lib.cfear_filter_cacfar(ctx.h, p, C.byref(d), C.byref(cp), o, o, 64, None), WIDE),
+        ("cfear_filter_kstrongest_legacy",
+         lambda d, fl: lib.cfear_filter_kstrongest_legacy(ctx.h, p, C.byref(d), 5, 10.0, 0.0438, 2.5, o, o, 64), WIDE),
+        ("cfear_filter_kstrongest_rowkeys",
+         lambda d, fl: lib.cfear_filter_kstrongest_rowkeys(ctx.h, p, C.byref(d), C.byref(kp), fl, o, o), BAD),
+        ("cfear_filter_cacfar_rowkeys",
+         lambda d, fl: lib.cfear_filter_cacfar_rowkeys(ctx.h, p, C.byref(d), C.byref(cp), fl, o, o, 8), BAD),
+        ("cfear_polar_rotate_ccw", lambda d, fl: lib.cfear_polar_rotate_ccw(ctx.h, p, C.byref(d), o, 16, 256), None)]
+
+    def refused(name, call, what, d, flags, text):
+        rc = call(d, flags)
+        assert rc == L.ERR_INVALID_ARGUMENT, (name, what, rc)
+        assert lib.cfear_last_error(ctx.h).decode() == text, (name, what, lib.cfear_last_error(ctx.h).decode())
+
+    for name, call, wide_text in entries:
+        rowkeys = name.endswith("_rowkeys")
+        for what, d in geometry.items():
+            for flags in ((0, L.ROWKEYS_BINS_MAJOR) if rowkeys else (0,)):
+                refused(name, call, what, d, flags, BAD)
+        if wide_text is None:                                  # the rotation has no width limit (and nothing is launched here)
+            continue
+        for what, d in wide.items():
+            refused(name, call, what, d, 0, wide_text)
+        if rowkeys:
+            for what, d in wide_bins_major.items():
+                refused(name, call, what, d, L.ROWKEYS_BINS_MAJOR, wide_text)
+    # the rotation adds its destination terms on top of the shared check
+    refused("cfear_polar_rotate_ccw", lambda d, fl: lib.cfear_polar_rotate_ccw(ctx.h, p, C.byref(d), o, 3, 256), "dst_stride < rows",
+            L.PolarDesc(4, 16, 16, 1, 64), 0, BAD)
+    refused("cfear_polar_rotate_ccw", lambda d, fl: lib.cfear_polar_rotate_ccw(ctx.h, p, C.byref(d), o, 16, 255),
+            "dst_batch_stride < cols * dst_stride", L.PolarDesc(4, 16, 16, 2, 64), 0, BAD)

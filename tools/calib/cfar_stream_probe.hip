@@ -156,7 +156,7 @@ int main() {
   uint8_t* img; uint32_t *keys, *res; int32_t* cnt;
   hipMalloc(&img, bytes); hipMalloc(&keys, (size_t)IMAGES * AZ * KCAP * 4); hipMalloc(&cnt, (size_t)IMAGES * AZ * NSEG * 4); hipMalloc(&res, 64);
   hipLaunchKernelGGL(fill_kernel, dim3(4096), dim3(256), 0, 0, img, bytes);
-  const double N = 2.0 * W, scaling = N * (std::pow(0.01, -1.0 / N) - 1.0), cc = 2.0 * W / scaling;      // cfar.cpp:12-16, filter.hip cfar_build_lut
+  const double N = 2.0 * W, scaling = N * (std::pow(0.01, -1.0 / N) - 1.0), cc = 2.0 * W / scaling;      // cfar.cpp:12-16, cacfar.hip cfar_build_lut
   for (int i = 0; i < 256; i++) {
     a.lut[i] = 0;
     if (i < THR) continue;
