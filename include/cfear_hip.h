@@ -1384,6 +1384,113 @@ int cfear_closure_candidates_batch(cfear_ctx* ctx, const double* positions, cons
                                    const int64_t* node_offsets, int64_t n_nodes, int32_t n_graphs, const cfear_closure_params* par,
                                    cfear_closure_candidate* out, int32_t* failed_graph);
 
+/* ---- after the path: scoring the loop detector (loop rows, ROC and precision-recall curves) ---------------------------
+ * cfear_loop_stats_batch restates, for a batch of graphs and all their candidates in one launch (csrc/loopeval.hip),
+ *   PoseGraph::UpdateStatistics (tbv_slam/src/tbv_slam/posegraph.cpp:332-371): the ground-truth-labelled row of a candidate,
+ *   EvaluationManager::getCandidateLoopStatus (place_recognition_radar/src/place_recognition_radar/EvaluationManager.cpp:12-27).
+ * Poses are planar (x, y, theta).  Per candidate, in fp64, whatever has_gt says (the reference computes Terror before it
+ * asks has_Tgt_), with (c, s) the cosine and sine of an angle and d = p_to - p_from:
+ *     Tgt_diff = Tfrom^-1 Tto:   cgd = cf ct + sf st,  sgd = cf st - sf ct,  xgd = cf dx + sf dy,  ygd = cf dy - sf dx
+ *     diff = Tguess^-1 Tgt_diff: cd = cg cgd + sg sgd, sd = cg sgd - sg cgd,  ex = xgd - xg,  ey = ygd - yg,
+ *                                diff.x = cg ex + sg ey,  diff.y = cg ey - sg ex,  diff.z = atan2(sd, cd)
+ * diff.z is what Eigen's rotation().eulerAngles(0, 1, 2)[2] returns for a rotation about z: there the first two angles are
+ * atan2(0, 1) = 0 and the third is atan2(R10, R00), the matrix entries themselves.
+ * Only when has_gt[from]: candidate_loop_distance = sqrt((dx dx + dy dy) + 0.0) if has_gt[to] (else -1), and the search over
+ * the nodes k < from of the same graph with from - k > min_index_gap and has_gt[k] for the smallest
+ * d = sqrt((dx dx + dy dy) + 0.0); the strict `<` keeps the lowest k among equal distances.  It starts from
+ * no_loop_distance with id_close = from and close_xy = p_from, which is also what a `from` without ground truth reports.
+ * Flags: is_loop = closest_loop_distance < max_distance; transl_error = sqrt(diff.x^2 + diff.y^2);
+ * rot_error = (180 / pi) |diff.z|; candidate_close = transl_error < max_registration_translation and rot_error <
+ * max_registration_rotation_deg; prediction_pos_ok = !is_loop or candidate_close.                                       */
+typedef struct cfear_loop_stats_params {
+  double max_distance;                  /* 6     (EvaluationManager.cpp:14)                                            */
+  double max_registration_translation;  /* 4     (:15)                                                                 */
+  double max_registration_rotation_deg; /* 2.5   (:16)                                                                 */
+  double no_loop_distance;              /* 100000 (posegraph.cpp:334)                                                  */
+  int32_t min_index_gap;                /* 10    (posegraph.cpp:358)                                                   */
+  int32_t pad;
+} cfear_loop_stats_params;              /* 40 bytes */
+void cfear_loop_stats_params_default(cfear_loop_stats_params* p);
+typedef struct cfear_loop_candidate {
+  int32_t graph;                        /* index into node_offsets                                                     */
+  int32_t from, to;                     /* node indices within the graph                                               */
+  int32_t guess_nr;                     /* >= 0                                                                        */
+  double guess_xyt[3];                  /* Tguess: the candidate's estimate of Tfrom^-1 Tto                            */
+} cfear_loop_candidate;                 /* 40 bytes */
+typedef struct cfear_loop_row {
+  double diff[3];                       /* Terror (x, y, theta): loop.csv's diff.x, diff.y, diff.z                     */
+  double closest_loop_distance, candidate_loop_distance;
+  double transl_error, rot_error;       /* getCandidateLoopStatus's two errors (metres, degrees)                       */
+  double close_xy[2];                   /* position of node id_close                                                   */
+  int32_t id_close;                     /* within the graph; = from when nothing was found                             */
+  int32_t is_loop, candidate_close, prediction_pos_ok;
+} cfear_loop_row;                       /* 88 bytes */
+/* Graph g owns nodes [node_offsets[g], node_offsets[g + 1]) of gt_xyt [n_nodes][3] and has_gt [n_nodes]; node_offsets
+ * (host, n_graphs + 1 entries) starts at 0 and ends at n_nodes.  gt_xyt, has_gt, candidates [n_cand] and rows [n_cand] are
+ * all host or all device memory.  One wavefront serves a candidate; a row is bit-identical wherever its graph and its
+ * candidate sit in the batch and whichever memory the buffers were.  A graph of 0 nodes is legal, n_cand = 0 is OK.  The
+ * whole call is refused with CFEAR_ERR_INVALID_ARGUMENT before anything is written, cfear_last_error naming the culprit and
+ * *failed_candidate (optional, -1 otherwise) its index: a candidate whose graph, from or to does not exist, whose guess
+ * or whose from / to pose is not finite, or whose guess_nr is negative.  Also refused, with *failed_candidate = -1: offsets
+ * that do not run from 0 to n_nodes without descending, a node with has_gt whose pose is not finite, a parameter that is
+ * NaN, min_index_gap < 0, null pointers, host and device buffers mixed.  For host buffers every check is made before a
+ * context is needed; device buffers are checked by a kernel of their own, before the rows are computed.                 */
+int cfear_loop_stats_batch(cfear_ctx* ctx, const int64_t* node_offsets, const double* gt_xyt, const uint8_t* has_gt, int64_t n_nodes,
+                           int32_t n_graphs, const cfear_loop_candidate* candidates, int64_t n_cand, const cfear_loop_stats_params* par,
+                           cfear_loop_row* rows, int64_t* failed_candidate);
+
+/* cfear_loop_curves_batch: what place_recognition_radar/python/LoopClosureEval.py and evaluation/3_loop_closure/
+ * 3_loop_closure.py ask of sklearn for a table of (label, score) rows -- metrics.roc_curve, metrics.auc,
+ * precision_recall_curve, and ComputeClassifierStatistics at a probability threshold -- for a batch of experiments in one
+ * call, one workgroup each.  Per experiment, with integer counts until the final divisions:
+ *   sort by score, descending (-0.0 reads as 0.0); idx = the last position of every run of equal scores;
+ *   tps = cumsum(y)[idx], fps = 1 + idx - tps, thr = score[idx]              (n_thresholds entries)
+ *   ROC: with more than two thresholds and drop_intermediate, keep the first, the last and every i whose second difference
+ *        of fps or of tps is not 0; prepend (0, 0, +inf); fpr = fps / fps[last], tpr = tps / tps[last]     (n_roc entries)
+ *   PR:  precision = tps / (tps + fps) (0 where that is 0 / 0), recall = tps / tps[last], both reversed, then 1 and 0
+ *        appended (n_pr = n_thresholds + 1 entries); pr_thr = thr reversed (n_pr - 1 entries)
+ *   reference_endpoints: tpr[last] = tpr[last - 1], recall[0] = recall[1], precision[0] = precision[1], as 3_loop_closure.py:
+ *        157,164-165 does before it integrates and plots
+ *   auc = sum_i (fpr[i + 1] - fpr[i]) (tpr[i + 1] + tpr[i]) / 2 over the arrays as returned, in a fixed order
+ *   at the threshold: pred = score >= p_threshold; a label is read as 0 where y = 1, pred = 1 and pos_ok = 0
+ *        (CorrectLabelForPosition, on a copy: the curves use y as given); confusion = {tn, fp, fn, tp}, accuracy,
+ *        precision = tp / (tp + fp), recall = tp / (tp + fn), 0 where a denominator is 0.
+ * An order-preserving 64-bit key is made of every score and sorted with the row's label beside it (the non-NaN doubles
+ * need more than 63 bits, so the label cannot ride inside the key).  Experiments of up to CFEAR_LOOPEVAL_LDS_ROWS rows are
+ * sorted in LDS (profile row "loop_curves_lds"); larger ones in global memory by the same workgroup, chunks of
+ * CFEAR_LOOPEVAL_LDS_ROWS sorted and merged through LDS (profile row "loop_curves_global").                              */
+#define CFEAR_LOOPEVAL_LDS_ROWS 16384
+typedef struct cfear_loop_curves_params {
+  double p_threshold;                   /* 0.9 (LoopClosureEval.py --p-threshold)                                      */
+  int32_t drop_intermediate;            /* 1: roc_curve's default                                                      */
+  int32_t reference_endpoints;          /* 1: the curves as the reference's scripts plot them; 0: as sklearn returns them */
+} cfear_loop_curves_params;             /* 16 bytes */
+void cfear_loop_curves_params_default(cfear_loop_curves_params* p);
+typedef struct cfear_loop_curves_result {
+  double auc;
+  double accuracy, precision, recall;   /* at p_threshold, of the position-corrected labels                            */
+  int64_t n_pos, n_neg;                 /* rows with y = 1 / y = 0                                                     */
+  int64_t confusion[4];                 /* tn, fp, fn, tp at p_threshold                                               */
+  int32_t n_thresholds, n_roc, n_pr;    /* distinct scores; entries of the roc_* arrays; of pr_precision and pr_recall */
+  int32_t status;                       /* CFEAR_OK or CFEAR_ERR_INVALID_ARGUMENT                                      */
+} cfear_loop_curves_result;             /* 96 bytes */
+/* Experiment e owns rows [row_offsets[e], row_offsets[e + 1]) of y [n_rows] (0 or 1), score [n_rows] and pos_ok [n_rows]
+ * (optional: NULL reads as all 1); row_offsets (host, n_exp + 1 entries) runs from 0 to n_rows.  y, score, pos_ok and the six
+ * curve arrays are all host or all device memory.  Each curve array holds n_rows + n_exp doubles and experiment e's
+ * entries start at row_offsets[e] + e: n_roc of roc_fpr, roc_tpr and roc_thr, n_pr of pr_precision and pr_recall, n_pr - 1
+ * of pr_thr; entries beyond those are not written.  results [n_exp] is host memory; the call returns when it is written.
+ * An experiment's own trouble is its status and leaves the others alone: CFEAR_ERR_INVALID_ARGUMENT for no rows, one class
+ * only (sklearn yields NaN), a label other than 0 or 1, or a NaN score; its counts are then 0 and none of its curve
+ * entries is written.  An experiment's arrays and record are bit-identical wherever it sits in the batch and whichever
+ * memory the buffers were.  The whole call is refused with CFEAR_ERR_INVALID_ARGUMENT before anything is written
+ * (*failed_experiment, optional, names the experiment, -1 otherwise) for offsets that do not run from 0 to n_rows without
+ * descending, an experiment of more than 2^30 rows (CFEAR_ERR_CAPACITY), a NaN p_threshold, null pointers, host and
+ * device buffers mixed; n_exp = 0 is OK.                                                                                */
+int cfear_loop_curves_batch(cfear_ctx* ctx, const int64_t* row_offsets, const uint8_t* y, const double* score, const uint8_t* pos_ok,
+                            int64_t n_rows, int32_t n_exp, const cfear_loop_curves_params* par, double* roc_fpr, double* roc_tpr,
+                            double* roc_thr, double* pr_precision, double* pr_recall, double* pr_thr,
+                            cfear_loop_curves_result* results, int32_t* failed_experiment);
+
 #ifdef __cplusplus
 }
 #endif

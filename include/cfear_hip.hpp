@@ -1556,3 +1556,82 @@ inline std::vector<cfear_pgo_summary> SolvePoseGraphs(CFEAR_Radarodometry::Conte
     std::copy(poses.begin() + node_off[g], poses.begin() + node_off[g + 1], graphs[g].poses.begin());
   return out;
 }
+
+// Scoring the loop detector.  LoopStats (cfear_loop_stats_batch): PoseGraph::UpdateStatistics (posegraph.cpp:332-371) and
+// EvaluationManager::getCandidateLoopStatus for every candidate of a batch of graphs in ONE device call; a graph is its
+// planar ground-truth poses and one has_Tgt_ flag per node.  LoopCurves (cfear_loop_curves_batch): sklearn's roc_curve, auc
+// and precision_recall_curve and the statistics at p_threshold for a batch of experiments, as LoopClosureEval.py and
+// 3_loop_closure.py ask for them.  par == nullptr: the reference's constants.
+struct LoopGraph {
+  std::vector<CFEAR_Radarodometry::Pose2d> gt;       // Tgt of every node
+  std::vector<uint8_t> has_gt;                       // has_Tgt_; empty: every node has ground truth
+};
+inline std::vector<cfear_loop_row> LoopStats(CFEAR_Radarodometry::Context& ctx, const std::vector<LoopGraph>& graphs,
+                                             const std::vector<cfear_loop_candidate>& candidates,
+                                             const cfear_loop_stats_params* par = nullptr, int64_t* failed_candidate = nullptr) {
+  cfear_loop_stats_params def;
+  if (!par) { cfear_loop_stats_params_default(&def); par = &def; }
+  std::vector<int64_t> off(1, 0);
+  std::vector<double> gt;
+  std::vector<uint8_t> has;
+  for (const LoopGraph& g : graphs) {
+    if (!g.has_gt.empty() && g.has_gt.size() != g.gt.size()) throw CFEAR_Radarodometry::CfearError(CFEAR_ERR_INVALID_ARGUMENT, "one has_gt flag per pose");
+    for (size_t k = 0; k < g.gt.size(); k++) {
+      gt.push_back(g.gt[k].x); gt.push_back(g.gt[k].y); gt.push_back(g.gt[k].theta);
+      has.push_back(g.has_gt.empty() ? 1 : g.has_gt[k]);
+    }
+    off.push_back((int64_t)has.size());
+  }
+  std::vector<cfear_loop_row> rows(candidates.size());
+  ctx.check(cfear_loop_stats_batch(ctx.get(), off.data(), gt.data(), has.data(), (int64_t)has.size(), (int32_t)graphs.size(), candidates.data(),
+                                   (int64_t)candidates.size(), par, rows.data(), failed_candidate));
+  return rows;
+}
+
+struct LoopExperiment {
+  std::vector<uint8_t> y;                            // 0 or 1
+  std::vector<double> score;
+  std::vector<uint8_t> pos_ok;                       // empty (in every experiment of a call): all 1
+};
+struct LoopCurve {
+  std::vector<double> roc_fpr, roc_tpr, roc_thr, pr_precision, pr_recall, pr_thr;
+  cfear_loop_curves_result record;                   // record.status: the experiment's own (CFEAR_ERR_INVALID_ARGUMENT: empty arrays)
+};
+inline std::vector<LoopCurve> LoopCurves(CFEAR_Radarodometry::Context& ctx, const std::vector<LoopExperiment>& experiments,
+                                         const cfear_loop_curves_params* par = nullptr) {
+  cfear_loop_curves_params def;
+  if (!par) { cfear_loop_curves_params_default(&def); par = &def; }
+  std::vector<int64_t> off(1, 0);
+  std::vector<uint8_t> y, ok;
+  std::vector<double> score;
+  for (const LoopExperiment& e : experiments) {
+    if (e.y.size() != e.score.size() || (!e.pos_ok.empty() && e.pos_ok.size() != e.y.size()) || (e.pos_ok.empty() && !ok.empty() && !e.y.empty()))
+      throw CFEAR_Radarodometry::CfearError(CFEAR_ERR_INVALID_ARGUMENT, "y, score and pos_ok hold one entry per row; pos_ok in every experiment or in none");
+    y.insert(y.end(), e.y.begin(), e.y.end());
+    score.insert(score.end(), e.score.begin(), e.score.end());
+    ok.insert(ok.end(), e.pos_ok.begin(), e.pos_ok.end());
+    off.push_back((int64_t)y.size());
+  }
+  if (!ok.empty() && ok.size() != y.size())
+    throw CFEAR_Radarodometry::CfearError(CFEAR_ERR_INVALID_ARGUMENT, "pos_ok in every experiment or in none");
+  const size_t total = y.size() + experiments.size();
+  std::vector<double> a[6];
+  for (auto& v : a) v.assign(total, 0.0);
+  std::vector<cfear_loop_curves_result> rec(experiments.size());
+  ctx.check(cfear_loop_curves_batch(ctx.get(), off.data(), y.data(), score.data(), ok.empty() ? nullptr : ok.data(), (int64_t)y.size(),
+                                    (int32_t)experiments.size(), par, a[0].data(), a[1].data(), a[2].data(), a[3].data(), a[4].data(), a[5].data(),
+                                    rec.data(), nullptr));
+  std::vector<LoopCurve> out(experiments.size());
+  for (size_t e = 0; e < experiments.size(); e++) {
+    const size_t o = (size_t)off[e] + e, n_roc = (size_t)rec[e].n_roc, n_pr = (size_t)rec[e].n_pr;
+    LoopCurve& c = out[e];
+    c.record = rec[e];
+    c.roc_fpr.assign(a[0].begin() + o, a[0].begin() + o + n_roc);
+    c.roc_tpr.assign(a[1].begin() + o, a[1].begin() + o + n_roc);
+    c.roc_thr.assign(a[2].begin() + o, a[2].begin() + o + n_roc);
+    c.pr_precision.assign(a[3].begin() + o, a[3].begin() + o + n_pr);
+    c.pr_recall.assign(a[4].begin() + o, a[4].begin() + o + n_pr);
+    c.pr_thr.assign(a[5].begin() + o, a[5].begin() + o + (n_pr ? n_pr - 1 : 0));
+  }
+  return out;
+}

@@ -294,6 +294,7 @@ EXPORTS = [
     "cfear_cart_params_default", "cfear_polar_to_cartesian", "cfear_cart_quality_batch",
     "cfear_cacfar_plan", "cfear_filter_cacfar_rowkeys", "cfear_kstrong_plan",
     "cfear_closure_params_default", "cfear_closure_candidates_batch",
+    "cfear_loop_stats_params_default", "cfear_loop_stats_batch", "cfear_loop_curves_params_default", "cfear_loop_curves_batch",
 ]
 
 PIPE_GRAPH, PIPE_TIMING = 1, 2      # enum { CFEAR_PIPE_GRAPH, CFEAR_PIPE_TIMING }
@@ -407,6 +408,29 @@ class ClosureCandidate(C.Structure):    # cfear_closure_candidate
 CLOSURE_CANDIDATE_DTYPE = np.dtype([("to", "<i4"), ("exhausted", "<i4"), ("eucl", "<f8"), ("trav", "<f8"), ("rel", "<f8"),
                                     ("odom_bounds", "<f8")])
 assert C.sizeof(ClosureParams) == 40 and C.sizeof(ClosureCandidate) == 40 == CLOSURE_CANDIDATE_DTYPE.itemsize
+
+LOOPEVAL_LDS_ROWS = 16384                         # CFEAR_LOOPEVAL_LDS_ROWS
+
+
+class LoopStatsParams(C.Structure):     # cfear_loop_stats_params
+    _fields_ = [("max_distance", C.c_double), ("max_registration_translation", C.c_double),
+                ("max_registration_rotation_deg", C.c_double), ("no_loop_distance", C.c_double), ("min_index_gap", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+class LoopCurvesParams(C.Structure):    # cfear_loop_curves_params
+    _fields_ = [("p_threshold", C.c_double), ("drop_intermediate", C.c_int32), ("reference_endpoints", C.c_int32)]
+
+
+LOOP_CANDIDATE_DTYPE = np.dtype([("graph", "<i4"), ("from", "<i4"), ("to", "<i4"), ("guess_nr", "<i4"), ("guess_xyt", "<f8", (3,))])
+LOOP_ROW_DTYPE = np.dtype([("diff", "<f8", (3,)), ("closest_loop_distance", "<f8"), ("candidate_loop_distance", "<f8"),
+                           ("transl_error", "<f8"), ("rot_error", "<f8"), ("close_xy", "<f8", (2,)), ("id_close", "<i4"),
+                           ("is_loop", "<i4"), ("candidate_close", "<i4"), ("prediction_pos_ok", "<i4")])
+LOOP_CURVES_RESULT_DTYPE = np.dtype([("auc", "<f8"), ("accuracy", "<f8"), ("precision", "<f8"), ("recall", "<f8"), ("n_pos", "<i8"),
+                                     ("n_neg", "<i8"), ("confusion", "<i8", (4,)), ("n_thresholds", "<i4"), ("n_roc", "<i4"),
+                                     ("n_pr", "<i4"), ("status", "<i4")])
+assert C.sizeof(LoopStatsParams) == 40 and C.sizeof(LoopCurvesParams) == 16
+assert LOOP_CANDIDATE_DTYPE.itemsize == 40 and LOOP_ROW_DTYPE.itemsize == 88 and LOOP_CURVES_RESULT_DTYPE.itemsize == 96
 
 _LIB = None
 
@@ -586,5 +610,13 @@ def lib():
     L.cfear_closure_params_default.restype = None
     L.cfear_closure_candidates_batch.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int32, C.POINTER(ClosureParams), vp,
                                                  C.POINTER(C.c_int32)]
+    L.cfear_loop_stats_params_default.argtypes = [C.POINTER(LoopStatsParams)]
+    L.cfear_loop_stats_params_default.restype = None
+    L.cfear_loop_stats_batch.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int32, vp, C.c_int64, C.POINTER(LoopStatsParams), vp,
+                                         C.POINTER(C.c_int64)]
+    L.cfear_loop_curves_params_default.argtypes = [C.POINTER(LoopCurvesParams)]
+    L.cfear_loop_curves_params_default.restype = None
+    L.cfear_loop_curves_batch.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int32, C.POINTER(LoopCurvesParams), vp, vp, vp, vp, vp, vp,
+                                          vp, C.POINTER(C.c_int32)]
     _LIB = L
     return L

@@ -2956,3 +2956,411 @@ class KittiEvalOdom:
                                   zip(r["first_frame"], r["r_err"], r["t_err"], r["length"], r["speed"]))
                 f.writelines(eval_result_lines(i, summaries[k]))
         return summaries, rows
+
+
+# ------------------------------------------------------------------------------------------------
+# scoring the loop detector: loop rows (PoseGraph::UpdateStatistics), loop.csv (EvaluationManager), ROC / PR curves
+# (place_recognition_radar/python/LoopClosureEval.py, evaluation/3_loop_closure/3_loop_closure.py)
+# ------------------------------------------------------------------------------------------------
+def _struct_params(cls, default, kw, what):
+    p = cls()
+    default(C.byref(p))
+    for k, v in kw.items():
+        if k == "pad" or not hasattr(p, k):
+            raise L.CfearError(L.ERR_INVALID_ARGUMENT, "unknown %s field %r" % (what, k))
+        setattr(p, k, type(getattr(p, k))(v))
+    return p
+
+
+def loop_stats_params(**kw):
+    """cfear_loop_stats_params with the reference's constants: max_distance 6, max_registration_translation 4,
+    max_registration_rotation_deg 2.5 (EvaluationManager.cpp:14-16), no_loop_distance 100000, min_index_gap 10
+    (posegraph.cpp:334,358)."""
+    return _struct_params(L.LoopStatsParams, L.lib().cfear_loop_stats_params_default, kw, "cfear_loop_stats_params")
+
+
+def loop_curves_params(**kw):
+    """cfear_loop_curves_params: p_threshold 0.9, drop_intermediate 1, reference_endpoints 1."""
+    return _struct_params(L.LoopCurvesParams, L.lib().cfear_loop_curves_params_default, kw, "cfear_loop_curves_params")
+
+
+def _device_bytes(n, like):
+    import torch
+    return torch.zeros(n, dtype=torch.uint8, device=like.device)
+
+
+def loop_stats_flat(node_offsets, gt_xyt, has_gt, candidates, ctx=None, **params):
+    """cfear_loop_stats_batch on the flat arrays: node_offsets int64 [n_graphs + 1] (host), gt_xyt float64 [n_nodes, 3],
+    has_gt uint8 [n_nodes] and candidates (LOOP_CANDIDATE_DTYPE records) all NumPy, or all torch CUDA tensors (the candidates
+    then as their bytes, uint8 [n_cand * 40]).  Returns LOOP_ROW_DTYPE records: a NumPy array, or for device buffers a uint8
+    tensor of their bytes.  A refusal raises CfearError with .candidate = the candidate it names (-1: none)."""
+    par = loop_stats_params(**params)
+    off = np.ascontiguousarray(node_offsets, np.int64)
+    device = _is_torch(gt_xyt) or _is_torch(candidates)
+    ctx = ctx or default_context()
+    if device:
+        n_cand = candidates.numel() // L.LOOP_CANDIDATE_DTYPE.itemsize
+        rows = _device_bytes(n_cand * L.LOOP_ROW_DTYPE.itemsize, candidates)
+        _torch_ready(ctx, gt_xyt, has_gt, candidates, rows)
+    else:
+        gt_xyt = np.ascontiguousarray(gt_xyt, np.float64).reshape(-1, 3)
+        has_gt = np.ascontiguousarray(has_gt, np.uint8)
+        candidates = np.ascontiguousarray(candidates, L.LOOP_CANDIDATE_DTYPE)
+        n_cand = candidates.shape[0]
+        rows = np.zeros(n_cand, L.LOOP_ROW_DTYPE)
+    n_nodes = int(has_gt.shape[0])
+    bad = C.c_int64(-1)
+    rc = ctx._lib.cfear_loop_stats_batch(ctx.h, off.ctypes.data, _ptr(gt_xyt)[0], _ptr(has_gt)[0], n_nodes, len(off) - 1,
+                                         _ptr(candidates)[0], n_cand, C.byref(par), _ptr(rows)[0], C.byref(bad))
+    if rc != L.OK:
+        err = L.CfearError(rc, ctx._lib.cfear_last_error(ctx.h).decode())
+        err.candidate = int(bad.value)
+        raise err
+    return rows
+
+
+def loop_candidates(cands):
+    """LOOP_CANDIDATE_DTYPE records from such an array, or from dicts / tuples of (graph, from, to, guess_nr, guess_xyt)."""
+    if isinstance(cands, np.ndarray) and cands.dtype == L.LOOP_CANDIDATE_DTYPE:
+        return np.ascontiguousarray(cands)
+    out = np.zeros(len(cands), L.LOOP_CANDIDATE_DTYPE)
+    for i, c in enumerate(cands):
+        if not isinstance(c, dict):
+            c = dict(zip(("graph", "from", "to", "guess_nr", "guess_xyt"), c))
+        out[i] = (int(c.get("graph", 0)), int(c["from"]), int(c["to"]), int(c.get("guess_nr", 0)),
+                  np.asarray(c.get("guess_xyt", (0.0, 0.0, 0.0)), np.float64).reshape(3))
+    return out
+
+
+def loop_stats(graphs, candidates, ctx=None, **params):
+    """cfear_loop_stats_batch: PoseGraph::UpdateStatistics (posegraph.cpp:332-371) and EvaluationManager::
+    getCandidateLoopStatus for every candidate of a batch of graphs in one device call.  graphs: a list of gt_xyt [n, 3]
+    planar ground-truth poses, or of (gt_xyt, has_gt [n]); candidates: loop_candidates() input, `graph` indexing `graphs`.
+    Keyword overrides: loop_stats_params().  Returns LOOP_ROW_DTYPE records in candidate order: diff (loop.csv's diff.x,
+    diff.y, diff.z), closest_loop_distance, candidate_loop_distance, transl_error, rot_error, close_xy, id_close, is_loop,
+    candidate_close, prediction_pos_ok."""
+    gts, has = [], []
+    for k, g in enumerate(graphs):
+        gt, h = g if isinstance(g, tuple) else (g, None)
+        gt = np.asarray(gt, np.float64).reshape(-1, 3)
+        h = np.ones(gt.shape[0], np.uint8) if h is None else np.asarray(h).astype(np.uint8).reshape(-1)
+        if h.shape[0] != gt.shape[0]:
+            raise L.CfearError(L.ERR_INVALID_ARGUMENT, "graph %d: %d has_gt flags for %d poses" % (k, h.shape[0], gt.shape[0]))
+        gts.append(gt)
+        has.append(h)
+    off = np.concatenate([[0], np.cumsum([g.shape[0] for g in gts])]).astype(np.int64)
+    gt = np.concatenate(gts, 0) if gts else np.zeros((0, 3))
+    h = np.concatenate(has) if has else np.zeros(0, np.uint8)
+    return loop_stats_flat(off, gt, h, loop_candidates(candidates), ctx, **params)
+
+
+LOOP_CURVE_ARRAYS = ("roc_fpr", "roc_tpr", "roc_thr", "pr_precision", "pr_recall", "pr_thr")
+
+
+def loop_curves_flat(row_offsets, y, score, pos_ok=None, ctx=None, **params):
+    """cfear_loop_curves_batch on the flat arrays: row_offsets int64 [n_exp + 1] (host); y uint8, score float64 and the
+    optional pos_ok uint8, [n_rows] each, all NumPy or all torch CUDA tensors.  Returns (arrays, records): the six curve
+    arrays of n_rows + n_exp entries (NaN where the call wrote nothing) keyed by LOOP_CURVE_ARRAYS, of the inputs' kind, and
+    the LOOP_CURVES_RESULT_DTYPE records (NumPy).  A refusal raises CfearError with .experiment."""
+    par = loop_curves_params(**params)
+    off = np.ascontiguousarray(row_offsets, np.int64)
+    n_exp = len(off) - 1
+    ctx = ctx or default_context()
+    if _is_torch(score):
+        import torch
+        n_rows = int(score.shape[0])
+        arrays = {k: torch.full((n_rows + n_exp,), float("nan"), dtype=torch.float64, device=score.device) for k in LOOP_CURVE_ARRAYS}
+        _torch_ready(ctx, y, score, pos_ok, *arrays.values())
+    else:
+        y = np.ascontiguousarray(y, np.uint8)
+        score = np.ascontiguousarray(score, np.float64)
+        pos_ok = None if pos_ok is None else np.ascontiguousarray(pos_ok, np.uint8)
+        n_rows = int(score.shape[0])
+        arrays = {k: np.full(n_rows + n_exp, np.nan) for k in LOOP_CURVE_ARRAYS}
+    if int(y.shape[0]) != n_rows or (pos_ok is not None and int(pos_ok.shape[0]) != n_rows):
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "y, score and pos_ok must hold one entry per row")
+    rec = np.zeros(max(n_exp, 0), L.LOOP_CURVES_RESULT_DTYPE)
+    bad = C.c_int32(-1)
+    rc = ctx._lib.cfear_loop_curves_batch(ctx.h, off.ctypes.data, _ptr(y)[0], _ptr(score)[0], _ptr(pos_ok)[0], n_rows, n_exp,
+                                          C.byref(par), *[_ptr(arrays[k])[0] for k in LOOP_CURVE_ARRAYS], rec.ctypes.data, C.byref(bad))
+    if rc != L.OK:
+        err = L.CfearError(rc, ctx._lib.cfear_last_error(ctx.h).decode())
+        err.experiment = int(bad.value)
+        raise err
+    return arrays, rec
+
+
+def loop_curve_slices(arrays, rec, row_offsets):
+    """One dict per experiment of a loop_curves_flat() answer: the six arrays cut to their lengths, and `record`."""
+    out = []
+    for e, r in enumerate(rec):
+        o = int(row_offsets[e]) + e
+        lens = dict(roc_fpr=r["n_roc"], roc_tpr=r["n_roc"], roc_thr=r["n_roc"], pr_precision=r["n_pr"], pr_recall=r["n_pr"],
+                    pr_thr=max(int(r["n_pr"]) - 1, 0))
+        d = {k: arrays[k][o:o + int(lens[k])] for k in LOOP_CURVE_ARRAYS}
+        d["record"] = r
+        out.append(d)
+    return out
+
+
+def loop_curves(experiments, ctx=None, curves=None, **params):
+    """cfear_loop_curves_batch: sklearn's roc_curve, auc and precision_recall_curve, and the confusion matrix, accuracy,
+    precision and recall at p_threshold, for every experiment in one device call and without sklearn.  experiments: a list
+    of (y, score) or (y, score, pos_ok) -- pos_ok for all or for none.  Keyword overrides: loop_curves_params().  Returns a
+    dict per experiment: roc_fpr, roc_tpr, roc_thr, pr_precision, pr_recall, pr_thr and `record` (auc, accuracy,
+    precision, recall, n_pos, n_neg, confusion = tn, fp, fn, tp, n_thresholds, n_roc, n_pr, status).  An experiment with no
+    rows, one class only, a label other than 0 or 1 or a NaN score has status ERR_INVALID_ARGUMENT and empty arrays.
+    curves: a stand-in for loop_curves_flat with its signature (the tests' NumPy model)."""
+    if not experiments:
+        return []
+    with_ok = [len(e) > 2 and e[2] is not None for e in experiments]
+    if any(with_ok) and not all(with_ok):
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "pos_ok for every experiment or for none")
+    off = np.concatenate([[0], np.cumsum([len(e[1]) for e in experiments])]).astype(np.int64)
+    y = np.concatenate([np.asarray(e[0]).astype(np.uint8).reshape(-1) for e in experiments])
+    score = np.concatenate([np.asarray(e[1], np.float64).reshape(-1) for e in experiments])
+    ok = np.concatenate([np.asarray(e[2]).astype(np.uint8).reshape(-1) for e in experiments]) if all(with_ok) else None
+    if curves is None:
+        arrays, rec = loop_curves_flat(off, y, score, ok, ctx, **params)
+    else:
+        arrays, rec = curves(off, y, score, ok, **params)
+    return loop_curve_slices(arrays, rec, off)
+
+
+LOOP_CSV_HEADER = ("from.x,from.y,from.z,to.x,to.y,to.z,close.x,close.y,close.z,diff.x,diff.y,diff.z,closest_loop_distance,"
+                   "candidate_loop_distance,id_from,id_to,id_close,guess_nr").split(",")   # LoopCandidates::namesToString
+
+
+def loop_table(graphs, candidates, rows, quality, **columns):
+    """The columns of loop.csv for loop_stats() rows, as a dict of NumPy arrays in file order: the 18 of LOOP_CSV_HEADER,
+    then `quality` (name -> [n_cand] values) in the order of the reference's std::map (sorted by name), then `columns`
+    (the pars_str / vals_str pair of EvaluationManager::writeResultsToCSV: a scalar or an [n_cand] array each)."""
+    cands = loop_candidates(candidates)
+    gts = [np.asarray(g[0] if isinstance(g, tuple) else g, np.float64).reshape(-1, 3) for g in graphs]
+    n = len(cands)
+    pf = np.array([gts[c["graph"]][c["from"]] for c in cands]).reshape(n, 3)
+    pt = np.array([gts[c["graph"]][c["to"]] for c in cands]).reshape(n, 3)
+    zero = np.zeros(n)
+    t = {"from.x": pf[:, 0], "from.y": pf[:, 1], "from.z": zero, "to.x": pt[:, 0], "to.y": pt[:, 1], "to.z": zero,
+         "close.x": rows["close_xy"][:, 0], "close.y": rows["close_xy"][:, 1], "close.z": zero,
+         "diff.x": rows["diff"][:, 0], "diff.y": rows["diff"][:, 1], "diff.z": rows["diff"][:, 2],
+         "closest_loop_distance": rows["closest_loop_distance"], "candidate_loop_distance": rows["candidate_loop_distance"],
+         "id_from": cands["from"].astype(np.int64), "id_to": cands["to"].astype(np.int64),
+         "id_close": rows["id_close"].astype(np.int64), "guess_nr": cands["guess_nr"].astype(np.int64)}
+    for k in sorted(quality):
+        t[k] = np.asarray(quality[k], np.float64).reshape(n)
+    for k, v in columns.items():
+        t[k] = np.broadcast_to(np.asarray(v), (n,)).copy()
+    return t
+
+
+def write_loop_csv(path, table, quality_names=()):
+    """EvaluationManager::writeResultsToCSV (EvaluationManager.cpp:29-57): the header of LoopCandidates::namesToString and
+    one line per row of `table` (loop_table()).  The row's own floating-point values are written as "%.6g", which is what
+    the reference's setprecision(6) stream writes; the columns named in quality_names as "%.6f" (Join, cfear_radarodometry/
+    utils.h:64-83, is std::fixed); integers and strings as they are.  The reference's scripts therefore see ROUNDED rows:
+    labels computed from a file can differ from the flags of loop_stats() where an error lies within the rounding of a
+    limit."""
+    names = list(table)
+    with open(path, "w") as f:
+        f.write(",".join(names) + "\n")
+        cols = [np.asarray(table[k]) for k in names]
+        for i in range(len(cols[0]) if cols else 0):
+            vals = []
+            for k, c in zip(names, cols):
+                v = c[i]
+                if c.dtype.kind == "f":
+                    vals.append(("%.6f" if k in quality_names else "%.6g") % v)
+                else:
+                    vals.append(str(v))
+            f.write(",".join(vals) + "\n")
+
+
+def read_loop_csv(path):
+    """loop.csv -> a dict of NumPy arrays in file order (what pandas.read_csv(skipinitialspace=True) gives the reference's
+    scripts): int64 where every value of a column is an integer literal, float64 where every value is a number, else str."""
+    with open(path) as f:
+        lines = [ln.rstrip("\n") for ln in f if ln.strip()]
+    names = [s.strip() for s in lines[0].split(",")]
+    cells = [[s.strip() for s in ln.split(",")] for ln in lines[1:]]
+    table = {}
+    for j, k in enumerate(names):
+        col = [r[j] for r in cells]
+        for kind in (np.int64, np.float64):
+            try:
+                table[k] = np.array([kind(v) for v in col], kind)
+                break
+            except ValueError:
+                continue
+        else:
+            table[k] = np.array(col)
+    return table
+
+
+def write_loop_result(path, train, test, coef, intercept, p_threshold, nr_correct_candidates, nr_loops):
+    """WriteFile of place_recognition_radar/python/LoopClosureEval.py:26-52 (its lines :31-46).  train, test: records or
+    dicts with accuracy, precision and recall."""
+    ratio = nr_correct_candidates / nr_loops if nr_loops else float("nan")
+    lines = ["Training accuracy[%], {:.3f}\n".format(train["accuracy"] * 100),
+             "Training precision [%], {:.3f}\n".format(train["precision"] * 100),
+             "Training recall [%], {:.3f}\n".format(train["recall"] * 100),
+             "Testing accurac [%], {:.3f}\n".format(test["accuracy"] * 100),
+             "Testing precision [%], {:.3f}\n".format(test["precision"] * 100),
+             "Testing recall [%], {:.3f}\n".format(test["recall"] * 100),
+             "nr correct candidates, {}\n".format(nr_correct_candidates),
+             "nr loops, {}\n".format(nr_loops),
+             "correct_loop_ratio [%], {:.3f}\n".format(ratio * 100),
+             "Coef, {}\n".format(np.asarray(coef, np.float64).reshape(1, -1)),
+             "Intercept {}\n".format(np.asarray(intercept, np.float64).reshape(-1)),
+             "Threshold, {}\n".format(p_threshold)]
+    with open(path, "w") as f:
+        f.writelines(lines)
+    return lines
+
+
+class LoopClosureEval:
+    """evaluation/3_loop_closure/3_loop_closure.py's loop over the settings 1) - 8) of the paper's ablation, without pandas,
+    sklearn or matplotlib: labels, training rows, classifiers (logreg_fit_batch, all models of all settings in one call),
+    probabilities, best-guess selection and the curves of all settings in one loop_curves() call.
+    table: loop.csv's columns as a dict of arrays (loop_table() / read_loop_csv()); it needs diff.x, diff.y, diff.z,
+    closest_loop_distance, id_from, id_to, guess_nr, odom-bounds, sc-sim, alignment_quality.  The three columns that tell
+    the settings apart ("SC - odometry_coupled_closure", "Scan Context - raw_scan_context", "SC - augment_sc") default to
+    1, 0, 1 where the table lacks them.  The script's TrainClassifier leaves class weights alone, so class_weight_balanced
+    is 0 here.  The threshold statistics in a setting's record are those of its masked score y_prob at p_threshold, with
+    `candidate close` as pos_ok."""
+
+    NAMES = ("1) Radar Scan Context", "2) Aggregated point cloud map", "3) Origin augmentation", "4) Alignment loop verification",
+             "5) Odometry decoupled", "6) Odometry coupled", "7) Cascaded classifier", "8) Multiple candidate selection")
+    FEATURE_COLS_ALL = (["sc-sim"], ["odom-bounds", "sc-sim"], ["sc-sim", "alignment_quality"],
+                        ["odom-bounds", "sc-sim", "alignment_quality"])
+    COUPLED, RAW, AUGMENT = "SC - odometry_coupled_closure", "Scan Context - raw_scan_context", "SC - augment_sc"
+
+    def __init__(self, table, p_threshold=0.9, max_distance=6.0, max_registration_distance=4.0, max_registration_rotation=2.5,
+                 ctx=None):
+        n = len(table["guess_nr"])
+        t = {k: np.asarray(v) for k, v in table.items()}
+        for k, v in ((self.COUPLED, 1), (self.RAW, 0), (self.AUGMENT, 1)):
+            t.setdefault(k, np.full(n, v, np.int64))
+        dx, dy, dz = (np.asarray(t[k], np.float64) for k in ("diff.x", "diff.y", "diff.z"))
+        transl = np.sqrt(dx * dx + dy * dy)                                                     # 3_loop_closure.py:87-92
+        t["is loop"] = (np.asarray(t["closest_loop_distance"], np.float64) < max_distance).astype(np.int64)
+        t["candidate close"] = (transl < max_registration_distance) & (np.fabs(dz) < max_registration_rotation * math.pi / 180.0)
+        t["candidate transl_error"] = transl
+        t["candidate rot_error"] = 180.0 / math.pi * np.fabs(dz)
+        t["prediction pos ok"] = ((t["is loop"] == 0) | t["candidate close"]).astype(np.int64)
+        keep = np.asarray(t["guess_nr"]) >= 0                                                   # :93
+        self.table = {k: v[keep] for k, v in t.items()}
+        self.p_threshold = float(p_threshold)
+        self.ctx = ctx
+
+    @classmethod
+    def settings_name(cls, feature_cols=None, guess0=True, radar_raw=1, augment=0, odometry_coupled=1, cascaded=False):
+        """GetNameFromSettings (3_loop_closure.py:26-52): the setting's name, '' for a combination that is not one of the
+        eight; without arguments, the eight names."""
+        if feature_cols is None:
+            return list(cls.NAMES)
+        sc, al, full = ["sc-sim"], ["sc-sim", "alignment_quality"], ["odom-bounds", "sc-sim", "alignment_quality"]
+        known = {(tuple(sc), True, 0, 1, 0, False): 0, (tuple(sc), True, 0, 0, 0, False): 1, (tuple(sc), True, 0, 0, 1, False): 2,
+                 (tuple(al), True, 0, 0, 1, False): 3, (tuple(full), True, 0, 0, 1, False): 4, (tuple(full), True, 1, 0, 1, False): 5,
+                 (tuple(full), True, 1, 0, 1, True): 6, (tuple(full), False, 1, 0, 1, False): 7}
+        k = known.get((tuple(feature_cols), bool(guess0), int(odometry_coupled), int(radar_raw), int(augment), bool(cascaded)))
+        return "" if k is None else cls.NAMES[k]
+
+    def settings(self):
+        """The named combinations present in the table, in the script's product order (:96-111), each a dict with its name,
+        its settings, `rows` (the table rows of the combination) and `train` (those of guess 0 with `prediction pos ok` and
+        id_from != id_to, :115-118)."""
+        t = self.table
+        uniq = lambda k: list(dict.fromkeys(np.asarray(t[k]).tolist()))
+        out = []
+        for guess0 in (True, False):
+            for raw in uniq(self.RAW):
+                for coupled in uniq(self.COUPLED):
+                    for augment in uniq(self.AUGMENT):
+                        for cols in self.FEATURE_COLS_ALL:
+                            for cascaded in (True, False):
+                                name = self.settings_name(cols, guess0, raw, augment, coupled, cascaded)
+                                if not name:
+                                    continue
+                                rows = np.flatnonzero((t[self.COUPLED] == coupled) & (t[self.RAW] == raw) & (t[self.AUGMENT] == augment))
+                                g0 = rows[t["guess_nr"][rows] == 0]
+                                train = g0[(t["prediction pos ok"][g0] == 1) & (t["id_from"][g0] != t["id_to"][g0])]
+                                out.append(dict(name=name, feature_cols=list(cols), guess0=guess0, cascaded=cascaded, rows=rows,
+                                                guess0_rows=g0, train=train))
+        return out
+
+    def _features(self, cols):
+        """The columns `cols` as one [rows, len(cols)] array; the same object for the same columns, so that the models
+        that read it share one upload."""
+        cache = self.__dict__.setdefault("_feature_cache", {})
+        if tuple(cols) not in cache:
+            cache[tuple(cols)] = np.ascontiguousarray(np.stack([np.asarray(self.table[c], np.float64) for c in cols], 1))
+        return cache[tuple(cols)]
+
+    def model_jobs(self, settings):
+        """The logreg_fit_batch jobs of `settings` -> (jobs, where): where[i] = (setting index, "single" | "sc" | "align")."""
+        y = np.asarray(self.table["is loop"], np.float64)
+        jobs, where = [], []
+        n = len(y)
+        for s, st in enumerate(settings):
+            mask = np.zeros(n, np.uint8)
+            mask[st["train"]] = 1
+            models = [("sc", ["odom-bounds", "sc-sim"]), ("align", ["alignment_quality"])] if st["cascaded"] else [("single", st["feature_cols"])]
+            for kind, cols in models:
+                jobs.append(dict(X=self._features(cols), y=y, row_mask=mask))
+                where.append((s, kind))
+        return jobs, where
+
+    @staticmethod
+    def _linear(X, m):
+        return X @ np.asarray(m["coef"][:X.shape[1]], np.float64) + float(m["intercept"])
+
+    def scores(self, settings, models, where):
+        """(y, y_prob, pos_ok, rows) per setting from the fitted records: probabilities 1 / (1 + exp(-z)); for setting 8 the
+        row of the highest probability among the nr_guess rows of every query, the first maximum winning (:133-141); for
+        setting 7 the first classifier's predict() (z > 0) times the second's probability (:151-154); y_prob = probability x
+        `prediction pos ok`."""
+        t = self.table
+        by = {w: m for w, m in zip(where, models)}
+        out = []
+        for s, st in enumerate(settings):
+            sel = st["guess0_rows"]
+            if not st["guess0"]:
+                m = by[(s, "single")]
+                rows = st["rows"]
+                nr_guess = int(np.asarray(t["guess_nr"])[rows].max()) + 1
+                p_all = 1.0 / (1.0 + np.exp(-self._linear(self._features(st["feature_cols"])[rows], m)))
+                M = p_all.reshape(-1, nr_guess)
+                sel = rows[np.arange(0, rows.shape[0], nr_guess) + np.argmax(M, axis=1)]
+            if st["cascaded"]:
+                z_sc = self._linear(self._features(["odom-bounds", "sc-sim"])[sel], by[(s, "sc")])
+                z_al = self._linear(self._features(["alignment_quality"])[sel], by[(s, "align")])
+                proba = (z_sc > 0.0).astype(np.float64) * (1.0 / (1.0 + np.exp(-z_al)))
+            else:
+                proba = 1.0 / (1.0 + np.exp(-self._linear(self._features(st["feature_cols"])[sel], by[(s, "single")])))
+            y_prob = proba * t["prediction pos ok"][sel]
+            out.append((t["is loop"][sel].astype(np.uint8), y_prob, np.asarray(t["candidate close"][sel]).astype(np.uint8), sel))
+        return out
+
+    def evaluate(self, models=None, curves=None, **curve_params):
+        """All settings: one logreg_fit_batch call (unless `models`, the records of an earlier call, are given), then one
+        loop_curves call.  Returns a list of dicts: name, models (the setting's fitted records), rows, y, y_prob, and the
+        loop_curves() entries.  A setting whose training rows hold one class only raises ValueError, as sklearn does in the
+        script."""
+        settings = self.settings()
+        jobs, where = self.model_jobs(settings)
+        if models is None:
+            models = logreg_fit_batch(jobs, self.ctx, class_weight_balanced=0) if jobs else np.zeros(0, L.LOGREG_RESULT_DTYPE)
+        for (s, kind), m in zip(where, models):
+            if m["status"] != L.OK:
+                raise ValueError("%s: the %s classifier could not be fitted (status %d)" % (settings[s]["name"], kind, m["status"]))
+        sc = self.scores(settings, models, where)
+        curve_params.setdefault("p_threshold", self.p_threshold)
+        cv = loop_curves([(y, p, ok) for y, p, ok, _ in sc], self.ctx, curves, **curve_params)
+        out = []
+        for s, st in enumerate(settings):
+            d = dict(cv[s], name=st["name"], rows=sc[s][3], y=sc[s][0], y_prob=sc[s][1],
+                     models=[m for (k, _), m in zip(where, models) if k == s])
+            out.append(d)
+        self.models_ = models
+        return out

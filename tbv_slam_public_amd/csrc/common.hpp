@@ -84,6 +84,7 @@ enum WsSlot : int {
   kWsCart = 21,           // Cartesian image / CorAlCart quality: staged images, job records, partial sums, staged outputs
   kWsCartMap = 22,        // the fixed-point polar -> Cartesian map of the last geometry (cfear_ctx::cart_map_*)
   kWsClosure = 23,        // vicinity closure: staged positions, steps and motions, the block table, staged candidates
+  kWsLoopEval = 24,       // loop rows and curves: staged graphs, candidates, scores and curves, job table, sort and scan scratch
 };
 
 struct cfear_ctx {
@@ -96,7 +97,7 @@ struct cfear_ctx {
   std::vector<Event> event_pool;
   // grow-only device workspaces (indexed by WsSlot so stages of one pipeline do not alias)
   struct Ws { DevBuf<void> p; size_t bytes = 0; };
-  Ws ws[24];
+  Ws ws[25];
   // pinned host staging for small read-backs
   PinnedBuf<char> pinned;
   size_t pinned_bytes = 0;
