@@ -605,9 +605,11 @@ typedef struct cfear_coral_result {
 /* Limits.  The kernel sorts the merged cloud into a uniform grid of radius * 1.0001 cells over its bounding box, rows
  * along y.  radius must be > 0 (not NaN), else CFEAR_ERR_INVALID_ARGUMENT.  CFEAR_ERR_CAPACITY:
  *   - n_ref + n_src > 16384 in any job: the call returns at entry, nothing is launched, no record is written;
- *   - per job, as results[j].status: more than 4096 grid rows (y extent / radius), more than 2^31 - 1 grid cells, or a
- *     NaN coordinate.  The limits are not symmetric: two clusters 4200 radii apart along y are refused, along x they
- *     are served; radius 0.05 over a 300 m scan is refused.
+ *   - per job, as results[j].status: more than 4096 grid rows (y extent / radius), more than 2^31 - 1 grid cells.
+ *     The limits are not symmetric: two clusters 4200 radii apart along y are
+ *     refused, along x they are served; radius 0.05 over a 300 m scan is refused.  A NaN coordinate among finite points
+ *     is NOT refused: the bounding box skips it (fminf / fmaxf), the point is nobody's neighbour, and the job's measures
+ *     stay finite.
  * An empty cloud is the job's status CFEAR_ERR_EMPTY_CLOUD and does not fail the call.  Any other failed job makes the
  * batch call return that job's status (the first such job's); every record is written all the same -- failed jobs as
  * zeros with their status, all others valid.  The per_point rows of a failed job are unspecified.
@@ -937,7 +939,12 @@ typedef struct cfear_verify_result {
  * (cfear_verify_apply_constraints; not available with use_covariance_sampling).                                       */
 int cfear_verify_loop_candidates(cfear_ctx* ctx, const cfear_verify_job* jobs, int32_t n_jobs,
                                  const cfear_verify_params* par, cfear_verify_result* results);
-/* ApplyConstratins (loopclosure.cpp:261-274) over host records: groups [n] = the candidates' query ids.  No context. */
+/* ApplyConstratins (loopclosure.cpp:261-274) over host records: groups [n] = the candidates' query ids.  No context.
+ * Per query the candidates are ordered by probability, larger first, ties in input order; `rank` is the position in that
+ * order and a candidate is accepted when probability > model_threshold (strictly), every one or only rank 0.  A NaN
+ * probability (odom_bounds of an empty odometry chain is 0/0, cfear_verify_by_odometry) ranks after every finite one of its
+ * query, in input order, and is never accepted -- so it never takes the best place from a finite candidate.  (The
+ * reference's std::sort is undefined with NaN keys; this is the rule chosen here, and the oracle's.)                    */
 int cfear_verify_apply_constraints(const int32_t* groups, int32_t n, const cfear_verify_params* par, cfear_verify_result* results);
 /* loopclosure::VerifyByOdometry (loopclosure.cpp:776-808).  rel_xyt [n][3]: the odometry constraints'
  * RelativeMotion(i, i+1), i = to .. from-1.  similarity = 1 - exp(-(max(|T_odom| - 5, 0) / travelled)^2 / 2 sigma^2);

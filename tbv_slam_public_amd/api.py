@@ -1421,11 +1421,12 @@ def verify_params(ctx=None, **kw):
 def VerifyByOdometry(rel_xyt, odom_sigma_error=0.03, verify_via_odometry=True, ctx=None):
     """loopclosure::VerifyByOdometry (loopclosure.cpp:776-808): rel_xyt [n, 3] = RelativeMotion(i, i+1) for
     i = to .. from-1 -> similarity (quality["odom-bounds"])."""
-    ctx = ctx or default_context()
-    r = np.ascontiguousarray(rel_xyt, dtype=np.float64).reshape(-1, 3)
+    r = np.ascontiguousarray(rel_xyt, dtype=np.float64).reshape(-1, 3)          # (host arithmetic: no context is made for it)
     out = C.c_double()
-    ctx.check(ctx._lib.cfear_verify_by_odometry(r.ctypes.data, int(r.shape[0]), float(odom_sigma_error),
-                                               int(bool(verify_via_odometry)), C.byref(out)))
+    rc = L.lib().cfear_verify_by_odometry(r.ctypes.data, int(r.shape[0]), float(odom_sigma_error),
+                                          int(bool(verify_via_odometry)), C.byref(out))
+    if rc != L.OK:
+        raise L.CfearError(rc, "cfear_verify_by_odometry")
     return out.value
 
 

@@ -246,7 +246,10 @@ void apply_constraints_groups(const int32_t* groups, size_t group_stride_bytes, 
     keys[i].prob = results[i].probability;
     grouped = grouped && (i == 0 || keys[i].group >= keys[i - 1].group);
   }
-  auto by_prob = [](const Key& a, const Key& b) { return a.prob > b.prob; };
+  // NaN (the odom-bounds feature of an empty odometry chain is 0/0) after every finite probability: `a.prob > b.prob` alone is
+  // no strict weak order with NaN among the keys (the reference's std::sort is undefined there), and a finite best could lose
+  // its place to one.  The stable sort keeps NaN entries in input order; `>` below never accepts them.
+  auto by_prob = [](const Key& a, const Key& b) { return a.prob > b.prob || (b.prob != b.prob && a.prob == a.prob); };
   if (!grouped) std::stable_sort(keys.begin(), keys.end(), [](const Key& a, const Key& b) { return a.group < b.group; });
   for (size_t i = 0; i < n;) {
     size_t e = i;
