@@ -36,6 +36,7 @@ constexpr int kCenBinsPerLane = 8;
 constexpr int kCenPass = 64 * kCenBinsPerLane;
 constexpr int kCenCloudSplit = 4;
 constexpr size_t kCenChunkBytes = 64u << 20;   // image bytes per chunk: stats + rows read it twice, the second time on-die
+constexpr int kCenMaxGridY = 65535;            // images per chunk: cen2018_rows_kernel has the image on gridDim.y
 
 struct CenArgs {
   const uint8_t* polar;
@@ -373,7 +374,7 @@ extern "C" int cfear_filter_cen2018(cfear_ctx* ctx, const uint8_t* polar, const 
     for (int i = 0; i < fsize; i++) h_taps[i] = h_taps[i] * inv;
   }
   const size_t img_bytes = (size_t)rows * desc->stride;
-  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)batch, kCenChunkBytes / std::max<size_t>(1, img_bytes)));
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>(std::min(batch, kCenMaxGridY), kCenChunkBytes / std::max<size_t>(1, img_bytes)));
 
   CenArgs a{};
   const cfear_polar_desc dd = st.images(a.polar, polar, *desc);
@@ -430,6 +431,7 @@ extern "C" int cfear_filter_cen2018(cfear_ctx* ctx, const uint8_t* polar, const 
       hipLaunchKernelGGL(rows_fn, dim3((rows + kCenRowsWaves - 1) / kCenRowsWaves, c.batch), dim3(64 * kCenRowsWaves), rows_lds,
                          ctx->stream, c);
     }
+    CFEAR_HIP_CHECK(ctx, hipGetLastError());                 // the cloud kernel trusts what the row kernel leaves in the scratch
     {
       ProfScope ps(ctx, "cen2018_cloud");
       hipLaunchKernelGGL(cen2018_cloud_kernel, dim3(c.batch, kCenCloudSplit), dim3(256), cloud_lds, ctx->stream, c);

@@ -13,6 +13,8 @@
 
 namespace {
 
+constexpr int kLegacyMaxGridY = 65535;     // images per launch of legacy_prepare_kernel: it has the image on gridDim.y
+
 __global__ __launch_bounds__(256) void legacy_prepare_kernel(const uint8_t* __restrict__ polar, int rows, int cols, int stride,
                                                              long long batch_stride, int u_z, uint8_t* __restrict__ rev,
                                                              int rev_stride, int32_t* __restrict__ first /*[batch][rows][2]*/) {
@@ -149,8 +151,11 @@ extern "C" int cfear_filter_kstrongest_legacy(cfear_ctx* ctx, const uint8_t* pol
   u_z = std::max(0, std::min(256, u_z));
   {
     ProfScope ps(ctx, "kstrong_legacy_prepare");
-    hipLaunchKernelGGL(legacy_prepare_kernel, dim3((rows + 3) / 4, batch), dim3(256), 0, ctx->stream, d_polar, rows, cols, desc->stride,
-                       (long long)dd.batch_stride, u_z, d_rev, rev_stride, d_first);
+    const long long bstride = batch > 1 ? (long long)dd.batch_stride : (long long)rows * desc->stride;
+    for (int b0 = 0; b0 < batch; b0 += kLegacyMaxGridY)
+      hipLaunchKernelGGL(legacy_prepare_kernel, dim3((rows + 3) / 4, std::min(kLegacyMaxGridY, batch - b0)), dim3(256), 0, ctx->stream,
+                         d_polar + b0 * bstride, rows, cols, desc->stride, bstride, u_z, d_rev + (size_t)b0 * rows * rev_stride, rev_stride,
+                         d_first + (size_t)b0 * rows * 2);
   }
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
   cfear_polar_desc rd{rows, cols, rev_stride, batch, (int64_t)rows * rev_stride};

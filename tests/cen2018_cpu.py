@@ -187,3 +187,119 @@ def parameter_cases():
 
 def mirror_case():
     return speckle_image(55, 32, 300), dict(zq=3.0, sigma_gauss=17, min_range_bins=2, range_res=0.0438)
+
+
+# ---- the matrix (tests/test_gpu_cen2018_matrix.py): every row kernel, pass count, bitmap word count, run shape, row count ---
+def plateau_image(seed, rows, cols):
+    """a noise floor with one wide return per row: runs of hundreds of bins, over several 64-bin words.  Row 0's starts at bin
+    0 and row 1's ends in the last bin."""
+    rng = np.random.default_rng(seed)
+    img = rng.integers(5, 40, (rows, cols)).astype(np.int32)
+    for i in range(rows):
+        wdt = min(int(rng.integers(60, 330)), cols)
+        amp = int(rng.integers(60, 140))
+        c = int(rng.integers(0, cols - wdt + 1))
+        if i == 0:
+            c = 0
+        elif i == 1:
+            c = cols - wdt
+        img[i, c:c + wdt] += amp
+    return np.clip(img, 0, 255).astype(np.uint8)
+
+
+def runs_of(mask_row):
+    """(start, one past the end) of every maximal run of a row's mask"""
+    m = np.concatenate(([0], np.asarray(mask_row).astype(np.int8), [0]))
+    dm = np.diff(m)
+    return list(zip(np.nonzero(dm == 1)[0].tolist(), np.nonzero(dm == -1)[0].tolist()))
+
+
+CONSTANT_ROWS = (0, 1, 37, 128, 254, 255)
+MATRIX_WIDTHS = (511, 512, 513, 1025, 4095, 4096, 4097, 8191, 8192)
+MATRIX_FILTERS = (5, 17, 9)                                                 # cen2018_rows_kernel<15>, <51> and <0>
+MATRIX_ROW_COUNTS = (1, 3, 255, 257, 513)
+
+
+def every_bin_image(seed, cols, constants):
+    """rows of one value each, then three speckle rows.  Above 4096 bins the last row ends in two bins of 0 and one of 255: a
+    run of the last bin alone whatever zq is, so that a target lies in the last bitmap word -- at 4097 bins, where the
+    whole-row runs of zq -1 have their targets near bin 2048, the only target the 65th word can hold."""
+    sp = speckle_image(seed, 3, cols)
+    if cols > 4096:
+        sp[2, cols - 3:cols - 1] = 0
+        sp[2, cols - 1] = 255
+    return np.concatenate([np.full((1, cols), v, np.uint8) for v in constants] + [sp])
+
+
+# zq == 0 keeps these constants.  A row of one value has y == 0 in every bin wherever its float mean is the value itself
+# (q == 0), and with zq == 0 that IS thres: the restatement cannot decide such a row.  37 and 254 at 4097 and 8192 bins: the
+# float sum of the row ends above cols * value, q < 0 in every bin, sigma is 1e-6 .. 2e-5 (test_cen2018_cpu.py checks the choice)
+ZERO_ZQ_CONSTANTS = {200: (), 4097: (37, 254), 8192: (37, 254)}
+# Replaced plateau seeds (the first tried is 1000 * sigma_gauss + cols + 1).  With it the plateau of row 0 or of row 1 is
+# over a third of these narrow rows, the row's mean and sigma rise with it and the row detects nothing at zq 0.5, so the case
+# held no run from bin 0 or into the last bin; the replacement is the first seed from 20000 above it that has them.
+# (9, 4097): row 1's plateau was 61 bins wide, two words; the first seed from 20000 above it whose run into the last bin
+# spans three.
+PLATEAU_SEEDS = {(5, 512): 25522, (5, 513): 25516, (17, 511): 37518, (17, 512): 37518, (17, 513): 37515, (9, 512): 29514,
+                 (9, 4097): 33098}
+_MATRIX = {}                                                                # built once; the tests only read it
+
+
+# name -> (images [n, rows, cols], parameters, facts).  The facts are what tests/test_cen2018_cpu.py proves of the restatement's
+# mask of the case: "long" a run over three or more words, one from bin 0 and one into the last bin; "long_hi" a run over
+# three or more words that ends at bin 4096 or above; "whole" a run of cols - min_range_bins bins in every constant row; "hi" a
+# target at bin 4096 or above (every case above 4096 bins); "last_word" a target (at or above min_range_bins, in the row's
+# last word).  Seeds: the first tried, but for PLATEAU_SEEDS and the min_range_bins image.
+def matrix_cases():
+    if _MATRIX:
+        return _MATRIX
+    P = dict(zq=1.0, sigma_gauss=17, min_range_bins=0, range_res=0.0438)
+    cases = {}
+    for fi, sg in enumerate(MATRIX_FILTERS):
+        for wi, cols in enumerate(MATRIX_WIDTHS):
+            rows = (3, 7, 33)[(wi + fi) % 3]
+            seed = 1000 * sg + cols
+            sp = speckle_image(seed, rows, cols)
+            if cols > 4096:
+                sp[rows - 1, cols - 1] = 255        # a return in the last bin: at 4097 bins the only target the 65th word can hold
+            pl = plateau_image(PLATEAU_SEEDS.get((sg, cols), seed + 1), rows, cols)
+            # up to 1025 bins a plateau is a large part of its row and lifts the row's sigma: zq 0.5 there
+            cases["s%dw%d" % (sg, cols)] = (np.stack([sp, pl]), dict(P, sigma_gauss=sg, zq=0.5 if cols <= 1025 else 1.0),
+                                            ("long", "long_hi", "hi") if cols > 4096 else ("long",))
+    for rows in MATRIX_ROW_COUNTS:
+        cases["rows%d" % rows] = (np.stack([speckle_image(3000 + rows, rows, 48)]), dict(P, sigma_gauss=5, zq=2.0), ())
+    # zq <= 0: zq -1 takes every constant row, zq 0 those of ZERO_ZQ_CONSTANTS; both the three speckle rows
+    for cols, sg in ((200, 5), (4097, 17), (8192, 9)):
+        for zq in (-1.0, 0.0):
+            for mr in (0, 2):
+                consts = CONSTANT_ROWS if zq < 0 else ZERO_ZQ_CONSTANTS[cols]
+                facts = (("whole",) if zq < 0 else ()) + (("hi",) if cols > 4096 else ())
+                cases["zq%gw%dm%d" % (zq, cols, mr)] = (every_bin_image(4000 + cols, cols, consts)[None],
+                                                        dict(P, sigma_gauss=sg, zq=zq, min_range_bins=mr), facts)
+    # the widest filter: a halo of 511 bins, and as many taps as bins; the narrowest: 3 taps, on 3 bins too
+    cases["s341w8192"] = (np.stack([speckle_image(5001, 3, 8192), plateau_image(5002, 3, 8192)]), dict(P, sigma_gauss=341), ("hi",))
+    cases["s341w1023"] = (np.stack([speckle_image(5003, 3, 1023), plateau_image(5004, 3, 1023)]), dict(P, sigma_gauss=341), ())
+    cases["s1w3"] = (np.stack([speckle_image(5005, 3, 3)]), dict(P, sigma_gauss=1), ())
+    cases["s1w65"] = (np.stack([speckle_image(5006, 3, 65)]), dict(P, sigma_gauss=1), ())
+    # min_range_bins at and beyond the row's end, and inside the last bitmap word (of 4, and of 71: the second pass over words)
+    # (seed 6005: the first from 6000 on whose image detects in bins 195 .. 199 and in bin 199 itself)
+    for mr, facts in ((195, ("last_word",)), (199, ("last_word",)), (200, ()), (205, ())):
+        cases["w200m%d" % mr] = (np.stack([speckle_image(6005, 3, 200)]), dict(P, sigma_gauss=5, zq=0.5, min_range_bins=mr), facts)
+    cases["w4500m4490"] = (np.stack([speckle_image(6001, 3, 4500)]), dict(P, zq=0.5, min_range_bins=4490), ("last_word", "hi"))
+    _MATRIX.update(cases)
+    return _MATRIX
+
+
+def chunk_case(sigma_gauss):
+    """11 images of 3 x 100 bins for the chunking test"""
+    imgs = np.stack([speckle_image(7000 + 20 * sigma_gauss + s, 3, 100) for s in range(11)])
+    return imgs, dict(zq=2.0, sigma_gauss=sigma_gauss, min_range_bins=0, range_res=0.0438)
+
+
+def big_batch_case():
+    """64 distinct 4 x 48 sweeps, and the index of the source of each of 70000"""
+    src = np.stack([speckle_image(8000 + s, 4, 48) for s in range(64)])
+    pick = np.random.default_rng(8064).integers(0, 64, 70000)
+    pick[:64] = np.arange(64)
+    pick[-1] = 63
+    return src, pick, dict(zq=2.0, sigma_gauss=5, min_range_bins=0, range_res=0.0438)

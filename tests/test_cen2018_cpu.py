@@ -1,5 +1,6 @@
 """CPU: the Cen2018 restatement (tests/cen2018_cpu.py) against an independent float64 form, its defining properties, the
-undecided-bin cap on every input the GPU tests use, and the C-ABI additions (symbols, struct size, defaults, refusals)."""
+undecided-bin cap on every input the GPU tests use, what the matrix inputs claim to hold, and the C-ABI additions (symbols,
+struct size, defaults, refusals)."""
 import ctypes as C
 import math
 import os
@@ -129,6 +130,88 @@ def test_undecided_rows_of_the_strided_parameter_and_mirror_inputs():
                 total += img.shape[0]
         print("undecided rows %s: %d of %d" % (name, bad, total))
         assert bad <= UNDECIDED_ROW_CAP * total, (name, bad, total)
+
+
+def _matrix():
+    if not hasattr(_matrix, "c"):
+        _matrix.c = R.matrix_cases()
+    return _matrix.c
+
+
+def _word_span(a, b):
+    """64-bin words the run [a, b) touches"""
+    return (b - 1) // 64 - a // 64 + 1
+
+
+@pytest.mark.parametrize("name", sorted(R.matrix_cases().keys()))
+def test_matrix_inputs_meet_the_cap_and_are_what_they_claim(name):
+    """Every input of tests/test_gpu_cen2018_matrix.py: the undecided-row cap (zero rows for a case of fewer than 200), and
+    the facts the case is there for, read off the restatement's mask."""
+    imgs, par, facts = _matrix()[name]
+    cols = imgs.shape[2]
+    bad = total = 0
+    runs, targets = [], []
+    for img in imgs:
+        r = R.cen2018(img, **par)
+        bad += int(r["undecided"].any(axis=1).sum())
+        total += img.shape[0]
+        runs += [ab for i in range(img.shape[0]) for ab in R.runs_of(r["mask"][i])]
+        targets += r["targets"][:, 1].tolist()
+    print("undecided rows %s: %d of %d" % (name, bad, total))
+    assert bad <= UNDECIDED_ROW_CAP * total, (name, bad, total)
+    assert set(facts) <= {"long", "long_hi", "whole", "hi", "last_word"}
+    assert ("hi" in facts) == (cols > 4096)                 # every case above 4096 bins holds a target up there
+    if "long" in facts:
+        assert any(_word_span(a, b) >= 3 for a, b in runs) and any(a == 0 for a, b in runs) and any(b == cols for a, b in runs)
+    if "long_hi" in facts:
+        assert any(_word_span(a, b) >= 3 and b > 4096 for a, b in runs)
+    if "whole" in facts:
+        assert sum(1 for a, b in runs if (a, b) == (par["min_range_bins"], cols)) >= len(R.CONSTANT_ROWS)
+    if "hi" in facts:
+        assert any(t >= 4096 for t in targets)
+    if "last_word" in facts:
+        assert par["min_range_bins"] >= (cols - 1) // 64 * 64 and len(targets) > 0
+    if par["min_range_bins"] >= cols:
+        assert not runs
+
+
+def test_matrix_holds_every_width_filter_row_count_and_parameter_edge():
+    m = _matrix()
+    for sg in R.MATRIX_FILTERS:
+        for cols in R.MATRIX_WIDTHS:
+            imgs, par, facts = m["s%dw%d" % (sg, cols)]
+            assert imgs.shape[0] == 2 and imgs.shape[1] % 2 == 1 and imgs.shape[2] == cols and par["sigma_gauss"] == sg
+            assert "long" in facts and (cols <= 4096 or "hi" in facts)
+    assert [m["rows%d" % r][0].shape[1:] for r in R.MATRIX_ROW_COUNTS] == [(r, 48) for r in R.MATRIX_ROW_COUNTS]
+    for cols in (200, 4097, 8192):
+        for mr in (0, 2):
+            imgs, par, facts = m["zq-1w%dm%d" % (cols, mr)]
+            assert par["zq"] == -1.0 and [int(row[0]) for row in imgs[0][:6]] == list(R.CONSTANT_ROWS) and "whole" in facts
+            assert (imgs[0][:6] == imgs[0][:6, :1]).all() and m["zq0w%dm%d" % (cols, mr)][1]["zq"] == 0.0
+    assert m["s341w8192"][1]["sigma_gauss"] == 341 and m["s341w1023"][0].shape[2] == 3 * 341 and m["s1w3"][1]["sigma_gauss"] == 1
+    assert [m["w200m%d" % mr][1]["min_range_bins"] for mr in (195, 199, 200, 205)] == [195, 199, 200, 205]
+
+
+def test_constants_left_out_under_zq_zero_are_the_undecidable_ones():
+    """zq == 0: a row of one value whose float mean is that value has q == p == y == 0 == thres in every bin, which the
+    restatement cannot decide; the matrix keeps exactly the constants for which that is not so."""
+    for cols, sg in ((200, 5), (4097, 17), (8192, 9)):
+        img = np.concatenate([np.full((1, cols), v, np.uint8) for v in R.CONSTANT_ROWS])
+        r = R.cen2018(img, zq=0.0, sigma_gauss=sg, min_range_bins=0)
+        und = r["undecided"].any(axis=1)
+        assert tuple(v for v, u in zip(R.CONSTANT_ROWS, und) if not u) == R.ZERO_ZQ_CONSTANTS[cols]
+        assert (r["y"][und] == 0).all() and (r["thres"][und] == 0).all()
+
+
+def test_undecided_rows_of_the_chunk_and_large_batch_inputs():
+    src, pick, par = R.big_batch_case()
+    refs = [R.cen2018(img, **par) for img in src]
+    assert not any(r["undecided"].any() for r in refs) and max(len(r["targets"]) for r in refs) <= 32
+    assert pick.shape == (70000,) and set(pick.tolist()) == set(range(64))
+    for sg in (5, 17):
+        imgs, par = R.chunk_case(sg)
+        assert imgs.shape == (11, 3, 100)
+        assert not any(R.cen2018(img, **par)["undecided"].any() for img in imgs)
 
 
 def test_case_list_is_complete():
