@@ -1,6 +1,6 @@
 """GPU: cfear_pgo_solve_batch (csrc/pgo_batch.hip) -- many pose graphs in one call, one wavefront each.
 
-The yardsticks are the unchanged host solver cfear_pgo_solve and the dense NumPy LM of tests/test_pgo.py; the device
+The yardsticks are the unchanged host solver cfear_pgo_solve and the dense NumPy LM of tests/pgo_dense.py; the device
 solver is never compared with itself, except where the claim IS self-consistency (batch invariance, bit for bit).
 
 Device against host, graph by graph (test_batch_matches_host_solver): the counts must be equal; poses and costs differ by
@@ -18,7 +18,8 @@ import numpy as np
 import pytest
 
 from tbv_slam_public_amd import synth
-from test_pgo import PAR, DensePGO, _loop_graph, dense_lm
+from pgo_dense import DensePGO, dense_lm
+from test_pgo import PAR, _loop_graph
 from tbv_slam_public_amd import _lib as L
 from tbv_slam_public_amd import api
 
@@ -53,7 +54,7 @@ def test_batch_matches_dense_lm_with_exact_steps(ctx, loop_scaling):
     par = dict(PAR, loop_scaling=loop_scaling)
     res = api.pose_graph_optimize_batch(graphs, ctx=ctx, loop_scaling=loop_scaling)
     for (poses, ids, cons), (out, summ) in zip(graphs, res):
-        ref, costs = dense_lm(DensePGO(cons, ids, par), poses)
+        ref, costs, _ = dense_lm(DensePGO(cons, ids, par), poses)
         print("dense LM: iterations", summ["iterations"], len(costs) - 1, "cost", summ["initial_cost"], costs[0], summ["final_cost"], min(costs),
               "max |dp|", np.abs(out[:, :3] - ref[:, :3]).max(), "max |dq|", np.abs(out[:, 3:] - ref[:, 3:]).max())
         assert summ["usable"] and summ["num_residual_blocks"] == 23 + 4

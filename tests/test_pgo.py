@@ -1,6 +1,6 @@
 """Pose-graph optimisation (cfear_pgo_solve: CeresLeastSquares::Solve, tbv_slam/src/tbv_slam/ceresoptimizer.cpp:13-113) -- host
-code.  Checked against a dense NumPy restatement written for this test: the same residual (PoseGraph3dErrorTerm,
-ceresoptimizer.h:62-97), loss and scaling, the quaternion tangent of ceres::EigenQuaternionParameterization, numeric
+code.  Checked against the dense NumPy restatement of tests/pgo_dense.py: the same residual (PoseGraph3dErrorTerm,
+ceresoptimizer.h:62-97), loss and scaling, the quaternion tangent of ceres::EigenQuaternionParameterization, per-block
 Jacobians, and the trust-region LM of tests/test_oracle_pinning.py with an EXACT dense solve of every step -- so the
 library's conjugate-gradient steps are compared with direct ones."""
 import numpy as np
@@ -8,149 +8,7 @@ import pytest
 
 from tbv_slam_public_amd import _lib as L
 from tbv_slam_public_amd import api
-
-
-def qmul(a, b):
-    ax, ay, az, aw = a
-    bx, by, bz, bw = b
-    return np.array([aw * bx + ax * bw + ay * bz - az * by, aw * by + ay * bw + az * bx - ax * bz,
-                     aw * bz + az * bw + ax * by - ay * bx, aw * bw - ax * bx - ay * by - az * bz])
-
-
-def qconj(a):
-    return np.array([-a[0], -a[1], -a[2], a[3]])
-
-
-def qrot(q, v):
-    return qmul(qmul(q, np.array([v[0], v[1], v[2], 0.0])), qconj(q))[:3]
-
-
-def plus(pose, d):
-    out = pose.copy()
-    out[:3] += d[:3]
-    nd = np.linalg.norm(d[3:])
-    if nd > 0:
-        dq = np.concatenate([np.sin(nd) / nd * d[3:], [np.cos(nd)]])
-        out[3:] = qmul(dq, pose[3:])
-    return out
-
-
-class DensePGO:
-    def __init__(self, constraints, ids, par):
-        self.cons = []
-        idx = {int(i): k for k, i in enumerate(ids)}
-        for typ in (0, 1):
-            for c in constraints:
-                if c["type"] != typ:
-                    continue
-                f = 1.0 / par["loop_scaling"] if typ == 1 else 1.0
-                I = np.diag([1 / par["odom_vxx"], 1 / par["odom_vyy"], 1, 1, 1, 1 / par["odom_vtt"]]) * f
-                self.cons.append((idx[c["id_begin"]], idx[c["id_end"]], np.asarray(c["t_be"], float), np.linalg.cholesky(I), typ == 1))
-
-    def residuals(self, x):
-        out, cost = [], 0.0
-        for a, b, meas, Lm, cauchy in self.cons:
-            pa, qa, pb, qb = x[a, :3], x[a, 3:], x[b, :3], x[b, 3:]
-            qai = qconj(qa)
-            q_ab = qmul(qai, qb)
-            p_ab = qrot(qai, pb - pa)
-            dq = qmul(meas[3:], qconj(q_ab))
-            r = Lm @ np.concatenate([p_ab - meas[:3], 2.0 * dq[:3]])
-            s = r @ r
-            if cauchy:
-                rho0, rho1 = 0.01 * np.log(1 + s / 0.01), 1.0 / (1 + s / 0.01)
-            else:
-                rho0, rho1 = s, 1.0
-            cost += 0.5 * rho0
-            out.append(r * np.sqrt(rho1))
-        return cost, np.concatenate(out)
-
-    def evaluate(self, x, want_jac):
-        cost, r = self.residuals(x)
-        if not want_jac:
-            return cost, r, None
-        n = x.shape[0]
-        J = np.zeros((r.size, 6 * (n - 1)))
-        h = 1e-6
-        # numeric Jacobian of the ROBUSTIFIED residual wrt the tangent would differentiate sqrt(rho'); Ceres scales the plain
-        # Jacobian by sqrt(rho') instead (Corrector, alpha = 0) -> differentiate the plain residual and scale
-        def plain(xx):
-            out = []
-            for a, b, meas, Lm, cauchy in self.cons:
-                pa, qa, pb, qb = xx[a, :3], xx[a, 3:], xx[b, :3], xx[b, 3:]
-                qai = qconj(qa)
-                out.append(Lm @ np.concatenate([qrot(qai, pb - pa) - meas[:3], 2.0 * qmul(meas[3:], qconj(qmul(qai, qb)))[:3]]))
-            return np.concatenate(out)
-        sc = []
-        for a, b, meas, Lm, cauchy in self.cons:
-            pa, qa, pb, qb = x[a, :3], x[a, 3:], x[b, :3], x[b, 3:]
-            qai = qconj(qa)
-            rr = Lm @ np.concatenate([qrot(qai, pb - pa) - meas[:3], 2.0 * qmul(meas[3:], qconj(qmul(qai, qb)))[:3]])
-            sc += [np.sqrt(1.0 / (1 + rr @ rr / 0.01)) if cauchy else 1.0] * 6
-        sc = np.array(sc)
-        for i in range(1, n):
-            for k in range(6):
-                d = np.zeros(6)
-                d[k] = h
-                xp, xm = x.copy(), x.copy()
-                xp[i], xm[i] = plus(x[i], d), plus(x[i], -d)
-                J[:, 6 * (i - 1) + k] = (plain(xp) - plain(xm)) / (2 * h) * sc
-        return cost, r, J
-
-
-def dense_lm(prob, x0, max_iter=200):
-    x = x0.copy()
-    n = x.shape[0]
-    radius, dec, reuse, diag = 1e4, 2.0, False, None
-    x_cost, r, J = prob.evaluate(x, True)
-    g = J.T @ r
-    scaling = 1.0 / (1.0 + np.sqrt((J * J).sum(0)))
-    J = J * scaling
-    x_norm = np.linalg.norm(x[1:])
-    summ = dict(cost=x_cost, ok=True, gmax=np.abs(g).max(), it=0)
-    costs, invalid = [], 0
-    while True:
-        costs.append(summ["cost"])
-        if summ["it"] >= max_iter or (summ["ok"] and summ["gmax"] <= 1e-10) or radius <= 1e-32:
-            break
-        summ = dict(cost=0.0, ok=False, gmax=summ["gmax"], it=summ["it"] + 1)
-        if not reuse:
-            diag = np.clip((J * J).sum(0), 1e-6, 1e32)
-        A = J.T @ J + np.diag(diag / radius)
-        step = -np.linalg.solve(A, J.T @ r)
-        reuse = True
-        mr = J @ step
-        mcc = -mr @ (r + mr / 2)
-        if not (mcc > 0):
-            invalid += 1
-            assert invalid < 5
-            radius /= dec; dec *= 2
-            summ.update(cost=x_cost)
-            continue
-        invalid = 0
-        delta = step * scaling
-        cand = x.copy()
-        for i in range(1, n):
-            cand[i] = plus(x[i], delta[6 * (i - 1):6 * i])
-        cand_cost, _, _ = prob.evaluate(cand, False)
-        if np.linalg.norm((x - cand)[1:]) <= 1e-8 * (x_norm + 1e-8):
-            break
-        if abs(x_cost - cand_cost) <= 1e-6 * x_cost:
-            break
-        rel = (x_cost - cand_cost) / mcc
-        if rel > 1e-3:
-            x = cand
-            x_norm = np.linalg.norm(x[1:])
-            x_cost, r, J = prob.evaluate(x, True)
-            g = J.T @ r
-            J = J * scaling
-            summ.update(cost=x_cost, ok=True, gmax=np.abs(g).max())
-            radius = min(1e16, radius / max(1 / 3, 1 - (2 * rel - 1) ** 3))
-            dec, reuse = 2.0, False
-        else:
-            summ.update(cost=cand_cost)
-            radius /= dec; dec *= 2; reuse = True
-    return x, costs
+from pgo_dense import DensePGO, dense_lm, plus, qconj, qmul, qrot  # noqa: F401  (moved there; still importable from here)
 
 
 def _loop_graph(n, rng, drift=(0.02, 0.01, 0.004), n_loops=4):
@@ -192,7 +50,7 @@ def test_pgo_matches_dense_lm_with_exact_steps(loop_scaling):
     poses, ids, cons, true = _loop_graph(24, rng)
     par = dict(PAR, loop_scaling=loop_scaling)
     out, summ = api.pose_graph_optimize(poses, ids, cons, loop_scaling=loop_scaling)
-    ref, costs = dense_lm(DensePGO(cons, ids, par), poses)
+    ref, costs, _ = dense_lm(DensePGO(cons, ids, par), poses)
     assert summ["usable"] and summ["num_residual_blocks"] == 23 + 4
     assert summ["iterations"] == len(costs) - 1                            # the same accept / reject history
     np.testing.assert_allclose(summ["initial_cost"], costs[0], rtol=1e-12)
