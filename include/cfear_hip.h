@@ -1221,9 +1221,12 @@ int cfear_pgo_solve_batch(cfear_ctx* ctx, cfear_pose3d* poses, const uint64_t* i
 /* OdometryKeyframeFuser::AddToGraph (odometrykeyframefuser.cpp:428-445) for `stream`: the odometry constraint from the
  * keyframe added by the LAST processed frame to the keyframe before it -- id_begin / id_end are the stream's keyframe
  * ordinals (RadarScan::counter), t_be = Tfrom^-1 * Tto, type odometry.  The reference stores information = C.inverse()
- * of cov_current with its 3x3 block rotated into the from-frame; Register's constant diag(0.01, 0.01, 0, 0, 0, 1e-4) is
- * singular, so the reference's matrix is not finite -- here information is the inverse on the planar (x, y, yaw)
- * sub-space and zero elsewhere.  CFEAR_ERR_INVALID_ARGUMENT if the last frame added no keyframe or the first one.   */
+ * of cov_current with its 3x3 block rotated into the from-frame.  Where C has an inverse -- the covariance sampled with
+ * estimate_cov_by_sampling (Identity on z, roll and pitch) and the Identity a failed registration leaves -- information
+ * is that full 6x6 inverse, as in the reference.  Register's constant diag(0.01, 0.01, 0, 0, 0, 1e-4) is singular, so
+ * the reference's matrix is not finite -- there information is the inverse on the planar (x, y, yaw) sub-space and
+ * zero elsewhere.  CFEAR_ERR_INVALID_ARGUMENT if the last PROCESSED frame added no keyframe or the first one: a frame
+ * that failed (an empty cloud) counts as processed and leaves no constraint behind.                                */
 int cfear_odometry_get_constraint(cfear_odometry* od, int32_t stream, cfear_graph_constraint* out);
 
 /* ---- after the path: trajectory evaluation (the KITTI odometry metric) ---------------------------------------------

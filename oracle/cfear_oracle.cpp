@@ -1482,6 +1482,9 @@ struct orc_fuser {
   std::vector<Keyframe> keyframes;
   double cov_current[36];
   int cov_sampled = 0;
+  // what the last frame decided on: {registered x, y, theta before the sanity check, acc, vel, 1 = the guess replaced it,
+  // |t| and |rot| of Tkeydiff}; NaN after a first frame, which registers nothing and decides nothing
+  double last_decision[8];
   // wall time per stage (seconds), named like the reference's `timing` keys: "Filtering" (radar_driver.cpp:87, 111),
   // "compensate" + "build_normals", "register" (odometrykeyframefuser.cpp:253-255) -- for bench.py's cpu_baseline.stage_ms
   double t_stage[4] = {0, 0, 0, 0};
@@ -1493,7 +1496,11 @@ extern "C" orc_fuser* orc_fuser_create(const orc_fuser_params* p) {
   f->par = *p;
   f->T_prev = f->Tmot = f->Tcurrent = aff_identity();                       // :35-39
   for (int k = 0; k < 36; k++) f->cov_current[k] = (k % 7 == 0) ? 1.0 : 0.0;   // cov_current = Identity (:36)
+  for (double& d : f->last_decision) d = std::nan("");
   return f;
+}
+extern "C" void orc_fuser_last_decision(const orc_fuser* f, double out[8]) {
+  std::memcpy(out, f->last_decision, sizeof(f->last_decision));
 }
 extern "C" void orc_fuser_last_cov(const orc_fuser* f, double cov36[36], int32_t* sampled) {
   std::memcpy(cov36, f->cov_current, sizeof(f->cov_current));
@@ -1531,6 +1538,7 @@ extern "C" int orc_fuser_process(orc_fuser* f, float* xyzi, int n, double pose_o
   const Aff2 Tguess = par.use_guess ? aff_mul(f->T_prev, TprevMot) : f->T_prev;   // :164-168
   if (f->keyframes.empty()) {                                               // :171-177
     f->keyframes.push_back(orc_fuser::Keyframe{aff_identity(), cur});
+    for (double& d : f->last_decision) d = std::nan("");
     info[1] = 1;
     aff_to_xyt(f->Tcurrent, pose_out);
     return 0;
@@ -1580,17 +1588,19 @@ extern "C" int orc_fuser_process(orc_fuser* f, float* xyzi, int n, double pose_o
                                  (Tmot_current.t[1] / dt) * (Tmot_current.t[1] / dt));
     const double ax = (Tmot_current.t[0] - f->Tmot.t[0]) / (dt * dt), ay = (Tmot_current.t[1] - f->Tmot.t[1]) / (dt * dt);
     const double acc = std::sqrt(ax * ax + ay * ay);
+    aff_to_xyt(Tcurrent, f->last_decision);
+    f->last_decision[3] = acc; f->last_decision[4] = vel;
+    f->last_decision[5] = (acc > acc_limit || vel > vel_limit) ? 1.0 : 0.0;
     if (acc > acc_limit || vel > vel_limit) Tcurrent = Tguess;              // :198-199
   }
   f->Tmot = aff_mul(aff_inv(f->T_prev), Tcurrent);                          // :200
   // KeyFrameBasedFuse :62-73
   const Aff2 Tkeydiff = aff_mul(aff_inv(f->keyframes.back().pose), Tcurrent);
   bool fuse = true;
-  if (par.use_keyframe) {
-    const double tn = std::sqrt(Tkeydiff.t[0] * Tkeydiff.t[0] + Tkeydiff.t[1] * Tkeydiff.t[1]);
-    const double rot = std::fabs(std::atan2(Tkeydiff.l[2], Tkeydiff.l[3]));
-    fuse = tn > par.min_keyframe_dist || rot > (par.min_keyframe_rot_deg * M_PI / 180.0);
-  }
+  const double tn = std::sqrt(Tkeydiff.t[0] * Tkeydiff.t[0] + Tkeydiff.t[1] * Tkeydiff.t[1]);
+  const double rot = std::fabs(std::atan2(Tkeydiff.l[2], Tkeydiff.l[3]));
+  f->last_decision[6] = tn; f->last_decision[7] = rot;
+  if (par.use_keyframe) fuse = tn > par.min_keyframe_dist || rot > (par.min_keyframe_rot_deg * M_PI / 180.0);
   if (fuse) {                                                               // :236-250 + AddToReference :470-476
     f->keyframes.push_back(orc_fuser::Keyframe{Tcurrent, cur});
     if ((int)f->keyframes.size() > par.submap_scan_size) f->keyframes.erase(f->keyframes.begin());

@@ -166,6 +166,10 @@ void orc_fuser_destroy(orc_fuser* f);
 void orc_fuser_stage_times(const orc_fuser* f, double seconds[4], int64_t* n_frames);
 /* cov_current after the last processed frame (row-major 6x6); *sampled = 1 if it is the sampled one. */
 void orc_fuser_last_cov(const orc_fuser* f, double cov36[36], int32_t* sampled);
+/* What the last processed frame decided on: out = {registered x, y, theta BEFORE the sanity check, acc, vel of
+ * AccelerationVelocitySanityCheck, 1 if the guess replaced the registered pose, |t| and |rot| of Tkeydiff}.  All NaN
+ * after a first frame (no registration, no decision).  Reads state only.                                          */
+void orc_fuser_last_decision(const orc_fuser* f, double out[8]);
 /* Feeds one filtered cloud (modified in place by compensation).  pose_out = Tcurrent (x,y,th).
  * info[0]=n_cells, info[1]=keyframe added, info[2]=register status, info[3]=outer iters.   */
 int orc_fuser_process(orc_fuser* f, float* xyzi, int n, double pose_out[3], int32_t info[4]);

@@ -127,6 +127,8 @@ def lib():
         L.orc_fuser_process.argtypes = [C.c_void_p, f32p, C.c_int, f64p, i32p]
         L.orc_fuser_last_cov.argtypes = [C.c_void_p, f64p, i32p]
         L.orc_fuser_last_cov.restype = None
+        L.orc_fuser_last_decision.argtypes = [C.c_void_p, f64p]
+        L.orc_fuser_last_decision.restype = None
         _LIB = L
     return _LIB
 
@@ -486,11 +488,14 @@ class Fuser:
         self._h = lib().orc_fuser_create(C.byref(p))
 
     def process(self, xyzi):
+        """-> (pose, info), or -1 where the frame itself failed (orc_fuser_process returned -1)."""
         x = np.ascontiguousarray(xyzi, dtype=np.float32).copy()
         pose = np.empty(3, np.float64)
         info = np.zeros(4, np.int32)
         rc = lib().orc_fuser_process(self._h, _p(x, C.c_float), x.shape[0], _p(pose, C.c_double),
                                      _p(info, C.c_int32))
+        if rc == -1:
+            return -1
         assert rc == 0
         return pose, info
 
@@ -518,6 +523,14 @@ class Fuser:
         flag = C.c_int32()
         lib().orc_fuser_last_cov(self._h, _p(cov, C.c_double), C.byref(flag))
         return cov, bool(flag.value)
+
+    def last_decision(self):
+        """What the last frame decided on -> dict(registered = pose before the sanity check, acc, vel, replaced =
+        the guess took its place, key_t / key_rot = |t| and |rot| of Tkeydiff); NaN after a first frame."""
+        d = np.zeros(8, np.float64)
+        lib().orc_fuser_last_decision(self._h, _p(d, C.c_double))
+        return dict(registered=d[:3].copy(), acc=float(d[3]), vel=float(d[4]), replaced=bool(d[5] == 1.0),
+                    key_t=float(d[6]), key_rot=float(d[7]))
 
     def __del__(self):
         try:

@@ -285,7 +285,10 @@ extern "C" int cfear_odometry_create(cfear_ctx* ctx, int32_t n_streams, const cf
        (od->copy_stream = make_stream_nonblocking());
   dev(od->d_slabs, (size_t)B * od->slabs_per_stream * od->slab_bytes);
   dev(od->d_surf_jobs, (size_t)B * cfear_surface_job_bytes());
-  dev(od->d_reg_jobs, (size_t)B * cfear_reg_job_bytes());
+  // records are laid out at the stride of the window (process_frame); rounded up to 16 bytes, the stride of the longest
+  // window is 8 bytes MORE than a whole record
+  const size_t reg_job_room = std::max(cfear_reg_job_bytes(), cfear_reg_job_stride(par->submap_scan_size + 1));
+  dev(od->d_reg_jobs, (size_t)B * reg_job_room);
   od->out_bytes = (size_t)B * (sizeof(cfear_reg_result) + 12);
   dev(od->d_out, od->out_bytes);
   pin(od->h_out, od->out_bytes);
@@ -304,7 +307,7 @@ extern "C" int cfear_odometry_create(cfear_ctx* ctx, int32_t n_streams, const cf
   dev(od->d_surf_scratch, (size_t)B * cfear_surface_scratch_bytes(od->cap_points));
   dev(od->d_reg_scratch, (size_t)B * cfear_register_scratch_bytes(par->submap_scan_size * od->cell_cap));
   pin(od->h_surf_jobs, (size_t)B * cfear_surface_job_bytes());
-  pin(od->h_reg_jobs, (size_t)B * cfear_reg_job_bytes());
+  pin(od->h_reg_jobs, (size_t)B * reg_job_room);
   if (par->estimate_cov_by_sampling) {
     od->fit.prepare(par->cov_sampling.samples_per_axis, par->cov_sampling.xy_range * 0.5, par->cov_sampling.yaw_range * 0.5);
     dev(od->d_samples, (size_t)B * od->fit.m * sizeof(cfear_reg_result));
@@ -781,6 +784,7 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
     memset(&fi, 0, sizeof(fi));
     fi.n_points = od->h_npts[b];
     fi.n_cells = od->h_ncells[b];
+    st.has_constraint = false;                                    // whatever this frame does, the last constraint is no longer "the last frame's"
     if (od->h_status[b] != CFEAR_OK) {
       // empty cloud / capacity: the reference would exit(0) (pointnormal.cpp:72-75); report and keep the state
       if (first_error == CFEAR_OK)
@@ -790,7 +794,6 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
       aff_to_xyt(st.Tcurrent, fi.pose);
       continue;
     }
-    st.has_constraint = false;
     if (st.job < 0) {                                             // first frame becomes the first keyframe
       st.keyframes.push_back(Keyframe{st.cur_slab, aff_identity(), st.n_keyframes++});
       fi.keyframe_added = 1;
@@ -918,6 +921,29 @@ extern "C" int cfear_odometry_get_peaks(cfear_odometry* od, int32_t stream, floa
   return copy_cloud_out(od, od->d_pk + (size_t)stream * od->cap_points * 4, od->h_npk[stream], xyzi, cap, n_out);
 }
 
+// 6x6 inverse by Gauss-Jordan elimination with partial pivoting; false (and `inv` undefined) where a pivot column holds
+// nothing but zeros or something not finite -- the matrix is singular as it stands, no tolerance is applied.
+static bool inverse66(const double* m, double* inv) {
+  double a[6][12];
+  for (int r = 0; r < 6; r++)
+    for (int c = 0; c < 6; c++) { a[r][c] = m[r * 6 + c]; a[r][6 + c] = r == c ? 1.0 : 0.0; }
+  for (int k = 0; k < 6; k++) {
+    int p = k;
+    for (int r = k + 1; r < 6; r++) if (std::fabs(a[r][k]) > std::fabs(a[p][k])) p = r;
+    if (a[p][k] == 0.0 || !std::isfinite(a[p][k])) return false;
+    if (p != k) for (int c = 0; c < 12; c++) std::swap(a[p][c], a[k][c]);
+    const double d = a[k][k];
+    for (int c = 0; c < 12; c++) a[k][c] /= d;
+    for (int r = 0; r < 6; r++) {
+      const double f = a[r][k];
+      if (r == k || f == 0.0) continue;
+      for (int c = 0; c < 12; c++) a[r][c] -= f * a[k][c];
+    }
+  }
+  for (int r = 0; r < 6; r++) for (int c = 0; c < 6; c++) inv[r * 6 + c] = a[r][6 + c];
+  return true;
+}
+
 extern "C" int cfear_odometry_get_constraint(cfear_odometry* od, int32_t stream, cfear_graph_constraint* out) {
   if (!od || !out || stream < 0 || stream >= od->n_streams) return CFEAR_ERR_INVALID_ARGUMENT;
   const StreamState& st = od->streams[stream];
@@ -928,7 +954,11 @@ extern "C" int cfear_odometry_get_constraint(cfear_odometry* od, int32_t stream,
   aff_to_xyt(st.c_Tdiff, xyt);
   cfear_pose3d_from_xyt(xyt, &out->t_be);
   out->type = 0;                                                  // ConstraintType::odometry
-  // information on the planar sub-space (x, y, yaw) = indices 0, 1, 5; the full 6x6 is singular (see cfear_hip.h)
+  // information = C.inverse() (:440) where C has one: the sampled covariance (Identity on z, roll, pitch) and the Identity
+  // of a failed registration.  Register's constant diagonal is singular: there it is the inverse on the planar sub-space
+  // (x, y, yaw) = indices 0, 1, 5 and zero elsewhere (see cfear_hip.h)
+  if (inverse66(st.c_cov, out->information)) return CFEAR_OK;
+  memset(out->information, 0, sizeof(out->information));
   const int ix[3] = {0, 1, 5};
   double M[9], I[9];
   for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) M[r * 3 + c] = st.c_cov[ix[r] * 6 + ix[c]];
