@@ -340,6 +340,37 @@ int cfear_filter_cen2018(cfear_ctx* ctx, const uint8_t* polar, const cfear_polar
                          float* xyzi, int32_t* n_points, int32_t cap_points, int32_t* targets, uint8_t* det_mask,
                          float* row_stats);
 
+/* Cen and Newman's 2019 landmark detector: replaces cen2019features (coral_alignment_quality/src/alignment_checker/
+ * Utils.cpp:436-594, declared in Utils.h:46), behind `evaluate_scans --scan-type cen2019`.  The reference stops at `targets`
+ * (Cen2019Radar's constructor body is commented out, ScanType.cpp:90-101); the cloud here is Cen2018Radar's: range_res * bin
+ * (the bin EDGE), azimuth (row + 1) / rows * 2 pi, intensity = the raw byte; ordered (row, bin).
+ * Per sweep, in float with one rounding per operation: f = v * float(1 / 255.0); g = |f[r+1] - f[r-1]| (BORDER_REFLECT101: 0 in
+ * the first and last bin) times float(1 / double(max g)); s = f - mean(f); h = s * (1 - g); mean and mean_h are fp64 sums
+ * divided by rows * cols and rounded to float.  The pixels with h > mean_h are gone through in descending h (equal h: ascending
+ * row * cols + bin; the reference's std::sort leaves that open): one whose bin is unmarked marks its bin and the contiguous
+ * bins with s < 0 left of it -- and right of it if bin < rows - 1, the reference's comparison -- and counts if none of those
+ * was marked; the walk ends after max_points counted ones.  Per row every maximal run of marked bins from min_range_bins on that
+ * an UNMARKED bin ends (a run into the last column emits nothing) and that has a marked bin of row - 1 or row + 1 (wrapping)
+ * within its extent emits one target: the last bin of the run with h > 0, else its first (getMaxInRegion as written).
+ * A flat sweep (max g = 0: the reference computes NaN everywhere) has no target: zero points, CFEAR_OK, mean_h NaN.
+ * xyzi float [batch][cap_points][4], n_points int32 [batch]; optional: targets int32 [batch][cap_points][2] (azimuth, bin),
+ * region_mask uint8 [batch][rows][cols] (the marks R), image_stats float [batch][4] (mean, max g, mean_h, h of the last
+ * candidate gone through; 0 if none), counts int32 [batch][3] (candidates, fresh candidates of the sweep -- those that would
+ * count with max_points unbounded --, candidates gone through: the reference's j).
+ * The image and every output are all host or all device memory.  An image with more than cap_points targets yields
+ * CFEAR_ERR_CAPACITY (n_points then holds the counts, the buffers the first cap_points).  CFEAR_ERR_INVALID_ARGUMENT:
+ * max_points < 0 (0 is valid and marks nothing), min_range_bins < 0, range_res not finite, rows * cols > 2^22 (the fp64 sum of
+ * f is exact in any order up to there), cols < 2 or > 8192, rows > 30719.  The call is synchronous.                         */
+typedef struct cfear_cen2019_params {
+  int32_t max_points;                   /* 1000 (Utils.h:46) */
+  int32_t min_range_bins;               /* 0 */
+  double range_res;                     /* 0.04328 (ScanType.h:62) */
+} cfear_cen2019_params;
+void cfear_cen2019_params_default(cfear_cen2019_params* par);
+int cfear_filter_cen2019(cfear_ctx* ctx, const uint8_t* polar, const cfear_polar_desc* desc, const cfear_cen2019_params* par,
+                         float* xyzi, int32_t* n_points, int32_t cap_points, int32_t* targets, uint8_t* region_mask,
+                         float* image_stats, int32_t* counts);
+
 /* ---- C: motion compensation ----------------------------------------------------------------
  * Replaces Compensate(cloud, mot, ccw)  utils.cpp:96-107 (+ GetRelTimeStamp utils.h:28-32).
  * xyzi float [n][4] modified in place; mot = (x, y, theta) of the previous motion.           */

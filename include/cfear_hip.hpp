@@ -826,6 +826,40 @@ class Cen2018Radar {
   std::vector<int32_t> targets_;
 };
 
+// cen2019features (Utils.h:46, Utils.cpp:495): the Cen and Newman 2019 targets of one polar sweep as (azimuth, bin) pairs.  The
+// reference's fft_data is the uint8 sweep times float(1 / 255.0) (ScanType.cpp:94); here it is the uint8 sweep itself.
+inline std::vector<int32_t> cen2019features(CFEAR_Radarodometry::Context& ctx, const uint8_t* image, int rows, int cols, int stride,
+                                            int max_points = 1000, int min_range = 0) {
+  cfear_polar_desc d{rows, cols, stride, 1, 0};
+  cfear_cen2019_params p;
+  cfear_cen2019_params_default(&p);
+  p.max_points = max_points;
+  p.min_range_bins = min_range;
+  const int32_t cap = rows * ((cols + 1) / 2);             // a row of n bins holds at most ceil(n / 2) runs
+  std::vector<float> xyzi((size_t)cap * 4);
+  std::vector<int32_t> tg((size_t)cap * 2);
+  int32_t n = 0;
+  ctx.check(cfear_filter_cen2019(ctx.get(), image, &d, &p, xyzi.data(), &n, cap, tg.data(), nullptr, nullptr, nullptr));
+  tg.resize(2 * (size_t)n);
+  return tg;
+}
+#ifdef CFEAR_HIP_HAVE_CV_BRIDGE
+// the reference's shape: targets = Ones(3, n) with the azimuths in row 0 and the bins in row 1 (Utils.cpp:584-592); Targets is
+// Eigen::MatrixXd there
+template <class Targets>
+double cen2019features(const cv::Mat& fft_data, Targets& targets, int max_points, int min_range) {
+  const std::vector<int32_t> tg = cen2019features(CFEAR_Radarodometry::Context::Default(), fft_data.data, fft_data.rows, fft_data.cols,
+                                                  (int)fft_data.step, max_points, min_range);
+  const int n = (int)(tg.size() / 2);
+  targets = Targets::Ones(3, n);
+  for (int k = 0; k < n; k++) {
+    targets(0, k) = tg[2 * (size_t)k];
+    targets(1, k) = tg[2 * (size_t)k + 1];
+  }
+  return 0.0;
+}
+#endif
+
 // p2pQuality, keypointRepetability (AlignmentQuality.h:119-150, AlignmentQuality.cpp:235-328) and scanEvaluator
 // (ScanEvaluator.h:21-137, ScanEvaluator.cpp:4-114) over cfear_p2p_quality.  A PoseScan here is the cloud, the pose and the
 // id the measures read (ScanType.h: GetCloudNoCopy, GetAffine, pose_id); Eigen::Affine3d becomes Pose2d.

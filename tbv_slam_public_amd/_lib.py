@@ -81,6 +81,10 @@ class Cen2018Params(C.Structure):
                 ("range_res", C.c_double)]
 
 
+class Cen2019Params(C.Structure):
+    _fields_ = [("max_points", C.c_int32), ("min_range_bins", C.c_int32), ("range_res", C.c_double)]
+
+
 class Cell(C.Structure):
     _fields_ = [("mean", C.c_double * 2), ("normal", C.c_double * 2), ("cov", C.c_double * 4),
                 ("scale", C.c_double), ("avg_intensity", C.c_double), ("lambda_min", C.c_double),
@@ -290,6 +294,7 @@ EXPORTS = [
     "cfear_candidate_pipe_create", "cfear_candidate_pipe_submit", "cfear_candidate_pipe_collect", "cfear_candidate_pipe_destroy", "cfear_candidate_pipe_stats",
     "cfear_eval_params_default", "cfear_eval_trajectories", "cfear_eval_check", "cfear_kitti_read", "cfear_kitti_write",
     "cfear_kitti_from_xyt", "cfear_cen2018_params_default", "cfear_filter_cen2018",
+    "cfear_cen2019_params_default", "cfear_filter_cen2019",
     "cfear_logreg_params_default", "cfear_logreg_fit_batch", "cfear_p2p_quality", "cfear_p2p_quality_batch",
     "cfear_cart_params_default", "cfear_polar_to_cartesian", "cfear_cart_quality_batch",
     "cfear_cacfar_plan", "cfear_filter_cacfar_rowkeys", "cfear_kstrong_plan",
@@ -479,6 +484,9 @@ def lib():
     L.cfear_cen2018_params_default.argtypes = [C.POINTER(Cen2018Params)]
     L.cfear_cen2018_params_default.restype = None
     L.cfear_filter_cen2018.argtypes = [vp, vp, C.POINTER(PolarDesc), C.POINTER(Cen2018Params), vp, vp, C.c_int32, vp, vp, vp]
+    L.cfear_cen2019_params_default.argtypes = [C.POINTER(Cen2019Params)]
+    L.cfear_cen2019_params_default.restype = None
+    L.cfear_filter_cen2019.argtypes = [vp, vp, C.POINTER(PolarDesc), C.POINTER(Cen2019Params), vp, vp, C.c_int32, vp, vp, vp, vp]
     L.cfear_compensate.argtypes = [vp, vp, C.c_int32, C.POINTER(C.c_double), C.c_int32]
     L.cfear_scan_create.argtypes = [vp, vp, C.c_int32, C.POINTER(FeatureParams), C.POINTER(vp)]
     L.cfear_scan_from_cells.argtypes = [vp, vp, C.c_int32, C.POINTER(vp)]

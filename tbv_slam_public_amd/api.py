@@ -389,6 +389,56 @@ def filter_cen2018(img, zq=3.0, sigma_gauss=17, min_range_bins=2, range_res=0.04
     return res
 
 
+def cen2019_params(**kw):
+    """cfear_cen2019_params with the reference's settings (max_points 1000, min_range_bins 0, range_res 0.04328), overridden
+    by keyword."""
+    p = L.Cen2019Params()
+    L.lib().cfear_cen2019_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in ("max_points", "min_range_bins", "range_res"):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def filter_cen2019(img, max_points=1000, min_range_bins=0, range_res=0.04328, cap_points=None, want_targets=False,
+                   want_mask=False, want_stats=False, want_counts=False, ctx=None):
+    """The Cen2019 detector (cen2019features, Utils.cpp:436-594; the cloud as Cen2018Radar's, ScanType.cpp:68-88) for a uint8
+    image [rows, cols] or a batch [b, rows, cols] (NumPy -> NumPy results, torch CUDA tensor -> torch CUDA results; a torch
+    view with a row pitch or a batch stride is used in place).  Returns dict(xyzi [b, cap, 4], n_points [b][, targets
+    [b, cap, 2] (azimuth, bin)][, region_mask [b, rows, cols]][, image_stats [b, 4] (mean, max g, mean_h, h of the last
+    candidate gone through)][, counts [b, 3] (candidates, fresh, gone through)])."""
+    ctx = ctx or default_context()
+    d, batch, rows, cols = _desc(img)
+    cap = int(cap_points or rows * ((cols + 1) // 2))      # a row of n bins holds at most ceil(n / 2) runs
+    par = cen2019_params(max_points=int(max_points), min_range_bins=int(min_range_bins), range_res=float(range_res))
+    if _is_torch(img):
+        import torch
+        assert img.dtype == torch.uint8 and img.stride(-1) == 1
+        d.stride = img.stride(-2)
+        d.batch_stride = img.stride(0) if img.ndim == 3 else rows * d.stride
+        mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=img.device)
+        i32, u8, f32 = torch.int32, torch.uint8, torch.float32
+    else:
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        mk = lambda shape, dt: np.empty(shape, dt)
+        i32, u8, f32 = np.int32, np.uint8, np.float32
+    res = dict(xyzi=mk((batch, cap, 4), f32), n_points=mk((batch,), i32))
+    if want_targets:
+        res["targets"] = mk((batch, cap, 2), i32)
+    if want_mask:
+        res["region_mask"] = mk((batch, rows, cols), u8)
+    if want_stats:
+        res["image_stats"] = mk((batch, 4), f32)
+    if want_counts:
+        res["counts"] = mk((batch, 3), i32)
+    p = img.data_ptr() if _is_torch(img) else _ptr(img)[0]
+    ctx.check(ctx._lib.cfear_filter_cen2019(ctx.h, p, C.byref(d), C.byref(par), _ptr(res["xyzi"])[0], _ptr(res["n_points"])[0],
+                                            cap, _ptr(res.get("targets"))[0], _ptr(res.get("region_mask"))[0],
+                                            _ptr(res.get("image_stats"))[0], _ptr(res.get("counts"))[0]))
+    return res
+
+
 def k_strongest_filter(img, k_strongest, z_min, range_res, min_distance, ctx=None):
     """The legacy k_strongest_filter / InsertStrongestK (radar_filters.cpp:25-78; CorAl's kstrongRadar).  img: uint8
     [rows, cols] or [batch, rows, cols] (NumPy or torch CUDA).  Returns dict(xyzi [batch, rows * k, 4], n_points)."""
