@@ -427,14 +427,7 @@ int cfear_check_reg_params(cfear_ctx* ctx, const cfear_reg_params* par);
 void cfear_reg_pair_geometry(const cfear_reg_params* par, int max_tar_cells, int max_src_cells, int* pairs_cap, RegLaunchHint* hint);
 size_t cfear_reg_job_stride(int max_scans);         // bytes of a record that holds up to max_scans scan views
 void cfear_reg_job_set_itr(void* job, int itr);
-// quadratic fit of the cost samples -> 6x6 covariance (covariance.hip, host)
-struct CovFit {
-  int n = 0, m = 0;
-  std::vector<double> offsets;   // [m][3] sample offsets (x, y, yaw) in the reference's loop order
-  std::vector<double> pinv;      // [10][m] pseudo-inverse of the design matrix
-  void prepare(int samples_per_axis, double xy_half, double yaw_half);
-  bool solve(const double* costs /*[m]*/, double score_scale, double covariance_scaler, double cov36[36]) const;
-};
+// quadratic fit of the cost samples -> 6x6 covariance: struct CovFit (covfit.hpp, host)
 
 // ---------------------------------------------------------------------------------------------
 // device helpers

@@ -1,4 +1,5 @@
-// covariance.hip -- covariance of a registration by cost sampling: host half.
+// covfit.hpp -- covariance of a registration by cost sampling: the host fit.  No HIP include: the functions below are plain
+// C++ and tests/cpp/covfit_check.cpp builds them with g++.
 //
 // Replaces the dense-algebra tail of OdometryKeyframeFuser::approximateCovarianceBySampling
 // (cfear_radarodometry/src/cfear_radarodometry/odometrykeyframefuser.cpp:318-377) and of its copy
@@ -8,24 +9,32 @@
 // expensive part -- come from the cost-only mode of matcher_kernel (matcher.hip), one launch for
 // all registrations of a batch.  The fit is a 27 x 10 problem per registration: host work, as in the
 // reference.
+#pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <limits>
 #include <vector>
 
-#include "common.hpp"
+// One-sided Jacobi (Hestenes) SVD of A (m x n, row-major), kept in the form a minimum-norm least-squares solve needs.
+// W (rows x cols, column-major) holds A (tall, m >= n) or A^T (wide) rotated until its columns are orthogonal: W = A R (or
+// A^T R) = U S; sig2[j] = |W_j|^2; thr = Eigen's rank decision: singular values <= sigma_max * min(m, n) * eps count as zero.
+struct JacobiSvd {
+  bool tall = true;
+  int m = 0, n = 0, rows = 0, cols = 0;
+  std::vector<double> W, R, sig2;
+  double thr = 0.0;
+  bool kept(int j) const { return std::sqrt(sig2[(size_t)j]) > thr; }
+};
 
-namespace {
-
-// Minimum-norm least squares through a one-sided Jacobi (Hestenes) SVD -- the quantity Eigen's
-// A.bdcSvd(ComputeThinU | ComputeThinV).solve(b) returns (odometrykeyframefuser.cpp:337), including
-// its rank decision: singular values <= sigma_max * min(m, n) * eps count as zero.
-// W (rows x cols, column-major here) is rotated until its columns are orthogonal: W R = U S.
-void lstsq_jacobi(const std::vector<double>& A /*m x n row-major*/, const std::vector<double>& b, int m, int n,
-                  double* x /*[n]*/) {
-  const bool tall = m >= n;
-  const int rows = tall ? m : n, cols = tall ? n : m;          // work on A (tall) or A^T (wide)
-  std::vector<double> W((size_t)rows * cols), R((size_t)cols * cols, 0.0);
+inline JacobiSvd jacobi_svd(const std::vector<double>& A /*m x n row-major*/, int m, int n) {
+  JacobiSvd f;
+  f.tall = m >= n; f.m = m; f.n = n;
+  const bool tall = f.tall;
+  const int rows = f.rows = tall ? m : n, cols = f.cols = tall ? n : m;          // work on A (tall) or A^T (wide)
+  std::vector<double>& W = f.W;
+  std::vector<double>& R = f.R;
+  W.assign((size_t)rows * cols, 0.0); R.assign((size_t)cols * cols, 0.0);
   for (int i = 0; i < m; i++)
     for (int j = 0; j < n; j++) {
       if (tall) W[(size_t)j * rows + i] = A[(size_t)i * n + j];
@@ -61,34 +70,43 @@ void lstsq_jacobi(const std::vector<double>& A /*m x n row-major*/, const std::v
       }
     if (!rotated) break;
   }
-  std::vector<double> sig2(cols);
+  f.sig2.assign((size_t)cols, 0.0);
   double smax2 = 0.0;
   for (int j = 0; j < cols; j++) {
     double t = 0.0;
     for (int i = 0; i < rows; i++) t += W[(size_t)j * rows + i] * W[(size_t)j * rows + i];
-    sig2[j] = t;
+    f.sig2[(size_t)j] = t;
     smax2 = std::max(smax2, t);
   }
-  const double thr = std::sqrt(smax2) * (double)std::min(m, n) * eps;
+  f.thr = std::sqrt(smax2) * (double)std::min(m, n) * eps;
+  return f;
+}
+
+// Minimum-norm least squares through that SVD -- the quantity Eigen's A.bdcSvd(ComputeThinU | ComputeThinV).solve(b)
+// returns (odometrykeyframefuser.cpp:337).
+inline void lstsq_jacobi(const std::vector<double>& A /*m x n row-major*/, const std::vector<double>& b, int m, int n,
+                         double* x /*[n]*/) {
+  const JacobiSvd f = jacobi_svd(A, m, n);
+  const int rows = f.rows, cols = f.cols;
   for (int j = 0; j < n; j++) x[j] = 0.0;
   for (int j = 0; j < cols; j++) {
-    if (!(std::sqrt(sig2[j]) > thr)) continue;
-    if (tall) {          // A = U S R^T:  x += R_j (U_j^T b) / s_j,  U_j s_j = W_j
+    if (!f.kept(j)) continue;
+    if (f.tall) {        // A = U S R^T:  x += R_j (U_j^T b) / s_j,  U_j s_j = W_j
       double dot = 0.0;
-      for (int i = 0; i < m; i++) dot += W[(size_t)j * rows + i] * b[i];
-      const double f = dot / sig2[j];
-      for (int i = 0; i < n; i++) x[i] += R[(size_t)j * cols + i] * f;
+      for (int i = 0; i < m; i++) dot += f.W[(size_t)j * rows + i] * b[i];
+      const double g = dot / f.sig2[(size_t)j];
+      for (int i = 0; i < n; i++) x[i] += f.R[(size_t)j * cols + i] * g;
     } else {             // A^T = U S R^T:  x += U_j (R_j^T b) / s_j
       double dot = 0.0;
-      for (int i = 0; i < m; i++) dot += R[(size_t)j * cols + i] * b[i];
-      const double f = dot / sig2[j];
-      for (int i = 0; i < n; i++) x[i] += W[(size_t)j * rows + i] * f;
+      for (int i = 0; i < m; i++) dot += f.R[(size_t)j * cols + i] * b[i];
+      const double g = dot / f.sig2[(size_t)j];
+      for (int i = 0; i < n; i++) x[i] += f.W[(size_t)j * rows + i] * g;
     }
   }
 }
 
 // eigenvalues of a symmetric 3x3 by cyclic Jacobi rotations (SelfAdjointEigenSolver<Matrix3d>, :349)
-bool sym3_eigenvalues(const double Hin[9], double ev[3]) {
+inline bool sym3_eigenvalues(const double Hin[9], double ev[3]) {
   double a[9];
   for (int k = 0; k < 9; k++) a[k] = Hin[k];
   for (int sweep = 0; sweep < 50; sweep++) {
@@ -120,13 +138,22 @@ bool sym3_eigenvalues(const double Hin[9], double ev[3]) {
   return std::isfinite(ev[0]) && std::isfinite(ev[1]) && std::isfinite(ev[2]);
 }
 
-}  // namespace
+// quadratic fit of the cost samples -> 6x6 covariance
+struct CovFit {
+  int n = 0, m = 0;
+  std::vector<double> offsets;   // [m][3] sample offsets (x, y, yaw) in the reference's loop order
+  std::vector<double> pinv;      // [10][m] pseudo-inverse of the design matrix
+  void prepare(int samples_per_axis, double xy_half, double yaw_half);
+  bool solve(const double* costs /*[m]*/, double score_scale, double covariance_scaler, double cov36[36]) const;
+};
 
 // The sampling grid -- hence the design matrix A and its pseudo-inverse -- is the same for every
-// registration that shares (samples_per_axis, ranges): A^+ (10 x m) is built once by solving the least
-// squares problem for the m unit right-hand sides; each registration then costs one 10 x m product.
-// (Eigen refactorises per call; the solutions agree to rounding.)
-void CovFit::prepare(int samples_per_axis, double xy_half, double yaw_half) {
+// registration that shares (samples_per_axis, ranges): A^+ (10 x m) is built once; each registration then costs one
+// 10 x m product.  (Eigen refactorises per call; the solutions agree to rounding.)
+// Column s of A^+ is the least-squares solution for the unit right-hand side e_s.  One factorisation serves all m of
+// them: the dot product of a rotated column with e_s is that column's entry s, so the operations -- hence the bits, up to
+// the sign of a zero -- are those of m separate solves, at 1/m of their cost.
+inline void CovFit::prepare(int samples_per_axis, double xy_half, double yaw_half) {
   n = samples_per_axis;
   m = n * n * n;
   auto lin = [this](double half, int i) {                // linspace(-half, half, n)[i]  (loopclosure.cpp:866-890)
@@ -144,17 +171,20 @@ void CovFit::prepare(int samples_per_axis, double xy_half, double yaw_half) {
     r[6] = x; r[7] = y; r[8] = z; r[9] = 1.0;
   }
   pinv.assign((size_t)10 * m, 0.0);
-  std::vector<double> e(m, 0.0);
-  double q[10];
-  for (int s = 0; s < m; s++) {
-    e[s] = 1.0;
-    lstsq_jacobi(A, e, m, 10, q);
-    e[s] = 0.0;
-    for (int k = 0; k < 10; k++) pinv[(size_t)k * m + s] = q[k];
+  const JacobiSvd f = jacobi_svd(A, m, 10);
+  const int rows = f.rows, cols = f.cols;
+  for (int j = 0; j < cols; j++) {
+    if (!f.kept(j)) continue;
+    const double* wj = &f.W[(size_t)j * rows];
+    const double* rj = &f.R[(size_t)j * cols];
+    for (int s = 0; s < m; s++) {
+      const double g = (f.tall ? wj[s] : rj[s]) / f.sig2[(size_t)j];
+      for (int k = 0; k < 10; k++) pinv[(size_t)k * m + s] += (f.tall ? rj[k] : wj[k]) * g;
+    }
   }
 }
 
-bool CovFit::solve(const double* costs, double score_scale, double covariance_scaler, double cov36[36]) const {
+inline bool CovFit::solve(const double* costs, double score_scale, double covariance_scaler, double cov36[36]) const {
   double q[10];
   for (int k = 0; k < 10; k++) {
     double t = 0.0;

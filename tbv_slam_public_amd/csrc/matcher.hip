@@ -33,6 +33,7 @@
 #include <memory>
 
 #include "common.hpp"
+#include "covfit.hpp"
 #include "fastmath.hpp"
 
 namespace {
