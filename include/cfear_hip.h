@@ -69,6 +69,8 @@ const char* cfear_status_string(int status);
 int cfear_ctx_create(int device, void* hip_stream, cfear_ctx** out);
 int cfear_ctx_destroy(cfear_ctx* ctx);
 int cfear_ctx_synchronize(cfear_ctx* ctx);
+/* ctx NULL: the text of the calling thread's last refusal by a call that was given no context (the calls that check
+ * their host arguments before they need one); empty if there was none.                                               */
 const char* cfear_last_error(const cfear_ctx* ctx);
 /* The hipStream_t the context enqueues on (the caller's, or the private one cfear_ctx_create made): lets the host
  * order other work -- a collective, a copy -- behind the library's kernels without a host synchronisation.        */
@@ -1326,6 +1328,66 @@ int cfear_eval_check(const cfear_eval_params* par, const int32_t* est_lengths, c
 int cfear_kitti_read(const char* path, double* poses, int64_t cap, int64_t* n_out);
 int cfear_kitti_write(const char* path, const double* poses, int64_t n);
 int cfear_kitti_from_xyt(const double* xyt, int64_t n, int64_t stride, double* poses);
+
+/* ---- after the path: synchronising estimate and ground truth by time -------------------------------------------------
+ * What EvalTrajectory::Save() does before it writes anything (cfear_radarodometry/src/cfear_radarodometry/
+ * eval_trajectory.cpp:265-315, cited as :line): One2OneCorrespondance (:400-423) interpolates the ground truth at the stamp
+ * of every estimated pose and drops the estimates that no two ground-truth poses bracket -- the step that turns a 4 Hz
+ * estimate and a 50 or 100 Hz ground truth into the equally long pair cfear_eval_trajectories and cfear_loop_stats_batch
+ * take.  For a batch of pairs in one call (csrc/trajsync.hip), the reference's semantics quirk for
+ * quirk:
+ *   time          ros::Time::toSec(), (double)sec + 1e-9 * (double)nsec with sec = ns / 10^9 (roscpp's TimeBase::toSec,
+ *                 restated: roscpp is not part of the reference tree).  ALL comparisons are on these doubles, which
+ *                 resolve about 2.4e-7 s around 1.5e9 s: distinct stamps can compare equal.
+ *   SearchByTime  (:424-442) a ground truth of 2 poses or fewer finds nothing (`<= 2`).  Otherwise j walks from the carried
+ *                 position to n_gt - 2 and the first j with t[j] <= ts && ts <= t[j+1] wins.  A hit leaves the position at
+ *                 j; a miss leaves it at the end and One2OneCorrespondance resets it to 0 (:412).  So the estimate stamps
+ *                 may be in any order: one that steps back misses, and the next is searched from 0.
+ *   pose_interp   (:461-491) alpha = (t - t1) / (t2 - t1), 0 when t2 == t1; translation (1 - alpha) p1 + alpha p2 with z
+ *                 then set to 0; rotation Quaterniond(R1).slerp(alpha, Quaterniond(R2)).toRotationMatrix(), restated from
+ *                 Eigen 3.3: the matrix -> quaternion conversion branches on the trace and otherwise picks the pivot by
+ *                 m11 > m00, then m22 > m(i,i), without normalising; slerp is linear where |dot| >= 1 - DBL_EPSILON, else
+ *                 acos / sin weights, the second negated for a negative dot; toRotationMatrix in its tx = 2x form.  No
+ *                 product is fused.
+ * CFEAR_SYNC_CHAINED carries the search position from one estimate of a pair to the next (One2OneCorrespondance);
+ * CFEAR_SYNC_INDEPENDENT searches every stamp from the first ground-truth pose (Interpolate(t, out), eval_trajectory.h:
+ * 141-144; tbv_slam_online.cpp:200-204).  They differ where a stamp lies in more than one interval.
+ *
+ * est, gt: [..][12] doubles, KITTI rows; stamps: nanoseconds (ros::Time::toNSec()).  Pair t is est_lengths[t] estimates from
+ * est_offsets[t] and gt_lengths[t] ground-truth poses from gt_offsets[t] (an offsets array may be NULL: the pairs follow each
+ * other).  Offsets, lengths and counts are host arrays; est, est_stamps, gt, gt_stamps and the four outputs are all host
+ * or all device memory (device poses 16-byte aligned) and the outputs do not overlap the inputs.  Pair t writes its
+ * counts[t] kept rows, compacted and in estimate order, at est_offsets[t] of every output -- so est_out, gt_out,
+ * est_offsets and counts are arguments of cfear_eval_trajectories as they are; what lies behind a pair's kept rows is not
+ * written.  Kept estimate poses are copied bit for bit, stamps_out holds the estimate's stamp, rows[i] names the estimate
+ * (its index within the pair: gather whatever else is kept per estimate, such as the covariances of cfear_cov_write), the
+ * interval and alpha.  est may be NULL (labelling stamps without poses); est_out is then unused.  A pair with no
+ * estimates or no ground truth is legal and keeps nothing.
+ * Refused with CFEAR_ERR_INVALID_ARGUMENT before anything is written, cfear_last_error naming the pair and the index:
+ * null pointers, n_traj < 0, a negative length or offset, host and device buffers mixed, an unknown mode, a stamp that is
+ * negative or whose seconds exceed 2^32 - 1 (ros::Time::sec is a uint32), and ground-truth stamps that descend within a
+ * pair.  The reference would walk an unsorted ground truth serially; a bag's ground-truth topic is recorded in time
+ * order and the parallel search needs that order, so an unsorted one is refused, not ignored.  Host buffers are checked
+ * before a context is needed (ctx may then be NULL: the refusal is the same, its text is at cfear_last_error(NULL)),
+ * device buffers by a kernel of their own, whose verdict is read together with counts: the call synchronises once.   */
+#define CFEAR_SYNC_CHAINED 0
+#define CFEAR_SYNC_INDEPENDENT 1
+typedef struct cfear_sync_row {
+  int32_t est_index, gt_index;          /* the estimate within its pair; the interval [gt_index, gt_index + 1] within its pair */
+  double alpha;
+} cfear_sync_row;                       /* 16 bytes */
+int cfear_sync_trajectories(cfear_ctx* ctx, int32_t mode, const double* est, const int64_t* est_stamps, const int64_t* est_offsets,
+                            const int32_t* est_lengths, const double* gt, const int64_t* gt_stamps, const int64_t* gt_offsets,
+                            const int32_t* gt_lengths, int32_t n_traj, double* est_out, double* gt_out, int64_t* stamps_out,
+                            cfear_sync_row* rows, int32_t* counts);
+/* Host writers, no context (Save()'s directory and file naming, DatasetToSequence, stays with the caller).
+ * cfear_tum_write: EvalTrajectory::WriteTUM (:185-211): per pose `sec.` + nsec zero-padded to 9 digits + a space, the
+ * translation std::fixed with 4 decimals, the quaternion x y z w under std::defaultfloat with the precision still 4
+ * (%.4g), from the matrix -> quaternion conversion above.  cfear_cov_write: EvalTrajectory::WriteCov (:214-232): the stamp,
+ * then the 36 entries of cov [n][36] row-major, space-separated, %g at the stream's default precision of 6
+ * (Eigen::StreamPrecision with DontAlignCols).  A stamp outside ros::Time's range: CFEAR_ERR_INVALID_ARGUMENT.          */
+int cfear_tum_write(const char* path, const double* poses, const int64_t* stamps, int64_t n);
+int cfear_cov_write(const char* path, const double* cov, const int64_t* stamps, int64_t n);
 
 /* ---- after the path: training the classifiers (alignment_checker's LogisticRegression::fit) --------------------------
  * What the reference asks of sklearn.linear_model.LogisticRegression(class_weight="balanced", max_iter=1000) through

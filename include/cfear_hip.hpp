@@ -59,6 +59,20 @@ struct PointXYZI { float x, y, z, intensity; };            // 16-byte PointXYZI 
 typedef std::vector<PointXYZI> PointCloud;
 struct Pose2d { double x, y, theta; };                     // Affine3dToVectorXYeZ (utils.cpp:115-122)
 
+// eval_trajectory.h:57-64 as a POD: the KITTI row of the pose (the rows of the 3 x 4 matrix), the 6 x 6 covariance row-major,
+// and the stamp in nanoseconds (ros::Time::toNSec())
+struct poseStamped {
+  std::array<double, 12> pose{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}};
+  std::array<double, 36> cov{};
+  int64_t t = 0;
+  poseStamped() {}
+  poseStamped(const std::array<double, 12>& _pose, const std::array<double, 36>& _cov, int64_t _t) : pose(_pose), cov(_cov), t(_t) {}
+  poseStamped(const Pose2d& p, int64_t _t) : t(_t) {
+    cfear_kitti_from_xyt(&p.x, 1, 3, pose.data());
+  }
+};
+typedef std::vector<poseStamped> poseStampedVector;
+
 struct CfearError : std::runtime_error {
   int status;
   CfearError(int st, const std::string& msg) : std::runtime_error(msg), status(st) {}
@@ -696,6 +710,12 @@ class OdometryKeyframeFuser {
       const auto it = stamp_map.find(nd.stamp);
       if (it != stamp_map.end()) { nd.Tgt = it->second; nd.has_Tgt = true; }
     }
+  }
+  // EvalTrajectory::GetGtVek() as it is (offline_odometry.cpp:137): planar poses from the KITTI rows
+  void AddGroundTruth(const poseStampedVector& gt_vek, int stream = 0) {
+    std::vector<std::pair<uint64_t, Pose2d>> v;
+    for (const poseStamped& gt : gt_vek) v.emplace_back((uint64_t)gt.t, Pose2d{gt.pose[3], gt.pose[7], std::atan2(gt.pose[4], gt.pose[0])});
+    AddGroundTruth(v, stream);
   }
 #ifdef CFEAR_HIP_HAVE_EIGEN_PCL
   // the reference's argument (odometrykeyframefuser.h:240): poseStampedVector = elements with .pose (Eigen::Affine3d) and .t (ros::Time)
@@ -1669,3 +1689,107 @@ inline std::vector<LoopCurve> LoopCurves(CFEAR_Radarodometry::Context& ctx, cons
   }
   return out;
 }
+
+// EvalTrajectory (eval_trajectory.h:70-184): the collector every executable of the reference ends in.  The Callback*Eigen
+// methods append stamped poses; Save() runs One2OneCorrespondance (eval_trajectory.cpp:400-423) through
+// cfear_sync_trajectories -- every estimate keeps the ground truth interpolated at its stamp, estimates without bracketing
+// ground truth are dropped, and the two vectors are replaced by the synchronised ones -- and writes the five files of
+// EvalTrajectory::Save (:265-315; three without a ground truth).  A stamped pose is a POD: the KITTI row of the pose, the
+// 6 x 6 covariance and the stamp in nanoseconds (ros::Time::toNSec()).  GetGtVek() feeds OdometryKeyframeFuser::
+// AddGroundTruth, as offline_odometry.cpp:134-137 does: after Save() its stamps are the estimate's.
+#include <sys/stat.h>
+namespace CFEAR_Radarodometry {
+
+class EvalTrajectory {
+ public:
+  class Parameters {                                         // eval_trajectory.h:75-110, without the topics
+   public:
+    std::string est_output_dir = "", gt_output_dir = "";
+    std::string sequence = "", method = "";
+    int job_nr = -1;
+  };
+  explicit EvalTrajectory(const Parameters& pars, bool disable_callback = true, Context* ctx = nullptr) : par(pars), ctx_(ctx) { (void)disable_callback; }
+  void CallbackEigen(const poseStamped& Test, const poseStamped& Tgt) { CallbackESTEigen(Test); CallbackGTEigen(Tgt); }
+  void CallbackGTEigen(const poseStamped& Tgt) { gt_vek.push_back(Tgt); }
+  void CallbackESTEigen(const poseStamped& Test) { est_vek.push_back(Test); }
+  size_t GetSize() { return std::min(gt_vek.size(), est_vek.size()); }
+  poseStampedVector& GetGtVek() { return gt_vek; }
+  poseStampedVector& GetEstVek() { return est_vek; }
+  // Interpolate(t, Tinterpolated), eval_trajectory.h:141-144: the search starts from the first ground-truth pose
+  bool Interpolate(int64_t t, poseStamped& Tinterpolated) {
+    std::vector<double> g;
+    std::vector<int64_t> gs;
+    Flatten(gt_vek, g, gs);
+    const int32_t n_est = 1, n_gt = (int32_t)gt_vek.size();
+    int32_t count = 0;
+    cfear_sync_row row{};
+    int64_t stamp = 0;
+    std::array<double, 12> out{};
+    context().check(cfear_sync_trajectories(context().get(), CFEAR_SYNC_INDEPENDENT, nullptr, &t, nullptr, &n_est, g.data(), gs.data(), nullptr, &n_gt, 1,
+                                            nullptr, out.data(), &stamp, &row, &count));
+    if (!count) return false;
+    Tinterpolated = poseStamped(out, gt_vek[(size_t)row.gt_index].cov, t);        // the covariance of the pose before (:455)
+    return true;
+  }
+  // Save(): the file name is Parameters::sequence as it is (the reference maps bag names to NN.txt in DatasetToSequence,
+  // eval_trajectory.cpp:64-132; that table stays with the caller)
+  void Save() {
+    if (est_vek.empty() && gt_vek.empty()) throw CfearError(CFEAR_ERR_INVALID_ARGUMENT, "Nothing to evaluate");
+    const std::string& name = par.sequence;
+    const bool have_gt = !gt_vek.empty();
+    if (have_gt) One2OneCorrespondance();
+    std::vector<double> e, g, cov;
+    std::vector<int64_t> es, gs;
+    Flatten(est_vek, e, es);
+    Flatten(gt_vek, g, gs);
+    for (const poseStamped& p : est_vek) cov.insert(cov.end(), p.cov.begin(), p.cov.end());
+    if (have_gt) {
+      MakeDirs(par.gt_output_dir);
+      Check(cfear_kitti_write((par.gt_output_dir + name).c_str(), g.data(), (int64_t)gs.size()), par.gt_output_dir + name);
+      Check(cfear_tum_write((par.gt_output_dir + "tum_" + name).c_str(), g.data(), gs.data(), (int64_t)gs.size()), par.gt_output_dir + "tum_" + name);
+    }
+    MakeDirs(par.est_output_dir);
+    Check(cfear_kitti_write((par.est_output_dir + name).c_str(), e.data(), (int64_t)es.size()), par.est_output_dir + name);
+    Check(cfear_tum_write((par.est_output_dir + "tum_" + name).c_str(), e.data(), es.data(), (int64_t)es.size()), par.est_output_dir + "tum_" + name);
+    Check(cfear_cov_write((par.est_output_dir + "cov_" + name).c_str(), cov.data(), es.data(), (int64_t)es.size()), par.est_output_dir + "cov_" + name);
+  }
+
+ private:
+  Context& context() { return ctx_ ? *ctx_ : Context::Default(); }
+  static void Check(int rc, const std::string& path) { if (rc != CFEAR_OK) throw CfearError(rc, path); }
+  static void Flatten(const poseStampedVector& v, std::vector<double>& poses, std::vector<int64_t>& stamps) {
+    for (const poseStamped& p : v) { poses.insert(poses.end(), p.pose.begin(), p.pose.end()); stamps.push_back(p.t); }
+  }
+  static void MakeDirs(const std::string& dir) {              // boost::filesystem::create_directories
+    for (size_t at = 1; at <= dir.size(); at++)
+      if (at == dir.size() || dir[at] == '/') ::mkdir(dir.substr(0, at).c_str(), 0777);
+  }
+  void One2OneCorrespondance() {
+    std::vector<double> e, g;
+    std::vector<int64_t> es, gs;
+    Flatten(est_vek, e, es);
+    Flatten(gt_vek, g, gs);
+    const int32_t n_est = (int32_t)est_vek.size(), n_gt = (int32_t)gt_vek.size();
+    int32_t count = 0;
+    std::vector<double> e_out(e.size()), g_out(e.size());
+    std::vector<int64_t> s_out(es.size());
+    std::vector<cfear_sync_row> rows(es.size());
+    context().check(cfear_sync_trajectories(context().get(), CFEAR_SYNC_CHAINED, e.data(), es.data(), nullptr, &n_est, g.data(), gs.data(), nullptr, &n_gt,
+                                            1, e_out.data(), g_out.data(), s_out.data(), rows.data(), &count));
+    poseStampedVector revised_est, revised_gt;
+    for (int32_t i = 0; i < count; i++) {
+      revised_est.push_back(est_vek[(size_t)rows[(size_t)i].est_index]);
+      poseStamped gt_i;
+      std::copy(g_out.begin() + (size_t)i * 12, g_out.begin() + (size_t)i * 12 + 12, gt_i.pose.begin());
+      gt_i.cov = gt_vek[(size_t)rows[(size_t)i].gt_index].cov;
+      gt_i.t = s_out[(size_t)i];
+      revised_gt.push_back(gt_i);
+    }
+    est_vek = revised_est;
+    gt_vek = revised_gt;
+  }
+  Parameters par;
+  Context* ctx_;
+  poseStampedVector est_vek, gt_vek;
+};
+}  // namespace CFEAR_Radarodometry

@@ -300,6 +300,7 @@ EXPORTS = [
     "cfear_cacfar_plan", "cfear_filter_cacfar_rowkeys", "cfear_kstrong_plan",
     "cfear_closure_params_default", "cfear_closure_candidates_batch",
     "cfear_loop_stats_params_default", "cfear_loop_stats_batch", "cfear_loop_curves_params_default", "cfear_loop_curves_batch",
+    "cfear_sync_trajectories", "cfear_tum_write", "cfear_cov_write",
 ]
 
 PIPE_GRAPH, PIPE_TIMING = 1, 2      # enum { CFEAR_PIPE_GRAPH, CFEAR_PIPE_TIMING }
@@ -377,6 +378,10 @@ assert EVAL_SUMMARY_DTYPE.itemsize == 360
 EVAL_ROW_DTYPE = np.dtype([("trajectory", "<i4"), ("first_frame", "<i4"), ("last_frame", "<i4"), ("pad", "<i4"),
                            ("length", "<f8"), ("r_err", "<f8"), ("t_err", "<f8"), ("speed", "<f8")])
 assert EVAL_ROW_DTYPE.itemsize == 48
+
+SYNC_MODE = {"chained": 0, "independent": 1}     # CFEAR_SYNC_CHAINED, CFEAR_SYNC_INDEPENDENT
+SYNC_ROW_DTYPE = np.dtype([("est_index", "<i4"), ("gt_index", "<i4"), ("alpha", "<f8")])      # cfear_sync_row
+assert SYNC_ROW_DTYPE.itemsize == 16
 
 LOGREG_MAX_FEATURES = 8
 
@@ -611,6 +616,9 @@ def lib():
     L.cfear_kitti_read.argtypes = [C.c_char_p, vp, C.c_int64, C.POINTER(C.c_int64)]
     L.cfear_kitti_write.argtypes = [C.c_char_p, vp, C.c_int64]
     L.cfear_kitti_from_xyt.argtypes = [vp, C.c_int64, C.c_int64, vp]
+    L.cfear_sync_trajectories.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
+    L.cfear_tum_write.argtypes = [C.c_char_p, vp, vp, C.c_int64]
+    L.cfear_cov_write.argtypes = [C.c_char_p, vp, vp, C.c_int64]
     L.cfear_logreg_params_default.argtypes = [C.POINTER(LogregParams)]
     L.cfear_logreg_params_default.restype = None
     L.cfear_logreg_fit_batch.argtypes = [vp, C.POINTER(LogregJob), C.c_int32, C.POINTER(LogregParams), vp]

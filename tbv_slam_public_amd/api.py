@@ -2310,7 +2310,88 @@ def _override_odometry_params(p, kw):
 
 class EvalTrajectory:
     """The KITTI-style trajectory text of the reference's evaluation (EvalTrajectory::Write, eval_trajectory.cpp:169-183;
-    MatToString, types.cpp:64-73): one pose per line, the top three rows of the 4 x 4 matrix, std::fixed (6 decimals)."""
+    MatToString, types.cpp:64-73): one pose per line, the top three rows of the 4 x 4 matrix, std::fixed (6 decimals).
+
+    An instance is the reference's collector (eval_trajectory.h:70-184): the Callback*Eigen methods append stamped poses,
+    Save() synchronises the two vectors by time (One2OneCorrespondance through sync_trajectories) and writes the five files
+    of EvalTrajectory::Save (:265-315).  A stamped pose is (pose, cov, t): a KITTI row [12] (or a 3 x 4 / 4 x 4 matrix),
+    a 6 x 6 covariance or None (zeros), and the stamp in nanoseconds (ros::Time::toNSec())."""
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx
+        self.est_vek, self.gt_vek = [], []
+
+    @staticmethod
+    def _stamped(p):
+        pose, cov, t = p
+        pose = np.asarray(pose, np.float64)
+        pose = pose.reshape(-1)[:12].copy() if pose.size in (12, 16) else None
+        if pose is None:
+            raise L.CfearError(L.ERR_INVALID_ARGUMENT, "a pose is a KITTI row [12], or a 3 x 4 or 4 x 4 matrix")
+        cov = np.zeros(36) if cov is None else np.asarray(cov, np.float64).reshape(36).copy()
+        return pose, cov, int(t)
+
+    def CallbackEigen(self, Test, Tgt):
+        self.CallbackESTEigen(Test)
+        self.CallbackGTEigen(Tgt)
+
+    def CallbackGTEigen(self, Tgt):
+        self.gt_vek.append(self._stamped(Tgt))
+
+    def CallbackESTEigen(self, Test):
+        self.est_vek.append(self._stamped(Test))
+
+    def GetSize(self):
+        return min(len(self.gt_vek), len(self.est_vek))
+
+    def GetGtVek(self):
+        """-> [(stamp ns, (x, y, theta))]: the pairs AddGroundTruth of the C++ mirror takes; the poses are loop_stats' gt_xyt.
+        After Save() the vector is the interpolated one, so its stamps are the estimate's (offline_odometry.cpp:134-137)."""
+        return [(t, (p[3], p[7], math.atan2(p[4], p[0]))) for p, _, t in self.gt_vek]
+
+    @staticmethod
+    def _arrays(vek):
+        n = len(vek)
+        return (np.array([p for p, _, _ in vek], np.float64).reshape(n, 12), np.array([c for _, c, _ in vek], np.float64).reshape(n, 36),
+                np.array([t for _, _, t in vek], np.int64))
+
+    def Interpolate(self, t):
+        """Interpolate(t, Tinterpolated) (eval_trajectory.h:141-144): -> (found, (pose, cov, t)); the search starts from the
+        first ground-truth pose, and the covariance is that of the pose before t (:455)."""
+        gt, cov, gs = self._arrays(self.gt_vek)
+        r = sync_trajectories(None, [np.array([t], np.int64)], [gt], [gs], mode="independent", ctx=self.ctx)
+        if r.counts[0] == 0:
+            return False, None
+        return True, (r.gt[0].copy(), cov[r.rows["gt_index"][0]].copy(), int(t))
+
+    def Save(self, est_dir, gt_dir, name):
+        """EvalTrajectory::Save (:265-315): est_dir/name, est_dir/tum_name, est_dir/cov_name and, with a ground truth,
+        gt_dir/name and gt_dir/tum_name, after One2OneCorrespondance -- which also replaces the two vectors by the
+        synchronised ones.  -> the paths written."""
+        if not self.est_vek and not self.gt_vek:
+            raise L.CfearError(L.ERR_INVALID_ARGUMENT, "Nothing to evaluate")
+        est, cov, es = self._arrays(self.est_vek)
+        gt, gcov, gs = self._arrays(self.gt_vek)
+        if len(self.gt_vek):
+            r = sync_trajectories([est], [es], [gt], [gs], mode="chained", ctx=self.ctx)
+            n = int(r.counts[0])
+            rows = r.rows[:n]
+            est, cov, es = r.est[:n], cov[rows["est_index"]], r.stamps[:n]
+            gt, gcov = r.gt[:n], gcov[rows["gt_index"]]
+            self.est_vek = [(est[i].copy(), cov[i].copy(), int(es[i])) for i in range(n)]
+            self.gt_vek = [(gt[i].copy(), gcov[i].copy(), int(es[i])) for i in range(n)]
+        written = []
+        os.makedirs(est_dir, exist_ok=True)
+        if len(gs):
+            os.makedirs(gt_dir, exist_ok=True)
+            written += [os.path.join(gt_dir, name), os.path.join(gt_dir, "tum_" + name)]
+            kitti_write(written[0], gt)
+            tum_write(written[1], gt, es)
+        paths = [os.path.join(est_dir, name), os.path.join(est_dir, "tum_" + name), os.path.join(est_dir, "cov_" + name)]
+        kitti_write(paths[0], est)
+        tum_write(paths[1], est, es)
+        cov_write(paths[2], cov, es)
+        return written + paths
 
     @staticmethod
     def MatToString(pose):
@@ -2907,11 +2988,106 @@ def kitti_from_xyt(xyt):
     return out
 
 
-def eval_trajectories(est, gt, lengths=None, step_size=10, alignment="6dof", want_rows=True, par=None, ctx=None):
+def _stamped_file(fn, path, values, width, stamps):
+    values = np.ascontiguousarray(values, np.float64).reshape(-1, width)
+    stamps = np.ascontiguousarray(stamps, np.int64).reshape(-1)
+    if stamps.shape[0] != values.shape[0]:
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "%s(%s): %d stamps for %d records" % (fn, path, stamps.shape[0], values.shape[0]))
+    rc = getattr(L.lib(), fn)(os.fsencode(path), values.ctypes.data, stamps.ctypes.data, values.shape[0])
+    if rc != L.OK:
+        raise L.CfearError(rc, "%s(%s)" % (fn, path))
+
+
+def tum_write(path, poses, stamps):
+    """EvalTrajectory::WriteTUM (eval_trajectory.cpp:185-211): `sec.nsec x y z qx qy qz qw` per pose; stamps in nanoseconds."""
+    _stamped_file("cfear_tum_write", path, poses, 12, stamps)
+
+
+def cov_write(path, cov, stamps):
+    """EvalTrajectory::WriteCov (eval_trajectory.cpp:214-232): the stamp and the 36 entries of the 6 x 6 covariance per line."""
+    _stamped_file("cfear_cov_write", path, cov, 36, stamps)
+
+
+class SyncResult:
+    """What sync_trajectories returns: est, gt [N, 12], stamps [N] and rows [N] (L.SYNC_ROW_DTYPE; on the device a uint8
+    [N, 16] tensor, rows_host() reads it back) hold pair t's counts[t] kept rows from offsets[t] on; offsets and counts are
+    host arrays.  eval_trajectories(r.est, r.gt, lengths=r.counts, offsets=r.offsets) scores it as it is."""
+
+    def __init__(self, est, gt, stamps, rows, counts, offsets):
+        self.est, self.gt, self.stamps, self.rows, self.counts, self.offsets = est, gt, stamps, rows, counts, offsets
+
+    def rows_host(self):
+        return self.rows.cpu().numpy().view(L.SYNC_ROW_DTYPE).reshape(-1) if _is_torch(self.rows) else self.rows
+
+    def pair(self, t):
+        """Pair t's kept rows as host arrays: dict(est, gt, stamps, rows)."""
+        sl = slice(int(self.offsets[t]), int(self.offsets[t]) + int(self.counts[t]))
+        host = lambda x: None if x is None else (x[sl].cpu().numpy() if _is_torch(x) else x[sl])
+        return dict(est=host(self.est), gt=host(self.gt), stamps=host(self.stamps), rows=self.rows_host()[sl])
+
+
+def sync_trajectories(est, est_stamps, gt, gt_stamps, mode="chained", ctx=None):
+    """EvalTrajectory's timestamp synchronisation for a batch of (estimate, ground truth) pairs in one device call
+    (cfear_sync_trajectories): every estimate keeps the ground truth interpolated at its stamp, estimates that no two
+    ground-truth poses bracket are dropped.  mode "chained": One2OneCorrespondance (eval_trajectory.cpp:400-423);
+    "independent": Interpolate(t, out) per stamp (eval_trajectory.h:141-144).
+
+    est, gt: lists (one entry per pair) of [n, 12] KITTI rows, est_stamps, gt_stamps: lists of [n] int64 nanoseconds; all
+    NumPy arrays, or all torch CUDA tensors (float64 / int64).  est may be None (labelling stamps).  -> SyncResult, on the
+    side the inputs are on."""
+    if mode not in L.SYNC_MODE:
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "unknown mode %r" % (mode,))
+    n_traj = len(est_stamps)
+    if len(gt) != n_traj or len(gt_stamps) != n_traj or (est is not None and len(est) != n_traj):
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "est, est_stamps, gt and gt_stamps must hold one entry per pair")
+    everything = list(est_stamps) + list(gt) + list(gt_stamps) + (list(est) if est is not None else [])
+    device = any(_is_torch(x) for x in everything)
+    if device and not all(_is_torch(x) for x in everything):
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "poses and stamps must all be torch CUDA tensors or all be host arrays")
+    if device:
+        import torch
+        dev = everything[0].device
+        for x in everything:
+            if not x.is_cuda or x.dtype not in (torch.float64, torch.int64):
+                raise L.CfearError(L.ERR_INVALID_ARGUMENT, "float64 poses and int64 stamps on the device are needed, got %s on %s" % (x.dtype, x.device))
+        cat = lambda xs, w, dt: (torch.cat([x.reshape(-1, w) if w else x.reshape(-1) for x in xs]).contiguous() if xs
+                                 else torch.zeros((0, w) if w else (0,), dtype=dt, device=dev))
+        zeros = lambda shape, dt: torch.zeros(shape, dtype={np.float64: torch.float64, np.int64: torch.int64, np.uint8: torch.uint8}[dt], device=dev)
+        f64, i64 = torch.float64, torch.int64
+    else:
+        cat = lambda xs, w, dt: (np.ascontiguousarray(np.concatenate([np.asarray(x, dt).reshape((-1, w) if w else (-1,)) for x in xs]))
+                                 if xs else np.zeros((0, w) if w else (0,), dt))
+        zeros = lambda shape, dt: np.zeros(shape, dt)
+        f64, i64 = np.float64, np.int64
+    es, gs = cat(list(est_stamps), 0, i64), cat(list(gt_stamps), 0, i64)
+    e = None if est is None else cat(list(est), 12, f64)
+    g = cat(list(gt), 12, f64)
+    le = np.array([int(x.shape[0]) for x in est_stamps], np.int32)
+    lg = np.array([int(x.shape[0]) for x in gt_stamps], np.int32)
+    if g.shape[0] != int(lg.sum()) or (e is not None and e.shape[0] != int(le.sum())):
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "a pair's poses and stamps differ in length")
+    n = int(le.sum())
+    offsets = np.zeros(n_traj, np.int64)
+    offsets[1:] = np.cumsum(le[:-1])
+    e_out = None if e is None else zeros((n, 12), np.float64)
+    g_out, s_out = zeros((n, 12), np.float64), zeros((n,), np.int64)
+    rows = zeros((n, 16), np.uint8) if device else np.zeros(n, L.SYNC_ROW_DTYPE)
+    counts = np.zeros(n_traj, np.int32)
+    ctx = ctx or default_context()
+    if device:
+        _torch_ready(ctx, es, gs, g, g_out, s_out, rows)
+    ctx.check(ctx._lib.cfear_sync_trajectories(ctx.h, L.SYNC_MODE[mode], _ptr(e)[0], _ptr(es)[0], None, le.ctypes.data, _ptr(g)[0], _ptr(gs)[0],
+                                               None, lg.ctypes.data, n_traj, _ptr(e_out)[0], _ptr(g_out)[0], _ptr(s_out)[0], _ptr(rows)[0],
+                                               counts.ctypes.data))
+    return SyncResult(e_out, g_out, s_out, rows, counts, offsets)
+
+
+def eval_trajectories(est, gt, lengths=None, step_size=10, alignment="6dof", want_rows=True, par=None, ctx=None, offsets=None):
     """The KITTI odometry metric of a batch of (estimate, ground truth) pairs in one call (cfear_eval_trajectories).
 
     est, gt: lists of [n_i, 12] arrays (one per pair), or one [N, 12] array / torch CUDA tensor each holding the pairs one
-    after the other with `lengths` [n_traj] (a single pair when lengths is None).  Returns (summaries, rows): structured
+    after the other with `lengths` [n_traj] (a single pair when lengths is None), or pair t at offsets[t] when `offsets`
+    [n_traj] is given (sync_trajectories' layout).  Returns (summaries, rows): structured
     arrays of L.EVAL_SUMMARY_DTYPE [n_traj] and L.EVAL_ROW_DTYPE [n_rows] (None unless want_rows); figures in radians and
     fractions (write_result's conversions: include/cfear_hip.h).  A pair whose two trajectories differ in length, one with
     fewer than 2 poses, step_size < 1 and the scale / 7dof alignments raise CfearError(ERR_INVALID_ARGUMENT)."""
@@ -2920,6 +3096,8 @@ def eval_trajectories(est, gt, lengths=None, step_size=10, alignment="6dof", wan
     if isinstance(est, (list, tuple)):
         if not isinstance(gt, (list, tuple)) or len(gt) != len(est):
             raise L.CfearError(L.ERR_INVALID_ARGUMENT, "est and gt must hold the same number of trajectories")
+        if offsets is not None:
+            raise L.CfearError(L.ERR_INVALID_ARGUMENT, "offsets address one flat array: lists of trajectories follow each other")
         est = [np.asarray(e, np.float64).reshape(-1, 12) for e in est]
         gt = [np.asarray(g, np.float64).reshape(-1, 12) for g in gt]
         le = np.array([e.shape[0] for e in est], np.int32)
@@ -2946,9 +3124,14 @@ def eval_trajectories(est, gt, lengths=None, step_size=10, alignment="6dof", wan
         lengths = np.array([n_e], np.int32) if lengths is None else np.ascontiguousarray(lengths, np.int32)
         lg = lengths if n_g == n_e else np.array([n_g], np.int32)
         rc = lib.cfear_eval_check(C.byref(p), lengths.ctypes.data, lg.ctypes.data, len(lengths))
-        if rc != L.OK or n_e != n_g or int(lengths.sum()) != n_e or len(lg) != len(lengths):
+        if offsets is not None:
+            offsets = np.ascontiguousarray(offsets, np.int64)
+            inside = len(offsets) == len(lengths) and (offsets >= 0).all() and (offsets + lengths <= n_e).all()
+        else:
+            inside = int(lengths.sum()) == n_e
+        if rc != L.OK or n_e != n_g or not inside or len(lg) != len(lengths):
             raise L.CfearError(L.ERR_INVALID_ARGUMENT, "evaluation refused: step_size >= 1, alignment none / 6dof, est and gt "
-                               "of one shape, lengths >= 2 that add up to it")
+                               "of one shape, lengths >= 2 that add up to it (or lie inside it from `offsets` on)")
     ctx = ctx or default_context()
     n_traj = len(lengths)
     summaries = np.zeros(n_traj, L.EVAL_SUMMARY_DTYPE)
@@ -2958,7 +3141,8 @@ def eval_trajectories(est, gt, lengths=None, step_size=10, alignment="6dof", wan
         cap = int(sum((int(n) + p.step_size - 1) // p.step_size for n in lengths)) * L.EVAL_NUM_LENGTHS
         rows = np.zeros(max(cap, 1), L.EVAL_ROW_DTYPE)
     n_rows = C.c_int64()
-    ctx.check(ctx._lib.cfear_eval_trajectories(ctx.h, _ptr(est)[0], _ptr(gt)[0], None, lengths.ctypes.data, n_traj, C.byref(p),
+    ctx.check(ctx._lib.cfear_eval_trajectories(ctx.h, _ptr(est)[0], _ptr(gt)[0], None if offsets is None else offsets.ctypes.data,
+                                               lengths.ctypes.data, n_traj, C.byref(p),
                                                summaries.ctypes.data, rows.ctypes.data if want_rows else None, cap,
                                                C.byref(n_rows)))
     return summaries, (rows[:n_rows.value] if want_rows else None)

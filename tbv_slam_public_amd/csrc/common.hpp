@@ -85,6 +85,7 @@ enum WsSlot : int {
   kWsCartMap = 22,        // the fixed-point polar -> Cartesian map of the last geometry (cfear_ctx::cart_map_*)
   kWsClosure = 23,        // vicinity closure: staged positions, steps and motions, the block table, staged candidates
   kWsLoopEval = 24,       // loop rows and curves: staged graphs, candidates, scores and curves, job table, sort and scan scratch
+  kWsTrajSync = 25,       // trajectory synchronisation: staged poses and stamps, pair and block tables, ranges, staged outputs
 };
 
 struct cfear_ctx {
@@ -97,7 +98,7 @@ struct cfear_ctx {
   std::vector<Event> event_pool;
   // grow-only device workspaces (indexed by WsSlot so stages of one pipeline do not alias)
   struct Ws { DevBuf<void> p; size_t bytes = 0; };
-  Ws ws[25];
+  Ws ws[26];
   // pinned host staging for small read-backs
   PinnedBuf<char> pinned;
   size_t pinned_bytes = 0;

@@ -5,13 +5,16 @@
 
 #include "common.hpp"
 
+// what a call refused before it needed a context (ctx == NULL) leaves for cfear_last_error(NULL), per host thread
+static thread_local std::string no_ctx_error;
+
 int cfear_set_error(cfear_ctx* ctx, int status, const char* fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(buf, sizeof(buf), fmt, ap);
   va_end(ap);
-  if (ctx) ctx->last_error = buf;
+  (ctx ? ctx->last_error : no_ctx_error) = buf;
   return status;
 }
 
@@ -435,7 +438,7 @@ int cfear_ctx_synchronize(cfear_ctx* ctx) {
   return CFEAR_OK;
 }
 
-const char* cfear_last_error(const cfear_ctx* ctx) { return ctx ? ctx->last_error.c_str() : ""; }
+const char* cfear_last_error(const cfear_ctx* ctx) { return ctx ? ctx->last_error.c_str() : no_ctx_error.c_str(); }
 
 int cfear_ctx_profile_enable(cfear_ctx* ctx, int enable) {
   if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
