@@ -1594,6 +1594,80 @@ int cfear_loop_curves_batch(cfear_ctx* ctx, const int64_t* row_offsets, const ui
                             double* roc_thr, double* pr_precision, double* pr_recall, double* pr_thr,
                             cfear_loop_curves_result* results, int32_t* failed_experiment);
 
+/* ---- after the path: finishing a batch of pose graphs (Align, graph.txt, the trajectory files, the map) ----------------
+ * What every run of the reference's SLAM executables ends in (tbv_slam/src/tbv_slam_offline.cpp:248-266): graph->Align(),
+ * graph->SaveGraphString(), graph->OutputGraph(), and the map PoseGraphVis::ProcessFrame publishes on the way
+ * (tbv_slam/src/tbv_slam/posegraph.cpp, cited as :line).  csrc/graphfinish.hip, DESIGN.md section 4.17.  The batch layout
+ * is cfear_pgo_solve_batch's: flat per-node arrays, graph g owns nodes [node_offsets[g], node_offsets[g + 1]) in ascending
+ * id order; node_offsets (host, n_graphs + 1 entries) runs from 0 to n_nodes without descending.
+ *
+ * cfear_graph_align_batch: PoseGraph::Align (:235-263) per graph.
+ *   A = Tgt.p, B = T.p of the nodes with has_gt, in node order; best_fit_transform(A, B) (cfear_radarodometry/src/
+ *   cfear_radarodometry/eval_trajectory.cpp:343-395): the centroids (sums divided by max(rows, 1)), H = sum (a - cA)(b - cB)^T,
+ *   R = V U^T of its SVD with the third row of V^T negated when det R < 0, t = cB - R cA.  The sums are split over the lanes
+ *   of one workgroup in an order the graph alone fixes; the SVD is the evaluator's host routine (cfear_eval_trajectories).
+ *   Tgtalign = the general inverse of [R | t] (Affine3d::inverse(): cofactors times 1 / det, t' = -(R' t)); every node of
+ *   the graph, with or without ground truth, becomes PoseEigToCeres(Tgtalign * GetPose()) (types.cpp:25-38): Eigen 3.3's
+ *   toRotationMatrix, the product (a0 b0 + a1 b1) + a2 b2 (+ t), Eigen 3.3's matrix -> quaternion assignment (the trace
+ *   branch when the trace is positive, else the largest diagonal entry by m11 > m00, then m22 > m(i,i)), then normalize():
+ *   every coefficient divided by sqrt((xx + zz) + (yy + ww)).  The rewrite happens also when Tgtalign is the identity.
+ *   ate = sum |Tgt.p - p_new| / max(n_gt, 1) over the nodes with ground truth: a mean, not an RMS.
+ *   H exactly zero (no or one node with ground truth, or all of them at one place): R = I, t = cB - cA, CFEAR_OK, as the
+ *   reference's JacobiSVD of a zero matrix returns identities.  H of rank 1 (all ground-truth positions on one line): the
+ *   reference's result depends on the SVD implementation, so the graph's status is CFEAR_ERR_SOLVER, its poses are left
+ *   untouched, align is the identity and ate is that of the untouched poses; the other graphs are not affected and the call
+ *   returns CFEAR_OK.  A graph's poses and summary are bit-identical whatever else the batch holds and wherever it sits.
+ * poses (in / out), gt and has_gt hold n_nodes entries and are all host or all device memory (device poses 8-byte aligned);
+ * summaries [n_graphs] is host memory; the call synchronises (the SVDs are host code).                                   */
+typedef struct cfear_graph_align_summary {
+  double align[12];                     /* Tgtalign as [r | t], row-major 3 x 4: what every pose was left-multiplied by */
+  double ate;
+  int32_t n_gt;                         /* nodes with ground truth                                                      */
+  int32_t status;                       /* CFEAR_OK or CFEAR_ERR_SOLVER                                                 */
+} cfear_graph_align_summary;            /* 112 bytes */
+int cfear_graph_align_batch(cfear_ctx* ctx, cfear_pose3d* poses, const cfear_pose3d* gt, const uint8_t* has_gt,
+                            const int64_t* node_offsets, int64_t n_nodes, int32_t n_graphs, cfear_graph_align_summary* summaries);
+
+/* cfear_graph_map_batch: the two maps of PoseGraphVis::ProcessFrame (:539-584) per graph.  The nodes whose ordinal within the
+ * graph is a multiple of skip_frames are taken in node order and their cloud_peaks_ points appended in cloud order, each
+ * through pcl::transformPointCloud<PointXYZI, double> with GetPose(): float(((m0 x + m1 y) + m2 z) + m3) for all three rows,
+ * the intensity copied.  The ground-truth map takes the same points of the selected nodes that have ground truth through
+ * PoseCeresToEig(Tgt) (the reference's Tgtalign there is the identity, :566).
+ * xyzi [n_points][4] holds every node's cloud, node k's points at [cloud_offsets[k], cloud_offsets[k + 1]); cloud_offsets
+ * (host, n_nodes + 1 entries) runs from 0 to n_points without descending; an empty cloud is legal.  poses, gt, has_gt and
+ * xyzi are all host or all device memory, and so are map [map_cap][4] and map_gt [map_gt_cap][4] (of either kind; device
+ * clouds and maps 16-byte aligned; map_gt is not used without want_gt_map).  summaries [n_graphs] (host) receives the point
+ * range of each graph in the two maps; the graphs follow each other in batch order.  The ranges are computed on the host
+ * from the offsets (has_gt is read back first when it is device memory) and written BEFORE anything else happens: a map
+ * larger than its capacity gives CFEAR_ERR_CAPACITY with the summaries complete and nothing written to either map, so that
+ * the caller can size the buffers (map may be NULL with map_cap 0) and call again.  Refused with
+ * CFEAR_ERR_INVALID_ARGUMENT: skip_frames < 1 (the reference would compute % 0), offset tables that do not run from 0 to the
+ * array lengths without descending, null pointers, buffers of mixed kinds.  One thread moves one point; a workgroup moves
+ * one tile of CFEAR_GRAPH_MAP_TILE points of one node (exported so that tests can straddle it).                           */
+#define CFEAR_GRAPH_MAP_TILE 256
+typedef struct cfear_graph_map_params {
+  int32_t skip_frames;                  /* 1: every node (PoseGraphVis::Parameters::skip_frames)                        */
+  int32_t want_gt_map;                  /* 1                                                                            */
+} cfear_graph_map_params;               /* 8 bytes */
+typedef struct cfear_graph_map_summary {
+  int64_t map_offset, map_points;       /* the graph's points in map                                                    */
+  int64_t map_gt_offset, map_gt_points; /* ... and in map_gt (0, 0 without want_gt_map)                                 */
+} cfear_graph_map_summary;              /* 32 bytes */
+int cfear_graph_map_batch(cfear_ctx* ctx, const cfear_pose3d* poses, const cfear_pose3d* gt, const uint8_t* has_gt,
+                          const int64_t* node_offsets, int64_t n_nodes, int32_t n_graphs, const float* xyzi,
+                          const int64_t* cloud_offsets, int64_t n_points, const cfear_graph_map_params* par, float* map,
+                          int64_t map_cap, float* map_gt, int64_t map_gt_cap, cfear_graph_map_summary* summaries);
+
+/* Host writers, no context.  cfear_graph_string_write: PoseGraph::SaveGraphString (:177-187): per node RadarScan::ToString
+ * (types.cpp:93-102) -- the 12 numbers of MatToString(GetPose().matrix()) (std::fixed, 6 decimals, one space between), a
+ * space, std::to_string(stamp_) and a newline -- and the std::endl SaveGraphString appends: every node line is followed by
+ * an empty line.  cfear_graph_output_write: PoseGraph::OutputGraph (:201-234): only the nodes with ground truth are
+ * written, the pose to est_path and Tgt to gt_path (the reference's local names mgt / mest are swapped, the files are not);
+ * when no node has ground truth every pose goes to est_path and gt_path is created empty.                               */
+int cfear_graph_string_write(const char* path, const cfear_pose3d* poses, const uint64_t* stamps, int64_t n);
+int cfear_graph_output_write(const char* est_path, const char* gt_path, const cfear_pose3d* poses, const cfear_pose3d* gt,
+                             const uint8_t* has_gt, int64_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1793,3 +1793,92 @@ class EvalTrajectory {
   poseStampedVector est_vek, gt_vek;
 };
 }  // namespace CFEAR_Radarodometry
+
+// The end of a pose-graph run (tbv_slam_offline.cpp:248-266): graph->Align(), graph->SaveGraphString(), graph->OutputGraph(),
+// and the maps PoseGraphVis::ProcessFrame builds, over the PoseGraph records SolvePoseGraphs solved.  GraphTruth holds Tgt and
+// has_Tgt_ of every node (empty: no node has ground truth).  AlignPoseGraphs (cfear_graph_align_batch) replaces every graph's
+// poses in ONE device call; a graph whose ground-truth positions lie on one line keeps its poses and reports CFEAR_ERR_SOLVER
+// in its own summary.  MapPoseGraphs (cfear_graph_map_batch) takes one cloud_peaks_ ([k][4] floats, flattened) per node.
+struct GraphTruth {
+  std::vector<cfear_pose3d> gt;
+  std::vector<uint8_t> has_gt;
+};
+struct GraphMaps {
+  std::vector<float> map, map_gt;                    // [points][4]
+  std::vector<cfear_graph_map_summary> ranges;       // per graph: its points in the two maps
+};
+namespace graph_finish_detail {
+inline void Flatten(const std::vector<PoseGraph>& graphs, const std::vector<GraphTruth>& truth, std::vector<cfear_pose3d>& poses,
+                    std::vector<cfear_pose3d>& gt, std::vector<uint8_t>& has, std::vector<int64_t>& off) {
+  if (truth.size() != graphs.size()) throw CFEAR_Radarodometry::CfearError(CFEAR_ERR_INVALID_ARGUMENT, "one GraphTruth per graph");
+  const cfear_pose3d ident{{0, 0, 0}, {0, 0, 0, 1}};
+  off.assign(1, 0);
+  for (size_t g = 0; g < graphs.size(); g++) {
+    const size_t n = graphs[g].poses.size();
+    const bool none = truth[g].gt.empty() && truth[g].has_gt.empty();
+    if (!none && (truth[g].gt.size() != n || truth[g].has_gt.size() != n))
+      throw CFEAR_Radarodometry::CfearError(CFEAR_ERR_INVALID_ARGUMENT, "one ground-truth pose and one flag per node");
+    poses.insert(poses.end(), graphs[g].poses.begin(), graphs[g].poses.end());
+    for (size_t k = 0; k < n; k++) { gt.push_back(none ? ident : truth[g].gt[k]); has.push_back(none ? 0 : truth[g].has_gt[k]); }
+    off.push_back((int64_t)poses.size());
+  }
+}
+}  // namespace graph_finish_detail
+inline std::vector<cfear_graph_align_summary> AlignPoseGraphs(CFEAR_Radarodometry::Context& ctx, std::vector<PoseGraph>& graphs,
+                                                              const std::vector<GraphTruth>& truth) {
+  std::vector<cfear_pose3d> poses, gt;
+  std::vector<uint8_t> has;
+  std::vector<int64_t> off;
+  graph_finish_detail::Flatten(graphs, truth, poses, gt, has, off);
+  std::vector<cfear_graph_align_summary> out(graphs.size());
+  ctx.check(cfear_graph_align_batch(ctx.get(), poses.data(), gt.data(), has.data(), off.data(), (int64_t)poses.size(), (int32_t)graphs.size(),
+                                    out.data()));
+  for (size_t g = 0; g < graphs.size(); g++) std::copy(poses.begin() + off[g], poses.begin() + off[g + 1], graphs[g].poses.begin());
+  return out;
+}
+inline GraphMaps MapPoseGraphs(CFEAR_Radarodometry::Context& ctx, const std::vector<PoseGraph>& graphs, const std::vector<GraphTruth>& truth,
+                               const std::vector<std::vector<std::vector<float>>>& clouds, int skip_frames = 1, bool want_gt_map = true) {
+  std::vector<cfear_pose3d> poses, gt;
+  std::vector<uint8_t> has;
+  std::vector<int64_t> off, coff(1, 0);
+  graph_finish_detail::Flatten(graphs, truth, poses, gt, has, off);
+  if (clouds.size() != graphs.size()) throw CFEAR_Radarodometry::CfearError(CFEAR_ERR_INVALID_ARGUMENT, "one list of clouds per graph");
+  std::vector<float> xyzi;
+  for (size_t g = 0; g < graphs.size(); g++) {
+    if (clouds[g].size() != graphs[g].poses.size()) throw CFEAR_Radarodometry::CfearError(CFEAR_ERR_INVALID_ARGUMENT, "one cloud per node");
+    for (const std::vector<float>& c : clouds[g]) {
+      if (c.size() % 4) throw CFEAR_Radarodometry::CfearError(CFEAR_ERR_INVALID_ARGUMENT, "a cloud holds 4 floats per point");
+      xyzi.insert(xyzi.end(), c.begin(), c.end());
+      coff.push_back((int64_t)(xyzi.size() / 4));
+    }
+  }
+  GraphMaps out;
+  out.ranges.resize(graphs.size());
+  const cfear_graph_map_params par{skip_frames, want_gt_map ? 1 : 0};
+  auto call = [&](float* m, int64_t cap, float* mg, int64_t cap_gt) {
+    return cfear_graph_map_batch(ctx.get(), poses.data(), gt.data(), has.data(), off.data(), (int64_t)poses.size(), (int32_t)graphs.size(), xyzi.data(),
+                                 coff.data(), (int64_t)(xyzi.size() / 4), &par, m, cap, mg, cap_gt, out.ranges.data());
+  };
+  const int rc = call(nullptr, 0, nullptr, 0);       // the sizes: CFEAR_ERR_CAPACITY with the ranges complete
+  if (rc != CFEAR_ERR_CAPACITY) ctx.check(rc);
+  int64_t n = 0, n_gt = 0;
+  for (const cfear_graph_map_summary& s : out.ranges) { n += s.map_points; n_gt += s.map_gt_points; }
+  out.map.resize((size_t)n * 4);
+  out.map_gt.resize((size_t)n_gt * 4);
+  ctx.check(call(out.map.data(), n, out.map_gt.data(), n_gt));
+  return out;
+}
+inline void SaveGraphString(const std::string& path, const PoseGraph& graph, const std::vector<uint64_t>& stamps) {
+  if (stamps.size() != graph.poses.size()) throw CFEAR_Radarodometry::CfearError(CFEAR_ERR_INVALID_ARGUMENT, "one stamp per node");
+  const int rc = cfear_graph_string_write(path.c_str(), graph.poses.data(), stamps.data(), (int64_t)stamps.size());
+  if (rc != CFEAR_OK) throw CFEAR_Radarodometry::CfearError(rc, path);
+}
+inline void OutputGraph(const std::string& est_path, const std::string& gt_path, const PoseGraph& graph, const GraphTruth& truth) {
+  const size_t n = graph.poses.size();
+  const bool none = truth.gt.empty() && truth.has_gt.empty();
+  if (!none && (truth.gt.size() != n || truth.has_gt.size() != n))
+    throw CFEAR_Radarodometry::CfearError(CFEAR_ERR_INVALID_ARGUMENT, "one ground-truth pose and one flag per node");
+  const int rc = cfear_graph_output_write(est_path.c_str(), gt_path.c_str(), graph.poses.data(), none ? nullptr : truth.gt.data(),
+                                          none ? nullptr : truth.has_gt.data(), (int64_t)n);
+  if (rc != CFEAR_OK) throw CFEAR_Radarodometry::CfearError(rc, est_path + ", " + gt_path);
+}

@@ -301,6 +301,7 @@ EXPORTS = [
     "cfear_closure_params_default", "cfear_closure_candidates_batch",
     "cfear_loop_stats_params_default", "cfear_loop_stats_batch", "cfear_loop_curves_params_default", "cfear_loop_curves_batch",
     "cfear_sync_trajectories", "cfear_tum_write", "cfear_cov_write",
+    "cfear_graph_align_batch", "cfear_graph_map_batch", "cfear_graph_string_write", "cfear_graph_output_write",
 ]
 
 PIPE_GRAPH, PIPE_TIMING = 1, 2      # enum { CFEAR_PIPE_GRAPH, CFEAR_PIPE_TIMING }
@@ -441,6 +442,17 @@ LOOP_CURVES_RESULT_DTYPE = np.dtype([("auc", "<f8"), ("accuracy", "<f8"), ("prec
                                      ("n_pr", "<i4"), ("status", "<i4")])
 assert C.sizeof(LoopStatsParams) == 40 and C.sizeof(LoopCurvesParams) == 16
 assert LOOP_CANDIDATE_DTYPE.itemsize == 40 and LOOP_ROW_DTYPE.itemsize == 88 and LOOP_CURVES_RESULT_DTYPE.itemsize == 96
+
+GRAPH_MAP_TILE = 256                              # CFEAR_GRAPH_MAP_TILE
+
+
+class GraphMapParams(C.Structure):      # cfear_graph_map_params
+    _fields_ = [("skip_frames", C.c_int32), ("want_gt_map", C.c_int32)]
+
+
+GRAPH_ALIGN_SUMMARY_DTYPE = np.dtype([("align", "<f8", (12,)), ("ate", "<f8"), ("n_gt", "<i4"), ("status", "<i4")])
+GRAPH_MAP_SUMMARY_DTYPE = np.dtype([("map_offset", "<i8"), ("map_points", "<i8"), ("map_gt_offset", "<i8"), ("map_gt_points", "<i8")])
+assert C.sizeof(GraphMapParams) == 8 and GRAPH_ALIGN_SUMMARY_DTYPE.itemsize == 112 and GRAPH_MAP_SUMMARY_DTYPE.itemsize == 32
 
 _LIB = None
 
@@ -634,5 +646,10 @@ def lib():
     L.cfear_loop_curves_params_default.restype = None
     L.cfear_loop_curves_batch.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int32, C.POINTER(LoopCurvesParams), vp, vp, vp, vp, vp, vp,
                                           vp, C.POINTER(C.c_int32)]
+    L.cfear_graph_align_batch.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int32, vp]
+    L.cfear_graph_map_batch.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int32, vp, vp, C.c_int64, C.POINTER(GraphMapParams), vp,
+                                        C.c_int64, vp, C.c_int64, vp]
+    L.cfear_graph_string_write.argtypes = [C.c_char_p, vp, vp, C.c_int64]
+    L.cfear_graph_output_write.argtypes = [C.c_char_p, C.c_char_p, vp, vp, vp, C.c_int64]
     _LIB = L
     return L

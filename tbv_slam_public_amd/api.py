@@ -3599,3 +3599,197 @@ class LoopClosureEval:
             out.append(d)
         self.models_ = models
         return out
+
+
+# ------------------------------------------------------------------------------------------------
+# finishing a batch of pose graphs: PoseGraph::Align, SaveGraphString, OutputGraph and the maps of
+# PoseGraphVis::ProcessFrame (tbv_slam/src/tbv_slam/posegraph.cpp:177-263, 539-584)
+# ------------------------------------------------------------------------------------------------
+def _finish_graph_arrays(graph, where):
+    """One graph -> (poses [n, 7], gt [n, 7], has_gt [n] uint8).  A graph is a PoseGraph, a list of LoadSimpleGraph node dicts,
+    or a (poses, gt, has_gt) tuple: poses [n, 7] (p, q) or [n, 3] (x, y, theta), gt likewise or None, has_gt [n] or None (all
+    nodes have ground truth when gt is given)."""
+    if isinstance(graph, PoseGraph):
+        return graph.poses, graph.gt, graph.has_gt
+    if isinstance(graph, (list, tuple)) and len(graph) and isinstance(graph[0], dict):
+        ident = np.array([0, 0, 0, 0, 0, 0, 1.0])
+        poses = [nd["T"] for nd in graph]
+        gt = [ident if nd.get("Tgt") is None else nd["Tgt"] for nd in graph]
+        has = [bool(nd.get("has_Tgt", False)) for nd in graph]
+    else:
+        if len(graph) not in (1, 2, 3):
+            raise L.CfearError(L.ERR_INVALID_ARGUMENT, "%s: node dicts, a PoseGraph or a (poses, gt, has_gt) tuple is needed" % where)
+        poses, gt, has = graph[0], (graph[1] if len(graph) > 1 else None), (graph[2] if len(graph) > 2 else None)
+
+    def seven(a, name):
+        a = np.asarray(a, np.float64)
+        if a.ndim != 2 or a.shape[1] not in (3, 7):
+            raise L.CfearError(L.ERR_INVALID_ARGUMENT, "%s: %s must be [n, 7] (p, q) or [n, 3] (x, y, theta), got %s" % (where, name, a.shape))
+        if a.shape[1] == 3:
+            a = np.array([np.concatenate(pose3d_from_xyt(p)) for p in a]).reshape(-1, 7)
+        return np.ascontiguousarray(a)
+    poses = seven(np.zeros((0, 7)) if len(poses) == 0 else poses, "poses")
+    n = poses.shape[0]
+    if gt is None:
+        gt = np.tile(np.array([0, 0, 0, 0, 0, 0, 1.0]), (n, 1))
+        has = np.zeros(n, np.uint8) if has is None else has
+    else:
+        gt = seven(np.zeros((0, 7)) if len(gt) == 0 else gt, "gt")
+    has = np.ones(n, np.uint8) if has is None else (np.asarray(has).reshape(-1) != 0).astype(np.uint8)
+    if gt.shape[0] != n or has.shape[0] != n:
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "%s: %d poses, %d ground-truth poses, %d flags" % (where, n, gt.shape[0], has.shape[0]))
+    return poses, np.ascontiguousarray(gt), np.ascontiguousarray(has)
+
+
+def _finish_batch(graphs):
+    arrs = [_finish_graph_arrays(g, "graph %d" % k) for k, g in enumerate(graphs)]
+    off = np.concatenate([[0], np.cumsum([a[0].shape[0] for a in arrs])]).astype(np.int64)
+    cat = lambda k, shape, dt: (np.ascontiguousarray(np.concatenate([a[k] for a in arrs], 0)) if arrs else np.zeros(shape, dt))
+    return cat(0, (0, 7), np.float64), cat(1, (0, 7), np.float64), cat(2, (0,), np.uint8), off
+
+
+def graph_align_batch(graphs, ctx=None):
+    """cfear_graph_align_batch: PoseGraph::Align (posegraph.cpp:235-263) for every graph of `graphs` (PoseGraph objects,
+    LoadSimpleGraph node lists or (poses, gt, has_gt) tuples, see PoseGraph) in ONE device call.  Returns a list of
+    (poses [n, 7], summary) in the order given; summary: dict(align [3, 4] = the transform every pose was left-multiplied by,
+    ate = the mean distance to the ground truth afterwards, n_gt, status).  A graph whose ground-truth positions lie on one
+    line keeps its poses and reports status L.ERR_SOLVER; the others are not affected.  PoseGraph objects are NOT updated
+    (PoseGraph.Align does that)."""
+    poses, gt, has, off = _finish_batch(graphs)
+    summ = np.zeros(len(off) - 1, L.GRAPH_ALIGN_SUMMARY_DTYPE)
+    ctx = ctx or default_context()
+    ctx.check(ctx._lib.cfear_graph_align_batch(ctx.h, poses.ctypes.data, gt.ctypes.data, has.ctypes.data, off.ctypes.data, int(off[-1]),
+                                               len(off) - 1, summ.ctypes.data))
+    return [(poses[off[g]:off[g + 1]].copy(),
+             dict(align=s["align"].reshape(3, 4).copy(), ate=float(s["ate"]), n_gt=int(s["n_gt"]), status=int(s["status"])))
+            for g, s in enumerate(summ)]
+
+
+def graph_map_batch(graphs, clouds=None, skip_frames=1, want_gt_map=True, ctx=None, device_out=False):
+    """cfear_graph_map_batch: the maps PoseGraphVis::ProcessFrame builds (posegraph.cpp:539-584) for every graph of `graphs` in
+    ONE device call: the cloud_peaks_ of every skip_frames-th node carried into the world by the node's pose, and, with
+    want_gt_map, the same points of the nodes with ground truth carried by Tgt.  clouds: per graph a list of float32 [k, 4]
+    arrays, one per node (None: the graphs' own clouds -- PoseGraph.clouds or the node dicts' cloud_peaks); when every cloud
+    is a torch CUDA tensor the node arrays are uploaded too and the call reads device memory.  device_out: the maps are torch
+    CUDA tensors.  Returns (map [N, 4], map_gt [M, 4] or None, summaries): graph g's points are
+    map[summaries[g]["map_offset"]:][:summaries[g]["map_points"]], likewise map_gt_offset / map_gt_points."""
+    poses, gt, has, off = _finish_batch(graphs)
+    if clouds is None:
+        clouds = []
+        for g in graphs:
+            if isinstance(g, PoseGraph):
+                clouds.append(g.clouds)
+            elif isinstance(g, (list, tuple)) and len(g) and isinstance(g[0], dict):
+                clouds.append([np.zeros((0, 4), np.float32) if nd.get("cloud_peaks") is None else
+                               (nd["cloud_peaks"]["xyzi"] if isinstance(nd["cloud_peaks"], dict) else nd["cloud_peaks"]) for nd in g])
+            else:
+                clouds.append(None)
+    if len(clouds) != len(off) - 1 or any(c is None or len(c) != off[g + 1] - off[g] for g, c in enumerate(clouds)):
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "clouds must hold one [k, 4] array per node of every graph")
+    flat = [c for per_graph in clouds for c in per_graph]
+    device_in = bool(flat) and all(_is_torch(c) for c in flat)
+    if any(_is_torch(c) for c in flat) and not device_in:
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "the clouds must all be torch CUDA tensors or all be host arrays")
+    coff = np.concatenate([[0], np.cumsum([int(c.shape[0]) for c in flat])]).astype(np.int64)
+    ctx = ctx or default_context()
+    if device_in or device_out:
+        import torch
+    if device_in:
+        for c in flat:
+            if c.dtype != torch.float32 or not c.is_cuda or c.dim() != 2 or c.shape[1] != 4:
+                raise L.CfearError(L.ERR_INVALID_ARGUMENT, "float32 [k, 4] CUDA tensors are needed, got %s %s on %s" % (c.dtype, tuple(c.shape), c.device))
+        xyzi = torch.cat(flat).contiguous()
+        d_poses, d_gt, d_has = (torch.from_numpy(a).to(xyzi.device) for a in (poses, gt, has))
+        node_ptrs = (d_poses.data_ptr(), d_gt.data_ptr(), d_has.data_ptr())
+        _torch_ready(ctx, xyzi, d_poses, d_gt, d_has)
+    else:
+        xyzi = (np.ascontiguousarray(np.concatenate([np.asarray(c, np.float32).reshape(-1, 4) for c in flat], 0)) if flat
+                else np.zeros((0, 4), np.float32))
+        node_ptrs = (poses.ctypes.data, gt.ctypes.data, has.ctypes.data)
+    par = L.GraphMapParams(int(skip_frames), int(bool(want_gt_map)))
+    summ = np.zeros(len(off) - 1, L.GRAPH_MAP_SUMMARY_DTYPE)
+
+    def call(m, mg):
+        return ctx._lib.cfear_graph_map_batch(ctx.h, node_ptrs[0], node_ptrs[1], node_ptrs[2], off.ctypes.data, int(off[-1]), len(off) - 1,
+                                              _ptr(xyzi)[0], coff.ctypes.data, int(coff[-1]), C.byref(par), _ptr(m)[0],
+                                              0 if m is None else int(m.shape[0]), _ptr(mg)[0], 0 if mg is None else int(mg.shape[0]),
+                                              summ.ctypes.data)
+    ctx.check(call(None, None), allowed=(L.ERR_CAPACITY,))            # the sizes
+    n_map, n_gt = int(summ["map_points"].sum()), int(summ["map_gt_points"].sum())
+    if device_out:
+        dev = xyzi.device if device_in else torch.device("cuda", ctx.device)
+        m = torch.zeros((n_map, 4), dtype=torch.float32, device=dev)
+        mg = torch.zeros((n_gt, 4), dtype=torch.float32, device=dev) if want_gt_map else None
+        _torch_ready(ctx, m, mg)
+    else:
+        m = np.zeros((n_map, 4), np.float32)
+        mg = np.zeros((n_gt, 4), np.float32) if want_gt_map else None
+    ctx.check(call(m, mg))
+    return m, mg, summ
+
+
+def SaveGraphString(path, poses, stamps):
+    """PoseGraph::SaveGraphString (posegraph.cpp:177-187): per node the 12 numbers of its pose matrix with 6 decimals, a space,
+    the stamp, and an empty line after every node line.  poses [n, 7] (p, q) or [n, 3]; stamps [n] unsigned integers."""
+    poses = _finish_graph_arrays((poses,), "SaveGraphString")[0]
+    stamps = np.ascontiguousarray(stamps, np.uint64).reshape(-1)
+    if stamps.shape[0] != poses.shape[0]:
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "SaveGraphString(%s): %d stamps for %d poses" % (path, stamps.shape[0], poses.shape[0]))
+    rc = L.lib().cfear_graph_string_write(os.fsencode(path), poses.ctypes.data, stamps.ctypes.data, poses.shape[0])
+    if rc != L.OK:
+        raise L.CfearError(rc, "cfear_graph_string_write(%s)" % path)
+
+
+def OutputGraph(est_path, gt_path, poses, gt=None, has_gt=None):
+    """PoseGraph::OutputGraph (posegraph.cpp:201-234): the poses of the nodes with ground truth to est_path and their Tgt to
+    gt_path, one KITTI line each; when no node has ground truth, every pose to est_path and an empty gt_path."""
+    poses, gt, has = _finish_graph_arrays((poses, gt, has_gt), "OutputGraph")
+    rc = L.lib().cfear_graph_output_write(os.fsencode(est_path), os.fsencode(gt_path), poses.ctypes.data, gt.ctypes.data, has.ctypes.data,
+                                          poses.shape[0])
+    if rc != L.OK:
+        raise L.CfearError(rc, "cfear_graph_output_write(%s, %s)" % (est_path, gt_path))
+
+
+class PoseGraph:
+    """The end of tbv_slam's PoseGraph (posegraph.h) over the calls above: Align(), SaveGraphString(path), OutputGraph() and
+    Map().  Fed by LoadSimpleGraph's node dicts (nodes=...), or by arrays: poses [n, 7] as pose_graph_optimize_batch returns
+    them (or [n, 3] planar), gt likewise, has_gt [n], stamps [n], clouds = one float32 [k, 4] peak cloud per node.
+    est_output_dir / gt_output_dir are PoseGraph::Parameters'; OutputGraph writes <dir>/00.txt into each."""
+
+    def __init__(self, nodes=None, poses=None, gt=None, has_gt=None, stamps=None, clouds=None, est_output_dir=".", gt_output_dir=".",
+                 ctx=None):
+        if nodes is not None:
+            self.poses, self.gt, self.has_gt = _finish_graph_arrays(list(nodes), "PoseGraph")
+            stamps = [int(nd.get("stamp", 0)) for nd in nodes] if stamps is None else stamps
+            if clouds is None:
+                clouds = [np.zeros((0, 4), np.float32) if nd.get("cloud_peaks") is None else
+                          (nd["cloud_peaks"]["xyzi"] if isinstance(nd["cloud_peaks"], dict) else nd["cloud_peaks"]) for nd in nodes]
+        else:
+            self.poses, self.gt, self.has_gt = _finish_graph_arrays((poses, gt, has_gt), "PoseGraph")
+        n = self.poses.shape[0]
+        self.stamps = np.zeros(n, np.uint64) if stamps is None else np.ascontiguousarray(stamps, np.uint64).reshape(-1)
+        self.clouds = [np.zeros((0, 4), np.float32)] * n if clouds is None else list(clouds)
+        self.est_output_dir, self.gt_output_dir, self.ctx = est_output_dir, gt_output_dir, ctx
+        self.Tgtalign, self.ate = None, None
+
+    def size(self):
+        return self.poses.shape[0]
+
+    def Align(self):
+        """PoseGraph::Align: the poses are replaced; returns the summary (graph_align_batch), kept as Tgtalign / ate too."""
+        (poses, s), = graph_align_batch([self], self.ctx)
+        self.poses, self.Tgtalign, self.ate = poses, s["align"], s["ate"]
+        return s
+
+    def SaveGraphString(self, path):
+        SaveGraphString(path, self.poses, self.stamps)
+
+    def OutputGraph(self):
+        for d in (self.est_output_dir, self.gt_output_dir):
+            os.makedirs(d, exist_ok=True)
+        OutputGraph(os.path.join(self.est_output_dir, "00.txt"), os.path.join(self.gt_output_dir, "00.txt"), self.poses, self.gt, self.has_gt)
+
+    def Map(self, skip_frames=1, want_gt_map=True, device_out=False):
+        """The maps of PoseGraphVis::ProcessFrame -> (map [N, 4], map_gt [M, 4] or None)."""
+        m, mg, _ = graph_map_batch([self], None, skip_frames, want_gt_map, self.ctx, device_out)
+        return m, mg

@@ -86,6 +86,7 @@ enum WsSlot : int {
   kWsClosure = 23,        // vicinity closure: staged positions, steps and motions, the block table, staged candidates
   kWsLoopEval = 24,       // loop rows and curves: staged graphs, candidates, scores and curves, job table, sort and scan scratch
   kWsTrajSync = 25,       // trajectory synchronisation: staged poses and stamps, pair and block tables, ranges, staged outputs
+  kWsGraphFinish = 26,    // graph alignment and maps: staged poses, flags and clouds, graph, node and tile tables, sums, staged maps
 };
 
 struct cfear_ctx {
@@ -98,7 +99,7 @@ struct cfear_ctx {
   std::vector<Event> event_pool;
   // grow-only device workspaces (indexed by WsSlot so stages of one pipeline do not alias)
   struct Ws { DevBuf<void> p; size_t bytes = 0; };
-  Ws ws[26];
+  Ws ws[27];
   // pinned host staging for small read-backs
   PinnedBuf<char> pinned;
   size_t pinned_bytes = 0;
@@ -402,6 +403,9 @@ struct CoralJob {
 int cfear_coral_launch_device(cfear_ctx* ctx, const CoralJob* d_jobs, int n_jobs, int cap, const cfear_coral_params* par,
                               cfear_coral_result* d_results);
 int cfear_coral_max_points();
+// evaluate.hip's 3 x 3 alignment: s = mean x (3), mean y (3), the covariance sum y x^T row-major (9) -> [r | t] with
+// r = u diag(1, 1, det u det v) v^T and t = mean y - r mean x; false (and r = I) when the second singular value vanishes
+bool cfear_align_from_sums(const double* s, double align[12]);
 
 struct RegLaunchHint {
   bool small_pairs = false;   // every job is a two-scan candidate that fits 20 KB of LDS: the 2-wavefront form, eight per CU
@@ -536,5 +540,14 @@ __device__ __forceinline__ double readlane_f64(double v, int lane) {
 __device__ __forceinline__ double wave_sum_f64(double v) {
   v = row16_sum_f64(v);
   return ((readlane_f64(v, 0) + readlane_f64(v, 16)) + readlane_f64(v, 32)) + readlane_f64(v, 48);
+}
+// Sum over a workgroup of 256 threads (4 wavefronts), the same value in every thread; red = 4 doubles of LDS.  Order: each
+// wave's wave_sum_f64, then the four waves in order (evaluate.hip, graphfinish.hip).
+__device__ __forceinline__ double block_sum(double v, double* red) {
+  v = wave_sum_f64(v);
+  __syncthreads();                                   // the previous sum's readers are done with red
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
 }
 #endif  // __HIPCC__

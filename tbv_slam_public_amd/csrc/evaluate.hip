@@ -112,15 +112,6 @@ __device__ __forceinline__ double rotation_error(const Pose& P) {
   return acos(fmax(fmin(d, 1.0), -1.0));
 }
 
-// Sum over the workgroup (kEvalThreads = 4 wavefronts), the same value in every thread; red = 4 doubles of LDS.
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  v = wave_sum_f64(v);
-  __syncthreads();                                   // the previous sum's readers are done with red
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 __global__ __launch_bounds__(kEvalThreads) void eval_normalise_kernel(EvalArgs a) {
   const int2 blk = a.blocks[blockIdx.x];
   const EvalTraj tr = a.traj[blk.x];
@@ -417,6 +408,9 @@ int check_eval_params(const cfear_eval_params* par) {
   return CFEAR_OK;
 }
 }  // namespace
+
+// the same routine for cfear_graph_align_batch (graphfinish.hip), which sums its own s[15]
+bool cfear_align_from_sums(const double* s, double align[12]) { return align_from_sums(s, align); }
 
 extern "C" void cfear_eval_params_default(cfear_eval_params* p) {
   p->step_size = 10;                                 // eval_odom.py's default --step_size

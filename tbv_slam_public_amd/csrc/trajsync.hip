@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "eigen_quat.hpp"   // sqrt_rn, quat_from_rows: Eigen 3.3 Quaternion(Matrix3d), no normalisation
 
 namespace {
 constexpr int kSyncThreads = 256;
@@ -62,44 +63,6 @@ __host__ __device__ __forceinline__ double to_sec(int64_t ns) {
   return (double)sec + 1e-9 * (double)(ns - sec * kNsPerSec);
 }
 __host__ __device__ __forceinline__ bool stamp_ok(int64_t ns) { return ns >= 0 && ns / kNsPerSec <= kMaxSec; }
-
-__host__ __device__ __forceinline__ double sqrt_rn(double v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __dsqrt_rn(v);
-#else
-  return std::sqrt(v);
-#endif
-}
-
-// Eigen 3.3 Quaternion(Matrix3d), src/Geometry/Quaternion.h quaternionbase_assign_impl<Other, 3, 3>: q = (x, y, z, w), no
-// normalisation.  m is a KITTI row (stride 4).  The trace is the unrolled redux of a 3-vector, m00 + (m11 + m22).
-template <int I>
-__host__ __device__ __forceinline__ void quat_pivot(const double* m, double* q) {
-  constexpr int J = (I + 1) % 3, K = (J + 1) % 3;
-  double t = sqrt_rn(((m[5 * I] - m[5 * J]) - m[5 * K]) + 1.0);
-  q[I] = 0.5 * t;
-  t = 0.5 / t;
-  q[3] = (m[4 * K + J] - m[4 * J + K]) * t;
-  q[J] = (m[4 * J + I] + m[4 * I + J]) * t;
-  q[K] = (m[4 * K + I] + m[4 * I + K]) * t;
-}
-__host__ __device__ __forceinline__ void quat_from_rows(const double* m, double* q) {
-  double t = m[0] + (m[5] + m[10]);
-  if (t > 0.0) {
-    t = sqrt_rn(t + 1.0);
-    q[3] = 0.5 * t;
-    t = 0.5 / t;
-    q[0] = (m[9] - m[6]) * t;
-    q[1] = (m[2] - m[8]) * t;
-    q[2] = (m[4] - m[1]) * t;
-    return;
-  }
-  int i = 0;
-  double mii = m[0];
-  if (m[5] > m[0]) { i = 1; mii = m[5]; }
-  if (m[10] > mii) i = 2;
-  if (i == 0) quat_pivot<0>(m, q); else if (i == 1) quat_pivot<1>(m, q); else quat_pivot<2>(m, q);
-}
 
 struct Pose { double m[12]; };
 __device__ __forceinline__ Pose pose_load(const double* p) {
