@@ -421,6 +421,11 @@ int cfear_scan_get_cells(const cfear_scan* scan, cfear_cell* out_host, int32_t c
  * the cell whose float mean is nearest to float(p) (FLANN L2_Simple in float, lowest index on ties) if that squared
  * distance is < d * d, else -1 (the reference returns an empty vector).  queries_xy / idx both host or both device. */
 int cfear_scan_closest_idx(const cfear_scan* scan, const double* queries_xy, int32_t n_queries, double d, int32_t* idx);
+/* The tie-aware GetClosestIdx: ALL cells at the minimum float distance.  lo[i] is exactly cfear_scan_closest_idx's answer (the
+ * lowest index, -1 beyond d), hi[i] the highest cell at the same float distance and count[i] how many there are (-1 and 0
+ * beyond d).  hi and count may be NULL; every buffer host or every buffer device.  d must be greater than 0.            */
+int cfear_scan_closest_ties(const cfear_scan* scan, const double* queries_xy, int32_t n_queries, double d, int32_t* lo, int32_t* hi,
+                            int32_t* count);
 /* Diagnostic: the route the surface-point kernels served this scan on (CFEAR_SURF_PATH_*), 0 for a scan that did not come
  * from them (cfear_scan_from_cells).  The thresholds between the routes are LDS arithmetic inside the kernels; the word
  * lets a test assert where its input ran.  A scan handed out by cfear_odometry_get_scan carries the word of the stream's
@@ -548,6 +553,35 @@ int cfear_get_cost(cfear_ctx* ctx, const cfear_scan* const* scans, int32_t n_sca
  * CFEAR_ERR_CAPACITY); pose echoes the evaluated source pose.  par->itr selects the radius as above. */
 int cfear_get_cost_batch(cfear_ctx* ctx, const cfear_reg_job* jobs, int32_t n_jobs,
                          const cfear_reg_params* par, cfear_reg_result* results);
+
+/* Diagnostic: which registrations hang on a nearest-neighbour tie.  FLANN's nearestKSearch with k = 1 returns ONE of several
+ * equidistant targets (pointnormal.cpp:249), this library the lowest index; a reference build may legally pick another, and
+ * where the tied cells differ the registered pose follows the pick.  The call replays the association
+ * step of AddScanPairCost (n_scan_normal.cpp:213-261) at the poses of every job -- Tsrctotar, the float query, the radius by
+ * itr (2 * radius when itr == 1), the direction test -- by brute force, keeps all minimisers of every query and counts.
+ * It is a snapshot at the poses it is given: it says nothing about the passes a registration makes from there.
+ *   records [n_jobs] and per_query (optional) may be host or device memory, both on the same side; device records stay
+ *     there, stream-ordered and not synchronised, as the results of cfear_register_batch do.
+ *   per_query [total][3] = {lo, hi, count} of every query: job j's block starts at the sum over the jobs before it of
+ *     n_src * (n_scans - 1), the entry of fixed scan t and source cell s inside it is t * n_src + s; a query outside the
+ *     radius has {-1, -1, 0}.  per_query_len = the caller's capacity in entries; too small: CFEAR_ERR_CAPACITY before
+ *     anything is launched (the library computes the lengths from cfear_scan_size).
+ * Refused with CFEAR_ERR_INVALID_ARGUMENT before anything is launched or written, cfear_last_error naming the job: null
+ * pointers, n_jobs < 0, itr < 0, a job with n_scans < 2 (or more than the matcher takes), a pose that is not finite.
+ * n_jobs == 0 is CFEAR_OK.                                                                                              */
+#define CFEAR_TIE_TILE 1024             /* target cells per LDS tile of the audit's search (tests cross it on purpose)      */
+typedef struct cfear_tie_record {
+  int32_t n_queries;                    /* source cells x fixed scans of the job                                            */
+  int32_t n_in_radius;
+  int32_t n_associated;                 /* = blocks cfear_cost_prepare builds at these poses and this itr                   */
+  int32_t n_tied;                       /* in radius, >= 2 target cells at the minimum float distance                       */
+  int32_t n_tied_effective;             /* ... and some cell of the group differs bitwise from the lowest one in mean,
+                                         * normal, cov, scale or nsamples: what the residual and the weight read            */
+  int32_t max_group;                    /* largest tie group among in-radius queries (1 if none tied; 0 if none in radius)  */
+  int32_t status, pad;                  /* CFEAR_OK or the status cfear_get_cost_batch would give the job                   */
+} cfear_tie_record;                     /* 32 bytes */
+int cfear_association_ties_batch(cfear_ctx* ctx, const cfear_reg_job* jobs, int32_t n_jobs, const cfear_reg_params* par, int32_t itr,
+                                 cfear_tie_record* records, int32_t* per_query, int64_t per_query_len);
 
 /* Covariance of a registration by cost sampling.  Replaces
  * OdometryKeyframeFuser::approximateCovarianceBySampling (odometrykeyframefuser.cpp:261-380) and

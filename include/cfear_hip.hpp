@@ -398,6 +398,15 @@ class MapPointNormal {
     ctx_.check(cfear_scan_closest_idx(scan_, q, 1, d, &idx));
     return idx >= 0 ? std::vector<int>{idx} : std::vector<int>{};
   }
+  // The tie-aware GetClosestIdx (cfear_scan_closest_ties): ALL cells at the minimum float distance of p, which the 1-NN search
+  // returns one of -- lo is GetClosestIdx's answer, hi the highest cell at that distance, count how many; {-1, -1, 0} beyond d.
+  struct ClosestTies { int lo, hi, count; };
+  ClosestTies GetClosestTies(double px, double py, double d) const {
+    const double q[2] = {px, py};
+    int32_t lo = -1, hi = -1, count = 0;
+    ctx_.check(cfear_scan_closest_ties(scan_, q, 1, d, &lo, &hi, &count));
+    return ClosestTies{lo, hi, count};
+  }
   // the route the surface-point kernels served this scan on (CFEAR_SURF_PATH_*; 0 for a scan made from cells): diagnostic
   uint32_t SurfacePath() const { uint32_t p = 0; ctx_.check(cfear_scan_surface_path(scan_, &p)); return p; }
   const cfear_scan* device() const { return scan_; }
@@ -542,6 +551,34 @@ class n_scan_normal_reg {
   cfear_reg_params par_;
   double score_ = 0;
 };
+
+// Which registrations hang on a nearest-neighbour tie (cfear_association_ties_batch): the association
+// step of every job -- scans[j] with the free source last, poses[j] one per scan -- replayed at the poses given, one launch
+// for the batch.  per_query (optional) receives {lo, hi, count} per query, offsets (optional) the first entry of every job
+// and, as its last element, the total.
+inline std::vector<cfear_tie_record> AssociationTies(Context& ctx, const std::vector<std::vector<const MapPointNormal*>>& scans,
+                                                     const std::vector<std::vector<Pose2d>>& poses, const cfear_reg_params& par,
+                                                     int itr = 1, std::vector<int32_t>* per_query = nullptr,
+                                                     std::vector<int64_t>* offsets = nullptr) {
+  const size_t n = scans.size();
+  if (poses.size() != n) throw CfearError(CFEAR_ERR_INVALID_ARGUMENT, "AssociationTies: one pose list per job");
+  std::vector<std::vector<const cfear_scan*>> h(n);
+  std::vector<cfear_reg_job> jobs(n);
+  std::vector<int64_t> off(n + 1, 0);
+  for (size_t j = 0; j < n; j++) {
+    if (scans[j].size() < 2 || poses[j].size() != scans[j].size())
+      throw CfearError(CFEAR_ERR_INVALID_ARGUMENT, "AssociationTies: a job needs two scans or more and one pose per scan");
+    for (const MapPointNormal* m : scans[j]) h[j].push_back(m->device());
+    jobs[j].scans = h[j].data(); jobs[j].n_scans = (int32_t)h[j].size(); jobs[j].pad = 0; jobs[j].poses_xyt = &poses[j][0].x;
+    off[j + 1] = off[j] + (int64_t)scans[j].back()->GetSize() * (int64_t)(scans[j].size() - 1);
+  }
+  std::vector<cfear_tie_record> records(n);
+  if (per_query) per_query->assign((size_t)off[n] * 3, 0);
+  ctx.check(cfear_association_ties_batch(ctx.get(), jobs.data(), (int32_t)n, &par, itr, records.data(),
+                                         per_query && off[n] > 0 ? per_query->data() : nullptr, off[n]));
+  if (offsets) *offsets = off;
+  return records;
+}
 
 // radarDriver + OdometryKeyframeFuser for n independent sequences, one frame per call (cfear_odometry_*): the whole
 // path polar image -> pose on the GPU; with par.keep_nodes the RadarScan of every frame can be collected.

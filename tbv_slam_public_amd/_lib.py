@@ -128,6 +128,16 @@ class RegJob(C.Structure):
                 ("poses_xyt", C.POINTER(C.c_double))]
 
 
+class TieRecord(C.Structure):      # cfear_tie_record
+    _fields_ = [(n, C.c_int32) for n in ("n_queries", "n_in_radius", "n_associated", "n_tied", "n_tied_effective", "max_group",
+                                         "status", "pad")]
+
+
+TIE_RECORD_DTYPE = np.dtype([(n, "<i4") for n in ("n_queries", "n_in_radius", "n_associated", "n_tied", "n_tied_effective",
+                                                  "max_group", "status", "pad")])
+assert TIE_RECORD_DTYPE.itemsize == C.sizeof(TieRecord) == 32
+TIE_TILE = 1024                     # CFEAR_TIE_TILE
+
 CANDIDATE_DTYPE = np.dtype([("target", "<i4"), ("source", "<i4"), ("target_xyt", "<f8", (3,)), ("source_xyt", "<f8", (3,))])
 assert CANDIDATE_DTYPE.itemsize == 56
 
@@ -302,6 +312,7 @@ EXPORTS = [
     "cfear_loop_stats_params_default", "cfear_loop_stats_batch", "cfear_loop_curves_params_default", "cfear_loop_curves_batch",
     "cfear_sync_trajectories", "cfear_tum_write", "cfear_cov_write",
     "cfear_graph_align_batch", "cfear_graph_map_batch", "cfear_graph_string_write", "cfear_graph_output_write",
+    "cfear_association_ties_batch", "cfear_scan_closest_ties",
 ]
 
 PIPE_GRAPH, PIPE_TIMING = 1, 2      # enum { CFEAR_PIPE_GRAPH, CFEAR_PIPE_TIMING }
@@ -555,6 +566,8 @@ def lib():
     L.cfear_sc_manager_size.argtypes = [vp]
     L.cfear_sc_manager_destroy.argtypes = [vp]
     L.cfear_scan_closest_idx.argtypes = [vp, vp, C.c_int32, C.c_double, vp]
+    L.cfear_scan_closest_ties.argtypes = [vp, vp, C.c_int32, C.c_double, vp, vp, vp]
+    L.cfear_association_ties_batch.argtypes = [vp, C.POINTER(RegJob), C.c_int32, C.POINTER(RegParams), C.c_int32, vp, vp, C.c_int64]
     L.cfear_scan_surface_path.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.cfear_polar_rotate_ccw.argtypes = [vp, vp, C.POINTER(PolarDesc), vp, C.c_int32, C.c_int64]
     L.cfear_verify_params_default.argtypes = [C.POINTER(VerifyParams)]

@@ -564,6 +564,25 @@ class MapPointNormal:
             return [int(out[0])] if out[0] >= 0 else []
         return out
 
+    def GetClosestTies(self, p, d):
+        """The tie-aware GetClosestIdx (cfear_scan_closest_ties): ALL cells at the minimum float distance of p, which FLANN's
+        1-NN search returns one of.  -> (lo, hi, count): lo is GetClosestIdx's answer (the lowest index), hi the highest
+        cell at the same distance, count how many there are; (-1, -1, 0) beyond d.  p: one point or an array [n, 2]
+        (NumPy or torch CUDA float64) -> ints or int32 [n] arrays."""
+        single = not _is_torch(p) and np.ndim(p) == 1
+        q = p if _is_torch(p) else np.ascontiguousarray(np.atleast_2d(p), dtype=np.float64)
+        n = int(q.shape[0])
+        if _is_torch(q):
+            import torch
+            q = q.contiguous()
+            lo, hi, cnt = (torch.empty(n, dtype=torch.int32, device=q.device) for _ in range(3))
+        else:
+            lo, hi, cnt = (np.empty(n, np.int32) for _ in range(3))
+        self.ctx.check(self.ctx._lib.cfear_scan_closest_ties(self._h, _ptr(q)[0], n, float(d), _ptr(lo)[0], _ptr(hi)[0], _ptr(cnt)[0]))
+        if single:
+            return int(lo[0]), int(hi[0]), int(cnt[0])
+        return lo, hi, cnt
+
     def GetCells(self):
         n = self.GetSize()
         out = np.zeros(max(n, 1), L.CELL_DTYPE)
@@ -864,6 +883,80 @@ class n_scan_normal_reg:
                 self.ctx.h, arr, n, C.byref(self.par), regs.ctypes.data, C.byref(sp), cov.ctypes.data, None,
                 ok.ctypes.data))
         return ok.astype(bool), cov
+
+
+# ------------------------------------------------------------------------------------------------
+# Which registrations hang on a nearest-neighbour tie
+# ------------------------------------------------------------------------------------------------
+def _tie_reg(par, ctx):
+    """An n_scan_normal_reg that carries `par`: None (the defaults), a RegParams, or an n_scan_normal_reg."""
+    reg = n_scan_normal_reg(ctx=ctx)
+    if par is not None:
+        reg.par = par.par if isinstance(par, n_scan_normal_reg) else par
+    return reg
+
+
+def association_ties(jobs, par=None, itr=1, want_queries=False, ctx=None, device_out=False):
+    """cfear_association_ties_batch: the association step of every job -- a list of (scans, Tsrc) as for RegisterBatch, or
+    a PrepareBatch result -- replayed at the poses given, with ALL nearest target cells of every query kept.  itr selects
+    the radius as in AddScanPairCost (2 * radius when itr == 1).  One launch for the batch.
+    -> a TIE_RECORD_DTYPE array [n]; with want_queries (records, per_query int32 [total, 3] = (lo, hi, count), offsets
+    int64 [n + 1]): job j's queries are per_query[offsets[j]:offsets[j + 1]], the entry of fixed scan t and source cell s
+    is t * n_src + s, (-1, -1, 0) outside the radius.  With device_out the records (uint8 [n, 32], to view on the host) and
+    per_query are torch CUDA tensors and nothing is synchronised."""
+    ctx = ctx or default_context()
+    reg = _tie_reg(par, ctx)
+    arr, n, keep = jobs if isinstance(jobs, tuple) else reg.PrepareBatch(jobs)
+    sizes = [int(k[2][-1].GetSize()) * (len(k[2]) - 1) for k in keep]
+    offsets = np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)]).astype(np.int64)
+    total = int(offsets[-1])
+    if device_out:
+        import torch
+        rec = torch.zeros((n, L.TIE_RECORD_DTYPE.itemsize), dtype=torch.uint8, device="cuda")
+        pq = torch.zeros((max(total, 1), 3), dtype=torch.int32, device="cuda") if want_queries else None
+        _torch_ready(ctx, rec)
+    else:
+        rec = np.zeros(n, L.TIE_RECORD_DTYPE)
+        pq = np.zeros((max(total, 1), 3), np.int32) if want_queries else None
+    if n:
+        ctx.check(ctx._lib.cfear_association_ties_batch(ctx.h, arr, n, C.byref(reg.par), int(itr), _ptr(rec)[0], _ptr(pq)[0], total))
+    return (rec, pq[:total], offsets) if want_queries else rec
+
+
+def flip_ties(scan):
+    """A MapPointNormal with the cells of `scan` in reverse order.  The matcher takes the lowest index among all minimisers, so
+    against the flipped scan every tie is decided the other way -- ties among distinct equidistant cells included; the
+    residual blocks keep their order (keyframe, source cell) as long as only TARGETS are flipped.  Through GetCells / cells=:
+    not a hot path."""
+    return MapPointNormal(cells=scan.GetCells()[::-1].copy(), ctx=scan.ctx)
+
+
+def tie_sensitivity(jobs, par=None, ctx=None):
+    """The legal spread of THESE registrations under the tie rule, as numbers: every job -- (scans, Tsrc) -- is audited at
+    its start poses (itr = 1), registered as given, registered again with every target scan flipped (flip_ties), and audited
+    at the registered poses (itr = 2).  Four batched calls.
+    -> dict of arrays over the jobs: ties_start, ties_end (TIE_RECORD_DTYPE), result, result_flipped (RESULT_DTYPE) and delta
+    [n, 3] = |dx|, |dy|, |dtheta| between the two registered poses.  Nothing here says which way FLANN decides: the spread
+    is between this library's rule and its opposite."""
+    ctx = ctx or default_context()
+    reg = _tie_reg(par, ctx)
+    jobs = [(list(scans), np.ascontiguousarray(T, dtype=np.float64).reshape(len(scans), 3)) for scans, T in jobs]
+    flipped = {}
+    for scans, _ in jobs:
+        for s in scans[:-1]:
+            if id(s) not in flipped:
+                flipped[id(s)] = flip_ties(s)
+    ties_start = association_ties(jobs, reg, 1, ctx=ctx)
+    result = reg.RegisterBatch(jobs)
+    result_flipped = reg.RegisterBatch([([flipped[id(s)] for s in scans[:-1]] + [scans[-1]], T) for scans, T in jobs])
+    end = []
+    for (scans, T), r in zip(jobs, result):
+        Te = T.copy()
+        Te[-1] = r["pose"]
+        end.append((scans, Te))
+    ties_end = association_ties(end, reg, 2, ctx=ctx)
+    return {"ties_start": ties_start, "ties_end": ties_end, "result": result, "result_flipped": result_flipped,
+            "delta": np.abs(result["pose"] - result_flipped["pose"]).reshape(len(jobs), 3)}
 
 
 class CeresCost:

@@ -87,6 +87,7 @@ enum WsSlot : int {
   kWsLoopEval = 24,       // loop rows and curves: staged graphs, candidates, scores and curves, job table, sort and scan scratch
   kWsTrajSync = 25,       // trajectory synchronisation: staged poses and stamps, pair and block tables, ranges, staged outputs
   kWsGraphFinish = 26,    // graph alignment and maps: staged poses, flags and clouds, graph, node and tile tables, sums, staged maps
+  kWsTieAudit = 27,       // tie audit: job records, staged queries, staged records and per-query groups
 };
 
 struct cfear_ctx {
@@ -99,7 +100,7 @@ struct cfear_ctx {
   std::vector<Event> event_pool;
   // grow-only device workspaces (indexed by WsSlot so stages of one pipeline do not alias)
   struct Ws { DevBuf<void> p; size_t bytes = 0; };
-  Ws ws[27];
+  Ws ws[28];
   // pinned host staging for small read-backs
   PinnedBuf<char> pinned;
   size_t pinned_bytes = 0;
@@ -431,6 +432,9 @@ int cfear_check_reg_params(cfear_ctx* ctx, const cfear_reg_params* par);
 // launch geometry of a batch of two-scan jobs from its largest target / source (what cfear_register_candidates derives)
 void cfear_reg_pair_geometry(const cfear_reg_params* par, int max_tar_cells, int max_src_cells, int* pairs_cap, RegLaunchHint* hint);
 size_t cfear_reg_job_stride(int max_scans);         // bytes of a record that holds up to max_scans scan views
+// whether a cost-only launch (cfear_get_cost_batch) can hold a registration of these sizes at all; sum_pad / max_pad: the
+// fixed scans' padded record counts (scan_grid_pad), total and largest.  What it cannot hold is the job's CFEAR_ERR_CAPACITY.
+bool cfear_reg_cost_fits(const cfear_reg_params* par, int n_scans, int sum_pad, int max_pad, int n_src);
 void cfear_reg_job_set_itr(void* job, int itr);
 // quadratic fit of the cost samples -> 6x6 covariance: struct CovFit (covfit.hpp, host)
 

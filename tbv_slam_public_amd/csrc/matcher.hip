@@ -1742,6 +1742,12 @@ void cfear_reg_pair_geometry(const cfear_reg_params* par, int max_tar_cells, int
   *hint = sz.hint(1);
 }
 
+// The capacity of the cost-only launches' last resort: 8 wavefronts, a CU's whole LDS, the match table in global scratch
+// (cfear_register_launch, hint.whole_cu) -- the job sizes the kernel would answer with write_capacity.
+bool cfear_reg_cost_fits(const cfear_reg_params* par, int n_scans, int sum_pad, int max_pad, int n_src) {
+  return mt_fit(kLdsCu - 256 - kPartBigBytes, n_scans - 1, sum_pad, max_pad, n_src, reg_dense_fields(par->cost), true).can;
+}
+
 extern "C" int cfear_register(cfear_ctx* ctx, const cfear_scan* const* scans, int32_t n_scans, double* poses_xyt,
                               const cfear_reg_params* par, cfear_reg_result* result) {
   if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
