@@ -170,16 +170,18 @@ extern "C" int cfear_closure_candidates_batch(cfear_ctx* ctx, const double* posi
   if (std::isnan(par->min_d_travel) || std::isnan(par->max_d_travel) || std::isnan(par->max_d_close) ||
       (par->verify_via_odometry && rel_xyt && std::isnan(par->odom_sigma_error)))
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "a threshold is NaN");
-  if (node_offsets[0] != 0 || node_offsets[n_graphs] != n_nodes) {
-    // the graph whose range the table mis-states: the first if it does not start at 0, else the last
-    if (failed_graph && n_graphs > 0) *failed_graph = node_offsets[0] != 0 ? 0 : n_graphs - 1;
-    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "graph %d: node_offsets must run from 0 to n_nodes over n_graphs + 1 entries",
-                           n_graphs > 0 ? (node_offsets[0] != 0 ? 0 : n_graphs - 1) : -1);
+  const OffsetsReport table = check_offsets(node_offsets, n_graphs, n_nodes);
+  if (table.start_not_0 || table.end_not_total) {
+    // the start and the end before the ranges; the graph whose range the table mis-states: the first if it does not start
+    // at 0, else the last
+    const int gi = n_graphs > 0 ? (table.start_not_0 ? 0 : n_graphs - 1) : -1;
+    if (failed_graph) *failed_graph = gi;
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "graph %d: node_offsets must run from 0 to n_nodes over n_graphs + 1 entries", gi);
   }
   int64_t n_blocks = 0;
   for (int gi = 0; gi < n_graphs; gi++) {
     const int64_t n = node_offsets[gi + 1] - node_offsets[gi];
-    if (n < 0 || node_offsets[gi + 1] > n_nodes || n > INT32_MAX - kClosureTile) {
+    if (gi == table.bad_range() || n > INT32_MAX - kClosureTile) {
       if (failed_graph) *failed_graph = gi;
       return cfear_set_error(ctx, n > 0 ? CFEAR_ERR_CAPACITY : CFEAR_ERR_INVALID_ARGUMENT,
                              "graph %d: offsets descend or leave the arrays, or more than %d nodes", gi, INT32_MAX - kClosureTile);

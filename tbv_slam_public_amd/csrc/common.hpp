@@ -6,12 +6,14 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <type_traits>
 #include <vector>
 
 #include "../../include/cfear_hip.h"
+#include "batch_tables.hpp"
 #include "owned.hpp"
 
 #define CFEAR_WAVE 64
@@ -221,6 +223,42 @@ class HostStage {
   hipError_t err_ = hipSuccess;       // the first copy-back or fetch() that failed
   bool host_ = false, device_ = false, sync_ = false, pending_ = false;
 };
+// The tables of a ragged batch (batch_tables.hpp) through a HostStage.  Constructed while the call plans its pieces; after
+// carve(), upload() builds the host record -- in the context's pinned staging when `pinned` (HostStage::pinned) -- and
+// uploads the first piece.  The second piece is the call's to fill at host_second() and to send with upload_second().
+class StagedTables {
+ public:
+  StagedTables(HostStage& st, size_t record_bytes, size_t block_bytes, size_t second_bytes = 0, bool pinned = false)
+      : st_(st), lay_(record_bytes, block_bytes, second_bytes), pinned_(pinned) {
+    st.piece(d_first_, lay_.first);
+    if (second_bytes) st.piece(d_second_, second_bytes);
+  }
+  int upload(const void* records, const void* blocks) {
+    h_ = (char*)(pinned_ ? st_.pinned(lay_.first + lay_.second) : st_.record(lay_.first + lay_.second));
+    if (!h_) return CFEAR_ERR_HIP;
+    if (lay_.record_bytes) memcpy(h_, records, lay_.record_bytes);
+    if (lay_.block_bytes) memcpy(h_ + lay_.blocks_at, blocks, lay_.block_bytes);
+    return st_.upload(d_first_, h_, lay_.first);
+  }
+  template <class T> const T* records() const { return (const T*)d_first_; }
+  template <class T> const T* blocks() const { return (const T*)(d_first_ + lay_.blocks_at); }
+  template <class T> T* second() const { return (T*)d_second_; }
+  template <class T> T* host_second() const { return (T*)(h_ + lay_.first); }
+  int upload_second() { return st_.upload(d_second_, h_ + lay_.first, lay_.second); }
+
+ private:
+  HostStage& st_;
+  TableLayout lay_;
+  bool pinned_;
+  char *d_first_ = nullptr, *d_second_ = nullptr, *h_ = nullptr;
+};
+// 0: all host, 1: all device, -1: mixed; null pointers are skipped
+inline int memory_kind(std::initializer_list<const void*> ptrs) {
+  int n = 0, dev = 0;
+  for (const void* p : ptrs)
+    if (p) { n++; dev += cfear_is_device_ptr(p); }
+  return dev == 0 ? 0 : dev == n ? 1 : -1;
+}
 // hipFuncAttributeMaxDynamicSharedMemorySize, once per (context, kernel, size): the attribute is per device and contexts are
 // per device, so a launch path asks every time and pays a linear look-up over a dozen entries instead of a runtime call
 int cfear_allow_lds(cfear_ctx* ctx, const void* kernel, size_t bytes);
@@ -404,7 +442,7 @@ struct CoralJob {
 int cfear_coral_launch_device(cfear_ctx* ctx, const CoralJob* d_jobs, int n_jobs, int cap, const cfear_coral_params* par,
                               cfear_coral_result* d_results);
 int cfear_coral_max_points();
-// evaluate.hip's 3 x 3 alignment: s = mean x (3), mean y (3), the covariance sum y x^T row-major (9) -> [r | t] with
+// evaluate.hip's 3 x 3 alignment, also cfear_graph_align_batch's (graphfinish.hip): s = mean x (3), mean y (3), the covariance sum y x^T row-major (9) -> [r | t] with
 // r = u diag(1, 1, det u det v) v^T and t = mean y - r mean x; false (and r = I) when the second singular value vanishes
 bool cfear_align_from_sums(const double* s, double align[12]);
 

@@ -1,6 +1,6 @@
 // eigen_quat.hpp -- the Eigen 3.3 quaternion conversions the reference's pose types go through, restated operation by
 // operation in fp64 without contraction (-ffp-contract=off): Quaterniond(Matrix3d) and toRotationMatrix().  Host and device.
-// Used by trajsync.hip (pose_interp) and graphfinish.hip (PoseEigToCeres / PoseCeresToEig).  Neither Eigen nor ROS is part
+// Used by trajsync.hip (pose_interp), graphfinish.hip (PoseEigToCeres) and pose_rows.hpp (PoseCeresToEig).  Neither Eigen nor ROS is part
 // of the reference tree or of this build ("restated, not pinned").
 #pragma once
 #include <cmath>

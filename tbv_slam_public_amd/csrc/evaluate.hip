@@ -2,18 +2,15 @@
 // reference's run scripts end in, radar_kitti_benchmark/python/eval_odom.py --align 6dof, i.e. KittiEvalOdom.eval of
 // radar_kitti_benchmark/python/kitti_odometry.py (cited below as :line).  DESIGN.md section 4.8.
 //
-// Everything is fp64.  The pose algebra has ONE operation order, shared with tests/kitti_eval_cpu.py and kept by
-// -ffp-contract=off, because the segment ends are decided by comparing sums of rounded distances (:182-195):
-//   inverse of [A | t]   cofactors of A, det = (a00 c00 + a01 c01) + a02 c02, adj / det (a division per entry) -- a real
-//                        inverse: the 3 x 3 blocks of a 6-decimal pose file are not orthonormal (np.linalg.inv, :229-238)
-//   product P Q          (p0 q0 + p1 q1) + p2 q2 per entry, ((p0 t0 + p1 t1) + p2 t2) + pt per row
+// Everything is fp64.  The pose algebra (pose_rows.hpp) has ONE operation order, shared with tests/kitti_eval_cpu.py,
+// because the segment ends are decided by comparing sums of rounded distances (:182-195).
 // Reductions are a fixed tree (a thread's strided serial sum, the wave's DPP butterfly, the four waves in order), one
 // workgroup per trajectory: a trajectory's figures do not depend on the batch it is evaluated in.  No atomics.
 //
 // Kernels (poses stay [pose][12], the 96-byte records a KITTI line holds: a segment reads four poses at unrelated frames):
 //   eval_normalise    thread per pose (flat grid over the batch's poses)   inv(first pose) * pose for both trajectories (:708-714)
 //   eval_align_sums   workgroup per pair    means and the 3 x 3 covariance of umeyama_alignment (:49-61); the SVD of the
-//                                           covariance is host code (align_from_sums)
+//                                           covariance is host code (cfear_align_from_sums)
 //   eval_apply_align  thread per pose       [r | t] * estimate (:730-737)
 //   eval_distance     wavefront per pair    the serial sum dist[i+1] = dist[i] + |p_i - p_{i+1}| (:123-141): the segment
 //                                           lengths are computed 64 at a time, the running sum is carried through readlane
@@ -29,10 +26,10 @@
 #include <string>
 #include <vector>
 
-#include "common.hpp"
+#include "pose_rows.hpp"
 
 namespace {
-constexpr int kEvalThreads = 256;
+constexpr int kEvalThreads = kAlignThreads;
 constexpr int kEvalLengths = CFEAR_EVAL_NUM_LENGTHS;
 static_assert(sizeof(cfear_eval_params) == 72, "cfear_eval_params is 72 bytes (include/cfear_hip.h)");
 static_assert(sizeof(cfear_eval_summary) == 360, "cfear_eval_summary is 360 bytes (include/cfear_hip.h)");
@@ -68,50 +65,6 @@ struct EvalArgs {
   double lengths[kEvalLengths];
 };
 
-struct Pose { double m[12]; };
-
-__device__ __forceinline__ Pose pose_load(const double* p) {
-  Pose r;
-#pragma unroll
-  for (int k = 0; k < 12; k += 2) { const g_f64x2 v = gload<g_f64x2>(p + k); r.m[k] = v.x; r.m[k + 1] = v.y; }
-  return r;
-}
-__device__ __forceinline__ void pose_store(double* p, const Pose& r) {
-#pragma unroll
-  for (int k = 0; k < 12; k += 2) { g_f64x2 v; v.x = r.m[k]; v.y = r.m[k + 1]; gstore<g_f64x2>(p + k, v); }
-}
-__device__ __forceinline__ Pose pose_inv(const Pose& P) {
-  const double a00 = P.m[0], a01 = P.m[1], a02 = P.m[2], a10 = P.m[4], a11 = P.m[5], a12 = P.m[6], a20 = P.m[8], a21 = P.m[9],
-               a22 = P.m[10];
-  const double c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
-  const double c10 = a02 * a21 - a01 * a22, c11 = a00 * a22 - a02 * a20, c12 = a01 * a20 - a00 * a21;
-  const double c20 = a01 * a12 - a02 * a11, c21 = a02 * a10 - a00 * a12, c22 = a00 * a11 - a01 * a10;
-  const double det = (a00 * c00 + a01 * c01) + a02 * c02;
-  Pose I;
-  I.m[0] = c00 / det; I.m[1] = c10 / det; I.m[2] = c20 / det;
-  I.m[4] = c01 / det; I.m[5] = c11 / det; I.m[6] = c21 / det;
-  I.m[8] = c02 / det; I.m[9] = c12 / det; I.m[10] = c22 / det;
-#pragma unroll
-  for (int r = 0; r < 3; r++) I.m[4 * r + 3] = -((I.m[4 * r] * P.m[3] + I.m[4 * r + 1] * P.m[7]) + I.m[4 * r + 2] * P.m[11]);
-  return I;
-}
-__device__ __forceinline__ Pose pose_mul(const Pose& A, const Pose& B) {
-  Pose R;
-#pragma unroll
-  for (int r = 0; r < 3; r++) {
-#pragma unroll
-    for (int c = 0; c < 3; c++) R.m[4 * r + c] = (A.m[4 * r] * B.m[c] + A.m[4 * r + 1] * B.m[4 + c]) + A.m[4 * r + 2] * B.m[8 + c];
-    R.m[4 * r + 3] = ((A.m[4 * r] * B.m[3] + A.m[4 * r + 1] * B.m[7]) + A.m[4 * r + 2] * B.m[11]) + A.m[4 * r + 3];
-  }
-  return R;
-}
-__device__ __forceinline__ double norm3(double x, double y, double z) { return __dsqrt_rn((x * x + y * y) + z * z); }
-// rotation_error, :143-155
-__device__ __forceinline__ double rotation_error(const Pose& P) {
-  const double d = 0.5 * (((P.m[0] + P.m[5]) + P.m[10]) - 1.0);
-  return acos(fmax(fmin(d, 1.0), -1.0));
-}
-
 __global__ __launch_bounds__(kEvalThreads) void eval_normalise_kernel(EvalArgs a) {
   const int2 blk = a.blocks[blockIdx.x];
   const EvalTraj tr = a.traj[blk.x];
@@ -123,40 +76,20 @@ __global__ __launch_bounds__(kEvalThreads) void eval_normalise_kernel(EvalArgs a
 }
 
 // umeyama_alignment(x = estimate, y = ground truth), :49-61: the means, then 1/n sum (y_i - my)(x_i - mx)^T
+struct EvalAlignSrc {
+  static constexpr bool kSkips = false;
+  const double *E, *G;
+  int n;
+  __device__ bool counts(int) const { return true; }
+  __device__ double x(int i, int k) const { return E[(size_t)i * 12 + 4 * k + 3]; }
+  __device__ double y(int i, int k) const { return G[(size_t)i * 12 + 4 * k + 3]; }
+  __device__ double mean_div(double) const { return (double)n; }
+  __device__ double cov(double sum) const { return sum / (double)n; }
+};
 __global__ __launch_bounds__(kEvalThreads) void eval_align_sums_kernel(EvalArgs a) {
   __shared__ double red[4];
   const EvalTraj tr = a.traj[blockIdx.x];
-  const double* E = a.E + tr.off * 12;
-  const double* G = a.G + tr.off * 12;
-  double s[6] = {0, 0, 0, 0, 0, 0};
-  for (int i = threadIdx.x; i < tr.n; i += kEvalThreads) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) { s[k] += E[(size_t)i * 12 + 4 * k + 3]; s[3 + k] += G[(size_t)i * 12 + 4 * k + 3]; }
-  }
-  double mean[6];
-#pragma unroll
-  for (int k = 0; k < 6; k++) mean[k] = block_sum(s[k], red) / (double)tr.n;
-  double c[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (int i = threadIdx.x; i < tr.n; i += kEvalThreads) {
-    double x[3], y[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) { x[k] = E[(size_t)i * 12 + 4 * k + 3] - mean[k]; y[k] = G[(size_t)i * 12 + 4 * k + 3] - mean[3 + k]; }
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-      for (int q = 0; q < 3; q++) c[3 * r + q] += y[r] * x[q];
-  }
-  double* out = a.sums + (size_t)blockIdx.x * 16;
-#pragma unroll
-  for (int k = 0; k < 9; k++) {
-    const double v = block_sum(c[k], red) / (double)tr.n;
-    if (threadIdx.x == 0) out[6 + k] = v;
-  }
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < 6; k++) out[k] = mean[k];
-    out[15] = 0.0;
-  }
+  align_sums(EvalAlignSrc{a.E + tr.off * 12, a.G + tr.off * 12, tr.n}, a.sums + (size_t)blockIdx.x * 16, red);
 }
 
 __global__ __launch_bounds__(kEvalThreads) void eval_apply_align_kernel(EvalArgs a) {
@@ -349,12 +282,15 @@ __global__ __launch_bounds__(kEvalThreads) void eval_frames_kernel(EvalArgs a) {
   }
 }
 
+}  // namespace
+
 // ---- host: the 3 x 3 SVD of umeyama_alignment (:63-77) ------------------------------------------------------------
 // One-sided Jacobi: the columns of C V are rotated until they are orthogonal, C V = U S.  r = u diag(1, 1, det u det v) v^T
 // is formed from the two leading singular pairs alone, u1 v1^T + u2 v2^T + (u1 x u2)(v1 x v2)^T: the third pair of a
 // planar trajectory belongs to the singular value 0 and is arbitrary in sign, and this form never reads it.
 // Returns false when the second singular value vanishes (all positions on one line): the rotation is then undetermined.
-bool align_from_sums(const double* s /*[15]*/, double align[12]) {
+// cfear_graph_align_batch (graphfinish.hip) solves its own s[15] with it.
+bool cfear_align_from_sums(const double* s /*[15]*/, double align[12]) {
   double A[3][3], V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
   for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) A[r][c] = s[6 + 3 * r + c];
   for (int sweep = 0; sweep < 60; sweep++) {
@@ -398,6 +334,7 @@ bool align_from_sums(const double* s /*[15]*/, double align[12]) {
   return ok;
 }
 
+namespace {
 int check_eval_params(const cfear_eval_params* par) {
   if (!par || par->step_size < 1) return CFEAR_ERR_INVALID_ARGUMENT;
   if (par->alignment != CFEAR_EVAL_ALIGN_NONE && par->alignment != CFEAR_EVAL_ALIGN_6DOF) return CFEAR_ERR_INVALID_ARGUMENT;
@@ -408,9 +345,6 @@ int check_eval_params(const cfear_eval_params* par) {
   return CFEAR_OK;
 }
 }  // namespace
-
-// the same routine for cfear_graph_align_batch (graphfinish.hip), which sums its own s[15]
-bool cfear_align_from_sums(const double* s, double align[12]) { return align_from_sums(s, align); }
 
 extern "C" void cfear_eval_params_default(cfear_eval_params* p) {
   p->step_size = 10;                                 // eval_odom.py's default --step_size
@@ -450,26 +384,23 @@ extern "C" int cfear_eval_trajectories(cfear_ctx* ctx, const double* est, const 
   std::vector<int32_t> h_counts((size_t)n_traj * kEvalLengths);
   std::vector<int2> blocks;                          // the per-pose kernels' flat grid: a ragged batch launches no empty workgroups
   int64_t total = 0, span = 0;
+  bool grid_ok = true;
   for (int t = 0; t < n_traj; t++) {
     const int64_t src = offsets ? offsets[t] : total;
     if (src < 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "trajectory %d: negative offset", t);
     traj[t] = EvalTraj{src, total, lengths[t], (int32_t)(((int64_t)lengths[t] + par->step_size - 1) / par->step_size)};
     total += lengths[t];
     span = std::max(span, src + lengths[t]);
-    for (int i = 0; i < lengths[t]; i += kEvalThreads) blocks.push_back(make_int2(t, i));
+    grid_ok = flat_grid_add(blocks, t, lengths[t], kEvalThreads) && grid_ok;
   }
-  if (blocks.size() > (size_t)INT32_MAX) return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "more than 2^31 x 256 poses in one call");
+  if (!grid_ok) return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "more than 2^31 x 256 poses in one call");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const size_t tab_traj = ((size_t)n_traj * sizeof(EvalTraj) + 15) & ~(size_t)15, tab1 = tab_traj + blocks.size() * sizeof(int2);
-  const size_t tab2 = (size_t)n_traj * sizeof(EvalPost);
   HostStage st(ctx, kWsEval);
   EvalArgs a{};
-  char *d_tab1, *d_tab2;
   st.in(a.est, est, (size_t)span * 96);
   st.in(a.gt, gt, (size_t)span * 96);
   if (st.mixed()) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "est and gt must both be host or both be device memory");
-  st.piece(d_tab1, tab1);
-  st.piece(d_tab2, tab2);
+  StagedTables tab(st, (size_t)n_traj * sizeof(EvalTraj), blocks.size() * sizeof(int2), (size_t)n_traj * sizeof(EvalPost));
   st.piece(a.E, (size_t)total * 96);
   st.piece(a.G, (size_t)total * 96);
   st.piece(a.dist, (size_t)total * 8);
@@ -479,13 +410,10 @@ extern "C" int cfear_eval_trajectories(cfear_ctx* ctx, const double* est, const 
   st.out(a.summaries, summaries, (size_t)n_traj * sizeof(cfear_eval_summary));
   if (rows) st.out(a.rows, rows, (size_t)row_cap * sizeof(cfear_eval_row));
   CFEAR_CHECK(st.carve());
-  char* h = (char*)st.record(tab1 + tab2);
-  memcpy(h, traj.data(), (size_t)n_traj * sizeof(EvalTraj));
-  memcpy(h + tab_traj, blocks.data(), blocks.size() * sizeof(int2));
-  CFEAR_CHECK(st.upload(d_tab1, h, tab1));
-  a.traj = (const EvalTraj*)d_tab1;
-  a.blocks = (const int2*)(d_tab1 + tab_traj);
-  a.post = (const EvalPost*)d_tab2;
+  CFEAR_CHECK(tab.upload(traj.data(), blocks.data()));
+  a.traj = tab.records<EvalTraj>();
+  a.blocks = tab.blocks<int2>();
+  a.post = tab.second<EvalPost>();
   a.row_cap = rows ? row_cap : 0;
   a.n_traj = n_traj;
   a.step = par->step_size;
@@ -514,19 +442,18 @@ extern "C" int cfear_eval_trajectories(cfear_ctx* ctx, const double* est, const 
   st.fetch(h_counts.data(), a.counts, h_counts.size() * 4);
   if (align) st.fetch(h_sums.data(), a.sums, h_sums.size() * 8);
   CFEAR_CHECK(st.wait());
-  EvalPost* post = (EvalPost*)(h + tab1);
+  EvalPost* post = tab.host_second<EvalPost>();
   int64_t row_total = 0;
   for (int t = 0; t < n_traj; t++) {
-    static const double kIdentity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    memcpy(post[t].align, kIdentity, sizeof(kIdentity));
+    memcpy(post[t].align, kIdentityRows, sizeof(kIdentityRows));
     post[t].status = CFEAR_OK;
     post[t].pad = 0;
-    if (align && !align_from_sums(h_sums.data() + (size_t)t * 16, post[t].align)) post[t].status = CFEAR_ERR_SOLVER;
+    if (align && !cfear_align_from_sums(h_sums.data() + (size_t)t * 16, post[t].align)) post[t].status = CFEAR_ERR_SOLVER;
     post[t].row_base = row_total;
     for (int k = 0; k < kEvalLengths; k++) row_total += h_counts[(size_t)t * kEvalLengths + k];
   }
   if (n_rows) *n_rows = row_total;
-  CFEAR_CHECK(st.upload(d_tab2, post, tab2));
+  CFEAR_CHECK(tab.upload_second());
   if (align) {
     ProfScope ps(ctx, "eval_apply_align");
     hipLaunchKernelGGL(eval_apply_align_kernel, per_pose, dim3(kEvalThreads), 0, ctx->stream, a);
@@ -589,8 +516,7 @@ extern "C" int cfear_kitti_write(const char* path, const double* poses, int64_t 
   FILE* f = fopen(path, "w");
   if (!f) return CFEAR_ERR_IO;
   bool ok = true;
-  for (int64_t i = 0; i < n && ok; i++)
-    for (int k = 0; k < 12 && ok; k++) ok = fprintf(f, k == 11 ? "%.6f\n" : "%.6f ", poses[i * 12 + k]) > 0;
+  for (int64_t i = 0; i < n && ok; i++) ok = kitti_row_write(f, poses + i * 12, "\n");
   ok = fclose(f) == 0 && ok;
   return ok ? CFEAR_OK : CFEAR_ERR_IO;
 }

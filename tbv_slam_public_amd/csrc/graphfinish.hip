@@ -6,10 +6,10 @@
 // cfear_graph_align_batch (:235-263).  Everything is fp64 without contraction (-ffp-contract=off):
 //   graph_align_sums     workgroup per graph   the centroids of Tgt.p and T.p over the nodes with ground truth and
 //                                              H^T = sum (b - cB)(a - cA)^T of best_fit_transform (cfear_radarodometry/src/
-//                                              cfear_radarodometry/eval_trajectory.cpp:343-395), as eval_align_sums sums them:
-//                                              a thread's strided serial sum, the wave's DPP butterfly, the four waves in order
+//                                              cfear_radarodometry/eval_trajectory.cpp:343-395): align_sums (pose_rows.hpp),
+//                                              the body eval_align_sums runs
 //   host                                       the evaluator's 3 x 3 SVD (cfear_align_from_sums, evaluate.hip) and the general
-//                                              inverse of [R | t] (Affine3d::inverse(): cofactors times 1 / det)
+//                                              inverse of [R | t] (affine_inverse, pose_rows.hpp)
 //   graph_align_apply    thread per node       PoseEigToCeres(Tgtalign * GetPose()) (types.cpp:25-38), eigen_quat.hpp
 //   graph_align_ate      workgroup per graph   sum |Tgt.p - p_new| / max(N, 1) over the nodes with ground truth (a mean)
 // A graph's sums depend on the graph alone, so its result does not depend on what else the batch holds.
@@ -28,11 +28,10 @@
 #include <cstdio>
 #include <vector>
 
-#include "common.hpp"
-#include "eigen_quat.hpp"
+#include "pose_rows.hpp"
 
 namespace {
-constexpr int kGfThreads = 256;
+constexpr int kGfThreads = kAlignThreads;
 constexpr int kMapTile = CFEAR_GRAPH_MAP_TILE;
 static_assert(kMapTile == kGfThreads, "one thread moves one point of a tile");
 static_assert(sizeof(cfear_pose3d) == 56, "cfear_pose3d is 7 doubles (include/cfear_hip.h)");
@@ -71,9 +70,8 @@ struct GfMapArgs {
   float* map_gt;
 };
 
-struct P3 { double p[3], q[4]; };
-__device__ __forceinline__ P3 p3_load(const cfear_pose3d* at) {
-  P3 r;
+__device__ __forceinline__ cfear_pose3d pose3d_load(const cfear_pose3d* at) {
+  cfear_pose3d r;
   const double* d = (const double*)at;
 #pragma unroll
   for (int k = 0; k < 3; k++) r.p[k] = gload<double>(d + k);
@@ -81,57 +79,23 @@ __device__ __forceinline__ P3 p3_load(const cfear_pose3d* at) {
   for (int k = 0; k < 4; k++) r.q[k] = gload<double>(d + 3 + k);
   return r;
 }
-// PoseCeresToEig (types.cpp:33-38) as a KITTI row
-__device__ __forceinline__ void p3_to_rows(const P3& P, double* m) {
-  quat_to_rows(P.q, m);
-  m[3] = P.p[0]; m[7] = P.p[1]; m[11] = P.p[2];
-}
-__device__ __forceinline__ double norm3(double x, double y, double z) { return __dsqrt_rn((x * x + y * y) + z * z); }
 
 // best_fit_transform(A = Tgt.p, B = T.p), eval_trajectory.cpp:343-368, in the layout cfear_align_from_sums reads: x = A, y = B
+struct GfAlignSrc {
+  static constexpr bool kSkips = true;
+  const cfear_pose3d *T, *G;
+  const uint8_t* has;
+  int n;
+  __device__ bool counts(int i) const { return has[i] != 0; }
+  __device__ double x(int i, int k) const { return gload<double>((const double*)(G + i) + k); }
+  __device__ double y(int i, int k) const { return gload<double>((const double*)(T + i) + k); }
+  __device__ double mean_div(double n_gt) const { return fmax(n_gt, 1.0); }   // std::max(row, 1), :361
+  __device__ double cov(double sum) const { return sum; }                     // H = AA^T BB is not divided by the rows (:368)
+};
 __global__ __launch_bounds__(kGfThreads) void graph_align_sums_kernel(GfAlignArgs a) {
   __shared__ double red[4];
   const GfGraph g = a.graphs[blockIdx.x];
-  const cfear_pose3d* T = a.poses + g.first;
-  const cfear_pose3d* G = a.gt + g.first;
-  const uint8_t* has = a.has_gt + g.first;
-  double s[6] = {0, 0, 0, 0, 0, 0}, cnt = 0.0;
-  for (int i = threadIdx.x; i < g.n; i += kGfThreads) {
-    if (!has[i]) continue;
-    cnt += 1.0;
-#pragma unroll
-    for (int k = 0; k < 3; k++) { s[k] += gload<double>((const double*)(G + i) + k); s[3 + k] += gload<double>((const double*)(T + i) + k); }
-  }
-  const double n_gt = block_sum(cnt, red);           // a count: exact
-  const double rows = fmax(n_gt, 1.0);               // std::max(row, 1), :361
-  double mean[6];
-#pragma unroll
-  for (int k = 0; k < 6; k++) mean[k] = block_sum(s[k], red) / rows;
-  double c[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (int i = threadIdx.x; i < g.n; i += kGfThreads) {
-    if (!has[i]) continue;
-    double x[3], y[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      x[k] = gload<double>((const double*)(G + i) + k) - mean[k];
-      y[k] = gload<double>((const double*)(T + i) + k) - mean[3 + k];
-    }
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-      for (int q = 0; q < 3; q++) c[3 * r + q] += y[r] * x[q];
-  }
-  double* out = a.sums + (size_t)blockIdx.x * 16;
-#pragma unroll
-  for (int k = 0; k < 9; k++) {
-    const double v = block_sum(c[k], red);           // H = AA^T BB is not divided by the rows (:368)
-    if (threadIdx.x == 0) out[6 + k] = v;
-  }
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < 6; k++) out[k] = mean[k];
-    out[15] = n_gt;
-  }
+  align_sums(GfAlignSrc{a.poses + g.first, a.gt + g.first, a.has_gt + g.first, g.n}, a.sums + (size_t)blockIdx.x * 16, red);
 }
 
 // itr->second.T = PoseEigToCeres(Tgtalign * itr->second.GetPose()), :252
@@ -142,22 +106,18 @@ __global__ __launch_bounds__(kGfThreads) void graph_align_apply_kernel(GfAlignAr
   if (i >= g.n) return;
   const GfPost& post = a.post[blk.x];
   if (!post.apply) return;
-  double A[12], B[12], R[12], q[4];
+  Pose A, B;
+  double q[4];
 #pragma unroll
-  for (int k = 0; k < 12; k++) A[k] = post.align[k];
+  for (int k = 0; k < 12; k++) A.m[k] = post.align[k];
   cfear_pose3d* at = a.poses + g.first + i;
-  p3_to_rows(p3_load(at), B);
-#pragma unroll
-  for (int r = 0; r < 3; r++) {
-#pragma unroll
-    for (int c = 0; c < 3; c++) R[4 * r + c] = (A[4 * r] * B[c] + A[4 * r + 1] * B[4 + c]) + A[4 * r + 2] * B[8 + c];
-    R[4 * r + 3] = ((A[4 * r] * B[3] + A[4 * r + 1] * B[7]) + A[4 * r + 2] * B[11]) + A[4 * r + 3];
-  }
-  quat_from_rows(R, q);
+  pose3d_to_rows(pose3d_load(at), B.m);
+  const Pose R = pose_mul(A, B);
+  quat_from_rows(R.m, q);
   // Quaternion::normalize(): coeffs() /= norm(), the squared norm a 2-wide packet reduction, (xx + zz) + (yy + ww)
   const double norm = __dsqrt_rn((q[0] * q[0] + q[2] * q[2]) + (q[1] * q[1] + q[3] * q[3]));
   double* d = (double*)at;
-  gstore<double>(d + 0, R[3]); gstore<double>(d + 1, R[7]); gstore<double>(d + 2, R[11]);
+  gstore<double>(d + 0, R.m[3]); gstore<double>(d + 1, R.m[7]); gstore<double>(d + 2, R.m[11]);
 #pragma unroll
   for (int k = 0; k < 4; k++) gstore<double>(d + 3 + k, q[k] / norm);
 }
@@ -198,8 +158,8 @@ __global__ __launch_bounds__(kGfThreads) void graph_map_kernel(GfMapArgs a) {
   const int2 tile = a.tiles[blockIdx.x];
   const GfMapNode rec = a.nodes[tile.x];
   const bool with_gt = rec.dst_gt >= 0;
-  if (threadIdx.x == 0) p3_to_rows(p3_load(a.poses + rec.node), M[0]);
-  if (threadIdx.x == 1 && with_gt) p3_to_rows(p3_load(a.gt + rec.node), M[1]);
+  if (threadIdx.x == 0) pose3d_to_rows(pose3d_load(a.poses + rec.node), M[0]);
+  if (threadIdx.x == 1 && with_gt) pose3d_to_rows(pose3d_load(a.gt + rec.node), M[1]);
   __syncthreads();
   const int i = tile.y + (int)threadIdx.x;
   if (i >= rec.n) return;
@@ -208,46 +168,11 @@ __global__ __launch_bounds__(kGfThreads) void graph_map_kernel(GfMapArgs a) {
   if (with_gt) gstore<g_f32x4>(a.map_gt + (rec.dst_gt + i) * 4, tf_point(M[1], p));
 }
 
-// offsets [count + 1] run from 0 to `end` without descending
-bool offsets_ok(const int64_t* off, int64_t count, int64_t end) {
-  if (off[0] != 0 || off[count] != end) return false;
-  for (int64_t k = 0; k < count; k++)
-    if (off[k + 1] < off[k]) return false;
-  return true;
-}
-// 0: all host, 1: all device, -1: mixed; null pointers are skipped
-int memory_kind(std::initializer_list<const void*> ptrs) {
-  int n = 0, dev = 0;
-  for (const void* p : ptrs)
-    if (p) { n++; dev += cfear_is_device_ptr(p); }
-  return dev == 0 ? 0 : dev == n ? 1 : -1;
-}
-
-// Affine3d::inverse() of [R | t]: Eigen's compute_inverse_size3_helper (the cofactors of column 0 give the determinant, every
-// cofactor is multiplied by 1 / det), then t' = -(R' t)
-void affine_inverse(const double in[12], double out[12]) {
-  auto m = [&](int r, int c) { return in[4 * r + c]; };
-  auto cof = [&](int i, int j) {
-    const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
-    return m(i1, j1) * m(i2, j2) - m(i1, j2) * m(i2, j1);
-  };
-  const double c0 = cof(0, 0), c1 = cof(1, 0), c2 = cof(2, 0);
-  const double invdet = 1.0 / ((c0 * m(0, 0) + c1 * m(1, 0)) + c2 * m(2, 0));
-  for (int r = 0; r < 3; r++)
-    for (int c = 0; c < 3; c++) out[4 * r + c] = cof(c, r) * invdet;
-  for (int r = 0; r < 3; r++) out[4 * r + 3] = -((out[4 * r] * in[3] + out[4 * r + 1] * in[7]) + out[4 * r + 2] * in[11]);
-}
-
-const double kIdentity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-
-// MatToString (types.cpp:64-73) of PoseCeresToEig(p).matrix(): std::fixed, the stream's 6 decimals
+// MatToString (types.cpp:64-73) of PoseCeresToEig(p).matrix()
 bool write_pose_row(FILE* f, const cfear_pose3d& p, const char* end) {
   double m[12];
-  quat_to_rows(p.q, m);
-  m[3] = p.p[0]; m[7] = p.p[1]; m[11] = p.p[2];
-  for (int k = 0; k < 12; k++)
-    if (fprintf(f, k == 11 ? "%.6f%s" : "%.6f ", m[k], end) <= 0) return false;
-  return true;
+  pose3d_to_rows(p, m);
+  return kitti_row_write(f, m, end);
 }
 }  // namespace
 
@@ -259,7 +184,7 @@ extern "C" int cfear_graph_align_batch(cfear_ctx* ctx, cfear_pose3d* poses, cons
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
   if (cfear_is_device_ptr(node_offsets) || cfear_is_device_ptr(summaries))
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "node_offsets and summaries must be host memory");
-  if (!offsets_ok(node_offsets, n_graphs, n_nodes))
+  if (!check_offsets(node_offsets, n_graphs, n_nodes).fine())
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "node_offsets must run from 0 to n_nodes without descending");
   const int kind = n_nodes ? memory_kind({poses, gt, has_gt}) : 0;
   if (kind < 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "poses, gt and has_gt must be all host or all device memory");
@@ -267,36 +192,30 @@ extern "C" int cfear_graph_align_batch(cfear_ctx* ctx, cfear_pose3d* poses, cons
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "device poses must be 8-byte aligned");
   std::vector<GfGraph> graphs((size_t)n_graphs);
   std::vector<int2> blocks;
+  bool grid_ok = true;
   for (int g = 0; g < n_graphs; g++) {
     const int64_t n = node_offsets[g + 1] - node_offsets[g];
     if (n > INT32_MAX - kGfThreads) return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "graph %d holds more than 2^31 nodes", g);
     graphs[g] = GfGraph{node_offsets[g], (int32_t)n, 0};
-    for (int64_t i = 0; i < n; i += kGfThreads) blocks.push_back(make_int2(g, (int)i));
+    grid_ok = flat_grid_add(blocks, g, n, kGfThreads) && grid_ok;
   }
-  if (blocks.size() > (size_t)INT32_MAX) return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "more than 2^31 x 256 nodes in one call");
+  if (!grid_ok) return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "more than 2^31 x 256 nodes in one call");
   if (!ctx) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null context");
   if (n_graphs == 0) return CFEAR_OK;
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const size_t tab_graphs = ((size_t)n_graphs * sizeof(GfGraph) + 15) & ~(size_t)15, tab1 = tab_graphs + blocks.size() * sizeof(int2);
-  const size_t tab2 = (size_t)n_graphs * sizeof(GfPost);
   HostStage st(ctx, kWsGraphFinish);
   GfAlignArgs a{};
-  char *d_tab1, *d_tab2;
   st.in(a.poses, poses, (size_t)n_nodes * sizeof(cfear_pose3d), true);
   st.in(a.gt, gt, (size_t)n_nodes * sizeof(cfear_pose3d));
   st.in(a.has_gt, has_gt, (size_t)n_nodes);
-  st.piece(d_tab1, tab1);
-  st.piece(d_tab2, tab2);
+  StagedTables tab(st, (size_t)n_graphs * sizeof(GfGraph), blocks.size() * sizeof(int2), (size_t)n_graphs * sizeof(GfPost));
   st.piece(a.sums, (size_t)n_graphs * 16 * 8);
   st.piece(a.ate, (size_t)n_graphs * 8);
   CFEAR_CHECK(st.carve());
-  char* h = (char*)st.record(tab1 + tab2);
-  memcpy(h, graphs.data(), (size_t)n_graphs * sizeof(GfGraph));
-  if (!blocks.empty()) memcpy(h + tab_graphs, blocks.data(), blocks.size() * sizeof(int2));
-  CFEAR_CHECK(st.upload(d_tab1, h, tab1));
-  a.graphs = (const GfGraph*)d_tab1;
-  a.blocks = (const int2*)(d_tab1 + tab_graphs);
-  a.post = (const GfPost*)d_tab2;
+  CFEAR_CHECK(tab.upload(graphs.data(), blocks.data()));
+  a.graphs = tab.records<GfGraph>();
+  a.blocks = tab.blocks<int2>();
+  a.post = tab.second<GfPost>();
   {
     ProfScope ps(ctx, "graph_align_sums");
     hipLaunchKernelGGL(graph_align_sums_kernel, dim3(n_graphs), dim3(kGfThreads), 0, ctx->stream, a);
@@ -306,7 +225,7 @@ extern "C" int cfear_graph_align_batch(cfear_ctx* ctx, cfear_pose3d* poses, cons
   st.fetch(h_sums.data(), a.sums, h_sums.size() * 8);
   CFEAR_CHECK(st.wait());
   // host half: best_fit_transform's SVD (:376-393) and the inverse of :249
-  GfPost* post = (GfPost*)(h + tab1);
+  GfPost* post = tab.host_second<GfPost>();
   std::vector<int32_t> status((size_t)n_graphs, CFEAR_OK);
   for (int g = 0; g < n_graphs; g++) {
     const double* s = h_sums.data() + (size_t)g * 16;
@@ -323,11 +242,11 @@ extern "C" int cfear_graph_align_batch(cfear_ctx* ctx, cfear_pose3d* poses, cons
     post[g].apply = ok && finite;
     post[g].pad = 0;
     if (!post[g].apply) {
-      memcpy(post[g].align, kIdentity, sizeof(kIdentity));
+      memcpy(post[g].align, kIdentityRows, sizeof(kIdentityRows));
       status[g] = CFEAR_ERR_SOLVER;
     }
   }
-  CFEAR_CHECK(st.upload(d_tab2, post, tab2));
+  CFEAR_CHECK(tab.upload_second());
   if (!blocks.empty()) {
     ProfScope ps(ctx, "graph_align_apply");
     hipLaunchKernelGGL(graph_align_apply_kernel, dim3((unsigned)blocks.size()), dim3(kGfThreads), 0, ctx->stream, a);
@@ -340,7 +259,7 @@ extern "C" int cfear_graph_align_batch(cfear_ctx* ctx, cfear_pose3d* poses, cons
   st.fetch(h_ate.data(), a.ate, h_ate.size() * 8);
   CFEAR_CHECK(st.finish());
   for (int g = 0; g < n_graphs; g++) {
-    memcpy(summaries[g].align, post[g].align, sizeof(kIdentity));
+    memcpy(summaries[g].align, post[g].align, sizeof(post[g].align));
     summaries[g].ate = h_ate[g];
     summaries[g].n_gt = (int32_t)h_sums[(size_t)g * 16 + 15];
     summaries[g].status = status[g];
@@ -361,9 +280,9 @@ extern "C" int cfear_graph_map_batch(cfear_ctx* ctx, const cfear_pose3d* poses, 
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
   if (cfear_is_device_ptr(node_offsets) || cfear_is_device_ptr(cloud_offsets) || cfear_is_device_ptr(summaries))
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "node_offsets, cloud_offsets and summaries must be host memory");
-  if (!offsets_ok(node_offsets, n_graphs, n_nodes))
+  if (!check_offsets(node_offsets, n_graphs, n_nodes).fine())
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "node_offsets must run from 0 to n_nodes without descending");
-  if (!offsets_ok(cloud_offsets, n_nodes, n_points))
+  if (!check_offsets(cloud_offsets, n_nodes, n_points).fine())
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "cloud_offsets must run from 0 to n_points without descending");
   const int in_kind = memory_kind({n_nodes ? poses : nullptr, n_nodes && want_gt ? gt : nullptr, n_nodes && want_gt ? has_gt : nullptr,
                                    n_points ? xyzi : nullptr});
@@ -400,9 +319,8 @@ extern "C" int cfear_graph_map_batch(cfear_ctx* ctx, const cfear_pose3d* poses, 
       if (n > INT32_MAX - kMapTile) return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "node %lld holds more than 2^31 points", (long long)k);
       const bool with_gt = want_gt && has_gt[k];
       if (n > 0 && !too_many) {
-        for (int64_t i = 0; i < n; i += kMapTile) tiles.push_back(make_int2((int)nodes.size(), (int)i));
+        too_many = !flat_grid_add(tiles, (int32_t)nodes.size(), n, kMapTile);
         nodes.push_back(GfMapNode{cloud_offsets[k], total, with_gt ? total_gt : -1, (int32_t)n, (int32_t)k});
-        too_many = tiles.size() > (size_t)INT32_MAX;
       }
       total += n;
       if (with_gt) total_gt += n;
@@ -415,24 +333,19 @@ extern "C" int cfear_graph_map_batch(cfear_ctx* ctx, const cfear_pose3d* poses, 
                            (long long)total, (long long)(want_gt ? total_gt : 0), (long long)map_cap, (long long)(want_gt ? map_gt_cap : 0));
   if (too_many) return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "more than 2^31 tiles in one call");
   if (total == 0) return CFEAR_OK;
-  const size_t tab_nodes = nodes.size() * sizeof(GfMapNode), tab = tab_nodes + tiles.size() * sizeof(int2);
   HostStage st(ctx, kWsGraphFinish);
   GfMapArgs a{};
-  char* d_tab;
   st.in(a.poses, poses, (size_t)n_nodes * sizeof(cfear_pose3d));
   if (want_gt) st.in(a.gt, gt, (size_t)n_nodes * sizeof(cfear_pose3d));
   st.in(a.xyzi, xyzi, (size_t)n_points * 16);
   st.out(a.map, map, (size_t)total * 16);
   if (want_gt && total_gt > 0) st.out(a.map_gt, map_gt, (size_t)total_gt * 16);
-  st.piece(d_tab, tab);
+  // megabytes at a realistic size: staged in pinned memory
+  StagedTables tab(st, nodes.size() * sizeof(GfMapNode), tiles.size() * sizeof(int2), 0, true);
   CFEAR_CHECK(st.carve());
-  char* h = (char*)st.pinned(tab);                    // megabytes at a realistic size: staged in pinned memory
-  if (!h) return CFEAR_ERR_HIP;
-  memcpy(h, nodes.data(), tab_nodes);
-  memcpy(h + tab_nodes, tiles.data(), tiles.size() * sizeof(int2));
-  CFEAR_CHECK(st.upload(d_tab, h, tab));
-  a.nodes = (const GfMapNode*)d_tab;
-  a.tiles = (const int2*)(d_tab + tab_nodes);
+  CFEAR_CHECK(tab.upload(nodes.data(), tiles.data()));
+  a.nodes = tab.records<GfMapNode>();
+  a.tiles = tab.blocks<int2>();
   {
     ProfScope ps(ctx, "graph_map");
     hipLaunchKernelGGL(graph_map_kernel, dim3((unsigned)tiles.size()), dim3(kGfThreads), 0, ctx->stream, a);

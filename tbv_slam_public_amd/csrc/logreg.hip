@@ -43,19 +43,10 @@ struct LrJob {
 
 enum LrFlag : int { kLrContinue = 0, kLrConverged, kLrFailed, kLrAccepted, kLrRetry };
 
-template <int CTRL> __device__ __forceinline__ double dpp_f64(double v) {
-  const long long b = __double_as_longlong(v);
-  int lo = (int)b, hi = (int)(b >> 32);
-  lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false);
-  hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-// the same bits in every lane: each level adds a pair both ways round, and a + b == b + a
-__device__ __forceinline__ double wave_sum(double v) {
-  v += dpp_f64<0xB1>(v);                                     // quad_perm [1,0,3,2]
-  v += dpp_f64<0x4E>(v);                                     // quad_perm [2,3,0,1]
-  v += dpp_f64<0x141>(v);                                    // row_half_mirror
-  v += dpp_f64<0x140>(v);                                    // row_mirror
+// The same bits in every lane: each level adds a pair both ways round, and a + b == b + a.  Not common.hpp's wave_sum_f64
+// nor pgo_batch.hip's sum: the order of the additions differs, so the rounding does.
+__device__ __forceinline__ double wave_sum_rows_xor16_xor32(double v) {
+  v = row16_sum_f64(v);                                      // the DPP butterfly inside each row of 16 lanes
   v += __shfl_xor(v, 16);
   v += __shfl_xor(v, 32);
   return v;
@@ -66,7 +57,7 @@ template <int N> __device__ void block_sums(double (&acc)[N], double* part, doub
   const int lane = threadIdx.x & (CFEAR_WAVE - 1), wave = threadIdx.x / CFEAR_WAVE;
 #pragma unroll
   for (int k = 0; k < N; k++) {
-    const double s = wave_sum(acc[k]);
+    const double s = wave_sum_rows_xor16_xor32(acc[k]);
     if (lane == 0) part[wave * N + k] = s;
   }
   __syncthreads();

@@ -369,14 +369,6 @@ __global__ __launch_bounds__(kCurveThreads) void loop_curves_kernel(const CurveA
   }
 }
 
-// offsets [n + 1] must run from 0 to total without descending; returns the index of the range that does not, -2 if fine
-int bad_offsets(const int64_t* off, int32_t n, int64_t total) {
-  if (off[0] != 0) return n > 0 ? 0 : -1;
-  for (int32_t g = 0; g < n; g++)
-    if (off[g + 1] < off[g] || off[g + 1] > total) return g;
-  if (off[n] != total) return n > 0 ? n - 1 : -1;
-  return -2;
-}
 int next_pow2(int64_t n) {
   int p = CFEAR_WAVE * 2;                                        // a pair per lane of a wavefront at least
   while (p < n) p <<= 1;
@@ -408,12 +400,10 @@ extern "C" int cfear_loop_stats_batch(cfear_ctx* ctx, const int64_t* node_offset
       std::isnan(par->no_loop_distance) || par->min_index_gap < 0)
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "a parameter is NaN, or min_index_gap is negative");
   if (cfear_is_device_ptr(node_offsets)) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "node_offsets must be host memory");
-  int n_dev = 0, n_buf = 0;
-  for (const void* p : {(const void*)gt_xyt, (const void*)has_gt, (const void*)candidates, (const void*)rows})
-    if (p) { n_buf++; n_dev += cfear_is_device_ptr(p); }
-  if (n_dev != 0 && n_dev != n_buf)
+  const int kind = memory_kind({gt_xyt, has_gt, candidates, rows});
+  if (kind < 0)
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "gt_xyt, has_gt, candidates and rows must be all host or all device memory");
-  const int bad_graph = bad_offsets(node_offsets, n_graphs, n_nodes);
+  const int bad_graph = (int)check_offsets(node_offsets, n_graphs, n_nodes).first_fault();
   if (bad_graph != -2)
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "graph %d: node_offsets must run from 0 to n_nodes over n_graphs + 1 entries without descending", bad_graph);
   for (int32_t g = 0; g < n_graphs; g++)
@@ -421,7 +411,7 @@ extern "C" int cfear_loop_stats_batch(cfear_ctx* ctx, const int64_t* node_offset
       return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "graph %d: more than 2^31 - 1 nodes", g);
   if ((n_cand + kStatsWaves - 1) / kStatsWaves > INT32_MAX || (n_nodes + kStatsThreads - 1) / kStatsThreads > INT32_MAX)
     return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "more candidates or nodes than one launch addresses");
-  if (!n_dev) {
+  if (kind == 0) {
     for (int64_t i = 0; i < n_nodes; i++)
       if (has_gt[i] && !fin3(gt_xyt + 3 * i))
         return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "node %lld (flat index) has ground truth that is not finite", (long long)i);
@@ -446,7 +436,7 @@ extern "C" int cfear_loop_stats_batch(cfear_ctx* ctx, const int64_t* node_offset
   st.piece(a.flags, 16);
   CFEAR_CHECK(st.carve());
   a.n_nodes = n_nodes; a.n_cand = n_cand; a.n_graphs = n_graphs; a.par = *par;
-  if (n_dev) {
+  if (kind == 1) {
     unsigned long long* h = (unsigned long long*)st.record(16);
     h[0] = h[1] = ~0ull;
     CFEAR_CHECK(st.upload(a.flags, h, 16));
@@ -495,13 +485,9 @@ extern "C" int cfear_loop_curves_batch(cfear_ctx* ctx, const int64_t* row_offset
   if (std::isnan(par->p_threshold)) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "p_threshold is NaN");
   if (cfear_is_device_ptr(row_offsets) || cfear_is_device_ptr(results))
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "row_offsets and results must be host memory");
-  int n_dev = 0, n_buf = 0;
-  for (const void* p : {(const void*)y, (const void*)score, (const void*)pos_ok, (const void*)roc_fpr, (const void*)roc_tpr, (const void*)roc_thr,
-                        (const void*)pr_precision, (const void*)pr_recall, (const void*)pr_thr})
-    if (p) { n_buf++; n_dev += cfear_is_device_ptr(p); }
-  if (n_dev != 0 && n_dev != n_buf)
+  if (memory_kind({y, score, pos_ok, roc_fpr, roc_tpr, roc_thr, pr_precision, pr_recall, pr_thr}) < 0)
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "y, score, pos_ok and the six curve arrays must be all host or all device memory");
-  const int bad_exp = bad_offsets(row_offsets, n_exp, n_rows);
+  const int bad_exp = (int)check_offsets(row_offsets, n_exp, n_rows).first_fault();
   if (bad_exp != -2) {
     if (failed_experiment) *failed_experiment = bad_exp;
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "experiment %d: row_offsets must run from 0 to n_rows over n_exp + 1 entries without descending", bad_exp);

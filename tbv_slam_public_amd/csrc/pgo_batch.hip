@@ -53,12 +53,9 @@ struct PgoArgs {
   int32_t max_iter, pad;
 };
 
-// ---- wavefront helpers ------------------------------------------------------------------------------------------------
-__device__ inline double lane_value(double v, int lane) {      // v of `lane`, uniform
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-  return __hiloint2double(hi, lo);
-}
-__device__ inline double wave_sum(double v) {                  // the same bits in every lane: a + b == b + a at every level
+// ---- wavefront helpers (a lane's value, uniform: readlane_f64, common.hpp) ---------------------------------------------
+// Not common.hpp's wave_sum_f64 nor logreg.hip's sum: the order of the additions differs, so the rounding does.
+__device__ inline double wave_sum_xor32_to_1(double v) {         // the same bits in every lane: a + b == b + a at every level
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
@@ -140,7 +137,7 @@ __device__ double evaluate(const G& g, const cfear_pose3d* pts, bool with_jac) {
       for (int k = 0; k < 6; k++) g.Jat(c, i, 6 + k) = d[i][k] * sr;
   }
   __syncthreads();
-  return wave_sum(cost);
+  return wave_sum_xor32_to_1(cost);
 }
 
 // out[node][k] = sum over the node's blocks of sum_i J[i][side 6 + k] * w_i, w = J itself (column norms) or the residuals
@@ -210,7 +207,7 @@ __device__ void JtJv(const G& g, const double* v, double radius, double* out) {
 __device__ double dot(const G& g, const double* a, const double* b) {
   double s = 0;
   for (int k = g.lane; k < 6 * g.n; k += kPgoThreads) s += a[k] * b[k];
-  return wave_sum(s);
+  return wave_sum_xor32_to_1(s);
 }
 
 // ChainPrecond::build, first half: H(i, i) into Ld and H(i, i-1) into Lo, node by node
@@ -254,12 +251,12 @@ __device__ bool factor_chain(const G& g, bool with_chain) {
       // Lo = E Lp^-T (row r by forward substitution); S -= Lo Lo^T
       for (int q = 0; q < 6; q++) {
         double s = g.Lo[(size_t)36 * nd + r * 6 + q];
-        for (int k = 0; k < q; k++) s -= X[k] * lane_value(Lp[k], q);
-        X[q] = s / lane_value(Lp[q], q);
+        for (int k = 0; k < q; k++) s -= X[k] * readlane_f64(Lp[k], q);
+        X[q] = s / readlane_f64(Lp[q], q);
       }
       for (int q = 0; q < 6; q++) {
         double s = 0;
-        for (int k = 0; k < 6; k++) s += X[k] * lane_value(X[k], q);
+        for (int k = 0; k < 6; k++) s += X[k] * readlane_f64(X[k], q);
         S[q] -= s;
       }
     }
@@ -267,8 +264,8 @@ __device__ bool factor_chain(const G& g, bool with_chain) {
     double Lr[6] = {0, 0, 0, 0, 0, 0};
     for (int j = 0; j < 6; j++) {
       double s = S[j];
-      for (int k = 0; k < j; k++) s -= Lr[k] * lane_value(Lr[k], j);
-      const double piv = lane_value(s, j);
+      for (int k = 0; k < j; k++) s -= Lr[k] * readlane_f64(Lr[k], j);
+      const double piv = readlane_f64(s, j);
       if (!(piv > 0.0)) { ok = false; break; }
       const double dj = std::sqrt(piv);
       Lr[j] = r == j ? dj : (r > j ? s / dj : 0.0);
@@ -301,7 +298,7 @@ __device__ void precond_apply(const G& g, const double* rv, double* z) {
       double s = rhs;
       for (int t = 0; t < kk; t++) s -= ld[t] * zu[t];
       s /= ld[kk];
-      zu[kk] = lane_value(s, kk);
+      zu[kk] = readlane_f64(s, kk);
       if (k == kk) mine = s;
     }
     if (g.lane < 6) z[(size_t)6 * nd + k] = mine;
@@ -327,7 +324,7 @@ __device__ void precond_apply(const G& g, const double* rv, double* z) {
       double s = rhs;
       for (int t = kk + 1; t < 6; t++) s -= ld[t] * zu[t];
       s /= dg;
-      zu[kk] = lane_value(s, kk);
+      zu[kk] = readlane_f64(s, kk);
       if (k == kk) mine = s;
     }
     if (g.lane < 6) z[(size_t)6 * nd + k] = mine;
@@ -344,7 +341,7 @@ __device__ double x_norm_of(const G& g) {
     for (int k = 0; k < 3; k++) s += g.x[i].p[k] * g.x[i].p[k];
     for (int k = 0; k < 4; k++) s += g.x[i].q[k] * g.x[i].q[k];
   }
-  return std::sqrt(wave_sum(s));
+  return std::sqrt(wave_sum_xor32_to_1(s));
 }
 __device__ double max_abs(const G& g, const double* v) {
   double m = 0;
@@ -440,7 +437,7 @@ __global__ __launch_bounds__(kPgoThreads) void pgo_batch_kernel(PgoArgs a) {
       double s = 0.0;
       for (int c = lane; c < g.m; c += kPgoThreads)
         for (int i = 0; i < 6; i++) { const double t = g.t[(size_t)i * g.m + c]; s -= t * (g.res[(size_t)i * g.m + c] + t / 2.0); }
-      model_cost_change = wave_sum(s);
+      model_cost_change = wave_sum_xor32_to_1(s);
     }
     if (!finite || !(model_cost_change > 0.0)) {                   // HandleInvalidStep
       if (++invalid >= 5) { usable = false; break; }
@@ -462,7 +459,7 @@ __global__ __launch_bounds__(kPgoThreads) void pgo_batch_kernel(PgoArgs a) {
       for (int k = 0; k < 4; k++) step_norm2 += (xi.q[k] - ci.q[k]) * (xi.q[k] - ci.q[k]);
     }
     __syncthreads();
-    step_norm2 = wave_sum(step_norm2);
+    step_norm2 = wave_sum_xor32_to_1(step_norm2);
     const double cand_cost = evaluate(g, g.cand, false);
     if (std::sqrt(step_norm2) <= parameter_tolerance * (x_norm + parameter_tolerance)) break;    // ParameterToleranceReached
     const double cost_change = x_cost - cand_cost;
@@ -523,13 +520,14 @@ extern "C" int cfear_pgo_solve_batch(cfear_ctx* ctx, cfear_pose3d* poses, const 
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
   if (cfear_is_device_ptr(poses) || cfear_is_device_ptr(summaries))
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "poses and summaries must be host memory");
-  if (node_offsets[0] != 0 || constraint_offsets[0] != 0 || node_offsets[n_graphs] != n_nodes || constraint_offsets[n_graphs] != n_constraints)
+  const OffsetsReport nodes = check_offsets(node_offsets, n_graphs, n_nodes), cons = check_offsets(constraint_offsets, n_graphs, n_constraints);
+  if (nodes.start_not_0 || cons.start_not_0 || nodes.end_not_total || cons.end_not_total)
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "offsets must run from 0 to n_nodes / n_constraints over n_graphs + 1 entries");
+  const int64_t descends = std::min(nodes.descends, cons.descends);   // between a right start and a right end only a descent is left
   for (int gi = 0; gi < n_graphs; gi++)
-    if (node_offsets[gi + 1] < node_offsets[gi] || constraint_offsets[gi + 1] < constraint_offsets[gi] ||
-        node_offsets[gi + 1] - node_offsets[gi] > INT32_MAX / 72 || constraint_offsets[gi + 1] - constraint_offsets[gi] > INT32_MAX / 72) {
+    if (gi == descends || node_offsets[gi + 1] - node_offsets[gi] > INT32_MAX / 72 || constraint_offsets[gi + 1] - constraint_offsets[gi] > INT32_MAX / 72) {
       if (failed_graph) *failed_graph = gi;
-      return cfear_set_error(ctx, node_offsets[gi + 1] < node_offsets[gi] || constraint_offsets[gi + 1] < constraint_offsets[gi] ? CFEAR_ERR_INVALID_ARGUMENT : CFEAR_ERR_CAPACITY,
+      return cfear_set_error(ctx, gi == descends ? CFEAR_ERR_INVALID_ARGUMENT : CFEAR_ERR_CAPACITY,
                              "graph %d: offsets descend, or more than %d nodes / constraints", gi, INT32_MAX / 72);
     }
   if (n_graphs == 0) return CFEAR_OK;

@@ -16,7 +16,7 @@
 //                                             the kept flags (ballot + popcount); independent mode skips the recurrence
 //   sync_interp   thread per estimate         pose_interp of the kept estimates, written compacted
 // Everything is fp64 without contraction (-ffp-contract=off).  The three Eigen 3.3 routines pose_interp calls (matrix ->
-// quaternion, slerp, toRotationMatrix) and roscpp's toSec are restated here operation by operation; neither Eigen nor ROS
+// quaternion and toRotationMatrix in eigen_quat.hpp, slerp here) and roscpp's toSec are restated operation by operation; neither Eigen nor ROS
 // is part of the reference tree or of this build ("restated, not pinned").
 #include <algorithm>
 #include <cfloat>
@@ -25,8 +25,7 @@
 #include <cstdio>
 #include <vector>
 
-#include "common.hpp"
-#include "eigen_quat.hpp"   // sqrt_rn, quat_from_rows: Eigen 3.3 Quaternion(Matrix3d), no normalisation
+#include "pose_rows.hpp"    // Pose; eigen_quat.hpp: quat_from_rows (Eigen 3.3 Quaternion(Matrix3d), no normalisation), quat_to_rows
 
 namespace {
 constexpr int kSyncThreads = 256;
@@ -64,18 +63,6 @@ __host__ __device__ __forceinline__ double to_sec(int64_t ns) {
 }
 __host__ __device__ __forceinline__ bool stamp_ok(int64_t ns) { return ns >= 0 && ns / kNsPerSec <= kMaxSec; }
 
-struct Pose { double m[12]; };
-__device__ __forceinline__ Pose pose_load(const double* p) {
-  Pose r;
-#pragma unroll
-  for (int k = 0; k < 12; k += 2) { const g_f64x2 v = gload<g_f64x2>(p + k); r.m[k] = v.x; r.m[k + 1] = v.y; }
-  return r;
-}
-__device__ __forceinline__ void pose_store(double* p, const Pose& r) {
-#pragma unroll
-  for (int k = 0; k < 12; k += 2) { g_f64x2 v; v.x = r.m[k]; v.y = r.m[k + 1]; gstore<g_f64x2>(p + k, v); }
-}
-
 // pose_interp, :461-491
 __device__ __forceinline__ Pose pose_interp(double alpha, const Pose& A, const Pose& B) {
   double qa[4], qb[4], q[4];
@@ -97,15 +84,8 @@ __device__ __forceinline__ Pose pose_interp(double alpha, const Pose& A, const P
   if (d < 0.0) scale1 = -scale1;
 #pragma unroll
   for (int k = 0; k < 4; k++) q[k] = scale0 * qa[k] + scale1 * qb[k];
-  // QuaternionBase::toRotationMatrix
-  const double tx = 2.0 * q[0], ty = 2.0 * q[1], tz = 2.0 * q[2];
-  const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
-  const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
-  const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
   Pose R;
-  R.m[0] = 1.0 - (tyy + tzz); R.m[1] = txy - twz;         R.m[2] = txz + twy;
-  R.m[4] = txy + twz;         R.m[5] = 1.0 - (txx + tzz); R.m[6] = tyz - twx;
-  R.m[8] = txz - twy;         R.m[9] = tyz + twx;         R.m[10] = 1.0 - (txx + tyy);
+  quat_to_rows(q, R.m);
   R.m[3] = (1.0 - alpha) * A.m[3] + alpha * B.m[3];
   R.m[7] = (1.0 - alpha) * A.m[7] + alpha * B.m[7];
   R.m[11] = 0.0;                                       // result.translation()(2) = 0, :488
@@ -239,6 +219,7 @@ extern "C" int cfear_sync_trajectories(cfear_ctx* ctx, int32_t mode, const doubl
   std::vector<SyncPair> pairs((size_t)n_traj);
   std::vector<int2> blocks;
   int64_t total_est = 0, total_gt = 0, span_est = 0, span_gt = 0;
+  bool grid_ok = true;
   for (int t = 0; t < n_traj; t++) {
     if (est_lengths[t] < 0 || gt_lengths[t] < 0)
       return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "pair %d: negative length", t);
@@ -249,21 +230,19 @@ extern "C" int cfear_sync_trajectories(cfear_ctx* ctx, int32_t mode, const doubl
     total_gt += gt_lengths[t];
     span_est = std::max(span_est, es + est_lengths[t]);
     span_gt = std::max(span_gt, gs + gt_lengths[t]);
-    for (int i = 0; i < est_lengths[t]; i += kSyncThreads) blocks.push_back(make_int2(t, i));
+    grid_ok = flat_grid_add(blocks, t, est_lengths[t], kSyncThreads) && grid_ok;
   }
   if (total_est > 0 && (!est_stamps || !stamps_out || !gt_out || !rows || (est && !est_out)))
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
   if (total_gt > 0 && (!gt || !gt_stamps)) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
-  int n_dev = 0, n_buf = 0;
-  for (const void* p : {(const void*)(total_est ? est : nullptr), (const void*)(total_est ? est_stamps : nullptr),
-                        (const void*)(total_gt ? gt : nullptr), (const void*)(total_gt ? gt_stamps : nullptr),
-                        (const void*)(total_est && est ? est_out : nullptr), (const void*)(total_est ? gt_out : nullptr),
-                        (const void*)(total_est ? stamps_out : nullptr), (const void*)(total_est ? rows : nullptr)})
-    if (p) { n_buf++; n_dev += cfear_is_device_ptr(p); }
-  if (n_dev != 0 && n_dev != n_buf)
+  const int kind = memory_kind({total_est ? est : nullptr, total_est ? est_stamps : nullptr, total_gt ? gt : nullptr,
+                                total_gt ? gt_stamps : nullptr, total_est && est ? est_out : nullptr, total_est ? gt_out : nullptr,
+                                total_est ? stamps_out : nullptr, total_est ? rows : nullptr});
+  if (kind < 0)
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT,
                            "est, est_stamps, gt, gt_stamps and the four outputs must be all host or all device memory");
-  if (!n_dev) {
+  const bool host = kind == 0;
+  if (host) {
     for (int t = 0; t < n_traj; t++) {
       const SyncPair& p = pairs[t];
       for (int i = 0; i < p.n_est; i++)
@@ -280,20 +259,16 @@ extern "C" int cfear_sync_trajectories(cfear_ctx* ctx, int32_t mode, const doubl
              (((uintptr_t)est_stamps | (uintptr_t)gt_stamps | (uintptr_t)stamps_out | (uintptr_t)rows) & 7)) {
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "device poses must be 16-byte aligned, device stamps and rows 8-byte aligned");
   }
-  if (blocks.size() > (size_t)INT32_MAX) return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "more than 2^31 x 256 estimates in one call");
+  if (!grid_ok) return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "more than 2^31 x 256 estimates in one call");
   if (!ctx) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null context");
   if (n_traj == 0) return CFEAR_OK;
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const bool host = !n_dev;
   if (total_est == 0 && host) {                        // nothing to search, nothing to launch
     for (int t = 0; t < n_traj; t++) counts[t] = 0;
     return CFEAR_OK;
   }
-  const size_t tab_pairs = ((size_t)n_traj * sizeof(SyncPair) + 15) & ~(size_t)15, tab = tab_pairs + blocks.size() * sizeof(int2);
   HostStage st(ctx, kWsTrajSync);
   SyncArgs a{};
-  char* d_tab;
-  unsigned long long* d_flags;
   st.in(a.est, est, (size_t)span_est * 96);
   st.in(a.est_stamps, est_stamps, (size_t)span_est * 8);
   st.in(a.gt, gt, (size_t)span_gt * 96);
@@ -307,23 +282,20 @@ extern "C" int cfear_sync_trajectories(cfear_ctx* ctx, int32_t mode, const doubl
   } else {
     a.est_out = est_out; a.gt_out = gt_out; a.stamps_out = stamps_out; a.rows = rows;
   }
-  st.piece(d_tab, tab);
+  StagedTables tab(st, (size_t)n_traj * sizeof(SyncPair), blocks.size() * sizeof(int2), 32);   // second piece: the check's flags
   st.piece(a.range, (size_t)total_est * sizeof(int2));
   st.piece(a.counts, (size_t)n_traj * 4);
-  st.piece(d_flags, 32);
   CFEAR_CHECK(st.carve());
-  char* h = (char*)st.record(tab + 32);
-  memcpy(h, pairs.data(), (size_t)n_traj * sizeof(SyncPair));
-  memcpy(h + tab_pairs, blocks.data(), blocks.size() * sizeof(int2));
-  CFEAR_CHECK(st.upload(d_tab, h, tab));
-  a.pairs = (const SyncPair*)d_tab;
-  a.blocks = (const int2*)(d_tab + tab_pairs);
+  CFEAR_CHECK(tab.upload(pairs.data(), blocks.data()));
+  a.pairs = tab.records<SyncPair>();
+  a.blocks = tab.blocks<int2>();
   a.n_traj = n_traj;
   a.mode = mode;
+  unsigned long long* const d_flags = tab.second<unsigned long long>();
   if (!host) {                                         // also without a single estimate: the ground truth is checked as a host caller's is
-    unsigned long long* hf = (unsigned long long*)(h + tab);
+    unsigned long long* hf = tab.host_second<unsigned long long>();
     hf[0] = hf[1] = hf[2] = hf[3] = ~0ull;
-    CFEAR_CHECK(st.upload(d_flags, hf, 32));
+    CFEAR_CHECK(tab.upload_second());
     a.flags = d_flags;
     ProfScope ps(ctx, "sync_check");
     const int64_t longest = std::max<int64_t>(*std::max_element(est_lengths, est_lengths + n_traj), *std::max_element(gt_lengths, gt_lengths + n_traj));

@@ -240,6 +240,17 @@ def align_cases():
     has = np.ones(12, np.uint8)
     has[7] = 0
     _ALIGN["collinear"] = (off_line, line, has)
+    # the edges of the sums' workgroup of 256 threads: one node per thread, one node more, two nodes (one with ground truth:
+    # two are always collinear), and a 300-node graph in which one whole wavefront of the workgroup counts nothing
+    for n, seed in ((256, 5), (257, 6)):
+        est, gt = G.lap(n, seed, planar=False)
+        _ALIGN["%d nodes" % n] = (est, gt, np.ones(n, np.uint8))
+    est, gt = G.lap(2, 7)
+    _ALIGN["two nodes"] = (est, gt, np.array([0, 1], np.uint8))
+    est, gt = G.lap(300, 8, planar=False)
+    has = np.ones(300, np.uint8)
+    has[64:128] = 0
+    _ALIGN["a wavefront without ground truth"] = (est, gt, has)
     return _ALIGN
 
 

@@ -173,6 +173,7 @@ def test_synthetic_inputs_against_the_restatement(alignment, step):
     rng = np.random.default_rng(100 * step + len(alignment))
     pairs = {"planar": planar(rng, 1500), "planar, 6 decimals": planar(rng, 1200, decimals=6), "3-D": spatial(rng, 1400),
              "3-D short": spatial(rng, 300), "shorter than 100 m": planar(rng, 40), "two poses": planar(rng, 2),
+             "one pose per thread": planar(rng, 256), "one pose more than threads": spatial(rng, 257),
              "exact steps, stationary stretches": exact_steps()}
     if alignment == "6dof":
         del pairs["two poses"]                          # two positions lie on a line: see test_degenerate_alignment_is_reported

@@ -190,6 +190,46 @@ def test_refusals_name_the_graph_and_leave_poses_untouched(ctx):
     assert rc == L.OK and bad == -1 and after.tobytes() != before.tobytes()
 
 
+def _tables_call(ctx, node, n_nodes, con, n_cons):
+    """Two offset tables alone: a malformed one is refused before an array is read -> (rc, failed graph, message)."""
+    node, con = np.array(node, np.int64), np.array(con, np.int64)
+    poses, ids, cons = np.zeros((16, 7)), np.arange(16, dtype=np.uint64), np.zeros(16, L.GRAPH_CONSTRAINT_DTYPE)
+    summ = np.zeros(len(node), L.PGO_SUMMARY_DTYPE)
+    p, bad = L.PgoParams(), C.c_int32(-7)
+    ctx._lib.cfear_pgo_params_default(C.byref(p))
+    rc = ctx._lib.cfear_pgo_solve_batch(ctx.h, poses.ctypes.data, ids.ctypes.data, node.ctypes.data, n_nodes, cons.ctypes.data, con.ctypes.data,
+                                        n_cons, len(node) - 1, C.byref(p), summ.ctypes.data, C.byref(bad))
+    return rc, bad.value, ctx._lib.cfear_last_error(ctx.h).decode()
+
+
+def test_malformed_offset_tables_blame_the_same_graph_as_before(ctx):
+    """The tables of tests/test_batch_tables_cpu.py, as node offsets beside a sound constraint table and the other way
+    round.  This entry point asks for its context first, so it is not among that test's calls without a device.  It tests the
+    start and the end of both tables before any range, and then blames the first range that descends or is too large; the
+    literals are what the library answered before the checks were folded into one helper."""
+    from test_batch_tables_cpu import BIG, TABLES
+    inv, cap = L.ERR_INVALID_ARGUMENT, L.ERR_CAPACITY
+    ends = "offsets must run from 0 to n_nodes / n_constraints over n_graphs + 1 entries"
+    graph = "graph %d: offsets descend, or more than 29826161 nodes / constraints"
+    want = {"start not 0": (inv, -1, ends), "end short of total": (inv, -1, ends), "end past total": (inv, -1, ends),
+            "descends": (inv, 1, graph % 1), "leaves then descends": (inv, 2, graph % 2),
+            "first range leaves, second descends": (inv, 1, graph % 1), "descends and wrong end": (inv, -1, ends),
+            "start not 0 and descends": (inv, -1, ends), "no ranges, start not 0": (inv, -1, ends),
+            "no ranges, start not 0 but equal to total": (inv, -1, ends), "second range over capacity": (cap, 1, graph % 1)}
+    sound = {1: [0], 4: [0, 2, 4, 6]}
+    assert sorted(want) == sorted(t for t in TABLES if t not in ("fine", "empty ranges", "no ranges"))
+    for name, (off, total) in TABLES.items():
+        if name in want:
+            mine = sound[len(off)]
+            assert _tables_call(ctx, off, total, mine, mine[-1]) == want[name], ("node_offsets", name)
+            assert _tables_call(ctx, mine, mine[-1], off, total) == want[name], ("constraint_offsets", name)
+    # a descent in one table and a wrong end in the other: the ends are tested first; two descents: the earlier graph
+    assert _tables_call(ctx, [0, 5, 3, 8], 8, [0, 2, 4, 6], 7) == (inv, -1, ends)
+    assert _tables_call(ctx, [0, 3, 2, 8], 8, [0, 5, 3, 6], 6) == (inv, 1, graph % 1)
+    assert _tables_call(ctx, [0, 2, 2 + BIG, 3 + BIG], 3 + BIG, [0, 5, 3, 6], 6) == (inv, 1, graph % 1)
+    assert _tables_call(ctx, [0, 2 + BIG, 3 + BIG, 4 + BIG], 4 + BIG, [0, 3, 2, 6], 6) == (cap, 0, graph % 0)
+
+
 def test_sizes_from_two_nodes_to_8192_nodes_and_1024_loops(ctx):
     big = synth.pgo_lap_graph(8192, np.random.default_rng(21), n_loops=1024)[:3]
     small = synth.pgo_lap_graph(2, np.random.default_rng(22), n_loops=1)[:3]
