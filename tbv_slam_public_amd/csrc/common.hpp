@@ -15,6 +15,7 @@
 #include "../../include/cfear_hip.h"
 #include "batch_tables.hpp"
 #include "owned.hpp"
+#include "reg_layout.hpp"
 
 #define CFEAR_WAVE 64
 
@@ -304,10 +305,7 @@ struct ScanView {          // plain pointers into one slab; passed to kernels by
   int32_t cap;
   int32_t pad;
 };
-constexpr int kScanGrid = 32;                                  // grid cells per axis
-constexpr int kScanGridCells = kScanGrid * kScanGrid;
-constexpr int kScanGridStartPad = kScanGridCells + 8;          // u16 entries per scan: a multiple of 16 bytes
-__host__ __device__ inline int scan_grid_pad(int n) { return (n + 7) & ~7; }        // records per scan, padded: both record arrays are runs of 16-byte pieces
+// (kScanGrid, kScanGridCells, kScanGridStartPad, scan_grid_pad: reg_layout.hpp -- the matcher's LDS arithmetic is made of them)
 __host__ __device__ inline size_t scan_grid_bytes(int n) { return (size_t)kScanGridStartPad * 2 + (size_t)scan_grid_pad(n) * 10; }
 constexpr float kScanGridMinEdge = 2.0f;                       // cell edge floor [m]: the matcher's radius (registration.h:131)
 
@@ -389,20 +387,6 @@ int cfear_surface_launch(cfear_ctx* ctx, const void* d_jobs, int n_jobs, const c
                          const cfear_surface_polar* polar = nullptr, uint32_t* d_path_out = nullptr);
 // the route word (CFEAR_SURF_PATH_*) of job `job` of the last launch over d_scratch, read from its scratch header (waits for the stream)
 int cfear_surface_read_path(cfear_ctx* ctx, const char* d_scratch, int cap_points, int job, uint32_t* path);
-size_t cfear_reg_job_bytes();
-int cfear_reg_max_scans();
-void cfear_reg_fill_job(void* dst, const ScanView* views, int n_scans, const double* poses_xyt);
-size_t cfear_register_scratch_bytes(int pairs_cap);
-// Cost-only launches of the matcher (GetCost / cost sampling): n_samples = 0 evaluates each job
-// at its own source pose, n_samples = samples_per_axis^3 at the sampling grid around it; results then holds
-// max(n_samples, 1) records per job.  blocks_per_job workgroups share a job's samples (scratch: n_jobs x
-// blocks_per_job x cfear_register_scratch_bytes).
-struct RegCostMode {
-  int n_samples = 0, samples_per_axis = 0, blocks_per_job = 1;
-  double xy_half = 0.0, yaw_half = 0.0;
-  const cfear_reg_result* prior = nullptr;   // device, [n_jobs]: evaluate around prior[j].pose with itr = prior[j].outer_iters
-};
-// What the caller knows about the batch's registrations (the kernel decides per registration from the device-side sizes):
 // cfear_coral_quality_batch in two halves (coral.hip): launch, then read back -- host work of the caller in between
 struct CoralPending {
   explicit CoralPending(cfear_ctx* ctx) : stage(ctx, kWsCoral) {}
@@ -415,19 +399,6 @@ int cfear_coral_enqueue(cfear_ctx* ctx, const cfear_coral_job* jobs, int32_t n_j
                         CoralPending& pend);
 int cfear_coral_collect(cfear_ctx* ctx, const cfear_coral_job* jobs, CoralPending& pend, cfear_coral_result* results, double* per_point);
 
-// One registration of the matcher (matcher.hip).  The scan views come LAST so that a batch whose jobs use at most m scans can be
-// stored with the shorter stride reg_job_stride(m): a two-scan loop-closure candidate is 0.5 KB instead of 1.9 KB to build and
-// upload.  Kernels only ever touch scans[0 .. n_scans).
-constexpr int kRegMaxScans = 16;
-struct RegJob {
-  int32_t n_scans;
-  int32_t itr;                                // cost-only launches: this job's leftover itr_ (0: use par.itr)
-  double poses[kRegMaxScans][3];
-  ScanView scans[kRegMaxScans];
-};
-inline size_t reg_job_stride(int max_scans) {
-  return (offsetof(RegJob, scans) + (size_t)max_scans * sizeof(ScanView) + 15) & ~(size_t)15;
-}
 // One CorAl job of coral_kernel (coral.hip): two peak clouds on the DEVICE and their poses
 struct CoralJob {
   const float4* ref;
@@ -446,35 +417,6 @@ int cfear_coral_max_points();
 // r = u diag(1, 1, det u det v) v^T and t = mean y - r mean x; false (and r = I) when the second singular value vanishes
 bool cfear_align_from_sums(const double* s, double align[12]);
 
-struct RegLaunchHint {
-  bool small_pairs = false;   // every job is a two-scan candidate that fits 20 KB of LDS: the 2-wavefront form, eight per CU
-  bool big_pass = false;      // registrations the regular form is not good at may be among them (dense scans): add the large forms
-  bool whole_cu = false;      // cost-only launches: a job that does not fit half a CU's LDS is among them
-};
-int cfear_register_launch(cfear_ctx* ctx, const void* d_jobs, int n_jobs, const cfear_reg_params* par, int pairs_cap,
-                          char* d_scratch, cfear_reg_result* d_results, const RegCostMode* mode = nullptr,
-                          size_t job_stride = 0,    // 0: full records (cfear_reg_job_bytes)
-                          RegLaunchHint hint = RegLaunchHint());
-// candidate batches in two halves (matcher.hip; cfear_candidate_pipe in shard.hip runs them on different streams)
-struct CandGeometry { int pairs_cap = 1; RegLaunchHint hint; };
-struct cfear_scan_table;
-int cfear_candidates_expand(cfear_ctx* ctx, hipStream_t stream, const cfear_scan_table* table, const cfear_candidate* cands, int32_t n,
-                            const cfear_reg_params* par, cfear_candidate* h_stage, char* d_jobs, int32_t* d_trailer, int trailer_status,
-                            CandGeometry* geom);
-int cfear_candidates_match(cfear_ctx* ctx, const char* d_jobs, int32_t n, const cfear_reg_params* par, const CandGeometry* geom,
-                           cfear_reg_result* d_res);
-int cfear_candidates_enqueue(cfear_ctx* ctx, const cfear_scan_table* table, const cfear_candidate* cands, int32_t n,
-                             const cfear_reg_params* par, cfear_candidate* h_stage, cfear_reg_result* d_res, int32_t* d_trailer,
-                             int trailer_status);
-int cfear_check_reg_params(cfear_ctx* ctx, const cfear_reg_params* par);
-// launch geometry of a batch of two-scan jobs from its largest target / source (what cfear_register_candidates derives)
-void cfear_reg_pair_geometry(const cfear_reg_params* par, int max_tar_cells, int max_src_cells, int* pairs_cap, RegLaunchHint* hint);
-size_t cfear_reg_job_stride(int max_scans);         // bytes of a record that holds up to max_scans scan views
-// whether a cost-only launch (cfear_get_cost_batch) can hold a registration of these sizes at all; sum_pad / max_pad: the
-// fixed scans' padded record counts (scan_grid_pad), total and largest.  What it cannot hold is the job's CFEAR_ERR_CAPACITY.
-bool cfear_reg_cost_fits(const cfear_reg_params* par, int n_scans, int sum_pad, int max_pad, int n_src);
-void cfear_reg_job_set_itr(void* job, int itr);
-// quadratic fit of the cost samples -> 6x6 covariance: struct CovFit (covfit.hpp, host)
 
 // ---------------------------------------------------------------------------------------------
 // device helpers

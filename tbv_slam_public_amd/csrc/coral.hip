@@ -26,6 +26,7 @@
 
 #include "common.hpp"
 #include "gridsort.hpp"
+#include "pose2d.hpp"
 
 namespace {
 
@@ -50,22 +51,8 @@ __host__ __device__ inline size_t coral_scratch_bytes(int cap) {
   return ((size_t)cap * (16 + 8 + 8 + 8 + 4 + 4) + 255) / 256 * 256;
 }
 
-struct Aff2d { double l0, l1, l2, l3, t0, t1; };
-__device__ __forceinline__ Aff2d aff_xyt(const double* p) {
-  double s, c;
-  sincos(p[2], &s, &c);
-  return Aff2d{c, -s, s, c, p[0], p[1]};
-}
-__device__ __forceinline__ Aff2d aff_compose(const Aff2d& a, const Aff2d& b) {     // Eigen Transform * Transform
-  Aff2d r;
-  r.l0 = a.l0 * b.l0 + a.l1 * b.l2; r.l1 = a.l0 * b.l1 + a.l1 * b.l3;
-  r.l2 = a.l2 * b.l0 + a.l3 * b.l2; r.l3 = a.l2 * b.l1 + a.l3 * b.l3;
-  r.t0 = a.l0 * b.t0 + a.l1 * b.t1 + a.t0;
-  r.t1 = a.l2 * b.t0 + a.l3 * b.t1 + a.t1;
-  return r;
-}
 // pcl::transformPointCloud<PointXYZI, double> (PCL 1.10 common/impl/transforms.hpp): float(((t0 x + t1 y) + t2 z) + t3)
-__device__ __forceinline__ float2 tf_point(const float4 p, const Aff2d& T) {
+__device__ __forceinline__ float2 tf_point(const float4 p, const Aff2& T) {
   const double x = (double)p.x, y = (double)p.y, z = (double)p.z;
   return make_float2((float)(((T.l0 * x + T.l1 * y) + 0.0 * z) + T.t0), (float)(((T.l2 * x + T.l3 * y) + 0.0 * z) + T.t1));
 }
@@ -120,11 +107,11 @@ __global__ __launch_bounds__(kCoralThreads) void coral_kernel(const CoralJob* __
 #else
 #define CORAL_T(k)
 #endif
-  const Aff2d Tref = aff_xyt(job.ref_pose);
-  const Aff2d Tsrc = aff_compose(aff_xyt(job.src_pose), aff_xyt(job.offset));            // src->GetAffine() * Toffset (:101)
+  const Aff2 Tref = aff_from_xyt(job.ref_pose);
+  const Aff2 Tsrc = aff_mul(aff_from_xyt(job.src_pose), aff_from_xyt(job.offset));            // src->GetAffine() * Toffset (:101)
   auto point = [&](int i) -> float2 {                          // merged index: source points first (:132, :155)
     const bool s = i < n_src;                                  // (the transform selected field by field: both stay in registers)
-    const Aff2d T{s ? Tsrc.l0 : Tref.l0, s ? Tsrc.l1 : Tref.l1, s ? Tsrc.l2 : Tref.l2, s ? Tsrc.l3 : Tref.l3, s ? Tsrc.t0 : Tref.t0, s ? Tsrc.t1 : Tref.t1};
+    const Aff2 T{s ? Tsrc.l0 : Tref.l0, s ? Tsrc.l1 : Tref.l1, s ? Tsrc.l2 : Tref.l2, s ? Tsrc.l3 : Tref.l3, s ? Tsrc.t0 : Tref.t0, s ? Tsrc.t1 : Tref.t1};
     return tf_point(gload_f4(s ? job.src + i : job.ref + (i - n_src)), T);   // (global_load: gload's comment in common.hpp)
   };
   // ---- 1. bounding box of the merged cloud ------------------------------------------------------

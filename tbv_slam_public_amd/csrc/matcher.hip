@@ -27,14 +27,15 @@
 // Forms (template NW = wavefronts per registration; LDS per workgroup is a launch parameter): 2 (two-scan loop-closure
 // candidates, eight per CU), 4 (regular), 8 and 16 (what the regular form defers: dense scans; and batches too small to
 // fill the chip, whose latency counts).
+// Host side here: the launch (cfear_register_launch, first_form), cfear_reg_fill_job and the cfear_cost object, which launches
+// assoc_kernel and eval_kernel itself.  Every other entry point is register.hip's; the LDS arithmetic is reg_layout.hpp's.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <memory>
 
-#include "common.hpp"
-#include "covfit.hpp"
 #include "fastmath.hpp"
+#include "registration.hpp"
 
 namespace {
 
@@ -54,9 +55,8 @@ __device__ unsigned long long g_reg_sum[4];   // every workgroup of a launch: su
 #define REG_TACC(k)
 #endif
 
-constexpr int kMaxScans = kRegMaxScans;
 constexpr int kRegDeferred = 1000;            // internal status between the launches of a batch with large registrations
-// (struct RegJob and reg_job_stride: common.hpp -- verify.hip's kernels write job records too)
+// (struct RegJob: registration.hpp -- verify.hip's kernels write job records too)
 
 struct MatchCommon {
   cfear_reg_params par;
@@ -80,40 +80,6 @@ struct MatchCommon {
   double xy_half, yaw_half;
   const cfear_reg_result* prior;              // cost-only: source pose and itr_ come from these records (device)
 };
-
-int reg_dense_fields(int cost) { return cost == CFEAR_P2P ? 3 : (cost == CFEAR_P2L ? 5 : 6); }
-
-// Global scratch of one workgroup: the u16 match table of the large forms, then the tail of the dense arrays.
-__host__ __device__ inline size_t match_bytes_global(int pairs_cap) { return ((size_t)pairs_cap * 2 + 255) / 256 * 256; }
-size_t reg_scratch_bytes(int pairs_cap) { return match_bytes_global(pairs_cap) + ((size_t)pairs_cap * 52 + 255) / 256 * 256; }
-
-struct Aff2 { double l0, l1, l2, l3, t0, t1; };
-
-// registration.cpp:128-135 vectorToAffine3d + n_scan_normal.cpp:350-351
-__device__ __forceinline__ Aff2 aff_from_xyt(const double* p) {
-  double s, c;
-  sincos(p[2], &s, &c);
-  return Aff2{c, -s, s, c, p[0], p[1]};
-}
-__device__ __forceinline__ Aff2 aff_mul(const Aff2& a, const Aff2& b) {
-  Aff2 r;
-  r.l0 = a.l0 * b.l0 + a.l1 * b.l2;
-  r.l1 = a.l0 * b.l1 + a.l1 * b.l3;
-  r.l2 = a.l2 * b.l0 + a.l3 * b.l2;
-  r.l3 = a.l2 * b.l1 + a.l3 * b.l3;
-  r.t0 = a.l0 * b.t0 + a.l1 * b.t1 + a.t0;
-  r.t1 = a.l2 * b.t0 + a.l3 * b.t1 + a.t1;
-  return r;
-}
-__device__ __forceinline__ Aff2 aff_inv(const Aff2& a) {   // Eigen Affine inverse: adjugate / det
-  const double det = a.l0 * a.l3 - a.l2 * a.l1;
-  const double invdet = 1.0 / det;
-  Aff2 r;
-  r.l0 = a.l3 * invdet; r.l1 = -a.l1 * invdet; r.l2 = -a.l2 * invdet; r.l3 = a.l0 * invdet;
-  r.t0 = -(r.l0 * a.t0 + r.l1 * a.t1);
-  r.t1 = -(r.l2 * a.t0 + r.l3 * a.t1);
-  return r;
-}
 
 __device__ __forceinline__ double similarity(double x, double y) { return 2 * fmin(x, y) / (x + y); }
 // registration.cpp:67-75
@@ -175,9 +141,7 @@ __device__ __forceinline__ void loss_eval(int loss, double a, double w, double s
 }
 
 // ---------------------------------------------------------------------------------------------------
-// LDS map of a registration workgroup.  Fixed block: the reduction's partials, the scan's int partials, the solver state.
-// Behind it (mt_carve): keyframe transforms and pointers, the source means, the match table, then the REGION that holds the
-// keyframes' tables and the dense correspondence arrays -- side by side when both fit, aliased when they do not.
+// The LDS map of a registration workgroup (the fixed block, MtFit / mt_fit, kPartBigBytes): reg_layout.hpp.
 // ---------------------------------------------------------------------------------------------------
 // LDS-resident solver state (doubles; the int fields share the last slots).  Nothing of the trust-region bookkeeping is held
 // in registers across an evaluation: wavefront 0 loads the block, walks one round of the chain and stores it back.
@@ -187,50 +151,7 @@ enum {
   S_LASTREL = 33, S_FINAL = 34, S_INTS = 35 /* 8 ints */, S_OUTER = 39 /* x[3] prev_par[3] prev_score */, S_COUNT = 48
 };
 enum { SI_ITER = 0, SI_REUSE = 1, SI_INVALID = 2, SI_PUSHED = 3, SI_USABLE = 4, SI_DONE = 5, SI_ITSUCC = 6, SI_FLAG = 7 };
-constexpr int kMaxNW = 16;
-constexpr size_t kPartOff = 0;                               // [10][16] doubles: the block reduction's partials (one buffer: two
-constexpr size_t kIpartOff = kMaxNW * 10 * 8;                //   barriers separate consecutive uses); [2][16] ints
-constexpr size_t kStateOff = kIpartOff + 2 * kMaxNW * 4;
-constexpr size_t kFixedLds = kStateOff + S_COUNT * 8;        // 1792 bytes
-constexpr int kPtrs = 6;                                     // per keyframe: mean, normal, nsamples, scale, cov, grid block
-
-// What a registration of these sizes gets from `lds_total` bytes: shared by the kernel (mt_carve) and the host (which form
-// and how much LDS a batch wants).  sum_pad / max_pad: the keyframes' padded record counts (scan_grid_pad).
-struct MtFit {
-  size_t off_smean, off_match, off_region;
-  int region;              // bytes of the region
-  int tables_all;          // bytes of every keyframe's tables together
-  int dense_cap;           // correspondences the LDS arrays hold
-  bool gmatch;             // the match table lives in global scratch
-  bool resident;           // tables and dense arrays side by side: staged once per registration
-  bool can;                // the registration can run at all in this LDS
-  bool good;               // ... and is one this LDS is GOOD for: tables in at most two groups, LDS arrays for 40 % of the pairs
-};
-__host__ __device__ inline MtFit mt_fit(size_t lds_total, int last, int sum_pad, int max_pad, int n_src, int fields, bool allow_gmatch) {
-  MtFit m;
-  size_t off = kFixedLds + (size_t)last * (12 * 8 + kPtrs * 8 + 16) + ((((size_t)last + 1) * 4 + 15) & ~(size_t)15);
-  m.off_smean = off; off += (size_t)n_src * 16;
-  const size_t n_pairs = (size_t)last * n_src;
-  const size_t match_bytes = ((n_pairs + 7) & ~(size_t)7) * 2;
-  const size_t need_one = (size_t)kScanGridStartPad * 2 + (size_t)max_pad * 10;
-  m.off_match = off;
-  // the match table: in LDS, unless that leaves no room for the largest keyframe's tables (1 400-cell scans in half a CU's
-  // LDS) -- then in the job's global scratch (L2; written and read once per outer iteration by the same thread)
-  m.gmatch = allow_gmatch && ((off + match_bytes + 15) & ~(size_t)15) + need_one > lds_total;
-  if (!m.gmatch) off += match_bytes;
-  off = (off + 15) & ~(size_t)15;
-  m.off_region = off;
-  m.tables_all = (int)((size_t)last * kScanGridStartPad * 2 + (size_t)sum_pad * 10);
-  const size_t per = (size_t)fields * 8 + 2;
-  m.can = sum_pad <= 65535 && n_src < 65536 && off + need_one <= lds_total && off + 4096 <= lds_total;
-  m.region = m.can ? (int)(lds_total - off) : 0;
-  const size_t dense_all = ((n_pairs + 3) & ~(size_t)3) * per;
-  m.resident = m.can && (size_t)m.tables_all + dense_all + 16 <= (size_t)m.region;
-  if (m.resident) m.dense_cap = (int)((n_pairs + 3) & ~(size_t)3);
-  else m.dense_cap = (int)((size_t)m.region / per) & ~3;
-  m.good = m.can && (m.resident || (m.tables_all <= 2 * m.region && 5 * (size_t)m.dense_cap >= 2 * n_pairs));
-  return m;
-}
+static_assert(S_COUNT == kRegStateDoubles, "reg_layout.hpp sizes the fixed LDS block by the solver state");
 
 struct MtLds {
   double* kf;              // [last][12]: Ttar (l0..l3, t0, t1), Tsrctotar (l0..l3, t0, t1)
@@ -271,7 +192,6 @@ __device__ __forceinline__ void mt_carve(uint8_t* smem, const MtFit& m, int last
 // instructions instead of 180 (and instead of the 300 of ten full 64-lane reductions, which the forms other than 4 wavefronts
 // used until round 5: a third of an LM iteration of the 8-wavefront form).  bank_mask performs the class select (banks = lane
 // quads): row_mirror splits on lane bit 3 (banks 0,1 | 2,3), row_half_mirror on bit 2 (banks 0,2 | 1,3).
-constexpr size_t kPartBigBytes = 10 * 4 * kMaxNW * 8;        // the partials of the 8- / 16-wavefront forms: at the END of their LDS
 template <int NW>
 __device__ __forceinline__ void block_reduce10(double v[10], double* buf /*[10][4 NW]*/) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -453,7 +373,6 @@ struct Slots {
   double *tmx, *tmy, *a0, *a1, *a2, *w;
   int32_t* tidx;        // matched target cell
 };
-__host__ __device__ inline size_t slots_bytes(int cap) { return ((size_t)cap * 52 + 255) / 256 * 256; }
 __device__ __forceinline__ Slots slots_of(char* scratch, int cap) {
   Slots s;
   double* p = (double*)scratch;
@@ -640,7 +559,7 @@ __device__ int mt_associate(const RegJob& job, const MatchCommon& cm, int itr, c
       const Aff2 Ttar{k[0], k[1], k[2], k[3], k[4], k[5]};
       double sn, cs;
       sincos_pose<true>(xsrc[2], &sn, &cs);
-      const Aff2 Tst = aff_mul(aff_inv(Ttar), Aff2{cs, -sn, sn, cs, xsrc[0], xsrc[1]});
+      const Aff2 Tst = aff_mul(aff_inv(Ttar), aff_from_cs(cs, sn, xsrc[0], xsrc[1]));
       double* o = f.kf + k0 * 12 + 6;
       o[0] = Tst.l0; o[1] = Tst.l1; o[2] = Tst.l2; o[3] = Tst.l3; o[4] = Tst.t0; o[5] = Tst.t1;
     }
@@ -1371,15 +1290,6 @@ __global__ __launch_bounds__(256) void eval_kernel(const RegJob* __restrict__ jo
   if (threadIdx.x == 0 && o.neq) for (int k = 0; k < 10; k++) o.neq[k] = acc[k];
 }
 
-int check_params(cfear_ctx* ctx, const cfear_reg_params* p) {
-  if (!p) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null parameters");
-  if (p->cost < 0 || p->cost > 2 || p->loss < 0 || p->loss > 5 || p->weight_opt < 0 || p->weight_opt > 4)
-    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "bad cost/loss/weight option");
-  if (p->max_itr_association < 1 || p->max_itr_solver < 0 || !(p->radius > 0))
-    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "bad iteration limits / radius");
-  return CFEAR_OK;
-}
-
 typedef void (*MatcherFn)(const RegJob*, MatchCommon);
 template <int NW, bool CO>
 MatcherFn matcher_fn_nw(int cost, bool huber) {
@@ -1410,12 +1320,6 @@ MatcherFn matcher_fn(int nw, int cost, bool huber, bool cost_only, bool wide = f
 
 }  // namespace
 
-size_t cfear_reg_job_bytes() { return sizeof(RegJob); }
-int cfear_reg_max_scans() { return kMaxScans; }
-void cfear_reg_job_set_itr(void* job, int itr) { ((RegJob*)job)->itr = itr; }
-size_t cfear_reg_job_stride(int max_scans) { return reg_job_stride(max_scans); }
-size_t cfear_register_scratch_bytes(int pairs_cap) { return reg_scratch_bytes(pairs_cap); }
-
 // Writes the used prefix of a job record: reg_job_stride(n_scans) bytes at dst.
 void cfear_reg_fill_job(void* dst, const ScanView* views, int n_scans, const double* poses_xyt) {
   RegJob* j = (RegJob*)dst;
@@ -1428,9 +1332,6 @@ void cfear_reg_fill_job(void* dst, const ScanView* views, int n_scans, const dou
 }
 
 namespace {
-constexpr size_t kLdsCu = 160 * 1024;                        // LDS of a gfx950 compute unit
-constexpr size_t kLdsPairs = 20 * 1024;                      // the 2-wavefront form for two-scan candidates: eight per CU
-size_t regular_lds(bool huber) { return huber ? kLdsCu / 4 : (kLdsCu / 3) & ~(size_t)255; }   // four (three: matcher_kernel) per CU
 
 // The first launch's form for a batch of n_wgs workgroups (measured: tools/form_sweep.py).  A batch that fills
 // the chip several times over runs the regular form -- 4 wavefronts, four registrations per CU (two-scan candidates from eight
@@ -1510,366 +1411,6 @@ int cfear_register_launch(cfear_ctx* ctx, const void* d_jobs, int n_jobs, const 
   return CFEAR_OK;
 }
 
-// ---- host-facing wrappers ----------------------------------------------------------------------
-namespace {
-
-// what the host learns about a batch while it marshals it: the scratch size and which forms its registrations want
-struct JobSizes {
-  int pairs_cap = 1, cost;
-  bool huber, small_pairs = true, any_large = false, any_huge = false;
-  explicit JobSizes(const cfear_reg_params* par) : cost(par->cost), huber(par->loss == CFEAR_LOSS_HUBER) {}
-  void add(int n_scans, int sum_pad, int max_pad, int n_src) {
-    const int last = n_scans - 1, fields = reg_dense_fields(cost);
-    pairs_cap = std::max(pairs_cap, last * std::max(n_src, 1));
-    any_huge = any_huge || !mt_fit((uint32_t)(kLdsCu / 2 - 256 - kPartBigBytes), last, sum_pad, max_pad, n_src, fields, true).can;
-    small_pairs = small_pairs && n_scans == 2 && mt_fit(kLdsPairs, last, sum_pad, max_pad, n_src, fields, false).good;
-    any_large = any_large || !mt_fit(regular_lds(huber), last, sum_pad, max_pad, n_src, fields, false).good;
-  }
-  RegLaunchHint hint(int n_jobs) const { RegLaunchHint h; h.small_pairs = small_pairs && n_jobs > 0; h.big_pass = any_large; h.whole_cu = any_huge; return h; }
-};
-
-int gather_job(cfear_ctx* ctx, const cfear_scan* const* scans, int n_scans, const double* poses, unsigned char* dst, JobSizes& sz) {
-  if (n_scans < 2 || n_scans > kMaxScans)
-    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "n_scans must be in [2,%d]", kMaxScans);
-  ScanView views[kMaxScans];
-  int sum_pad = 0, max_pad = 0, n_src = 0;
-  for (int i = 0; i < n_scans; i++) {
-    if (!scans[i]) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null scan handle");
-    if (scans[i]->ctx != ctx) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "scan belongs to another context");
-    views[i] = scans[i]->view;
-    const int nc = cfear_scan_size(scans[i]);
-    if (nc < 0) return nc;
-    if (i < n_scans - 1) { sum_pad += scan_grid_pad(nc); max_pad = std::max(max_pad, scan_grid_pad(nc)); }
-    else n_src = nc;
-  }
-  sz.add(n_scans, sum_pad, max_pad, n_src);
-  cfear_reg_fill_job(dst, views, n_scans, poses);
-  return CFEAR_OK;
-}
-
-}  // namespace
-
-namespace {
-
-// A batch of jobs as device records, built in the stage's pinned record with the stride of the batch's longest job, and
-// where its n_results results go: used in place when they are device memory, copied back by finish() when the host's.
-struct JobBatch {
-  explicit JobBatch(const cfear_reg_params* par) : sz(par) {}
-  JobSizes sz;
-  size_t stride = 0;
-  char* d_jobs = nullptr;
-  cfear_reg_result* d_res = nullptr;
-};
-int stage_jobs(cfear_ctx* ctx, HostStage& st, const cfear_reg_job* jobs, int n_jobs, const int32_t* itrs /*nullable: per-job itr_*/,
-               cfear_reg_result* results, size_t n_results, JobBatch& b) {
-  int max_scans = 2;
-  for (int j = 0; j < n_jobs; j++) max_scans = std::max(max_scans, std::min(jobs[j].n_scans, kMaxScans));
-  b.stride = reg_job_stride(max_scans);
-  const size_t jb = (size_t)n_jobs * b.stride;
-  unsigned char* hjobs = (unsigned char*)st.pinned(jb);
-  if (!hjobs) return CFEAR_ERR_HIP;
-  for (int j = 0; j < n_jobs; j++) {
-    unsigned char* dst = hjobs + (size_t)j * b.stride;
-    CFEAR_CHECK(gather_job(ctx, jobs[j].scans, jobs[j].n_scans, jobs[j].poses_xyt, dst, b.sz));
-    if (itrs) cfear_reg_job_set_itr(dst, itrs[j]);
-  }
-  st.piece(b.d_jobs, jb);
-  st.out(b.d_res, results, n_results * sizeof(cfear_reg_result));
-  CFEAR_CHECK(st.carve());
-  return st.upload(b.d_jobs, hjobs, jb);
-}
-
-}  // namespace
-
-// results on the device stay there, stream-ordered and not synchronised (the sharded entry hands them to the collective)
-extern "C" int cfear_register_batch(cfear_ctx* ctx, const cfear_reg_job* jobs, int32_t n_jobs,
-                                    const cfear_reg_params* par, cfear_reg_result* results) {
-  if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
-  if (!jobs || !results || n_jobs < 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
-  CFEAR_CHECK(check_params(ctx, par));
-  if (n_jobs == 0) return CFEAR_OK;
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  HostStage st(ctx, kWsRegJobs);
-  JobBatch b(par);
-  CFEAR_CHECK(stage_jobs(ctx, st, jobs, n_jobs, nullptr, results, (size_t)n_jobs, b));
-  char* scr = (char*)cfear_workspace(ctx, kWsRegScratch, reg_scratch_bytes(b.sz.pairs_cap) * (size_t)n_jobs);
-  if (!scr) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-  CFEAR_CHECK(cfear_register_launch(ctx, b.d_jobs, n_jobs, par, b.sz.pairs_cap, scr, b.d_res, nullptr, b.stride, b.sz.hint(n_jobs)));
-  return st.finish();
-}
-
-// ---- candidate pairs among a table of scans (loop closure) ---------------------------------------------------------
-// The table holds a reference on every scan (cfear_scan::refs): a scan destroyed while a table still names it keeps its slab
-// until the table goes too, so a candidate can never read another scan's cells through a recycled slab.
-struct cfear_scan_table {
-  cfear_ctx* ctx = nullptr;
-  DevBuf<ScanView> d_views;             // [n] device
-  std::vector<int32_t> n_cells;         // host copy of the cell counts (launch geometry)
-  std::vector<cfear_scan*> scans;       // referenced handles
-};
-
-namespace {
-// candidate -> the job record matcher_kernel reads: scans {target, source}, poses {target, source guess}
-__global__ __launch_bounds__(256) void expand_candidates_kernel(const ScanView* __restrict__ views, const cfear_candidate* __restrict__ cands,
-                                                                int n, char* __restrict__ jobs, size_t stride, int32_t* __restrict__ trailer,
-                                                                int trailer_status) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i == 0 && trailer) { trailer[0] = trailer_status; trailer[1] = n; }   // the sharded step's {rank status, records} (shard.hip)
-  if (i >= n) return;
-  const cfear_candidate c = cands[i];
-  RegJob* j = (RegJob*)(jobs + (size_t)i * stride);
-  j->n_scans = 2; j->itr = 0;
-#pragma unroll
-  for (int k = 0; k < 3; k++) { j->poses[0][k] = c.target_xyt[k]; j->poses[1][k] = c.source_xyt[k]; }
-  j->scans[0] = views[c.target];
-  j->scans[1] = views[c.source];
-}
-}  // namespace
-
-extern "C" int cfear_scan_table_create(cfear_ctx* ctx, const cfear_scan* const* scans, int32_t n_scans, cfear_scan_table** out) {
-  if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
-  if (!scans || !out || n_scans < 1) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument / empty table");
-  *out = nullptr;
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  HostStage st(ctx, kWsRegJobs);
-  const size_t vb = (size_t)n_scans * sizeof(ScanView);
-  ScanView* views = (ScanView*)st.record(vb);
-  std::unique_ptr<cfear_scan_table> t(new cfear_scan_table());
-  t->ctx = ctx;
-  t->n_cells.resize((size_t)n_scans);
-  for (int i = 0; i < n_scans; i++) {
-    if (!scans[i]) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null scan handle");
-    if (scans[i]->ctx != ctx) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "scan belongs to another context");
-    const int nc = cfear_scan_size(scans[i]);
-    if (nc < 0) return nc;
-    views[i] = scans[i]->view;
-    t->n_cells[(size_t)i] = nc;
-  }
-  if (!(t->d_views = dev_alloc<ScanView>(vb))) return cfear_set_error(ctx, CFEAR_ERR_HIP, "scan table: hipMalloc failed");
-  if (st.upload(t->d_views.get(), views, vb) != CFEAR_OK || st.finish() != CFEAR_OK)
-    return cfear_set_error(ctx, CFEAR_ERR_HIP, "scan table upload failed");
-  t->scans.resize((size_t)n_scans);
-  for (int i = 0; i < n_scans; i++) { t->scans[(size_t)i] = const_cast<cfear_scan*>(scans[i]); cfear_scan_retain(t->scans[(size_t)i]); }
-  *out = t.release();
-  return CFEAR_OK;
-}
-
-extern "C" int cfear_scan_table_size(const cfear_scan_table* t) { return t ? (int)t->n_cells.size() : CFEAR_ERR_INVALID_ARGUMENT; }
-
-extern "C" int cfear_scan_table_destroy(cfear_scan_table* t) {
-  if (!t) return CFEAR_OK;
-  (void)hipSetDevice(t->ctx->device);
-  (void)hipStreamSynchronize(t->ctx->stream);
-  for (cfear_scan* s : t->scans) (void)cfear_scan_destroy(s);          // drops the table's reference
-  delete t;
-  return CFEAR_OK;
-}
-
-// A candidate batch in two halves (cfear_candidate_pipe runs them on different streams; cfear_candidates_enqueue is both in a row).
-// expand: validates the candidates while it copies them into `h_stage` (PINNED host memory, n records, owned by the caller until
-// the kernel has run) and turns them into job records at d_jobs (n * reg_job_stride(2) bytes) on `stream` -- no upload: pinned
-// memory is mapped into the device's address space, the kernel reads the 56-byte records over PCIe itself.  d_trailer
-// (optional, device int32[2]) receives {trailer_status, n}: the status trailer of a sharded step travels behind the block
-// without an enqueue of its own.  geom receives what the matcher's launch needs to know about the batch.
-int cfear_candidates_expand(cfear_ctx* ctx, hipStream_t stream, const cfear_scan_table* table, const cfear_candidate* cands, int32_t n,
-                            const cfear_reg_params* par, cfear_candidate* h_stage, char* d_jobs, int32_t* d_trailer, int trailer_status,
-                            CandGeometry* geom) {
-  if (table->ctx != ctx) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "table belongs to another context");
-  const int nt = (int)table->n_cells.size();
-  JobSizes sz(par);
-  int max_tar = 0, max_src = 0;
-  for (int i = 0; i < n; i++) {
-    const cfear_candidate& c = cands[i];
-    if (c.target < 0 || c.target >= nt || c.source < 0 || c.source >= nt)
-      return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "candidate %d refers to scan %d / %d of a table of %d", i, c.target, c.source, nt);
-    max_tar = std::max(max_tar, table->n_cells[(size_t)c.target]);
-    max_src = std::max(max_src, table->n_cells[(size_t)c.source]);
-    h_stage[i] = c;
-  }
-  // the launch geometry from the LARGEST target and source of the batch (a pair's needs grow with both: if that pair fits a
-  // form, every candidate does) -- one evaluation per batch, not per candidate (4096 candidates: 0.1 ms of host time)
-  sz.add(2, scan_grid_pad(max_tar), scan_grid_pad(max_tar), max_src);
-  geom->pairs_cap = sz.pairs_cap; geom->hint = sz.hint(n);
-  hipLaunchKernelGGL(expand_candidates_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const ScanView*)table->d_views.get(),
-                     (const cfear_candidate*)h_stage, n, d_jobs, reg_job_stride(2), d_trailer, trailer_status);
-  CFEAR_HIP_CHECK(ctx, hipGetLastError());
-  return CFEAR_OK;
-}
-
-// match: the matcher over the job records expand left at d_jobs, on the context's stream; records to d_res (device)
-int cfear_candidates_match(cfear_ctx* ctx, const char* d_jobs, int32_t n, const cfear_reg_params* par, const CandGeometry* geom,
-                           cfear_reg_result* d_res) {
-  char* scr = (char*)cfear_workspace(ctx, kWsRegScratch, reg_scratch_bytes(geom->pairs_cap) * (size_t)n);
-  if (!scr) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-  return cfear_register_launch(ctx, d_jobs, n, par, geom->pairs_cap, scr, d_res, nullptr, reg_job_stride(2), geom->hint);
-}
-
-int cfear_candidates_enqueue(cfear_ctx* ctx, const cfear_scan_table* table, const cfear_candidate* cands, int32_t n,
-                             const cfear_reg_params* par, cfear_candidate* h_stage, cfear_reg_result* d_res, int32_t* d_trailer,
-                             int trailer_status) {
-  char* ws = (char*)cfear_workspace(ctx, kWsRegJobs, (size_t)n * reg_job_stride(2) + 512);
-  if (!ws) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-  CandGeometry geom;
-  const int rc = cfear_candidates_expand(ctx, ctx->stream, table, cands, n, par, h_stage, ws, d_trailer, trailer_status, &geom);
-  if (rc != CFEAR_OK) return rc;
-  return cfear_candidates_match(ctx, ws, n, par, &geom, d_res);
-}
-
-extern "C" int cfear_register_candidates(cfear_ctx* ctx, const cfear_scan_table* table, const cfear_candidate* cands, int32_t n,
-                                         const cfear_reg_params* par, cfear_reg_result* results) {
-  if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
-  if (!table || !results || n < 0 || (n > 0 && !cands)) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
-  int rc = check_params(ctx, par);
-  if (rc != CFEAR_OK || n == 0) return rc;
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  // the candidates are copied into the pinned record and read from there by the expanding kernel (cfear_candidates_expand)
-  HostStage st(ctx, kWsCandResults);
-  cfear_candidate* hc = (cfear_candidate*)st.pinned((size_t)n * sizeof(cfear_candidate));
-  if (!hc) return CFEAR_ERR_HIP;
-  cfear_reg_result* d_res;
-  st.out(d_res, results, (size_t)n * sizeof(cfear_reg_result));
-  CFEAR_CHECK(st.carve());
-  CFEAR_CHECK(cfear_candidates_enqueue(ctx, table, cands, n, par, hc, d_res, nullptr, 0));
-  return st.finish();
-}
-
-int cfear_check_reg_params(cfear_ctx* ctx, const cfear_reg_params* par) { return check_params(ctx, par); }
-
-void cfear_reg_pair_geometry(const cfear_reg_params* par, int max_tar_cells, int max_src_cells, int* pairs_cap, RegLaunchHint* hint) {
-  JobSizes sz(par);
-  sz.add(2, scan_grid_pad(max_tar_cells), scan_grid_pad(max_tar_cells), max_src_cells);
-  *pairs_cap = sz.pairs_cap;
-  *hint = sz.hint(1);
-}
-
-// The capacity of the cost-only launches' last resort: 8 wavefronts, a CU's whole LDS, the match table in global scratch
-// (cfear_register_launch, hint.whole_cu) -- the job sizes the kernel would answer with write_capacity.
-bool cfear_reg_cost_fits(const cfear_reg_params* par, int n_scans, int sum_pad, int max_pad, int n_src) {
-  return mt_fit(kLdsCu - 256 - kPartBigBytes, n_scans - 1, sum_pad, max_pad, n_src, reg_dense_fields(par->cost), true).can;
-}
-
-extern "C" int cfear_register(cfear_ctx* ctx, const cfear_scan* const* scans, int32_t n_scans, double* poses_xyt,
-                              const cfear_reg_params* par, cfear_reg_result* result) {
-  if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
-  if (!scans || !poses_xyt || !result) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
-  cfear_reg_job job;
-  job.scans = scans; job.n_scans = n_scans; job.pad = 0; job.poses_xyt = poses_xyt;
-  int rc = cfear_register_batch(ctx, &job, 1, par, result);
-  if (rc != CFEAR_OK) return rc;
-  // Tsrc.back() = vectorToAffine3d(parameters.back()) whenever a solve was usable (n_scan_normal.cpp:117-119)
-  poses_xyt[3 * (n_scans - 1)] = result->pose[0];
-  poses_xyt[3 * (n_scans - 1) + 1] = result->pose[1];
-  poses_xyt[3 * (n_scans - 1) + 2] = result->pose[2];
-  return result->status;
-}
-
-// ---- GetCost for batches and covariance by cost sampling ---------------------------------------------
-namespace {
-
-// Runs the cost-only mode over `jobs`; results (host or device) receives max(mode.n_samples, 1) records per job.
-// itrs (nullable) = per-job leftover itr_; otherwise par->itr applies to every job.
-int run_cost_batch(cfear_ctx* ctx, const cfear_reg_job* jobs, int n_jobs, const cfear_reg_params* par,
-                   const int32_t* itrs, RegCostMode mode, cfear_reg_result* results) {
-  CFEAR_CHECK(check_params(ctx, par));
-  if (n_jobs == 0) return CFEAR_OK;
-  const int m = mode.n_samples > 0 ? mode.n_samples : 1;
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  HostStage st(ctx, kWsRegJobs);
-  JobBatch b(par);
-  CFEAR_CHECK(stage_jobs(ctx, st, jobs, n_jobs, itrs, results, (size_t)n_jobs * m, b));
-  // a few workgroups per job when the batch alone cannot fill the GPU; scratch bounded to 1 GiB per launch
-  mode.blocks_per_job = std::max(1, std::min(m, (1024 + n_jobs - 1) / n_jobs));
-  const size_t per = reg_scratch_bytes(b.sz.pairs_cap) * (size_t)mode.blocks_per_job;
-  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_jobs, ((size_t)1 << 30) / per));
-  char* scr = (char*)cfear_workspace(ctx, kWsRegScratch, per * (size_t)chunk);
-  if (!scr) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
-  for (int j0 = 0; j0 < n_jobs; j0 += chunk) {
-    const int nj = std::min(chunk, n_jobs - j0);
-    CFEAR_CHECK(cfear_register_launch(ctx, b.d_jobs + (size_t)j0 * b.stride, nj, par, b.sz.pairs_cap, scr, b.d_res + (size_t)j0 * m, &mode,
-                                      b.stride, b.sz.hint(nj)));
-  }
-  return st.finish();
-}
-
-}  // namespace
-
-extern "C" int cfear_get_cost_batch(cfear_ctx* ctx, const cfear_reg_job* jobs, int32_t n_jobs,
-                                    const cfear_reg_params* par, cfear_reg_result* results) {
-  if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
-  if (!jobs || !results || n_jobs < 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
-  return run_cost_batch(ctx, jobs, n_jobs, par, nullptr, RegCostMode{}, results);
-}
-
-extern "C" void cfear_cov_sampling_params_default(cfear_cov_sampling_params* p) {
-  if (!p) return;
-  p->xy_range = 0.4;                  // odometrykeyframefuser.h:107 (loopclosure.cpp:108: +-0.2)
-  p->yaw_range = 0.0043625;           // :108 (loopclosure.cpp:109 uses +-0.0022)
-  p->samples_per_axis = 3;            // :109
-  p->pad = 0;
-  p->covariance_scaler = 4.0;         // :110
-}
-
-extern "C" int cfear_covariance_by_sampling_batch(cfear_ctx* ctx, const cfear_reg_job* jobs, int32_t n_jobs,
-                                                  const cfear_reg_params* par, const cfear_reg_result* regs,
-                                                  const cfear_cov_sampling_params* sp, double* cov36, double* samples,
-                                                  int32_t* success) {
-  if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
-  if (!jobs || !regs || !sp || !cov36 || !success || n_jobs < 0)
-    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
-  const int n = sp->samples_per_axis;
-  if (n < 1 || n > 15) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "samples_per_axis must be in [1,15]");
-  RegCostMode mode;
-  mode.samples_per_axis = n;
-  mode.n_samples = n * n * n;
-  mode.xy_half = sp->xy_range * 0.5;                       // odometrykeyframefuser.cpp:276-277
-  mode.yaw_half = sp->yaw_range * 0.5;
-  std::vector<int32_t> itrs(n_jobs);
-  for (int j = 0; j < n_jobs; j++) itrs[j] = regs[j].outer_iters;      // GetCost's radius follows the leftover itr_
-  const int m = mode.n_samples;
-  std::vector<cfear_reg_result> out((size_t)n_jobs * m);
-  CFEAR_CHECK(run_cost_batch(ctx, jobs, n_jobs, par, itrs.data(), mode, out.data()));
-  CovFit fit;
-  fit.prepare(n, mode.xy_half, mode.yaw_half);
-  std::vector<double> costs(m);
-  for (int j = 0; j < n_jobs; j++) {
-    double sample_cost = 0.0;                              // :282; a failed GetCost leaves the previous value (:307)
-    for (int s = 0; s < m; s++) {
-      const cfear_reg_result& r = out[(size_t)j * m + s];
-      if (r.status == CFEAR_OK) sample_cost = r.final_cost;
-      costs[s] = sample_cost;
-      if (samples) {
-        double* o = samples + ((size_t)j * m + s) * 4;
-        o[0] = fit.offsets[3 * (size_t)s]; o[1] = fit.offsets[3 * (size_t)s + 1]; o[2] = fit.offsets[3 * (size_t)s + 2];
-        o[3] = sample_cost;
-      }
-    }
-    // GetCovarianceScaler (n_scan_normal.cpp:433-439): final_cost / (num_residuals_reduced - num_parameters_reduced)
-    bool ok = regs[j].num_residuals - 3 != 0;
-    if (ok) {
-      const double score_scale = regs[j].final_cost / (double)(regs[j].num_residuals - 3);
-      ok = fit.solve(costs.data(), score_scale, sp->covariance_scaler, cov36 + (size_t)j * 36);
-    }
-    success[j] = ok ? 1 : 0;
-    if (!ok) {                                             // caller keeps Register's reg_cov (n_scan_normal.cpp:171-175)
-      double* c = cov36 + (size_t)j * 36;
-      for (int k = 0; k < 36; k++) c[k] = 0.0;
-      c[0] = 0.01; c[7] = 0.01; c[35] = 1e-4;
-    }
-  }
-  return CFEAR_OK;
-}
-
-extern "C" int cfear_covariance_by_sampling(cfear_ctx* ctx, const cfear_scan* const* scans, int32_t n_scans,
-                                            const double* poses_xyt, const cfear_reg_params* par,
-                                            const cfear_reg_result* reg, const cfear_cov_sampling_params* sp,
-                                            double* cov36, double* samples, int32_t* success) {
-  if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
-  if (!scans || !poses_xyt) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
-  cfear_reg_job job;
-  job.scans = scans; job.n_scans = n_scans; job.pad = 0; job.poses_xyt = poses_xyt;
-  return cfear_covariance_by_sampling_batch(ctx, &job, 1, par, reg, sp, cov36, samples, success);
-}
-
 // ---- cfear_cost: one association set kept on the device -------------------------------------------
 struct cfear_cost {
   cfear_ctx* ctx;
@@ -1889,15 +1430,16 @@ extern "C" int cfear_cost_prepare(cfear_ctx* ctx, const cfear_scan* const* scans
   if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
   if (!scans || !poses_xyt || !out) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
   *out = nullptr;
-  CFEAR_CHECK(check_params(ctx, par));
+  CFEAR_CHECK(cfear_check_reg_params(ctx, par));
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   HostStage st(ctx, kWsRegJobs);                      // (no piece: the object owns its device memory)
   unsigned char* hjob = (unsigned char*)st.record(sizeof(RegJob));
   JobSizes sz(par);
-  CFEAR_CHECK(gather_job(ctx, scans, n_scans, poses_xyt, hjob, sz));
+  RegJobCells cells;
+  CFEAR_CHECK(cfear_reg_gather_job(ctx, scans, n_scans, poses_xyt, hjob, sz, &cells));
   CostHandle c(new cfear_cost());
   c->ctx = ctx; c->par = *par; c->pairs_cap = sz.pairs_cap; c->n_scans = n_scans;
-  c->n_src = cfear_scan_size(scans[n_scans - 1]);
+  c->n_src = cells.n[n_scans - 1];
   c->n_slots = (n_scans - 1) * c->n_src;
   if (!(c->d_job = dev_alloc<char>(sizeof(RegJob) + 256)) || !(c->d_scratch = dev_alloc<char>(slots_bytes(c->pairs_cap))) ||
       !(c->d_out = dev_alloc<double>(((size_t)c->pairs_cap * 10 + 16) * sizeof(double))))

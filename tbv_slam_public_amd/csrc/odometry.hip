@@ -16,41 +16,8 @@
 #include <cmath>
 #include <cstdlib>
 
-#include "common.hpp"
 #include "covfit.hpp"
-
-namespace {
-
-struct Aff2 { double l[4]; double t[2]; };
-Aff2 aff_identity() { return Aff2{{1, 0, 0, 1}, {0, 0}}; }
-Aff2 aff_from_xyt(double x, double y, double th) {      // registration.cpp:128-135 vectorToAffine3d
-  const double c = std::cos(th), s = std::sin(th);
-  return Aff2{{c, -s, s, c}, {x, y}};
-}
-Aff2 aff_mul(const Aff2& a, const Aff2& b) {
-  Aff2 r;
-  r.l[0] = a.l[0] * b.l[0] + a.l[1] * b.l[2];
-  r.l[1] = a.l[0] * b.l[1] + a.l[1] * b.l[3];
-  r.l[2] = a.l[2] * b.l[0] + a.l[3] * b.l[2];
-  r.l[3] = a.l[2] * b.l[1] + a.l[3] * b.l[3];
-  r.t[0] = a.l[0] * b.t[0] + a.l[1] * b.t[1] + a.t[0];
-  r.t[1] = a.l[2] * b.t[0] + a.l[3] * b.t[1] + a.t[1];
-  return r;
-}
-Aff2 aff_inv(const Aff2& a) {                            // Eigen Affine inverse
-  const double det = a.l[0] * a.l[3] - a.l[2] * a.l[1];
-  const double invdet = 1.0 / det;
-  Aff2 r;
-  r.l[0] = a.l[3] * invdet; r.l[1] = -a.l[1] * invdet; r.l[2] = -a.l[2] * invdet; r.l[3] = a.l[0] * invdet;
-  r.t[0] = -(r.l[0] * a.t[0] + r.l[1] * a.t[1]);
-  r.t[1] = -(r.l[2] * a.t[0] + r.l[3] * a.t[1]);
-  return r;
-}
-void aff_to_xyt(const Aff2& a, double p[3]) {            // utils.cpp:115-122 Affine3dToVectorXYeZ
-  p[0] = a.t[0]; p[1] = a.t[1]; p[2] = std::atan2(a.l[2], a.l[3]);
-}
-
-}  // namespace
+#include "registration.hpp"
 
 // ---- frame policy as pure host functions (no GPU, no context): the two decisions OdometryKeyframeFuser takes per frame ----
 // KeyFrameBasedFuse (odometrykeyframefuser.cpp:62-73): diff = T_keyframe^-1 * Tcurrent as (x, y, theta).  For a planar
@@ -193,8 +160,8 @@ extern "C" int cfear_odometry_create(cfear_ctx* ctx, int32_t n_streams, const cf
   if (!desc || !par || !out || n_streams < 1) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
   *out = nullptr;
   if (desc->batch != n_streams) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "desc.batch must equal n_streams");
-  if (par->submap_scan_size < 1 || par->submap_scan_size + 1 > cfear_reg_max_scans())
-    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "submap_scan_size must be in [1,%d]", cfear_reg_max_scans() - 1);
+  if (par->submap_scan_size < 1 || par->submap_scan_size + 1 > kRegMaxScans)
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "submap_scan_size must be in [1,%d]", kRegMaxScans - 1);
   if (!(par->res > 0.05f)) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "res must be > 0.05");   // odometrykeyframefuser.cpp:25
   if (par->estimate_cov_by_sampling && (par->cov_sampling.samples_per_axis < 1 || par->cov_sampling.samples_per_axis > 15))
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "cov_sampling.samples_per_axis must be in [1,15]");
@@ -288,7 +255,7 @@ extern "C" int cfear_odometry_create(cfear_ctx* ctx, int32_t n_streams, const cf
   dev(od->d_surf_jobs, (size_t)B * cfear_surface_job_bytes());
   // records are laid out at the stride of the window (process_frame); rounded up to 16 bytes, the stride of the longest
   // window is 8 bytes MORE than a whole record
-  const size_t reg_job_room = std::max(cfear_reg_job_bytes(), cfear_reg_job_stride(par->submap_scan_size + 1));
+  const size_t reg_job_room = std::max(sizeof(RegJob), reg_job_stride(par->submap_scan_size + 1));
   dev(od->d_reg_jobs, (size_t)B * reg_job_room);
   od->out_bytes = (size_t)B * (sizeof(cfear_reg_result) + 12);
   dev(od->d_out, od->out_bytes);
@@ -306,7 +273,7 @@ extern "C" int cfear_odometry_create(cfear_ctx* ctx, int32_t n_streams, const cf
     od->h_results = h.r; od->h_status = h.st; od->h_ncells = h.nc; od->h_npts = h.np;
   }
   dev(od->d_surf_scratch, (size_t)B * cfear_surface_scratch_bytes(od->cap_points));
-  dev(od->d_reg_scratch, (size_t)B * cfear_register_scratch_bytes(par->submap_scan_size * od->cell_cap));
+  dev(od->d_reg_scratch, (size_t)B * reg_scratch_bytes(par->submap_scan_size * od->cell_cap));
   pin(od->h_surf_jobs, (size_t)B * cfear_surface_job_bytes());
   pin(od->h_reg_jobs, (size_t)B * reg_job_room);
   if (par->estimate_cov_by_sampling) {
@@ -628,10 +595,10 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
   // ---- M: the registration jobs depend on host state only: they are built and uploaded (copy stream) while the
   //      surface kernels, already enqueued above, run -- 2.3 KB per stream, ~0.3 ms of host time for 2048 streams
   //      that would otherwise sit between the sweep and the surface kernels (:164-186) ------------------------
-  const size_t rjb = cfear_reg_job_stride(par.submap_scan_size + 1);   // records cover the keyframe window + the new scan
+  const size_t rjb = reg_job_stride(par.submap_scan_size + 1);   // records cover the keyframe window + the new scan
   int n_jobs = 0;
-  std::vector<ScanView> views(cfear_reg_max_scans());
-  std::vector<double> poses(3 * (size_t)cfear_reg_max_scans());
+  std::vector<ScanView> views(kRegMaxScans);
+  std::vector<double> poses(3 * (size_t)kRegMaxScans);
   // Longest first: registrations differ by ~2x in work (cells, outer and LM iterations), and 2048 of them over the 512
   // workgroup slots of the chip end with whatever the last-started ones need.  A stream's previous registration is a
   // good estimate of its next one, so the batch is ordered by it (the job index is only a slot in the batch) -- in
@@ -830,10 +797,11 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
     }
     // Tcurrent = T_vek.back(): Register rewrites Tsrc via vectorToAffine3d (registration failures are
     // ignored by the reference: `bool success` is shadowed, odometrykeyframefuser.cpp:184-193)
-    Aff2 Tcurrent = aff_from_xyt(rr.pose[0], rr.pose[1], rr.pose[2]);
+    Aff2 Tcurrent = aff_from_xyt(rr.pose);
     {                                                             // AccelerationVelocitySanityCheck :76-94
       const Aff2 Tmot_current = aff_mul(aff_inv(st.T_prev), Tcurrent);
-      if (!cfear_acc_vel_sanity_check(st.Tmot.t, Tmot_current.t)) Tcurrent = st.Tguess;   // :198-199
+      const double prev_xy[2] = {st.Tmot.t0, st.Tmot.t1}, curr_xy[2] = {Tmot_current.t0, Tmot_current.t1};
+      if (!cfear_acc_vel_sanity_check(prev_xy, curr_xy)) Tcurrent = st.Tguess;            // :198-199
     }
     st.Tmot = aff_mul(aff_inv(st.T_prev), Tcurrent);              // :200
     const Aff2 Tkeydiff = aff_mul(aff_inv(st.keyframes.back().pose), Tcurrent);
@@ -850,7 +818,7 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
         memcpy(st.c_cov, cv, sizeof(st.c_cov));
         // C.block<3,3>(0,0) = Tfrom^-1.rotation() * Cov.block<3,3>(0,0) * Tfrom^-1.rotation()^T
         const Aff2 Ti = aff_inv(Tcurrent);
-        const double R[9] = {Ti.l[0], Ti.l[1], 0, Ti.l[2], Ti.l[3], 0, 0, 0, 1};
+        const double R[9] = {Ti.l0, Ti.l1, 0, Ti.l2, Ti.l3, 0, 0, 0, 1};
         double t[9], o[9];
         for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) { t[r * 3 + c] = 0; for (int k = 0; k < 3; k++) t[r * 3 + c] += R[r * 3 + k] * cv[k * 6 + c]; }
         for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) { o[r * 3 + c] = 0; for (int k = 0; k < 3; k++) o[r * 3 + c] += t[r * 3 + k] * R[c * 3 + k]; }

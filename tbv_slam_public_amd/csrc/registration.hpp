@@ -1,0 +1,58 @@
+// registration.hpp -- the internal interface of the registration family: the matcher's job record and launch (matcher.hip),
+// the host entry points around it (register.hip), and what their callers share (odometry.hip, verify.hip, shard.hip,
+// tieaudit.hip).  The launch arithmetic is reg_layout.hpp's, the planar pose algebra pose2d.hpp's.
+#pragma once
+#include "common.hpp"
+#include "pose2d.hpp"
+#include "reg_layout.hpp"
+
+// One registration of the matcher.  Kernels only ever touch scans[0 .. n_scans); a batch is stored with reg_job_stride.
+struct RegJob {
+  int32_t n_scans;
+  int32_t itr;                                // cost-only launches: this job's leftover itr_ (0: use par.itr)
+  double poses[kRegMaxScans][3];
+  ScanView scans[kRegMaxScans];
+};
+static_assert(offsetof(RegJob, scans) == kRegJobHeadBytes && sizeof(ScanView) == kRegViewBytes, "reg_layout.hpp restates the record");
+
+// Writes the used prefix of a job record: reg_job_stride(n_scans) bytes at dst.
+void cfear_reg_fill_job(void* dst, const ScanView* views, int n_scans, const double* poses_xyt);
+int cfear_check_reg_params(cfear_ctx* ctx, const cfear_reg_params* par);
+
+// Cost-only launches of the matcher (GetCost / cost sampling): n_samples = 0 evaluates each job
+// at its own source pose, n_samples = samples_per_axis^3 at the sampling grid around it; results then holds
+// max(n_samples, 1) records per job.  blocks_per_job workgroups share a job's samples (scratch: n_jobs x
+// blocks_per_job x reg_scratch_bytes).
+struct RegCostMode {
+  int n_samples = 0, samples_per_axis = 0, blocks_per_job = 1;
+  double xy_half = 0.0, yaw_half = 0.0;
+  const cfear_reg_result* prior = nullptr;   // device, [n_jobs]: evaluate around prior[j].pose with itr = prior[j].outer_iters
+};
+int cfear_register_launch(cfear_ctx* ctx, const void* d_jobs, int n_jobs, const cfear_reg_params* par, int pairs_cap,
+                          char* d_scratch, cfear_reg_result* d_results, const RegCostMode* mode = nullptr,
+                          size_t job_stride = 0,    // 0: full records (sizeof(RegJob))
+                          RegLaunchHint hint = RegLaunchHint());
+
+// The checks every entry point makes of the handles it is given.  job >= 0 words a refusal as "job <job>: ...", -1 without
+// the prefix.  A scan handle of `ctx`: its cell count, or the refusal's status (< 0).
+int cfear_reg_check_scan(cfear_ctx* ctx, const cfear_scan* scan, int job);
+// A cfear_reg_job: n_scans, then scan by scan the handle and (check_poses: the tie audit) a pose that is there and finite --
+// the first fault in that order is the one named.  cells receives the cell counts and the fixed scans' padded record counts.
+struct RegJobCells { int32_t n[kRegMaxScans]; int sum_pad, max_pad; };
+int cfear_reg_check_job(cfear_ctx* ctx, const cfear_scan* const* scans, int n_scans, const double* poses_xyt, int job, bool check_poses,
+                        RegJobCells* cells);
+// check + the job's record at dst + its sizes into sz
+int cfear_reg_gather_job(cfear_ctx* ctx, const cfear_scan* const* scans, int n_scans, const double* poses_xyt, unsigned char* dst,
+                         JobSizes& sz, RegJobCells* cells);
+
+// candidate batches in two halves (register.hip; cfear_candidate_pipe in shard.hip runs them on different streams)
+struct CandGeometry { int pairs_cap = 1; RegLaunchHint hint; };
+struct cfear_scan_table;
+int cfear_candidates_expand(cfear_ctx* ctx, hipStream_t stream, const cfear_scan_table* table, const cfear_candidate* cands, int32_t n,
+                            const cfear_reg_params* par, cfear_candidate* h_stage, char* d_jobs, int32_t* d_trailer, int trailer_status,
+                            CandGeometry* geom);
+int cfear_candidates_match(cfear_ctx* ctx, const char* d_jobs, int32_t n, const cfear_reg_params* par, const CandGeometry* geom,
+                           cfear_reg_result* d_res);
+int cfear_candidates_enqueue(cfear_ctx* ctx, const cfear_scan_table* table, const cfear_candidate* cands, int32_t n,
+                             const cfear_reg_params* par, cfear_candidate* h_stage, cfear_reg_result* d_res, int32_t* d_trailer,
+                             int trailer_status);

@@ -10,7 +10,7 @@
 
 #include <cstring>
 
-#include "common.hpp"
+#include "registration.hpp"
 
 extern "C" int cfear_shard_range(int32_t n, int32_t world, int32_t rank, int32_t* lo, int32_t* hi, int32_t* per_rank) {
   if (n < 0 || world < 1 || rank < 0 || rank >= world || !lo || !hi) return CFEAR_ERR_INVALID_ARGUMENT;

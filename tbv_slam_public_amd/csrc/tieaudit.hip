@@ -10,8 +10,8 @@
 #include <algorithm>
 #include <cmath>
 
-#include "common.hpp"
 #include "fastmath.hpp"
+#include "registration.hpp"
 
 namespace {
 
@@ -29,29 +29,8 @@ struct TieJob {
   double poses[kRegMaxScans][3];
   ScanView scans[kRegMaxScans];
 };
-size_t tie_job_stride(int max_scans) { return (offsetof(TieJob, scans) + (size_t)max_scans * sizeof(ScanView) + 15) & ~(size_t)15; }
+size_t tie_job_stride(int max_scans) { return reg_record_stride(offsetof(TieJob, scans), max_scans); }
 
-// matcher.hip:90-116, restated: registration.cpp:128-135 vectorToAffine3d, Eigen's Affine product and inverse
-struct Aff2 { double l0, l1, l2, l3, t0, t1; };
-__device__ __forceinline__ Aff2 aff_mul(const Aff2& a, const Aff2& b) {
-  Aff2 r;
-  r.l0 = a.l0 * b.l0 + a.l1 * b.l2;
-  r.l1 = a.l0 * b.l1 + a.l1 * b.l3;
-  r.l2 = a.l2 * b.l0 + a.l3 * b.l2;
-  r.l3 = a.l2 * b.l1 + a.l3 * b.l3;
-  r.t0 = a.l0 * b.t0 + a.l1 * b.t1 + a.t0;
-  r.t1 = a.l2 * b.t0 + a.l3 * b.t1 + a.t1;
-  return r;
-}
-__device__ __forceinline__ Aff2 aff_inv(const Aff2& a) {   // adjugate / det
-  const double det = a.l0 * a.l3 - a.l2 * a.l1;
-  const double invdet = 1.0 / det;
-  Aff2 r;
-  r.l0 = a.l3 * invdet; r.l1 = -a.l1 * invdet; r.l2 = -a.l2 * invdet; r.l3 = a.l0 * invdet;
-  r.t0 = -(r.l0 * a.t0 + r.l1 * a.t1);
-  r.t1 = -(r.l2 * a.t0 + r.l3 * a.t1);
-  return r;
-}
 // Tsrctotar = Ttar^-1 * Tsrc (n_scan_normal.cpp:222) with the matcher's two rotations: libm for the fixed scan
 // (mt_stage_once), the polynomial sincos of the evaluation points for the source (mt_associate)
 __device__ __forceinline__ Aff2 tie_src_to_tar(const double* tar, const double* src) {
@@ -59,7 +38,7 @@ __device__ __forceinline__ Aff2 tie_src_to_tar(const double* tar, const double* 
   sincos(tar[2], &st, &ct);
   if (fabs(src[2]) <= 1e5) sincos_reduced<true>(src[2], &ss, &cs);
   else sincos(src[2], &ss, &cs);
-  return aff_mul(aff_inv(Aff2{ct, -st, st, ct, tar[0], tar[1]}), Aff2{cs, -ss, ss, cs, src[0], src[1]});
+  return aff_mul(aff_inv(aff_from_cs(ct, st, tar[0], tar[1])), aff_from_cs(cs, ss, src[0], src[1]));
 }
 
 // cells a and b differ in something the residual or the weight reads (mean, normal, cov, scale, nsamples), bit for bit
@@ -206,50 +185,31 @@ extern "C" int cfear_association_ties_batch(cfear_ctx* ctx, const cfear_reg_job*
   if (n_jobs == 0) return CFEAR_OK;
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   int max_scans = 2;
-  int64_t total = 0;
-  for (int j = 0; j < n_jobs; j++) {
-    const cfear_reg_job& jb = jobs[j];
-    if (jb.n_scans < 2 || jb.n_scans > kRegMaxScans)
-      return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "job %d: n_scans must be in [2,%d]", j, kRegMaxScans);
-    if (!jb.scans || !jb.poses_xyt) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "job %d: null scans or poses", j);
-    for (int i = 0; i < jb.n_scans; i++) {
-      if (!jb.scans[i]) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "job %d: null scan handle", j);
-      if (jb.scans[i]->ctx != ctx) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "job %d: scan belongs to another context", j);
-      for (int k = 0; k < 3; k++)
-        if (!std::isfinite(jb.poses_xyt[3 * i + k]))
-          return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "job %d: pose %d is not finite", j, i);
-    }
-    max_scans = std::max(max_scans, (int)jb.n_scans);
-    const int n_src = cfear_scan_size(jb.scans[jb.n_scans - 1]);
-    if (n_src < 0) return n_src;
-    total += (int64_t)n_src * (jb.n_scans - 1);
-  }
-  if (per_query && per_query_len < total)
-    return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "per_query holds %lld entries, the batch has %lld queries", (long long)per_query_len,
-                           (long long)total);
+  for (int j = 0; j < n_jobs; j++) max_scans = std::max(max_scans, std::min((int)jobs[j].n_scans, kRegMaxScans));
   HostStage st(ctx, kWsTieAudit);
   const size_t stride = tie_job_stride(max_scans), jb_bytes = (size_t)n_jobs * stride;
   char* hjobs = (char*)st.pinned(jb_bytes);
   if (!hjobs) return CFEAR_ERR_HIP;
-  int64_t q_off = 0;
+  int64_t total = 0;
   for (int j = 0; j < n_jobs; j++) {
     const cfear_reg_job& jb = jobs[j];
+    RegJobCells cells;
+    CFEAR_CHECK(cfear_reg_check_job(ctx, jb.scans, jb.n_scans, jb.poses_xyt, j, true, &cells));
     TieJob* tj = (TieJob*)(hjobs + (size_t)j * stride);
     const int last = jb.n_scans - 1;
-    int sum_pad = 0, max_pad = 0;
     tj->n_scans = jb.n_scans;
-    tj->q_off = q_off;
+    tj->q_off = total;
     for (int i = 0; i < jb.n_scans; i++) {
-      const int nc = cfear_scan_size(jb.scans[i]);
-      if (nc < 0) return nc;
-      tj->n_cells[i] = nc;
+      tj->n_cells[i] = cells.n[i];
       tj->scans[i] = jb.scans[i]->view;
       for (int k = 0; k < 3; k++) tj->poses[i][k] = jb.poses_xyt[3 * i + k];
-      if (i < last) { sum_pad += scan_grid_pad(nc); max_pad = std::max(max_pad, scan_grid_pad(nc)); }
     }
-    tj->cap_status = cfear_reg_cost_fits(par, jb.n_scans, sum_pad, max_pad, tj->n_cells[last]) ? CFEAR_OK : CFEAR_ERR_CAPACITY;
-    q_off += (int64_t)tj->n_cells[last] * last;
+    tj->cap_status = cfear_reg_cost_fits(par, jb.n_scans, cells.sum_pad, cells.max_pad, cells.n[last]) ? CFEAR_OK : CFEAR_ERR_CAPACITY;
+    total += (int64_t)cells.n[last] * last;
   }
+  if (per_query && per_query_len < total)
+    return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "per_query holds %lld entries, the batch has %lld queries", (long long)per_query_len,
+                           (long long)total);
   char* d_jobs;
   cfear_tie_record* d_rec;
   int32_t* d_pq = nullptr;

@@ -20,23 +20,7 @@
 #include <numeric>
 #include <vector>
 
-#include "common.hpp"
-
-namespace {
-
-// planar Affine3d algebra on (x, y, theta)
-inline void xyt_compose(const double a[3], const double b[3], double o[3]) {      // a * b
-  const double c = std::cos(a[2]), s = std::sin(a[2]);
-  const double x = c * b[0] - s * b[1] + a[0], y = s * b[0] + c * b[1] + a[1];
-  o[0] = x; o[1] = y; o[2] = a[2] + b[2];
-}
-inline void xyt_inverse(const double a[3], double o[3]) {                         // a^-1
-  const double c = std::cos(a[2]), s = std::sin(a[2]);
-  const double x = -(c * a[0] + s * a[1]), y = s * a[0] - c * a[1];
-  o[0] = x; o[1] = y; o[2] = -a[2];
-}
-
-}  // namespace
+#include "registration.hpp"
 
 extern "C" void cfear_verify_params_default(cfear_verify_params* p) {
   if (!p) return;
@@ -117,19 +101,6 @@ struct VerifyChain {
   cfear_verify_params par;
 };
 
-__device__ __forceinline__ void d_xyt_compose(const double a[3], const double b[3], double o[3]) {
-  double s, c;
-  sincos(a[2], &s, &c);
-  const double x = c * b[0] - s * b[1] + a[0], y = s * b[0] + c * b[1] + a[1];
-  o[0] = x; o[1] = y; o[2] = a[2] + b[2];
-}
-__device__ __forceinline__ void d_xyt_inverse(const double a[3], double o[3]) {
-  double s, c;
-  sincos(a[2], &s, &c);
-  const double x = -(c * a[0] + s * a[1]), y = s * a[0] - c * a[1];
-  o[0] = x; o[1] = y; o[2] = -a[2];
-}
-
 // RegisterLoopCandidate's problem (loopclosure.cpp:35-60): scans {to, from}, poses {Tto = Tfrom * t_be, Tfrom}
 __global__ __launch_bounds__(256) void verify_expand_kernel(const VerifyChain c) {
   const int j = blockIdx.x * 256 + threadIdx.x;
@@ -139,7 +110,7 @@ __global__ __launch_bounds__(256) void verify_expand_kernel(const VerifyChain c)
   RegJob* r = (RegJob*)(c.reg_jobs + (size_t)j * c.stride);
   r->n_scans = 2; r->itr = 0;
   double tto[3];
-  d_xyt_compose(v.from_pose, v.t_be_guess, tto);
+  xyt_compose(v.from_pose, v.t_be_guess, tto);
 #pragma unroll
   for (int k = 0; k < 3; k++) { r->poses[0][k] = tto[k]; r->poses[1][k] = v.from_pose[k]; }
   r->scans[0] = v.to; r->scans[1] = v.from;
@@ -160,8 +131,8 @@ __global__ __launch_bounds__(256) void verify_prepare_kernel(const VerifyChain c
   double* C = r.cov;
   if (r.reg_ok) {
     double inv[3];
-    d_xyt_inverse(reg.pose, inv);                          // Trevised^-1
-    d_xyt_compose(inv, rj->poses[0], r.t_be);              // Talign = Trevised^-1 * Tto
+    xyt_inverse(reg.pose, inv);                          // Trevised^-1
+    xyt_compose(inv, rj->poses[0], r.t_be);              // Talign = Trevised^-1 * Tto
     for (int k = 0; k < 36; k++) C[k] = 0.0;
     C[0] = 0.01; C[7] = 0.01; C[35] = 1e-4;                 // n_scan_normal.cpp:171-175
     // reg_cov.block<3,3>(0,0) = R^-1 * block * R^-T: only the x-y part of the block is touched by a yaw rotation
@@ -185,7 +156,7 @@ __global__ __launch_bounds__(256) void verify_prepare_kernel(const VerifyChain c
     for (int k = 0; k < 36; k++) C[k] = (k % 7 == 0) ? 1.0 : 0.0;
   }
   double to_pose[3];
-  d_xyt_compose(v.from_pose, r.t_be, to_pose);
+  xyt_compose(v.from_pose, r.t_be, to_pose);
   RegJob* qj = (RegJob*)(c.cost_jobs + (size_t)j * c.stride);
   qj->n_scans = 2; qj->itr = 0;
 #pragma unroll
@@ -324,7 +295,7 @@ int verify_device_chain(cfear_ctx* ctx, const cfear_verify_job* jobs, int32_t n_
   cfear_reg_pair_geometry(&rp, max_cells, max_cells, &pairs_cap, &hint);
   cfear_reg_pair_geometry(&qp, max_cells, max_cells, &pairs_cap_q, &hint_q);
   hint_q.small_pairs = false;
-  char* scr = (char*)cfear_workspace(ctx, kWsRegScratch, cfear_register_scratch_bytes(std::max(pairs_cap, pairs_cap_q)) * n);
+  char* scr = (char*)cfear_workspace(ctx, kWsRegScratch, reg_scratch_bytes(std::max(pairs_cap, pairs_cap_q)) * n);
   if (!scr) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
   CFEAR_CHECK(st.carve());
   mark(0);

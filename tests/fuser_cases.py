@@ -21,7 +21,7 @@ DEFAULTS = dict(res=3.0, submap_scan_size=4, weight_intensity=1, use_guess=1, co
                 reg_max_itr_solver=20, reg_min_itr=3, reg_radius=2.0, reg_cov_scale=1.0, reg_regularization=0.0,
                 cov_sampling_xy_range=0.4, cov_sampling_yaw_range=0.0043625, cov_sampling_samples_per_axis=3,
                 cov_sampling_covariance_scaler=4.0)
-REG_MAX_SCANS = 16                     # cfear_reg_max_scans(): the longest window is one less (the GPU test checks the value)
+REG_MAX_SCANS = 16                     # kRegMaxScans: the longest window is one less (the GPU test checks the value)
 
 _WALLS = 12
 _POINTS = 550

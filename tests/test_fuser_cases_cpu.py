@@ -108,7 +108,7 @@ def _event(name, ev):
         return not any(r["keyframe"] for _, _, r in fr)
     if ev == "keyframe_below_dist":          # a keyframe on rotation alone
         return any(r["keyframe"] and r["key_t"] < p["min_keyframe_dist"] for _, _, r in fr)
-    if ev == "full_window":                  # the window reaches cfear_reg_max_scans() - 1 scans and then evicts three times
+    if ev == "full_window":                  # the window reaches kRegMaxScans - 1 scans and then evicts three times
         return p["submap_scan_size"] == FC.REG_MAX_SCANS - 1 and sum(r["keyframe"] for _, _, r in fr) + 1 >= p["submap_scan_size"] + 3
     if ev == "failed_then_good":
         return any(_has_failed_then_good(oracle_trace(name, b)) for b in range(B))

@@ -144,7 +144,7 @@ def test_case_defaults_are_the_library_defaults():
                 break
         else:
             assert getattr(p, k) == v, k
-    # cfear_reg_max_scans(): a window of REG_MAX_SCANS - 1 keyframes is the longest that create accepts
+    # kRegMaxScans: a window of REG_MAX_SCANS - 1 keyframes is the longest that create accepts
     api.OdometryKeyframeFuser(1, 32, 64, api.odometry_params(submap_scan_size=FC.REG_MAX_SCANS - 1)).close()
     with pytest.raises(Exception):
         api.OdometryKeyframeFuser(1, 32, 64, api.odometry_params(submap_scan_size=FC.REG_MAX_SCANS))

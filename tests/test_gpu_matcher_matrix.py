@@ -1,4 +1,4 @@
-"""GPU: the scan matcher on every cost metric, loss, weight option and limit check_params accepts.
+"""GPU: the scan matcher on every cost metric, loss, weight option and limit cfear_check_reg_params accepts.
 
 Scans are uploaded from the oracle's cells (MapPointNormal(cells=...)), so that a 1e-9 difference in a mean cannot decide a
 tie.  The references are the CPU oracle (oracle/cfear_oracle.cpp) and, for everything point-wise, DenseProblem of
@@ -393,7 +393,7 @@ def _bad_params():
 
 
 def test_refusals():
-    """Every parameter record check_params must refuse, through the four entries that take one: CFEAR_ERR_INVALID_ARGUMENT, the
+    """Every parameter record cfear_check_reg_params must refuse, through the four entries that take one: CFEAR_ERR_INVALID_ARGUMENT, the
     input poses untouched, the outputs as they were, and not one kernel launched (the profile counters stay 0)."""
     from tbv_slam_public_amd import api, _lib as L
     cells, maps, gt = _scene()

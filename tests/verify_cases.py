@@ -7,8 +7,10 @@ by tests/test_gpu_verify_matrix.py; the CPU-only checks of what the pool is mean
                (no registration and no CFEAR cost with any partner at any guess)
   dense nodes  ~1 600 cells (synth.scene_dense, as tests/test_gpu_register.py::_dense_cells) and 3 000 cells (three dense
                worlds side by side, the construction of test_large_registrations_on_every_form)
-  predict_hint a restatement of the launch-hint thresholds (JobSizes::add over mt_fit, csrc/matcher.hip) -- used ONLY to
-               choose inputs; the GPU tests assert what the library reports (profile names, reg["reserved"])."""
+  predict_hint a restatement of the launch-hint thresholds (JobSizes::add over mt_fit, csrc/reg_layout.hpp) -- used ONLY to
+               choose inputs; the GPU tests assert what the library reports (profile names, reg["reserved"]).
+               tests/test_reg_layout_cpu.py holds _mt_fit and predict_hint to the header itself, on the CPU: for every
+               max_cells from 0 to 3200, cost and loss, against a stand-alone program that includes reg_layout.hpp."""
 import numpy as np
 
 RANGE_RES = 0.0438
