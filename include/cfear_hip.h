@@ -583,6 +583,70 @@ typedef struct cfear_tie_record {
 int cfear_association_ties_batch(cfear_ctx* ctx, const cfear_reg_job* jobs, int32_t n_jobs, const cfear_reg_params* par, int32_t itr,
                                  cfear_tie_record* records, int32_t* per_query, int64_t per_query_len);
 
+/* Diagnostic: which scans hang on the in-voxel summation order of pcl::VoxelGrid.  PCL sorts (voxel, point) pairs with an
+ * unstable std::sort and sums a voxel's points sequentially in float (pointnormal.cpp:277-280), so the last bits of a centroid
+ * are libstdc++'s to choose; this library pins input order.  Per scan -- the cloud MapPointNormal hands to VoxelGrid, after
+ * compensation -- and per voxel, with leaf = (float)(radius / downsample_factor), inv_leaf = 1.0f / leaf,
+ * r2 = (float)((double)radius * radius), u = 2^-24 and the voxel's n points in INPUT order:
+ *   c_fwd, c_rev  the sequential float sums first to last and last to first, divided by (float)n; c_fwd is this library's centroid
+ *   e             per axis, in fp64: S = sum x, A = sum |x|, g = (n-1)u / (1 - (n-1)u), mid = S / n, t = g A / n,
+ *                 e = (t + u (|mid| + t)) + 2^-40 (|mid| + 1): the float centroid of EVERY order lies in [mid - e, mid + e]
+ *   pair classes  against every point p of the scan, with the smallest and largest squared distance d2min, d2max from p to
+ *                 that box: sure-in if d2max (1 + 8u) < r2, sure-out if d2min (1 - 8u) >= r2, exposed otherwise
+ *   exposed       the voxel has an exposed pair; at the threshold: sure_in < 6 <= sure_in + exposed (pointnormal.cpp:291)
+ *   changed       the float radius test (dx = c.x - p.x; d = dx * dx; d += dy * dy; d < r2) admits different points at
+ *                 c_fwd and at c_rev: a witness that one legal order does differ
+ * n_voxels_exposed == 0: no reference build can differ from this library through the in-voxel order on this scan;
+ * n_voxels_changed_reversed > 0: at least one legal order does.  The truth lies between the two.
+ *   xyzi [..][4] float, host or device; scan s holds lengths[s] points from point offsets[s] on (offsets NULL: the scans
+ *     follow each other); offsets and lengths are host arrays.
+ *   records [n_scans] and voxels (optional) are host or device memory, both on the same side.  A scan of no points has status
+ *     CFEAR_ERR_EMPTY_CLOUD, one with a coordinate that is not finite CFEAR_ERR_INVALID_ARGUMENT, one of more than
+ *     CFEAR_VOXEL_AUDIT_MAX_POINTS points -- or whose grid reaches beyond 2^23 voxels from the origin or holds 2^31 or more --
+ *     CFEAR_ERR_CAPACITY, with n_points set and every counter 0; the other records are complete and the call returns the
+ *     first such status.
+ *   voxels [voxel_cap]: the rows of scan 0 in ascending voxel key -- the order of VoxelGrid's output --, then scan 1's, ...;
+ *     *n_voxels_out (optional, host) = the rows of the batch.  More than voxel_cap: the table holds the first voxel_cap, every
+ *     record is complete, and the call returns CFEAR_ERR_CAPACITY (behind a scan's status, if there is one).
+ * The call reads the voxel counts back between its two launches, so it is synchronous on either side.
+ * Refused with CFEAR_ERR_INVALID_ARGUMENT before anything is launched or written: null xyzi, lengths, params or records,
+ * n_scans < 0, voxel_cap < 0, a radius or downsample_factor that is not finite and > 0, a negative length or offset.      */
+#define CFEAR_VOXEL_AUDIT_TILE 1024          /* points per LDS tile of the audit's sweeps (tests cross it on purpose)          */
+#define CFEAR_VOXEL_AUDIT_MAX_POINTS 40960   /* per scan: n_pairs_exposed <= points x voxels stays below 2^31                  */
+typedef struct cfear_voxel_audit_params {
+  float radius;                         /* MapPointNormal's radius (3.0)                                                    */
+  float pad;
+  double downsample_factor;             /* (1.0)                                                                            */
+} cfear_voxel_audit_params;             /* 16 bytes */
+void cfear_voxel_audit_params_default(cfear_voxel_audit_params* p);
+typedef struct cfear_voxel_audit_record {
+  int32_t status;
+  int32_t n_points;
+  int32_t n_voxels;
+  int32_t n_centroids_reversed_differ;  /* voxels whose c_fwd and c_rev differ in a bit                                     */
+  int32_t n_pairs_exposed;
+  int32_t n_voxels_exposed;
+  int32_t n_voxels_exposed_at_threshold;
+  int32_t n_voxels_changed_reversed;
+  int32_t max_voxel_points;
+  int32_t pad;
+  double max_halfwidth;                 /* the largest e of the scan, either axis                                           */
+} cfear_voxel_audit_record;             /* 48 bytes */
+typedef struct cfear_voxel_audit_voxel {
+  uint32_t key;                         /* ijk0 + ijk1 * div_bx, as VoxelGrid computes it                                   */
+  int32_t n_points;
+  float c_fwd[2];
+  float c_rev[2];
+  double e[2];
+  int32_t n_sure_in;
+  int32_t n_exposed;
+  int32_t changed_reversed;
+  int32_t pad;
+} cfear_voxel_audit_voxel;              /* 56 bytes */
+int cfear_voxel_order_audit_batch(cfear_ctx* ctx, const float* xyzi, const int64_t* offsets, const int32_t* lengths, int32_t n_scans,
+                                  const cfear_voxel_audit_params* par, cfear_voxel_audit_record* records,
+                                  cfear_voxel_audit_voxel* voxels, int64_t voxel_cap, int64_t* n_voxels_out);
+
 /* Covariance of a registration by cost sampling.  Replaces
  * OdometryKeyframeFuser::approximateCovarianceBySampling (odometrykeyframefuser.cpp:261-380) and
  * loopclosure::approximateCovarianceBySampling (tbv_slam/src/tbv_slam/loopclosure.cpp:99-208):

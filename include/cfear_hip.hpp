@@ -580,6 +580,45 @@ inline std::vector<cfear_tie_record> AssociationTies(Context& ctx, const std::ve
   return records;
 }
 
+// Which scans hang on the in-voxel summation order of pcl::VoxelGrid (cfear_voxel_order_audit_batch):
+// clouds[s] = the xyzi floats of scan s (four per point), the cloud MapPointNormal hands to VoxelGrid.  One call for the
+// batch.  voxels (optional) receives every scan's rows in ascending voxel key, offsets (optional) the first row of every
+// scan and, as its last element, the total.  A scan that is empty, not finite or too large carries its status in its
+// record; only a refusal of the call throws.
+inline std::vector<cfear_voxel_audit_record> VoxelOrderAudit(Context& ctx, const std::vector<std::vector<float>>& clouds, float radius = 3.0f,
+                                                             double downsample_factor = 1.0,
+                                                             std::vector<cfear_voxel_audit_voxel>* voxels = nullptr,
+                                                             std::vector<int64_t>* offsets = nullptr) {
+  const size_t n = clouds.size();
+  std::vector<int32_t> lengths(n);
+  std::vector<float> xyzi;
+  for (size_t s = 0; s < n; s++) {
+    if (clouds[s].size() % 4) throw CfearError(CFEAR_ERR_INVALID_ARGUMENT, "VoxelOrderAudit: a cloud holds four floats per point");
+    lengths[s] = (int32_t)(clouds[s].size() / 4);
+    xyzi.insert(xyzi.end(), clouds[s].begin(), clouds[s].end());
+  }
+  const int64_t cap = (int64_t)(xyzi.size() / 4);            // no scan has more voxels than points
+  xyzi.resize(xyzi.size() + 4, 0.f);
+  cfear_voxel_audit_params par;
+  cfear_voxel_audit_params_default(&par);
+  par.radius = radius;
+  par.downsample_factor = downsample_factor;
+  std::vector<cfear_voxel_audit_record> records(n);
+  if (voxels) voxels->assign((size_t)cap, cfear_voxel_audit_voxel{});
+  int64_t rows = 0;
+  const int rc = cfear_voxel_order_audit_batch(ctx.get(), xyzi.data(), nullptr, lengths.data(), (int32_t)n, &par, records.data(),
+                                               voxels && cap > 0 ? voxels->data() : nullptr, cap, &rows);
+  bool carried = false;
+  for (const cfear_voxel_audit_record& r : records) carried = carried || r.status == rc;
+  if (rc != CFEAR_OK && !carried) ctx.check(rc);
+  if (voxels) voxels->resize((size_t)rows);
+  if (offsets) {
+    offsets->assign(n + 1, 0);
+    for (size_t s = 0; s < n; s++) (*offsets)[s + 1] = (*offsets)[s] + records[s].n_voxels;
+  }
+  return records;
+}
+
 // radarDriver + OdometryKeyframeFuser for n independent sequences, one frame per call (cfear_odometry_*): the whole
 // path polar image -> pose on the GPU; with par.keep_nodes the RadarScan of every frame can be collected.
 // Sharded candidate steps kept in flight (cfear_candidate_pipe): what the loop-closure thread of a rank

@@ -138,6 +138,19 @@ TIE_RECORD_DTYPE = np.dtype([(n, "<i4") for n in ("n_queries", "n_in_radius", "n
 assert TIE_RECORD_DTYPE.itemsize == C.sizeof(TieRecord) == 32
 TIE_TILE = 1024                     # CFEAR_TIE_TILE
 
+
+class VoxelAuditParams(C.Structure):      # cfear_voxel_audit_params
+    _fields_ = [("radius", C.c_float), ("pad", C.c_float), ("downsample_factor", C.c_double)]
+
+
+VOXEL_AUDIT_RECORD_DTYPE = np.dtype([(n, "<i4") for n in ("status", "n_points", "n_voxels", "n_centroids_reversed_differ", "n_pairs_exposed",
+                                                          "n_voxels_exposed", "n_voxels_exposed_at_threshold", "n_voxels_changed_reversed",
+                                                          "max_voxel_points", "pad")] + [("max_halfwidth", "<f8")])
+VOXEL_AUDIT_VOXEL_DTYPE = np.dtype([("key", "<u4"), ("n_points", "<i4"), ("c_fwd", "<f4", (2,)), ("c_rev", "<f4", (2,)), ("e", "<f8", (2,)),
+                                    ("n_sure_in", "<i4"), ("n_exposed", "<i4"), ("changed_reversed", "<i4"), ("pad", "<i4")])
+assert C.sizeof(VoxelAuditParams) == 16 and VOXEL_AUDIT_RECORD_DTYPE.itemsize == 48 and VOXEL_AUDIT_VOXEL_DTYPE.itemsize == 56
+VOXEL_AUDIT_TILE, VOXEL_AUDIT_MAX_POINTS = 1024, 40960      # CFEAR_VOXEL_AUDIT_TILE, CFEAR_VOXEL_AUDIT_MAX_POINTS
+
 CANDIDATE_DTYPE = np.dtype([("target", "<i4"), ("source", "<i4"), ("target_xyt", "<f8", (3,)), ("source_xyt", "<f8", (3,))])
 assert CANDIDATE_DTYPE.itemsize == 56
 
@@ -313,6 +326,7 @@ EXPORTS = [
     "cfear_sync_trajectories", "cfear_tum_write", "cfear_cov_write",
     "cfear_graph_align_batch", "cfear_graph_map_batch", "cfear_graph_string_write", "cfear_graph_output_write",
     "cfear_association_ties_batch", "cfear_scan_closest_ties",
+    "cfear_voxel_audit_params_default", "cfear_voxel_order_audit_batch",
 ]
 
 PIPE_GRAPH, PIPE_TIMING = 1, 2      # enum { CFEAR_PIPE_GRAPH, CFEAR_PIPE_TIMING }
@@ -568,6 +582,9 @@ def lib():
     L.cfear_scan_closest_idx.argtypes = [vp, vp, C.c_int32, C.c_double, vp]
     L.cfear_scan_closest_ties.argtypes = [vp, vp, C.c_int32, C.c_double, vp, vp, vp]
     L.cfear_association_ties_batch.argtypes = [vp, C.POINTER(RegJob), C.c_int32, C.POINTER(RegParams), C.c_int32, vp, vp, C.c_int64]
+    L.cfear_voxel_audit_params_default.argtypes = [C.POINTER(VoxelAuditParams)]
+    L.cfear_voxel_audit_params_default.restype = None
+    L.cfear_voxel_order_audit_batch.argtypes = [vp, vp, vp, vp, C.c_int32, C.POINTER(VoxelAuditParams), vp, vp, C.c_int64, C.POINTER(C.c_int64)]
     L.cfear_scan_surface_path.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.cfear_polar_rotate_ccw.argtypes = [vp, vp, C.POINTER(PolarDesc), vp, C.c_int32, C.c_int64]
     L.cfear_verify_params_default.argtypes = [C.POINTER(VerifyParams)]

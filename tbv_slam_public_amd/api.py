@@ -959,6 +959,71 @@ def tie_sensitivity(jobs, par=None, ctx=None):
             "delta": np.abs(result["pose"] - result_flipped["pose"]).reshape(len(jobs), 3)}
 
 
+# ------------------------------------------------------------------------------------------------
+# Which scans hang on the in-voxel summation order of pcl::VoxelGrid
+# ------------------------------------------------------------------------------------------------
+def voxel_order_audit(clouds, radius=3.0, downsample_factor=1.0, voxels=False, ctx=None, device_out=False):
+    """cfear_voxel_order_audit_batch: per scan -- clouds is a list of [n, 4] float32 arrays, all NumPy or all torch CUDA tensors,
+    the clouds MapPointNormal would hand to VoxelGrid -- whether a reference build can differ from this library through the
+    order in which a voxel's points are summed.  n_voxels_exposed == 0: it cannot; n_voxels_changed_reversed > 0: the
+    reversed order does; the truth lies between the two.  One call for the batch.
+    -> a VOXEL_AUDIT_RECORD_DTYPE array [n]; with voxels (records, table VOXEL_AUDIT_VOXEL_DTYPE [total], offsets int64
+    [n + 1]): scan s's voxels, in ascending key, are table[offsets[s]:offsets[s + 1]].  A scan that is empty, holds a
+    coordinate that is not finite or is too large carries its status in its record and has no rows; nothing is raised for
+    it.  With device_out the records (uint8 [n, 48]) and the table (uint8 [total, 56]) are torch CUDA tensors."""
+    ctx = ctx or default_context()
+    clouds = list(clouds)
+    n = len(clouds)
+    dev = n > 0 and _is_torch(clouds[0])
+    lengths = np.array([int(c.shape[0]) for c in clouds], np.int32)
+    total = int(lengths.sum())
+    if dev:
+        import torch
+        xyzi = torch.cat([c.reshape(-1, 4).float() for c in clouds]).contiguous() if total else torch.zeros((1, 4), device="cuda")
+    else:
+        xyzi = np.concatenate([np.asarray(c, np.float32).reshape(-1, 4) for c in clouds] + [np.zeros((1, 4), np.float32)])
+    par = L.VoxelAuditParams(float(radius), 0.0, float(downsample_factor))
+    cap = max(total, 1)
+    if device_out:
+        import torch
+        rec = torch.zeros((n, L.VOXEL_AUDIT_RECORD_DTYPE.itemsize), dtype=torch.uint8, device="cuda")
+        tab = torch.zeros((cap, L.VOXEL_AUDIT_VOXEL_DTYPE.itemsize), dtype=torch.uint8, device="cuda") if voxels else None
+    else:
+        rec = np.zeros(n, L.VOXEL_AUDIT_RECORD_DTYPE)
+        tab = np.zeros(cap, L.VOXEL_AUDIT_VOXEL_DTYPE) if voxels else None
+    _torch_ready(ctx, xyzi, rec)
+    rows = C.c_int64(0)
+    rc = ctx._lib.cfear_voxel_order_audit_batch(ctx.h, _ptr(xyzi)[0], None, lengths.ctypes.data, n, C.byref(par), _ptr(rec)[0], _ptr(tab)[0],
+                                                cap, C.byref(rows))
+    status = (rec.cpu().numpy().view(L.VOXEL_AUDIT_RECORD_DTYPE).reshape(-1) if device_out else rec)["status"]
+    if rc != L.OK and not (status == rc).any():            # a refusal of the call, not a scan's own status
+        ctx.check(rc)
+    if not voxels:
+        return rec
+    counts = (rec.cpu().numpy().view(L.VOXEL_AUDIT_RECORD_DTYPE).reshape(-1) if device_out else rec)["n_voxels"]
+    return rec, tab[:rows.value], np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int64)
+
+
+def voxel_order_spread(job, par=None, radius=3.0, origin=(0.0, 0.0), weight_intensity=True, ctx=None):
+    """The legal spread of THIS registration under the in-voxel order, as numbers: job = (clouds, Tsrc), the clouds of the
+    job's scans ([n, 4] float32, the free source last).  The scans are built from the clouds as given and from the clouds
+    reversed -- this library sums a voxel in input order, so the reversed cloud is the opposite order in every voxel -- and
+    both jobs are registered in one batch.  Existing calls only.
+    -> dict: audit (VOXEL_AUDIT_RECORD_DTYPE, one per cloud), result, result_reversed (RESULT_DTYPE records) and delta [3] =
+    |dx|, |dy|, |dtheta| between the two registered poses.  Nothing here says which order libstdc++'s sort leaves: the
+    spread is between this library's order and its opposite."""
+    ctx = ctx or default_context()
+    reg = _tie_reg(par, ctx)
+    clouds, T = job
+    clouds = [np.ascontiguousarray(c, dtype=np.float32).reshape(-1, 4) for c in clouds]
+    T = np.ascontiguousarray(T, dtype=np.float64).reshape(len(clouds), 3)
+    fwd = [MapPointNormal(c, radius, origin, weight_intensity, ctx=ctx) for c in clouds]
+    rev = [MapPointNormal(np.ascontiguousarray(c[::-1]), radius, origin, weight_intensity, ctx=ctx) for c in clouds]
+    res = reg.RegisterBatch([(fwd, T), (rev, T)])
+    return {"audit": voxel_order_audit(clouds, radius, MapPointNormal.downsample_factor, ctx=ctx), "result": res[0],
+            "result_reversed": res[1], "delta": np.abs(res[0]["pose"] - res[1]["pose"]).reshape(3)}
+
+
 class CeresCost:
     """cfear_cost: Ceres-compatible evaluation of one association set (n_scan_normal.cpp:264-318)."""
 

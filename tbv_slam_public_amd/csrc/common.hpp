@@ -91,6 +91,8 @@ enum WsSlot : int {
   kWsTrajSync = 25,       // trajectory synchronisation: staged poses and stamps, pair and block tables, ranges, staged outputs
   kWsGraphFinish = 26,    // graph alignment and maps: staged poses, flags and clouds, graph, node and tile tables, sums, staged maps
   kWsTieAudit = 27,       // tie audit: job records, staged queries, staged records and per-query groups
+  kWsVoxelAudit = 28,     // voxel-order audit: staged clouds, scan tables, leader lists and flags, staged records and voxel rows
+  kWsCount
 };
 
 struct cfear_ctx {
@@ -103,7 +105,7 @@ struct cfear_ctx {
   std::vector<Event> event_pool;
   // grow-only device workspaces (indexed by WsSlot so stages of one pipeline do not alias)
   struct Ws { DevBuf<void> p; size_t bytes = 0; };
-  Ws ws[28];
+  Ws ws[kWsCount];
   // pinned host staging for small read-backs
   PinnedBuf<char> pinned;
   size_t pinned_bytes = 0;
