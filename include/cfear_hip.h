@@ -373,6 +373,46 @@ int cfear_filter_cen2019(cfear_ctx* ctx, const uint8_t* polar, const cfear_polar
                          float* xyzi, int32_t* n_points, int32_t cap_points, int32_t* targets, uint8_t* region_mask,
                          float* image_stats, int32_t* counts);
 
+/* Which landmarks of cfear_filter_cen2019 hang on the order among equal h that cen2019features' std::sort leaves open
+ * (DESIGN.md sections 3 and 4.20; tests/cen2019_audit_cpu.py is the definition).  The batch, its limits and its refusals are
+ * cfear_filter_cen2019's.  Per sweep, with T = rows - 1, a run a maximal stretch of bins with s < 0 and a run's touchers its own
+ * candidates, the candidate right of it and the one left of it if that sits at a bin < T:
+ *   a candidate is SURELY fresh if in every run it touches it alone attains the largest h among the touchers, POSSIBLY fresh if
+ *   it attains it; every order's fresh candidates lie between the two sets, so every order's walk ends at an h in [h_lo, h_hi],
+ *   the h of the max_points-th largest surely fresh candidate and of the max_points-th largest possibly fresh one (-inf: fewer
+ *   exist, the walk goes through everything; +inf: max_points == 0).  The candidates with h > h_hi are gone through under every
+ *   order, those with h < h_lo under none; the BAND between is the order's to decide (a band of one candidate is the walk's last
+ *   under every order: it counts as gone through and n_band is 0).
+ *   R_in / R_out: the marks from the candidates above the band / with the band, the run that straddles column T marked whole
+ *   only if its largest own h sits at bins < T alone (R_in) / at some bin < T (R_out).  R_in <= R(order) <= R_out for every order.
+ *   A target is CERTAIN if R_in emits it from a run that is the same maximal run (from min_range_bins on) in R_out: every order
+ *   emits it, at the same bin.
+ *   The WITNESS is the sweep filtered with equal h in DESCENDING row * cols + bin: one legal order's outcome.
+ * n_marks_in == n_marks_out ("clear"): no order of equal h changes a mark or a target of this sweep.  It does NOT say that a
+ * reference build agrees: the result is conditional on mean_h (the order of its fp64 sum is a separate open point, DESIGN.md
+ * section 4.10b) and on `g /= maxg`.  An exposed sweep need not change either: n_*_changed_reversed > 0 shows that one does.
+ * records [batch]; optional: targets int32 [batch][cap_points][2] (the filter's, same order), certain uint8 [batch][cap_points]
+ * (1 = certain, parallel to targets), marks uint8 [batch][rows][cols] (bit 0 R_in, bit 1 R, bit 2 R_out, bit 3 the witness's R).
+ * cap_points may be 0 when targets and certain are NULL.  The image and every output are all host or all device memory.  A sweep
+ * with more than cap_points targets yields CFEAR_ERR_CAPACITY when targets or certain is given: every record is complete, the
+ * arrays hold the first cap_points.  A flat sweep has zeros in the integer fields and NaN levels.  A sweep's record and arrays
+ * are bit-identical alone and at any batch position.  The call is synchronous.                                            */
+typedef struct cfear_cen2019_order_record {
+  int32_t n_candidates, n_fresh;        /* as counts[0], counts[1] of the filter (this library's order)                      */
+  int32_t n_sure_fresh, n_possibly_fresh;
+  int32_t n_band;                       /* candidates whose processing the order decides; 0: the cut is order-free           */
+  int32_t n_rows_straddle_tied;         /* rows whose straddling run has its largest own h on both sides of T, among those
+                                           gone through under some order                                                      */
+  int32_t n_marks_in, n_marks, n_marks_out;   /* popcounts of R_in, this library's R, R_out                                  */
+  int32_t n_targets, n_targets_certain; /* this library's targets; those certain under every order                           */
+  int32_t n_targets_reversed, n_targets_changed_reversed;   /* the witness: its targets, the symmetric difference with ours  */
+  int32_t n_marks_changed_reversed;
+  float h_hi, h_lo;
+} cfear_cen2019_order_record;           /* 64 bytes */
+int cfear_cen2019_order_audit(cfear_ctx* ctx, const uint8_t* polar, const cfear_polar_desc* desc, const cfear_cen2019_params* par,
+                              cfear_cen2019_order_record* records, int32_t* targets, uint8_t* certain, int32_t cap_points,
+                              uint8_t* marks);
+
 /* ---- C: motion compensation ----------------------------------------------------------------
  * Replaces Compensate(cloud, mot, ccw)  utils.cpp:96-107 (+ GetRelTimeStamp utils.h:28-32).
  * xyzi float [n][4] modified in place; mot = (x, y, theta) of the previous motion.           */

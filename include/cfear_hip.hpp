@@ -939,6 +939,31 @@ inline std::vector<int32_t> cen2019features(CFEAR_Radarodometry::Context& ctx, c
   tg.resize(2 * (size_t)n);
   return tg;
 }
+// Which of those targets hang on the order among equal h that the reference's std::sort leaves open (cfear_cen2019_order_audit;
+// DESIGN.md section 4.20).  record.n_marks_in == record.n_marks_out: no order changes this sweep.  targets are cen2019features',
+// certain[k] says whether every order emits target k.
+struct Cen2019OrderAudit {
+  cfear_cen2019_order_record record;
+  std::vector<int32_t> targets;      // (azimuth, bin) pairs
+  std::vector<uint8_t> certain;
+  bool clear() const { return record.n_marks_in == record.n_marks_out; }
+};
+inline Cen2019OrderAudit cen2019OrderAudit(CFEAR_Radarodometry::Context& ctx, const uint8_t* image, int rows, int cols, int stride,
+                                           int max_points = 1000, int min_range = 0) {
+  cfear_polar_desc d{rows, cols, stride, 1, 0};
+  cfear_cen2019_params p;
+  cfear_cen2019_params_default(&p);
+  p.max_points = max_points;
+  p.min_range_bins = min_range;
+  const int32_t cap = rows * ((cols + 1) / 2);
+  Cen2019OrderAudit out;
+  out.targets.resize((size_t)cap * 2);
+  out.certain.resize((size_t)cap);
+  ctx.check(cfear_cen2019_order_audit(ctx.get(), image, &d, &p, &out.record, out.targets.data(), out.certain.data(), cap, nullptr));
+  out.targets.resize(2 * (size_t)out.record.n_targets);
+  out.certain.resize((size_t)out.record.n_targets);
+  return out;
+}
 #ifdef CFEAR_HIP_HAVE_CV_BRIDGE
 // the reference's shape: targets = Ones(3, n) with the azimuths in row 0 and the bins in row 1 (Utils.cpp:584-592); Targets is
 // Eigen::MatrixXd there

@@ -149,6 +149,11 @@ VOXEL_AUDIT_RECORD_DTYPE = np.dtype([(n, "<i4") for n in ("status", "n_points", 
 VOXEL_AUDIT_VOXEL_DTYPE = np.dtype([("key", "<u4"), ("n_points", "<i4"), ("c_fwd", "<f4", (2,)), ("c_rev", "<f4", (2,)), ("e", "<f8", (2,)),
                                     ("n_sure_in", "<i4"), ("n_exposed", "<i4"), ("changed_reversed", "<i4"), ("pad", "<i4")])
 assert C.sizeof(VoxelAuditParams) == 16 and VOXEL_AUDIT_RECORD_DTYPE.itemsize == 48 and VOXEL_AUDIT_VOXEL_DTYPE.itemsize == 56
+CEN2019_ORDER_RECORD_DTYPE = np.dtype([(n, "<i4") for n in (                 # cfear_cen2019_order_record
+    "n_candidates", "n_fresh", "n_sure_fresh", "n_possibly_fresh", "n_band", "n_rows_straddle_tied", "n_marks_in", "n_marks",
+    "n_marks_out", "n_targets", "n_targets_certain", "n_targets_reversed", "n_targets_changed_reversed",
+    "n_marks_changed_reversed")] + [("h_hi", "<f4"), ("h_lo", "<f4")])
+assert CEN2019_ORDER_RECORD_DTYPE.itemsize == 64
 VOXEL_AUDIT_TILE, VOXEL_AUDIT_MAX_POINTS = 1024, 40960      # CFEAR_VOXEL_AUDIT_TILE, CFEAR_VOXEL_AUDIT_MAX_POINTS
 
 CANDIDATE_DTYPE = np.dtype([("target", "<i4"), ("source", "<i4"), ("target_xyt", "<f8", (3,)), ("source_xyt", "<f8", (3,))])
@@ -327,6 +332,7 @@ EXPORTS = [
     "cfear_graph_align_batch", "cfear_graph_map_batch", "cfear_graph_string_write", "cfear_graph_output_write",
     "cfear_association_ties_batch", "cfear_scan_closest_ties",
     "cfear_voxel_audit_params_default", "cfear_voxel_order_audit_batch",
+    "cfear_cen2019_order_audit",
 ]
 
 PIPE_GRAPH, PIPE_TIMING = 1, 2      # enum { CFEAR_PIPE_GRAPH, CFEAR_PIPE_TIMING }
@@ -529,6 +535,7 @@ def lib():
     L.cfear_cen2019_params_default.argtypes = [C.POINTER(Cen2019Params)]
     L.cfear_cen2019_params_default.restype = None
     L.cfear_filter_cen2019.argtypes = [vp, vp, C.POINTER(PolarDesc), C.POINTER(Cen2019Params), vp, vp, C.c_int32, vp, vp, vp, vp]
+    L.cfear_cen2019_order_audit.argtypes = [vp, vp, C.POINTER(PolarDesc), C.POINTER(Cen2019Params), vp, vp, vp, C.c_int32, vp]
     L.cfear_compensate.argtypes = [vp, vp, C.c_int32, C.POINTER(C.c_double), C.c_int32]
     L.cfear_scan_create.argtypes = [vp, vp, C.c_int32, C.POINTER(FeatureParams), C.POINTER(vp)]
     L.cfear_scan_from_cells.argtypes = [vp, vp, C.c_int32, C.POINTER(vp)]

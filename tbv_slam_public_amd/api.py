@@ -439,6 +439,45 @@ def filter_cen2019(img, max_points=1000, min_range_bins=0, range_res=0.04328, ca
     return res
 
 
+def cen2019_order_audit(img, max_points=1000, min_range_bins=0, cap_points=None, want_targets=False, want_marks=False, ctx=None):
+    """cfear_cen2019_order_audit: which landmarks of filter_cen2019 hang on the order among equal h that the reference's
+    std::sort leaves open (DESIGN.md section 4.20), for a uint8 image [rows, cols] or a batch [b, rows, cols] (NumPy, or a torch
+    CUDA tensor -- a view with a row pitch or a batch stride is used in place).  Returns dict(records: a
+    CEN2019_ORDER_RECORD_DTYPE array [b] (NumPy on either side)[, targets [b, cap, 2] and certain uint8 [b, cap]: the filter's
+    targets and whether every order emits each][, marks uint8 [b, rows, cols]: bit 0 R_in, bit 1 R, bit 2 R_out, bit 3 the
+    reversed order's R]).  records["n_marks_in"] == records["n_marks_out"]: no order changes that sweep."""
+    ctx = ctx or default_context()
+    d, batch, rows, cols = _desc(img)
+    cap = int(cap_points or rows * ((cols + 1) // 2)) if want_targets else 0
+    par = cen2019_params(max_points=int(max_points), min_range_bins=int(min_range_bins))
+    dev = _is_torch(img)
+    if dev:
+        import torch
+        assert img.dtype == torch.uint8 and img.stride(-1) == 1
+        d.stride = img.stride(-2)
+        d.batch_stride = img.stride(0) if img.ndim == 3 else rows * d.stride
+        mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=img.device)
+        i32, u8 = torch.int32, torch.uint8
+    else:
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        mk = lambda shape, dt: np.empty(shape, dt)
+        i32, u8 = np.int32, np.uint8
+    rec = mk((batch, L.CEN2019_ORDER_RECORD_DTYPE.itemsize), u8)
+    res = {}
+    if want_targets:
+        res["targets"] = mk((batch, cap, 2), i32)
+        res["certain"] = mk((batch, cap), u8)
+    if want_marks:
+        res["marks"] = mk((batch, rows, cols), u8)
+    _torch_ready(ctx, img, rec, *res.values())
+    p = img.data_ptr() if dev else _ptr(img)[0]
+    rc = ctx._lib.cfear_cen2019_order_audit(ctx.h, p, C.byref(d), C.byref(par), _ptr(rec)[0], _ptr(res.get("targets"))[0],
+                                            _ptr(res.get("certain"))[0], cap, _ptr(res.get("marks"))[0])
+    ctx.check(rc)
+    res["records"] = (rec.cpu().numpy() if dev else rec).view(L.CEN2019_ORDER_RECORD_DTYPE).reshape(batch)
+    return res
+
+
 def k_strongest_filter(img, k_strongest, z_min, range_res, min_distance, ctx=None):
     """The legacy k_strongest_filter / InsertStrongestK (radar_filters.cpp:25-78; CorAl's kstrongRadar).  img: uint8
     [rows, cols] or [batch, rows, cols] (NumPy or torch CUDA).  Returns dict(xyzi [batch, rows * k, 4], n_points)."""

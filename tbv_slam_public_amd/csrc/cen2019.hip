@@ -28,158 +28,17 @@
 //   cen2019_emit_kernel     a wavefront per row: R of the row and of its two neighbours (wrapping), the runs an unmarked bin
 //                           ends, their adjacency test and getMaxInRegion's bin -> target bitmap
 //   cen2019_cloud_kernel    compaction in (row, bin) order without atomics, as cen2018_cloud_kernel; also the sweep's counts
+// The limits, C19Args, the device helpers and the launchers c19_launch_* live in cen2019_dev.hpp: cen2019_audit.hip runs this
+// chain twice (C19Args::tie_rev = 1 reverses the order among equal h; the filter always passes 0) and the select on key sets of its own.
 // Rows are read with 16-byte loads only where all 16 bytes lie inside the row, and byte by byte elsewhere (ragged widths,
 // odd strides, rows narrower than a piece): nothing is read beyond a row's own `cols` bytes.
 #include <cmath>
 
-#include "common.hpp"
+#include "cen2019_dev.hpp"
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4), aligned(4)));
-typedef unsigned long long u64;
-
-constexpr int kC19MaxCols = 8192;
-constexpr long long kC19MaxPixels = 1ll << 22;   // the fp64 sum of f is exact in any order up to here
-constexpr int kC19CloudSplit = 4;
-constexpr size_t kC19CloudLists = 4 * 64 * 64 * 2;                          // cen2019_cloud_kernel: a bin list per wavefront
-constexpr int kC19MaxRows = (int)((160 * 1024 - kC19CloudLists - 8 * 1024) / 4) - 1;   // ... an offset per row, and its static tables
-constexpr size_t kC19ChunkBytes = 64u << 20;     // image bytes per chunk
-constexpr size_t kC19KeyBytes = 256u << 20;      // selection-buffer bytes per chunk (8 per pixel)
-constexpr int kC19MaxGridY = 65535;              // images per chunk: the row kernels have the image on gridDim.y
-constexpr unsigned kC19None = 0xffffu;
-
-struct C19Args {
-  const uint8_t* polar;
-  int rows, cols, stride, batch;
-  long long batch_stride;
-  int max_points, min_range_bins;
-  int words;                         // 64-bin words per row
-  int rowb_bytes;                    // LDS bytes of a staged row
-  int per_wave;                      // LDS bytes per wavefront of the kernel being launched
-  // scratch, per chunk
-  float* row_maxg;                   // [batch][rows]
-  double* row_sum;                   // [batch][rows]: sum of f, then sum of h
-  float* img;                        // [batch][4]: mean, float(1 / maxg), mean_h, maxg
-  u64* keys;                         // [batch][rows][cols]: a row's fresh keys at the start of its piece
-  int32_t* row_cnt;                  // [batch][rows][4]: candidates, fresh, processed, targets
-  u64* row_minkey;                   // [batch][rows]: the smallest processed key
-  u64* cut;                          // [batch]: K
-  u64* mark_bits;                    // [batch][rows][words]: R
-  u64* hpos_bits;                    // [batch][rows][words]: h > 0
-  u64* tgt_bits;                     // [batch][rows][words]
-  // outputs
-  uint8_t* region_mask;              // optional [batch][rows][cols]
-  float* image_stats;                // optional [batch][4]
-  int32_t* counts;                   // optional [batch][3]
-  const double* cos_t;
-  const double* sin_t;
-  double range_res;
-  float* xyzi;
-  int32_t* n_points;
-  int32_t* targets;
-  int cap_points;
-};
-
-__device__ __forceinline__ float c19_f(uint32_t byte) { return (float)byte * (float)(1 / 255.0); }   // convertTo(CV_32F, 1/255.0)
-
-__device__ __forceinline__ void c19_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ u64 c19_wave_max_u64(u64 v) {
-  for (int o = 32; o; o >>= 1) {
-    const u64 t = __shfl_xor(v, o);
-    v = t > v ? t : v;
-  }
-  return v;
-}
-__device__ __forceinline__ float c19_wave_max_f32(float v) {
-  for (int o = 32; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-
-// the row's bytes into LDS; the caller synchronises the wavefront
-__device__ __forceinline__ void c19_stage_row(const uint8_t* rowp, int cols, uint8_t* rowb, int lane) {
-  int done = 0;
-  if ((((uintptr_t)rowp) & 3) == 0) {
-    done = cols & ~15;
-    for (int j = lane * 16; j < done; j += 64 * 16) *(u32x4*)(rowb + j) = *(const u32x4*)(rowp + j);
-  }
-  for (int j = done + lane; j < cols; j += 64) rowb[j] = rowp[j];
-}
-
-// |f[j + 1] - f[j - 1]| with BORDER_REFLECT101: 0 in the first and the last bin (Utils.cpp:499-504)
-__device__ __forceinline__ float c19_grad(const uint8_t* rowb, int j, int cols) {
-  return (j > 0 && j < cols - 1) ? fabsf(c19_f(rowb[j + 1]) - c19_f(rowb[j - 1])) : 0.f;
-}
-// s and h of bin j (Utils.cpp:507-512); inv = float(1 / double(maxg)), infinite for a flat sweep (h is NaN then, as in the reference)
-__device__ __forceinline__ void c19_sh(const uint8_t* rowb, int j, int cols, float mean, float inv, float& s, float& h) {
-  const float g = c19_grad(rowb, j, cols) * inv;
-  s = c19_f(rowb[j]) - mean;
-  h = s * (1.f - g);
-}
-// descending h = descending key; -0 and +0 are one value (the comparison of the reference's sort)
-__device__ __forceinline__ uint32_t c19_ord(float h) {
-  const uint32_t u = __float_as_uint(h == 0.f ? 0.f : h);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float c19_unord(uint32_t o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
-// 54 bits: 32 of h, 22 of the flat index (rows * cols <= 2^22), descending in the index so that the larger key comes first
-__device__ __forceinline__ u64 c19_key(uint32_t ord, uint32_t flat) { return ((u64)ord << 22) | (u64)(0x3fffffu - flat); }
-__device__ __forceinline__ uint32_t c19_key_flat(u64 key) { return 0x3fffffu - (uint32_t)(key & 0x3fffffull); }
-
-__device__ __forceinline__ bool c19_bit(const u64* bits, int j) { return (bits[j >> 6] >> (j & 63)) & 1ull; }
-
-// prevz[w] = the last bin before word w with a clear bit (-1: none), nextz[w] = the first bin from word w on with a clear
-// bit (words * 64: none), w = 0 .. words.  Bins >= cols are clear.
-__device__ __forceinline__ void c19_zero_tables(const u64* bits, int words, int* prevz, int* nextz, int lane) {
-  for (int w = lane; w <= words; w += 64) {
-    int pz = -1, nz = words * 64;
-    for (int p = w - 1; p >= 0; p--) {
-      const u64 z = ~bits[p];
-      if (z) { pz = p * 64 + 63 - __clzll((long long)z); break; }
-    }
-    for (int p = w; p < words; p++) {
-      const u64 z = ~bits[p];
-      if (z) { nz = p * 64 + __ffsll((long long)z) - 1; break; }
-    }
-    prevz[w] = pz;
-    nextz[w] = nz;
-  }
-}
-// first bin of the run of set bits that ends at, or contains, bin j (bit j itself is not looked at)
-__device__ __forceinline__ int c19_run_start(const u64* bits, const int* prevz, int j) {
-  const int w = j >> 6, b = j & 63;
-  const u64 zb = ~bits[w] & ((1ull << b) - 1ull);
-  return zb ? w * 64 + 64 - __clzll((long long)zb) : prevz[w] + 1;
-}
-// last bin of the run of set bits that contains bin j
-__device__ __forceinline__ int c19_run_end(const u64* bits, const int* nextz, int j) {
-  const int w = j >> 6, b = j & 63;
-  const u64 za = b == 63 ? 0ull : (~bits[w] & ~((2ull << b) - 1ull));
-  return (za ? w * 64 + __ffsll((long long)za) - 1 : nextz[w + 1]) - 1;
-}
-// the highest set bit of bits[] in [u, v], -1 if none
-__device__ __forceinline__ int c19_highest(const u64* bits, int u, int v) {
-  for (int w = v >> 6; w >= (u >> 6); w--) {
-    u64 m = bits[w];
-    if (w == (v >> 6) && (v & 63) != 63) m &= (2ull << (v & 63)) - 1ull;
-    if (w == (u >> 6)) m &= ~((1ull << (u & 63)) - 1ull);
-    if (m) return w * 64 + 63 - __clzll((long long)m);
-  }
-  return -1;
-}
-__device__ __forceinline__ void c19_set_range(u64* bits, int u, int v) {
-  for (int w = u >> 6; w <= (v >> 6); w++) {
-    u64 m = ~0ull;
-    if (w == (v >> 6) && (v & 63) != 63) m &= (2ull << (v & 63)) - 1ull;
-    if (w == (u >> 6)) m &= ~((1ull << (u & 63)) - 1ull);
-    atomicOr(&bits[w], m);
-  }
-}
+typedef c19_u64 u64;
 
 // ---- the row's largest gradient and its sum of f ------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void cen2019_range_kernel(const C19Args a) {
@@ -258,13 +117,7 @@ __global__ __launch_bounds__(256) void cen2019_hsum_kernel(const C19Args a) {
   if (lane == 0) a.row_sum[(long long)b * a.rows + r] = sum;
 }
 
-// LDS of a wavefront of the fresh kernel: rowb | neg u64 [words + 1] | cand u64 [words] | tail u64 [64] | prevz, nextz int
-// [words + 1] each | bound int [64] | runtop u16 [cols].  A key is recomputed from the row's bytes wherever it is needed (a
-// run's own candidates, three per run, the fresh ones): a table of them would halve the wavefronts a compute unit holds.
-__host__ __device__ inline int c19_fresh_lds(int cols, int words, int rowb_bytes) {
-  return rowb_bytes + (2 * words + 1 + 64) * 8 + (2 * (words + 1) + 64) * 4 + ((cols * 2 + 15) & ~15);
-}
-
+// LDS of a wavefront: c19_fresh_lds (cen2019_dev.hpp)
 __global__ __launch_bounds__(256) void cen2019_fresh_kernel(const C19Args a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -284,10 +137,11 @@ __global__ __launch_bounds__(256) void cen2019_fresh_kernel(const C19Args a) {
   c19_stage_row(a.polar + (long long)b * a.batch_stride + (long long)r * a.stride, cols, rowb, lane);
   c19_wave_sync();
   const float mean = a.img[b * 4], inv = a.img[b * 4 + 1], mean_h = a.img[b * 4 + 2];
+  const uint32_t tie = c19_tie(a.tie_rev);
   const auto key_of = [&](int j) {
     float s, h;
     c19_sh(rowb, j, cols, mean, inv, s, h);
-    return c19_key(c19_ord(h), flat0 + j);
+    return c19_key(c19_ord(h), flat0 + j, tie);
   };
 
   // ---- the s < 0 and candidate bitmaps (Utils.cpp:517-523) -------------------------------------------------------------
@@ -309,69 +163,8 @@ __global__ __launch_bounds__(256) void cen2019_fresh_kernel(const C19Args a) {
   c19_wave_sync();
   c19_zero_tables(neg, words, prevz, nextz, lane);
 
-  // ---- the best own candidate of every run: a lane per stretch of C bins (C odd: no LDS bank conflicts) ---------------------------
-  {
-    const int C = ((cols + 63) / 64) | 1;
-    const int j_beg = lane * C, j_end = min(cols, j_beg + C);
-    u64 cur = 0ull, first_best = 0ull;
-    int first_end = -1;
-    bool from_start = true, closed = j_beg >= cols;
-    for (int j = j_beg; j < j_end; j++) {
-      if (c19_bit(neg, j)) {
-        if (c19_bit(cand, j)) {
-          const u64 k = key_of(j);
-          cur = k > cur ? k : cur;
-        }
-        if (j == cols - 1 || !c19_bit(neg, j + 1)) {           // the run ends here
-          if (from_start) { first_end = j; first_best = cur; }
-          else runtop[j] = cur ? (unsigned short)(c19_key_flat(cur) - flat0) : (unsigned short)kC19None;
-          cur = 0ull;
-          closed = true;
-          from_start = false;
-        }
-      } else {
-        cur = 0ull;
-        closed = true;
-        from_start = false;
-      }
-    }
-    tail[lane] = cur;
-    bound[lane] = closed;
-    c19_wave_sync();
-    if (first_end >= 0) {                                      // the run may have begun in the stretches before
-      u64 best = first_best;
-      for (int p = lane - 1; p >= 0; p--) {
-        const u64 t = tail[p];
-        best = t > best ? t : best;
-        if (bound[p]) break;
-      }
-      runtop[first_end] = best ? (unsigned short)(c19_key_flat(best) - flat0) : (unsigned short)kC19None;
-    }
-  }
-  c19_wave_sync();
-
   // ---- the best candidate TOUCHING every run: its own, the one right of it, the one left of it if that sits below T --------------
-  for (int w = lane; w < words; w += 64) {
-    const u64 word = neg[w];
-    u64 ends = word & ~((word >> 1) | ((neg[w + 1] & 1ull) << 63));
-    while (ends) {
-      const int v = w * 64 + __ffsll((long long)ends) - 1;
-      ends &= ends - 1;
-      const int u = c19_run_start(neg, prevz, v);
-      unsigned top = runtop[v];
-      u64 ktop = top != kC19None ? key_of((int)top) : 0ull;
-      if (v + 1 < cols && c19_bit(cand, v + 1)) {
-        const u64 k = key_of(v + 1);
-        if (k > ktop) { ktop = k; top = v + 1; }
-      }
-      if (u >= 1 && u - 1 < T && c19_bit(cand, u - 1)) {
-        const u64 k = key_of(u - 1);
-        if (k > ktop) { ktop = k; top = u - 1; }
-      }
-      runtop[v] = (unsigned short)top;
-    }
-  }
-  c19_wave_sync();
+  c19_run_tops(neg, cand, prevz, tail, bound, runtop, cols, words, T, flat0, tie, lane, key_of);
 
   // ---- fresh candidates: the best key in each run they touch; their keys, compacted --------------------------------------------
   u64* seg = a.keys + row * cols;
@@ -402,14 +195,6 @@ __global__ __launch_bounds__(256) void cen2019_fresh_kernel(const C19Args a) {
 // are fresh (every candidate is processed), all ones for max_points == 0 (none is).  Radix select over the 54 key bits, 11 a
 // pass: cen2019_hist_kernel counts the keys that match the digits chosen so far by their next digit (several workgroups a
 // sweep, LDS histograms flushed with atomics: a count does not depend on the order), cen2019_pick_kernel chooses the digit.
-constexpr int kC19Digit = 11, kC19Bins = 1 << kC19Digit, kC19Passes = 5;
-
-struct C19Select {
-  u64 prefix;                        // the digits chosen so far
-  int rank;                          // the key wanted is the rank-th largest of those that match prefix
-  int active;                        // 0: the cutoff is not binding (or max_points == 0), a.cut is final
-};
-
 __global__ __launch_bounds__(256) void cen2019_select_init_kernel(const C19Args a, C19Select* sel, int* ghist) {
   __shared__ int sh_tot[4];
   const int b = blockIdx.x, t = threadIdx.x;
@@ -505,6 +290,7 @@ __global__ __launch_bounds__(256) void cen2019_mark_kernel(const C19Args a) {
   c19_wave_sync();
   const float mean = a.img[b * 4], inv = a.img[b * 4 + 1], mean_h = a.img[b * 4 + 2];
   const u64 K = a.cut[b];
+  const uint32_t tie = c19_tie(a.tie_rev);
 
   // ---- the processed candidates (key >= K); R starts as those with s >= 0: their own bins ----------------------------------------
   int n_proc = 0;
@@ -518,7 +304,7 @@ __global__ __launch_bounds__(256) void cen2019_mark_kernel(const C19Args a) {
       ng = s < 0.f;
       hp = h > 0.f;
       if (h > mean_h) {
-        const u64 k = c19_key(c19_ord(h), flat0 + j);
+        const u64 k = c19_key(c19_ord(h), flat0 + j, tie);
         pr = k >= K;
         if (pr) kmin = k < kmin ? k : kmin;
       }
@@ -567,11 +353,11 @@ __global__ __launch_bounds__(256) void cen2019_mark_kernel(const C19Args a) {
       if (c19_bit(proc, j)) {
         float s, h;
         c19_sh(rowb, j, cols, mean, inv, s, h);
-        const u64 k = c19_key(c19_ord(h), flat0 + j);
+        const u64 k = c19_key(c19_ord(h), flat0 + j, tie);
         best = k > best ? k : best;
       }
     best = c19_wave_max_u64(best);
-    const int bin = (int)(c19_key_flat(best) - flat0);
+    const int bin = (int)(c19_key_flat(best, tie) - flat0);
     // the best at r < T marks the whole run, and every later one finds its bin marked; the best at r >= T marks [u, r], the
     // others at r' >= T extend that to r', and those at r < T find their bin marked and are skipped
     if (lane == 0) c19_set_range(marks, u, bin < T ? v : c19_highest(proc, u, v));
@@ -749,10 +535,71 @@ __global__ __launch_bounds__(256) void cen2019_cloud_kernel(const C19Args a) {
   }
 }
 
-// wavefronts (rows) per workgroup of a row kernel whose wavefront needs per_wave bytes of LDS: up to 4, within 64 KB
-int c19_waves(int per_wave) { return std::max(1, std::min(4, (64 * 1024) / per_wave)); }
+// a row kernel over the chunk: a wavefront per row, the sweep on gridDim.y
+void c19_rows_launch(cfear_ctx* ctx, const C19Args& c, void (*fn)(const C19Args), int per_wave, const char* name) {
+  ProfScope ps(ctx, name);
+  C19Args k = c;
+  k.per_wave = per_wave;
+  const int waves = c19_waves(per_wave);
+  hipLaunchKernelGGL(fn, dim3((c.rows + waves - 1) / waves, c.batch), dim3(64 * waves), (size_t)per_wave * waves, ctx->stream, k);
+}
 
 }  // namespace
+
+int c19_check_input(cfear_ctx* ctx, const uint8_t* polar, const cfear_polar_desc* desc, const cfear_cen2019_params* par) {
+  if (!polar || !desc || !par) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "cen2019: null argument");
+  if (desc->rows <= 0 || desc->cols <= 0 || desc->stride < desc->cols || desc->batch <= 0 ||
+      (desc->batch > 1 && desc->batch_stride < (int64_t)desc->rows * desc->stride))
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "cen2019: bad polar descriptor");
+  if (desc->cols < 2 || desc->cols > kC19MaxCols)
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "cen2019: cols must be in [2, %d]", kC19MaxCols);
+  if ((long long)desc->rows * desc->cols > kC19MaxPixels)
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "cen2019: rows * cols > 2^22 unsupported (the fp64 sum of the sweep must be exact)");
+  if (desc->rows > kC19MaxRows) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "cen2019: rows > %d unsupported", kC19MaxRows);
+  if (par->max_points < 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "cen2019: max_points < 0");
+  if (par->min_range_bins < 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "cen2019: min_range_bins < 0");
+  if (!std::isfinite(par->range_res)) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "cen2019: range_res must be finite");
+  return CFEAR_OK;
+}
+
+int c19_launch_stats(cfear_ctx* ctx, const C19Args& c) {
+  c19_rows_launch(ctx, c, cen2019_range_kernel, c.rowb_bytes, "cen2019_range");
+  {
+    ProfScope ps(ctx, "cen2019_image");
+    hipLaunchKernelGGL(cen2019_image_kernel, dim3(c.batch), dim3(256), 0, ctx->stream, c, 0);
+  }
+  c19_rows_launch(ctx, c, cen2019_hsum_kernel, c.rowb_bytes, "cen2019_hsum");
+  {
+    ProfScope ps(ctx, "cen2019_image");
+    hipLaunchKernelGGL(cen2019_image_kernel, dim3(c.batch), dim3(256), 0, ctx->stream, c, 1);
+  }
+  CFEAR_HIP_CHECK(ctx, hipGetLastError());
+  return CFEAR_OK;
+}
+
+void c19_launch_select(cfear_ctx* ctx, const C19Args& c, C19Select* d_sel, int* d_hist) {
+  ProfScope ps(ctx, "cen2019_select");
+  const int slices = std::max(1, std::min((c.rows + 3) / 4, 2048 / c.batch));
+  hipLaunchKernelGGL(cen2019_select_init_kernel, dim3(c.batch), dim3(256), 0, ctx->stream, c, d_sel, d_hist);
+  for (int pass = kC19Passes - 1; pass >= 0; pass--) {
+    hipLaunchKernelGGL(cen2019_hist_kernel, dim3(c.batch, slices), dim3(256), 0, ctx->stream, c, d_sel, d_hist, pass * kC19Digit);
+    hipLaunchKernelGGL(cen2019_pick_kernel, dim3(c.batch), dim3(256), 0, ctx->stream, c, d_sel, d_hist, pass * kC19Digit);
+  }
+}
+
+int c19_launch_detect(cfear_ctx* ctx, const C19Args& c, C19Select* d_sel, int* d_hist) {
+  const int lds_fresh = (c19_fresh_lds(c.cols, c.words, c.rowb_bytes) + 15) & ~15;
+  const int lds_mark = (c19_mark_lds(c.words, c.rowb_bytes) + 15) & ~15;
+  const int lds_emit = (c.words + 1) * 4 * 8;
+  CFEAR_CHECK(cfear_allow_lds(ctx, (const void*)cen2019_fresh_kernel, (size_t)lds_fresh * c19_waves(lds_fresh)));
+  c19_rows_launch(ctx, c, cen2019_fresh_kernel, lds_fresh, "cen2019_fresh");
+  CFEAR_HIP_CHECK(ctx, hipGetLastError());                   // the kernels below trust what the fresh kernel leaves in the scratch
+  c19_launch_select(ctx, c, d_sel, d_hist);
+  c19_rows_launch(ctx, c, cen2019_mark_kernel, lds_mark, "cen2019_mark");
+  c19_rows_launch(ctx, c, cen2019_emit_kernel, lds_emit, "cen2019_emit");
+  CFEAR_HIP_CHECK(ctx, hipGetLastError());
+  return CFEAR_OK;
+}
 
 extern "C" void cfear_cen2019_params_default(cfear_cen2019_params* par) {
   if (!par) return;
@@ -766,17 +613,7 @@ extern "C" int cfear_filter_cen2019(cfear_ctx* ctx, const uint8_t* polar, const 
                                     int32_t* targets, uint8_t* region_mask, float* image_stats, int32_t* counts) {
   if (!polar || !desc || !par || !xyzi || !n_points || cap_points <= 0)
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "cen2019: null argument");
-  if (desc->rows <= 0 || desc->cols <= 0 || desc->stride < desc->cols || desc->batch <= 0 ||
-      (desc->batch > 1 && desc->batch_stride < (int64_t)desc->rows * desc->stride))
-    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "cen2019: bad polar descriptor");
-  if (desc->cols < 2 || desc->cols > kC19MaxCols)
-    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "cen2019: cols must be in [2, %d]", kC19MaxCols);
-  if ((long long)desc->rows * desc->cols > kC19MaxPixels)
-    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "cen2019: rows * cols > 2^22 unsupported (the fp64 sum of the sweep must be exact)");
-  if (desc->rows > kC19MaxRows) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "cen2019: rows > %d unsupported", kC19MaxRows);
-  if (par->max_points < 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "cen2019: max_points < 0");
-  if (par->min_range_bins < 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "cen2019: min_range_bins < 0");
-  if (!std::isfinite(par->range_res)) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "cen2019: range_res must be finite");
+  CFEAR_CHECK(c19_check_input(ctx, polar, desc, par));
   if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const int rows = desc->rows, cols = desc->cols, batch = desc->batch;
@@ -819,12 +656,7 @@ extern "C" int cfear_filter_cen2019(cfear_ctx* ctx, const uint8_t* polar, const 
   a.max_points = par->max_points; a.min_range_bins = par->min_range_bins;
   a.words = words; a.rowb_bytes = (cols + 15) & ~15;
   a.cos_t = d_cos; a.sin_t = d_sin; a.range_res = par->range_res; a.cap_points = cap_points;
-  const int lds_rowb = a.rowb_bytes;
-  const int lds_fresh = (c19_fresh_lds(cols, words, a.rowb_bytes) + 15) & ~15;
-  const int lds_mark = (c19_mark_lds(words, a.rowb_bytes) + 15) & ~15;
-  const int lds_emit = (words + 1) * 4 * 8;
   const size_t cloud_lds = (size_t)(rows + 1) * 4 + kC19CloudLists;
-  CFEAR_CHECK(cfear_allow_lds(ctx, (const void*)cen2019_fresh_kernel, (size_t)lds_fresh * c19_waves(lds_fresh)));
   CFEAR_CHECK(cfear_allow_lds(ctx, (const void*)cen2019_cloud_kernel, cloud_lds));
 
   const C19Args base = a;
@@ -838,37 +670,8 @@ extern "C" int cfear_filter_cen2019(cfear_ctx* ctx, const uint8_t* polar, const 
     if (base.region_mask) c.region_mask = base.region_mask + (size_t)b0 * pixels;
     if (base.image_stats) c.image_stats = base.image_stats + (size_t)b0 * 4;
     if (base.counts) c.counts = base.counts + (size_t)b0 * 3;
-    auto rows_launch = [&](void (*fn)(const C19Args), int per_wave, const char* name) {
-      ProfScope ps(ctx, name);
-      C19Args k = c;
-      k.per_wave = per_wave;
-      const int waves = c19_waves(per_wave);
-      hipLaunchKernelGGL(fn, dim3((rows + waves - 1) / waves, c.batch), dim3(64 * waves), (size_t)per_wave * waves, ctx->stream, k);
-    };
-    rows_launch(cen2019_range_kernel, lds_rowb, "cen2019_range");
-    {
-      ProfScope ps(ctx, "cen2019_image");
-      hipLaunchKernelGGL(cen2019_image_kernel, dim3(c.batch), dim3(256), 0, ctx->stream, c, 0);
-    }
-    rows_launch(cen2019_hsum_kernel, lds_rowb, "cen2019_hsum");
-    {
-      ProfScope ps(ctx, "cen2019_image");
-      hipLaunchKernelGGL(cen2019_image_kernel, dim3(c.batch), dim3(256), 0, ctx->stream, c, 1);
-    }
-    rows_launch(cen2019_fresh_kernel, lds_fresh, "cen2019_fresh");
-    CFEAR_HIP_CHECK(ctx, hipGetLastError());                 // the kernels below trust what the fresh kernel leaves in the scratch
-    {
-      ProfScope ps(ctx, "cen2019_select");
-      const int slices = std::max(1, std::min((rows + 3) / 4, 2048 / c.batch));
-      hipLaunchKernelGGL(cen2019_select_init_kernel, dim3(c.batch), dim3(256), 0, ctx->stream, c, d_sel, d_hist);
-      for (int pass = kC19Passes - 1; pass >= 0; pass--) {
-        hipLaunchKernelGGL(cen2019_hist_kernel, dim3(c.batch, slices), dim3(256), 0, ctx->stream, c, d_sel, d_hist, pass * kC19Digit);
-        hipLaunchKernelGGL(cen2019_pick_kernel, dim3(c.batch), dim3(256), 0, ctx->stream, c, d_sel, d_hist, pass * kC19Digit);
-      }
-    }
-    rows_launch(cen2019_mark_kernel, lds_mark, "cen2019_mark");
-    rows_launch(cen2019_emit_kernel, lds_emit, "cen2019_emit");
-    CFEAR_HIP_CHECK(ctx, hipGetLastError());
+    CFEAR_CHECK(c19_launch_stats(ctx, c));
+    CFEAR_CHECK(c19_launch_detect(ctx, c, d_sel, d_hist));
     {
       ProfScope ps(ctx, "cen2019_cloud");
       hipLaunchKernelGGL(cen2019_cloud_kernel, dim3(c.batch, kC19CloudSplit), dim3(256), cloud_lds, ctx->stream, c);
