@@ -92,9 +92,13 @@ int cfear_ctx_get_stream(const cfear_ctx* ctx, void** hip_stream);
  *                            so that small batches cross chunk boundaries; INT32_MAX lifts the cap again.  A context that
  *                            never set it reads 0 and sizes its chunks by the budget alone; 0 itself is not a cap and,
  *                            unlike the options above, is refused.
+ *   CFEAR_OPT_REPLAY_CHUNK   0 (default): cfear_odometry_replay_clouds sizes its frame chunks by the free device memory;
+ *                            n >= 1: at most n frames per chunk, so that a short trace crosses chunk boundaries inside
+ *                            a keyframe window.  (Numbered apart from the enum: the enum's count is part of the pinned ABI.)
  * Returns CFEAR_ERR_INVALID_ARGUMENT for an unknown option or a value outside its range.                          */
 enum cfear_option { CFEAR_OPT_FUSED_DECODE = 0, CFEAR_OPT_MATCHER_LDS_KB = 1, CFEAR_OPT_MATCHER_WAVES = 2,
                     CFEAR_OPT_HOST_TIMELINE = 3, CFEAR_OPT_SC_QUERY_CHUNK = 4, CFEAR_OPT_PGO_GRAPH_CHUNK = 5, CFEAR_OPT_COUNT = 6 };
+#define CFEAR_OPT_REPLAY_CHUNK 100
 int cfear_ctx_set_option(cfear_ctx* ctx, int32_t option, int64_t value);
 int cfear_ctx_get_option(const cfear_ctx* ctx, int32_t option, int64_t* value);
 /* Per-kernel-family device time measured with hipEvents on the context's stream.
@@ -497,6 +501,31 @@ int cfear_scan_surface_path(const cfear_scan* scan, uint32_t* path);
 #define CFEAR_SURF_PATH_SLAB_COUNT_SHIFT 16  /* fast: slabs, saturating at 255                                         */
 #define CFEAR_SURF_PATH_SLAB_COUNT_MASK 0xFF0000u
 int cfear_scan_destroy(cfear_scan* scan);
+
+/* N clouds -> N scans in one call: the batched counterpart of cfear_scan_create, for callers without a live fuser (loop
+ * closure on fresh sweeps, scan evaluation, training data from stored clouds).  Cloud i is the lengths[i] points behind
+ * xyzi + 4 * offsets[i]; offsets and lengths are host arrays counted in points, xyzi is host or device memory and is NOT
+ * modified (a cloud that gets compensated is compensated in a copy).  par is shared by the batch; with par->compensate set
+ * cloud i is compensated by mots[3 i .. 3 i + 2], or by par->mot when mots is NULL (then par->mot serves every cloud).
+ * One arena holds all N scans, max_cells cells each (1 .. 16 384), and one launch sequence of the surface-point kernels
+ * serves them (a few sequences where their scratch memory bounds a launch: 1 GiB).
+ * A cloud that fails does not stop the others: status[i] (host, [n_scans]) is CFEAR_ERR_EMPTY_CLOUD for lengths[i] == 0,
+ * CFEAR_ERR_CAPACITY for a scan of more than max_cells cells (or a cloud beyond 2^20 points), CFEAR_OK otherwise; the call
+ * returns the first status that is not CFEAR_OK, *out is valid whenever status was written (any return but
+ * CFEAR_ERR_INVALID_ARGUMENT / CFEAR_ERR_HIP) and must be destroyed.
+ * cfear_scan_batch_get hands out BORROWED handles, NULL for a scan that failed: views into the arena, valid until
+ * cfear_scan_batch_destroy wherever a const cfear_scan* is taken -- cfear_register_batch, cfear_scan_table_create,
+ * cfear_scan_get_cells, cfear_scan_closest_idx / _ties, cfear_scan_surface_path, the audits.  cfear_scan_destroy on a
+ * borrowed handle is refused with CFEAR_ERR_INVALID_ARGUMENT and frees nothing.  A scan table holds its own reference: the
+ * arena stays allocated until the last table that names one of its scans is destroyed as well.  A served scan's cells and
+ * route word are the bits cfear_scan_create gives on the same cloud.                                                    */
+typedef struct cfear_scan_batch cfear_scan_batch;
+int cfear_scan_create_batch(cfear_ctx* ctx, const float* xyzi, const int64_t* offsets, const int32_t* lengths, int32_t n_scans,
+                            const cfear_feature_params* par, const double* mots, int32_t max_cells, cfear_scan_batch** out,
+                            int32_t* status);
+int cfear_scan_batch_size(const cfear_scan_batch* batch);
+int cfear_scan_batch_get(const cfear_scan_batch* batch, int32_t i, const cfear_scan** scan);
+int cfear_scan_batch_destroy(cfear_scan_batch* batch);
 
 /* ---- M: registration -----------------------------------------------------------------------
  * n_scan_normal_reg (n_scan_normal.h:27-85, n_scan_normal.cpp) in mode
@@ -1282,6 +1311,62 @@ int cfear_odometry_process_clouds(cfear_odometry* od, const cfear_sc_cloud* clou
  * estimate_cov_by_sampling is set and the fit succeeded (odometrykeyframefuser.cpp:196, 203-208).
  * sampled (optional, [n_streams]) receives 1 where the sampled covariance was used.                */
 int cfear_odometry_get_covariance(cfear_odometry* od, double* cov, int32_t* sampled);
+
+/* ---- replay of a recorded trajectory ------------------------------------------------------------------------------
+ * Registers frame t from the RECORDED pose of frame t - 1 and the RECORDED keyframe set, for every frame of one or more
+ * sequences, as a few batched launches: no frame's input depends on another frame's result, so one legal divergence
+ * between two builds cannot poison the frames behind it, and "how good is each registration" is
+ * separated from "how does drift accumulate".  The trace may be another build's, ground truth or this library's own.
+ * A frame's state is what cfear_odometry_process would hold had the trace been its own output, derived with the same
+ * functions.  Per sequence, with trace poses P_0 .. P_n-1 (seq_offsets [n_seq + 1] delimits the sequences' frames):
+ *   frame 0    the first keyframe, at P_0; no job: reg_status 1, is_keyframe 1, pose = guess = P_0.
+ *   motion     M_1 = identity, M_t = P_t-2^-1 P_t-1; frame t's cloud is compensated by M_t (par->compensate,
+ *              par->radar_ccw), its guess is P_t-1 M_t (par->use_guess; P_t-1 otherwise).
+ *   keyframes  frame t >= 1 is one iff cfear_keyframe_based_fuse(xyt(P_lastkf^-1 P_t), ...): by the TRACE pose.
+ *   window     the last min(submap_scan_size, count) keyframes among the frames before t, in order, at their trace poses.
+ *   job        scans [window.., scan_t], poses [window trace poses.., guess_t], par->reg: what FormatScans builds.
+ *   sanity     cfear_acc_vel_sanity_check on M_t and P_t-1^-1 pose.
+ * A frame whose scan failed (empty cloud, capacity) reports that status in reg_status and runs no job; so does a frame
+ * whose window holds such a scan; the other frames are unaffected and the call returns the first such status.
+ * estimate_cov_by_sampling and keep_nodes are NOT part of a replay and are ignored; submap_scan_size <= 15.
+ * The scans are made by the surface-point kernels and registered by the matcher through their launchers, unchanged; job
+ * and result records are written and read on the device, one read-back of `out` ends each chunk of frames.
+ * The matcher's forms agree to 1e-11 where a batch size changes the form (see cfear_reg_job): a replay of this library's
+ * own trace meets the live poses to that, not necessarily to the bit -- the trace also keeps (x, y, theta) where the live
+ * state keeps the matrix.
+ * Refused with CFEAR_ERR_INVALID_ARGUMENT before anything is launched, the message naming the sequence or frame: a null
+ * argument, n_seq < 1, seq_offsets that do not start at 0 or hold an empty sequence (not ascending), a trace pose that is
+ * not finite, a cloud with n < 0 or without points, unknown flags, a desc.batch other than the number of frames.
+ * cfear_odometry_replay is the same for raw sweeps: desc (batch = all frames, one behind the other at batch_stride) and polar
+ * as cfear_odometry_process takes them, host or device; par->filter_type selects the filter, par->rotate_ccw the decode of
+ * [range bins][azimuths] sources.  The filter runs through its own entry points, the clouds stay on the device.
+ * CFEAR_REPLAY_AUDIT folds the two audits into every record, through their own entry points on the same scans, poses and
+ * clouds: cfear_association_ties_batch twice -- at the guess with itr = 1 (n_tied_start, n_tied_effective_start) and at the
+ * registered pose with itr = 2 (_end) --, cfear_voxel_order_audit_batch on every frame's compensated cloud, n_voxels_exposed
+ * and n_voxels_changed_reversed summed over the job's scans (the frame's own scan where it has no job); exposed = 1 iff an
+ * *_effective_* count or n_voxels_exposed is > 0.  Without the flag these fields are -1 and every other field is the same bits.
+ * The caveats of DESIGN.md section 3 carry over: a tie is a snapshot at two poses -- one that exists only at an association
+ * pass in between is invisible to it --, a tie between bitwise equal cells is not counted as effective, and nothing here
+ * says which way FLANN decides a tie or which order libstdc++ leaves a voxel's points in: exposed = 0 says a reference build
+ * has no such licence to differ on this frame, exposed = 1 only that it has one.                                       */
+#define CFEAR_REPLAY_AUDIT 1
+typedef struct cfear_replay_frame {
+  double pose[3];                       /* Register's result for this frame (raw, before the sanity check)                */
+  double guess[3];                      /* the start pose the job was given                                               */
+  double dev[3];                        /* (x, y, theta) of T_trace(t)^-1 T_final(t); T_final = pose, or guess where sanity_ok = 0 */
+  double score, final_cost, last_relative_decrease;
+  int32_t n_points, n_cells, is_keyframe, n_targets;
+  int32_t reg_status, outer_iters, lm_iters, num_residuals;
+  int32_t sanity_ok;
+  int32_t n_tied_start, n_tied_effective_start, n_tied_end, n_tied_effective_end;   /* CFEAR_REPLAY_AUDIT, else -1         */
+  int32_t n_voxels_exposed, n_voxels_changed_reversed;                              /* summed over the job's scans; else -1 */
+  int32_t exposed;                                                                  /* 1 / 0 with the audit, else -1       */
+} cfear_replay_frame;                   /* 160 bytes, no implicit padding */
+int cfear_odometry_replay(cfear_ctx* ctx, const cfear_polar_desc* desc, const uint8_t* polar, const cfear_odometry_params* par,
+                          const double* trace_xyt, const int32_t* seq_offsets, int32_t n_seq, int32_t flags, cfear_replay_frame* out);
+int cfear_odometry_replay_clouds(cfear_ctx* ctx, const cfear_sc_cloud* clouds, const cfear_odometry_params* par,
+                                 const double* trace_xyt, const int32_t* seq_offsets, int32_t n_seq, int32_t flags,
+                                 cfear_replay_frame* out);
 /* The RadarScan of a stream's LAST processed frame (scan_, odometrykeyframefuser.cpp:172, 244) -- call after a frame
  * whose keyframe_added is set to collect a pose-graph node; valid until the next cfear_odometry_process:
  *   get_scan   a copy of cloud_normal_ (MapPointNormal) as a new handle (cfear_scan_destroy it)

@@ -375,7 +375,7 @@ class MapPointNormal {
     return boost::shared_ptr<MapPointNormal>(new MapPointNormal(ctx_, TransformCells(Affine3dToPose2d(T))));
   }
 #endif
-  ~MapPointNormal() { cfear_scan_destroy(scan_); }
+  ~MapPointNormal() { if (!borrowed_) cfear_scan_destroy(scan_); }
   MapPointNormal(const MapPointNormal&) = delete;
   MapPointNormal& operator=(const MapPointNormal&) = delete;
   size_t GetSize() const { return (size_t)cfear_scan_size(scan_); }
@@ -411,10 +411,13 @@ class MapPointNormal {
   uint32_t SurfacePath() const { uint32_t p = 0; ctx_.check(cfear_scan_surface_path(scan_, &p)); return p; }
   const cfear_scan* device() const { return scan_; }
  private:
+  friend class ScanBatch;
+  MapPointNormal(Context& ctx, const cfear_scan* borrowed) : ctx_(ctx), scan_(const_cast<cfear_scan*>(borrowed)), borrowed_(true) {}
   const std::vector<cfear_cell>& cached() { if (cache_.empty()) cache_ = GetCells(); return cache_; }
   std::vector<cfear_cell> cache_;
   Context& ctx_;
   cfear_scan* scan_ = nullptr;
+  bool borrowed_ = false;                 // a view into a ScanBatch's arena: the batch owns the cells
 #ifdef CFEAR_HIP_HAVE_EIGEN_PCL
   pcl::PointCloud<pcl::PointXYZI>::Ptr input_;
 #endif
@@ -423,8 +426,58 @@ class MapPointNormal {
 typedef boost::shared_ptr<MapPointNormal> MapNormalPtr;                                       // pointnormal.h:108
 #endif
 
+// N clouds -> N scans in one call and one arena (cfear_scan_create_batch): what a caller without a live fuser uses to turn
+// stored clouds into scans -- loop closure on fresh sweeps, scan evaluation, training data.  at(i) is a MapPointNormal that
+// borrows scan i (nullptr where the scan failed: status(i) says why) and is valid while the batch lives.  motions: empty, or
+// one (x, y, theta) per cloud to compensate it by (in a copy; the clouds stay as they are).
+class ScanBatch {
+ public:
+  ScanBatch(Context& ctx, const std::vector<PointCloud>& clouds, float radius, int32_t max_cells, double ox = 0, double oy = 0,
+            bool weight_intensity = false, const std::vector<Pose2d>& motions = std::vector<Pose2d>(), bool ccw = false)
+      : ctx_(ctx), status_(clouds.size(), 0) {
+    std::vector<float> xyzi;
+    std::vector<int64_t> offsets(clouds.size());
+    std::vector<int32_t> lengths(clouds.size());
+    for (size_t i = 0; i < clouds.size(); i++) {
+      offsets[i] = (int64_t)(xyzi.size() / 4);
+      lengths[i] = (int32_t)clouds[i].size();
+      if (!clouds[i].empty()) xyzi.insert(xyzi.end(), &clouds[i][0].x, &clouds[i][0].x + 4 * clouds[i].size());
+    }
+    cfear_feature_params fp{};
+    fp.radius = radius; fp.downsample_factor = MapPointNormal::downsample_factor(); fp.origin[0] = ox; fp.origin[1] = oy;
+    fp.weight_intensity = weight_intensity ? 1 : 0;
+    fp.compensate = motions.empty() ? 0 : 1;
+    fp.ccw = ccw ? 1 : 0;
+    if (!motions.empty() && motions.size() != clouds.size()) throw std::invalid_argument("ScanBatch: one motion per cloud");
+    const int rc = cfear_scan_create_batch(ctx_.get(), xyzi.empty() ? nullptr : xyzi.data(), offsets.data(), lengths.data(),
+                                           (int32_t)clouds.size(), &fp, motions.empty() ? nullptr : &motions[0].x, max_cells, &h_,
+                                           status_.data());
+    if (!h_) ctx_.check(rc);                              // a cloud that failed is a status, not an exception
+    scans_.resize(clouds.size());
+    for (size_t i = 0; i < clouds.size(); i++) {
+      const cfear_scan* s = nullptr;
+      ctx_.check(cfear_scan_batch_get(h_, (int32_t)i, &s));
+      if (s) scans_[i].reset(new MapPointNormal(ctx_, s));
+    }
+  }
+  ~ScanBatch() { scans_.clear(); if (h_) cfear_scan_batch_destroy(h_); }
+  ScanBatch(const ScanBatch&) = delete;
+  ScanBatch& operator=(const ScanBatch&) = delete;
+  size_t size() const { return scans_.size(); }
+  MapPointNormal* at(size_t i) const { return scans_[i].get(); }
+  int32_t status(size_t i) const { return status_[i]; }
+  const cfear_scan_batch* get() const { return h_; }
+
+ private:
+  Context& ctx_;
+  cfear_scan_batch* h_ = nullptr;
+  std::vector<int32_t> status_;
+  std::vector<std::unique_ptr<MapPointNormal>> scans_;
+};
+
 // The device views of a set of scans, uploaded once (cfear_scan_table): what the loop-closure thread keeps for the graph's
-// nodes so that a candidate is two indices and two poses.  Holds no reference on the scans.
+// nodes so that a candidate is two indices and two poses.  The library's table holds a reference of its own on
+// every scan (a scan destroyed first keeps its cells until the table goes); this wrapper does not keep the MapPointNormals alive.
 class ScanTable {
  public:
   ScanTable(Context& ctx, const std::vector<const MapPointNormal*>& scans) : ctx_(ctx), h_(nullptr) {
@@ -617,6 +670,30 @@ inline std::vector<cfear_voxel_audit_record> VoxelOrderAudit(Context& ctx, const
     for (size_t s = 0; s < n; s++) (*offsets)[s + 1] = (*offsets)[s] + records[s].n_voxels;
   }
   return records;
+}
+
+// A recorded trajectory replayed frame by frame (cfear_odometry_replay_clouds): clouds[f] = the
+// filtered cloud of frame f BEFORE compensation, trace[f] its recorded pose, seq_offsets the first frame of every sequence and,
+// as its last element, the number of frames (empty: one sequence).  One record per frame; a frame whose cloud is empty
+// carries the status in reg_status, as do the frames whose window holds it; only a refusal of the call throws.  audit folds the
+// tie and voxel-order audits into the records (CFEAR_REPLAY_AUDIT, with the caveats of cfear_hip.h).  Raw sweeps go through
+// cfear_odometry_replay directly.
+inline std::vector<cfear_replay_frame> OdometryReplay(Context& ctx, const std::vector<PointCloud>& clouds, const std::vector<Pose2d>& trace,
+                                                      const cfear_odometry_params& par,
+                                                      const std::vector<int32_t>& seq_offsets = std::vector<int32_t>(), bool audit = false) {
+  if (clouds.size() != trace.size() || clouds.empty()) throw CfearError(CFEAR_ERR_INVALID_ARGUMENT, "OdometryReplay: one cloud per trace pose");
+  std::vector<cfear_sc_cloud> c(clouds.size());
+  for (size_t f = 0; f < clouds.size(); f++) {
+    c[f].xyzi = clouds[f].empty() ? nullptr : &clouds[f][0].x;
+    c[f].n = (int32_t)clouds[f].size();
+    c[f].pad = 0;
+  }
+  std::vector<int32_t> seq = seq_offsets;
+  if (seq.empty()) seq = {0, (int32_t)clouds.size()};
+  std::vector<cfear_replay_frame> out(clouds.size());
+  const int rc = cfear_odometry_replay_clouds(ctx.get(), c.data(), &par, &trace[0].x, seq.data(), (int32_t)seq.size() - 1, audit ? CFEAR_REPLAY_AUDIT : 0, out.data());
+  if (rc != CFEAR_OK && rc != CFEAR_ERR_EMPTY_CLOUD && rc != CFEAR_ERR_CAPACITY) ctx.check(rc);
+  return out;
 }
 
 // radarDriver + OdometryKeyframeFuser for n independent sequences, one frame per call (cfear_odometry_*): the whole

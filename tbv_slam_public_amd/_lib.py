@@ -333,7 +333,18 @@ EXPORTS = [
     "cfear_association_ties_batch", "cfear_scan_closest_ties",
     "cfear_voxel_audit_params_default", "cfear_voxel_order_audit_batch",
     "cfear_cen2019_order_audit",
+    "cfear_scan_create_batch", "cfear_scan_batch_size", "cfear_scan_batch_get", "cfear_scan_batch_destroy",
+    "cfear_odometry_replay_clouds", "cfear_odometry_replay",
 ]
+REPLAY_AUDIT = 1                    # #define CFEAR_REPLAY_AUDIT
+
+# cfear_replay_frame: one record per frame of a replay (cfear_odometry_replay_clouds)
+REPLAY_FRAME_DTYPE = np.dtype([("pose", "<f8", 3), ("guess", "<f8", 3), ("dev", "<f8", 3), ("score", "<f8"), ("final_cost", "<f8"),
+                               ("last_relative_decrease", "<f8")] +
+                              [(n, "<i4") for n in ("n_points", "n_cells", "is_keyframe", "n_targets", "reg_status", "outer_iters", "lm_iters",
+                                                    "num_residuals", "sanity_ok", "n_tied_start", "n_tied_effective_start", "n_tied_end",
+                                                    "n_tied_effective_end", "n_voxels_exposed", "n_voxels_changed_reversed", "exposed")])
+assert REPLAY_FRAME_DTYPE.itemsize == 160
 
 PIPE_GRAPH, PIPE_TIMING = 1, 2      # enum { CFEAR_PIPE_GRAPH, CFEAR_PIPE_TIMING }
 
@@ -347,6 +358,7 @@ OPT_FUSED_DECODE, OPT_MATCHER_LDS_KB, OPT_MATCHER_WAVES, OPT_HOST_TIMELINE, OPT_
 # OPT_COUNT counts the options above, which all take 0 as "the library's choice"; it is NOT the header's CFEAR_OPT_COUNT (6).
 # CFEAR_OPT_PGO_GRAPH_CHUNK follows them with a different value range: n >= 1 graphs per chunk of cfear_pgo_solve_batch, 0 refused.
 OPT_PGO_GRAPH_CHUNK = 5
+OPT_REPLAY_CHUNK = 100              # #define CFEAR_OPT_REPLAY_CHUNK: frames per chunk of a replay, 0 = by free memory (numbered apart from the enum)
 
 
 class PgoParams(C.Structure):
@@ -593,6 +605,12 @@ def lib():
     L.cfear_voxel_audit_params_default.restype = None
     L.cfear_voxel_order_audit_batch.argtypes = [vp, vp, vp, vp, C.c_int32, C.POINTER(VoxelAuditParams), vp, vp, C.c_int64, C.POINTER(C.c_int64)]
     L.cfear_scan_surface_path.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.cfear_scan_create_batch.argtypes = [vp, vp, vp, vp, C.c_int32, C.POINTER(FeatureParams), vp, C.c_int32, C.POINTER(vp), vp]
+    L.cfear_scan_batch_size.argtypes = [vp]
+    L.cfear_scan_batch_get.argtypes = [vp, C.c_int32, C.POINTER(vp)]
+    L.cfear_scan_batch_destroy.argtypes = [vp]
+    L.cfear_odometry_replay_clouds.argtypes = [vp, C.POINTER(ScCloud), C.POINTER(OdometryParams), vp, vp, C.c_int32, C.c_int32, vp]
+    L.cfear_odometry_replay.argtypes = [vp, C.POINTER(PolarDesc), vp, C.POINTER(OdometryParams), vp, vp, C.c_int32, C.c_int32, vp]
     L.cfear_polar_rotate_ccw.argtypes = [vp, vp, C.POINTER(PolarDesc), vp, C.c_int32, C.c_int64]
     L.cfear_verify_params_default.argtypes = [C.POINTER(VerifyParams)]
     L.cfear_verify_params_default.restype = None

@@ -632,7 +632,9 @@ class MapPointNormal:
 
     def close(self):
         if getattr(self, "_h", None):
-            if getattr(self.ctx, "h", None):              # the context may already be gone at interpreter exit: its
+            if getattr(self, "_batch", None) is not None:  # borrowed from a ScanBatch: the batch owns the cells
+                self._batch = None
+            elif getattr(self.ctx, "h", None):            # the context may already be gone at interpreter exit: its
                 self.ctx._lib.cfear_scan_destroy(self._h)   # objects died with it, destroying them again would be a use after free
             self._h = None
 
@@ -641,6 +643,96 @@ class MapPointNormal:
             self.close()
         except Exception:
             pass
+
+
+class ScanBatch:
+    """cfear_scan_batch: N scans in one arena, made by one call (scan_create_batch).  batch[i] is a MapPointNormal that
+    BORROWS scan i -- usable wherever a MapPointNormal is (Register*, ScanTable, GetCells, GetClosestIdx, path, the audits)
+    and keeping the batch alive -- or None where the scan failed; batch.status is the int32 [n] array of per-scan statuses
+    (L.OK, L.ERR_EMPTY_CLOUD, L.ERR_CAPACITY)."""
+
+    def __init__(self, h, status, ctx):
+        self.ctx, self._h, self.status = ctx, h, status
+        self._scans = []
+        for i in range(int(ctx._lib.cfear_scan_batch_size(h))):
+            s = C.c_void_p()
+            ctx.check(ctx._lib.cfear_scan_batch_get(h, i, C.byref(s)))
+            m = None
+            if s.value:
+                m = MapPointNormal._from_handle(s, ctx)
+                m._batch = self
+            self._scans.append(m)
+
+    def __len__(self):
+        return len(self._scans)
+
+    def __getitem__(self, i):
+        return self._scans[i]
+
+    def __iter__(self):
+        return iter(self._scans)
+
+    def close(self):
+        """Destroys the batch; the MapPointNormals it handed out must not be used afterwards."""
+        if getattr(self, "_h", None):
+            for m in self._scans:
+                if m is not None:
+                    m._h, m._batch = None, None
+            if getattr(self.ctx, "h", None):
+                self.ctx._lib.cfear_scan_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def scan_create_batch(clouds, radius=3.0, origin=(0.0, 0.0), weight_intensity=False, compensate=None, ccw=False, max_cells=None,
+                      downsample_factor=None, ctx=None):
+    """cfear_scan_create_batch: one MapPointNormal per cloud in one call -> a ScanBatch.  clouds: a list of [n, 4] float32
+    arrays, all NumPy or all torch CUDA tensors (they are concatenated), or a tuple (xyzi [total, 4], offsets, lengths) that
+    is used in place.  compensate: None, or the [N, 3] motions the clouds are compensated by (in a copy: the clouds stay as
+    they are).  max_cells: the cells a scan may hold (default: the longest cloud's points, at most 16 384).  A cloud that is
+    empty or exceeds max_cells gives None in the batch and its status in batch.status; nothing is raised for it."""
+    ctx = ctx or default_context()
+    if isinstance(clouds, tuple):
+        xyzi, offsets, lengths = clouds
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        lengths = np.ascontiguousarray(lengths, dtype=np.int32)
+    else:
+        clouds = list(clouds)
+        lengths = np.array([int(c.shape[0]) for c in clouds], np.int32)
+        offsets = (np.cumsum(lengths, dtype=np.int64) - lengths).astype(np.int64)
+        if clouds and _is_torch(clouds[0]):
+            import torch
+            xyzi = torch.cat([c.reshape(-1, 4) for c in clouds]).float().contiguous()
+        else:
+            xyzi = np.ascontiguousarray(np.concatenate([np.asarray(c, np.float32).reshape(-1, 4) for c in clouds]) if clouds
+                                        else np.zeros((0, 4), np.float32))
+    n = int(lengths.shape[0])
+    if not _is_torch(xyzi):
+        xyzi = np.ascontiguousarray(xyzi, dtype=np.float32)
+    fp = L.FeatureParams()
+    fp.radius = float(radius)
+    fp.downsample_factor = float(MapPointNormal.downsample_factor if downsample_factor is None else downsample_factor)
+    fp.origin[0], fp.origin[1] = float(origin[0]), float(origin[1])
+    fp.weight_intensity = int(bool(weight_intensity))
+    fp.compensate = int(compensate is not None)
+    fp.ccw = int(bool(ccw))
+    mots = None if compensate is None else np.ascontiguousarray(compensate, dtype=np.float64).reshape(n, 3)
+    if max_cells is None:
+        max_cells = max(1, min(16384, int(lengths.max()) if n else 1))
+    status = np.zeros(n, np.int32)
+    h = C.c_void_p()
+    _torch_ready(ctx, xyzi)
+    rc = ctx._lib.cfear_scan_create_batch(ctx.h, _ptr(xyzi)[0] if xyzi.shape[0] else None, offsets.ctypes.data, lengths.ctypes.data, n,
+                                          C.byref(fp), None if mots is None else mots.ctypes.data, int(max_cells), C.byref(h),
+                                          status.ctypes.data)
+    if not h.value:
+        ctx.check(rc)
+    return ScanBatch(h, status, ctx)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2017,6 +2109,88 @@ def _cloud_ptr(cloud):
         return c.ctypes.data, c.shape[0], c
     assert cloud.dim() == 2 and cloud.shape[1] == 4 and cloud.is_contiguous()
     return cloud.data_ptr(), int(cloud.shape[0]), cloud
+
+
+# ------------------------------------------------------------------------------------------------
+# replay of a recorded trajectory
+# ------------------------------------------------------------------------------------------------
+def odometry_replay(clouds, trace, par=None, seq_offsets=None, audit=False, ctx=None):
+    """cfear_odometry_replay / cfear_odometry_replay_clouds: every frame registered from the RECORDED pose of the frame before
+    it and the recorded keyframe set, as a few batched launches -- no frame's input depends on another frame's result.
+    clouds: one float32 [n, 4] array (NumPy or torch CUDA) per frame, the filtered clouds BEFORE compensation, all sequences
+    one behind the other -- or ONE uint8 array [frames, rows, cols] of raw sweeps (NumPy or torch CUDA, laid out as
+    OdometryKeyframeFuser.process takes them), which go through the filter par selects first; trace: [frames, 3] (x, y,
+    theta), another build's, ground truth or OdometryKeyframeFuser's own; seq_offsets: [n_seq + 1] frame offsets of the
+    sequences (default: one sequence); audit: fold the tie and voxel-order audits into the records (CFEAR_REPLAY_AUDIT; the
+    caveats of include/cfear_hip.h apply), else those fields are -1.  -> a REPLAY_FRAME_DTYPE array [frames].  A frame whose
+    cloud is empty carries the status in reg_status, as do the frames whose window holds it; nothing is raised."""
+    ctx = ctx or default_context()
+    par = par or odometry_params()
+    trace = np.ascontiguousarray(trace, dtype=np.float64).reshape(-1, 3)
+    n = trace.shape[0]
+    flags = L.REPLAY_AUDIT if audit else 0
+    if (isinstance(clouds, np.ndarray) or _is_torch(clouds)) and clouds.ndim == 3:      # raw sweeps
+        img = clouds if _is_torch(clouds) else np.ascontiguousarray(clouds, dtype=np.uint8)
+        d, batch, rows, cols = _desc(img)
+        if _is_torch(img):
+            import torch
+            assert img.dtype == torch.uint8 and img.stride(-1) == 1
+            d.stride, d.batch_stride = img.stride(-2), img.stride(0)
+        seq = np.ascontiguousarray([0, n] if seq_offsets is None else seq_offsets, dtype=np.int32)
+        if seq.ndim != 1 or seq.shape[0] < 2:
+            raise ValueError("odometry_replay: seq_offsets holds the sequences' first frames and the number of frames")
+        _torch_ready(ctx, img)
+        out = np.zeros(n, L.REPLAY_FRAME_DTYPE)
+        rc = ctx._lib.cfear_odometry_replay(ctx.h, C.byref(d), _ptr(img)[0], C.byref(par), trace.ctypes.data, seq.ctypes.data,
+                                            seq.shape[0] - 1, flags, out.ctypes.data)
+        ctx.check(rc, allowed=(L.ERR_EMPTY_CLOUD, L.ERR_CAPACITY))
+        return out
+    clouds = list(clouds)
+    if len(clouds) != n:
+        raise ValueError("odometry_replay: %d clouds for %d trace poses" % (len(clouds), n))
+    seq = np.ascontiguousarray([0, n] if seq_offsets is None else seq_offsets, dtype=np.int32)
+    if seq.ndim != 1 or seq.shape[0] < 2 or seq[-1] != n:
+        raise ValueError("odometry_replay: seq_offsets must end at the number of frames")
+    arr = (L.ScCloud * max(n, 1))()
+    keep = []
+    for i, c in enumerate(clouds):
+        ptr, m, k = _cloud_ptr(c)
+        arr[i].xyzi, arr[i].n = (ptr if m else None), m
+        keep.append(k)
+    _torch_ready(ctx, *keep)
+    out = np.zeros(n, L.REPLAY_FRAME_DTYPE)
+    rc = ctx._lib.cfear_odometry_replay_clouds(ctx.h, arr, C.byref(par), trace.ctypes.data, seq.ctypes.data, seq.shape[0] - 1, flags,
+                                               out.ctypes.data)
+    ctx.check(rc, allowed=(L.ERR_EMPTY_CLOUD, L.ERR_CAPACITY))
+    return out
+
+
+def replay_summary(records, tol_xy, tol_theta, seq_offsets=None):
+    """What a replay says about two builds: a frame is EQUAL when |dev| <= (tol_xy, tol_xy, tol_theta), else it DIFFERS; a
+    differing frame is `exposed` when the audit flagged it (records["exposed"] > 0: a tie or a voxel order may legally
+    decide it) -- without the audit (exposed = -1) every differing frame counts as not exposed.  Frames without a job (the
+    first of a sequence, failed scans) are counted apart.  -> dict(n_frames, n_no_job, n_equal, n_differ_exposed,
+    n_differ_not_exposed, worst_dev_equal / _differ_exposed / _differ_not_exposed ([3] maxima of |dev|), first_not_exposed:
+    per sequence the first frame (index into records) that differs and is not exposed, -1 where none)."""
+    r = np.asarray(records)
+    n = r.shape[0]
+    seq = np.asarray([0, n] if seq_offsets is None else seq_offsets, dtype=np.int64)
+    d = np.abs(r["dev"])
+    job = r["n_targets"] > 0
+    equal = job & (d[:, 0] <= tol_xy) & (d[:, 1] <= tol_xy) & (d[:, 2] <= tol_theta)
+    differ = job & ~equal
+    exposed = differ & (r["exposed"] > 0)
+    hidden = differ & ~exposed
+
+    def worst(mask):
+        return d[mask].max(axis=0) if mask.any() else np.zeros(3)
+    first = []
+    for a, b in zip(seq[:-1], seq[1:]):
+        idx = np.flatnonzero(hidden[a:b])
+        first.append(int(a + idx[0]) if idx.size else -1)
+    return dict(n_frames=int(n), n_no_job=int((~job).sum()), n_equal=int(equal.sum()), n_differ_exposed=int(exposed.sum()),
+                n_differ_not_exposed=int(hidden.sum()), worst_dev_equal=worst(equal), worst_dev_differ_exposed=worst(exposed),
+                worst_dev_differ_not_exposed=worst(hidden), first_not_exposed=first)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -115,12 +115,16 @@ struct cfear_ctx {
   struct Slab { DevBuf<void> p; int cap; };
   std::vector<Slab> free_slabs;
   int64_t live_scans = 0;
-  int trig_rows = 0;       // rows the cos/sin tables in ws[kWsTrig] were built for
+  // the largest arena a destroyed cfear_scan_batch left behind, so that create / destroy / create does not hipMalloc
+  struct Arena { DevBuf<void> p; size_t bytes = 0; };
+  Arena free_arena;
+  int trig_rows = 0;      // rows the cos/sin tables in ws[kWsTrig] were built for
   // geometry the map in ws[kWsCartMap] was built for (cartesian.hip); cart_map_w = 0: none
   int cart_map_rows = 0, cart_map_w = 0;
   float cart_map_radar_res = 0.f, cart_map_cart_res = 0.f;
   int n_cu = 256;          // compute units of the device (cfear_ctx_create)
   int64_t opt[CFEAR_OPT_COUNT] = {1, 0, 0, 0};   // cfear_ctx_set_option (test / measurement hooks; include/cfear_hip.h)
+  int64_t replay_chunk = 0;      // CFEAR_OPT_REPLAY_CHUNK
   bool surf_list_dirty = true;   // the surface pipeline's hand-over counter may be non-zero (see cfear_surface_launch)
   std::vector<std::pair<const void*, int>> lds_allowed;   // kernels and the dynamic LDS they were already allowed on this device (cfear_allow_lds)
 };
@@ -318,8 +322,31 @@ struct cfear_scan {
   int32_t n_cells_host;    // -1 until read back
   uint32_t surf_path = 0;  // CFEAR_SURF_PATH_* of the surface-point launch that made the cells (0: none did)
   int32_t refs = 1;        // the caller's handle + one per scan table that names it (handles are used from one host thread)
+  cfear_scan_batch* batch = nullptr;   // a borrowed view into that batch's arena (cfear_scan_create_batch): `slab` is empty, the
+                                       // first reference is the batch's own and cfear_scan_destroy refuses to drop it
 };
-void cfear_scan_retain(cfear_scan* scan);   // cfear_scan_destroy drops one reference; the slab is recycled with the last
+void cfear_scan_retain(cfear_scan* scan);   // a scan table's reference; cfear_scan_release drops it
+// Drops one reference, the slab (or, with the last handle of a destroyed batch, the arena) is recycled with the last.  The
+// public cfear_scan_destroy is this for a handle of the caller's own and a refusal for a borrowed one, whatever its count:
+// a table's reference can only be dropped by the table.
+int cfear_scan_release(cfear_scan* scan);
+
+// N scans in one arena (cfear_scan_create_batch, surface.hip): scan i's slab is arena + i * cfear_scan_slab_bytes(max_cells).
+// The arena outlives cfear_scan_batch_destroy for as long as a scan table still names one of its scans: the batch is freed
+// with the last reference on its last scan (cfear_scan_destroy), and its arena goes to cfear_ctx::free_arena.
+struct cfear_scan_batch {
+  cfear_ctx* ctx = nullptr;
+  DevBuf<void> arena;
+  size_t arena_bytes = 0;
+  std::vector<cfear_scan*> scans;      // [n_scans]; nullptr where the scan failed
+  int32_t live = 0;                    // handles not yet deleted
+  bool released = false;               // cfear_scan_batch_destroy was called: the handles' first reference is gone
+};
+void cfear_scan_batch_free(cfear_scan_batch* b);   // live == 0: recycles the arena and deletes the batch
+// cfear_scan_create_batch behind its argument checks, cloud by cloud (surface.hip): clouds[i] = the lengths[i] >= 0 points of
+// scan i, on_host[i] whether they are host memory, one_buffer whether they are all pieces of one buffer of the caller's
+int cfear_scan_batch_build(cfear_ctx* ctx, const float* const* clouds, const char* on_host, bool one_buffer, const int32_t* lengths, int n_scans,
+                           const cfear_feature_params* par, const double* mots, int max_cells, cfear_scan_batch** out, int32_t* status);
 
 size_t cfear_scan_slab_bytes(int cap);
 ScanView cfear_scan_view(void* slab, int cap);

@@ -350,6 +350,16 @@ int cfear_scan_clone_view(cfear_ctx* ctx, const ScanView& src, int n, cfear_scan
 
 void cfear_scan_retain(cfear_scan* scan) { if (scan) scan->refs++; }
 
+// The arena may still be read by enqueued kernels of this stream; its next user is on the same stream (as for the slabs).
+void cfear_scan_batch_free(cfear_scan_batch* b) {
+  cfear_ctx* ctx = b->ctx;
+  if (b->arena_bytes > ctx->free_arena.bytes) {
+    ctx->free_arena.p = std::move(b->arena);
+    ctx->free_arena.bytes = b->arena_bytes;
+  }
+  delete b;
+}
+
 // ---- C-ABI ---------------------------------------------------------------------------------------
 extern "C" {
 
@@ -403,6 +413,12 @@ int cfear_ctx_get_stream(const cfear_ctx* ctx, void** hip_stream) {
 
 int cfear_ctx_set_option(cfear_ctx* ctx, int32_t option, int64_t value) {
   if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
+  if (option == CFEAR_OPT_REPLAY_CHUNK) {                  // numbered apart from the enum (include/cfear_hip.h)
+    if (value < 0 || value > INT32_MAX)
+      return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "option %d: value %lld out of range", (int)option, (long long)value);
+    ctx->replay_chunk = value;
+    return CFEAR_OK;
+  }
   bool ok = false;
   switch (option) {
     case CFEAR_OPT_FUSED_DECODE: case CFEAR_OPT_HOST_TIMELINE: ok = value == 0 || value == 1; break;
@@ -418,6 +434,7 @@ int cfear_ctx_set_option(cfear_ctx* ctx, int32_t option, int64_t value) {
 }
 
 int cfear_ctx_get_option(const cfear_ctx* ctx, int32_t option, int64_t* value) {
+  if (ctx && value && option == CFEAR_OPT_REPLAY_CHUNK) { *value = ctx->replay_chunk; return CFEAR_OK; }
   if (!ctx || !value || option < 0 || option >= CFEAR_OPT_COUNT) return CFEAR_ERR_INVALID_ARGUMENT;
   *value = ctx->opt[option];
   return CFEAR_OK;
@@ -569,6 +586,21 @@ int cfear_scan_size(const cfear_scan* scan) {
 
 int cfear_scan_destroy(cfear_scan* scan) {
   if (!scan) return CFEAR_OK;
+  if (scan->batch)                                         // a view into a batch's arena: never the caller's to destroy
+    return cfear_set_error(scan->ctx, CFEAR_ERR_INVALID_ARGUMENT, "the scan is borrowed from a scan batch: destroy the batch instead");
+  return cfear_scan_release(scan);
+}
+
+}  // extern "C"
+
+int cfear_scan_release(cfear_scan* scan) {
+  if (!scan) return CFEAR_OK;
+  if (cfear_scan_batch* b = scan->batch) {                 // a scan table's reference on a borrowed handle
+    if (--scan->refs > 0) return CFEAR_OK;
+    delete scan;
+    if (--b->live == 0) cfear_scan_batch_free(b);          // the batch is gone and this was the last table naming its arena
+    return CFEAR_OK;
+  }
   if (--scan->refs > 0) return CFEAR_OK;                   // a scan table still names it (cfear_scan_retain)
   cfear_ctx* ctx = scan->ctx;
   // the slab may still be read by enqueued kernels of this stream; later users are on the same
@@ -578,5 +610,3 @@ int cfear_scan_destroy(cfear_scan* scan) {
   delete scan;
   return CFEAR_OK;
 }
-
-}  // extern "C"

@@ -29,16 +29,8 @@ extern "C" int cfear_keyframe_based_fuse(const double diff_xyt[3], int32_t use_k
   const double rot = std::fabs(diff_xyt[2]);
   return (tn > min_keyframe_dist || rot > (min_keyframe_rot_deg * M_PI / 180.0)) ? 1 : 0;
 }
-// AccelerationVelocitySanityCheck (odometrykeyframefuser.cpp:76-94): 4 Hz, 200 m/s and 200 m/s^2, strict comparisons,
-// acceleration tested first; only the translations of the two motions enter.  1 = sane, 0 = use the guess (:198-199).
 extern "C" int cfear_acc_vel_sanity_check(const double tmot_prev_xy[2], const double tmot_curr_xy[2]) {
-  const double dt = 0.25, vel_limit = 200, acc_limit = 200;
-  const double vel = std::sqrt((tmot_curr_xy[0] / dt) * (tmot_curr_xy[0] / dt) + (tmot_curr_xy[1] / dt) * (tmot_curr_xy[1] / dt));
-  const double ax = (tmot_curr_xy[0] - tmot_prev_xy[0]) / (dt * dt), ay = (tmot_curr_xy[1] - tmot_prev_xy[1]) / (dt * dt);
-  const double acc = std::sqrt(ax * ax + ay * ay);
-  if (acc > acc_limit) return 0;
-  else if (vel > vel_limit) return 0;
-  return 1;
+  return pose2d_acc_vel_sane(tmot_prev_xy, tmot_curr_xy);        // pose2d.hpp: the replay's score kernel takes it from there too
 }
 
 namespace {

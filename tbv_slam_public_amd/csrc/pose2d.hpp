@@ -69,3 +69,15 @@ POSE2D_FN void xyt_inverse(const double a[3], double o[3]) {                    
   const double x = -(c * a[0] + s * a[1]), y = s * a[0] - c * a[1];
   o[0] = x; o[1] = y; o[2] = -a[2];
 }
+
+// AccelerationVelocitySanityCheck (odometrykeyframefuser.cpp:76-94): 4 Hz, 200 m/s and 200 m/s^2, strict comparisons,
+// acceleration tested first; only the translations of the two motions enter.  1 = sane, 0 = use the guess (:198-199).
+POSE2D_FN int pose2d_acc_vel_sane(const double tmot_prev_xy[2], const double tmot_curr_xy[2]) {
+  const double dt = 0.25, vel_limit = 200, acc_limit = 200;
+  const double vel = sqrt((tmot_curr_xy[0] / dt) * (tmot_curr_xy[0] / dt) + (tmot_curr_xy[1] / dt) * (tmot_curr_xy[1] / dt));
+  const double ax = (tmot_curr_xy[0] - tmot_prev_xy[0]) / (dt * dt), ay = (tmot_curr_xy[1] - tmot_prev_xy[1]) / (dt * dt);
+  const double acc = sqrt(ax * ax + ay * ay);
+  if (acc > acc_limit) return 0;
+  else if (vel > vel_limit) return 0;
+  return 1;
+}

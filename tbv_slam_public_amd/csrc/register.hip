@@ -171,7 +171,7 @@ extern "C" int cfear_scan_table_destroy(cfear_scan_table* t) {
   if (!t) return CFEAR_OK;
   (void)hipSetDevice(t->ctx->device);
   (void)hipStreamSynchronize(t->ctx->stream);
-  for (cfear_scan* s : t->scans) (void)cfear_scan_destroy(s);          // drops the table's reference
+  for (cfear_scan* s : t->scans) (void)cfear_scan_release(s);          // drops the table's reference
   delete t;
   return CFEAR_OK;
 }

@@ -1802,6 +1802,176 @@ extern "C" int cfear_scan_create(cfear_ctx* ctx, float* xyzi, int32_t n, const c
   return CFEAR_OK;
 }
 
+// ---- N clouds -> N scans in one arena ---------------------------------------------------------------------------------
+namespace {
+constexpr size_t kScanBatchScratch = (size_t)1 << 30;   // surface scratch one launch sequence may take (2.1 MiB per scan up to kMaxPoints points)
+
+// One launch sequence over the clouds idx[0..m) of the batch: status, route word and cell count of each into hst [3][m].
+// A host cloud is staged, and so is a device cloud that gets compensated (the caller's points are const): in one piece
+// where the caller states that the clouds are pieces of ONE buffer (the xyzi + offsets entry: the span between the first and
+// the last cloud is then the caller's memory) and they lie one behind the other without much between them, else cloud by
+// cloud -- clouds handed in one by one may be separate allocations with unmapped memory between them.
+int scan_batch_chunk(cfear_ctx* ctx, const float* const* clouds, const char* on_host, bool one_buffer, const int32_t* lengths, const int* idx, int m,
+                     int cap_points, const cfear_feature_params* par, const double* mots, int max_cells, char* arena, size_t slab_bytes,
+                     int32_t* hst) {
+  HostStage st(ctx, kWsSurface);
+  const bool comp = par->compensate != 0;
+  bool dense = true;
+  const float* end = clouds[idx[0]];
+  int64_t sum = 0;
+  for (int k = 0; k < m; k++) {
+    const int i = idx[k];
+    dense = dense && on_host[i] == on_host[idx[0]] && clouds[i] >= end;
+    end = clouds[i] + 4 * (size_t)lengths[i];
+    sum += lengths[i];
+  }
+  const float* lo = clouds[idx[0]];
+  const bool host0 = on_host[idx[0]] != 0;
+  dense = dense && one_buffer && (host0 || comp) && (end - lo) / 4 <= 2 * sum + 4096;
+  const size_t span_bytes = dense ? (size_t)(end - lo) * 4 : 0;
+  const float* d_span = nullptr;
+  std::vector<const float*> d_cloud((size_t)m, nullptr);
+  if (dense) {
+    st.piece(d_span, span_bytes);                  // (on_host[] already says which side: no pointer query per piece)
+  } else {
+    for (int k = 0; k < m; k++) {
+      const int i = idx[k];
+      if (on_host[i] || comp) st.piece(d_cloud[(size_t)k], (size_t)lengths[i] * 16);
+      else d_cloud[(size_t)k] = clouds[i];         // a device cloud that is only read: in place
+    }
+  }
+  char* d_jobs;
+  int32_t* d_st;
+  st.piece(d_jobs, (size_t)m * sizeof(SurfJob));
+  st.piece(d_st, (size_t)m * 12);                  // status [m] | route word [m] | cells [m]
+  char* d_scratch = (char*)cfear_workspace(ctx, kWsSurfaceScratch, (size_t)m * cfear_surface_scratch_bytes(cap_points));
+  if (!d_scratch) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
+  CFEAR_CHECK(st.carve());
+  // host clouds are uploaded; the device clouds that are compensated are copied, the caller's stay as they are
+  if (dense && host0) CFEAR_CHECK(st.upload((void*)d_span, lo, span_bytes));
+  if (dense && !host0) CFEAR_HIP_CHECK(ctx, hipMemcpyAsync((void*)d_span, lo, span_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  for (int k = 0; !dense && k < m; k++) {
+    const int i = idx[k];
+    if (on_host[i]) CFEAR_CHECK(st.upload((void*)d_cloud[(size_t)k], clouds[i], (size_t)lengths[i] * 16));
+    else if (comp) CFEAR_HIP_CHECK(ctx, hipMemcpyAsync((void*)d_cloud[(size_t)k], clouds[i], (size_t)lengths[i] * 16, hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  char* hjobs = (char*)st.record((size_t)m * sizeof(SurfJob));
+  for (int k = 0; k < m; k++) {
+    const int i = idx[k];
+    const float* d = dense ? d_span + (clouds[i] - lo) : d_cloud[(size_t)k];
+    cfear_surface_fill_job(hjobs + (size_t)k * sizeof(SurfJob), const_cast<float*>(d), nullptr, lengths[i], par->compensate,
+                           mots ? mots + 3 * (size_t)i : par->mot, cfear_scan_view(arena + (size_t)i * slab_bytes, max_cells));
+  }
+  CFEAR_CHECK(st.upload(d_jobs, hjobs, (size_t)m * sizeof(SurfJob)));
+  CFEAR_CHECK(cfear_surface_launch(ctx, d_jobs, m, par, d_scratch, d_st, d_st + 2 * m, max_cells, cap_points, nullptr, (uint32_t*)(d_st + m)));
+  st.back(hst, d_st, (size_t)m * 12);
+  return st.finish();
+}
+}  // namespace
+
+// cfear_scan_create_batch behind its argument checks, cloud by cloud: clouds[i] = the lengths[i] points of scan i, on_host[i]
+// whether they are host memory, one_buffer whether all of them are pieces of one buffer of the caller's (only then may the
+// memory BETWEEN two clouds be read).  The replay (replay.hip) calls it with the clouds its caller handed in one by one.
+int cfear_scan_batch_build(cfear_ctx* ctx, const float* const* clouds, const char* on_host, bool one_buffer, const int32_t* lengths, int n_scans,
+                           const cfear_feature_params* par, const double* mots, int max_cells, cfear_scan_batch** out, int32_t* status) {
+  *out = nullptr;
+  if (max_cells < 1 || max_cells > kMaxPoints)
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "max_cells must be in [1, %d]", kMaxPoints);
+  std::vector<int> idx;                            // the clouds that get a job
+  for (int i = 0; i < n_scans; i++) {
+    status[i] = lengths[i] == 0 ? CFEAR_ERR_EMPTY_CLOUD : lengths[i] > kScanCreateMaxPoints ? CFEAR_ERR_CAPACITY : CFEAR_OK;
+    if (status[i] == CFEAR_OK) idx.push_back(i);
+  }
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  std::unique_ptr<cfear_scan_batch, int (*)(cfear_scan_batch*)> b(new cfear_scan_batch(), cfear_scan_batch_destroy);
+  b->ctx = ctx;
+  b->scans.assign((size_t)n_scans, nullptr);
+  const size_t slab_bytes = cfear_scan_slab_bytes(max_cells);
+  b->arena_bytes = slab_bytes * (size_t)n_scans;
+  if (ctx->free_arena.bytes >= b->arena_bytes) {
+    b->arena = std::move(ctx->free_arena.p);
+    b->arena_bytes = ctx->free_arena.bytes;
+    ctx->free_arena.bytes = 0;
+  } else if (!(b->arena = dev_alloc<void>(b->arena_bytes))) {
+    return cfear_set_error(ctx, CFEAR_ERR_HIP, "scan batch: hipMalloc of %zu bytes failed", b->arena_bytes);
+  }
+  std::vector<int32_t> hst;
+  for (size_t c0 = 0; c0 < idx.size();) {          // chunks the surface scratch bounds
+    size_t c1 = c0;
+    int cap_points = 0;
+    while (c1 < idx.size()) {
+      const int cp = std::max(cap_points, lengths[idx[c1]]);
+      if (c1 > c0 && (c1 - c0 + 1) * cfear_surface_scratch_bytes(cp) > kScanBatchScratch) break;
+      cap_points = cp;
+      c1++;
+    }
+    const int m = (int)(c1 - c0);
+    hst.assign((size_t)m * 3, 0);
+    CFEAR_CHECK(scan_batch_chunk(ctx, clouds, on_host, one_buffer, lengths, idx.data() + c0, m, cap_points, par, mots, max_cells,
+                                 (char*)b->arena.get(), slab_bytes, hst.data()));
+    for (int k = 0; k < m; k++) {
+      const int i = idx[c0 + (size_t)k];
+      status[i] = hst[(size_t)k];
+      if (status[i] != CFEAR_OK) continue;
+      cfear_scan* s = new cfear_scan();
+      s->ctx = ctx;
+      s->view = cfear_scan_view((char*)b->arena.get() + (size_t)i * slab_bytes, max_cells);
+      s->n_cells_host = hst[(size_t)(2 * m + k)];
+      s->surf_path = (uint32_t)hst[(size_t)(m + k)];
+      s->batch = b.get();
+      b->scans[(size_t)i] = s;
+      b->live++;
+    }
+    c0 = c1;
+  }
+  *out = b.release();
+  for (int i = 0; i < n_scans; i++)
+    if (status[i] != CFEAR_OK) return cfear_set_error(ctx, status[i], "scan %d: %s", i, cfear_status_string(status[i]));
+  return CFEAR_OK;
+}
+
+extern "C" int cfear_scan_create_batch(cfear_ctx* ctx, const float* xyzi, const int64_t* offsets, const int32_t* lengths, int32_t n_scans,
+                                       const cfear_feature_params* par, const double* mots, int32_t max_cells, cfear_scan_batch** out,
+                                       int32_t* status) {
+  if (!ctx) return CFEAR_ERR_INVALID_ARGUMENT;
+  if (!offsets || !lengths || !par || !out || !status || n_scans < 1)
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument / empty batch");
+  *out = nullptr;
+  bool any = false;
+  for (int i = 0; i < n_scans; i++) {
+    if (lengths[i] < 0 || offsets[i] < 0 || (lengths[i] > 0 && !xyzi))
+      return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "scan %d: negative offset or length, or no points", i);
+    any = any || lengths[i] > 0;
+  }
+  std::vector<const float*> clouds((size_t)n_scans);
+  for (int i = 0; i < n_scans; i++) clouds[(size_t)i] = xyzi ? xyzi + 4 * offsets[i] : nullptr;
+  const std::vector<char> on_host((size_t)n_scans, (char)(any && !cfear_is_device_ptr(xyzi)));
+  return cfear_scan_batch_build(ctx, clouds.data(), on_host.data(), /*one_buffer=*/true, lengths, n_scans, par, mots, max_cells, out, status);
+}
+
+extern "C" int cfear_scan_batch_size(const cfear_scan_batch* batch) { return batch ? (int)batch->scans.size() : CFEAR_ERR_INVALID_ARGUMENT; }
+
+extern "C" int cfear_scan_batch_get(const cfear_scan_batch* batch, int32_t i, const cfear_scan** scan) {
+  if (!batch || !scan) return CFEAR_ERR_INVALID_ARGUMENT;
+  *scan = nullptr;
+  if (i < 0 || (size_t)i >= batch->scans.size())
+    return cfear_set_error(batch->ctx, CFEAR_ERR_INVALID_ARGUMENT, "scan %d of a batch of %zu", i, batch->scans.size());
+  *scan = batch->scans[(size_t)i];
+  return CFEAR_OK;
+}
+
+extern "C" int cfear_scan_batch_destroy(cfear_scan_batch* batch) {
+  if (!batch) return CFEAR_OK;
+  batch->released = true;                          // drops the batch's reference on every scan; those a scan table still names stay
+  for (cfear_scan*& s : batch->scans) {
+    cfear_scan* h = s;
+    s = nullptr;
+    if (h && --h->refs == 0) { delete h; batch->live--; }
+  }
+  if (batch->live == 0) cfear_scan_batch_free(batch);
+  return CFEAR_OK;
+}
+
 extern "C" int cfear_scan_surface_path(const cfear_scan* scan, uint32_t* path) {
   if (!scan || !path) return CFEAR_ERR_INVALID_ARGUMENT;
   *path = scan->surf_path;
