@@ -9,7 +9,7 @@
 The sensor drives a closed circle, so the last nodes revisit the first ones: the demo prints the loop constraints the
 verifier accepts and how far their registered transforms are from the ground truth.  `run(backend)` is shared with
 tests/test_gpu_tbv_loop.py, which runs it a second time with the CPU oracle behind the same host logic.
-    python examples/loop_closure_demo.py [--frames 68] [--raw-scan-context | --batched-scan-context]"""
+    python examples/loop_closure_demo.py [--frames 68] [--raw-scan-context] [--batched-scan-context]"""
 import argparse
 import os
 import sys
@@ -92,7 +92,8 @@ def run(backend, n_frames=68, scene=None, log=None, raw_scan_context=False, batc
     raw_scan_context: TBV's --raw_radar_scan true (loopclosure.cpp:573-577): each node's descriptor is made from its raw
     polar sweep instead of the local map of peaks.
     batched_scan_context: the offline form (tbv_slam_offline): every node's candidates come from one whole-graph call
-    (api.sc_detect_sequence, local maps merged on the GPU) before the loop; the candidates are the same."""
+    (api.sc_detect_sequence, local maps merged on the GPU) before the loop; the candidates are the same.  With
+    raw_scan_context as well, the whole lap's raw candidates come from one api.sc_detect_batch call."""
     sc = scene or circle_scene()
     imgs = np.stack([sc.render(f, n_frames) for f in range(n_frames)])
     gt = np.stack([sc.pose_at(f, n_frames) for f in range(n_frames)])
@@ -101,7 +102,10 @@ def run(backend, n_frames=68, scene=None, log=None, raw_scan_context=False, batc
     poses, nodes = backend.sequence(imgs)
     rsc = backend.scan_context()
     batched = None
-    if batched_scan_context:
+    if batched_scan_context and raw_scan_context:
+        raw_par = backend.api.sc_raw_params(transpose=int(imgs.shape[1] < imgs.shape[2]))     # RSCManagerNative's rule for a sweep
+        batched = backend.api.sc_detect_batch([(imgs, poses)], n_detect=[n_frames - 1], raw_par=raw_par)[0]
+    elif batched_scan_context:
         batched = backend.api.sc_detect_sequence([nd["peaks"] for nd in nodes], poses, n_aggregate=1, n_detect=n_frames - 1)
     cands = []
     for i in range(n_frames - 1):                                                # the closure thread trails the odometry by one node
@@ -144,8 +148,6 @@ if __name__ == "__main__":
     ap.add_argument("--batched-scan-context", action="store_true",
                     help="propose every node's candidates with one whole-graph call before verifying (offline mode)")
     a = ap.parse_args()
-    if a.raw_scan_context and a.batched_scan_context:
-        ap.error("--batched-scan-context covers the local-map (cloud) mode only")
     out = run(HipBackend(), a.frames, log=print, raw_scan_context=a.raw_scan_context, batched_scan_context=a.batched_scan_context)
     acc = sum(r["accepted"] for r in out["results"])
     drift = np.abs(out["poses"][-1] - out["gt"][-1])

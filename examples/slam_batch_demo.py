@@ -3,7 +3,7 @@
 
   radar sweeps  -> CFEAR-3 odometry of all laps at once (OdometryKeyframeFuser, one stream per lap); every keyframe
                    leaves a graph node and the odometry constraint of cfear_odometry_get_constraint
-  per lap       -> loop candidates of the whole graph in one call (api.sc_detect_sequence)
+  all laps      -> the Scan Context loop candidates of every graph in ONE call (api.sc_detect_batch)
   all laps      -> every candidate registered, scored and classified in one call (api.verify_loop_candidates)
   all laps      -> every pose graph solved in ONE call (api.pose_graph_optimize_batch, one wavefront per graph)
   all laps      -> raw and corrected trajectories scored by ONE api.eval_trajectories call (KITTI odometry metric)
@@ -22,8 +22,10 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import loop_closure_demo as demo          # noqa: E402
 
 
-def run(n_laps=3, n_frames=68, loop_scaling=1.0, log=None):
-    """-> dict(raw, corrected, gt [lap][node, 3], keyframes [lap] frame indices, loops [lap] accepted constraints, pgo [lap] summaries, before, after)."""
+def run(n_laps=3, n_frames=68, loop_scaling=1.0, log=None, per_lap_scan_context=False):
+    """-> dict(raw, corrected, gt [lap][node, 3], keyframes [lap] frame indices, candidates [(lap, from, to)], loops [lap] accepted
+    constraints, pgo [lap] summaries, before, after).  per_lap_scan_context: one api.sc_detect_sequence call per lap, the loop the
+    batch call replaced (the candidates are the same)."""
     from tbv_slam_public_amd import api
     backend = demo.HipBackend()
     scenes = [demo.circle_scene(seed=21 + lap) for lap in range(n_laps)]
@@ -53,10 +55,16 @@ def run(n_laps=3, n_frames=68, loop_scaling=1.0, log=None):
     od.close()
     poses = [raw[lap, kf[lap]] for lap in range(n_laps)]                         # node poses; ids = keyframe ordinals 0, 1, 2, ...
     gt = [gt[lap][kf[lap]] for lap in range(n_laps)]
-    # ---- loop candidates per graph, then ONE verification call for all laps ---------------------------------------------
+    # ---- loop candidates of all graphs in ONE call, then ONE verification call for all laps ------------------------------
     cands, owner = [], []
-    for lap in range(n_laps):
-        found = api.sc_detect_sequence([nd["peaks"] for nd in nodes[lap]], poses[lap], n_aggregate=1, n_detect=len(kf[lap]) - 1)
+    n_detect = [len(kf[lap]) - 1 for lap in range(n_laps)]
+    if per_lap_scan_context:
+        found_all = [api.sc_detect_sequence([nd["peaks"] for nd in nodes[lap]], poses[lap], n_aggregate=1, n_detect=n_detect[lap])
+                     for lap in range(n_laps)]
+    else:
+        found_all = api.sc_detect_batch([([nd["peaks"] for nd in nodes[lap]], poses[lap]) for lap in range(n_laps)], n_aggregate=1,
+                                        n_detect=n_detect)
+    for lap, found in enumerate(found_all):
         for i, group in enumerate(found):
             for c in group:
                 to = c["nn_idx"]
@@ -91,8 +99,8 @@ def run(n_laps=3, n_frames=68, loop_scaling=1.0, log=None):
             gap = [np.hypot(*(t[-1, :2] - gt[lap][-1, :2])) for t in (poses[lap], corrected[lap])]
             log("%3d %6d %21d %6d %14d %18.3f -> %.3f %22.3f -> %.3f" % (lap, len(kf[lap]), len(cons[lap]), len(loops[lap]), solved[lap][1]["iterations"],
                                                                    gap[0], gap[1], summaries[lap]["ate"], summaries[n_laps + lap]["ate"]))
-    return dict(raw=poses, keyframes=kf, corrected=corrected, gt=gt, loops=loops, pgo=[s for _, s in solved], before=summaries[:n_laps],
-                after=summaries[n_laps:])
+    return dict(raw=poses, keyframes=kf, corrected=corrected, gt=gt, candidates=[(lap, c["from"], c["to"]) for lap, c in zip(owner, cands)],
+                loops=loops, pgo=[s for _, s in solved], before=summaries[:n_laps], after=summaries[n_laps:])
 
 
 if __name__ == "__main__":

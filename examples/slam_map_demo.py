@@ -51,8 +51,9 @@ def solve_laps(n_laps, n_frames, loop_scaling):
     poses = [raw[lap, kf[lap]] for lap in range(n_laps)]
     gt = [gt[lap][kf[lap]] for lap in range(n_laps)]
     cands, owner = [], []
-    for lap in range(n_laps):
-        found = api.sc_detect_sequence([nd["peaks"] for nd in nodes[lap]], poses[lap], n_aggregate=1, n_detect=len(kf[lap]) - 1)
+    found_all = api.sc_detect_batch([([nd["peaks"] for nd in nodes[lap]], poses[lap]) for lap in range(n_laps)], n_aggregate=1,
+                                    n_detect=[len(kf[lap]) - 1 for lap in range(n_laps)])
+    for lap, found in enumerate(found_all):
         for i, group in enumerate(found):
             for c in group:
                 to = c["nn_idx"]

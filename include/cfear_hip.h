@@ -85,9 +85,11 @@ int cfear_ctx_get_stream(const cfear_ctx* ctx, void** hip_stream);
  *                            that many KB, so that ordinary scans exercise the keyframe groups and the global tail of
  *                            the correspondence arrays (which only unusually large registrations reach otherwise).
  *   CFEAR_OPT_MATCHER_WAVES  0 (default): wavefronts per registration chosen by the batch; 2, 4, 8, 16 force a form.
- *   CFEAR_OPT_HOST_TIMELINE  1: the batched odometry prints where the host spends a frame (every 256 calls).
- *   CFEAR_OPT_SC_QUERY_CHUNK 0 (default): cfear_sc_detect_sequence sizes its query chunks by a device budget; n >= 1:
- *                            at most n query nodes per chunk, so that small graphs cross chunk boundaries.
+ *   CFEAR_OPT_HOST_TIMELINE  1: the batched odometry prints where the host spends a frame (every 256 calls), and
+ *                            cfear_sc_detect_batch where it spends every call (one line on stderr).
+ *   CFEAR_OPT_SC_QUERY_CHUNK 0 (default): cfear_sc_detect_sequence and cfear_sc_detect_batch size their query chunks by a
+ *                            device budget; n >= 1: at most n query nodes per chunk, so that small graphs cross chunk
+ *                            boundaries (in a batch the chunks run over the concatenated detected nodes of all graphs).
  *   CFEAR_OPT_PGO_GRAPH_CHUNK n >= 1: cfear_pgo_solve_batch takes at most n graphs per chunk (on top of its device budget),
  *                            so that small batches cross chunk boundaries; INT32_MAX lifts the cap again.  A context that
  *                            never set it reads 0 and sizes its chunks by the budget alone; 0 itself is not a cap and,
@@ -1082,6 +1084,48 @@ int cfear_sc_local_map_descriptors(cfear_ctx* ctx, const cfear_sc_node* nodes, i
  * Refused with CFEAR_ERR_CAPACITY: num_candidates_from_tree > 64.                                                      */
 int cfear_sc_detect_sequence(cfear_ctx* ctx, const cfear_sc_manager_params* par, const cfear_sc_node* nodes, int32_t n_nodes,
                              int32_t n_aggregate, int32_t n_detect, cfear_sc_candidate* out, int32_t* n_out);
+
+/* The same for a batch of graphs in one call, in either descriptor mode, with the ranking on the device.  The graphs' nodes
+ * lie one behind the other: graph g owns nodes [node_off[g], node_off[g + 1]) (node_off[0] = 0; empty graphs are allowed)
+ * and detects its first n_detect[g] of them; nodes past that only join local maps.  Graph g's rows are what a fresh
+ * cfear_sc_manager returns when its nodes 0 .. n_detect[g] - 1 are added in order -- _add with the local map, or _add_raw --
+ * each detected right after it is added, with the odometry similarity evaluated on the device as in
+ * cfear_sc_detect_sequence: in cloud mode they equal cfear_sc_detect_sequence of that graph alone byte for byte.
+ *   CFEAR_SC_NODES_CLOUD  one point buffer xyzi [point_off[n_nodes]][4] (host or device), node i's cloud in its own frame at
+ *                         [point_off[i], point_off[i + 1]); the local map of a node merges the nodes of ITS graph whose id
+ *                         lies within n_aggregate (ScansToLocalMap, as above).  imgs / desc / raw are not read.
+ *   CFEAR_SC_NODES_RAW    node i's descriptor is cfear_sc_raw_descriptors of sweep i of imgs (host or device; desc->batch
+ *                         must be n_nodes), without lateral augmentations whatever augment_sc says (cfear_sc_manager_add_raw).
+ *                         xyzi / point_off / n_aggregate / Tinv are not read.
+ * out [sum n_detect][par->n_candidates] and n_out [sum n_detect] hold the detected nodes' rows in graph order, both in host
+ * or both in device memory (device rows stay in HBM for a later stage; the call is then asynchronous unless an input was
+ * staged).  nn_idx counts within the node's graph; records past n_out[i] are all-zero bytes.  Among equal min_dist the pair
+ * visited first (augmentation, then search rank) ranks first, as the manager's stable sort leaves them.
+ * Refused before anything is launched, out / n_out untouched, the message naming "graph g, node i" where one node is at
+ * fault: everything cfear_sc_detect_sequence and cfear_sc_raw_descriptors refuse, a non-monotone node_off or point_off, a
+ * null array with a positive count, n_detect[g] outside [0, nodes of g], ids that do not increase strictly within a graph,
+ * an unknown mode, out and n_out in different memories.  n_graphs = 0 or no detected node: CFEAR_OK, the device untouched.
+ * The arguments are checked before the context is: a null ctx is refused last (CFEAR_ERR_INVALID_ARGUMENT).            */
+#define CFEAR_SC_NODES_CLOUD 0
+#define CFEAR_SC_NODES_RAW 1
+typedef struct cfear_sc_batch {
+  int32_t n_graphs;
+  int32_t mode;                         /* CFEAR_SC_NODES_CLOUD / CFEAR_SC_NODES_RAW, for the whole call          */
+  const int32_t* node_off;              /* [n_graphs + 1] host                                                   */
+  const int32_t* n_detect;              /* [n_graphs] host; NULL: every node                                     */
+  const int32_t* ids;                   /* [n_nodes] host, strictly increasing within a graph; NULL: 0, 1, ...   */
+  const double* T;                      /* [n_nodes][8] host: node -> world rows 0 and 1; Todom = (T[3], T[7])   */
+  const double* Tinv;                   /* [n_nodes][8] host: world -> node (cloud mode)                         */
+  const float* xyzi;                    /* cloud mode: [point_off[n_nodes]][4], host or device                   */
+  const int64_t* point_off;             /* cloud mode: [n_nodes + 1] host                                        */
+  int32_t n_aggregate;                  /* cloud mode                                                            */
+  int32_t pad;
+  const uint8_t* imgs;                  /* raw mode: n_nodes sweeps, host or device                              */
+  const cfear_polar_desc* desc;         /* raw mode: their layout, batch = n_nodes                               */
+  const cfear_sc_raw_params* raw;       /* raw mode                                                              */
+} cfear_sc_batch;                       /* 96 bytes */
+int cfear_sc_detect_batch(cfear_ctx* ctx, const cfear_sc_manager_params* par, const cfear_sc_batch* batch,
+                          cfear_sc_candidate* out, int32_t* n_out);
 
 /* ---- caller: loop-candidate verification --------------------------------------------------------------
  * What the loop-closure thread does per candidate (tbv_slam/src/tbv_slam/loopclosure.cpp:658-725), for a batch:

@@ -1680,6 +1680,58 @@ inline std::vector<std::vector<cfear_sc_candidate>> DetectLoopClosureSequence(
   return res;
 }
 
+// The same for a batch of graphs in one call (cfear_sc_detect_batch, cloud mode): every graph as DetectLoopClosureSequence
+// takes it.  The clouds are gathered into the call's one point buffer, so they cross to the device in one copy.
+// -> per graph, the candidates of every detected node, closest first (nn_idx counts within the graph)
+struct ScGraph {
+  std::vector<const CFEAR_Radarodometry::PointCloud*> clouds;
+  std::vector<ScNodeRows8> T, Tinv;
+  std::vector<int> ids;
+  int n_detect = 0;
+};
+inline std::vector<std::vector<std::vector<cfear_sc_candidate>>> DetectLoopClosureBatch(
+    CFEAR_Radarodometry::Context& ctx, const std::vector<ScGraph>& graphs, int n_aggregate,
+    const cfear_sc_manager_params* par = nullptr) {
+  cfear_sc_manager_params def;
+  if (!par) { cfear_sc_manager_params_default(&def); par = &def; }
+  std::vector<int32_t> node_off{0}, n_detect, ids;
+  std::vector<int64_t> point_off{0};
+  std::vector<double> T, Tinv;
+  std::vector<float> xyzi;
+  size_t rows = 0;
+  for (const ScGraph& g : graphs) {
+    if (g.T.size() != g.clouds.size() || g.Tinv.size() != g.clouds.size() || g.ids.size() != g.clouds.size())
+      throw CFEAR_Radarodometry::CfearError(CFEAR_ERR_INVALID_ARGUMENT, "one matrix pair and one id per cloud");
+    for (size_t i = 0; i < g.clouds.size(); i++) {
+      if (!g.clouds[i]->empty()) xyzi.insert(xyzi.end(), &(*g.clouds[i])[0].x, &(*g.clouds[i])[0].x + 4 * g.clouds[i]->size());
+      point_off.push_back((int64_t)(xyzi.size() / 4));
+      T.insert(T.end(), g.T[i].begin(), g.T[i].end());
+      Tinv.insert(Tinv.end(), g.Tinv[i].begin(), g.Tinv[i].end());
+      ids.push_back(g.ids[i]);
+    }
+    node_off.push_back(node_off.back() + (int32_t)g.clouds.size());
+    n_detect.push_back(g.n_detect);
+    rows += (size_t)std::max(g.n_detect, 0);
+  }
+  cfear_sc_batch b = cfear_sc_batch();
+  b.n_graphs = (int32_t)graphs.size();
+  b.mode = CFEAR_SC_NODES_CLOUD;
+  b.node_off = node_off.data(); b.n_detect = n_detect.data(); b.ids = ids.data();
+  b.T = T.data(); b.Tinv = Tinv.data(); b.xyzi = xyzi.data(); b.point_off = point_off.data();
+  b.n_aggregate = n_aggregate;
+  const int nc = std::max(par->n_candidates, 1);
+  std::vector<cfear_sc_candidate> out(std::max<size_t>(rows, 1) * nc);
+  std::vector<int32_t> n_out(std::max<size_t>(rows, 1));
+  ctx.check(cfear_sc_detect_batch(ctx.get(), par, &b, out.data(), n_out.data()));
+  std::vector<std::vector<std::vector<cfear_sc_candidate>>> res(graphs.size());
+  size_t row = 0;
+  for (size_t g = 0; g < graphs.size(); g++) {
+    res[g].resize((size_t)std::max(graphs[g].n_detect, 0));
+    for (size_t i = 0; i < res[g].size(); i++, row++) res[g][i].assign(out.begin() + row * nc, out.begin() + row * nc + n_out[row]);
+  }
+  return res;
+}
+
 // Loop-candidate verification of tbv_slam::loopclosure (tbv_slam/src/tbv_slam/loopclosure.cpp:320-384, 261-274,
 // 776-808) for a batch of candidates.
 namespace tbv_slam {

@@ -235,6 +235,16 @@ class ScNode(C.Structure):         # cfear_sc_node
     _fields_ = [("cloud", ScCloud), ("T", C.c_double * 8), ("Tinv", C.c_double * 8), ("id", C.c_int32), ("pad", C.c_int32)]
 
 
+SC_NODES_CLOUD, SC_NODES_RAW = 0, 1   # CFEAR_SC_NODES_*
+
+
+class ScBatch(C.Structure):        # cfear_sc_batch
+    _fields_ = [("n_graphs", C.c_int32), ("mode", C.c_int32), ("node_off", C.c_void_p), ("n_detect", C.c_void_p),
+                ("ids", C.c_void_p), ("T", C.c_void_p), ("Tinv", C.c_void_p), ("xyzi", C.c_void_p), ("point_off", C.c_void_p),
+                ("n_aggregate", C.c_int32), ("pad", C.c_int32), ("imgs", C.c_void_p), ("desc", C.POINTER(PolarDesc)),
+                ("raw", C.POINTER(ScRawParams))]
+
+
 SC_CANDIDATE_DTYPE = np.dtype([("min_dist", "<f8"), ("min_dist_sc", "<f8"), ("min_dist_odom", "<f8"),
                                ("yaw_diff_rad", "<f4"), ("nn_idx", "<i4"), ("argmin_shift", "<i4"), ("pad", "<i4"),
                                ("Taug", "<f8", (3,))])
@@ -335,6 +345,7 @@ EXPORTS = [
     "cfear_cen2019_order_audit",
     "cfear_scan_create_batch", "cfear_scan_batch_size", "cfear_scan_batch_get", "cfear_scan_batch_destroy",
     "cfear_odometry_replay_clouds", "cfear_odometry_replay",
+    "cfear_sc_detect_batch",
 ]
 REPLAY_AUDIT = 1                    # #define CFEAR_REPLAY_AUDIT
 
@@ -596,6 +607,7 @@ def lib():
                                                  C.POINTER(C.c_double), C.c_int32, vp, vp, vp]
     L.cfear_sc_detect_sequence.argtypes = [vp, C.POINTER(ScManagerParams), C.POINTER(ScNode), C.c_int32, C.c_int32, C.c_int32,
                                            vp, vp]
+    L.cfear_sc_detect_batch.argtypes = [vp, C.POINTER(ScManagerParams), C.POINTER(ScBatch), vp, vp]
     L.cfear_sc_manager_size.argtypes = [vp]
     L.cfear_sc_manager_destroy.argtypes = [vp]
     L.cfear_scan_closest_idx.argtypes = [vp, vp, C.c_int32, C.c_double, vp]

@@ -2609,6 +2609,102 @@ def sc_detect_sequence(clouds, poses_xyt=None, n_aggregate=1, n_detect=None, ids
     return [_sc_candidates(out[i, :n_out[i]]) for i in range(nd)]
 
 
+def _is_u8(x):
+    return str(getattr(x, "dtype", "")).endswith("uint8")
+
+
+def sc_flatten_graphs(graphs, ids=None):
+    """The flat tables of cfear_sc_batch from one (clouds, poses) or (sweeps, poses) pair per graph, built with NumPy: clouds
+    are float32 [m, 4] arrays (NumPy or torch CUDA, one per node), sweeps one uint8 [n, H, W] array or a list of [H, W]
+    ones; poses [n, 3] (x, y, theta).  ids: one array per graph (default 0, 1, ... in each).
+    -> dict(node_off, T, Tinv, ids, and xyzi + point_off or imgs), what sc_detect_batch takes as flat=."""
+    sizes = [len(g[1]) for g in graphs]
+    flat = dict(node_off=np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32))
+    poses = np.concatenate([np.zeros((0, 3))] + [np.asarray(g[1], np.float64).reshape(-1, 3) for g in graphs])
+    flat["T"], flat["Tinv"] = sc_node_affines(poses)
+    flat["ids"] = None if ids is None else np.concatenate([np.zeros(0, np.int32)] + [np.asarray(i, np.int32) for i in ids])
+    data = [g[0] for g, n in zip(graphs, sizes) if n > 0]
+    for d, n in zip(data, [n for n in sizes if n > 0]):
+        if len(d) != n:
+            raise ValueError("one pose per cloud or sweep")
+    if data and (_is_u8(data[0]) or _is_u8(data[0][0])):
+        host = isinstance(data[0] if _is_u8(data[0]) else data[0][0], np.ndarray)
+        if not host:
+            import torch
+        data = [d if _is_u8(d) else (np.stack(d) if host else torch.stack(list(d))) for d in data]
+        flat["imgs"] = data[0] if len(data) == 1 else (np.concatenate(data) if host else torch.cat(data))
+        return flat
+    clouds = [c for d in data for c in d]
+    flat["point_off"] = np.concatenate([[0], np.cumsum([c.shape[0] for c in clouds])]).astype(np.int64)
+    if all(isinstance(c, np.ndarray) for c in clouds):
+        flat["xyzi"] = np.concatenate([np.zeros((0, 4), np.float32)] + [np.asarray(c, np.float32).reshape(-1, 4) for c in clouds])
+    else:
+        import torch
+        flat["xyzi"] = torch.cat([c.reshape(-1, 4) for c in clouds])
+    return flat
+
+
+def sc_detect_batch(graphs=None, n_aggregate=1, n_detect=None, ids=None, par=None, raw_par=None, ctx=None, device_out=False,
+                    flat=None, records=False, **manager_kw):
+    """Scan Context candidate proposal for a batch of graphs in one call (cfear_sc_detect_batch): for every graph what a fresh
+    RSCManagerNative returns when the graph's nodes 0 .. n_detect[g] - 1 (default: all) are added in order -- with their
+    local maps (n_aggregate) in cloud mode, with their raw sweeps in raw mode -- each detected right after it is added.
+    graphs: see sc_flatten_graphs; or flat = its result (pre-flattened arrays; host clouds cross in ONE copy).  raw_par:
+    cfear_sc_raw_params of raw mode (default: an azimuth-major sweep, transpose = 1).  manager_kw: as sc_detect_sequence.
+    -> one list per graph of per-node candidate lists (nn_idx counts within the graph); with device_out the record tensor
+    (torch CUDA uint8 [nodes, n_candidates, 64], viewable as _lib.SC_CANDIDATE_DTYPE on the host), the counts (torch CUDA
+    int32 [nodes]) and the first row of every graph (NumPy [graphs + 1]); with records the same three on the host (the
+    records as a _lib.SC_CANDIDATE_DTYPE array [nodes, n_candidates])."""
+    ctx = ctx or default_context()
+    p = sc_manager_params(par, **manager_kw)
+    if flat is None:
+        flat = sc_flatten_graphs(graphs, ids)
+    node_off = np.ascontiguousarray(flat["node_off"], np.int32)
+    G, N = node_off.shape[0] - 1, int(node_off[-1])
+    nd = np.diff(node_off).astype(np.int32) if n_detect is None else np.ascontiguousarray(n_detect, np.int32)
+    T = np.ascontiguousarray(flat["T"], np.float64)
+    b = L.ScBatch()
+    b.n_graphs, b.node_off, b.n_detect, b.T = G, node_off.ctypes.data, nd.ctypes.data, T.ctypes.data
+    keep = [T]
+    if flat.get("ids") is not None:
+        keep.append(np.ascontiguousarray(flat["ids"], np.int32))
+        b.ids = keep[-1].ctypes.data
+    if "imgs" in flat:
+        b.mode = L.SC_NODES_RAW
+        raw = raw_par if raw_par is not None else sc_raw_params(transpose=1)
+        d, ptr, k = _image_desc(flat["imgs"])
+        if len(flat["imgs"].shape) == 2:
+            d.batch = 1
+        keep += [raw, d, k]
+        b.imgs, b.desc, b.raw = ptr, C.pointer(d), C.pointer(raw)
+        dev_in = [flat["imgs"]]
+    else:
+        b.mode, b.n_aggregate = L.SC_NODES_CLOUD, int(n_aggregate)
+        Ti = np.ascontiguousarray(flat["Tinv"], np.float64)
+        po = np.ascontiguousarray(flat["point_off"], np.int64)
+        xyzi = flat["xyzi"] if _is_torch(flat["xyzi"]) else np.ascontiguousarray(flat["xyzi"], np.float32)
+        keep += [Ti, po, xyzi]
+        b.Tinv, b.point_off, b.xyzi = Ti.ctypes.data, po.ctypes.data, _ptr(xyzi)[0]
+        dev_in = [xyzi]
+    if nd.shape[0] != G:
+        raise ValueError("one n_detect per graph")
+    D, nc = int(nd.sum()), max(int(p.n_candidates), 1)
+    if device_out:
+        import torch
+        out = torch.zeros((max(D, 1), nc, 64), dtype=torch.uint8, device="cuda:%d" % ctx.device)
+        n_out = torch.zeros(max(D, 1), dtype=torch.int32, device=out.device)
+    else:
+        out = np.zeros((max(D, 1), nc), L.SC_CANDIDATE_DTYPE)
+        n_out = np.zeros(max(D, 1), np.int32)
+    _torch_ready(ctx, out, n_out, *dev_in)
+    ctx.check(ctx._lib.cfear_sc_detect_batch(ctx.h, C.byref(p), C.byref(b), _ptr(out)[0], _ptr(n_out)[0]))
+    del keep
+    row_off = np.concatenate([[0], np.cumsum(nd)])
+    if device_out or records:
+        return out[:D], n_out[:D], row_off
+    return [[_sc_candidates(out[i, :n_out[i]]) for i in range(row_off[g], row_off[g + 1])] for g in range(G)]
+
+
 class RSCManagerNative:
     """The same manager as a library object (cfear_sc_manager_*): database in HBM, policy in the library's C++.
     Same two calls as RSCManager; what a C++ host uses (include/cfear_hip.hpp)."""

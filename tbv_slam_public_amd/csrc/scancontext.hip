@@ -19,7 +19,9 @@
 #include <algorithm>
 #include <cfloat>
 #include <climits>
+#include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <vector>
 
 #include "common.hpp"
@@ -255,26 +257,25 @@ struct ScSearchArgs {
 
 __device__ __forceinline__ bool sc_key_less(float da, int ia, float db, int ib) { return da < db || (da == db && ia < ib); }
 
-__global__ __launch_bounds__(kScSearchThreads) void sc_keysearch_kernel(const ScSearchArgs a) {
+// One search by the whole workgroup, shared by sc_keysearch_kernel and sc_batch_keysearch_kernel.  dbkeys: the ring keys the
+// query may see, [.][n_aug][R] from its database's node 0; qkey: the query's own key; srow: its odometry similarities by
+// database index (odometry mode).  The n_out pairs go to `off`: (qi, db_base + database index).
+__device__ __forceinline__ void sc_keysearch_body(const double* dbkeys, const double* qkey, const double* srow, int L, int K, int R,
+                                                  int n_aug, int odometry, int off, int qi, int db_base, int32_t* pairs,
+                                                  double* pair_sim) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  const int t = blockIdx.x, k = blockIdx.y, R = a.R, K = a.k_sel;
-  if (a.pair_off[t * a.n_aug + k] < 0) return;
-  const int off = a.pair_off[t * a.n_aug + k] - a.pair_base;
-  const int L = a.n_search[t * a.n_aug + k];
   float* ld = (float*)smem;                          // [K][threads] distances of every thread's list
   int* li = (int*)(ld + (size_t)K * kScSearchThreads);   // [K][threads] indices
   float* qk = (float*)(li + (size_t)K * kScSearchThreads);   // [R + 1] query key
   float* rd = qk + R + 1;                            // [waves] per-wave minimum
   int* ri = (int*)(rd + kScSearchThreads / 64);
-  const int i = a.q0 + t;
-  for (int r = threadIdx.x; r < R; r += blockDim.x) qk[r] = (float)a.ringkey[((size_t)i * a.n_aug + k) * R + r];   // eig2stdvec
+  for (int r = threadIdx.x; r < R; r += blockDim.x) qk[r] = (float)qkey[r];   // eig2stdvec
   __syncthreads();
-  const double* srow = a.odometry ? a.sim + (size_t)t * a.ld : nullptr;
   int cnt = 0;
   for (int idx = threadIdx.x; idx < L; idx += blockDim.x) {
-    const double* kk = a.ringkey + (size_t)idx * a.n_aug * R;
+    const double* kk = dbkeys + (size_t)idx * n_aug * R;
     float d = 0.f;
-    if (a.odometry) {                                // L2norm (:250-257)
+    if (odometry) {                                  // L2norm (:250-257)
       for (int r = 0; r < R; r++) {
         const double err = (double)(qk[r] - (float)kk[r]);
         d = (float)((double)d + err * err);
@@ -301,7 +302,7 @@ __global__ __launch_bounds__(kScSearchThreads) void sc_keysearch_kernel(const Sc
     li[pos * kScSearchThreads + threadIdx.x] = idx;
     cnt = min(cnt + 1, K);
   }
-  const int n_out = a.odometry ? min(L, K) : K;
+  const int n_out = odometry ? min(L, K) : K;
   int head = 0;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int c = 0; c < n_out; c++) {
@@ -322,11 +323,172 @@ __global__ __launch_bounds__(kScSearchThreads) void sc_keysearch_kernel(const Sc
     if (head < cnt && li[head * kScSearchThreads + threadIdx.x] == bi) head++;
     if (threadIdx.x == 0) {
       const int db_idx = bi == INT_MAX ? 0 : bi;      // vanilla: a tree with fewer points leaves node 0 in place
-      a.pairs[2 * (off + c)] = t * a.n_aug + k;
-      a.pairs[2 * (off + c) + 1] = db_idx;
-      a.pair_sim[off + c] = a.odometry ? srow[db_idx] : 0.0;
+      pairs[2 * (off + c)] = qi;
+      pairs[2 * (off + c) + 1] = db_base + db_idx;
+      pair_sim[off + c] = odometry ? srow[db_idx] : 0.0;
     }
   }
+}
+
+__global__ __launch_bounds__(kScSearchThreads) void sc_keysearch_kernel(const ScSearchArgs a) {
+  const int t = blockIdx.x, k = blockIdx.y;
+  if (a.pair_off[t * a.n_aug + k] < 0) return;
+  sc_keysearch_body(a.ringkey, a.ringkey + ((size_t)(a.q0 + t) * a.n_aug + k) * a.R, a.odometry ? a.sim + (size_t)t * a.ld : nullptr,
+                    a.n_search[t * a.n_aug + k], a.k_sel, a.R, a.n_aug, a.odometry, a.pair_off[t * a.n_aug + k] - a.pair_base,
+                    t * a.n_aug + k, 0, a.pairs, a.pair_sim);
+}
+
+// ---- a batch of graphs (cfear_sc_detect_batch) ----------------------------------------------------
+// The detected nodes of every graph, one behind the other, are the queries d = 0 .. D - 1; a chunk [q0, q0 + nq) of them may
+// start and end inside a graph.  Every query carries its graph: first (the query index of the graph's node 0; positions,
+// segments and ring keys are indexed by query), db_base (the descriptor index of the graph's node 0 in the database) and
+// row_off, the start of its row of trav / sim: query d with i = d - first[d] earlier nodes owns i entries, so the rows of a
+// chunk are packed one behind the other (a prefix sum of i) instead of a [nq][largest graph] rectangle.
+struct ScBatchTab {
+  const int32_t* first;              // [D]
+  const int32_t* db_base;            // [D]
+  const int32_t* center;             // [D] the query's node in the caller's node list
+  const long long* row_off;          // [D + 1]
+  const double2* pos;                // [D] Todom
+  const double* seg;                 // [D] |p_{d+1} - p_d| (unused at a graph's last node)
+  const int32_t* n_search;           // [D][n_aug]
+  const int32_t* pair_off;           // [D][n_aug] first pair (of the whole call); -1: no search
+  const int32_t* node_pairs;         // [D + 1] first pair of every query
+};
+
+// sc_travel_kernel's sums, back to the graph's first node: trav[row + s] is the sum down to node i - 1 - s
+__global__ __launch_bounds__(256) void sc_batch_travel_kernel(const ScBatchTab tb, int q0, int nq, double* trav) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nq) return;
+  const int d = q0 + t, g0 = tb.first[d], i = d - g0;
+  double* row = trav + (tb.row_off[d] - tb.row_off[q0]);
+  double s = 0.0;
+  for (int m = i - 1; m >= 0; m--) {
+    s += tb.seg[g0 + m];
+    row[i - 1 - m] = s;
+  }
+}
+
+// sc_odom_sim_kernel's terms against the graph's own earlier nodes: one workgroup per query, sim[row + idx]
+__global__ __launch_bounds__(256) void sc_batch_odom_sim_kernel(const ScBatchTab tb, const double* trav, int q0, double sigma,
+                                                                double* sim) {
+  const int d = q0 + blockIdx.x, g0 = tb.first[d], i = d - g0;
+  const long long ro = tb.row_off[d] - tb.row_off[q0];
+  const double2 pi = tb.pos[d];
+  for (int idx = threadIdx.x; idx < i; idx += blockDim.x) {
+    const double2 pj = tb.pos[g0 + idx];
+    const double est = hypot(pi.x - pj.x, pi.y - pj.y);
+    const double e5 = est - 5.0;
+    const double error = e5 < 0.0 ? 0.0 : e5;        // std::max(est - 5.0, 0.0)
+    const double rel = error / trav[ro + (i - 1 - idx)];
+    const double prob = exp(-rel * rel / (2 * sigma * sigma));
+    sim[ro + idx] = 1.0 - prob;
+  }
+}
+
+struct ScBatchSearchArgs {
+  ScBatchTab tb;
+  const double* ringkey;             // [D][n_aug][R]
+  const double* sim;                 // odometry mode: the chunk's packed rows
+  int pair_base, q0, R, n_aug, k_sel, odometry;
+  int query_is_node;                 // raw mode: the query descriptor is the database entry of the node
+  int32_t* pairs;
+  double* pair_sim;
+};
+
+// one workgroup per (query, augmentation): sc_keysearch_kernel over the graph's own eligible prefix
+__global__ __launch_bounds__(kScSearchThreads) void sc_batch_keysearch_kernel(const ScBatchSearchArgs a) {
+  const int t = blockIdx.x, k = blockIdx.y, d = a.q0 + t;
+  const int po = a.tb.pair_off[d * a.n_aug + k];
+  if (po < 0) return;
+  const int g0 = a.tb.first[d];
+  sc_keysearch_body(a.ringkey + (size_t)g0 * a.n_aug * a.R, a.ringkey + ((size_t)d * a.n_aug + k) * a.R,
+                    a.odometry ? a.sim + (a.tb.row_off[d] - a.tb.row_off[a.q0]) : nullptr, a.tb.n_search[d * a.n_aug + k], a.k_sel, a.R,
+                    a.n_aug, a.odometry, po - a.pair_base, a.query_is_node ? a.tb.db_base[d] + (d - g0) : t * a.n_aug + k,
+                    a.tb.db_base[d], a.pairs, a.pair_sim);
+}
+
+// ring keys of the raw descriptors of the queries (no sector keys: the distance kernel forms its own)
+__global__ __launch_bounds__(256) void sc_batch_raw_keys_kernel(const double* db, const ScBatchTab tb, int R, int S, double* ringkey) {
+  const int d = blockIdx.x;
+  sc_keys(db + (size_t)(tb.db_base[d] + (d - tb.first[d])) * R * S, R, S, ringkey + (size_t)d * R, nullptr);
+}
+
+// sc_rank_kernel: detectLoopClosureID's ranking (:300-322), one wavefront per query.  The query's pairs are contiguous, in
+// visiting order (augmentation, then search rank), at most kScMaxAug * kScMaxTreeK = 64 lanes x 8.  n_sel = min(n_candidates,
+// pairs) rounds each take the smallest remaining (min_dist, visiting position): what a stable sort of the growing list
+// followed by dropping the last entry leaves, as among equal min_dist the earlier-visited pair stays in front.  The lane that
+// owns the winner writes its 64-byte record; records past n_sel keep the zeros the caller's rows were cleared to.
+constexpr int kScRankPerLane = kScMaxAug * kScMaxTreeK / 64;
+
+struct ScRankArgs {
+  ScBatchTab tb;
+  const int32_t* pairs;
+  const double* dist;
+  const int32_t* shift;
+  const double* pair_sim;
+  int pair_base, q0, nq, n_aug, n_candidates, odometry;
+  double unit;                       // 360 / num_sector
+  double shift_y[kScMaxAug];
+  cfear_sc_candidate* out;           // [D][n_candidates]
+  int32_t* n_out;                    // [D]
+};
+
+__device__ __forceinline__ bool sc_rank_less(double da, int pa, double db, int pb) { return da < db || (!(db < da) && pa < pb); }
+
+__global__ __launch_bounds__(256) void sc_rank_kernel(const ScRankArgs a) {
+  const int lane = threadIdx.x & 63, t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= a.nq) return;                             // the whole wavefront
+  const int d = a.q0 + t;
+  const int p0 = a.tb.node_pairs[d] - a.pair_base, P = a.tb.node_pairs[d + 1] - a.tb.node_pairs[d];
+  const int n_sel = min(a.n_candidates, P);
+  double md[kScRankPerLane];
+#pragma unroll
+  for (int j = 0; j < kScRankPerLane; j++) {
+    const int pos = lane + 64 * j;
+    md[j] = 0.0;
+    if (pos < P) md[j] = a.odometry ? a.dist[p0 + pos] + a.pair_sim[p0 + pos] : a.dist[p0 + pos];
+  }
+  uint32_t taken = 0;
+  for (int c = 0; c < n_sel; c++) {
+    double bd = 0.0;
+    int bp = INT_MAX;
+#pragma unroll
+    for (int j = 0; j < kScRankPerLane; j++) {
+      const int pos = lane + 64 * j;
+      if (pos < P && !((taken >> j) & 1u) && (bp == INT_MAX || sc_rank_less(md[j], pos, bd, bp))) { bd = md[j]; bp = pos; }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      const double od = __shfl_xor(bd, o);
+      const int op = __shfl_xor(bp, o);
+      if (op != INT_MAX && (bp == INT_MAX || sc_rank_less(od, op, bd, bp))) { bd = od; bp = op; }
+    }
+    bp = __shfl(bp, 0);                              // one answer for the wavefront, whatever a NaN did to the order
+    if (bp == INT_MAX) break;
+    if ((bp & 63) != lane) continue;
+    taken |= 1u << (bp >> 6);
+    const int p = p0 + bp;
+    double shift_y = 0.0;                            // of the augmentation whose pairs hold p: the last that starts at or before it
+#pragma unroll
+    for (int kk = 0; kk < kScMaxAug; kk++) {
+      const int po = kk < a.n_aug ? a.tb.pair_off[d * a.n_aug + kk] : -1;
+      if (po >= 0 && po - a.pair_base <= p) shift_y = a.shift_y[kk];
+    }
+    const int shift = a.shift[p];
+    const double dist = a.dist[p], osim = a.odometry ? a.pair_sim[p] : 0.0;
+    cfear_sc_candidate r;
+    r.min_dist_sc = dist;
+    r.min_dist_odom = osim;
+    r.min_dist = a.odometry ? dist + osim : dist;
+    const float ang = (float)(shift * a.unit);
+    r.yaw_diff_rad = (float)(ang * M_PI / 180.0);
+    r.nn_idx = a.pairs[2 * p + 1] - a.tb.db_base[d];
+    r.argmin_shift = shift;
+    r.pad = 0;
+    r.Taug[0] = 0.0; r.Taug[1] = shift_y; r.Taug[2] = 0.0;
+    a.out[(size_t)d * a.n_candidates + c] = r;
+  }
+  if (lane == 0) a.n_out[d] = n_sel;
 }
 
 struct ScDistArgs {
@@ -1400,4 +1562,278 @@ extern "C" int cfear_sc_detect_sequence(cfear_ctx* ctx, const cfear_sc_manager_p
     for (size_t j = 0; j < similar.size(); j++) out[(size_t)i * par->n_candidates + j] = similar[j];
   }
   return CFEAR_OK;
+}
+
+// ---- cfear_sc_detect_batch: the same for a batch of graphs, in either descriptor mode, ranked on the device -----------------
+namespace {
+static_assert(sizeof(cfear_sc_batch) == 96, "cfear_sc_batch is 96 bytes (include/cfear_hip.h)");
+
+// everything the call refuses, decided on the host; ctx may be null.  D: the detected nodes of the whole batch
+int check_sc_batch(cfear_ctx* ctx, const cfear_sc_manager_params* par, const cfear_sc_batch* b, const cfear_sc_candidate* out,
+                   const int32_t* n_out, int64_t* D) {
+  if (!par || !b) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
+  CFEAR_CHECK(check_sc_params(ctx, &par->sc));
+  if (par->num_candidates_from_tree < 1 || par->n_candidates < 1 || !(par->odom_sigma_error > 0))
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "bad scan-context manager parameters");
+  if (par->num_candidates_from_tree > kScMaxTreeK)
+    return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "num_candidates_from_tree %d > %d", par->num_candidates_from_tree, kScMaxTreeK);
+  if (b->mode != CFEAR_SC_NODES_CLOUD && b->mode != CFEAR_SC_NODES_RAW)
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "unknown node mode %d", (int)b->mode);
+  const int G = b->n_graphs;
+  if (G < 0 || (G > 0 && !b->node_off)) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null node_off");
+  *D = 0;
+  if (G == 0) return CFEAR_OK;
+  if (b->node_off[0] != 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "graph 0: node_off[0] must be 0");
+  for (int g = 0; g < G; g++) {
+    if (b->node_off[g + 1] < b->node_off[g]) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "graph %d: node_off decreases", g);
+    const int n = b->node_off[g + 1] - b->node_off[g], nd = b->n_detect ? b->n_detect[g] : n;
+    if (nd < 0 || nd > n)
+      return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "graph %d: n_detect %d must be in [0, nodes = %d]", g, nd, n);
+    *D += nd;
+  }
+  const int64_t N = b->node_off[G];
+  if (N > 0 && !b->T) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null T");
+  if (b->ids)
+    for (int g = 0; g < G; g++)
+      for (int i = b->node_off[g] + 1; i < b->node_off[g + 1]; i++)
+        if (b->ids[i] <= b->ids[i - 1])
+          return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "graph %d, node %d: ids must increase strictly", g, i - b->node_off[g]);
+  if (b->mode == CFEAR_SC_NODES_CLOUD) {
+    if (b->n_aggregate < 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "n_aggregate must be >= 0");
+    if (N > 0 && (!b->Tinv || !b->point_off)) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null Tinv or point_off");
+    if (N > 0 && b->point_off[0] < 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "graph 0, node 0: point_off is negative");
+    for (int g = 0; g < G; g++)
+      for (int i = b->node_off[g]; i < b->node_off[g + 1]; i++) {
+        const int64_t n = b->point_off[i + 1] - b->point_off[i];
+        if (n < 0 || n > INT32_MAX)
+          return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "graph %d, node %d: point_off decreases (or the cloud is past 2^31 points)",
+                                 g, i - b->node_off[g]);
+        if (n > 0 && !b->xyzi) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "graph %d, node %d: null cloud", g, i - b->node_off[g]);
+      }
+  } else {
+    if (N > 0 && (!b->imgs || !b->desc || !b->raw)) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null sweeps");
+    if (N > 0 && b->desc->batch != N)
+      return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "%d sweeps for %lld nodes", (int)b->desc->batch, (long long)N);
+  }
+  if (*D > INT32_MAX / (kScMaxAug * kScMaxTreeK)) return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "%lld detected nodes", (long long)*D);
+  if (*D > 0) {
+    if (!out || !n_out) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null output");
+    if (memory_kind({out, n_out}) < 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "out and n_out must share host or device memory");
+  }
+  return CFEAR_OK;
+}
+
+// first / last member of the local map of node c of the graph [nb, ne): the ids within n_aggregate of c's
+int2 sc_batch_members(const int32_t* ids, int nb, int ne, int c, int n_aggregate) {
+  if (!ids) return make_int2((int)std::max<int64_t>(nb, (int64_t)c - n_aggregate), (int)std::min<int64_t>(ne - 1, (int64_t)c + n_aggregate));
+  const int64_t lo_id = (int64_t)ids[c] - n_aggregate, hi_id = (int64_t)ids[c] + n_aggregate;
+  const int lo = (int)(std::lower_bound(ids + nb, ids + c, lo_id, [](int32_t v, int64_t w) { return (int64_t)v < w; }) - ids);
+  const int hi = (int)(std::upper_bound(ids + c, ids + ne, hi_id, [](int64_t w, int32_t v) { return w < (int64_t)v; }) - ids) - 1;
+  return make_int2(lo, hi);
+}
+}  // namespace
+
+extern "C" int cfear_sc_detect_batch(cfear_ctx* ctx, const cfear_sc_manager_params* par, const cfear_sc_batch* batch,
+                                     cfear_sc_candidate* out, int32_t* n_out) {
+  int64_t D64 = 0;
+  const auto t_start = std::chrono::steady_clock::now();
+  CFEAR_CHECK(check_sc_batch(ctx, par, batch, out, n_out, &D64));
+  if (!ctx) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null context");
+  if (D64 == 0) return CFEAR_OK;
+  const cfear_sc_batch& b = *batch;
+  const bool raw = b.mode == CFEAR_SC_NODES_RAW, odo = par->odometry_coupled_closure != 0;
+  const int G = b.n_graphs, N = b.node_off[G], D = (int)D64;
+  const int R = par->sc.num_ring, S = par->sc.num_sector, cells = R * S, K = par->num_candidates_from_tree;
+  const std::vector<double> shifts = sc_aug_shifts(!raw && par->augment_sc != 0);
+  const int A = (int)shifts.size();
+  // one table for the whole batch (uploaded once): the node records of the local maps, then the per-query arrays
+  size_t tab_bytes = 0;
+  auto take = [&](size_t bytes) { const size_t o = tab_bytes; tab_bytes = (tab_bytes + bytes + 15) & ~(size_t)15; return o; };
+  const size_t o_nodes = take(raw ? 0 : (size_t)N * sizeof(ScMapNode)), o_first = take((size_t)D * 4), o_dbb = take((size_t)D * 4),
+               o_center = take((size_t)D * 4), o_mem = take((size_t)D * 8), o_row = take((size_t)(D + 1) * 8),
+               o_pos = take((size_t)D * 16), o_seg = take((size_t)D * 8), o_ns = take((size_t)D * A * 4),
+               o_po = take((size_t)D * A * 4), o_np = take((size_t)(D + 1) * 4);
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  HostStage st(ctx, kWsScSequence);
+  char* h = (char*)st.record(tab_bytes);
+  int32_t *h_first = (int32_t*)(h + o_first), *h_dbb = (int32_t*)(h + o_dbb), *h_center = (int32_t*)(h + o_center);
+  int2* h_mem = (int2*)(h + o_mem);
+  long long* h_row = (long long*)(h + o_row);
+  double2* h_pos = (double2*)(h + o_pos);
+  double* h_seg = (double*)(h + o_seg);
+  int32_t *h_ns = (int32_t*)(h + o_ns), *h_po = (int32_t*)(h + o_po), *h_np = (int32_t*)(h + o_np);
+  // host policy, O(nodes), per graph: segment lengths, recent-node exclusion, the vanilla tree schedule (a counter and a
+  // tree per graph), every (query, augmentation)'s eligible prefix and its place in the pair list
+  // CFEAR_OPT_HOST_TIMELINE = 1: where the host spends the call, one line on stderr
+  double t_ms[5] = {0, 0, 0, 0, 0};
+  auto t_last = t_start;
+  auto lap = [&](int i) {
+    const auto now = std::chrono::steady_clock::now();
+    t_ms[i] += std::chrono::duration<double, std::milli>(now - t_last).count();
+    t_last = now;
+  };
+  int total = 0, max_len = 0;
+  {
+    int d0 = 0;
+    h_row[0] = 0;
+    for (int g = 0; g < G; g++) {
+      const int nb = b.node_off[g], ne = b.node_off[g + 1], nd = b.n_detect ? b.n_detect[g] : ne - nb;
+      auto px = [&](int i) { return b.T[(size_t)(nb + i) * 8 + 3]; };
+      auto py = [&](int i) { return b.T[(size_t)(nb + i) * 8 + 7]; };
+      for (int i = 0; i + 1 < nd; i++) h_seg[d0 + i] = std::hypot(px(i) - px(i + 1), py(i) - py(i + 1));
+      int counter = 0, tree_n = 0;
+      for (int i = 0; i < nd; i++) {
+        const int d = d0 + i;
+        h_first[d] = d0;
+        h_dbb[d] = raw ? nb : d0;
+        h_center[d] = nb + i;
+        if (!raw) h_mem[d] = sc_batch_members(b.ids, nb, ne, nb + i, b.n_aggregate);
+        h_pos[d] = make_double2(px(i), py(i));
+        h_row[d + 1] = h_row[d] + (odo ? i : 0);
+        h_np[d] = total;
+        for (int k = 0; k < A; k++) { h_ns[(size_t)d * A + k] = 0; h_po[(size_t)d * A + k] = -1; }
+        const int nex = sc_num_exclude_recent(i, par->distance_exclude_recent, [&](int j) { return h_seg[d0 + j]; });
+        if (i + 1 < nex + 1) continue;               // detectLoopClosureID's gate (:288-291)
+        for (int k = 0; k < A; k++) {
+          int L, cnt;
+          if (odo) { L = std::max(i - 1 - nex, 0); cnt = std::min(L, K); }
+          else { sc_tree_step(counter, tree_n, i + 1, nex); L = tree_n; cnt = K; }
+          h_ns[(size_t)d * A + k] = L;
+          if (cnt > 0) { h_po[(size_t)d * A + k] = total; total += cnt; }
+        }
+      }
+      max_len = std::max(max_len, nd);
+      d0 += nd;
+    }
+    h_np[D] = total;
+  }
+  lap(0);
+  // query chunks of the concatenated list: the chunk's query descriptors, its packed odometry rows and its pair list
+  const size_t per_query = (raw ? 0 : (size_t)A * cells * 8) + (odo ? (size_t)2 * max_len * 8 : 0) + (size_t)A * K * (8 + 8 + 4 + 8);
+  int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)D, kScSeqBudget / per_query));
+  if (ctx->opt[CFEAR_OPT_SC_QUERY_CHUNK] > 0) chunk = (int)std::min<int64_t>(chunk, ctx->opt[CFEAR_OPT_SC_QUERY_CHUNK]);
+  int max_chunk_pairs = 1;
+  long long max_rows = 1;
+  for (int q0 = 0; q0 < D; q0 += chunk) {
+    const int q1 = std::min(D, q0 + chunk);
+    max_chunk_pairs = std::max(max_chunk_pairs, h_np[q1] - h_np[q0]);
+    max_rows = std::max(max_rows, h_row[q1] - h_row[q0]);
+  }
+  const size_t n_db = raw ? (size_t)N : (size_t)D;   // raw mode describes every sweep in one launch, cloud mode the detected nodes
+  const size_t nc = (size_t)par->n_candidates;
+  char* d_tab;
+  const float* d_xyzi = nullptr;
+  double *d_db, *d_rk, *d_q = nullptr, *d_trav = nullptr, *d_sim = nullptr, *d_dist, *d_psim;
+  int32_t *d_pairs, *d_shift, *d_nout;
+  cfear_sc_candidate* d_out;
+  if (!raw) st.in(d_xyzi, b.xyzi, (size_t)b.point_off[N] * 16);
+  st.piece(d_tab, tab_bytes);
+  st.piece(d_db, n_db * cells * 8);
+  st.piece(d_rk, (size_t)D * A * R * 8);
+  if (!raw) st.piece(d_q, (size_t)chunk * A * cells * 8);
+  if (odo) { st.piece(d_trav, (size_t)max_rows * 8); st.piece(d_sim, (size_t)max_rows * 8); }
+  st.piece(d_pairs, (size_t)max_chunk_pairs * 8);
+  st.piece(d_dist, (size_t)max_chunk_pairs * 8);
+  st.piece(d_shift, (size_t)max_chunk_pairs * 4);
+  st.piece(d_psim, (size_t)max_chunk_pairs * 8);
+  st.out(d_out, out, (size_t)D * nc * sizeof(cfear_sc_candidate));   // device rows are written in place
+  st.out(d_nout, n_out, (size_t)D * 4);
+  CFEAR_CHECK(st.carve());
+  lap(1);
+  // raw mode: every sweep's descriptor, straight into the database; what cfear_sc_raw_descriptors refuses is refused here,
+  // before the first launch of this call
+  if (raw) CFEAR_CHECK(cfear_sc_raw_descriptors(ctx, b.imgs, b.desc, &par->sc, b.raw, d_db, nullptr, nullptr));
+  if (!raw) {
+    ScMapNode* hn = (ScMapNode*)(h + o_nodes);
+    for (int i = 0; i < N; i++) {
+      hn[i].xyzi = (const float4*)d_xyzi + b.point_off[i];
+      hn[i].n = (int32_t)(b.point_off[i + 1] - b.point_off[i]);
+      hn[i].pad = 0;
+      memcpy(hn[i].T, b.T + (size_t)i * 8, 64);
+      memcpy(hn[i].Tinv, b.Tinv + (size_t)i * 8, 64);
+    }
+  }
+  CFEAR_CHECK(st.upload(d_tab, h, tab_bytes));
+  lap(2);
+  CFEAR_HIP_CHECK(ctx, hipMemsetAsync(d_out, 0, (size_t)D * nc * sizeof(cfear_sc_candidate), ctx->stream));
+  CFEAR_HIP_CHECK(ctx, hipMemsetAsync(d_nout, 0, (size_t)D * 4, ctx->stream));
+  ScBatchTab tb{};
+  tb.first = (const int32_t*)(d_tab + o_first); tb.db_base = (const int32_t*)(d_tab + o_dbb);
+  tb.center = (const int32_t*)(d_tab + o_center); tb.row_off = (const long long*)(d_tab + o_row);
+  tb.pos = (const double2*)(d_tab + o_pos); tb.seg = (const double*)(d_tab + o_seg);
+  tb.n_search = (const int32_t*)(d_tab + o_ns); tb.pair_off = (const int32_t*)(d_tab + o_po);
+  tb.node_pairs = (const int32_t*)(d_tab + o_np);
+  ScMapArgs ma{};
+  ma.nodes = (const ScMapNode*)(d_tab + o_nodes);
+  ma.bin = sc_bin(&par->sc);
+  ma.n_aug = A;
+  for (int k = 0; k < kScMaxAug; k++) ma.shift_y[k] = k < A ? shifts[k] : 0.0;
+  if (raw) {
+    {
+      ProfScope ps(ctx, "sc_raw_keys");
+      hipLaunchKernelGGL(sc_batch_raw_keys_kernel, dim3(D), dim3(256), 0, ctx->stream, d_db, tb, R, S, d_rk);
+    }
+    CFEAR_HIP_CHECK(ctx, hipGetLastError());
+  }
+  const size_t search_lds = (size_t)K * kScSearchThreads * 8 + (size_t)(R + 1) * 4 + (kScSearchThreads / 64) * 8;
+  CFEAR_CHECK(cfear_allow_lds(ctx, (const void*)sc_batch_keysearch_kernel, search_lds));
+  for (int q0 = 0; q0 < D; q0 += chunk) {
+    const int nq = std::min(chunk, D - q0);
+    const int p0 = h_np[q0], np = h_np[q0 + nq] - p0;
+    if (!raw) {
+      ma.center = tb.center + q0;
+      ma.members = (const int2*)(d_tab + o_mem) + q0;
+      ma.desc = d_q;
+      ma.db = d_db + (size_t)q0 * cells;
+      ma.ringkey = d_rk + (size_t)q0 * A * R;
+      ma.sectorkey = nullptr;
+      CFEAR_CHECK(sc_local_map_launch(ctx, ma, nq));
+    }
+    if (np == 0) continue;
+    if (odo) {
+      {
+        ProfScope ps(ctx, "sc_odom_terms");
+        hipLaunchKernelGGL(sc_batch_travel_kernel, dim3((nq + 255) / 256), dim3(256), 0, ctx->stream, tb, q0, nq, d_trav);
+        hipLaunchKernelGGL(sc_batch_odom_sim_kernel, dim3(nq), dim3(256), 0, ctx->stream, tb, (const double*)d_trav, q0,
+                           par->odom_sigma_error, d_sim);
+      }
+      CFEAR_HIP_CHECK(ctx, hipGetLastError());
+    }
+    ScBatchSearchArgs sa{};
+    sa.tb = tb;
+    sa.ringkey = d_rk;
+    sa.sim = d_sim;
+    sa.pair_base = p0;
+    sa.q0 = q0; sa.R = R; sa.n_aug = A; sa.k_sel = K; sa.odometry = odo ? 1 : 0; sa.query_is_node = raw ? 1 : 0;
+    sa.pairs = d_pairs;
+    sa.pair_sim = d_psim;
+    {
+      ProfScope ps(ctx, "sc_keysearch");
+      hipLaunchKernelGGL(sc_batch_keysearch_kernel, dim3(nq, A), dim3(kScSearchThreads), search_lds, ctx->stream, sa);
+    }
+    CFEAR_HIP_CHECK(ctx, hipGetLastError());
+    ScDistArgs da{};
+    da.desc_q = raw ? d_db : d_q; da.desc_c = d_db; da.pairs = d_pairs; da.dist = d_dist; da.shift = d_shift;
+    CFEAR_CHECK(sc_distance_launch(ctx, da, np, &par->sc));
+    ScRankArgs ra{};
+    ra.tb = tb;
+    ra.pairs = d_pairs; ra.dist = d_dist; ra.shift = d_shift; ra.pair_sim = d_psim;
+    ra.pair_base = p0; ra.q0 = q0; ra.nq = nq; ra.n_aug = A; ra.n_candidates = par->n_candidates; ra.odometry = odo ? 1 : 0;
+    ra.unit = 360.0 / (double)S;
+    for (int k = 0; k < kScMaxAug; k++) ra.shift_y[k] = k < A ? shifts[k] : 0.0;
+    ra.out = d_out; ra.n_out = d_nout;
+    {
+      ProfScope ps(ctx, "sc_rank");
+      hipLaunchKernelGGL(sc_rank_kernel, dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, ra);
+    }
+    CFEAR_HIP_CHECK(ctx, hipGetLastError());
+  }
+  lap(3);
+  const int rc = st.finish();
+  lap(4);
+  if (ctx->opt[CFEAR_OPT_HOST_TIMELINE])
+    fprintf(stderr, "cfear_sc_detect_batch host timeline: %d graphs, %d detected nodes, %d pairs, %d-query chunks: checks + policy tables %.3f ms, "
+            "workspace + staged inputs %.3f ms, node table + upload %.3f ms, launches %.3f ms, drain + read-back %.3f ms\n",
+            G, D, total, chunk, t_ms[0], t_ms[1], t_ms[2], t_ms[3], t_ms[4]);
+  return rc;
 }
