@@ -168,7 +168,18 @@ __device__ __forceinline__ void kstrong_row(const KStrongArgs& a, const int r, c
 
   // The row lives on in LDS: the (rare) later passes over it re-read it from there instead of keeping 4 NCHUNK
   // registers alive across the whole kernel (occupancy: 8 wavefronts per SIMD need <= 64 VGPRs).
+  // Each re-read stands behind a compiler barrier: the row does not change, so without one the compiler lifts the reads
+  // -- and the masked copies of every word that the byte compares start from -- out of the loop that re-tests the row,
+  // and holds the whole unrolled compaction's words at once: 48 registers more than 7 wavefronts per SIMD leave, which went
+  // to scratch memory (and a kernel that declares any is dispatched with a private segment on every wavefront).
+  auto reload_chunk = [&](const int c, uint32_t (&x)[4]) {
+    asm volatile("" ::: "memory");
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (!STAGED || (c * 64 + lane) * 16 < cols16) v = *(const uint4*)(rowbuf + (c * 64 + lane) * 16);
+    x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+  };
   auto reload_row = [&](uint32_t (&x)[NCHUNK * 4]) {
+    asm volatile("" ::: "memory");
 #pragma unroll
     for (int c = 0; c < NCHUNK; c++) {
       uint4 v = make_uint4(0, 0, 0, 0);
@@ -301,11 +312,10 @@ __device__ __forceinline__ void kstrong_row(const KStrongArgs& a, const int r, c
     //     Invariant: c_lo = #(>= lo) >= k > c_hi = #(>= hi), so on exit without a trial in [k, 256] the cut is T = lo with
     //     c_lo >= k > c_hi.  A trial is tested for "< k" FIRST: k may exceed 256 (kMaxK = 1024), and a count in (256, k) is
     //     below the cut, not above it (every row with k > 256 ends here, exactly).
-    uint32_t bt[NCHUNK];
-    int t_lane = c_lane, t_incl = c_incl, n_c = n_ge;
-#pragma unroll
-    for (int c = 0; c < NCHUNK; c++) bt[c] = bm[c];
-    bool exact = false;
+    // The bitmaps of the trial that lands in [k, 256] go straight into the scatter tables in LDS (scatter_prepare): kept in
+    // registers until the loop's end they were part of what went to scratch memory.
+    int n_c = n_ge;
+    bool exact = false, prepared = false;
     if (n_ge > 256) {
       int lo = a.u_zmin, c_lo = n_ge, hi = 256, c_hi = 0;
       bool first = true;
@@ -318,8 +328,14 @@ __device__ __forceinline__ void kstrong_row(const KStrongArgs& a, const int r, c
         {
           uint32_t wx[NCHUNK * 4];
           reload_row(wx);
-          if (mid & 0x80) candidate_bitmaps<NCHUNK, MASK, true>(wx, tm4, a.cols, lane, bx);
-          else candidate_bitmaps<NCHUNK, MASK, false>(wx, tm4, a.cols, lane, bx);
+          if (mid & 0x80) candidate_bitmaps<NCHUNK, false, true>(wx, tm4, a.cols, lane, bx);
+          else candidate_bitmaps<NCHUNK, false, false>(wx, tm4, a.cols, lane, bx);
+          // mid > z_min: a bin that passes the trial passes z_min too, so the candidates' bitmap carries the byte validity
+          // (one AND per chunk; the sixteen validity masks, hoisted out of this loop, were the MASK forms' scratch memory)
+          if (MASK) {
+#pragma unroll
+            for (int c = 0; c < NCHUNK; c++) bx[c] &= bm[c];
+          }
         }
         int x_lane = 0;
 #pragma unroll
@@ -329,9 +345,8 @@ __device__ __forceinline__ void kstrong_row(const KStrongArgs& a, const int r, c
         if (cnt < k) { hi = mid; c_hi = cnt; }
         else if (cnt > 256) { lo = mid; c_lo = cnt; }
         else {
-#pragma unroll
-          for (int c = 0; c < NCHUNK; c++) bt[c] = bx[c];
-          t_lane = x_lane; t_incl = x_incl; n_c = cnt;
+          scatter_prepare(bx, x_lane, x_incl);
+          n_c = cnt; prepared = true;
           break;
         }
       }
@@ -341,7 +356,7 @@ __device__ __forceinline__ void kstrong_row(const KStrongArgs& a, const int r, c
       // (b) 64 < n_c <= 256 candidates: one key per lane and round (registers), an LDS histogram of the keys'
       //     intensities -> T; the keys >= T (the survivors plus the ties at the cut, <= 64 unless a plateau is
       //     wider) are packed into list[] by ballot and cut by rank below -- the reference's tie rule.
-      scatter_prepare(bt, t_lane, t_incl);
+      if (!prepared) scatter_prepare(bm, c_lane, c_incl);
       scatter_carry = 0;
       uint32_t kr[4];
       bool kv[4];
@@ -372,8 +387,6 @@ __device__ __forceinline__ void kstrong_row(const KStrongArgs& a, const int r, c
       }
     }
     if (!have_list) {
-    uint32_t wt[NCHUNK * 4];
-    reload_row(wt);
     const int skip_eq = n_eq - (k - n_gt);         // drop the lowest-range ties: lexicographic (intensity, range)
     // ---- ordered compaction: all (> T) plus the (== T) bins of rank >= skip_eq in position order -----
     // (T >= z_min, so ">= T" implies candidacy; only the MASK variant needs the validity bits)
@@ -385,14 +398,15 @@ __device__ __forceinline__ void kstrong_row(const KStrongArgs& a, const int r, c
     int g_base = 0, e_base = 0;                    // survivors > T / bins == T before the current chunk
 #pragma unroll
     for (int c = 0; c < NCHUNK; c++) {
+      uint32_t wt[4];                              // one chunk of the row at a time
+      reload_chunk(c, wt);
       uint32_t mg[4], me[4];
       int cg = 0, ce = 0;
 #pragma unroll
       for (int d = 0; d < 4; d++) {
-        const int i = c * 4 + d;
         const uint32_t valid = MASK ? ((bm[c] << (3 - d)) & 0x80808080u) : 0x80808080u;
-        mg[d] = thr_gt > 255 ? 0u : (swar_ge(wt[i], tg4, tghi) & valid);
-        me[d] = swar_ge(wt[i], te4, tehi) & valid & ~mg[d];
+        mg[d] = thr_gt > 255 ? 0u : (swar_ge(wt[d], tg4, tghi) & valid);
+        me[d] = swar_ge(wt[d], te4, tehi) & valid & ~mg[d];
         cg += __popc(mg[d]);
         ce += __popc(me[d]);
       }
@@ -415,7 +429,7 @@ __device__ __forceinline__ void kstrong_row(const KStrongArgs& a, const int r, c
             const int e_sel_before = e_run > skip_eq ? e_run - skip_eq : 0;
             if (selected) {
               const int pos = (c * 64 + lane) * 16 + d * 4 + by;
-              list[g_run + e_sel_before] = (((wt[c * 4 + d] >> (8 * by)) & 0xffu) << 24) | (uint32_t)pos;
+              list[g_run + e_sel_before] = (((wt[d] >> (8 * by)) & 0xffu) << 24) | (uint32_t)pos;
             }
             if (is_eq) e_run++; else g_run++;
           }
@@ -551,9 +565,19 @@ __device__ __forceinline__ void kstrong_row(const KStrongArgs& a, const int r, c
 // per-wavefront LDS of a row: [raw row + 16-byte halos] (not STAGED) | scratch | list
 __host__ __device__ constexpr int kstrong_scratch_bytes(int nchunk) { return ((nchunk + 1) / 2 + 2) * 256 > 1024 ? ((nchunk + 1) / 2 + 2) * 256 : 1024; }
 
+// The sweep is issue-bound and feels where its code lands: CFEAR_KSTRONG_HEAD_PAD bytes (0 / 16 / 32 / 48) of s_nop at the kernel
+// head move it through the four placements.  A change to kstrong_row is measured at all four (EXPERIMENTS.md) and the best
+// one becomes the default here.
+#ifndef CFEAR_KSTRONG_HEAD_PAD
+#define CFEAR_KSTRONG_HEAD_PAD 0
+#endif
+
 template <int NCHUNK, bool VEC, bool MASK>
 __global__ __launch_bounds__(256, 7) void kstrongest_rows_kernel(const KStrongArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+#if CFEAR_KSTRONG_HEAD_PAD > 0
+  asm volatile(".rept %0\n\ts_nop 0\n\t.endr" ::"n"(CFEAR_KSTRONG_HEAD_PAD / 4));
+#endif
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int r = blockIdx.x * kRowsPerBlock + wave;          // grid = (row quads, images): no division
   if (r >= a.rows) return;                                  // no workgroup barrier below

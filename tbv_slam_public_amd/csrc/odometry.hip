@@ -60,7 +60,10 @@ constexpr int kDecodeHold = 32;
 
 struct cfear_odometry {
   cfear_ctx* ctx = nullptr;
-  Stream copy_stream;                  // uploads the registration jobs while the surface kernel runs (first: the buffers and events used on it go before it)
+  // Every small copy of a frame runs here, ordered against the kernel stream by events: job tables and image offsets go up
+  // while kernels run, the result block comes down while the next sweep runs.  A copy on the kernel stream itself makes the
+  // kernel behind it wait for a copy-engine round trip.  (first: the buffers and events used on it go before it)
+  Stream copy_stream;
   int n_streams = 0;
   cfear_polar_desc desc{};             // layout the filters see: rows = azimuths
   cfear_polar_desc in_desc{};          // layout of the caller's images (differs when par.rotate_ccw)
@@ -105,8 +108,16 @@ struct cfear_odometry {
   std::vector<int> last_slab;                // slab that holds each stream's last processed scan
   int cur_buf = 0;
   const uint8_t* prefetched = nullptr;       // polar pointer whose filter output sits in buffer cur_buf ^ 1
-  Event ev_results;
-  Event ev_jobs;                             // the job upload on copy_stream
+  Event ev_results;                          // this frame's read-back has landed (copy_stream)
+  Event ev_jobs;                             // the registration job upload on copy_stream
+  Event ev_surf_jobs;                        // the surface job upload on copy_stream
+  Event ev_offsets[2];                       // the image-offset upload of each filter buffer on copy_stream
+  Event ev_frame;                            // the frame's last work on the kernel stream: the read-back waits for it
+  // The read-back moves to the copy stream only when the kernel stream is a stream object.  A context may also be given one
+  // of the runtime's stream HANDLES (the null stream, hipStreamLegacy, hipStreamPerThread: small integers, not pointers), and
+  // hipStreamWaitEvent on another stream reads the stream an event was recorded on through that value.  Behind such a
+  // handle the read-back stays on the kernel stream, in front of the prefetched sweep.
+  bool readback_on_copy_stream = false;
   DevBuf<char> d_slabs, d_surf_jobs, d_reg_jobs;
   // what a frame returns to the host lives in ONE device block (and one pinned block): results | status | n_cells |
   // n_points -- one read-back per frame instead of four small copies queued between the matcher and the next sweep
@@ -138,10 +149,16 @@ struct cfear_odometry {
   std::vector<ScanView> views;         // [n_streams * slabs_per_stream]
 };
 
+// both streams idle: what an error exit and the teardown need before buffers are reused or freed
+static void drain_streams(cfear_odometry* od) {
+  if (od->copy_stream) (void)hipStreamSynchronize(od->copy_stream.get());
+  (void)hipStreamSynchronize(od->ctx->stream);
+}
+
 extern "C" int cfear_odometry_destroy(cfear_odometry* od) {
   if (!od) return CFEAR_OK;
   (void)hipSetDevice(od->ctx->device);
-  (void)hipStreamSynchronize(od->ctx->stream);
+  drain_streams(od);
   delete od;
   return CFEAR_OK;
 }
@@ -242,7 +259,10 @@ extern "C" int cfear_odometry_create(cfear_ctx* ctx, int32_t n_streams, const cf
     dev(od->d_npts2[i], (size_t)B * 4);
   }
   ok = ok && (od->ev_results = make_event(hipEventDisableTiming)) && (od->ev_jobs = make_event(hipEventDisableTiming)) &&
+       (od->ev_surf_jobs = make_event(hipEventDisableTiming)) && (od->ev_offsets[0] = make_event(hipEventDisableTiming)) &&
+       (od->ev_offsets[1] = make_event(hipEventDisableTiming)) && (od->ev_frame = make_event(hipEventDisableTiming)) &&
        (od->copy_stream = make_stream_nonblocking());
+  od->readback_on_copy_stream = ctx->stream != nullptr && ctx->stream != hipStreamLegacy && ctx->stream != hipStreamPerThread;
   dev(od->d_slabs, (size_t)B * od->slabs_per_stream * od->slab_bytes);
   dev(od->d_surf_jobs, (size_t)B * cfear_surface_job_bytes());
   // records are laid out at the stride of the window (process_frame); rounded up to 16 bytes, the stride of the longest
@@ -293,7 +313,7 @@ extern "C" int cfear_odometry_create(cfear_ctx* ctx, int32_t n_streams, const cf
 }
 
 // ---- F: filter (radar_driver.cpp:48-73) of one batch of polar images into filter buffer `buf` -------
-static int run_filter(cfear_odometry* od, const uint8_t* polar, int buf, const int64_t* offsets = nullptr) {
+static int run_filter_enqueue(cfear_odometry* od, const uint8_t* polar, int buf, const int64_t* offsets) {
   cfear_ctx* ctx = od->ctx;
   const int B = od->n_streams, rows = od->desc.rows, k = od->par.kstrong.k_strongest;
   const cfear_odometry_params& par = od->par;
@@ -304,9 +324,16 @@ static int run_filter(cfear_odometry* od, const uint8_t* polar, int buf, const i
     if (!od->fused || par.rotate_ccw || !cfear_is_device_ptr(polar))
       return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "image offsets need device images, the k-strongest filter "
                              "(k <= 64, no keep_nodes) and rows = azimuths");
+    // The table goes up on the copy stream, so the sweep does not queue behind a copy on its own stream.  Reuse: filter
+    // buffer `buf` was last swept two frames ago (the previous frame, if no prefetch ran in between).  That sweep stands in
+    // front of its frame's surface kernels and matcher on the kernel stream, and the host has waited for that frame's
+    // ev_results since -- so neither d_offsets2[buf] nor this half of h_offsets (whose upload that sweep waited for) is
+    // still in use.  The other half of both belongs to the frame in flight and is not touched.
     int64_t* h = od->h_offsets.get() + (size_t)buf * B;
     memcpy(h, offsets, (size_t)B * 8);
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(od->d_offsets2[buf].get(), h, (size_t)B * 8, hipMemcpyHostToDevice, ctx->stream));
+    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(od->d_offsets2[buf].get(), h, (size_t)B * 8, hipMemcpyHostToDevice, od->copy_stream.get()));
+    CFEAR_HIP_CHECK(ctx, hipEventRecord(od->ev_offsets[buf].get(), od->copy_stream.get()));
+    CFEAR_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, od->ev_offsets[buf].get(), 0));
     d_offsets = od->d_offsets2[buf].get();
   }
   if (!cfear_is_device_ptr(polar)) {
@@ -397,6 +424,13 @@ static int run_filter(cfear_odometry* od, const uint8_t* polar, int buf, const i
   return cfear_kstrong_device(ctx, d_polar, &dd, &kp, &o, par.rotate_ccw != 0);
 }
 
+static int run_filter(cfear_odometry* od, const uint8_t* polar, int buf, const int64_t* offsets = nullptr) {
+  const int rc = run_filter_enqueue(od, polar, buf, offsets);
+  // an error behind the offset upload: the caller may come back with other offsets before a frame has been synchronised
+  if (rc != CFEAR_OK && offsets) drain_streams(od);
+  return rc;
+}
+
 extern "C" int cfear_odometry_get_covariance(cfear_odometry* od, double* cov, int32_t* sampled) {
   if (!od || !cov) return CFEAR_ERR_INVALID_ARGUMENT;
   memcpy(cov, od->cov.data(), od->cov.size() * sizeof(double));
@@ -422,6 +456,9 @@ extern "C" int cfear_odometry_discard_prefetch(cfear_odometry* od) {
   if (!od) return CFEAR_ERR_INVALID_ARGUMENT;
   od->prefetched = nullptr;
   od->prefetched_offsets.clear();
+  // the discarded sweep and its offset upload may still be in flight, and the caller is about to reuse what they read
+  (void)hipSetDevice(od->ctx->device);
+  drain_streams(od);
   return CFEAR_OK;
 }
 
@@ -527,7 +564,10 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
   // ---- C + N: compensate with the previous motion, surface points (odometrykeyframefuser.cpp:146-161)
   const size_t sjb = cfear_surface_job_bytes();
   for (int b = 0; b < B; b++)
-    if (od->streams[b].free_slabs.empty()) return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "stream %d: no free scan slab", b);
+    if (od->streams[b].free_slabs.empty()) {
+      drain_streams(od);           // this frame's sweep and its offset upload are in flight; the next call reuses their buffer
+      return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "stream %d: no free scan slab", b);
+    }
   for (int b = 0; b < B; b++) {
     StreamState& st = od->streams[b];
     st.cur_slab = st.free_slabs.back();
@@ -547,8 +587,10 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
                              od->d_npts + b, 0, par.compensate, mot, od->views[(size_t)b * od->slabs_per_stream + st.cur_slab]);
   }
   // From here on every stream holds a slab: an error exit must hand the slabs back, or submap_scan_size + 2 failed
-  // calls would drain a stream's free list.
+  // calls would drain a stream's free list.  It also leaves both streams idle: the next call fills the pinned tables and
+  // uploads them on the copy stream at once, which only this frame's ev_results would otherwise have made safe.
   auto fail = [&](int code) {
+    drain_streams(od);
     for (int b = 0; b < B; b++) {
       StreamState& st = od->streams[b];
       if (st.cur_slab >= 0) { st.free_slabs.push_back(st.cur_slab); st.cur_slab = -1; }
@@ -561,7 +603,13 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
     if (_e != hipSuccess)                                                                                     \
       return fail(cfear_set_error(ctx, CFEAR_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__)); \
   } while (0)
-  OD_CHECK(hipMemcpyAsync(od->d_surf_jobs.get(), od->h_surf_jobs.get(), (size_t)B * sjb, hipMemcpyHostToDevice, ctx->stream));
+  // The table goes up on the copy stream now, while the sweep (prefetched a frame ago) may still run; the kernel stream
+  // waits for it in front of the surface kernels.  Reuse: d_surf_jobs was last read by the previous frame's surface kernels,
+  // h_surf_jobs by the upload those kernels waited for; they stand in front of that frame's matcher on the kernel stream, and
+  // the host has waited for that frame's ev_results (or, after an error, for both streams) since.
+  OD_CHECK(hipMemcpyAsync(od->d_surf_jobs.get(), od->h_surf_jobs.get(), (size_t)B * sjb, hipMemcpyHostToDevice, od->copy_stream.get()));
+  OD_CHECK(hipEventRecord(od->ev_surf_jobs.get(), od->copy_stream.get()));
+  OD_CHECK(hipStreamWaitEvent(ctx->stream, od->ev_surf_jobs.get(), 0));
   cfear_feature_params fp{};
   fp.radius = par.res;
   fp.downsample_factor = par.downsample_factor;
@@ -666,10 +714,14 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
       lrc = cfear_register_launch(ctx, od->d_reg_jobs.get(), n_jobs, &par.reg, par.submap_scan_size * od->cell_cap,
                                   od->d_reg_scratch.get(), od->d_samples.get(), &mode, rjb, hint);
       if (lrc != CFEAR_OK) return lrc;
-      if (hipMemcpyAsync(od->h_samples.get(), od->d_samples.get(), (size_t)n_jobs * od->fit.m * sizeof(cfear_reg_result),
-                         hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-        return cfear_set_error(ctx, CFEAR_ERR_HIP, "sample read-back failed");
     }
+    return CFEAR_OK;
+  };
+  auto read_samples = [&](hipStream_t s) -> int {
+    if (!par.estimate_cov_by_sampling || n_jobs == 0) return CFEAR_OK;
+    if (hipMemcpyAsync(od->h_samples.get(), od->d_samples.get(), (size_t)n_jobs * od->fit.m * sizeof(cfear_reg_result),
+                       hipMemcpyDeviceToHost, s) != hipSuccess)
+      return cfear_set_error(ctx, CFEAR_ERR_HIP, "sample read-back failed");
     return CFEAR_OK;
   };
   const bool launched_big = od->big_regs > 0;
@@ -685,12 +737,27 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
       rc = cfear_compensate_batch_device(ctx, od->d_pk, (size_t)od->cap_points, od->d_npk, od->d_mot.get(), B, od->cap_points, par.radar_ccw);
       if (rc != CFEAR_OK) return fail(rc);
     }
-    OD_CHECK(hipMemcpyAsync(od->h_npk.get(), od->d_npk, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
   }
   if (!rows_mode)     // the point counts came from the filter / the caller: bring them into the block first
     OD_CHECK(hipMemcpyAsync(od->d_npts_out, od->d_npts, (size_t)B * 4, hipMemcpyDeviceToDevice, ctx->stream));
-  OD_CHECK(hipMemcpyAsync(od->h_out.get(), od->d_out.get(), od->out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  OD_CHECK(hipEventRecord(od->ev_results.get(), ctx->stream));
+  // What the host reads of the frame, in stream order behind the frame's last kernel-stream work; ev_results behind it.
+  auto read_back = [&](hipStream_t s) -> int {
+    const int src = read_samples(s);
+    if (src != CFEAR_OK) return src;
+    hipError_t e = hipSuccess;
+    if (par.keep_nodes) e = hipMemcpyAsync(od->h_npk.get(), od->d_npk, (size_t)B * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(od->h_out.get(), od->d_out.get(), od->out_bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipEventRecord(od->ev_results.get(), s);
+    return e == hipSuccess ? CFEAR_OK : cfear_set_error(ctx, CFEAR_ERR_HIP, "result read-back failed: %s", hipGetErrorString(e));
+  };
+  // The frame's kernel-stream work ends here.  The read-back comes down on the copy stream (below, behind the prefetch), so
+  // the next sweep follows the matcher with no copy in between -- or here, where the kernel stream is a handle.
+  if (od->readback_on_copy_stream) {
+    OD_CHECK(hipEventRecord(od->ev_frame.get(), ctx->stream));
+  } else {
+    rc = read_back(ctx->stream);
+    if (rc != CFEAR_OK) return fail(rc);
+  }
   int prefetch_rc = CFEAR_OK;
   if (polar_next) {
     // (Tried twice: the sweep on its own low-priority stream.  Enqueued ahead of this frame's kernels it simply ran first
@@ -712,6 +779,16 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
       if (offsets_next) od->prefetched_offsets.assign(offsets_next, offsets_next + B);
     }
   }
+  // The read-back is enqueued behind the prefetch so that the next sweep's offset upload, on the same copy stream, does
+  // not wait for this frame's matcher.  Reuse: d_out, d_samples and d_npk are written next by the NEXT frame's surface
+  // kernels, matcher and filter of this buffer, none of which is enqueued before the host has passed ev_results below (the
+  // prefetched sweep writes the other filter buffer only); h_out, h_samples and h_npk were last written by the previous
+  // frame's read-back, which the host waited for in that frame.
+  if (od->readback_on_copy_stream) {
+    OD_CHECK(hipStreamWaitEvent(od->copy_stream.get(), od->ev_frame.get(), 0));
+    rc = read_back(od->copy_stream.get());
+    if (rc != CFEAR_OK) return fail(rc);
+  }
   g_tl.mark(2);
   OD_CHECK(hipEventSynchronize(od->ev_results.get()));
   g_tl.mark(3);
@@ -724,6 +801,8 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
     for (int j = 0; j < n_jobs && !retry; j++) retry = od->h_results[j].status == CFEAR_ERR_CAPACITY && od->h_results[j].reserved != 0.0;
     if (retry) {
       rc = launch_register(true);
+      if (rc != CFEAR_OK) return fail(rc);
+      rc = read_samples(ctx->stream);
       if (rc != CFEAR_OK) return fail(rc);
       OD_CHECK(hipMemcpyAsync(od->h_results, od->d_results, (size_t)n_jobs * sizeof(cfear_reg_result), hipMemcpyDeviceToHost, ctx->stream));
       OD_CHECK(hipStreamSynchronize(ctx->stream));

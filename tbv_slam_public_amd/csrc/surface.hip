@@ -836,8 +836,8 @@ __global__ __launch_bounds__(kSurfThreads) void surface_points_kernel(const Surf
 //                          with per-thread digit counters; then the cells, one lane per voxel, from slabs of sorted
 //                          points staged in LDS, with the three neighbour runs found by O(1) look-ups in the cell ->
 //                          ordinal map instead of binary searches.
-//   surface_finish_kernel  per scan: compaction in voxel order + the x-sorted copy for the matcher (small LDS, 8
-//                          wavefronts per SIMD).
+//   surface_finish_kernel  per scan: compaction in voxel order + the x-sorted copy for the matcher (small LDS; built
+//                          for 5 wavefronts per SIMD, 90 VGPRs: its launch bound says why not more).
 // The first version ran all of this in one 1024-thread workgroup per CU (148 KiB of LDS) at ~3 % of the VALU peak: every
 // phase waited on barriers and dependent LDS chains with 4 wavefronts per SIMD.  (A flat lane-per-voxel kernel over all
 // scans, fed through global scratch, was tried in between: 1.6 - 2.1 ms per 2048 scans -- its dependent global look-ups
@@ -1499,7 +1499,10 @@ __global__ __launch_bounds__(kFastThreads, 4) void surface_sort_mixed_kernel(con
 
 constexpr int kFinishThreads = 256;
 
-__global__ __launch_bounds__(kFinishThreads) void surface_finish_kernel(const SurfJob* __restrict__ jobs, const SurfCommon cm) {
+// Five wavefronts per SIMD: the kernel waits (its loads, the round's barrier), so it gains from residency, and 5 is the most the
+// compiler reaches without scratch memory (90 VGPRs; unbounded it took 114 = 4 wavefronts, bounds of 6 and 8 spill 20 / 76
+// bytes per lane).  0.117-0.122 -> 0.108-0.112 ms per 4096 scans (EXPERIMENTS.md).
+__global__ __launch_bounds__(kFinishThreads, 5) void surface_finish_kernel(const SurfJob* __restrict__ jobs, const SurfCommon cm) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];       // sort keys: next_pow2(cell capacity) x 8 bytes
   __shared__ int red_i2[2][kFinishThreads / 64];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
