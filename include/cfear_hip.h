@@ -97,10 +97,16 @@ int cfear_ctx_get_stream(const cfear_ctx* ctx, void** hip_stream);
  *   CFEAR_OPT_REPLAY_CHUNK   0 (default): cfear_odometry_replay_clouds sizes its frame chunks by the free device memory;
  *                            n >= 1: at most n frames per chunk, so that a short trace crosses chunk boundaries inside
  *                            a keyframe window.  (Numbered apart from the enum: the enum's count is part of the pinned ABI.)
+ *   CFEAR_OPT_KSTRONG_ROW_PAIRS 1 (default): the k-strongest row sweep of 4-byte-aligned images of at most 4096 bins, without
+ *                            peaks, gives one wavefront two adjacent rows and selects both in one ranking pass when they
+ *                            hold at most 64 candidates together; 0: one row per wavefront, the table cfear_kstrong_plan
+ *                            describes.  The results are the same bit for bit.  Read per filter call.  (Numbered apart
+ *                            from the enum, as above.)
  * Returns CFEAR_ERR_INVALID_ARGUMENT for an unknown option or a value outside its range.                          */
 enum cfear_option { CFEAR_OPT_FUSED_DECODE = 0, CFEAR_OPT_MATCHER_LDS_KB = 1, CFEAR_OPT_MATCHER_WAVES = 2,
                     CFEAR_OPT_HOST_TIMELINE = 3, CFEAR_OPT_SC_QUERY_CHUNK = 4, CFEAR_OPT_PGO_GRAPH_CHUNK = 5, CFEAR_OPT_COUNT = 6 };
 #define CFEAR_OPT_REPLAY_CHUNK 100
+#define CFEAR_OPT_KSTRONG_ROW_PAIRS 101
 int cfear_ctx_set_option(cfear_ctx* ctx, int32_t option, int64_t value);
 int cfear_ctx_get_option(const cfear_ctx* ctx, int32_t option, int64_t* value);
 /* Per-kernel-family device time measured with hipEvents on the context's stream.

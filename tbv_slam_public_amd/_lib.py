@@ -370,6 +370,7 @@ OPT_FUSED_DECODE, OPT_MATCHER_LDS_KB, OPT_MATCHER_WAVES, OPT_HOST_TIMELINE, OPT_
 # CFEAR_OPT_PGO_GRAPH_CHUNK follows them with a different value range: n >= 1 graphs per chunk of cfear_pgo_solve_batch, 0 refused.
 OPT_PGO_GRAPH_CHUNK = 5
 OPT_REPLAY_CHUNK = 100              # #define CFEAR_OPT_REPLAY_CHUNK: frames per chunk of a replay, 0 = by free memory (numbered apart from the enum)
+OPT_KSTRONG_ROW_PAIRS = 101         # #define CFEAR_OPT_KSTRONG_ROW_PAIRS: 1 (default) two rows per wavefront in the k-strongest sweep, 0 = the single-row table
 
 
 class PgoParams(C.Structure):

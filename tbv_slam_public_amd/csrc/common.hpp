@@ -125,6 +125,7 @@ struct cfear_ctx {
   int n_cu = 256;          // compute units of the device (cfear_ctx_create)
   int64_t opt[CFEAR_OPT_COUNT] = {1, 0, 0, 0};   // cfear_ctx_set_option (test / measurement hooks; include/cfear_hip.h)
   int64_t replay_chunk = 0;      // CFEAR_OPT_REPLAY_CHUNK
+  int64_t kstrong_row_pairs = 1; // CFEAR_OPT_KSTRONG_ROW_PAIRS
   bool surf_list_dirty = true;   // the surface pipeline's hand-over counter may be non-zero (see cfear_surface_launch)
   std::vector<std::pair<const void*, int>> lds_allowed;   // kernels and the dynamic LDS they were already allowed on this device (cfear_allow_lds)
 };

@@ -419,6 +419,12 @@ int cfear_ctx_set_option(cfear_ctx* ctx, int32_t option, int64_t value) {
     ctx->replay_chunk = value;
     return CFEAR_OK;
   }
+  if (option == CFEAR_OPT_KSTRONG_ROW_PAIRS) {
+    if (value != 0 && value != 1)
+      return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "option %d: value %lld out of range", (int)option, (long long)value);
+    ctx->kstrong_row_pairs = value;
+    return CFEAR_OK;
+  }
   bool ok = false;
   switch (option) {
     case CFEAR_OPT_FUSED_DECODE: case CFEAR_OPT_HOST_TIMELINE: ok = value == 0 || value == 1; break;
@@ -435,6 +441,7 @@ int cfear_ctx_set_option(cfear_ctx* ctx, int32_t option, int64_t value) {
 
 int cfear_ctx_get_option(const cfear_ctx* ctx, int32_t option, int64_t* value) {
   if (ctx && value && option == CFEAR_OPT_REPLAY_CHUNK) { *value = ctx->replay_chunk; return CFEAR_OK; }
+  if (ctx && value && option == CFEAR_OPT_KSTRONG_ROW_PAIRS) { *value = ctx->kstrong_row_pairs; return CFEAR_OK; }
   if (!ctx || !value || option < 0 || option >= CFEAR_OPT_COUNT) return CFEAR_ERR_INVALID_ARGUMENT;
   *value = ctx->opt[option];
   return CFEAR_OK;

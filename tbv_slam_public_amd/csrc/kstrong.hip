@@ -592,6 +592,227 @@ __global__ __launch_bounds__(256, 7) void kstrongest_rows_kernel(const KStrongAr
   kstrong_row<NCHUNK, VEC, MASK, false>(a, r, b, img, rowbuf, hist, list, lane);
 }
 
+// ---- two rows per wavefront ---------------------------------------------------------------------------------
+// A radar azimuth holds two dozen bins >= z_min, so everything kstrong_row does after the byte compares -- the scan, the
+// scatter, the ranking, the emission -- runs on a wavefront with a third of its lanes live, once per row.  Here wavefront w of
+// a 128-thread workgroup owns rows 4 blockIdx.x + 2 w and + 1 from the load on: when the two rows hold at most 64 candidates
+// TOGETHER (so each is on kstrong_row's "n_ge <= 64" branch) one scatter round, one ranking loop and one emission serve
+// both.  (The rows are counted by a scan each, not by one packed scan: a first row beyond 64 alone ends the joint attempt before
+// the second row's compares, which is what keeps dense scenes at the single-row kernel's time.)  Slots are numbered row 0 first; the owner id of a slot is (row << 6 | lane), which still grows with the
+// slot, so the max-scan spreads it as before.  Row 0's keys go to list[0 ..), row 1's to list[kpad ..), and a lane ranks its
+// key against its own row's segment: two addresses per LDS read instead of one.  Any other pair -- and the last row of an odd
+// image -- takes kstrong_row<STAGED> on each row in turn (row 1 waits in its sixteen registers), so the results are the
+// single-row kernel's bit for bit.
+// Both rows stay in registers until their candidates' bytes have been fetched, and ONE row buffer in LDS holds them in turn
+// (row 0, then row 1): a wavefront with two rows then needs no more LDS than one of the single-row kernel's, and as many
+// wavefronts are resident as the registers allow -- with two buffers it was 3.5 per SIMD, and the sweep, which needs the other
+// wavefronts' instructions to cover a wavefront's loads, ran 10 % SLOWER than one row per wavefront (EXPERIMENTS.md).
+// Seven wavefronts per SIMD without scratch memory (six for the MASK forms): the Makefile binds the <4, ...> forms to that.
+// VEC only, no peaks (no halo bytes are kept), NCHUNK <= 4: cfear_kstrong_device routes the rest to the table of 16.
+// per-wavefront scratch: marker u8[256] | sexcl[2][64] | spw[2][NP][64] (never below what kstrong_row carves from it)
+__host__ __device__ constexpr int kstrong_pair_scratch_bytes(int nchunk) { return (3 + 2 * ((nchunk + 1) / 2)) * 256; }
+// per-wavefront LDS: one row, to the next multiple of 16 bins | scratch | two key lists
+__host__ __device__ constexpr int kstrong_pair_wave_bytes(int nchunk, int cols, int kpad) {
+  return ((cols + 15) & ~15) + kstrong_pair_scratch_bytes(nchunk) + 2 * kpad * 4;
+}
+constexpr int kPairRows = 2;                       // rows per wavefront; kRowsPerBlock / kPairRows wavefronts per workgroup
+
+template <int NCHUNK, bool MASK>
+__global__ __launch_bounds__(64 * kRowsPerBlock / kPairRows, MASK ? 6 : 7) void kstrongest_rowpairs_kernel(const KStrongArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+#if CFEAR_KSTRONG_HEAD_PAD > 0
+  asm volatile(".rept %0\n\ts_nop 0\n\t.endr" ::"n"(CFEAR_KSTRONG_HEAD_PAD / 4));
+#endif
+  static_assert(kstrong_pair_scratch_bytes(NCHUNK) >= kstrong_scratch_bytes(NCHUNK), "kstrong_row's scratch fits the pair's");
+  constexpr int NP = (NCHUNK + 1) / 2;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int r0 = blockIdx.x * kRowsPerBlock + kPairRows * wave;
+  if (r0 >= a.rows) return;                                 // no workgroup barrier below
+  const bool has1 = r0 + 1 < a.rows;                        // odd row counts: the last wavefront owns one row
+  const int b = a.batch0 + blockIdx.y;
+  const uint8_t* img = a.polar + (a.image_offsets ? a.image_offsets[b] : (long long)b * a.batch_stride);
+  const int k = a.k;
+  const int kpad = max((k + 3) & ~3, 64);
+  const int cols16 = (a.cols + 15) & ~15;
+  uint8_t* rowbuf = smem + wave * kstrong_pair_wave_bytes(NCHUNK, a.cols, kpad);           // [cols16]: row 0, later row 1
+  uint32_t* hist = (uint32_t*)(rowbuf + cols16);
+  uint32_t* list = (uint32_t*)(rowbuf + cols16 + kstrong_pair_scratch_bytes(NCHUNK));      // [2][kpad]
+
+  // ---- load both rows before the first use (8 loads in flight at NCHUNK = 4), compare -----------------------------------
+  uint32_t w0[NCHUNK * 4], w1[NCHUNK * 4];
+  auto stage = [&](const uint32_t (&w)[NCHUNK * 4]) {       // the pieces kstrong_row<STAGED> and the byte fetch may read
+#pragma unroll
+    for (int c = 0; c < NCHUNK; c++)
+      if ((c * 64 + lane) * 16 < cols16) *(uint4*)(rowbuf + (c * 64 + lane) * 16) = make_uint4(w[c * 4], w[c * 4 + 1], w[c * 4 + 2], w[c * 4 + 3]);
+  };
+  auto wave_sync = [&]() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  };
+  uint32_t bm0[NCHUNK], bm1[NCHUNK];
+  {
+    const int r1 = has1 ? r0 + 1 : r0;                      // an absent row reads row 0 again and is not used
+    load_row<NCHUNK, true>(img + (long long)r0 * a.stride, a.cols, lane, w0, cfear_piece_inside_image(r0, a.cols & ~15, a.rows, a.stride));
+    load_row<NCHUNK, true>(img + (long long)r1 * a.stride, a.cols, lane, w1, cfear_piece_inside_image(r1, a.cols & ~15, a.rows, a.stride));
+  }
+  const uint32_t tz4 = (uint32_t)(a.u_zmin & 0x7f) * 0x01010101u;
+  if (a.u_zmin & 0x80) candidate_bitmaps<NCHUNK, MASK, true>(w0, tz4, a.cols, lane, bm0);
+  else candidate_bitmaps<NCHUNK, MASK, false>(w0, tz4, a.cols, lane, bm0);
+  stage(w0);
+  int c0 = 0, c1 = 0;
+#pragma unroll
+  for (int c = 0; c < NCHUNK; c++) c0 += __popc(bm0[c]);
+  const int incl0 = wave_incl_scan_i32(c0);
+  const int n0 = __builtin_amdgcn_readlane(incl0, 63);
+  int n1 = 65, incl1 = 0;
+  if (has1 && n0 <= 64) {                                   // a first row beyond 64 alone: the second row's compares are kstrong_row's
+    if (a.u_zmin & 0x80) candidate_bitmaps<NCHUNK, MASK, true>(w1, tz4, a.cols, lane, bm1);
+    else candidate_bitmaps<NCHUNK, MASK, false>(w1, tz4, a.cols, lane, bm1);
+#pragma unroll
+    for (int c = 0; c < NCHUNK; c++) c1 += __popc(bm1[c]);
+    incl1 = wave_incl_scan_i32(c1);
+    n1 = __builtin_amdgcn_readlane(incl1, 63);
+  } else {
+#pragma unroll
+    for (int c = 0; c < NCHUNK; c++) bm1[c] = 0;
+  }
+  const int e0 = incl0 - c0, e1 = n0 + incl1 - c1;
+
+  if (__builtin_expect(!has1 || n0 + n1 > 64, 0)) {
+    // ---- the rows one after the other, each from the row buffer: every path of kstrong_row, none of it written twice.
+    //      (Two calls, not a loop of two turns: in a loop the compiler computes what kstrong_row derives from the lane id and
+    //      the geometry before the loop and holds it across -- in scratch memory.)
+    wave_sync();                                            // row 0 is staged
+    kstrong_row<NCHUNK, true, MASK, true>(a, r0, b, img, rowbuf, hist, list, lane);
+    if (!has1) return;
+    wave_sync();                                            // the buffer, the scratch and the list are free again
+    stage(w1);
+    wave_sync();
+    kstrong_row<NCHUNK, true, MASK, true>(a, r0 + 1, b, img, rowbuf, hist, list, lane);
+    return;
+  }
+
+  // ---- slots: row 0's candidates lane-major, then row 1's; one candidate per lane ------------------------------------------
+  uint8_t* marker = (uint8_t*)hist;                         // [256] (row << 6 | lane) of the slot that starts a run, else 0
+  uint32_t* sexcl = hist + 64;                              // [2][64] first slot of each lane's run, by owner id
+  uint32_t* spw = hist + 192;                               // [2][NP][64] bitmaps
+  const int n = n0 + n1;
+  {
+    ((uint32_t*)marker)[lane] = 0;
+    sexcl[lane] = e0;
+    sexcl[64 + lane] = e1;
+#pragma unroll
+    for (int p = 0; p < NP; p++) {
+      spw[p * 64 + lane] = (bm0[2 * p] >> 4) | (2 * p + 1 < NCHUNK ? bm0[2 * p + 1] : 0u);
+      spw[(NP + p) * 64 + lane] = (bm1[2 * p] >> 4) | (2 * p + 1 < NCHUNK ? bm1[2 * p + 1] : 0u);
+    }
+    list[lane] = 0xFFFFFFFFu;                               // the padding ranks above every key: both segments, up to the
+    list[kpad + lane] = 0xFFFFFFFFu;                        // longer one's end (the ranking loop reads both that far)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (c0) marker[e0] = (uint8_t)lane;                     // e0 < n0, e1 < n <= 64
+    if (c1) marker[e1] = (uint8_t)(64 + lane);
+    wave_sync();
+  }
+  const bool valid = lane < n;
+  const int row1 = lane >= n0 ? 1 : 0;                      // the row of this lane's slot
+  uint32_t* seg = list + (row1 ? kpad : 0);                 // its row's keys
+  uint32_t key = 0;
+  {
+    const int own = wave_incl_scan_max_i32((int)marker[lane]);
+    int pos = 0;
+    if (valid) {
+      const int ol = own & 63;
+      const uint32_t* sp = spw + (own >> 6) * (NP * 64) + ol;
+      int q = lane - (int)sexcl[own];
+      uint32_t word = sp[0];
+      int p = 0;
+#pragma unroll
+      for (int pp = 1; pp < NP; pp++) {
+        const int c = __popc(word);
+        const uint32_t nxt = sp[pp * 64];
+        if (p == pp - 1 && q >= c) { q -= c; word = nxt; p = pp; }
+      }
+      int t = 0;
+      { const int c = __popc(word & 0xFFFFu); if (q >= c) { q -= c; t = 16; word >>= 16; } }
+      { const int c = __popc(word & 0xFFu);   if (q >= c) { q -= c; t += 8; word >>= 8; } }
+      { const int c = __popc(word & 0xFu);    if (q >= c) { q -= c; t += 4; word >>= 4; } }
+      { const int c = __popc(word & 0x3u);    if (q >= c) { q -= c; t += 2; word >>= 2; } }
+      if (q >= (int)(word & 1u)) t += 1;
+      pos = p * 2048 + ol * 16 + ((t & 4) << 8) + ((t & 3) << 2) + (t >> 3);
+    }
+    // the candidates' bytes: row 0's from the buffer as it stands, then row 1 takes its place
+    uint32_t byte = 0;
+    if (valid && !row1) byte = rowbuf[pos];
+    wave_sync();
+    stage(w1);
+    wave_sync();
+    if (valid && row1) byte = rowbuf[pos];
+    if (valid) {
+      key = (byte << 24) | (uint32_t)pos;
+      seg[lane - (row1 ? n0 : 0)] = key;
+    }
+  }
+  wave_sync();                                              // the scatter tables have been read: their first words become
+  if (a.row_keys && lane < 4) hist[lane] = 0;               // the rows' bitmaps of kept bins beyond min_range_bin
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+  // ---- rank: ascending packed key within the lane's own row; survivors have rank >= drop ---------------------------------
+  const int n_all = row1 ? n1 : n0;
+  const int n_sel = min(n_all, k);
+  const int nq = (max(n0, n1) + 3) & ~3;                    // wave-uniform, <= 64 <= kpad
+  int rank = -1;
+  if (valid) {
+    rank = 0;
+    for (int i = 0; i < nq; i += 4) {
+      const uint4 q = *(const uint4*)(seg + i);             // two addresses per instruction
+      rank += (q.x < key) + (q.y < key) + (q.z < key) + (q.w < key);
+    }
+    rank -= n_all - n_sel;                                  // < 0: below the cut
+  }
+  // ---- emit ----------------------------------------------------------------------------------------------------------------
+  const long long obase = ((long long)b * a.rows + r0 + row1) * k;
+  const int range = (int)(key & 0xFFFFFFu);
+  bool beyond = false;
+  if (rank >= 0) {
+    if (a.sel_range) a.sel_range[obase + rank] = range;
+    if (a.sel_intensity) a.sel_intensity[obase + rank] = (uint8_t)(key >> 24);
+    beyond = range > a.min_range_bin;                       // radar_filters.cpp:327
+  }
+  if (__builtin_expect(a.row_keys != nullptr, 1)) {         // k <= 64: the ranks fit one pair of words per row
+    uint32_t* bits = hist + 2 * row1;
+    if (beyond) atomicOr(&bits[rank >> 5], 1u << (rank & 31));
+    wave_sync();
+    if (beyond) {
+      const uint32_t m0 = bits[0], m1 = bits[1];
+      const int idx = rank < 32 ? __popc(m0 & ((1u << rank) - 1u)) : __popc(m0) + __popc(m1 & ((1u << (rank - 32)) - 1u));
+      a.row_keys[obase + idx] = key;
+    }
+  }
+  const unsigned long long bal = __ballot(beyond);
+  const unsigned long long lanes1 = n0 >= 64 ? 0ull : ~0ull << n0;      // the lanes that hold row 1's slots
+  if (a.sel_range || a.sel_intensity) {                     // unused slots, both rows
+#pragma nounroll
+    for (int h = 0; h < kPairRows; h++) {
+      const long long ob = ((long long)b * a.rows + r0 + h) * k;
+      for (int j = min(h ? n1 : n0, k) + lane; j < k; j += 64) {
+        if (a.sel_range) a.sel_range[ob + j] = -1;
+        if (a.sel_intensity) a.sel_intensity[ob + j] = 0;
+      }
+    }
+  }
+  if (lane < kPairRows) {                                   // lane h reports row h
+    const long long ro = (long long)b * a.rows + r0 + lane;
+    if (a.row_valid) {
+      a.row_valid[ro * 2] = __popcll(bal & (lane ? lanes1 : ~lanes1));
+      a.row_valid[ro * 2 + 1] = 0;
+    }
+    if (a.sel_count) a.sel_count[ro] = min(lane ? n1 : n0, k);
+  }
+}
+
 // ---- [range bins][azimuths] sources: the driver's decode fused into the sweep ---------------------------------------
 // radarDriver::Callback (radar_driver.cpp:74-90) rotates such a sweep 90 degrees counter-clockwise before Process();
 // rotate_ccw_rows_kernel + kstrongest_rows_kernel move the image through HBM three times (read, write, read).  The fused
@@ -1079,6 +1300,11 @@ constexpr int kKStrongEntries = 16;
   kstrongest_rows_kernel<N, true, true>
 const KStrongFn kKStrongTable[kKStrongEntries] = {CFEAR_KSTRONG_ROW4(1), CFEAR_KSTRONG_ROW4(2), CFEAR_KSTRONG_ROW4(4), CFEAR_KSTRONG_ROW4(8)};
 #undef CFEAR_KSTRONG_ROW4
+// two rows per wavefront (VEC, no peaks, NCHUNK <= 4): index 2 log2(NCHUNK) + MASK
+constexpr int kKStrongPairEntries = 6;
+const KStrongFn kKStrongPairTable[kKStrongPairEntries] = {
+  kstrongest_rowpairs_kernel<1, false>, kstrongest_rowpairs_kernel<1, true>, kstrongest_rowpairs_kernel<2, false>,
+  kstrongest_rowpairs_kernel<2, true>,  kstrongest_rowpairs_kernel<4, false>, kstrongest_rowpairs_kernel<4, true>};
 
 // What follows from the filter's parameters alone, for the row sweep and the bins-major route alike: the candidate threshold,
 // the bin the cloud starts beyond, and the list capacity (k survivors, or up to 64 candidates to rank).
@@ -1165,13 +1391,19 @@ int cfear_kstrong_device(cfear_ctx* ctx, const uint8_t* d_polar, const cfear_pol
   }
   if (plan.table_index < 0 || plan.table_index >= kKStrongEntries || plan.nchunk * 1024 < a.cols)   // a missing kernel is an error
     return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "k-strongest: no kernel for %d bins", a.cols);
-  const KStrongFn fn = kKStrongTable[plan.table_index];
+  // Two rows per wavefront wherever the pair kernel exists: 4-byte-aligned images, at most 4096 bins, no peaks (its fallback
+  // reads the staged row, which keeps no halo bytes).  The plan keeps describing the single-row instantiation, which is what
+  // everything else -- and CFEAR_OPT_KSTRONG_ROW_PAIRS = 0 -- launches.
+  const bool pairs = plan.vec && plan.nchunk <= 4 && !a.want_peaks && ctx->kstrong_row_pairs != 0;
+  const KStrongFn fn = pairs ? kKStrongPairTable[plan.table_index / 4 * 2 + plan.mask] : kKStrongTable[plan.table_index];
+  const unsigned threads = pairs ? 64 * kRowsPerBlock / kPairRows : 64 * kRowsPerBlock;
+  const size_t lds = pairs ? (size_t)(kRowsPerBlock / kPairRows) * kstrong_pair_wave_bytes(plan.nchunk, a.cols, plan.kpad) : (size_t)plan.lds_bytes;
   {
     ProfScope ps(ctx, "kstrongest_rows");
     for (int b0 = 0; b0 < a.batch; b0 += 65535) {             // gridDim.y limit
       a.batch0 = b0;
       dim3 grid((unsigned)((a.rows + kRowsPerBlock - 1) / kRowsPerBlock), (unsigned)std::min(65535, a.batch - b0));
-      hipLaunchKernelGGL(fn, grid, dim3(256), (size_t)plan.lds_bytes, ctx->stream, a);
+      hipLaunchKernelGGL(fn, grid, dim3(threads), lds, ctx->stream, a);
     }
   }
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
