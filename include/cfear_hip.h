@@ -227,6 +227,24 @@ int cfear_kstrong_plan(const cfear_polar_desc* desc, const cfear_kstrong_params*
 int cfear_filter_kstrongest_rowkeys(cfear_ctx* ctx, const uint8_t* polar, const cfear_polar_desc* desc,
                                     const cfear_kstrong_params* par, int32_t flags, uint32_t* row_keys, int32_t* row_counts);
 
+/* Row keys of SEVERAL k-strongest parameter sets from ONE sweep.  FilterKstrongest keeps the k largest (intensity, range)
+ * pairs among the bins >= uchar(z_min) and the near cut applies only when the cloud is built, so for k_c <= k_sup and
+ * uchar(z_min_c) >= uchar(z_min_sup) the selection of (k_c, z_min_c) is the top k_c entries of the selection of
+ * (k_sup, z_min_sup) restricted to intensity >= uchar(z_min_c).  sel_range / sel_intensity / sel_count: the lists
+ * cfear_filter_kstrongest leaves for n_images images of `rows` azimuths at (k_sup, z_min_sup), k_sup <= 64.  Class c takes
+ * image classes[c].image and gets what cfear_filter_kstrongest_rowkeys gives that image with the class's own parameters, bit
+ * for bit, at a row stride of 64 keys:
+ *   row_keys   uint32 [n_classes][rows][64]   (entries beyond the row's count are not written)
+ *   row_counts int32  [n_classes][rows][2]    {kept bins of the row, 0}
+ * All buffers are device memory except `classes` (host).  Refused with CFEAR_ERR_INVALID_ARGUMENT before any launch: k_sup
+ * outside [1, 64]; a class with k_strongest outside [1, k_sup], uchar(z_min) below that of z_min_sup, image outside
+ * [0, n_images) or range_res <= 0; n_images, rows or n_classes < 1; null pointers; host pointers where device memory is
+ * required (and a device pointer for classes).                                                                            */
+typedef struct cfear_rowkeys_class { int32_t image; int32_t k_strongest; float z_min, range_res, min_distance; } cfear_rowkeys_class;
+int cfear_kstrong_rowkeys_derive(cfear_ctx* ctx, const int32_t* sel_range, const uint8_t* sel_intensity, const int32_t* sel_count,
+                                 int32_t n_images, int32_t rows, int32_t k_sup, float z_min_sup,
+                                 const cfear_rowkeys_class* classes, int32_t n_classes, uint32_t* row_keys, int32_t* row_counts);
+
 /* Legacy filter: replaces k_strongest_filter / InsertStrongestK (radar_filters.cpp:25-78), which CorAl's standalone
  * kstrongRadar scan type still calls (coral_alignment_quality/src/alignment_checker/ScanType.cpp:104-114); TBV itself uses
  * the structured filter above.  Different rule: the first bin >= z_min of a row sets a floor, later bins
@@ -1427,6 +1445,65 @@ int cfear_odometry_get_scan(cfear_odometry* od, int32_t stream, cfear_scan** out
 int cfear_odometry_get_cloud(cfear_odometry* od, int32_t stream, float* xyzi, int32_t cap, int32_t* n_out);
 int cfear_odometry_get_peaks(cfear_odometry* od, int32_t stream, float* xyzi, int32_t cap, int32_t* n_out);
 int cfear_odometry_destroy(cfear_odometry* od);
+
+/* ---- a parameter grid of odometry streams as one batch ------------------------------------------------------------------
+ * The reference evaluates CFEAR as a grid of configurations over sequences (launch/oxford/eval/params/grid_search/: one
+ * job per (sequence, configuration), dealt to processes by utils/worker).  A grid object advances all of those jobs one frame
+ * per call: stream s runs configuration stream_config[s] on the images of sequence stream_sequence[s].  Per stream the state
+ * and every field of cfear_frame_info are those of a cfear_odometry created with that configuration and fed that sequence's
+ * images, with the failure semantics of cfear_odometry_process: a failed stream reports its own status and keeps its state,
+ * the others go on, and the call returns the first such status.
+ *
+ * What the streams share is computed once:
+ *   sweep     per sequence image ONE k-strongest row sweep serves all of its k-strongest streams: directly (the fused row
+ *             keys) where they agree on (k, uchar(z_min), min range bin, range_res) -- one filter class --, else at
+ *             (max k, min uchar(z_min)) into sel_* lists from which cfear_kstrong_rowkeys_derive writes every class's row
+ *             keys.  CA-CFAR configurations get one sweep per distinct (sequence, cfear_cacfar_params).
+ *   surface   one launch per distinct (res, downsample_factor, weight_intensity, radar_ccw, filter kind, range_res, row
+ *             stride) over that group's jobs; a job reads its class's shared row keys with its own motion and compensate.
+ *   matcher   one launch per distinct (cfear_reg_params, submap_scan_size) over that group's jobs.
+ * All groups' results come down in one read-back per call.
+ *
+ * desc: the layout of the n_sequences = desc->batch images a call is given.  stream_sequence / stream_config: [n_streams], or
+ * both NULL for the full product, sequence-major and configuration fastest (n_streams must then be desc->batch * n_configs):
+ * the order of utils/worker's loops, stream s being the reference's job_<s + 1>.
+ *
+ * cfear_odometry_grid_plan: the grouping as pure host code (no context, no device); cfear_odometry_grid_create takes its
+ * grouping from this very plan.  streams (optional) [n_streams]; totals (optional); why (optional, why_len bytes) receives
+ * the reason of a refusal.  The streams of a surface group occupy surface_slot [first, first + n) of that group and those of
+ * a matcher group matcher_slot [first, first + n): both slot orders are permutations of the streams in which every group is
+ * contiguous, streams in index order inside a group.
+ * Refused with CFEAR_ERR_INVALID_ARGUMENT, the message naming the configuration or stream: null desc or configs, n_configs
+ * or n_streams < 1, only one of the two stream arrays, the full product with another n_streams, an index outside its range,
+ * keep_nodes or estimate_cov_by_sampling set, a k-strongest configuration that the fused row-key hand-over of
+ * cfear_odometry_create would not take (k > 64, more than 4096 azimuths, rows * k beyond the surface stage's capacity), more
+ * than 4096 azimuths with CA-CFAR, rotate_ccw that differs between configurations, and whatever cfear_odometry_create
+ * refuses for that configuration.  Graph nodes, constraints, sampled covariances and the prefetch are outside a grid.     */
+typedef struct cfear_odometry_grid cfear_odometry_grid;
+typedef struct cfear_grid_stream {
+  int32_t sequence, config;
+  int32_t sweep;                        /* index of the sweep that produces this stream's row keys                        */
+  int32_t filter_class;                 /* index of its filter class (classes are numbered sweep by sweep)                */
+  int32_t surface_group, matcher_group;
+  int32_t surface_slot, matcher_slot;
+} cfear_grid_stream;
+typedef struct cfear_grid_totals {
+  int32_t n_streams, n_sequences;
+  int32_t n_sweeps;                     /* k-strongest + CA-CFAR                                                          */
+  int32_t n_classes;                    /* over all sweeps                                                                */
+  int32_t n_derived_classes;            /* of those, classes whose keys cfear_kstrong_rowkeys_derive writes               */
+  int32_t max_classes_per_sequence;
+  int32_t n_surface_groups, n_matcher_groups;
+} cfear_grid_totals;
+int cfear_odometry_grid_plan(const cfear_polar_desc* desc, const cfear_odometry_params* configs, int32_t n_configs,
+                             const int32_t* stream_sequence, const int32_t* stream_config, int32_t n_streams,
+                             cfear_grid_stream* streams, cfear_grid_totals* totals, char* why, int32_t why_len);
+int cfear_odometry_grid_create(cfear_ctx* ctx, const cfear_polar_desc* desc, const cfear_odometry_params* configs, int32_t n_configs,
+                               const int32_t* stream_sequence, const int32_t* stream_config, int32_t n_streams,
+                               cfear_odometry_grid** out);
+/* polar: desc->batch images laid out per desc, host or device.  info: host array [n_streams].                             */
+int cfear_odometry_grid_process(cfear_odometry_grid* grid, const uint8_t* polar, cfear_frame_info* info);
+int cfear_odometry_grid_destroy(cfear_odometry_grid* grid);
 
 /* ---- after the path: pose-graph nodes on disk ------------------------------------------------
  * simple_graph.sgh = Boost binary archive of std::vector<std::pair<RadarScan, std::vector<Constraint3d>>>

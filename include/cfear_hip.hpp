@@ -928,6 +928,51 @@ class OdometryKeyframeFuser {
   std::vector<Status> status_;
 };
 
+// A parameter grid of odometry streams as one batch (cfear_odometry_grid): stream s runs configs[stream_config[s]] on the
+// images of sequence stream_sequence[s]; with both lists empty the streams are the full product, sequence-major and
+// configuration fastest (the reference's job_<s + 1> of a grid_search evaluation).
+class OdometryGrid {
+ public:
+  struct Plan { std::vector<cfear_grid_stream> streams; cfear_grid_totals totals; };
+  OdometryGrid(Context& ctx, int rows, int cols, const std::vector<cfear_odometry_params>& configs, int n_sequences,
+               const std::vector<int32_t>& stream_sequence = {}, const std::vector<int32_t>& stream_config = {})
+      : ctx_(ctx) {
+    const bool product = stream_sequence.empty() && stream_config.empty();
+    n_ = product ? n_sequences * (int)configs.size() : (int)stream_sequence.size();
+    cfear_polar_desc d{rows, cols, cols, n_sequences, (int64_t)rows * cols};
+    ctx_.check(cfear_odometry_grid_create(ctx_.get(), &d, configs.data(), (int32_t)configs.size(), product ? nullptr : stream_sequence.data(),
+                                          product ? nullptr : stream_config.data(), n_, &grid_));
+  }
+  ~OdometryGrid() { cfear_odometry_grid_destroy(grid_); }
+  OdometryGrid(const OdometryGrid&) = delete;
+  OdometryGrid& operator=(const OdometryGrid&) = delete;
+  // the grouping as host code: needs no context and no device; throws CfearError with the refusal's reason
+  static Plan plan(int rows, int cols, const std::vector<cfear_odometry_params>& configs, int n_sequences,
+                   const std::vector<int32_t>& stream_sequence = {}, const std::vector<int32_t>& stream_config = {}) {
+    const bool product = stream_sequence.empty() && stream_config.empty();
+    const int n = product ? n_sequences * (int)configs.size() : (int)stream_sequence.size();
+    cfear_polar_desc d{rows, cols, cols, n_sequences, (int64_t)rows * cols};
+    Plan p;
+    p.streams.resize((size_t)(n > 0 ? n : 0));
+    char why[256] = "";
+    const int st = cfear_odometry_grid_plan(&d, configs.data(), (int32_t)configs.size(), product ? nullptr : stream_sequence.data(),
+                                            product ? nullptr : stream_config.data(), n, p.streams.data(), &p.totals, why, (int32_t)sizeof(why));
+    if (st != CFEAR_OK) throw CfearError(st, why);
+    return p;
+  }
+  int size() const { return n_; }
+  // polar: [n_sequences][rows][cols] uint8 (host or device)
+  std::vector<cfear_frame_info> processFrame(const uint8_t* polar) {
+    std::vector<cfear_frame_info> info((size_t)n_);
+    ctx_.check(cfear_odometry_grid_process(grid_, polar, info.data()));
+    return info;
+  }
+ private:
+  Context& ctx_;
+  cfear_odometry_grid* grid_ = nullptr;
+  int n_ = 0;
+};
+
 }  // namespace CFEAR_Radarodometry
 
 // CorAlRadarQuality (coral_alignment_quality AlignmentQuality.cpp:99-230) over two peak clouds.

@@ -346,7 +346,24 @@ EXPORTS = [
     "cfear_scan_create_batch", "cfear_scan_batch_size", "cfear_scan_batch_get", "cfear_scan_batch_destroy",
     "cfear_odometry_replay_clouds", "cfear_odometry_replay",
     "cfear_sc_detect_batch",
+    "cfear_kstrong_rowkeys_derive",
+    "cfear_odometry_grid_plan", "cfear_odometry_grid_create", "cfear_odometry_grid_process", "cfear_odometry_grid_destroy",
 ]
+
+
+class RowkeysClass(C.Structure):    # cfear_rowkeys_class
+    _fields_ = [("image", C.c_int32), ("k_strongest", C.c_int32), ("z_min", C.c_float), ("range_res", C.c_float),
+                ("min_distance", C.c_float)]
+
+
+# cfear_grid_stream: one record per stream of cfear_odometry_grid_plan
+GRID_STREAM_DTYPE = np.dtype([(n, "<i4") for n in ("sequence", "config", "sweep", "filter_class", "surface_group", "matcher_group",
+                                                   "surface_slot", "matcher_slot")])
+
+
+class GridTotals(C.Structure):      # cfear_grid_totals
+    _fields_ = [(n, C.c_int32) for n in ("n_streams", "n_sequences", "n_sweeps", "n_classes", "n_derived_classes",
+                                         "max_classes_per_sequence", "n_surface_groups", "n_matcher_groups")]
 REPLAY_AUDIT = 1                    # #define CFEAR_REPLAY_AUDIT
 
 # cfear_replay_frame: one record per frame of a replay (cfear_odometry_replay_clouds)
@@ -678,6 +695,14 @@ def lib():
     L.cfear_keyframe_based_fuse.argtypes = [C.POINTER(C.c_double), C.c_int32, C.c_double, C.c_double]
     L.cfear_acc_vel_sanity_check.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.cfear_odometry_get_covariance.argtypes = [vp, vp, vp]
+    L.cfear_kstrong_rowkeys_derive.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.POINTER(RowkeysClass),
+                                               C.c_int32, vp, vp]
+    L.cfear_odometry_grid_plan.argtypes = [C.POINTER(PolarDesc), C.POINTER(OdometryParams), C.c_int32, vp, vp, C.c_int32, vp,
+                                           C.POINTER(GridTotals), C.c_char_p, C.c_int32]
+    L.cfear_odometry_grid_create.argtypes = [vp, C.POINTER(PolarDesc), C.POINTER(OdometryParams), C.c_int32, vp, vp, C.c_int32,
+                                             C.POINTER(vp)]
+    L.cfear_odometry_grid_process.argtypes = [vp, vp, vp]
+    L.cfear_odometry_grid_destroy.argtypes = [vp]
     L.cfear_odometry_destroy.argtypes = [vp]
     L.cfear_rccl_unique_id.argtypes = [vp]
     L.cfear_rccl_comm_init.argtypes = [vp, vp, C.c_int32, C.c_int32, C.POINTER(RcclComm)]

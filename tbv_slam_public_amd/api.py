@@ -3028,6 +3028,110 @@ class OdometryKeyframeFuser:
             pass
 
 
+# ---- a parameter grid of odometry streams as one batch ---------------------------------------------------------
+def kstrong_rowkeys_derive(sel_range, sel_intensity, sel_count, classes, z_min_sup, ctx=None):
+    """cfear_kstrong_rowkeys_derive: the row keys of several k-strongest parameter sets from the sel_* lists of ONE sweep
+    (filter_kstrongest on torch CUDA images at (k_sup, z_min_sup), k_sup <= 64).  sel_range int32 / sel_intensity uint8
+    [n_images, rows, k_sup], sel_count int32 [n_images, rows]; classes: (image, k, z_min, range_res, min_distance) each.
+    Returns (row_keys uint32-as-int32 [n_classes, rows, 64], row_counts int32 [n_classes, rows, 2]) as CUDA tensors: what
+    filter_kstrongest_rowkeys gives image `image` with the class's own parameters, at a row stride of 64."""
+    import torch
+    ctx = ctx or default_context()
+    n_images, rows, k_sup = sel_range.shape
+    arr = (L.RowkeysClass * max(len(classes), 1))()
+    for i, (image, k, z_min, range_res, min_distance) in enumerate(classes):
+        arr[i] = L.RowkeysClass(int(image), int(k), float(z_min), float(range_res), float(min_distance))
+    keys = torch.zeros((len(classes), rows, 64), dtype=torch.int32, device=sel_range.device)
+    cnt = torch.zeros((len(classes), rows, 2), dtype=torch.int32, device=sel_range.device)
+    ctx.check(ctx._lib.cfear_kstrong_rowkeys_derive(ctx.h, _ptr(sel_range)[0], _ptr(sel_intensity)[0], _ptr(sel_count)[0], n_images, rows,
+                                                    k_sup, float(z_min_sup), arr, len(classes), _ptr(keys)[0], _ptr(cnt)[0]))
+    return keys, cnt
+
+
+def odometry_grid_configs(preset="CFEAR-3", dataset="oxford", **lists):
+    """The configurations of a parameter grid: the product of the keyword lists (names as in odometry_params) over
+    odometry_preset(preset, dataset), last keyword fastest -- the order of the reference's grid_search loops when the
+    keywords are given in its order.  A scalar is a list of one."""
+    import itertools
+    names = list(lists)
+    values = [list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] for v in lists.values()]
+    return [odometry_preset(preset, dataset, **dict(zip(names, combo))) for combo in itertools.product(*values)]
+
+
+def _grid_args(rows, cols, configs, n_sequences, stream_sequence, stream_config):
+    d = L.PolarDesc()
+    d.rows, d.cols, d.stride, d.batch = int(rows), int(cols), int(cols), int(n_sequences)
+    d.batch_stride = int(rows) * int(cols)
+    arr = (L.OdometryParams * max(len(configs), 1))()
+    for i, p in enumerate(configs):
+        C.memmove(C.byref(arr[i]), C.byref(p), C.sizeof(L.OdometryParams))
+    sq = None if stream_sequence is None else np.ascontiguousarray(stream_sequence, np.int32)
+    sc = None if stream_config is None else np.ascontiguousarray(stream_config, np.int32)
+    assert sq is None or sc is None or sq.shape == sc.shape
+    n = len(configs) * int(n_sequences) if sq is None and sc is None else len(sq if sq is not None else sc)
+    return d, arr, sq, sc, n
+
+
+def odometry_grid_plan(rows, cols, configs, n_sequences, stream_sequence=None, stream_config=None, n_streams=None):
+    """cfear_odometry_grid_plan: how OdometryGrid groups its streams, as dict(streams=GRID_STREAM_DTYPE array, totals=dict).
+    Host code only: needs no GPU and no context.  Raises CfearError with the refusal's reason."""
+    d, arr, sq, sc, n = _grid_args(rows, cols, configs, n_sequences, stream_sequence, stream_config)
+    n = n if n_streams is None else int(n_streams)
+    streams = np.zeros(max(n, 1), L.GRID_STREAM_DTYPE)
+    totals = L.GridTotals()
+    why = C.create_string_buffer(256)
+    rc = L.lib().cfear_odometry_grid_plan(C.byref(d), arr, len(configs), None if sq is None else sq.ctypes.data,
+                                          None if sc is None else sc.ctypes.data, n, streams.ctypes.data, C.byref(totals), why, 256)
+    if rc != L.OK:
+        raise L.CfearError(rc, why.value.decode())
+    return dict(streams=streams[:n], totals={name: int(getattr(totals, name)) for name, _ in L.GridTotals._fields_})
+
+
+class OdometryGrid:
+    """A parameter grid of odometry streams advanced one frame per call (the reference's grid_search / loss_function
+    evaluations: one job per (sequence, configuration)).  Stream s runs configs[stream_config[s]] on the images of sequence
+    stream_sequence[s]; with both None the streams are the full product, sequence-major and configuration fastest.  Per
+    stream the results are those of an OdometryKeyframeFuser with that configuration; the polar sweep runs once per sequence
+    image, the surface and matcher stages once per group of equal parameters (odometry_grid_plan)."""
+
+    def __init__(self, rows, cols, configs, n_sequences, stream_sequence=None, stream_config=None, ctx=None):
+        self.ctx = ctx or default_context()
+        d, arr, sq, sc, n = _grid_args(rows, cols, configs, n_sequences, stream_sequence, stream_config)
+        self.configs = list(configs)
+        self.n_streams, self.n_sequences = n, int(n_sequences)
+        self._h = C.c_void_p()
+        self.ctx.check(self.ctx._lib.cfear_odometry_grid_create(self.ctx.h, C.byref(d), arr, len(configs),
+                                                                None if sq is None else sq.ctypes.data,
+                                                                None if sc is None else sc.ctypes.data, n, C.byref(self._h)))
+        self.stream_sequence = np.repeat(np.arange(n_sequences), len(configs)) if sq is None else sq
+        self.stream_config = np.tile(np.arange(len(configs)), n_sequences) if sc is None else sc
+        self._info = np.zeros(n, L.FRAMEINFO_DTYPE)
+
+    _PER_STREAM = (L.ERR_EMPTY_CLOUD, L.ERR_CAPACITY)
+
+    def process(self, polar):
+        """polar: uint8 [n_sequences, rows, cols] (NumPy or torch CUDA).  Returns a FRAMEINFO_DTYPE array [n_streams]; a
+        stream's own failure (an empty sweep, a capacity overflow) is its info["reg_status"], not an exception."""
+        self._keep = polar
+        self._info[:] = 0
+        rc = self.ctx._lib.cfear_odometry_grid_process(self._h, _ptr(polar)[0], self._info.ctypes.data)
+        if not (rc in self._PER_STREAM and (self._info["reg_status"] == rc).any()):
+            self.ctx.check(rc)
+        return self._info.copy()
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self.ctx, "h", None):
+                self.ctx._lib.cfear_odometry_grid_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ---- simple_graph.sgh (types.cpp:103-130): host-only, no GPU ---------------------------------------------------
 def pose3d_from_xyt(xyt):
     """PoseEigToCeres of a planar pose -> (p [3], q [4] = x, y, z, w)."""

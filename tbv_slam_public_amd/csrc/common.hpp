@@ -373,6 +373,14 @@ struct cfear_kstrong_fused {
 int cfear_kstrong_device(cfear_ctx* ctx, const uint8_t* d_polar, const cfear_polar_desc* desc,
                          const cfear_kstrong_params* par, const cfear_kstrong_out* o, bool dense_halo = false,
                          const cfear_kstrong_fused* fused = nullptr);
+// Row keys of several parameter sets from one sweep's sel_* lists (kstrong_derive.hip).  A class as the kernel reads it;
+// cfear_kstrong_derive_class fills one from the caller's record, 0 = refused (image, k or threshold outside the sweep's).
+struct KstrongDeriveClass { int32_t image, k, u_zmin, min_range_bin; };
+int cfear_kstrong_derive_class(const cfear_rowkeys_class* in, int n_images, int k_sup, int u_sup, KstrongDeriveClass* out);
+// d_row_keys [n_classes][rows][64], d_row_counts [n_classes][rows][2]; everything in device memory, k_sup <= 64
+int cfear_kstrong_derive_device(cfear_ctx* ctx, const int32_t* d_sel_range, const uint8_t* d_sel_intensity, const int32_t* d_sel_count,
+                                int rows, int k_sup, const KstrongDeriveClass* d_classes, int n_classes, uint32_t* d_row_keys,
+                                int32_t* d_row_counts);
 // fused decode + sweep for [range bins][azimuths] sources (sd = the SOURCE images); key output only
 bool cfear_kstrong_cols_supported(const uint8_t* d_src, const cfear_polar_desc* sd, const cfear_kstrong_params* par);
 bool cfear_kstrong_cols_preferred(const uint8_t* d_src, const cfear_polar_desc* sd, const cfear_kstrong_params* par);   // ... and the batch is large enough to pay

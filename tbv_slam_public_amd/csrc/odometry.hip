@@ -16,8 +16,7 @@
 #include <cmath>
 #include <cstdlib>
 
-#include "covfit.hpp"
-#include "registration.hpp"
+#include "odometry_policy.hpp"
 
 // ---- frame policy as pure host functions (no GPU, no context): the two decisions OdometryKeyframeFuser takes per frame ----
 // KeyFrameBasedFuse (odometrykeyframefuser.cpp:62-73): diff = T_keyframe^-1 * Tcurrent as (x, y, theta).  For a planar
@@ -32,25 +31,6 @@ extern "C" int cfear_keyframe_based_fuse(const double diff_xyt[3], int32_t use_k
 extern "C" int cfear_acc_vel_sanity_check(const double tmot_prev_xy[2], const double tmot_curr_xy[2]) {
   return pose2d_acc_vel_sane(tmot_prev_xy, tmot_curr_xy);        // pose2d.hpp: the replay's score kernel takes it from there too
 }
-
-namespace {
-
-struct Keyframe { int slab; Aff2 pose; uint64_t idx = 0; };
-struct StreamState {
-  Aff2 T_prev = aff_identity(), Tmot = aff_identity(), Tcurrent = aff_identity();
-  std::vector<Keyframe> keyframes;
-  std::vector<int> free_slabs;
-  int cur_slab = -1;
-  Aff2 Tguess = aff_identity();
-  int job = -1;              // index into this call's registration batch, -1 = first frame
-  uint64_t n_keyframes = 0;  // RadarScan::counter of this stream
-  bool has_constraint = false;          // the last frame added a keyframe behind another one (AddToGraph)
-  uint64_t c_from = 0, c_to = 0;
-  Aff2 c_Tdiff = aff_identity();
-  double c_cov[36] = {0};
-};
-
-}  // namespace
 
 // Fused decode of [range bins][azimuths] sweeps: candidates per azimuth beyond which the rotation kernel + row sweep are the
 // quicker route (the lists cost ~17 ns of a 2048-sweep pass per candidate and azimuth: equal at ~84, tools/decode_bench.py
@@ -666,7 +646,7 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
   int cls_n[5] = {0, 0, 0, 0, 0};
   for (int b = 0; b < B; b++) {
     StreamState& st = od->streams[b];
-    st.Tguess = par.use_guess ? aff_mul(st.T_prev, st.Tmot) : st.T_prev;      // :164-168
+    frame_policy_guess(st, par);                                              // :164-168
     st.job = -1;
     if (st.keyframes.empty()) continue;                                       // :171-177 first frame: no registration
     const double e = est[b];
@@ -819,94 +799,16 @@ static int process_frame(cfear_odometry* od, const uint8_t* polar, const uint8_t
   bool saw_big = false;
   for (int b = 0; b < B; b++) {
     StreamState& st = od->streams[b];
-    cfear_frame_info& fi = info[b];
-    memset(&fi, 0, sizeof(fi));
-    fi.n_points = od->h_npts[b];
-    fi.n_cells = od->h_ncells[b];
-    st.has_constraint = false;                                    // whatever this frame does, the last constraint is no longer "the last frame's"
-    if (od->h_status[b] != CFEAR_OK) {
-      // empty cloud / capacity: the reference would exit(0) (pointnormal.cpp:72-75); report and keep the state
-      if (first_error == CFEAR_OK)
-        first_error = cfear_set_error(ctx, od->h_status[b], "stream %d: surface points failed (%s)", b, cfear_status_string(od->h_status[b]));
-      fi.reg_status = od->h_status[b];
-      st.free_slabs.push_back(st.cur_slab);
-      aff_to_xyt(st.Tcurrent, fi.pose);
-      continue;
+    FrameOutcome fo;
+    fo.n_points = od->h_npts[b]; fo.n_cells = od->h_ncells[b]; fo.status = od->h_status[b];
+    if (st.job >= 0) {
+      fo.rr = od->h_results + st.job;
+      if (par.estimate_cov_by_sampling) fo.samples = od->h_samples.get() + (size_t)st.job * od->fit.m;
     }
-    if (st.job < 0) {                                             // first frame becomes the first keyframe
-      st.keyframes.push_back(Keyframe{st.cur_slab, aff_identity(), st.n_keyframes++});
-      fi.keyframe_added = 1;
-      fi.reg_status = 1;
-      aff_to_xyt(st.Tcurrent, fi.pose);
-      continue;
-    }
-    const cfear_reg_result& rr = od->h_results[st.job];
-    fi.reg_status = rr.status; fi.outer_iters = rr.outer_iters; fi.lm_iters = rr.lm_iters; fi.score = rr.score;
-    od->cost_est[b] = (double)rr.num_residuals * (3.0 * rr.outer_iters + rr.lm_iters);   // association ~ 3 LM iterations
-    if (rr.reserved != 0.0) saw_big = true;
-    {                                                             // cov_current = cov_vek.back() (:196)
-      double* cv = od->cov.data() + (size_t)b * 36;
-      for (int k = 0; k < 36; k++) cv[k] = 0.0;
-      if (rr.status == CFEAR_OK) { cv[0] = 0.1 * 0.1; cv[7] = 0.1 * 0.1; cv[35] = 0.01 * 0.01; }   // n_scan_normal.cpp:171-175
-      else for (int k = 0; k < 6; k++) cv[k * 7] = 1.0;          // FormatScans' Identity66 survives a failed Register
-      od->cov_sampled[b] = 0;
-      if (par.estimate_cov_by_sampling && rr.num_residuals - 3 != 0) {         // GetCovarianceScaler (:433-439)
-        const int m = od->fit.m;
-        std::vector<double> costs(m);
-        double sample_cost = 0.0;                                 // a failed GetCost keeps the previous value (:282, 307)
-        for (int s = 0; s < m; s++) {
-          const cfear_reg_result& sr = od->h_samples[(size_t)st.job * m + s];
-          if (sr.status == CFEAR_OK) sample_cost = sr.final_cost;
-          costs[s] = sample_cost;
-        }
-        double c36[36];
-        if (od->fit.solve(costs.data(), rr.final_cost / (double)(rr.num_residuals - 3), par.cov_sampling.covariance_scaler, c36)) {
-          memcpy(cv, c36, sizeof(c36));
-          od->cov_sampled[b] = 1;
-        }
-      }
-    }
-    // Tcurrent = T_vek.back(): Register rewrites Tsrc via vectorToAffine3d (registration failures are
-    // ignored by the reference: `bool success` is shadowed, odometrykeyframefuser.cpp:184-193)
-    Aff2 Tcurrent = aff_from_xyt(rr.pose);
-    {                                                             // AccelerationVelocitySanityCheck :76-94
-      const Aff2 Tmot_current = aff_mul(aff_inv(st.T_prev), Tcurrent);
-      const double prev_xy[2] = {st.Tmot.t0, st.Tmot.t1}, curr_xy[2] = {Tmot_current.t0, Tmot_current.t1};
-      if (!cfear_acc_vel_sanity_check(prev_xy, curr_xy)) Tcurrent = st.Tguess;            // :198-199
-    }
-    st.Tmot = aff_mul(aff_inv(st.T_prev), Tcurrent);              // :200
-    const Aff2 Tkeydiff = aff_mul(aff_inv(st.keyframes.back().pose), Tcurrent);
-    double kd[3];
-    aff_to_xyt(Tkeydiff, kd);
-    const bool fuse = cfear_keyframe_based_fuse(kd, par.use_keyframe, par.min_keyframe_dist, par.min_keyframe_rot_deg) != 0;   // :62-73
-    if (fuse) {                                                   // :236-250, AddToReference :470-476
-      {                                                           // AddToGraph :428-445: constraint to the latest keyframe
-        const Keyframe& to = st.keyframes.back();
-        st.has_constraint = true;
-        st.c_from = st.n_keyframes; st.c_to = to.idx;
-        st.c_Tdiff = aff_mul(aff_inv(Tcurrent), to.pose);         // Tfrom^-1 * Tto
-        const double* cv = od->cov.data() + (size_t)b * 36;
-        memcpy(st.c_cov, cv, sizeof(st.c_cov));
-        // C.block<3,3>(0,0) = Tfrom^-1.rotation() * Cov.block<3,3>(0,0) * Tfrom^-1.rotation()^T
-        const Aff2 Ti = aff_inv(Tcurrent);
-        const double R[9] = {Ti.l0, Ti.l1, 0, Ti.l2, Ti.l3, 0, 0, 0, 1};
-        double t[9], o[9];
-        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) { t[r * 3 + c] = 0; for (int k = 0; k < 3; k++) t[r * 3 + c] += R[r * 3 + k] * cv[k * 6 + c]; }
-        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) { o[r * 3 + c] = 0; for (int k = 0; k < 3; k++) o[r * 3 + c] += t[r * 3 + k] * R[c * 3 + k]; }
-        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) st.c_cov[r * 6 + c] = o[r * 3 + c];
-      }
-      st.keyframes.push_back(Keyframe{st.cur_slab, Tcurrent, st.n_keyframes++});
-      if ((int)st.keyframes.size() > par.submap_scan_size) {
-        st.free_slabs.push_back(st.keyframes.front().slab);
-        st.keyframes.erase(st.keyframes.begin());
-      }
-      fi.keyframe_added = 1;
-    } else {
-      st.free_slabs.push_back(st.cur_slab);
-    }
-    st.Tcurrent = Tcurrent;
-    st.T_prev = Tcurrent;                                         // :257
-    aff_to_xyt(Tcurrent, fi.pose);
+    const int src = frame_policy_apply(st, par, fo, &od->fit, od->cov.data() + (size_t)b * 36, &od->cov_sampled[b], &od->cost_est[b],
+                                       &saw_big, info[b]);
+    if (src != CFEAR_OK && first_error == CFEAR_OK)
+      first_error = cfear_set_error(ctx, src, "stream %d: surface points failed (%s)", b, cfear_status_string(src));
   }
   for (int b = 0; b < B; b++) od->streams[b].cur_slab = -1;      // every slab is a keyframe or back on the free list
 #undef OD_CHECK
