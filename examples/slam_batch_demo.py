@@ -10,7 +10,10 @@
 
 The laps are the closed circle of examples/loop_closure_demo.py with different landmark seeds.  --loop-scaling weighs the
 loops: the reference's 500000 leaves the graph leaning on odometry, 1 trusts the verified loops as much as a step.
-    python examples/slam_batch_demo.py [--laps 3] [--frames 68] [--loop-scaling 1]"""
+--device-rows keeps the detector's rows in HBM and lets api.verify_sc_rows turn them into verified candidates there (the row
+mapping, the guess, the odometry bound, registration and verification in one call): detect -> verify -> solve, no candidate
+crosses to the host before it is verified.
+    python examples/slam_batch_demo.py [--laps 3] [--frames 68] [--loop-scaling 1] [--device-rows]"""
 import argparse
 import os
 import sys
@@ -22,10 +25,29 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import loop_closure_demo as demo          # noqa: E402
 
 
-def run(n_laps=3, n_frames=68, loop_scaling=1.0, log=None, per_lap_scan_context=False):
+def _verify_device_rows(api, nodes, poses, n_detect):
+    """detect -> verify with the rows left on the device -> (candidates [(lap, from, to)], accepted loops per lap)."""
+    n_laps = len(nodes)
+    flat = api.sc_flatten_graphs([([nd["peaks"] for nd in nodes[lap]], poses[lap]) for lap in range(n_laps)])
+    rows, n_out, _ = api.sc_detect_batch(flat=flat, n_aggregate=1, n_detect=n_detect, device_out=True)
+    all_poses = np.concatenate(poses)
+    graphs = dict(node_off=flat["node_off"], table=api.ScanTable([nd["scan"] for lap in range(n_laps) for nd in nodes[lap]]),
+                  xyzi=flat["xyzi"], point_off=flat["point_off"], poses=all_poses,
+                  rel=api.loop_relative_motions(all_poses, flat["node_off"]))
+    out = api.verify_sc_rows(graphs, rows, n_out, n_detect)
+    loops = [[] for _ in range(n_laps)]
+    for c, r in zip(out["list"], out["results"]):
+        if r["accepted"]:
+            loops[c["graph"]].append(dict(id_begin=int(c["from"]), id_end=int(c["to"]), t_be=r["t_be"].copy(), information=np.eye(6), type=1))
+    return [(int(c["graph"]), int(c["from"]), int(c["to"])) for c in out["list"]], loops
+
+
+def run(n_laps=3, n_frames=68, loop_scaling=1.0, log=None, per_lap_scan_context=False, device_rows=False, narrow_sc_sim=False):
     """-> dict(raw, corrected, gt [lap][node, 3], keyframes [lap] frame indices, candidates [(lap, from, to)], loops [lap] accepted
     constraints, pgo [lap] summaries, before, after).  per_lap_scan_context: one api.sc_detect_sequence call per lap, the loop the
-    batch call replaced (the candidates are the same)."""
+    batch call replaced (the candidates are the same).  device_rows: the rows stay on the device and api.verify_sc_rows verifies them
+    there.  narrow_sc_sim: the host loop passes (double)(float)min_dist as the reference does (loopclosure.cpp:677) and as
+    verify_sc_rows always does."""
     from tbv_slam_public_amd import api
     backend = demo.HipBackend()
     scenes = [demo.circle_scene(seed=21 + lap) for lap in range(n_laps)]
@@ -58,7 +80,10 @@ def run(n_laps=3, n_frames=68, loop_scaling=1.0, log=None, per_lap_scan_context=
     # ---- loop candidates of all graphs in ONE call, then ONE verification call for all laps ------------------------------
     cands, owner = [], []
     n_detect = [len(kf[lap]) - 1 for lap in range(n_laps)]
-    if per_lap_scan_context:
+    if device_rows:
+        found_all = []
+        cand_ids, loops = _verify_device_rows(api, nodes, poses, n_detect)
+    elif per_lap_scan_context:
         found_all = [api.sc_detect_sequence([nd["peaks"] for nd in nodes[lap]], poses[lap], n_aggregate=1, n_detect=n_detect[lap])
                      for lap in range(n_laps)]
     else:
@@ -70,14 +95,17 @@ def run(n_laps=3, n_frames=68, loop_scaling=1.0, log=None, per_lap_scan_context=
                 to = c["nn_idx"]
                 rel = [demo.xyt_compose(demo.xyt_inverse(poses[lap][k]), poses[lap][k + 1]) for k in range(to, i)]
                 guess = demo.xyt_compose(demo.xyt_inverse(np.asarray(c["Taug"], np.float64)), np.array([0.0, 0.0, c["yaw_diff_rad"]]))
-                cands.append({"from": i, "to": to, "from_pose": poses[lap][i], "t_be_guess": guess, "sc_sim": c["min_dist"],
+                sim = float(np.float32(c["min_dist"])) if narrow_sc_sim else c["min_dist"]
+                cands.append({"from": i, "to": to, "from_pose": poses[lap][i], "t_be_guess": guess, "sc_sim": sim,
                               "odom_bounds": backend.odom_bounds(np.array(rel).reshape(-1, 3))})
                 owner.append(lap)
     jobs = [dict(from_scan=nodes[lap][c["from"]]["scan"], to_scan=nodes[lap][c["to"]]["scan"], from_peaks=nodes[lap][c["from"]]["peaks"],
                  to_peaks=nodes[lap][c["to"]]["peaks"], from_pose=c["from_pose"], t_be_guess=c["t_be_guess"], sc_sim=c["sc_sim"],
                  odom_bounds=c["odom_bounds"], group=lap * n_frames + c["from"]) for lap, c in zip(owner, cands)]
     res = api.verify_loop_candidates(jobs) if jobs else None
-    loops = [[] for _ in range(n_laps)]
+    if not device_rows:
+        loops = [[] for _ in range(n_laps)]
+        cand_ids = [(lap, c["from"], c["to"]) for lap, c in zip(owner, cands)]
     for k, (lap, c) in enumerate(zip(owner, cands)):
         if res is not None and res["accepted"][k]:
             # the odometry constraints number the keyframes 0, 1, 2, ... per stream: so do the loops
@@ -99,7 +127,7 @@ def run(n_laps=3, n_frames=68, loop_scaling=1.0, log=None, per_lap_scan_context=
             gap = [np.hypot(*(t[-1, :2] - gt[lap][-1, :2])) for t in (poses[lap], corrected[lap])]
             log("%3d %6d %21d %6d %14d %18.3f -> %.3f %22.3f -> %.3f" % (lap, len(kf[lap]), len(cons[lap]), len(loops[lap]), solved[lap][1]["iterations"],
                                                                    gap[0], gap[1], summaries[lap]["ate"], summaries[n_laps + lap]["ate"]))
-    return dict(raw=poses, keyframes=kf, corrected=corrected, gt=gt, candidates=[(lap, c["from"], c["to"]) for lap, c in zip(owner, cands)],
+    return dict(raw=poses, keyframes=kf, corrected=corrected, gt=gt, candidates=cand_ids,
                 loops=loops, pgo=[s for _, s in solved], before=summaries[:n_laps], after=summaries[n_laps:])
 
 
@@ -108,5 +136,6 @@ if __name__ == "__main__":
     ap.add_argument("--laps", type=int, default=3)
     ap.add_argument("--frames", type=int, default=68)
     ap.add_argument("--loop-scaling", type=float, default=1.0)
+    ap.add_argument("--device-rows", action="store_true", help="keep the Scan Context rows on the device: detect -> verify_sc_rows -> solve")
     a = ap.parse_args()
-    run(a.laps, a.frames, a.loop_scaling, log=print)
+    run(a.laps, a.frames, a.loop_scaling, log=print, device_rows=a.device_rows)

@@ -1892,6 +1892,82 @@ int cfear_loop_stats_batch(cfear_ctx* ctx, const int64_t* node_offsets, const do
                            int32_t n_graphs, const cfear_loop_candidate* candidates, int64_t n_cand, const cfear_loop_stats_params* par,
                            cfear_loop_row* rows, int64_t* failed_candidate);
 
+/* ---- loop candidates of batched graphs, verified from the detector's rows ------------------------------------------------
+ * The body of ScanContextClosure::SearchAndAddConstraint (tbv_slam/src/tbv_slam/loopclosure.cpp:653-724) for a batch of
+ * complete graphs, as one device stage between cfear_sc_detect_batch (or any candidate proposer) and the pose-graph solve:
+ * the row -> (from, to, guess_nr) mapping, the `speedup` rule (:682-688), Tsrcguess = Taug^-1 * Rz(yaw) under transl_guess
+ * (:692-696), VerifyByOdometry (:776-806) and the verification chain of cfear_verify_loop_candidates, without the host
+ * seeing a candidate.  csrc/verify.hip; DESIGN.md has the data flow.
+ * The graphs lie one behind the other as in cfear_sc_batch: graph g owns nodes [node_off[g], node_off[g + 1]).          */
+typedef struct cfear_loop_graphs {
+  int32_t n_graphs, pad;
+  const int32_t* node_off;              /* [n_graphs + 1] host, from 0 to n_nodes                                         */
+  const cfear_scan_table* table;        /* n_nodes entries: entry k = node k's cloud_normal_ (a scan may be named twice)  */
+  const float* peaks_xyzi;              /* [peak_off[n_nodes]][4] cloud_peaks_ of all nodes, host (staged with one copy)
+                                           or device: the point buffer cfear_sc_batch takes in cloud mode                */
+  const int64_t* peak_off;              /* [n_nodes + 1] host                                                             */
+  const double* poses_xyt;              /* [n_nodes][3] host: GetPose()                                                   */
+  const double* rel_xyt;                /* [n_nodes][3] host: RelativeMotion(k, k + 1), the entry of a graph's last node
+                                           ignored; NULL only with verify_via_odometry = 0                               */
+} cfear_loop_graphs;                    /* 56 bytes */
+typedef struct cfear_loop_verify_candidate {
+  int32_t graph;                        /* index into node_off                                                            */
+  int32_t from, to;                     /* within the graph, to < from                                                    */
+  int32_t guess_nr;                     /* >= 0                                                                           */
+  int32_t query;                        /* candidates of one query share it (ApplyConstratins runs per query); the rows
+                                           form writes the flat node index of `from`                                     */
+  int32_t skip;                         /* 1: not registered (the speedup rule)                                           */
+  double guess_xyt[3];                  /* constraint.t_be on entry                                                       */
+  double sc_sim;                        /* quality["sc-sim"]                                                              */
+  double odom_term;                     /* what a skipped candidate reports as odom_bounds (min_dist_odom); else unused   */
+} cfear_loop_verify_candidate;          /* 64 bytes */
+typedef struct cfear_loop_verify_params {
+  cfear_verify_params verify;           /* use_covariance_sampling is refused here                                        */
+  double odom_sigma_error;              /* 0.03 (loopclosure.h:123)                                                       */
+  int32_t verify_via_odometry;          /* 1 (:122); 0: odom_bounds of every candidate is exactly 1                       */
+  int32_t transl_guess;                 /* 1 (:126); 0: the guess is (0, 0, yaw)                                          */
+  int32_t speedup;                      /* 0 (:127); the shipped TBV-8 parameter files set it                             */
+  int32_t odometry_coupled_closure;     /* 1: the detector's setting; the speedup rule needs both                         */
+} cfear_loop_verify_params;             /* 184 bytes */
+void cfear_loop_verify_params_default(cfear_loop_verify_params* p);
+#define CFEAR_LOOP_SPEEDUP_ODOM 0.7     /* min_dist_odom above which `speedup` skips a row (loopclosure.cpp:683)          */
+/* cands [n_cand], host or device.  Candidate j is verified as cfear_verify_loop_candidates verifies the job {table[from],
+ * table[to], the two nodes' peaks, poses_xyt[from], guess_xyt, sc_sim, odom_bounds, group = query} with
+ * odom_bounds = VerifyByOdometry(from, to) over rel_xyt[to .. from - 1] of its graph, computed on the device in the order of
+ * cfear_verify_by_odometry (its sin / cos / exp are the device's: the last place may differ from the host's libm).
+ * A candidate with skip set is not registered: reg_ok = 0, identity t_be and cov, zero coral / cfear / reg,
+ * alignment_quality = -20, odom_bounds = odom_term, sc_sim as given, probability = 0, accepted = 0, rank = -1, and it takes
+ * no part in ApplyConstratins.
+ * results [n_cand]: host (ApplyConstratins applied per query) or device (accepted = rank = 0, the selection is the
+ * caller's).  list_out [n_cand] (optional, host or device): the list as verified.  loops_out [n_cand] (optional, in the
+ * memory of results): {graph, from, to, guess_nr, guess_xyt = the result's t_be}, what cfear_loop_stats_batch takes.
+ * Refused before anything is launched or written, the message naming "graph g, node k" or "candidate j": node_off or
+ * peak_off that do not start at 0 or descend, a table whose size is not n_nodes, a candidate whose graph, from or to does
+ * not exist or with to >= from or a negative guess_nr, poses, guesses, sc_sim or used rel_xyt entries that are not finite,
+ * null arrays with positive counts, use_covariance_sampling.  With host inputs every check is made before the context is
+ * looked at and a null ctx is refused last.  A device list is checked by the kernel that reads it: the first bad candidate
+ * is named and nothing is written to the outputs.  A candidate whose two peak clouds together exceed what one CorAl job takes
+ * (16384 points) fails the call with CFEAR_ERR_CAPACITY naming it, the outputs untouched.  n_graphs = 0 or n_cand = 0: CFEAR_OK, the device
+ * untouched.                                                                                                            */
+int cfear_verify_graph_candidates(cfear_ctx* ctx, const cfear_loop_graphs* graphs, const cfear_loop_verify_candidate* cands,
+                                  int32_t n_cand, const cfear_loop_verify_params* par, cfear_verify_result* results,
+                                  cfear_loop_verify_candidate* list_out, cfear_loop_candidate* loops_out);
+/* The same from Scan Context rows exactly as cfear_sc_detect_batch leaves them: rows [D][n_candidates] and n_out [D], both
+ * host or both device, D = sum n_detect; n_detect [n_graphs] host (NULL: every node).  Row d of graph g is the query
+ * from = d - (first row of g), its record s < n_out[d] the candidate {to = nn_idx, guess_nr = s}; records past n_out[d]
+ * are ignored.  The candidates are compacted in (row, guess_nr) order; per candidate, on the device:
+ *   guess  = Taug^-1 * (0, 0, (double)yaw_diff_rad) with transl_guess, else (0, 0, yaw)
+ *   sc_sim = (double)(float)min_dist (:677)
+ *   skip   = speedup and odometry_coupled_closure and min_dist_odom > 0.7, then sc_sim = min_dist unnarrowed and
+ *            odom_term = min_dist_odom (:684)
+ * results, list_out, loops_out hold D * n_candidates records each, of which the first *n_list are written.  Also refused:
+ * n_detect[g] outside [0, nodes of g], rows and n_out in different memories, n_candidates < 1; host rows are checked on
+ * the host (n_out outside [0, n_candidates] is a bad row), device rows by the kernel.                                    */
+int cfear_verify_sc_rows(cfear_ctx* ctx, const cfear_loop_graphs* graphs, const cfear_sc_candidate* rows, const int32_t* n_out,
+                         const int32_t* n_detect, int32_t n_candidates, const cfear_loop_verify_params* par,
+                         cfear_verify_result* results, cfear_loop_verify_candidate* list_out, cfear_loop_candidate* loops_out,
+                         int32_t* n_list);
+
 /* cfear_loop_curves_batch: what place_recognition_radar/python/LoopClosureEval.py and evaluation/3_loop_closure/
  * 3_loop_closure.py ask of sklearn for a table of (label, score) rows -- metrics.roc_curve, metrics.auc,
  * precision_recall_curve, and ComputeClassifierStatistics at a probability threshold -- for a batch of experiments in one

@@ -1917,6 +1917,76 @@ inline std::vector<cfear_loop_row> LoopStats(CFEAR_Radarodometry::Context& ctx, 
   return rows;
 }
 
+// Loop candidates of a batch of graphs verified from the detector's rows (cfear_verify_sc_rows) or from a candidate list
+// (cfear_verify_graph_candidates): the body of ScanContextClosure::SearchAndAddConstraint (loopclosure.cpp:653-724) as one
+// device stage.  The graphs are added one behind the other; `table` holds one scan per node, in that order.
+struct LoopVerifyGraphs {
+  std::vector<int32_t> node_off = std::vector<int32_t>(1, 0);
+  const CFEAR_Radarodometry::ScanTable* table = nullptr;        // cloud_normal_ of every node
+  std::vector<float> peaks;                                      // cloud_peaks_ of every node, [points][4]
+  std::vector<int64_t> peak_off = std::vector<int64_t>(1, 0);
+  std::vector<CFEAR_Radarodometry::Pose2d> poses;                // GetPose()
+  std::vector<CFEAR_Radarodometry::Pose2d> rel;                  // RelativeMotion(k, k + 1); a graph's last entry is ignored
+  // one graph: a peaks cloud and a pose per node, and the odometry constraints' motions (one fewer, or none when
+  // verify_via_odometry is off)
+  void AddGraph(const std::vector<const CFEAR_Radarodometry::PointCloud*>& node_peaks, const std::vector<CFEAR_Radarodometry::Pose2d>& node_poses,
+                const std::vector<CFEAR_Radarodometry::Pose2d>& motions) {
+    if (node_peaks.size() != node_poses.size() || (!motions.empty() && motions.size() + 1 != node_poses.size()))
+      throw CFEAR_Radarodometry::CfearError(CFEAR_ERR_INVALID_ARGUMENT, "one cloud and one pose per node, one motion per step");
+    for (size_t i = 0; i < node_peaks.size(); i++) {
+      if (!node_peaks[i]->empty()) peaks.insert(peaks.end(), &(*node_peaks[i])[0].x, &(*node_peaks[i])[0].x + 4 * node_peaks[i]->size());
+      peak_off.push_back((int64_t)(peaks.size() / 4));
+      poses.push_back(node_poses[i]);
+      rel.push_back(i < motions.size() ? motions[i] : CFEAR_Radarodometry::Pose2d());
+    }
+    node_off.push_back(node_off.back() + (int32_t)node_peaks.size());
+  }
+  cfear_loop_graphs record() const {
+    static_assert(sizeof(CFEAR_Radarodometry::Pose2d) == 3 * sizeof(double), "Pose2d must be three packed doubles");
+    cfear_loop_graphs g = cfear_loop_graphs();
+    g.n_graphs = (int32_t)node_off.size() - 1;
+    g.node_off = node_off.data();
+    g.table = table ? table->get() : nullptr;
+    g.peaks_xyzi = peaks.empty() ? nullptr : peaks.data();
+    g.peak_off = peak_off.data();
+    g.poses_xyt = poses.empty() ? nullptr : &poses[0].x;
+    g.rel_xyt = rel.empty() ? nullptr : &rel[0].x;
+    return g;
+  }
+};
+struct LoopVerifyOutput {
+  std::vector<cfear_verify_result> results;          // one per compacted candidate, ApplyConstratins applied per query
+  std::vector<cfear_loop_verify_candidate> list;     // the candidates as verified
+  std::vector<cfear_loop_candidate> loops;           // guess_xyt = the registered t_be: what LoopStats takes
+};
+inline LoopVerifyOutput VerifyGraphCandidates(CFEAR_Radarodometry::Context& ctx, const LoopVerifyGraphs& graphs,
+                                              const std::vector<cfear_loop_verify_candidate>& candidates,
+                                              const cfear_loop_verify_params* par = nullptr) {
+  cfear_loop_verify_params def;
+  if (!par) { cfear_loop_verify_params_default(&def); par = &def; }
+  const cfear_loop_graphs g = graphs.record();
+  LoopVerifyOutput out;
+  out.results.resize(candidates.size()); out.list.resize(candidates.size()); out.loops.resize(candidates.size());
+  ctx.check(cfear_verify_graph_candidates(ctx.get(), &g, candidates.data(), (int32_t)candidates.size(), par, out.results.data(),
+                                          out.list.data(), out.loops.data()));
+  return out;
+}
+// rows [sum n_detect][n_candidates] and n_out [sum n_detect] as DetectLoopClosureBatch's call leaves them
+inline LoopVerifyOutput VerifyScRows(CFEAR_Radarodometry::Context& ctx, const LoopVerifyGraphs& graphs,
+                                     const std::vector<cfear_sc_candidate>& rows, const std::vector<int32_t>& n_out,
+                                     const std::vector<int32_t>& n_detect, int n_candidates, const cfear_loop_verify_params* par = nullptr) {
+  cfear_loop_verify_params def;
+  if (!par) { cfear_loop_verify_params_default(&def); par = &def; }
+  const cfear_loop_graphs g = graphs.record();
+  LoopVerifyOutput out;
+  out.results.resize(rows.size()); out.list.resize(rows.size()); out.loops.resize(rows.size());
+  int32_t n = 0;
+  ctx.check(cfear_verify_sc_rows(ctx.get(), &g, rows.data(), n_out.data(), n_detect.empty() ? nullptr : n_detect.data(), n_candidates, par,
+                                 out.results.data(), out.list.data(), out.loops.data(), &n));
+  out.results.resize((size_t)n); out.list.resize((size_t)n); out.loops.resize((size_t)n);
+  return out;
+}
+
 struct LoopExperiment {
   std::vector<uint8_t> y;                            // 0 or 1
   std::vector<double> score;

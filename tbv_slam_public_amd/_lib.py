@@ -348,6 +348,7 @@ EXPORTS = [
     "cfear_sc_detect_batch",
     "cfear_kstrong_rowkeys_derive",
     "cfear_odometry_grid_plan", "cfear_odometry_grid_create", "cfear_odometry_grid_process", "cfear_odometry_grid_destroy",
+    "cfear_loop_verify_params_default", "cfear_verify_graph_candidates", "cfear_verify_sc_rows",
 ]
 
 
@@ -515,6 +516,23 @@ LOOP_CURVES_RESULT_DTYPE = np.dtype([("auc", "<f8"), ("accuracy", "<f8"), ("prec
 assert C.sizeof(LoopStatsParams) == 40 and C.sizeof(LoopCurvesParams) == 16
 assert LOOP_CANDIDATE_DTYPE.itemsize == 40 and LOOP_ROW_DTYPE.itemsize == 88 and LOOP_CURVES_RESULT_DTYPE.itemsize == 96
 
+
+
+class LoopGraphs(C.Structure):          # cfear_loop_graphs
+    _fields_ = [("n_graphs", C.c_int32), ("pad", C.c_int32), ("node_off", C.c_void_p), ("table", C.c_void_p), ("peaks_xyzi", C.c_void_p),
+                ("peak_off", C.c_void_p), ("poses_xyt", C.c_void_p), ("rel_xyt", C.c_void_p)]
+
+
+class LoopVerifyParams(C.Structure):    # cfear_loop_verify_params
+    _fields_ = [("verify", VerifyParams), ("odom_sigma_error", C.c_double), ("verify_via_odometry", C.c_int32),
+                ("transl_guess", C.c_int32), ("speedup", C.c_int32), ("odometry_coupled_closure", C.c_int32)]
+
+
+LOOP_VERIFY_CANDIDATE_DTYPE = np.dtype([("graph", "<i4"), ("from", "<i4"), ("to", "<i4"), ("guess_nr", "<i4"), ("query", "<i4"),
+                                        ("skip", "<i4"), ("guess_xyt", "<f8", (3,)), ("sc_sim", "<f8"), ("odom_term", "<f8")])
+LOOP_SPEEDUP_ODOM = 0.7                           # CFEAR_LOOP_SPEEDUP_ODOM
+assert C.sizeof(LoopGraphs) == 56 and C.sizeof(LoopVerifyParams) == 184 and LOOP_VERIFY_CANDIDATE_DTYPE.itemsize == 64
+
 GRAPH_MAP_TILE = 256                              # CFEAR_GRAPH_MAP_TILE
 
 
@@ -646,6 +664,11 @@ def lib():
     L.cfear_verify_params_default.restype = None
     L.cfear_verify_loop_candidates.argtypes = [vp, C.POINTER(VerifyJob), C.c_int32, C.POINTER(VerifyParams), vp]
     L.cfear_verify_apply_constraints.argtypes = [vp, C.c_int32, C.POINTER(VerifyParams), vp]
+    L.cfear_loop_verify_params_default.argtypes = [C.POINTER(LoopVerifyParams)]
+    L.cfear_loop_verify_params_default.restype = None
+    L.cfear_verify_graph_candidates.argtypes = [vp, C.POINTER(LoopGraphs), vp, C.c_int32, C.POINTER(LoopVerifyParams), vp, vp, vp]
+    L.cfear_verify_sc_rows.argtypes = [vp, C.POINTER(LoopGraphs), vp, vp, vp, C.c_int32, C.POINTER(LoopVerifyParams), vp, vp, vp,
+                                       C.POINTER(C.c_int32)]
     L.cfear_verify_by_odometry.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_double)]
     L.cfear_get_cost.argtypes = [vp, C.POINTER(vp), C.c_int32, C.POINTER(C.c_double), C.POINTER(RegParams),
                                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32,

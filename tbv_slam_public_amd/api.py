@@ -1815,6 +1815,151 @@ def prepare_verify_batch(cands):
     return (arr, n, keep + [cands])
 
 
+def loop_verify_params(**kw):
+    """cfear_loop_verify_params with the reference's defaults (loopclosure.h:122-127: verify_via_odometry, odom_sigma_error
+    0.03, transl_guess, speedup off; odometry_coupled_closure as the detector's default).  Keywords name its own fields,
+    verify = a verify_params() record, or fields of that record."""
+    p = L.LoopVerifyParams()
+    L.lib().cfear_loop_verify_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k == "verify":
+            p.verify = v
+        elif k in ("odom_sigma_error", "verify_via_odometry", "transl_guess", "speedup", "odometry_coupled_closure"):
+            setattr(p, k, type(getattr(p, k))(v))
+        elif k in ("align_coef", "loop_coef"):
+            for i, x in enumerate(v):
+                getattr(p.verify, k)[i] = float(x)
+        else:
+            if k == "pad" or not hasattr(p.verify, k):
+                raise L.CfearError(L.ERR_INVALID_ARGUMENT, "unknown cfear_loop_verify_params field %r" % (k,))
+            setattr(p.verify, k, type(getattr(p.verify, k))(v))
+    return p
+
+
+def loop_relative_motions(poses_xyt, node_off):
+    """rel_xyt [n_nodes, 3] of cfear_loop_graphs from the nodes' poses: RelativeMotion(k, k + 1) = pose[k]^-1 * pose[k + 1]
+    within every graph (the entry of a graph's last node is 0), for graphs whose odometry constraints are their poses'."""
+    P = np.asarray(poses_xyt, np.float64).reshape(-1, 3)
+    rel = np.zeros_like(P)
+    for g in range(len(node_off) - 1):
+        for k in range(int(node_off[g]), int(node_off[g + 1]) - 1):
+            a, b = P[k], P[k + 1]
+            c, s = np.cos(a[2]), np.sin(a[2])
+            inv = np.array([-(c * a[0] + s * a[1]), s * a[0] - c * a[1], -a[2]])
+            ci, si = np.cos(inv[2]), np.sin(inv[2])
+            rel[k] = (ci * b[0] - si * b[1] + inv[0], si * b[0] + ci * b[1] + inv[1], inv[2] + b[2])
+    return rel
+
+
+def _loop_graphs(graphs):
+    """cfear_loop_graphs of dict(node_off, table, xyzi, point_off, poses, rel): the flat arrays of sc_flatten_graphs plus a
+    ScanTable over all nodes, the nodes' poses [n, 3] and their relative motions [n, 3] (or None) -> (record, keep-alive)."""
+    node_off = np.ascontiguousarray(graphs["node_off"], np.int32)
+    po = None if graphs.get("point_off") is None else np.ascontiguousarray(graphs["point_off"], np.int64)
+    poses = None if graphs.get("poses") is None else np.ascontiguousarray(graphs["poses"], np.float64)
+    rel = None if graphs.get("rel") is None else np.ascontiguousarray(graphs["rel"], np.float64)
+    xyzi = graphs.get("xyzi")
+    if xyzi is not None and not _is_torch(xyzi):
+        xyzi = np.ascontiguousarray(xyzi, np.float32)
+    g = L.LoopGraphs()
+    g.n_graphs = node_off.shape[0] - 1
+    g.node_off = node_off.ctypes.data
+    table = graphs.get("table")
+    g.table = table._h if table is not None else None
+    g.peaks_xyzi = _ptr(xyzi)[0]
+    g.peak_off = None if po is None else po.ctypes.data
+    g.poses_xyt = None if poses is None else poses.ctypes.data
+    g.rel_xyt = None if rel is None else rel.ctypes.data
+    return g, [node_off, po, poses, rel, xyzi, table]
+
+
+def _loop_verify_outputs(ctx, cap, device_out, want_loops):
+    if device_out:
+        import torch
+        dev = "cuda:%d" % ctx.device
+        res = torch.zeros(max(cap, 1) * L.VERIFY_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        lst = torch.zeros(max(cap, 1) * L.LOOP_VERIFY_CANDIDATE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        loops = torch.zeros(max(cap, 1) * L.LOOP_CANDIDATE_DTYPE.itemsize, dtype=torch.uint8, device=dev) if want_loops else None
+    else:
+        res = np.zeros(max(cap, 1), L.VERIFY_RESULT_DTYPE)
+        lst = np.zeros(max(cap, 1), L.LOOP_VERIFY_CANDIDATE_DTYPE)
+        loops = np.zeros(max(cap, 1), L.LOOP_CANDIDATE_DTYPE) if want_loops else None
+    return res, lst, loops
+
+
+def _loop_verify_result(n, res, lst, loops):
+    sizes = (L.VERIFY_RESULT_DTYPE.itemsize, L.LOOP_VERIFY_CANDIDATE_DTYPE.itemsize, L.LOOP_CANDIDATE_DTYPE.itemsize)
+    cut = [None if x is None else (x[:n * sz] if _is_torch(x) else x[:n]) for x, sz in zip((res, lst, loops), sizes)]
+    return dict(n=n, results=cut[0], list=cut[1], loops=cut[2])
+
+
+def loop_verify_candidates(cands):
+    """LOOP_VERIFY_CANDIDATE_DTYPE records from such an array or from dicts with graph, from, to and optionally guess_nr,
+    query (default: 2^16 graph + from), skip, guess_xyt, sc_sim, odom_term."""
+    if isinstance(cands, np.ndarray) and cands.dtype == L.LOOP_VERIFY_CANDIDATE_DTYPE:
+        return np.ascontiguousarray(cands)
+    out = np.zeros(len(cands), L.LOOP_VERIFY_CANDIDATE_DTYPE)
+    for i, c in enumerate(cands):
+        g, f = int(c.get("graph", 0)), int(c["from"])
+        out[i] = (g, f, int(c["to"]), int(c.get("guess_nr", 0)), int(c.get("query", (g << 16) + f)), int(c.get("skip", 0)),
+                  np.asarray(c.get("guess_xyt", (0.0, 0.0, 0.0)), np.float64).reshape(3), float(c.get("sc_sim", 0.0)),
+                  float(c.get("odom_term", 0.0)))
+    return out
+
+
+def verify_graph_candidates(graphs, cands, par=None, ctx=None, device_out=False, want_loops=False):
+    """cfear_verify_graph_candidates: a candidate list of a batch of graphs (MiniClosure / GTVicinity pairs, a caller's own)
+    verified as verify_loop_candidates verifies it, with the scans, peaks, poses and quality["odom-bounds"] looked up and
+    computed on the device.  graphs: dict(node_off, table = a ScanTable with one entry per node, xyzi + point_off = the
+    nodes' peaks as sc_flatten_graphs lays them out (NumPy or torch CUDA), poses [n, 3], rel [n, 3] or None (see
+    loop_relative_motions)).  cands: loop_verify_candidates() input, or a torch CUDA uint8 tensor of such records.
+    -> dict(n, results = VERIFY_RESULT_DTYPE records, list = LOOP_VERIFY_CANDIDATE_DTYPE records, loops =
+    LOOP_CANDIDATE_DTYPE records with guess_xyt = the registered t_be, if want_loops); with device_out all three as torch
+    CUDA uint8 tensors of the records' bytes, accepted = rank = 0 (verify_apply_constraints is the caller's)."""
+    ctx = ctx or default_context()
+    par = par or loop_verify_params()
+    g, keep = _loop_graphs(graphs)
+    if _is_torch(cands):
+        n = cands.numel() // L.LOOP_VERIFY_CANDIDATE_DTYPE.itemsize
+    else:
+        cands = loop_verify_candidates(cands)
+        n = cands.shape[0]
+    res, lst, loops = _loop_verify_outputs(ctx, n, device_out, want_loops)
+    _torch_ready(ctx, res, lst, loops, cands, graphs.get("xyzi"))
+    ctx.check(ctx._lib.cfear_verify_graph_candidates(ctx.h, C.byref(g), _ptr(cands)[0] if n else None, n, C.byref(par), _ptr(res)[0],
+                                                     _ptr(lst)[0], _ptr(loops)[0]))
+    del keep
+    return _loop_verify_result(n, res, lst, loops)
+
+
+def verify_sc_rows(graphs, rows, n_out, n_detect=None, par=None, ctx=None, device_out=False, want_loops=False):
+    """cfear_verify_sc_rows: the body of ScanContextClosure::SearchAndAddConstraint (loopclosure.cpp:653-724) for the rows
+    of sc_detect_batch(device_out=True) or (records=True), which never have to leave the device: row -> (from, to, guess_nr),
+    the speedup rule, Tsrcguess under transl_guess, VerifyByOdometry, registration and verification, ApplyConstratins per
+    query (host results).  graphs: as verify_graph_candidates; rows [D, n_candidates] SC_CANDIDATE_DTYPE (or the uint8
+    [D, n_candidates, 64] tensor), n_out [D]; n_detect one count per graph (default: every node).  -> as
+    verify_graph_candidates, n = the number of compacted candidates."""
+    ctx = ctx or default_context()
+    par = par or loop_verify_params()
+    g, keep = _loop_graphs(graphs)
+    nd = None if n_detect is None else np.ascontiguousarray(n_detect, np.int32)
+    if _is_torch(rows):
+        nc = int(rows.shape[1]) if rows.dim() >= 2 else 0
+    else:
+        rows = np.ascontiguousarray(rows, L.SC_CANDIDATE_DTYPE)
+        nc = int(rows.shape[1]) if rows.ndim == 2 else 0
+    if n_out is not None and not _is_torch(n_out):
+        n_out = np.ascontiguousarray(n_out, np.int32)
+    D = int(np.diff(np.asarray(graphs["node_off"])).clip(0).sum()) if nd is None else int(nd.clip(0).sum())
+    res, lst, loops = _loop_verify_outputs(ctx, D * max(nc, 0), device_out, want_loops)
+    n = C.c_int32(0)
+    _torch_ready(ctx, res, lst, loops, rows, n_out, graphs.get("xyzi"))
+    ctx.check(ctx._lib.cfear_verify_sc_rows(ctx.h, C.byref(g), _ptr(rows)[0], _ptr(n_out)[0], None if nd is None else nd.ctypes.data, nc,
+                                            C.byref(par), _ptr(res)[0], _ptr(lst)[0], _ptr(loops)[0], C.byref(n)))
+    del keep
+    return _loop_verify_result(int(n.value), res, lst, loops)
+
+
 def logreg_params(ctx=None, **kw):
     """cfear_logreg_params with the reference's settings (C = 1, balanced class weights, intercept, 100 Newton steps)."""
     p = L.LogregParams()

@@ -25,6 +25,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "pose2d.hpp"
 
 namespace {
 
@@ -124,20 +125,7 @@ __global__ __launch_bounds__(kClosureOrigins) void closure_odom_kernel(const Clo
   const int to = c->to;
   if (to < 0) return;
   if (!a.verify_via_odometry) { c->odom_bounds = 1.0; return; }
-  const double* rel = a.rel + 3 * b.node0;
-  double T0 = 0.0, T1 = 0.0, T2 = 0.0, trav = 0.0;
-  for (int k = i; k < to; k++) {
-    const double d0 = rel[3 * (size_t)k], d1 = rel[3 * (size_t)k + 1], d2 = rel[3 * (size_t)k + 2];
-    trav += sqrt(d0 * d0 + d1 * d1);
-    const double cs = cos(T2), sn = sin(T2);
-    const double x = cs * d0 - sn * d1 + T0, y = sn * d0 + cs * d1 + T1;
-    T0 = x; T1 = y; T2 = T2 + d2;
-  }
-  const double est = sqrt(T0 * T0 + T1 * T1);
-  const double over = est - 5.0;
-  const double error = over < 0.0 ? 0.0 : over;                 // std::max(over, 0.0): a NaN stays a NaN
-  const double r = error / trav;
-  c->odom_bounds = 1.0 - exp(-r * r / a.two_sigma2);
+  c->odom_bounds = odom_chain_similarity(a.rel + 3 * b.node0, i, to, a.two_sigma2);
 }
 
 }  // namespace

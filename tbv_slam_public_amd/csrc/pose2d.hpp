@@ -70,6 +70,27 @@ POSE2D_FN void xyt_inverse(const double a[3], double o[3]) {                    
   o[0] = x; o[1] = y; o[2] = -a[2];
 }
 
+#if defined(__HIPCC__)
+// loopclosure::VerifyByOdometry (loopclosure.cpp:783-795) on the device, for closure_odom_kernel (closure.hip) and
+// verify_fill_kernel (verify.hip): the motions rel[begin .. end) ([k][3], RelativeMotion(k, k + 1)) composed in order, in
+// the arithmetic and order of cfear_verify_by_odometry (verify.hip).  two_sigma2 = 2 sigma^2.
+__device__ __forceinline__ double odom_chain_similarity(const double* rel, int begin, int end, double two_sigma2) {
+  double T0 = 0.0, T1 = 0.0, T2 = 0.0, trav = 0.0;
+  for (int k = begin; k < end; k++) {
+    const double d0 = rel[3 * (size_t)k], d1 = rel[3 * (size_t)k + 1], d2 = rel[3 * (size_t)k + 2];
+    trav += sqrt(d0 * d0 + d1 * d1);
+    const double cs = cos(T2), sn = sin(T2);
+    const double x = cs * d0 - sn * d1 + T0, y = sn * d0 + cs * d1 + T1;
+    T0 = x; T1 = y; T2 = T2 + d2;
+  }
+  const double est = sqrt(T0 * T0 + T1 * T1);
+  const double over = est - 5.0;
+  const double error = over < 0.0 ? 0.0 : over;                 // std::max(over, 0.0): a NaN stays a NaN
+  const double r = error / trav;
+  return 1.0 - exp(-r * r / two_sigma2);
+}
+#endif
+
 // AccelerationVelocitySanityCheck (odometrykeyframefuser.cpp:76-94): 4 Hz, 200 m/s and 200 m/s^2, strict comparisons,
 // acceleration tested first; only the translations of the two motions enter.  1 = sane, 0 = use the guess (:198-199).
 POSE2D_FN int pose2d_acc_vel_sane(const double tmot_prev_xy[2], const double tmot_curr_xy[2]) {

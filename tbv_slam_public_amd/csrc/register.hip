@@ -114,13 +114,7 @@ extern "C" int cfear_register_batch(cfear_ctx* ctx, const cfear_reg_job* jobs, i
 // ---- candidate pairs among a table of scans (loop closure) ---------------------------------------------------------
 // The table holds a reference on every scan (cfear_scan::refs): a scan destroyed while a table still names it keeps its slab
 // until the table goes too, so a candidate can never read another scan's cells through a recycled slab.
-struct cfear_scan_table {
-  cfear_ctx* ctx = nullptr;
-  DevBuf<ScanView> d_views;             // [n] device
-  std::vector<int32_t> n_cells;         // host copy of the cell counts (launch geometry)
-  std::vector<cfear_scan*> scans;       // referenced handles
-};
-
+// (struct cfear_scan_table: registration.hpp)
 namespace {
 // candidate -> the job record matcher_kernel reads: scans {target, source}, poses {target, source guess}
 __global__ __launch_bounds__(256) void expand_candidates_kernel(const ScanView* __restrict__ views, const cfear_candidate* __restrict__ cands,

@@ -47,7 +47,13 @@ int cfear_reg_gather_job(cfear_ctx* ctx, const cfear_scan* const* scans, int n_s
 
 // candidate batches in two halves (register.hip; cfear_candidate_pipe in shard.hip runs them on different streams)
 struct CandGeometry { int pairs_cap = 1; RegLaunchHint hint; };
-struct cfear_scan_table;
+// A table of scans (register.hip makes and frees it; verify.hip reads its views as the nodes of batched graphs)
+struct cfear_scan_table {
+  cfear_ctx* ctx = nullptr;
+  DevBuf<ScanView> d_views;             // [n] device
+  std::vector<int32_t> n_cells;         // host copy of the cell counts (launch geometry)
+  std::vector<cfear_scan*> scans;       // referenced handles
+};
 int cfear_candidates_expand(cfear_ctx* ctx, hipStream_t stream, const cfear_scan_table* table, const cfear_candidate* cands, int32_t n,
                             const cfear_reg_params* par, cfear_candidate* h_stage, char* d_jobs, int32_t* d_trailer, int trailer_status,
                             CandGeometry* geom);

@@ -96,6 +96,7 @@ struct VerifyChain {
   const cfear_reg_result* q;
   const cfear_coral_result* coral;
   cfear_verify_result* out;
+  const int32_t* out_index;             // record j's place in `out` (the graph route skips candidates); nullptr: j
   int32_t* first_bad;                   // smallest candidate index whose CorAl job failed (INT_MAX: none)
   int n;
   cfear_verify_params par;
@@ -124,7 +125,7 @@ __global__ __launch_bounds__(256) void verify_prepare_kernel(const VerifyChain c
   const VerifyDev& v = c.cand[j];
   const cfear_reg_result reg = c.reg[j];
   const RegJob* rj = (const RegJob*)(c.reg_jobs + (size_t)j * c.stride);
-  cfear_verify_result& r = c.out[j];
+  cfear_verify_result& r = c.out[c.out_index ? c.out_index[j] : j];
   r.reg = reg;
   r.reg_ok = reg.status == CFEAR_OK ? 1 : 0;
   r.cov_sampled = 0;
@@ -174,7 +175,7 @@ __global__ __launch_bounds__(256) void verify_finish_kernel(const VerifyChain c)
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= c.n) return;
   const VerifyDev& v = c.cand[j];
-  cfear_verify_result& r = c.out[j];
+  cfear_verify_result& r = c.out[c.out_index ? c.out_index[j] : j];
   const cfear_coral_result co = c.coral[j];
   const cfear_reg_result q = c.q[j];
   if (co.status != CFEAR_OK && co.status != CFEAR_ERR_EMPTY_CLOUD) atomicMin(c.first_bad, j);
@@ -206,15 +207,17 @@ __global__ __launch_bounds__(256) void verify_finish_kernel(const VerifyChain c)
 // ApplyConstratins per query (candidates sharing `group`): sort by probability, larger first; accept above the threshold, every
 // candidate or only the best (loopclosure.cpp:261-274).  The keys are pulled out of the 480-byte records first (the sort then
 // walks 16-byte entries); candidate lists arrive grouped by query, so the usual case is one pass over short runs.
+// pick (optional, [n], ascending): the records that take part -- groups and results are indexed by pick[i] instead of i.
 void apply_constraints_groups(const int32_t* groups, size_t group_stride_bytes, size_t n, const cfear_verify_params* par,
-                              cfear_verify_result* results) {
+                              cfear_verify_result* results, const int32_t* pick = nullptr) {
   struct Key { int32_t group, index; double prob; };
   std::vector<Key> keys(n);
   bool grouped = true;
   for (size_t i = 0; i < n; i++) {
-    keys[i].group = *(const int32_t*)((const char*)groups + i * group_stride_bytes);
-    keys[i].index = (int32_t)i;
-    keys[i].prob = results[i].probability;
+    const size_t at = pick ? (size_t)pick[i] : i;
+    keys[i].group = *(const int32_t*)((const char*)groups + at * group_stride_bytes);
+    keys[i].index = (int32_t)at;
+    keys[i].prob = results[at].probability;
     grouped = grouped && (i == 0 || keys[i].group >= keys[i - 1].group);
   }
   // NaN (the odom-bounds feature of an empty odometry chain is 0/0) after every finite probability: `a.prob > b.prob` alone is
@@ -237,6 +240,61 @@ void apply_constraints_groups(const int32_t* groups, size_t group_stride_bytes, 
 }
 void apply_constraints(const cfear_verify_job* jobs, size_t n, const cfear_verify_params* par, cfear_verify_result* results) {
   if (n) apply_constraints_groups(&jobs[0].group, sizeof(cfear_verify_job), n, par, results);
+}
+
+// ---- the chain in three parts, shared by the two routes that fill VerifyDev: the host (verify_device_chain, from
+// cfear_verify_job records) and the device (verify_graph_route, from the candidates of batched graphs) ------------------
+// The chain's own buffers for n candidates, planned before carve(); `out`, `out_index` and `first_bad` are the route's.
+void verify_chain_plan(HostStage& st, VerifyChain& c, size_t n) {
+  c.stride = reg_job_stride(2);
+  c.out_index = nullptr;
+  st.piece(c.cand, n * sizeof(VerifyDev));
+  st.piece(c.reg_jobs, n * c.stride);
+  st.piece(c.cost_jobs, n * c.stride);
+  st.piece(c.coral_jobs, n * sizeof(CoralJob));
+  st.piece(c.reg, n * sizeof(cfear_reg_result));
+  st.piece(c.q, n * sizeof(cfear_reg_result));
+  st.piece(c.coral, n * sizeof(cfear_coral_result));
+}
+// The two matcher launches' parameters and geometry from the largest cell count among the candidates' scans, and the
+// matcher's scratch for n candidates.
+struct ChainGeometry {
+  cfear_reg_params rp, qp;
+  int pairs_cap = 1, pairs_cap_q = 1;
+  RegLaunchHint hint, hint_q;
+  char* scr = nullptr;
+};
+int verify_chain_geometry(cfear_ctx* ctx, int max_cells, size_t n, ChainGeometry& g) {
+  // RegisterLoopCandidate: P2L, Huber 0.1, uniform weights, SetParameters(4, 10) (loopclosure.cpp:56-57); CFEARQuality:
+  // n_scan_normal_reg(P2L, Huber, 0.3), fresh -- itr_ = 0 (AlignmentQuality.cpp:330-354)
+  cfear_reg_params_default(&g.rp);
+  g.rp.cost = CFEAR_P2L; g.rp.max_itr_association = 4; g.rp.max_itr_solver = 10;
+  cfear_reg_params_default(&g.qp);
+  g.qp.cost = CFEAR_P2L; g.qp.loss_limit = 0.3; g.qp.itr = 0;
+  cfear_reg_pair_geometry(&g.rp, max_cells, max_cells, &g.pairs_cap, &g.hint);
+  cfear_reg_pair_geometry(&g.qp, max_cells, max_cells, &g.pairs_cap_q, &g.hint_q);
+  g.hint_q.small_pairs = false;
+  g.scr = (char*)cfear_workspace(ctx, kWsRegScratch, reg_scratch_bytes(std::max(g.pairs_cap, g.pairs_cap_q)) * n);
+  if (!g.scr) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
+  return CFEAR_OK;
+}
+// expand -> matcher -> prepare -> matcher (cost only) -> coral -> finish over the n_jobs records at c.cand; cap = the largest
+// n_from + n_to among them.  Nothing is read back.
+int verify_chain_launch(cfear_ctx* ctx, VerifyChain& c, int32_t n_jobs, int cap, const cfear_verify_params* par, const ChainGeometry& g) {
+  c.n = n_jobs; c.par = *par;
+  const dim3 grid((unsigned)(((size_t)n_jobs + 255) / 256)), block(256);
+  { ProfScope ps(ctx, "verify_glue"); hipLaunchKernelGGL(verify_expand_kernel, grid, block, 0, ctx->stream, c); }
+  int rc = cfear_register_launch(ctx, c.reg_jobs, n_jobs, &g.rp, g.pairs_cap, g.scr, (cfear_reg_result*)c.reg, nullptr, c.stride, g.hint);
+  if (rc == CFEAR_OK) {
+    { ProfScope ps(ctx, "verify_glue"); hipLaunchKernelGGL(verify_prepare_kernel, grid, block, 0, ctx->stream, c); }
+    RegCostMode mode;                                        // GetCost at the jobs' own poses
+    rc = cfear_register_launch(ctx, c.cost_jobs, n_jobs, &g.qp, g.pairs_cap_q, g.scr, (cfear_reg_result*)c.q, &mode, c.stride, g.hint_q);
+  }
+  if (rc == CFEAR_OK) rc = cfear_coral_launch_device(ctx, c.coral_jobs, n_jobs, cap, &par->coral, (cfear_coral_result*)c.coral);
+  if (rc != CFEAR_OK) return rc;
+  { ProfScope ps(ctx, "verify_glue"); hipLaunchKernelGGL(verify_finish_kernel, grid, block, 0, ctx->stream, c); }
+  CFEAR_HIP_CHECK(ctx, hipGetLastError());
+  return CFEAR_OK;
 }
 
 int verify_device_chain(cfear_ctx* ctx, const cfear_verify_job* jobs, int32_t n_jobs, const cfear_verify_params* par,
@@ -271,32 +329,13 @@ int verify_device_chain(cfear_ctx* ctx, const cfear_verify_job* jobs, int32_t n_
   }
   // ---- device buffers: one workspace, carved ---------------------------------------------------------------------------
   VerifyChain c;
-  c.stride = reg_job_stride(2);
-  st.piece(c.cand, n * sizeof(VerifyDev));
-  st.piece(c.reg_jobs, n * c.stride);
-  st.piece(c.cost_jobs, n * c.stride);
-  st.piece(c.coral_jobs, n * sizeof(CoralJob));
-  st.piece(c.reg, n * sizeof(cfear_reg_result));
-  st.piece(c.q, n * sizeof(cfear_reg_result));
-  st.piece(c.coral, n * sizeof(cfear_coral_result));
+  verify_chain_plan(st, c, n);
   // results on the DEVICE (a sharded caller gathers them there): the finish kernel writes them in place, nothing but the error
   // flag comes back, and ApplyConstratins is the caller's (cfear_verify_apply_constraints over the gathered list)
   const bool host_out = st.out(c.out, results, n * sizeof(cfear_verify_result));
   st.piece(c.first_bad, 4);
-  // RegisterLoopCandidate: P2L, Huber 0.1, uniform weights, SetParameters(4, 10) (loopclosure.cpp:56-57); CFEARQuality:
-  // n_scan_normal_reg(P2L, Huber, 0.3), fresh -- itr_ = 0 (AlignmentQuality.cpp:330-354)
-  cfear_reg_params rp, qp;
-  cfear_reg_params_default(&rp);
-  rp.cost = CFEAR_P2L; rp.max_itr_association = 4; rp.max_itr_solver = 10;
-  cfear_reg_params_default(&qp);
-  qp.cost = CFEAR_P2L; qp.loss_limit = 0.3; qp.itr = 0;
-  int pairs_cap = 1, pairs_cap_q = 1;
-  RegLaunchHint hint, hint_q;
-  cfear_reg_pair_geometry(&rp, max_cells, max_cells, &pairs_cap, &hint);
-  cfear_reg_pair_geometry(&qp, max_cells, max_cells, &pairs_cap_q, &hint_q);
-  hint_q.small_pairs = false;
-  char* scr = (char*)cfear_workspace(ctx, kWsRegScratch, reg_scratch_bytes(std::max(pairs_cap, pairs_cap_q)) * n);
-  if (!scr) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
+  ChainGeometry geo;
+  CFEAR_CHECK(verify_chain_geometry(ctx, max_cells, n, geo));
   CFEAR_CHECK(st.carve());
   mark(0);
   VerifyDev* hc = (VerifyDev*)st.pinned(n * sizeof(VerifyDev));
@@ -312,21 +351,9 @@ int verify_device_chain(cfear_ctx* ctx, const cfear_verify_job* jobs, int32_t n_
     v.sc_sim = jb.sc_sim; v.odom_bounds = jb.odom_bounds;
   }
   mark(1);
-  c.n = n_jobs; c.par = *par;
-  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
   // ---- the chain ---------------------------------------------------------------------------------------------------------
   CFEAR_CHECK(st.upload((void*)c.cand, hc, n * sizeof(VerifyDev)));
-  { ProfScope ps(ctx, "verify_glue"); hipLaunchKernelGGL(verify_expand_kernel, grid, block, 0, ctx->stream, c); }
-  int rc = cfear_register_launch(ctx, c.reg_jobs, n_jobs, &rp, pairs_cap, scr, (cfear_reg_result*)c.reg, nullptr, c.stride, hint);
-  if (rc == CFEAR_OK) {
-    { ProfScope ps(ctx, "verify_glue"); hipLaunchKernelGGL(verify_prepare_kernel, grid, block, 0, ctx->stream, c); }
-    RegCostMode mode;                                        // GetCost at the jobs' own poses
-    rc = cfear_register_launch(ctx, c.cost_jobs, n_jobs, &qp, pairs_cap_q, scr, (cfear_reg_result*)c.q, &mode, c.stride, hint_q);
-  }
-  if (rc == CFEAR_OK) rc = cfear_coral_launch_device(ctx, c.coral_jobs, n_jobs, cap, &par->coral, (cfear_coral_result*)c.coral);
-  if (rc != CFEAR_OK) return rc;
-  { ProfScope ps(ctx, "verify_glue"); hipLaunchKernelGGL(verify_finish_kernel, grid, block, 0, ctx->stream, c); }
-  CFEAR_HIP_CHECK(ctx, hipGetLastError());
+  CFEAR_CHECK(verify_chain_launch(ctx, c, n_jobs, cap, par, geo));
   mark(2);
   st.back(&first_bad, c.first_bad, 4);
   CFEAR_CHECK(st.finish());
@@ -343,6 +370,434 @@ int verify_device_chain(cfear_ctx* ctx, const cfear_verify_job* jobs, int32_t n_
   fprintf(stderr, "verify us: scan clouds + sizes %.0f | fill records %.0f | enqueue the chain %.0f | kernels + read-back %.0f | ApplyConstratins %.0f\n",
           t_acc[0], t_acc[1], t_acc[2], t_acc[3], t_acc[4]);
 #endif
+  return CFEAR_OK;
+}
+
+// ---- the graph route: VerifyDev filled on the device from the candidates of batched graphs ---------------------------------
+// What ScanContextClosure::SearchAndAddConstraint does per candidate before it registers (loopclosure.cpp:653-701), for all
+// candidates of a batch of graphs at once and without the host seeing one:
+//   rows form only:  sc_rows_scan_kernel    the first candidate of every detector row (one workgroup's prefix sum over n_out)
+//                    sc_rows_expand_kernel  row records -> the compacted list in (row, guess_nr) order: from, to, guess_nr,
+//                                           the narrowed sc-sim, Tsrcguess, the speedup rule
+//   both forms:      graph_skip_scan_kernel every candidate's rank among the registered ones
+//                    verify_fill_kernel     list -> VerifyDev (views from the scan table, peaks from peak_off, the pose, and
+//                                           VerifyByOdometry over the graph's motions), validation, and the header
+//   ONE read-back of the 32-byte header; then the chain of verify_chain_launch over the registered candidates, writing each
+//   record at its place in the list, and
+//                    graph_list_finish_kernel  the records of the skipped candidates, and the cfear_loop_candidate list
+// A list of c candidates costs O(c) host work whatever the graphs' lengths: the odometry chains are walked by the lanes.
+constexpr int kNone = 0x7fffffff;
+
+struct GraphHeader {                    // the graph route's one read-back
+  int32_t n_list;                       // candidates in the compacted list
+  int32_t n_active;                     // of them not skipped: the chain's batch
+  int32_t max_points;                   // largest n_from + n_to among those
+  int32_t max_cells;                    // largest cell count among their scans
+  int32_t first_invalid;                // smallest index of a candidate that cannot be used (kNone: none)
+  int32_t first_capacity;               // ... whose two peak clouds exceed cfear_coral_max_points()
+  int32_t first_bad_row;                // rows form: smallest row whose n_out lies outside [0, n_candidates]
+  int32_t pad;
+};
+static_assert(sizeof(GraphHeader) == 32, "header record");
+
+struct GraphArgs {
+  const ScanView* views;                // [n_nodes] the scan table
+  const float4* peaks;                  // [peak_off[n_nodes]]
+  const int64_t* peak_off;              // [n_nodes + 1]
+  const double* poses;                  // [n_nodes][3]
+  const double* rel;                    // [n_nodes][3] or nullptr
+  const int32_t* node_off;              // [n_graphs + 1]
+  cfear_loop_verify_candidate* list;    // [cap] the compacted list
+  int32_t* active_rank;                 // [cap] candidates before j that are not skipped
+  int32_t* out_index;                   // [cap] registered candidate a -> its place j in the list
+  VerifyDev* cand;                      // [cap] the chain's records, dense over the registered candidates
+  GraphHeader* hdr;
+  cfear_verify_result* out;             // [cap]
+  cfear_loop_candidate* loops;          // [cap] or nullptr
+  // rows form
+  const cfear_sc_candidate* rows;       // [n_rows][nc]
+  const int32_t* n_out;                 // [n_rows]
+  const int32_t* det_off;               // [n_graphs + 1] the first row of every graph
+  int32_t* row_start;                   // [n_rows] the first candidate of every row
+  int32_t n_rows, nc;
+  int32_t n_graphs;
+  int32_t n_fixed;                      // list form: the list's length; rows form: -1 (hdr->n_list)
+  int32_t max_points_allowed;
+  int32_t verify_via_odometry, transl_guess, speedup_rule;
+  int32_t skipped_rank;                 // -1 for host results, 0 for device results (no selection was made)
+  double two_sigma2;
+};
+
+__host__ __device__ inline bool fin1(double x) { return fabs(x) <= 1.7976931348623157e308; }
+// 0: usable; else an index into kGraphCandFault.  The same test on the host (host lists) and in verify_fill_kernel.
+__host__ __device__ inline int graph_cand_fault(const cfear_loop_verify_candidate& c, const int32_t* node_off, int n_graphs) {
+  if (c.graph < 0 || c.graph >= n_graphs) return 1;
+  const int nn = node_off[c.graph + 1] - node_off[c.graph];
+  if (c.from < 0 || c.from >= nn) return 2;
+  if (c.to < 0 || c.to >= nn) return 3;
+  if (c.to >= c.from) return 4;
+  if (c.guess_nr < 0) return 5;
+  if (!fin1(c.guess_xyt[0]) || !fin1(c.guess_xyt[1]) || !fin1(c.guess_xyt[2])) return 6;
+  if (!fin1(c.sc_sim)) return 7;
+  return 0;
+}
+const char* const kGraphCandFault[] = {"", "its graph does not exist", "its from node does not exist", "its to node does not exist",
+                                       "to must lie before from", "guess_nr is negative", "its guess is not finite", "its sc_sim is not finite"};
+
+// Exclusive prefix sums of value(i), i < n, by ONE workgroup of 256 threads, 256 items a round: write(i, sum before i).
+// Returns the total in every thread.
+template <class V, class W>
+__device__ __forceinline__ int block_excl_scan_256(int n, V value, W write) {
+  __shared__ int wave_total[4];
+  const int wave = threadIdx.x >> 6;
+  int carry = 0;
+  for (int base = 0; base < n; base += 256) {
+    const int i = base + (int)threadIdx.x;
+    const int v = i < n ? value(i) : 0;
+    const int incl = wave_incl_scan_i32(v);
+    __syncthreads();                                   // the previous round's readers are done with wave_total
+    if ((threadIdx.x & 63) == 63) wave_total[wave] = incl;
+    __syncthreads();
+    int before = carry;
+    for (int w = 0; w < wave; w++) before += wave_total[w];
+    if (i < n) write(i, before + incl - v);
+    carry += ((wave_total[0] + wave_total[1]) + wave_total[2]) + wave_total[3];
+  }
+  return carry;
+}
+
+__global__ __launch_bounds__(256) void sc_rows_scan_kernel(const GraphArgs a) {
+  int bad = kNone;
+  const int total = block_excl_scan_256(
+      a.n_rows,
+      [&](int d) {
+        const int c = a.n_out[d];
+        if (c < 0 || c > a.nc) { bad = min(bad, d); return 0; }
+        return c;
+      },
+      [&](int d, int start) { a.row_start[d] = start; });
+  if (bad != kNone) atomicMin(&a.hdr->first_bad_row, bad);
+  if (threadIdx.x == 0) a.hdr->n_list = total;
+}
+
+// loopclosure.cpp:660-696 for record s of row d
+__global__ __launch_bounds__(256) void sc_rows_expand_kernel(const GraphArgs a) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (long long)a.n_rows * a.nc) return;
+  const int d = (int)(t / a.nc), s = (int)(t % a.nc);
+  const int cnt = a.n_out[d];
+  if (cnt < 0 || cnt > a.nc || s >= cnt) return;           // a bad row writes nothing (the host refuses it by the header)
+  int lo = 0, hi = a.n_graphs;                             // the last graph whose first row is <= d (empty graphs share a first row)
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (a.det_off[mid] <= d) lo = mid; else hi = mid;
+  }
+  const cfear_sc_candidate r = a.rows[(size_t)d * a.nc + s];
+  cfear_loop_verify_candidate c;
+  c.graph = lo;
+  c.from = d - a.det_off[lo];                              // idx_from = the query node (:660)
+  c.to = r.nn_idx;                                         // idx_to (:661)
+  c.guess_nr = s;                                          // std::distance(candidates.begin(), itr) (:675)
+  c.query = a.node_off[lo] + c.from;
+  c.skip = a.speedup_rule && r.min_dist_odom > CFEAR_LOOP_SPEEDUP_ODOM ? 1 : 0;   // :682-688
+  const double yaw[3] = {0.0, 0.0, (double)r.yaw_diff_rad};                         // rot_offset: -src_yaw_offset = sc_cand_yaw (:692-694)
+  if (a.transl_guess) {                                    // Tsrcguess = Taug^-1 * rot_offset (:695-696)
+    double inv[3];
+    xyt_inverse(r.Taug, inv);
+    xyt_compose(inv, yaw, c.guess_xyt);
+  } else {
+    c.guess_xyt[0] = yaw[0]; c.guess_xyt[1] = yaw[1]; c.guess_xyt[2] = yaw[2];
+  }
+  c.sc_sim = c.skip ? r.min_dist : (double)(float)r.min_dist;                       // `const float sc_cand_sim` (:677); :684 passes itr->min_dist
+  c.odom_term = r.min_dist_odom;
+  a.list[a.row_start[d] + s] = c;
+}
+
+__global__ __launch_bounds__(256) void graph_skip_scan_kernel(const GraphArgs a) {
+  const int n = a.n_fixed >= 0 ? a.n_fixed : a.hdr->n_list;
+  const int total = block_excl_scan_256(
+      n, [&](int j) { return a.list[j].skip ? 0 : 1; }, [&](int j, int rank) { a.active_rank[j] = rank; });
+  if (threadIdx.x == 0) { a.hdr->n_active = total; a.hdr->n_list = n; }
+}
+
+// One lane per candidate: the VerifyDev record verify_device_chain fills on the host, and quality["odom-bounds"]
+__global__ __launch_bounds__(256) void verify_fill_kernel(const GraphArgs a) {
+  const int n = a.n_fixed >= 0 ? a.n_fixed : a.hdr->n_list;
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const cfear_loop_verify_candidate c = a.list[j];
+  if (graph_cand_fault(c, a.node_off, a.n_graphs)) { atomicMin(&a.hdr->first_invalid, j); return; }
+  if (c.skip) return;
+  const int node0 = a.node_off[c.graph];
+  const int kf = node0 + c.from, kt = node0 + c.to;
+  const long long nf = a.peak_off[kf + 1] - a.peak_off[kf], nt = a.peak_off[kt + 1] - a.peak_off[kt];
+  if (nf + nt > a.max_points_allowed) { atomicMin(&a.hdr->first_capacity, j); return; }
+  const int at = a.active_rank[j];
+  a.out_index[at] = j;
+  VerifyDev& v = a.cand[at];
+  v.to = a.views[kt]; v.from = a.views[kf];
+  v.from_peaks = nf > 0 ? a.peaks + a.peak_off[kf] : nullptr;
+  v.to_peaks = nt > 0 ? a.peaks + a.peak_off[kt] : nullptr;
+  v.n_from = (int32_t)nf; v.n_to = (int32_t)nt;
+#pragma unroll
+  for (int k = 0; k < 3; k++) { v.from_pose[k] = a.poses[3 * (size_t)kf + k]; v.t_be_guess[k] = c.guess_xyt[k]; }
+  v.sc_sim = c.sc_sim;
+  // VerifyByOdometry(from, to): RelativeMotion(k, k + 1), k = to .. from - 1, of the candidate's graph (:776-806)
+  v.odom_bounds = a.verify_via_odometry ? odom_chain_similarity(a.rel + 3 * (size_t)node0, c.to, c.from, a.two_sigma2) : 1.0;
+  atomicMax(&a.hdr->max_points, (int)(nf + nt));
+  atomicMax(&a.hdr->max_cells, max(*v.to.n_cells, *v.from.n_cells));
+}
+
+// After the chain: a skipped candidate's record (UpdateStatistics' row of loopclosure.cpp:684 and a constraint that was never
+// registered: Tdiff and Cov keep their Identity), and the candidate list cfear_loop_stats_batch takes
+__global__ __launch_bounds__(256) void graph_list_finish_kernel(const GraphArgs a) {
+  const int n = a.n_fixed >= 0 ? a.n_fixed : a.hdr->n_list;
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const cfear_loop_verify_candidate c = a.list[j];
+  cfear_verify_result& r = a.out[j];
+  if (c.skip) {
+    double* w = (double*)&r;
+    for (int k = 0; k < (int)(sizeof(cfear_verify_result) / 8); k++) w[k] = 0.0;
+    for (int k = 0; k < 36; k += 7) r.cov[k] = 1.0;
+    r.alignment_quality = -20.0;
+    r.odom_bounds = c.odom_term;
+    r.sc_sim = c.sc_sim;
+    r.rank = a.skipped_rank;
+  }
+  if (a.loops) {
+    cfear_loop_candidate l;
+    l.graph = c.graph; l.from = c.from; l.to = c.to; l.guess_nr = c.guess_nr;
+    l.guess_xyt[0] = r.t_be[0]; l.guess_xyt[1] = r.t_be[1]; l.guess_xyt[2] = r.t_be[2];
+    a.loops[j] = l;
+  }
+}
+static_assert(sizeof(cfear_verify_result) % 8 == 0 && sizeof(cfear_loop_verify_candidate) == 64 && sizeof(cfear_loop_verify_params) == 184 &&
+                  sizeof(cfear_loop_graphs) == 56,
+              "records of the graph route");
+
+struct GraphRows {                      // the rows form's inputs; rows == nullptr: the list form
+  const cfear_sc_candidate* rows = nullptr;
+  const int32_t* n_out = nullptr;
+  const int32_t* n_detect = nullptr;
+  int32_t nc = 0;
+};
+
+// Everything that can be refused without a device, in the order the header gives.  n_nodes, n_rows and the rows' first row per
+// graph come back for the route.
+int graph_route_check(cfear_ctx* ctx, const cfear_loop_graphs* g, const cfear_loop_verify_candidate* cands, int32_t n_cand,
+                      const GraphRows& rw, const cfear_loop_verify_params* par, const void* results, const void* list_out,
+                      const void* loops_out, const int32_t* n_list, std::vector<int32_t>& det_off, int64_t* n_cap) {
+  const auto refuse = [&](const char* what) { return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "%s", what); };
+  if (!g || !par || n_cand < 0) return refuse("null or negative argument");
+  if (g->n_graphs < 0 || !g->node_off) return refuse("null or negative argument (node_off holds n_graphs + 1 entries)");
+  if (cfear_is_device_ptr(g->node_off) || cfear_is_device_ptr(g->peak_off) || cfear_is_device_ptr(g->poses_xyt) || cfear_is_device_ptr(g->rel_xyt) ||
+      cfear_is_device_ptr(rw.n_detect))
+    return refuse("node_off, peak_off, poses_xyt, rel_xyt and n_detect must be host memory");
+  if (par->verify.use_covariance_sampling) return refuse("use_covariance_sampling is not available for candidates verified on the device");
+  if (par->verify_via_odometry && !(par->odom_sigma_error == par->odom_sigma_error)) return refuse("odom_sigma_error is NaN");
+  const int G = g->n_graphs;
+  if (g->node_off[0] != 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "graph 0: node_off must start at 0");
+  for (int gi = 0; gi < G; gi++)
+    if (g->node_off[gi + 1] < g->node_off[gi]) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "graph %d: node_off descends", gi);
+  const int N = g->node_off[G];
+  if (N > 0 && (!g->peak_off || !g->poses_xyt)) return refuse("null peak_off or poses_xyt with nodes");
+  if (N > 0 && par->verify_via_odometry && !g->rel_xyt) return refuse("rel_xyt may be null only with verify_via_odometry = 0");
+  if (N > 0 && g->peak_off[0] != 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "graph 0, node 0: peak_off must start at 0");
+  for (int gi = 0; gi < G; gi++)
+    for (int k = g->node_off[gi]; k < g->node_off[gi + 1]; k++) {
+      const int kk = k - g->node_off[gi];
+      if (g->peak_off[k + 1] < g->peak_off[k] || g->peak_off[k + 1] - g->peak_off[k] > INT32_MAX)
+        return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "graph %d, node %d: peak_off descends (or more than 2^31 - 1 points)", gi, kk);
+      const double* p = g->poses_xyt + 3 * (size_t)k;
+      if (!fin1(p[0]) || !fin1(p[1]) || !fin1(p[2]))
+        return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "graph %d, node %d: a pose that is not finite", gi, kk);
+      if (par->verify_via_odometry && k + 1 < g->node_off[gi + 1]) {
+        const double* r = g->rel_xyt + 3 * (size_t)k;
+        if (!fin1(r[0]) || !fin1(r[1]) || !fin1(r[2]))
+          return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "graph %d, node %d: a relative motion that is not finite", gi, kk);
+      }
+    }
+  if (N > 0 && g->peak_off[N] > 0 && !g->peaks_xyzi) return refuse("null peaks_xyzi with points");
+  if (rw.rows || rw.n_out || n_list) {                     // the rows form
+    if (!n_list) return refuse("null n_list");
+    if (rw.nc < 1) return refuse("n_candidates must be at least 1");
+    det_off.assign((size_t)G + 1, 0);
+    for (int gi = 0; gi < G; gi++) {
+      const int nn = g->node_off[gi + 1] - g->node_off[gi], nd = rw.n_detect ? rw.n_detect[gi] : nn;
+      if (nd < 0 || nd > nn) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "graph %d: n_detect %d outside [0, %d]", gi, nd, nn);
+      det_off[(size_t)gi + 1] = det_off[(size_t)gi] + nd;
+    }
+    const int D = det_off[(size_t)G];
+    if ((int64_t)D * rw.nc > INT32_MAX) return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "more than 2^31 - 1 row records");
+    *n_cap = (int64_t)D * rw.nc;
+    if (D > 0 && (!rw.rows || !rw.n_out)) return refuse("null rows or n_out with detected nodes");
+    if (D > 0 && memory_kind({rw.rows, rw.n_out}) < 0) return refuse("rows and n_out must be both host or both device memory");
+    if (D > 0 && memory_kind({rw.rows}) == 0)
+      for (int gi = 0; gi < G; gi++)
+        for (int d = det_off[(size_t)gi]; d < det_off[(size_t)gi + 1]; d++) {
+          const int from = d - det_off[(size_t)gi];
+          if (rw.n_out[d] < 0 || rw.n_out[d] > rw.nc)
+            return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "graph %d, node %d: n_out %d outside [0, %d]", gi, from, rw.n_out[d], rw.nc);
+          for (int s = 0; s < rw.n_out[d]; s++) {
+            const cfear_sc_candidate& r = rw.rows[(size_t)d * rw.nc + s];
+            const bool finite = fin1(r.min_dist) && fin1(r.min_dist_odom) && fin1((double)r.yaw_diff_rad) && fin1(r.Taug[0]) && fin1(r.Taug[1]) && fin1(r.Taug[2]);
+            if (r.nn_idx < 0 || r.nn_idx >= from || !finite)
+              return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "graph %d, node %d: candidate %d %s", gi, from, s,
+                                     finite ? "names a node that is not before its query" : "is not finite");
+          }
+        }
+  } else {
+    *n_cap = n_cand;
+    if (n_cand > 0 && !cands) return refuse("null candidates with a positive count");
+    if (n_cand > 0 && !cfear_is_device_ptr(cands))
+      for (int j = 0; j < n_cand; j++) {
+        const int f = graph_cand_fault(cands[j], g->node_off, G);
+        if (f) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "candidate %d: %s", j, kGraphCandFault[f]);
+      }
+  }
+  if (*n_cap > 0 && !results) return refuse("null results with candidates");
+  if (memory_kind({results, loops_out}) < 0) return refuse("loops_out must lie in the memory of results");
+  (void)list_out;
+  if (N > 0 && !g->table) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null scan table: it must hold one entry per node (%d)", N);
+  if (g->table && (int)g->table->n_cells.size() != N)
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "the scan table holds %d scans, the graphs %d nodes", (int)g->table->n_cells.size(), N);
+  if (!ctx) return refuse("null context");
+  if (g->table && g->table->ctx != ctx) return refuse("the scan table belongs to another context");
+  return CFEAR_OK;
+}
+
+int verify_graph_route(cfear_ctx* ctx, const cfear_loop_graphs* g, const cfear_loop_verify_candidate* cands, int32_t n_cand,
+                       const GraphRows& rw, const cfear_loop_verify_params* par, cfear_verify_result* results,
+                       cfear_loop_verify_candidate* list_out, cfear_loop_candidate* loops_out, int32_t* n_list) {
+  if (n_list) *n_list = 0;
+  std::vector<int32_t> det_off;
+  int64_t n_cap = 0;
+  CFEAR_CHECK(graph_route_check(ctx, g, cands, n_cand, rw, par, results, list_out, loops_out, n_list, det_off, &n_cap));
+  if (g->n_graphs == 0 || n_cap == 0) return CFEAR_OK;
+  const bool rows_form = !det_off.empty();
+  const size_t cap = (size_t)n_cap, N = (size_t)g->node_off[g->n_graphs], G = (size_t)g->n_graphs;
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  HostStage st(ctx, kWsVerify);
+  GraphArgs a{};
+  a.views = g->table->d_views.get();
+  const float* d_peaks = nullptr;
+  st.in(d_peaks, g->peaks_xyzi, (size_t)g->peak_off[N] * 16);
+  st.in(a.peak_off, g->peak_off, (N + 1) * 8);
+  st.in(a.poses, g->poses_xyt, N * 24);
+  if (par->verify_via_odometry) st.in(a.rel, g->rel_xyt, N * 24);
+  st.in(a.node_off, g->node_off, (G + 1) * 4);
+  if (rows_form) {
+    a.n_rows = det_off[G]; a.nc = rw.nc;
+    st.in(a.rows, rw.rows, cap * sizeof(cfear_sc_candidate));
+    st.in(a.n_out, rw.n_out, (size_t)a.n_rows * 4);
+    st.piece(a.det_off, (G + 1) * 4);
+    st.piece(a.row_start, (size_t)a.n_rows * 4);
+  }
+  // outputs of the caller in host memory get a piece and ONE copy-back of the records that were written
+  const bool host_out = st.is_host(results);
+  const bool host_list = list_out && st.is_host(list_out), host_loops = loops_out && host_out;
+  const bool host_cands = !rows_form && st.is_host(cands);
+  if (host_out) st.piece(a.out, cap * sizeof(cfear_verify_result)); else a.out = results;
+  st.piece(a.list, cap * sizeof(cfear_loop_verify_candidate));   // a device list_out is written at the end: a refusal leaves it alone
+  if (host_loops) st.piece(a.loops, cap * sizeof(cfear_loop_candidate)); else a.loops = loops_out;
+  st.piece(a.active_rank, cap * 4);
+  st.piece(a.out_index, cap * 4);
+  st.piece(a.hdr, sizeof(GraphHeader));
+  VerifyChain c;
+  verify_chain_plan(st, c, cap);
+  st.piece(c.first_bad, 4);
+  CFEAR_CHECK(st.carve());
+  a.peaks = (const float4*)d_peaks;
+  a.cand = (VerifyDev*)c.cand;
+  a.n_graphs = g->n_graphs;
+  a.n_fixed = rows_form ? -1 : n_cand;
+  a.max_points_allowed = cfear_coral_max_points();
+  a.verify_via_odometry = par->verify_via_odometry;
+  a.transl_guess = par->transl_guess;
+  a.speedup_rule = par->speedup && par->odometry_coupled_closure;
+  a.skipped_rank = host_out ? -1 : 0;
+  a.two_sigma2 = 2.0 * par->odom_sigma_error * par->odom_sigma_error;
+  // ---- the small records: the header, the rows' first row per graph --------------------------------------------------------
+  const size_t rec_bytes = sizeof(GraphHeader) + (rows_form ? (G + 1) * 4 : 0);
+  char* rec = (char*)st.record(rec_bytes);
+  GraphHeader* h0 = (GraphHeader*)rec;
+  h0->first_invalid = h0->first_capacity = h0->first_bad_row = kNone;
+  CFEAR_CHECK(st.upload(a.hdr, h0, sizeof(GraphHeader)));
+  const dim3 block(256), grid_cap((unsigned)((cap + 255) / 256));
+  if (rows_form) {
+    memcpy(rec + sizeof(GraphHeader), det_off.data(), (G + 1) * 4);
+    CFEAR_CHECK(st.upload((void*)a.det_off, rec + sizeof(GraphHeader), (G + 1) * 4));
+    ProfScope ps(ctx, "verify_graph_fill");
+    hipLaunchKernelGGL(sc_rows_scan_kernel, dim3(1), block, 0, ctx->stream, a);
+    hipLaunchKernelGGL(sc_rows_expand_kernel, grid_cap, block, 0, ctx->stream, a);
+  } else if (host_cands) {
+    CFEAR_CHECK(st.upload(a.list, cands, cap * sizeof(cfear_loop_verify_candidate)));
+  } else {
+    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(a.list, cands, cap * sizeof(cfear_loop_verify_candidate), hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  {
+    ProfScope ps(ctx, "verify_graph_fill");
+    hipLaunchKernelGGL(graph_skip_scan_kernel, dim3(1), block, 0, ctx->stream, a);
+    hipLaunchKernelGGL(verify_fill_kernel, grid_cap, block, 0, ctx->stream, a);
+  }
+  CFEAR_HIP_CHECK(ctx, hipGetLastError());
+  GraphHeader hdr;
+  st.fetch(&hdr, a.hdr, sizeof(hdr));
+  CFEAR_CHECK(st.wait());
+  // ---- the device's refusals: nothing has been written to the caller's outputs yet ------------------------------------------
+  if (hdr.first_bad_row != kNone)
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "row %d: n_out outside [0, %d]", hdr.first_bad_row, rw.nc);
+  if (hdr.first_invalid != kNone)
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "candidate %d: its graph, from, to, guess_nr, guess or sc_sim are not usable", hdr.first_invalid);
+  if (hdr.first_capacity != kNone)
+    return cfear_set_error(ctx, CFEAR_ERR_CAPACITY, "candidate %d: its two peak clouds exceed %d points", hdr.first_capacity, cfear_coral_max_points());
+  const size_t n = (size_t)hdr.n_list;
+  if (n == 0) return st.finish();
+  // ---- the chain, with the geometry verify_device_chain takes for the same jobs -----------------------------------------------
+  int32_t first_bad = kNone;
+  if (hdr.n_active > 0) {
+    ChainGeometry geo;
+    CFEAR_CHECK(verify_chain_geometry(ctx, hdr.max_cells, (size_t)hdr.n_active, geo));
+    c.out = a.out;
+    c.out_index = a.out_index;
+    CFEAR_CHECK(verify_chain_launch(ctx, c, hdr.n_active, std::max(1, hdr.max_points), &par->verify, geo));
+    st.back(&first_bad, c.first_bad, 4);
+  }
+  {
+    ProfScope ps(ctx, "verify_graph_fill");
+    hipLaunchKernelGGL(graph_list_finish_kernel, dim3((unsigned)((n + 255) / 256)), block, 0, ctx->stream, a);
+  }
+  CFEAR_HIP_CHECK(ctx, hipGetLastError());
+  std::vector<cfear_loop_verify_candidate> own_list;       // ApplyConstratins needs the queries and the skip flags
+  const cfear_loop_verify_candidate* hl = list_out;
+  if (host_out) st.back(results, a.out, n * sizeof(cfear_verify_result));
+  if (host_list) st.back(list_out, a.list, n * sizeof(cfear_loop_verify_candidate));
+  else if (list_out)
+    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(list_out, a.list, n * sizeof(cfear_loop_verify_candidate), hipMemcpyDeviceToDevice, ctx->stream));
+  if (host_loops) st.back(loops_out, a.loops, n * sizeof(cfear_loop_candidate));
+  if (host_out && !host_list) {
+    own_list.resize(n);
+    st.back(own_list.data(), a.list, n * sizeof(cfear_loop_verify_candidate));
+    hl = own_list.data();
+  }
+  CFEAR_CHECK(st.finish());
+  if (first_bad != kNone) {
+    cfear_coral_result bad;
+    int32_t at = 0;
+    st.fetch(&bad, c.coral + first_bad, sizeof(bad));
+    st.fetch(&at, a.out_index + first_bad, 4);
+    CFEAR_CHECK(st.wait());
+    return cfear_set_error(ctx, bad.status, "candidate %d: %s", at, cfear_status_string(bad.status));
+  }
+  if (n_list) *n_list = (int32_t)n;
+  if (host_out) {
+    std::vector<int32_t> pick;
+    pick.reserve(n);
+    for (size_t j = 0; j < n; j++)
+      if (!hl[j].skip) pick.push_back((int32_t)j);
+    if (!pick.empty()) apply_constraints_groups(&hl[0].query, sizeof(cfear_loop_verify_candidate), pick.size(), &par->verify, results, pick.data());
+  }
   return CFEAR_OK;
 }
 
@@ -537,4 +992,30 @@ extern "C" int cfear_verify_apply_constraints(const int32_t* groups, int32_t n, 
   if (!par || n < 0 || (n > 0 && (!groups || !results))) return CFEAR_ERR_INVALID_ARGUMENT;
   if (n > 0) apply_constraints_groups(groups, sizeof(int32_t), (size_t)n, par, results);
   return CFEAR_OK;
+}
+
+extern "C" void cfear_loop_verify_params_default(cfear_loop_verify_params* p) {
+  if (!p) return;
+  cfear_verify_params_default(&p->verify);
+  p->odom_sigma_error = 0.03;                  // loopclosure.h:123
+  p->verify_via_odometry = 1;                  // :122
+  p->transl_guess = 1;                         // :126
+  p->speedup = 0;                              // :127
+  p->odometry_coupled_closure = 1;             // RSCManager's default, cfear_sc_manager_params_default
+}
+
+extern "C" int cfear_verify_graph_candidates(cfear_ctx* ctx, const cfear_loop_graphs* graphs, const cfear_loop_verify_candidate* cands,
+                                             int32_t n_cand, const cfear_loop_verify_params* par, cfear_verify_result* results,
+                                             cfear_loop_verify_candidate* list_out, cfear_loop_candidate* loops_out) {
+  return verify_graph_route(ctx, graphs, cands, n_cand, GraphRows(), par, results, list_out, loops_out, nullptr);
+}
+
+extern "C" int cfear_verify_sc_rows(cfear_ctx* ctx, const cfear_loop_graphs* graphs, const cfear_sc_candidate* rows, const int32_t* n_out,
+                                    const int32_t* n_detect, int32_t n_candidates, const cfear_loop_verify_params* par,
+                                    cfear_verify_result* results, cfear_loop_verify_candidate* list_out, cfear_loop_candidate* loops_out,
+                                    int32_t* n_list) {
+  if (!n_list) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null n_list");
+  GraphRows rw;
+  rw.rows = rows; rw.n_out = n_out; rw.n_detect = n_detect; rw.nc = n_candidates;
+  return verify_graph_route(ctx, graphs, nullptr, 0, rw, par, results, list_out, loops_out, n_list);
 }
