@@ -12,8 +12,10 @@ The laps are the closed circle of examples/loop_closure_demo.py with different l
 loops: the reference's 500000 leaves the graph leaning on odometry, 1 trusts the verified loops as much as a step.
 --device-rows keeps the detector's rows in HBM and lets api.verify_sc_rows turn them into verified candidates there (the row
 mapping, the guess, the odometry bound, registration and verification in one call): detect -> verify -> solve, no candidate
-crosses to the host before it is verified.
-    python examples/slam_batch_demo.py [--laps 3] [--frames 68] [--loop-scaling 1] [--device-rows]"""
+crosses to the host before it is verified.  --sampled-covariances (with --device-rows) adds api.verify_sample_covariances
+behind it -- use_covariance_sampling_in_loop_closure, sampled and fitted on the device -- so that an accepted loop carries
+information = inv(cov), and solves with the constraints' own information (replace_cov_by_identity = 0).
+    python examples/slam_batch_demo.py [--laps 3] [--frames 68] [--loop-scaling 1] [--device-rows [--sampled-covariances]]"""
 import argparse
 import os
 import sys
@@ -25,8 +27,9 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import loop_closure_demo as demo          # noqa: E402
 
 
-def _verify_device_rows(api, nodes, poses, n_detect):
-    """detect -> verify with the rows left on the device -> (candidates [(lap, from, to)], accepted loops per lap)."""
+def _verify_device_rows(api, nodes, poses, n_detect, sampled=False):
+    """detect -> verify with the rows left on the device [-> sampled covariances] -> (candidates [(lap, from, to)], accepted loops
+    per lap, how many of them carry a sampled covariance)."""
     n_laps = len(nodes)
     flat = api.sc_flatten_graphs([([nd["peaks"] for nd in nodes[lap]], poses[lap]) for lap in range(n_laps)])
     rows, n_out, _ = api.sc_detect_batch(flat=flat, n_aggregate=1, n_detect=n_detect, device_out=True)
@@ -35,20 +38,33 @@ def _verify_device_rows(api, nodes, poses, n_detect):
                   xyzi=flat["xyzi"], point_off=flat["point_off"], poses=all_poses,
                   rel=api.loop_relative_motions(all_poses, flat["node_off"]))
     out = api.verify_sc_rows(graphs, rows, n_out, n_detect)
+    if sampled:
+        api.verify_sample_covariances(graphs, out)
     loops = [[] for _ in range(n_laps)]
+    n_sampled = 0
     for c, r in zip(out["list"], out["results"]):
         if r["accepted"]:
-            loops[c["graph"]].append(dict(id_begin=int(c["from"]), id_end=int(c["to"]), t_be=r["t_be"].copy(), information=np.eye(6), type=1))
-    return [(int(c["graph"]), int(c["from"]), int(c["to"])) for c in out["list"]], loops
+            # the reference stores information = Cov.inverse().  Register's constant covariance has no inverse and keeps the
+            # identity; so does a sampled one that the reference's rotation (the x-y-z block alone, loopclosure.cpp:93) has left
+            # indefinite, which the solver would refuse
+            use = bool(r["cov_sampled"]) and np.linalg.eigvalsh(r["cov"]).min() > 0
+            info = np.linalg.inv(r["cov"]) if use else np.eye(6)
+            n_sampled += int(use)
+            loops[c["graph"]].append(dict(id_begin=int(c["from"]), id_end=int(c["to"]), t_be=r["t_be"].copy(), information=info, type=1))
+    return [(int(c["graph"]), int(c["from"]), int(c["to"])) for c in out["list"]], loops, n_sampled
 
 
-def run(n_laps=3, n_frames=68, loop_scaling=1.0, log=None, per_lap_scan_context=False, device_rows=False, narrow_sc_sim=False):
+def run(n_laps=3, n_frames=68, loop_scaling=1.0, log=None, per_lap_scan_context=False, device_rows=False, narrow_sc_sim=False,
+        sampled_covariances=False):
     """-> dict(raw, corrected, gt [lap][node, 3], keyframes [lap] frame indices, candidates [(lap, from, to)], loops [lap] accepted
     constraints, pgo [lap] summaries, before, after).  per_lap_scan_context: one api.sc_detect_sequence call per lap, the loop the
     batch call replaced (the candidates are the same).  device_rows: the rows stay on the device and api.verify_sc_rows verifies them
     there.  narrow_sc_sim: the host loop passes (double)(float)min_dist as the reference does (loopclosure.cpp:677) and as
-    verify_sc_rows always does."""
+    verify_sc_rows always does.  sampled_covariances (device_rows only): the accepted loops carry the inverse of their sampled
+    covariance and the solve uses every constraint's own information; the dict gains n_sampled."""
     from tbv_slam_public_amd import api
+    if sampled_covariances and not device_rows:
+        raise ValueError("sampled_covariances needs device_rows")
     backend = demo.HipBackend()
     scenes = [demo.circle_scene(seed=21 + lap) for lap in range(n_laps)]
     gt = []
@@ -82,7 +98,7 @@ def run(n_laps=3, n_frames=68, loop_scaling=1.0, log=None, per_lap_scan_context=
     n_detect = [len(kf[lap]) - 1 for lap in range(n_laps)]
     if device_rows:
         found_all = []
-        cand_ids, loops = _verify_device_rows(api, nodes, poses, n_detect)
+        cand_ids, loops, n_sampled = _verify_device_rows(api, nodes, poses, n_detect, sampled_covariances)
     elif per_lap_scan_context:
         found_all = [api.sc_detect_sequence([nd["peaks"] for nd in nodes[lap]], poses[lap], n_aggregate=1, n_detect=n_detect[lap])
                      for lap in range(n_laps)]
@@ -112,7 +128,19 @@ def run(n_laps=3, n_frames=68, loop_scaling=1.0, log=None, per_lap_scan_context=
             loops[lap].append(dict(id_begin=c["from"], id_end=c["to"], t_be=res["t_be"][k].copy(), information=np.eye(6), type=1))
     # ---- every graph in one solve, every trajectory in one evaluation ---------------------------------------------------
     graphs = [(poses[lap], np.arange(len(kf[lap])), cons[lap] + loops[lap]) for lap in range(n_laps)]
-    solved = api.pose_graph_optimize_batch(graphs, loop_scaling=loop_scaling)
+    own = {}
+    if sampled_covariances:
+        # every constraint's own information.  An odometry constraint's is the inverse of Register's constant covariance on
+        # (x, y, yaw) and zero on z, roll and pitch, which a planar graph never moves: a unit weight there makes it definite
+        own = dict(replace_cov_by_identity=0)
+        for lap in range(n_laps):
+            for c in cons[lap]:
+                info = np.array(c["information"], np.float64)
+                for k in (2, 3, 4):
+                    if info[k, k] == 0.0:
+                        info[k, k] = 1.0
+                c["information"] = info
+    solved = api.pose_graph_optimize_batch(graphs, loop_scaling=loop_scaling, **own)
     corrected = []
     for out, _ in solved:
         xyt = np.zeros((len(out), 3))
@@ -127,8 +155,14 @@ def run(n_laps=3, n_frames=68, loop_scaling=1.0, log=None, per_lap_scan_context=
             gap = [np.hypot(*(t[-1, :2] - gt[lap][-1, :2])) for t in (poses[lap], corrected[lap])]
             log("%3d %6d %21d %6d %14d %18.3f -> %.3f %22.3f -> %.3f" % (lap, len(kf[lap]), len(cons[lap]), len(loops[lap]), solved[lap][1]["iterations"],
                                                                    gap[0], gap[1], summaries[lap]["ate"], summaries[n_laps + lap]["ate"]))
-    return dict(raw=poses, keyframes=kf, corrected=corrected, gt=gt, candidates=cand_ids,
-                loops=loops, pgo=[s for _, s in solved], before=summaries[:n_laps], after=summaries[n_laps:])
+    out = dict(raw=poses, keyframes=kf, corrected=corrected, gt=gt, candidates=cand_ids,
+               loops=loops, pgo=[s for _, s in solved], before=summaries[:n_laps], after=summaries[n_laps:])
+    if sampled_covariances:
+        out["n_sampled"] = n_sampled
+        if log:
+            log("sampled covariances: %d of %d accepted loops carry information = inv(cov); mean ATE %.3f -> %.3f m" % (
+                n_sampled, sum(len(l) for l in loops), np.mean([s["ate"] for s in summaries[:n_laps]]), np.mean([s["ate"] for s in summaries[n_laps:]])))
+    return out
 
 
 if __name__ == "__main__":
@@ -137,5 +171,7 @@ if __name__ == "__main__":
     ap.add_argument("--frames", type=int, default=68)
     ap.add_argument("--loop-scaling", type=float, default=1.0)
     ap.add_argument("--device-rows", action="store_true", help="keep the Scan Context rows on the device: detect -> verify_sc_rows -> solve")
+    ap.add_argument("--sampled-covariances", action="store_true",
+                    help="with --device-rows: sample the accepted loops' covariances on the device and solve with the constraints' own information")
     a = ap.parse_args()
-    run(a.laps, a.frames, a.loop_scaling, log=print, device_rows=a.device_rows)
+    run(a.laps, a.frames, a.loop_scaling, log=print, device_rows=a.device_rows, sampled_covariances=a.sampled_covariances)

@@ -772,6 +772,29 @@ int cfear_covariance_by_sampling_batch(cfear_ctx* ctx, const cfear_reg_job* jobs
                                        const cfear_reg_params* par, const cfear_reg_result* regs,
                                        const cfear_cov_sampling_params* sp, double* cov36, double* samples,
                                        int32_t* success);
+/* The fit alone, as a kernel (csrc/covfit.hip): per job the carry-over of failed samples (a sample whose status is not
+ * CFEAR_OK keeps the previous cost, 0.0 before the first good one), the quadratic fit, the convexity test and
+ * 2 H^-1 * regs[j].final_cost / (regs[j].num_residuals - 3) * covariance_scaler -- cov36 and success are bit for bit what the
+ * host fit of cfear_covariance_by_sampling_batch makes of the same records.  A refused fit, or num_residuals - 3 == 0,
+ * leaves diag(0.01, 0.01, 0, 0, 0, 1e-4) and success = 0.
+ * regs [n_jobs], samples [n_jobs][n^3] (the records the matcher's sampling mode leaves: status and final_cost are read),
+ * cov36 [n_jobs][36], success [n_jobs]: all four in host memory or all four in device memory (then the call is only enqueued
+ * on the context's stream).  Refused before the context is used: null arguments, samples_per_axis outside [1, 15], pointers
+ * in different memories.  n_jobs = 0: CFEAR_OK, the device untouched.                                                    */
+int cfear_cov_fit_records(cfear_ctx* ctx, const cfear_reg_result* regs, const cfear_reg_result* samples, int32_t n_jobs,
+                          const cfear_cov_sampling_params* sp, double* cov36, int32_t* success);
+/* Covariance by cost sampling for candidate pairs of a scan table: the counterpart of cfear_register_candidates, with no host
+ * round trip between the samples and the covariance (the candidates become job records on the device, the matcher samples
+ * around centres it reads from device records, cov_fit_kernel fits).  Job j's problem is {table[target] fixed at target_xyt,
+ * table[source] free}; its samples are centred on regs[j].pose where regs[j].status is CFEAR_OK and on the candidate's
+ * source_xyt otherwise; the association radius follows regs[j].outer_iters.  par: the parameters of the registration that
+ * made regs.  candidates: host or device memory.  regs [n], cov36 [n][36], success [n]: all host (one read-back at the end)
+ * or all device (enqueued on the context's stream; with a device candidate list the call first waits for the 16-byte verdict
+ * of the kernel that reads it).  Refused: null arguments, samples_per_axis outside [1, 15], regs / cov36 / success in
+ * different memories, a candidate that names a scan outside the table ("candidate j ...").  n = 0: CFEAR_OK.             */
+int cfear_covariance_by_sampling_candidates(cfear_ctx* ctx, const cfear_scan_table* table, const cfear_candidate* candidates,
+                                            int32_t n_candidates, const cfear_reg_params* par, const cfear_reg_result* regs,
+                                            const cfear_cov_sampling_params* sp, double* cov36, int32_t* success);
 
 /* Ceres-compatible evaluation of one association set (what AddScanPairCost would hand to
  * ceres::Problem, n_scan_normal.cpp:264-318): prepare associates once at `poses_xyt`;
@@ -1967,6 +1990,22 @@ int cfear_verify_sc_rows(cfear_ctx* ctx, const cfear_loop_graphs* graphs, const 
                          const int32_t* n_detect, int32_t n_candidates, const cfear_loop_verify_params* par,
                          cfear_verify_result* results, cfear_loop_verify_candidate* list_out, cfear_loop_candidate* loops_out,
                          int32_t* n_list);
+/* Sampled covariances (use_covariance_sampling_in_loop_closure; loopclosure.cpp:62-71, 99-208) for candidates the two calls
+ * above verified, as a pass of its own: list [n_list] and results [n_list] are their list_out and results, both in host
+ * memory or both in device memory.  For every candidate with skip == 0 and results[j].reg_ok == 1: par->verify.sampling's
+ * n^3 GetCost samples around results[j].reg.pose with scans {to, from} of its graph and the target fixed at
+ * poses_xyt[from] * guess_xyt (P2L, Huber 0.1, uniform weights, the radius of reg.outer_iters), the fit of
+ * cfear_cov_fit_records, and -- where the fit is accepted -- the x-y-z block rotated by the inverse of the registered yaw into
+ * `cov`, with cov_sampled = 1.  A refused fit leaves the record as it is (Register's constant, rotated; cov_sampled = 0).  No
+ * other byte of any record changes; skipped and failed candidates are left as they are.  par->verify.use_covariance_sampling
+ * is not read, the graphs' peaks and rel_xyt neither.  Nothing crosses to the host between the samples and the covariance;
+ * the call reads one 16-byte header back before the samples (how many candidates take part, and the verdict on the list).
+ * Refused with nothing written, the message naming "graph g, node k" or "candidate j": node_off that does not start at 0 or
+ * descends, poses that are not finite, a table whose size is not n_nodes, samples_per_axis outside [1, 15], list and results
+ * in different memories, a candidate cfear_verify_graph_candidates would refuse, a registered pose that is not finite.  A
+ * device list is checked by the kernel that reads it.  n_graphs = 0 or n_list = 0: CFEAR_OK, the device untouched.       */
+int cfear_verify_sample_covariances(cfear_ctx* ctx, const cfear_loop_graphs* graphs, const cfear_loop_verify_candidate* list,
+                                    int32_t n_list, const cfear_loop_verify_params* par, cfear_verify_result* results);
 
 /* cfear_loop_curves_batch: what place_recognition_radar/python/LoopClosureEval.py and evaluation/3_loop_closure/
  * 3_loop_closure.py ask of sklearn for a table of (label, score) rows -- metrics.roc_curve, metrics.auc,

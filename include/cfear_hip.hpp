@@ -577,6 +577,19 @@ class n_scan_normal_reg {
     results.resize(candidates.size());
     ctx_.check(cfear_register_candidates(ctx_.get(), table.get(), candidates.data(), (int32_t)candidates.size(), &par_, results.data()));
   }
+  // loopclosure::approximateCovarianceBySampling for the same list, around the poses RegisterCandidates left in `results`
+  // (cfear_covariance_by_sampling_candidates: samples and fit on the device): cov36 [n][36] row-major, success [n].
+  void CovarianceBySamplingCandidates(const ScanTable& table, const std::vector<cfear_candidate>& candidates,
+                                      const std::vector<cfear_reg_result>& results, std::vector<double>& cov36, std::vector<int32_t>& success,
+                                      const cfear_cov_sampling_params* sp = nullptr) {
+    if (results.size() != candidates.size()) throw CfearError(CFEAR_ERR_INVALID_ARGUMENT, "CovarianceBySamplingCandidates: one registration record per candidate");
+    cfear_cov_sampling_params def;
+    cfear_cov_sampling_params_default(&def);
+    cov36.assign(candidates.size() * 36, 0.0); success.assign(candidates.size(), 0);
+    if (candidates.empty()) return;
+    ctx_.check(cfear_covariance_by_sampling_candidates(ctx_.get(), table.get(), candidates.data(), (int32_t)candidates.size(), &par_, results.data(),
+                                                       sp ? sp : &def, cov36.data(), success.data()));
+  }
   const cfear_reg_params& params() const { return par_; }
   double getScore() const { return score_; }
   bool GetCovarianceScaler(double& cov_scale) const {                                         // n_scan_normal.cpp:433-439
@@ -604,6 +617,17 @@ class n_scan_normal_reg {
   cfear_reg_params par_;
   double score_ = 0;
 };
+
+// The covariance fit of cost sampling alone, as a kernel (cfear_cov_fit_records): regs [n], samples [n][samples_per_axis^3]
+// as the matcher's sampling mode leaves them -> cov36 [n][36] row-major, success [n].
+inline void CovFitRecords(Context& ctx, const std::vector<cfear_reg_result>& regs, const std::vector<cfear_reg_result>& samples,
+                          const cfear_cov_sampling_params& sp, std::vector<double>& cov36, std::vector<int32_t>& success) {
+  const size_t m = (size_t)sp.samples_per_axis * sp.samples_per_axis * sp.samples_per_axis;
+  if (samples.size() != regs.size() * m) throw CfearError(CFEAR_ERR_INVALID_ARGUMENT, "CovFitRecords: samples_per_axis^3 sample records per job");
+  cov36.assign(regs.size() * 36, 0.0); success.assign(regs.size(), 0);
+  if (regs.empty()) return;
+  ctx.check(cfear_cov_fit_records(ctx.get(), regs.data(), samples.data(), (int32_t)regs.size(), &sp, cov36.data(), success.data()));
+}
 
 // Which registrations hang on a nearest-neighbour tie (cfear_association_ties_batch): the association
 // step of every job -- scans[j] with the free source last, poses[j] one per scan -- replayed at the poses given, one launch
@@ -1985,6 +2009,16 @@ inline LoopVerifyOutput VerifyScRows(CFEAR_Radarodometry::Context& ctx, const Lo
                                  out.results.data(), out.list.data(), out.loops.data(), &n));
   out.results.resize((size_t)n); out.list.resize((size_t)n); out.loops.resize((size_t)n);
   return out;
+}
+// Sampled covariances for what either call above returned (cfear_verify_sample_covariances): `cov` and `cov_sampled` of the
+// registered candidates in out.results are updated in place.
+inline void VerifySampleCovariances(CFEAR_Radarodometry::Context& ctx, const LoopVerifyGraphs& graphs, LoopVerifyOutput& out,
+                                    const cfear_loop_verify_params* par = nullptr) {
+  cfear_loop_verify_params def;
+  if (!par) { cfear_loop_verify_params_default(&def); par = &def; }
+  if (out.list.size() != out.results.size()) throw CFEAR_Radarodometry::CfearError(CFEAR_ERR_INVALID_ARGUMENT, "VerifySampleCovariances: one record per candidate");
+  const cfear_loop_graphs g = graphs.record();
+  ctx.check(cfear_verify_sample_covariances(ctx.get(), &g, out.list.data(), (int32_t)out.list.size(), par, out.results.data()));
 }
 
 struct LoopExperiment {

@@ -349,6 +349,7 @@ EXPORTS = [
     "cfear_kstrong_rowkeys_derive",
     "cfear_odometry_grid_plan", "cfear_odometry_grid_create", "cfear_odometry_grid_process", "cfear_odometry_grid_destroy",
     "cfear_loop_verify_params_default", "cfear_verify_graph_candidates", "cfear_verify_sc_rows",
+    "cfear_cov_fit_records", "cfear_covariance_by_sampling_candidates", "cfear_verify_sample_covariances",
 ]
 
 
@@ -669,6 +670,9 @@ def lib():
     L.cfear_verify_graph_candidates.argtypes = [vp, C.POINTER(LoopGraphs), vp, C.c_int32, C.POINTER(LoopVerifyParams), vp, vp, vp]
     L.cfear_verify_sc_rows.argtypes = [vp, C.POINTER(LoopGraphs), vp, vp, vp, C.c_int32, C.POINTER(LoopVerifyParams), vp, vp, vp,
                                        C.POINTER(C.c_int32)]
+    L.cfear_verify_sample_covariances.argtypes = [vp, C.POINTER(LoopGraphs), vp, C.c_int32, C.POINTER(LoopVerifyParams), vp]
+    L.cfear_cov_fit_records.argtypes = [vp, vp, vp, C.c_int32, C.POINTER(CovSamplingParams), vp, vp]
+    L.cfear_covariance_by_sampling_candidates.argtypes = [vp, vp, vp, C.c_int32, C.POINTER(RegParams), vp, C.POINTER(CovSamplingParams), vp, vp]
     L.cfear_verify_by_odometry.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_double)]
     L.cfear_get_cost.argtypes = [vp, C.POINTER(vp), C.c_int32, C.POINTER(C.c_double), C.POINTER(RegParams),
                                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32,

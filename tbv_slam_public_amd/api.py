@@ -1960,6 +1960,77 @@ def verify_sc_rows(graphs, rows, n_out, n_detect=None, par=None, ctx=None, devic
     return _loop_verify_result(int(n.value), res, lst, loops)
 
 
+def verify_sample_covariances(graphs, out, par=None, ctx=None):
+    """cfear_verify_sample_covariances: sampled covariances (use_covariance_sampling_in_loop_closure) for the candidates
+    verify_graph_candidates / verify_sc_rows verified, as a pass of its own.  out: the dict either returned, with host
+    records or with device_out; its `results` are updated IN PLACE -- `cov` and `cov_sampled` of every candidate that was
+    registered and whose fit is accepted, no other byte -- and `out` is returned.  par: loop_verify_params(); its
+    verify.sampling is what is read (use_covariance_sampling is not)."""
+    ctx = ctx or default_context()
+    par = par or loop_verify_params()
+    g, keep = _loop_graphs(graphs)
+    n = int(out["n"])
+    res, lst = out["results"], out["list"]
+    if not _is_torch(res) and not (res.flags["C_CONTIGUOUS"] and res.flags["WRITEABLE"]):
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "results must be a contiguous, writeable array: they are updated in place")
+    _torch_ready(ctx, res, lst)
+    ctx.check(ctx._lib.cfear_verify_sample_covariances(ctx.h, C.byref(g), _ptr(lst)[0] if n else None, n, C.byref(par),
+                                                       _ptr(res)[0] if n else None))
+    del keep
+    return out
+
+
+def cov_fit_records(regs, samples, sampling=None, ctx=None):
+    """cfear_cov_fit_records: the covariance fit of cost sampling as a kernel.  regs [n] RESULT_DTYPE, samples [n, m]
+    RESULT_DTYPE (m = samples_per_axis^3: the records the matcher's sampling mode leaves) -> (success [n] int32,
+    cov [n, 6, 6]).  With torch CUDA uint8 tensors of the records' bytes for both, the outputs are torch CUDA tensors
+    (int32 [n], float64 [n, 6, 6]) and the call is only enqueued."""
+    ctx = ctx or default_context()
+    sp = sampling or n_scan_normal_reg.sampling_params()
+    if _is_torch(regs) != _is_torch(samples):
+        raise L.CfearError(L.ERR_INVALID_ARGUMENT, "regs and samples must be both NumPy arrays or both torch CUDA tensors")
+    if _is_torch(regs):
+        import torch
+        n = regs.numel() // L.RESULT_DTYPE.itemsize
+        cov = torch.zeros((n, 6, 6), dtype=torch.float64, device=regs.device)
+        ok = torch.zeros(n, dtype=torch.int32, device=regs.device)
+    else:
+        regs = np.ascontiguousarray(regs, L.RESULT_DTYPE)
+        samples = np.ascontiguousarray(samples, L.RESULT_DTYPE)
+        n = regs.shape[0]
+        cov, ok = np.zeros((n, 6, 6), np.float64), np.zeros(n, np.int32)
+    _torch_ready(ctx, regs, samples, cov, ok)
+    ctx.check(ctx._lib.cfear_cov_fit_records(ctx.h, _ptr(regs)[0], _ptr(samples)[0], n, C.byref(sp), _ptr(cov)[0], _ptr(ok)[0]))
+    return ok, cov
+
+
+def covariance_by_sampling_candidates(table, cands, regs, par=None, sampling=None, ctx=None):
+    """cfear_covariance_by_sampling_candidates: covariance by cost sampling for candidate pairs of a ScanTable, the
+    counterpart of n_scan_normal_reg.RegisterCandidates, with no host round trip between the samples and the covariance.
+    cands: a CANDIDATE_DTYPE array or a torch CUDA uint8 tensor of such records; regs: the RESULT_DTYPE records of the
+    candidates' registration (NumPy), or a torch CUDA uint8 tensor of them -- then the outputs are torch CUDA tensors.
+    par: the RegParams (or n_scan_normal_reg) of that registration.  -> (success [n] int32, cov [n, 6, 6])."""
+    ctx = ctx or default_context()
+    reg = _tie_reg(par, ctx)
+    sp = sampling or n_scan_normal_reg.sampling_params()
+    if _is_torch(cands):
+        n = cands.numel() // L.CANDIDATE_DTYPE.itemsize
+    else:
+        cands = np.ascontiguousarray(cands, dtype=L.CANDIDATE_DTYPE)
+        n = cands.shape[0]
+    if _is_torch(regs):
+        import torch
+        cov = torch.zeros((n, 6, 6), dtype=torch.float64, device=regs.device)
+        ok = torch.zeros(n, dtype=torch.int32, device=regs.device)
+    else:
+        regs = np.ascontiguousarray(regs, L.RESULT_DTYPE)
+        cov, ok = np.zeros((n, 6, 6), np.float64), np.zeros(n, np.int32)
+    _torch_ready(ctx, cands, regs, cov, ok)
+    ctx.check(ctx._lib.cfear_covariance_by_sampling_candidates(ctx.h, table._h, _ptr(cands)[0] if n else None, n, C.byref(reg.par),
+                                                               _ptr(regs)[0], C.byref(sp), _ptr(cov)[0], _ptr(ok)[0]))
+    return ok, cov
+
+
 def logreg_params(ctx=None, **kw):
     """cfear_logreg_params with the reference's settings (C = 1, balanced class weights, intercept, 100 Newton steps)."""
     p = L.LogregParams()

@@ -350,6 +350,141 @@ extern "C" int cfear_covariance_by_sampling_batch(cfear_ctx* ctx, const cfear_re
   return CFEAR_OK;
 }
 
+// ---- the same for candidate pairs of a scan table, without the host between the samples and the covariance ------------------
+// centre -> expand -> matcher (cost only, RegCostMode::prior = the centres) -> cov_fit_kernel (covfit.hip).  The candidates and
+// the registration records may already sit on the device; nothing is read back on the way.
+namespace {
+constexpr int kCovNone = 0x7fffffff;
+// One lane per candidate: where its samples are centred and which radius they use, as a record the matcher's cost-only mode
+// takes for `prior`.  A registration that failed is sampled around the candidate's own source pose (what verify_host_chain's
+// `posed` does); outer_iters = 0 selects par.itr, as a job record's itr does.
+__global__ __launch_bounds__(256) void cov_centre_kernel(const ScanView* __restrict__ views, int n_table,
+                                                         const cfear_candidate* __restrict__ cands,
+                                                         const cfear_reg_result* __restrict__ regs, int n, int par_itr,
+                                                         cfear_reg_result* __restrict__ centre, int32_t* __restrict__ head) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const cfear_candidate c = cands[j];
+  if (c.target < 0 || c.target >= n_table || c.source < 0 || c.source >= n_table) { atomicMin(&head[0], j); return; }
+  cfear_reg_result r = regs[j];
+  if (r.status != CFEAR_OK) { r.pose[0] = c.source_xyt[0]; r.pose[1] = c.source_xyt[1]; r.pose[2] = c.source_xyt[2]; }
+  if (r.outer_iters == 0) r.outer_iters = par_itr;
+  centre[j] = r;
+  atomicMax(&head[1], *views[c.target].n_cells);
+  atomicMax(&head[2], *views[c.source].n_cells);
+}
+}  // namespace
+
+void CovSamplePass::plan(HostStage& st, int n_jobs, int samples_per_axis, size_t extra_bytes) {
+  n = n_jobs; spa = samples_per_axis; m = spa * spa * spa; extra = extra_bytes;
+  st.piece(d_jobs, (size_t)n * reg_job_stride(2));
+  st.piece(d_centre, (size_t)n * sizeof(cfear_reg_result));
+  st.piece(d_samples, (size_t)n * m * sizeof(cfear_reg_result));
+  st.piece(d_block, pinv_bytes() + extra);
+}
+
+int CovSamplePass::stage(HostStage& st, const cfear_cov_sampling_params* sp) {
+  h_block = (char*)st.pinned(pinv_bytes() + extra);
+  if (!h_block) return CFEAR_ERR_HIP;
+  cfear_cov_fit_fill_pinv(sp, (double*)h_block);
+  return CFEAR_OK;
+}
+
+int CovSamplePass::upload(HostStage& st) { return st.upload(d_block, h_block, pinv_bytes() + extra); }
+
+int CovSamplePass::centre(cfear_ctx* ctx, const cfear_scan_table* table, const cfear_candidate* d_cands, const cfear_reg_result* d_regs,
+                          int n_jobs, const cfear_reg_params* par, int32_t* d_head) const {
+  ProfScope ps(ctx, "cov_glue");
+  hipLaunchKernelGGL(cov_centre_kernel, dim3((n_jobs + 255) / 256), dim3(256), 0, ctx->stream, (const ScanView*)table->d_views.get(),
+                     (int)table->n_cells.size(), d_cands, d_regs, n_jobs, (int)par->itr, d_centre, d_head);
+  CFEAR_HIP_CHECK(ctx, hipGetLastError());
+  return CFEAR_OK;
+}
+
+int CovSamplePass::sample_and_fit(cfear_ctx* ctx, const cfear_scan_table* table, const cfear_candidate* d_cands, int n_jobs,
+                                  int max_tar_cells, int max_src_cells, const cfear_reg_params* par, const cfear_reg_result* d_regs,
+                                  const cfear_cov_sampling_params* sp, double* d_cov36, int32_t* d_success) const {
+  const size_t stride = reg_job_stride(2);
+  {
+    ProfScope ps(ctx, "cov_glue");
+    hipLaunchKernelGGL(expand_candidates_kernel, dim3((n_jobs + 255) / 256), dim3(256), 0, ctx->stream, (const ScanView*)table->d_views.get(),
+                       d_cands, n_jobs, d_jobs, stride, (int32_t*)nullptr, 0);
+    CFEAR_HIP_CHECK(ctx, hipGetLastError());
+  }
+  const JobSizes sz = JobSizes(par).add(2, scan_grid_pad(max_tar_cells), scan_grid_pad(max_tar_cells), max_src_cells);
+  RegCostMode mode;
+  mode.samples_per_axis = spa;
+  mode.n_samples = m;
+  mode.xy_half = sp->xy_range * 0.5;                       // odometrykeyframefuser.cpp:276-277
+  mode.yaw_half = sp->yaw_range * 0.5;
+  // as run_cost_batch: a few workgroups per job when the batch alone cannot fill the GPU; scratch bounded to 1 GiB per launch
+  mode.blocks_per_job = std::max(1, std::min(m, (1024 + n_jobs - 1) / n_jobs));
+  const size_t per = reg_scratch_bytes(sz.pairs_cap) * (size_t)mode.blocks_per_job;
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_jobs, ((size_t)1 << 30) / per));
+  char* scr = (char*)cfear_workspace(ctx, kWsRegScratch, per * (size_t)chunk);
+  if (!scr) return cfear_set_error(ctx, CFEAR_ERR_HIP, "workspace allocation failed");
+  for (int j0 = 0; j0 < n_jobs; j0 += chunk) {
+    const int nj = std::min(chunk, n_jobs - j0);
+    mode.prior = d_centre + j0;
+    CFEAR_CHECK(cfear_register_launch(ctx, d_jobs + (size_t)j0 * stride, nj, par, sz.pairs_cap, scr, d_samples + (size_t)j0 * m, &mode, stride,
+                                      sz.hint(nj)));
+  }
+  return cfear_cov_fit_launch(ctx, d_regs, d_samples, n_jobs, m, (const double*)d_block, sp->covariance_scaler, d_cov36, d_success);
+}
+
+extern "C" int cfear_covariance_by_sampling_candidates(cfear_ctx* ctx, const cfear_scan_table* table, const cfear_candidate* cands, int32_t n,
+                                                       const cfear_reg_params* par, const cfear_reg_result* regs,
+                                                       const cfear_cov_sampling_params* sp, double* cov36, int32_t* success) {
+  if (!table || !regs || !sp || !cov36 || !success || n < 0 || (n > 0 && !cands)) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null argument");
+  CFEAR_CHECK(cfear_cov_check_sampling(ctx, sp));
+  if (memory_kind({regs, cov36, success}) < 0)
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "regs, cov36 and success must be all host or all device memory");
+  CFEAR_CHECK(cfear_check_reg_params(ctx, par));
+  if (!ctx) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null context");      // (a table cannot exist without one)
+  if (table->ctx != ctx) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "table belongs to another context");
+  const bool host_cands = n > 0 && !cfear_is_device_ptr(cands);
+  const int nt = (int)table->n_cells.size();
+  int max_tar = 0, max_src = 0;
+  for (int i = 0; host_cands && i < n; i++) {
+    const cfear_candidate& c = cands[i];
+    if (c.target < 0 || c.target >= nt || c.source < 0 || c.source >= nt)
+      return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "candidate %d refers to scan %d / %d of a table of %d", i, c.target, c.source, nt);
+    max_tar = std::max(max_tar, table->n_cells[(size_t)c.target]);
+    max_src = std::max(max_src, table->n_cells[(size_t)c.source]);
+  }
+  if (n == 0) return CFEAR_OK;
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  HostStage st(ctx, kWsRegJobs);
+  CovSamplePass pass;
+  const size_t cand_bytes = (size_t)n * sizeof(cfear_candidate);
+  pass.plan(st, n, sp->samples_per_axis, 16 + (host_cands ? cand_bytes : 0));
+  const cfear_reg_result* d_regs;
+  double* d_cov;
+  int32_t* d_ok;
+  st.in(d_regs, regs, (size_t)n * sizeof(cfear_reg_result));
+  st.out(d_cov, cov36, (size_t)n * 36 * sizeof(double));
+  st.out(d_ok, success, (size_t)n * sizeof(int32_t));
+  CFEAR_CHECK(st.carve());
+  CFEAR_CHECK(pass.stage(st, sp));
+  int32_t* h_head = (int32_t*)pass.h_extra();
+  h_head[0] = kCovNone; h_head[1] = h_head[2] = h_head[3] = 0;
+  if (host_cands) memcpy(pass.h_extra() + 16, cands, cand_bytes);
+  CFEAR_CHECK(pass.upload(st));
+  int32_t* d_head = (int32_t*)pass.d_extra();
+  const cfear_candidate* d_cands = host_cands ? (const cfear_candidate*)(pass.d_extra() + 16) : cands;
+  CFEAR_CHECK(pass.centre(ctx, table, d_cands, d_regs, n, par, d_head));
+  if (!host_cands) {                                       // a device list is checked by the kernel that reads it
+    int32_t head[4];
+    st.fetch(head, d_head, sizeof(head));
+    CFEAR_CHECK(st.wait());
+    if (head[0] != kCovNone)
+      return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "candidate %d refers to a scan outside the table of %d", head[0], nt);
+    max_tar = head[1]; max_src = head[2];
+  }
+  CFEAR_CHECK(pass.sample_and_fit(ctx, table, d_cands, n, max_tar, max_src, par, d_regs, sp, d_cov, d_ok));
+  return st.finish();
+}
+
 extern "C" int cfear_covariance_by_sampling(cfear_ctx* ctx, const cfear_scan* const* scans, int32_t n_scans,
                                             const double* poses_xyt, const cfear_reg_params* par,
                                             const cfear_reg_result* reg, const cfear_cov_sampling_params* sp,

@@ -62,3 +62,40 @@ int cfear_candidates_match(cfear_ctx* ctx, const char* d_jobs, int32_t n, const 
 int cfear_candidates_enqueue(cfear_ctx* ctx, const cfear_scan_table* table, const cfear_candidate* cands, int32_t n,
                              const cfear_reg_params* par, cfear_candidate* h_stage, cfear_reg_result* d_res, int32_t* d_trailer,
                              int trailer_status);
+
+// ---- covariance by cost sampling without the host between the samples and the fit (covfit.hip, register.hip) --------------
+// The fit: regs [n_jobs], samples [n_jobs][m], pinv [10][m] (CovFit::prepare's, cfear_cov_fit_fill_pinv) -> cov36 [n_jobs][36],
+// success [n_jobs]; everything in device memory, enqueued on the context's stream.
+size_t cfear_cov_fit_pinv_bytes(int samples_per_axis);
+void cfear_cov_fit_fill_pinv(const cfear_cov_sampling_params* sp, double* dst);
+int cfear_cov_fit_launch(cfear_ctx* ctx, const cfear_reg_result* d_regs, const cfear_reg_result* d_samples, int n_jobs, int m,
+                         const double* d_pinv, double covariance_scaler, double* d_cov36, int32_t* d_success);
+int cfear_cov_check_sampling(cfear_ctx* ctx, const cfear_cov_sampling_params* sp);      // samples_per_axis in [1, 15]
+// The pass over candidate pairs of a scan table (cfear_covariance_by_sampling_candidates; verify.hip's
+// cfear_verify_sample_covariances).  plan() before the stage's carve(): the job records, the sample centres, the samples and
+// one block that goes up in one copy from the pinned staging -- the pseudo-inverse, then `extra` bytes of the caller's
+// (h_extra() after stage(), d_extra() their place on the device).  centre() enqueues the kernel that reads the candidates:
+// centre j = regs[j].pose where regs[j].status is CFEAR_OK, else the candidate's own source pose; the radius follows
+// regs[j].outer_iters.  It checks the table indices (a bad candidate writes nothing; the smallest bad index -> head[0]) and
+// leaves the largest target and source cell counts in head[1], head[2]; head: device int32[4], {INT_MAX, 0, 0, 0} before.
+// sample_and_fit() enqueues expand -> matcher (cost only, around the centres) -> cov_fit_kernel.  Nothing is read back.
+struct CovSamplePass {
+  int n = 0, m = 0, spa = 0;
+  size_t extra = 0;
+  char* d_jobs = nullptr;
+  cfear_reg_result* d_centre = nullptr;
+  cfear_reg_result* d_samples = nullptr;
+  char* d_block = nullptr;
+  char* h_block = nullptr;
+  void plan(HostStage& st, int n_jobs, int samples_per_axis, size_t extra_bytes);
+  int stage(HostStage& st, const cfear_cov_sampling_params* sp);
+  int upload(HostStage& st);
+  size_t pinv_bytes() const { return (cfear_cov_fit_pinv_bytes(spa) + 255) / 256 * 256; }
+  char* h_extra() const { return h_block + pinv_bytes(); }
+  char* d_extra() const { return d_block + pinv_bytes(); }
+  int centre(cfear_ctx* ctx, const cfear_scan_table* table, const cfear_candidate* d_cands, const cfear_reg_result* d_regs, int n_jobs,
+             const cfear_reg_params* par, int32_t* d_head) const;
+  int sample_and_fit(cfear_ctx* ctx, const cfear_scan_table* table, const cfear_candidate* d_cands, int n_jobs, int max_tar_cells,
+                     int max_src_cells, const cfear_reg_params* par, const cfear_reg_result* d_regs,
+                     const cfear_cov_sampling_params* sp, double* d_cov36, int32_t* d_success) const;
+};

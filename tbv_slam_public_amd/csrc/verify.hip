@@ -1019,3 +1019,201 @@ extern "C" int cfear_verify_sc_rows(cfear_ctx* ctx, const cfear_loop_graphs* gra
   rw.rows = rows; rw.n_out = n_out; rw.n_detect = n_detect; rw.nc = n_candidates;
   return verify_graph_route(ctx, graphs, nullptr, 0, rw, par, results, list_out, loops_out, n_list);
 }
+
+// ---- sampled covariances for candidates that were verified on the device ------------------------------------------------------
+// What verify_host_chain does under use_covariance_sampling (loopclosure.cpp:62-71, 99-208), as a pass of its own over the
+// records cfear_verify_graph_candidates / cfear_verify_sc_rows wrote, without the host seeing a candidate:
+//   verify_sample_scan_kernel   every candidate's rank among those with skip == 0 and reg_ok == 1
+//   verify_sample_fill_kernel   list + results -> cfear_candidate {to fixed at Tfrom * guess, from free} and the dense
+//                               registration records (gathered from the 480-byte stride), validation, the header
+//   ONE read-back of the 16-byte header; then CovSamplePass (register.hip): centre -> expand -> matcher (cost only) -> cov_fit_kernel
+//   verify_sample_write_kernel  R^-1 C R^-T by the registered yaw into `cov`, cov_sampled = 1 -- where the fit was accepted;
+//                               a refused fit leaves the record as it is: Register's constant, rotated, cov_sampled = 0
+namespace {
+
+struct SampleArgs {
+  const ScanView* views;
+  const double* poses;                  // [n_nodes][3]
+  const int32_t* node_off;              // [n_graphs + 1]
+  const cfear_loop_verify_candidate* list;
+  cfear_verify_result* results;
+  int32_t* active_rank;                 // [n]
+  int32_t* out_index;                   // [n] sampled candidate a -> its place j in the list
+  cfear_candidate* cands;               // [n] dense over the sampled candidates
+  cfear_reg_result* regs;               // [n]
+  int32_t* head;                        // {first unusable candidate, largest `to` cell count, largest `from` cell count, sampled candidates}
+  const double* cov36;                  // [n][36] the fits
+  const int32_t* success;               // [n]
+  int32_t n_graphs, n;
+};
+
+__host__ __device__ inline bool sample_takes_part(const cfear_loop_verify_candidate& c, const cfear_verify_result& r) {
+  return c.skip == 0 && r.reg_ok == 1;
+}
+__host__ __device__ inline bool sample_pose_usable(const cfear_verify_result& r) {
+  return fin1(r.reg.pose[0]) && fin1(r.reg.pose[1]) && fin1(r.reg.pose[2]);
+}
+
+__global__ __launch_bounds__(256) void verify_sample_scan_kernel(const SampleArgs a) {
+  const int total = block_excl_scan_256(
+      a.n,
+      [&](int j) {
+        const cfear_loop_verify_candidate c = a.list[j];
+        return !graph_cand_fault(c, a.node_off, a.n_graphs) && sample_takes_part(c, a.results[j]) ? 1 : 0;
+      },
+      [&](int j, int rank) { a.active_rank[j] = rank; });
+  if (threadIdx.x == 0) a.head[3] = total;
+}
+
+__global__ __launch_bounds__(256) void verify_sample_fill_kernel(const SampleArgs a) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= a.n) return;
+  const cfear_loop_verify_candidate c = a.list[j];
+  if (graph_cand_fault(c, a.node_off, a.n_graphs)) { atomicMin(&a.head[0], j); return; }
+  const cfear_verify_result& r = a.results[j];
+  if (!sample_takes_part(c, r)) return;
+  if (!sample_pose_usable(r)) atomicMin(&a.head[0], j);   // (keeps its rank: the record below is never used after a refusal)
+  const int node0 = a.node_off[c.graph];
+  const int kf = node0 + c.from, kt = node0 + c.to;
+  const int at = a.active_rank[j];
+  a.out_index[at] = j;
+  const cfear_reg_result reg = r.reg;
+  cfear_candidate cd;
+  cd.target = kt; cd.source = kf;
+  double from_pose[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) { from_pose[k] = a.poses[3 * (size_t)kf + k]; cd.source_xyt[k] = reg.pose[k]; }
+  xyt_compose(from_pose, c.guess_xyt, cd.target_xyt);      // Tto = Tfrom * t_be, as verify_expand_kernel
+  a.cands[at] = cd;
+  a.regs[at] = reg;
+  atomicMax(&a.head[1], *a.views[kt].n_cells);
+  atomicMax(&a.head[2], *a.views[kf].n_cells);
+}
+
+__global__ __launch_bounds__(256) void verify_sample_write_kernel(const SampleArgs a, int n_active) {
+  const int at = blockIdx.x * 256 + threadIdx.x;
+  if (at >= n_active || !a.success[at]) return;
+  cfear_verify_result& r = a.results[a.out_index[at]];
+  const double* F = a.cov36 + (size_t)at * 36;
+  double inv[3];
+  xyt_inverse(a.regs[at].pose, inv);                       // Trevised^-1
+  // reg_cov.block<3,3>(0,0) = R^-1 * block * R^-T: only the x-y part of the block is touched by a yaw rotation
+  double sn, cs;
+  sincos(inv[2], &sn, &cs);
+  const double R[9] = {cs, -sn, 0, sn, cs, 0, 0, 0, 1};
+  double B[9], T[9], O[9];
+  for (int x = 0; x < 3; x++) for (int y = 0; y < 3; y++) B[x * 3 + y] = F[x * 6 + y];
+  for (int x = 0; x < 3; x++) for (int y = 0; y < 3; y++) {
+    double t = 0.0;
+    for (int k = 0; k < 3; k++) t += R[x * 3 + k] * B[k * 3 + y];
+    T[x * 3 + y] = t;
+  }
+  for (int x = 0; x < 3; x++) for (int y = 0; y < 3; y++) {
+    double t = 0.0;
+    for (int k = 0; k < 3; k++) t += T[x * 3 + k] * R[y * 3 + k];
+    O[x * 3 + y] = t;
+  }
+  for (int x = 0; x < 6; x++) for (int y = 0; y < 6; y++) r.cov[x * 6 + y] = x < 3 && y < 3 ? O[x * 3 + y] : F[x * 6 + y];
+  r.cov_sampled = 1;
+}
+
+// Everything that can be refused without a device, a null context last.
+int sample_route_check(cfear_ctx* ctx, const cfear_loop_graphs* g, const cfear_loop_verify_candidate* list, int32_t n_list,
+                       const cfear_loop_verify_params* par, const cfear_verify_result* results) {
+  const auto refuse = [&](const char* what) { return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "%s", what); };
+  if (!g || !par || n_list < 0) return refuse("null or negative argument");
+  if (g->n_graphs < 0 || !g->node_off) return refuse("null or negative argument (node_off holds n_graphs + 1 entries)");
+  if (cfear_is_device_ptr(g->node_off) || cfear_is_device_ptr(g->poses_xyt)) return refuse("node_off and poses_xyt must be host memory");
+  CFEAR_CHECK(cfear_cov_check_sampling(ctx, &par->verify.sampling));
+  const int G = g->n_graphs;
+  if (g->node_off[0] != 0) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "graph 0: node_off must start at 0");
+  for (int gi = 0; gi < G; gi++)
+    if (g->node_off[gi + 1] < g->node_off[gi]) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "graph %d: node_off descends", gi);
+  const int N = g->node_off[G];
+  if (N > 0 && !g->poses_xyt) return refuse("null poses_xyt with nodes");
+  for (int gi = 0; gi < G; gi++)
+    for (int k = g->node_off[gi]; k < g->node_off[gi + 1]; k++) {
+      const double* p = g->poses_xyt + 3 * (size_t)k;
+      if (!fin1(p[0]) || !fin1(p[1]) || !fin1(p[2]))
+        return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "graph %d, node %d: a pose that is not finite", gi, k - g->node_off[gi]);
+    }
+  if (n_list > 0 && (!list || !results)) return refuse("null list or results with a positive count");
+  if (memory_kind({list, results}) < 0) return refuse("list and results must be both host or both device memory");
+  if (n_list > 0 && !cfear_is_device_ptr(list))
+    for (int j = 0; j < n_list; j++) {
+      const int f = graph_cand_fault(list[j], g->node_off, G);
+      if (f) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "candidate %d: %s", j, kGraphCandFault[f]);
+      if (sample_takes_part(list[j], results[j]) && !sample_pose_usable(results[j]))
+        return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "candidate %d: its registered pose is not finite", j);
+    }
+  if (N > 0 && !g->table) return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "null scan table: it must hold one entry per node (%d)", N);
+  if (g->table && (int)g->table->n_cells.size() != N)
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "the scan table holds %d scans, the graphs %d nodes", (int)g->table->n_cells.size(), N);
+  if (!ctx) return refuse("null context");
+  if (g->table && g->table->ctx != ctx) return refuse("the scan table belongs to another context");
+  return CFEAR_OK;
+}
+
+}  // namespace
+
+extern "C" int cfear_verify_sample_covariances(cfear_ctx* ctx, const cfear_loop_graphs* g, const cfear_loop_verify_candidate* list,
+                                               int32_t n_list, const cfear_loop_verify_params* par, cfear_verify_result* results) {
+  CFEAR_CHECK(sample_route_check(ctx, g, list, n_list, par, results));
+  if (g->n_graphs == 0 || n_list == 0) return CFEAR_OK;
+  const size_t n = (size_t)n_list, N = (size_t)g->node_off[g->n_graphs], G = (size_t)g->n_graphs;
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  HostStage st(ctx, kWsVerify);
+  SampleArgs a{};
+  a.views = g->table ? g->table->d_views.get() : nullptr;  // (no table: no nodes, and every candidate is refused before it is looked up)
+  a.n_graphs = g->n_graphs; a.n = n_list;
+  st.in(a.poses, g->poses_xyt, N * 24);
+  st.in(a.node_off, g->node_off, (G + 1) * 4);
+  st.in(a.list, list, n * sizeof(cfear_loop_verify_candidate));
+  const bool host_out = st.in(a.results, results, n * sizeof(cfear_verify_result));
+  st.piece(a.active_rank, n * 4);
+  st.piece(a.out_index, n * 4);
+  st.piece(a.cands, n * sizeof(cfear_candidate));
+  st.piece(a.regs, n * sizeof(cfear_reg_result));
+  double* d_cov;
+  int32_t* d_ok;
+  st.piece(d_cov, n * 36 * sizeof(double));
+  st.piece(d_ok, n * 4);
+  CovSamplePass pass;
+  pass.plan(st, n_list, par->verify.sampling.samples_per_axis, 32);
+  CFEAR_CHECK(st.carve());
+  a.cov36 = d_cov; a.success = d_ok;
+  CFEAR_CHECK(pass.stage(st, &par->verify.sampling));
+  int32_t* h_head = (int32_t*)pass.h_extra();
+  for (int k = 0; k < 8; k++) h_head[k] = 0;
+  h_head[0] = h_head[4] = kNone;                           // [0..4): this route's header; [4..8): CovSamplePass::centre's
+  CFEAR_CHECK(pass.upload(st));
+  a.head = (int32_t*)pass.d_extra();
+  const dim3 block(256);
+  {
+    ProfScope ps(ctx, "cov_glue");
+    hipLaunchKernelGGL(verify_sample_scan_kernel, dim3(1), block, 0, ctx->stream, a);
+    hipLaunchKernelGGL(verify_sample_fill_kernel, dim3((unsigned)((n + 255) / 256)), block, 0, ctx->stream, a);
+  }
+  CFEAR_HIP_CHECK(ctx, hipGetLastError());
+  int32_t head[4];
+  st.fetch(head, a.head, sizeof(head));
+  CFEAR_CHECK(st.wait());
+  // ---- the device's refusal: nothing has been written to the caller's records yet -----------------------------------------------
+  if (head[0] != kNone)
+    return cfear_set_error(ctx, CFEAR_ERR_INVALID_ARGUMENT, "candidate %d: its graph, from, to, guess_nr, guess, sc_sim or registered pose are not usable", head[0]);
+  const int n_active = head[3];
+  if (n_active == 0) return st.finish();
+  // RegisterLoopCandidate's problem and parameters (loopclosure.cpp:56-57), as verify_host_chain hands them to the sampling
+  cfear_reg_params rp;
+  cfear_reg_params_default(&rp);
+  rp.cost = CFEAR_P2L; rp.max_itr_association = 4; rp.max_itr_solver = 10;
+  CFEAR_CHECK(pass.centre(ctx, g->table, a.cands, a.regs, n_active, &rp, a.head + 4));
+  CFEAR_CHECK(pass.sample_and_fit(ctx, g->table, a.cands, n_active, head[1], head[2], &rp, a.regs, &par->verify.sampling, d_cov, d_ok));
+  {
+    ProfScope ps(ctx, "cov_glue");
+    hipLaunchKernelGGL(verify_sample_write_kernel, dim3((unsigned)((n_active + 255) / 256)), block, 0, ctx->stream, a, n_active);
+  }
+  CFEAR_HIP_CHECK(ctx, hipGetLastError());
+  if (host_out) st.back(results, a.results, n * sizeof(cfear_verify_result));
+  return st.finish();
+}
